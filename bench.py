@@ -10,9 +10,13 @@ the finished palette-index columns to rank 0 (north_star), done by libemspec
 itself over RCCL (emspec_gather_columns: packed wire image, grouped send/recv)
 per stream-chunk on a side stream, so it overlaps the next chunk's compute.
 
-Prints ONE JSON line on rank 0 (contract: see the task statement / DESIGN.md §5, §6).
-At N = 1 the line also carries `configs` (the other named BASELINE configs measured beside the
-headline), `roofline_compute` (the bounds the kernel really sits under) and `cpu_baseline`.
+Prints ONE JSON line on rank 0 (contract: see DESIGN.md §5, §6).  A plain run sets up, warms up,
+times --steps steps and prints the line with the headline, its HBM roofline and `roofline_compute`
+(the bounds the kernel really sits under, from the committed profiles).  With --full it also carries,
+at N = 1, `configs` (the other named BASELINE configs measured beside the headline), `exact_mode`,
+`roofline_parity_dump` and `cpu_baseline`; with a gather, the packed / expanding counterpart of the
+timed form and the root's standalone expand.  --dump-outputs DIR writes the last timed step's
+outputs (a seeded sample of whole columns) as .npy files.
 """
 import argparse
 import glob
@@ -486,6 +490,28 @@ def time_launches(fn, stream, reps):
     return e0.elapsed_time(e1) / reps
 
 
+DUMP_BUDGET_BYTES = 48 << 20     # --dump-outputs: all files together stay under 64 MB
+DUMP_SEED = 20240611
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: write the timed path's outputs (device tensors [streams, columns, cells]) as DIR/<name>.npy.  The
+    same whole columns are taken from each output: a sample drawn with a fixed seed from the shape alone, so the same
+    arguments dump the same positions on every build; DIR/sample_positions.npy holds them as (stream, column) pairs.
+    Floating outputs are written as float32, integer ones as float32 (one-byte cells) or float64 (wider cells: exact)."""
+    os.makedirs(path, exist_ok=True)
+    S0, C0 = (int(v) for v in next(iter(outputs.values())).shape[:2])
+    kinds = {name: (np.float32 if (t.dtype.is_floating_point or t.element_size() == 1) else np.float64) for name, t in outputs.items()}
+    col_bytes = sum(int(t.shape[2]) * np.dtype(kinds[name]).itemsize for name, t in outputs.items())
+    k = max(1, min(S0 * C0, DUMP_BUDGET_BYTES // col_bytes))
+    pos = np.sort(np.random.default_rng(DUMP_SEED).choice(S0 * C0, size=k, replace=False))
+    sel = torch.from_numpy(pos).to(next(iter(outputs.values())).device)
+    for name, t in outputs.items():
+        assert tuple(t.shape[:2]) == (S0, C0), (name, tuple(t.shape))
+        np.save(os.path.join(path, f"{name}.npy"), t.reshape(S0 * C0, -1)[sel].cpu().numpy().astype(kinds[name]))
+    np.save(os.path.join(path, "sample_positions.npy"), np.stack([pos // C0, pos % C0], axis=1).astype(np.float64))
+
+
 def roofline(cols, bytes_per_col, ms, note=None):
     ach = cols * bytes_per_col / (ms * 1e-3) / 1e9
     d = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
@@ -507,17 +533,17 @@ def main():
     ap.add_argument("--steps", type=int, default=50)      # (0.45 s of timed kernels at N = 1: long enough for a utilisation sampler to see)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="batch64", choices=["batch64", "single", "n16384", "n8192", "n1024", "paritydump"],
-                    help="paritydump: N=1 only, a step = the per-bin dump of 16 streams x 2^20 samples (the second roofline point of the default line, here on its own so that tools/profile_workload.sh can profile it)")
+                    help="paritydump: N=1 only, a step = the per-bin dump of 16 streams x 2^20 samples (the second roofline point of the --full line, here on its own so that tools/profile_workload.sh can profile it)")
     ap.add_argument("--streams", type=int, default=0, help="override streams per GPU")
     ap.add_argument("--log2-samples", type=int, default=22)
     ap.add_argument("--chunks", type=int, default=2, help="stream-chunks per step (gather overlap, N>1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="N=1: skip the side measurements of the other named configs")
+    ap.add_argument("--no-configs", action="store_true", help="with --full at N=1: skip the side measurements of the other named configs")
     ap.add_argument("--force-chunks", type=int, default=0, help="N=1: launch per stream-chunk as the N>1 path does (no gather)")
     ap.add_argument("--reassign", type=int, default=1)
     ap.add_argument("--mode", default="fast", choices=["fast", "exact"],
                     help="exact = EMSPEC_MODE_EXACT (binary64 + 64-bit fixed-point histogram, DESIGN.md 3.7); the default line is "
-                         "the fast mode and reports the exact mode's rate in `configs`")
+                         "the fast mode; --full reports the exact mode's rate in `configs`")
     ap.add_argument("--gather", default="lib", choices=["lib", "torch", "loopback", "dist-loopback"],
                     help="lib = libemspec's RCCL gather (default); torch = torch.distributed.gather of raw columns; "
                          "loopback = N=1 rehearsal: the rank's own columns go through pack + RCCL self send/recv + expand; "
@@ -542,7 +568,16 @@ def main():
                          "touches a GPU (the CPU test of the self-spawning launcher); --hang-rank R makes rank R exit 3")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo = rehearsal of the N>1 control flow on fewer GPUs than ranks (torch gather via host tensors)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements beside the headline: the other named configs, the EXACT mode, host-buffer, "
+                         "live and Node entries, the parity-dump roofline, the CPU baselines and, with a gather, its packed / "
+                         "expanding counterpart and the root's standalone expand (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy (float32 / "
+                         "float64; a fixed, seeded sample of whole columns, at most 64 MB in all; rank 0's shard at N > 1)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     args.gather_packed = not args.gather_expand
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -626,6 +661,8 @@ def main():
             dump()
         torch.cuda.synchronize(dev)
         ms = time_launches(dump, cur, args.steps)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"power": pw_, "column": cl_, "row": rw_})
         bpc = 4 * hop + 12 * K
         rf = roofline(Sd * Cd, bpc, ms, "algorithmic bytes = 4*hop in + 12*(N/2+1) per-bin dump out; 16 streams x 2^20 samples")
         pp, pf = profile_for("paritydump", lib_sha)
@@ -844,6 +881,9 @@ def main():
     step_deadline = max(args.step_deadline_min, args.step_deadline_factor * warm_s)
     elapsed = job.run(args.steps, timed=True, deadline_s=step_deadline)
     eng.device_status()           # raises if a kernel flagged a protocol error during the timed run (its columns would be invalid)
+    if args.dump_outputs and rank == 0:
+        # before anything else reuses the buffers: what a caller of the batch entry receives from the last timed step
+        dump_outputs(args.dump_outputs, {"db": job.db, "index": job.idx_bufs[(job.nstep - 1) % nbuf]})
     wire_bytes = job.wire_bytes
     if dist_on:
         wb = torch.tensor(wire_bytes, dtype=torch.float64, device=gdev)
@@ -851,12 +891,14 @@ def main():
         wire_bytes = [float(wb[0].item()), float(wb[1].item())]
     # the same job with the images kept packed on the root (EMSPEC_GATHER_PACKED: nothing is lost, the root only receives and
     # expands on demand): three more steps after the timed run, reported beside the headline, never as the headline
+    # (--full only, like every measurement beside the headline)
     packed_cps = expand_cps = None
-    if gathering and gather_mode == "lib" and not args.gather_packed:     # (also in the one-GPU loopback rehearsals)
+    side_gather = args.full and gathering and gather_mode == "lib"
+    if side_gather and not args.gather_packed:     # (also in the one-GPU loopback rehearsals)
         job.switch_to_packed()
         job.run(1, deadline_s=step_deadline)
         packed_cps = total_streams * C * 3 / job.run(3, deadline_s=step_deadline)
-    elif gathering and gather_mode == "lib":
+    elif side_gather:
         # the default line times the packed form; the expanding form (the root turns every image back into plain arrays, as at
         # N = 1) runs three steps after it on the same split and is reported beside it
         args_packed_was = job.packed
@@ -882,7 +924,7 @@ def main():
     # what the root's expand costs by itself: one other rank's chunk worth of columns, packed and expanded standalone,
     # times the (world - 1) images per gather and the chunks per step
     expand_ms = None
-    if rank == 0 and gathering and gather_mode == "lib":
+    if rank == 0 and side_gather:
         a, b = job.bounds[0]
         src = job.idx_bufs[0][a:b]
         wire = torch.empty((emspec.wire_bound((b - a) * C, R),), dtype=torch.uint8, device=dev)
@@ -997,7 +1039,7 @@ def main():
         else:
             line["roofline_valu"] = None
 
-        if world == 1 and args.workload == "batch64" and not args.no_configs:
+        if world == 1 and args.workload == "batch64" and args.full and not args.no_configs:
             # ---- the other named BASELINE configs, measured beside the headline on the same engine and input
             cfgs = {}
 
@@ -1125,7 +1167,7 @@ def main():
                 pd["traffic_source"] = f"{pp['file']}{'' if pf else ' (STALE, withheld)'}"
             line["roofline_parity_dump"] = pd
             del pw_, cl_, rw_
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(n, hop)
             line["cpu_baseline_js"] = js_baseline(n, hop)
         else:

@@ -120,6 +120,37 @@ def test_roofline_helper():
     assert abs(r["achieved"] - 1000 * 6144 / 1e-3 / 1e9) < 1e-9 and r["frac"] == r["achieved"] / 8000.0
 
 
+def test_dump_outputs_writes_a_seeded_sample_of_whole_columns(tmp_path):
+    """bench.dump_outputs (--dump-outputs): the same positions for the same shape, whole columns taken from every output at those
+    positions, float32 / float64 files only, and the byte budget kept even when the outputs are far larger."""
+    import numpy as np
+    import torch
+    S, C, R = 3, 500, 64
+    db = torch.arange(S * C * R, dtype=torch.float32).reshape(S, C, R)
+    idx = (torch.arange(S * C * R) % 251).to(torch.uint8).reshape(S, C, R)
+    col = torch.arange(S * C * R, dtype=torch.int32).reshape(S, C, R)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"db": db, "index": idx, "column": col})
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["column.npy", "db.npy", "index.npy", "sample_positions.npy"]
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    pos = np.load(tmp_path / "a" / "sample_positions.npy").astype(np.int64)
+    assert len(pos) == S * C and np.array_equal(pos[:, 0] * C + pos[:, 1], np.arange(S * C))     # small: every column, in order
+    assert np.array_equal(np.load(tmp_path / "a" / "db.npy"), db.reshape(S * C, R).numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "index.npy"), idx.reshape(S * C, R).numpy().astype(np.float32))
+    assert np.load(tmp_path / "a" / "column.npy").dtype == np.float64
+    # larger than the budget: a sample of whole columns, at most 64 MB in all
+    big = torch.zeros((4, 5000, 1024), dtype=torch.float32)
+    big.view(-1, 1024)[:, 0] = torch.arange(4 * 5000, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / "c"), {"db": big, "index": big.to(torch.uint8)})
+    total = sum(p.stat().st_size for p in (tmp_path / "c").iterdir())
+    pos = np.load(tmp_path / "c" / "sample_positions.npy").astype(np.int64)
+    assert total <= 64 * 10 ** 6 and 1000 < len(pos) < 4 * 5000 and np.all(np.diff(pos[:, 0] * 5000 + pos[:, 1]) > 0)
+    assert np.array_equal(np.load(tmp_path / "c" / "db.npy")[:, 0], pos[:, 0] * 5000 + pos[:, 1])
+
+
 def test_watchdog_ends_the_process():
     """bench.Watchdog: a deadline that expires ends the process with exit code 1 (os._exit from the watchdog thread - no re-exec,
     nothing that needs the main thread, which may be blocked inside a collective); a disarmed one does not."""

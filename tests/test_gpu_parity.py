@@ -840,7 +840,7 @@ def test_bench_one_rank_with_process_group_rehearsal():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_PORT="29539")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gather", "dist-loopback", "--no-cpu-baseline", "--no-configs",
-           "--steps", "3", "--warmup", "1", "--streams", "8", "--log2-samples", "19"]
+           "--steps", "3", "--warmup", "1", "--streams", "8", "--log2-samples", "19", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

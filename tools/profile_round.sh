@@ -12,7 +12,7 @@ tag=${1:-rXX}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$R/gpurun_out/$tag
 mkdir -p "$out"
-python3 "$R/bench.py" > "$out/bench_n1.json" 2> "$out/bench_n1.err" || exit 1
+python3 "$R/bench.py" --full > "$out/bench_n1.json" 2> "$out/bench_n1.err" || exit 1
 python3 "$R/tools/phase_cycles.py" 8 v > "$out/phase_cycles.txt" 2>&1
 python3 "$R/tools/host_rates.py" > "$out/host_rates.txt" 2>&1
 cd /tmp && export TMPDIR=/tmp

@@ -70,10 +70,14 @@ done
 # the bench lines, on the SAME box as the profiles they quote (tests/test_bench_helpers.py holds every profile's median
 # duration to <= 1.02 x the line's kernel time: between boxes the clocks differ by more than that)
 cd "$R"
-python bench.py > gpurun_out/${tag}_bench_n1.json 2> gpurun_out/${tag}_bench_n1.err
-python bench.py --mode exact --no-configs > gpurun_out/${tag}_bench_exact.json 2>> gpurun_out/${tag}_bench_n1.err
-python bench.py --gather loopback --no-cpu-baseline --no-configs > gpurun_out/${tag}_bench_loopback.json 2>> gpurun_out/${tag}_bench_n1.err
-python bench.py --gather loopback --gather-expand --no-cpu-baseline --no-configs > gpurun_out/${tag}_bench_loopback_expand.json 2>> gpurun_out/${tag}_bench_n1.err
-echo "bench lines written"
+# (--full: the lines carry the side measurements the committed summaries quote; they are written to $BENCH_LINES_DIR, by
+# default bench_lines/ - point it at the folder that comes back from the box to keep them beside the profiles)
+lines=${BENCH_LINES_DIR:-$R/bench_lines}
+mkdir -p "$lines"
+python bench.py --full > "$lines/${tag}_bench_n1.json" 2> "$lines/${tag}_bench_n1.err"
+python bench.py --full --mode exact --no-configs > "$lines/${tag}_bench_exact.json" 2>> "$lines/${tag}_bench_n1.err"
+python bench.py --full --gather loopback --no-cpu-baseline --no-configs > "$lines/${tag}_bench_loopback.json" 2>> "$lines/${tag}_bench_n1.err"
+python bench.py --full --gather loopback --gather-expand --no-cpu-baseline --no-configs > "$lines/${tag}_bench_loopback_expand.json" 2>> "$lines/${tag}_bench_n1.err"
+echo "bench lines written to $lines"
 fi
 echo "round check ($part) written under gpurun_out/"
