@@ -159,6 +159,7 @@ int get_plan(emspec_engine* e, int n, Plan** out) {
     if (it != e->plans.end()) { *out = &it->second; return EMSPEC_OK; }
     Plan p;
     p.n = n;
+    p.rows = e->cfg.rows;
     p.h_tw.resize(n);
     const double pi = 3.14159265358979323846;
     for (int q = 0; q < n / 2; ++q) {
@@ -226,11 +227,42 @@ int get_plan(emspec_engine* e, int n, Plan** out) {
     return EMSPEC_OK;
 }
 
+// A band of the table for the multi-resolution batch: rows [row0, row0 + rows) as a SLICE of the full plan's edge tables (float32
+// and binary64) - recomputing a band's table from its own ends would differ in the last bit and move bins across edges.  The
+// twiddles are the full plan's (both plans live until drop_plans, which drops them together).
+int get_band_plan(emspec_engine* e, int n, int row0, int rows, Plan** out) {
+    const auto key = std::make_tuple(n, row0, rows);
+    auto it = e->band_plans.find(key);
+    if (it != e->band_plans.end()) { *out = &it->second; return EMSPEC_OK; }
+    Plan* full;
+    int rc;
+    if ((rc = get_plan(e, n, &full))) return rc;
+    if (row0 < 0 || rows < 1 || row0 + rows > full->rows) return fail(e, EMSPEC_ERR_INVALID_ARG, "band outside the row table");
+    Plan p;
+    p.n = n;
+    p.row0 = row0;
+    p.rows = rows;
+    p.d_tw = full->d_tw;
+    p.d_tw64 = full->d_tw64;
+    p.h_ebin.assign(full->h_ebin.begin() + row0, full->h_ebin.begin() + row0 + rows + 1);
+    HIPCHK(e, hipMalloc(&p.d_ebin, sizeof(float) * (rows + 1)));
+    HIPCHK(e, hipMemcpy(p.d_ebin, p.h_ebin.data(), sizeof(float) * (rows + 1), hipMemcpyHostToDevice));
+    if (e->exact()) {
+        HIPCHK(e, hipMalloc(&p.d_ebin64, sizeof(double) * (rows + 1)));
+        HIPCHK(e, hipMemcpy(p.d_ebin64, full->d_ebin64 + row0, sizeof(double) * (rows + 1), hipMemcpyDeviceToDevice));
+        HIPCHK(e, hipMemcpy(&p.h_e0, full->d_ebin64 + row0, sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(e, hipMemcpy(&p.h_eR, full->d_ebin64 + row0 + rows, sizeof(double), hipMemcpyDeviceToHost));
+    }
+    auto ins = e->band_plans.emplace(key, std::move(p));
+    *out = &ins.first->second;
+    return EMSPEC_OK;
+}
+
 PlanDev plan_dev(const emspec_engine* e, const Plan& p, int hop, int reassign) {
     PlanDev d;
     d.tw = p.d_tw;
     d.ebin = p.d_ebin;
-    d.rows = e->cfg.rows;
+    d.rows = p.rows;
     d.log_rows = e->custom_edges_hz.empty() ? 1 : 0;
     d.D = latency(p.n, hop, reassign);
     d.reassign = reassign ? 1 : 0;
@@ -252,7 +284,7 @@ ExactPlanDev exact_plan_dev(const emspec_engine* e, const Plan& p, int hop, int 
     ExactPlanDev d;
     d.tw = p.d_tw64;
     d.ebin = p.d_ebin64;
-    d.rows = e->cfg.rows;
+    d.rows = p.rows;
     d.log_rows = e->custom_edges_hz.empty() ? 1 : 0;
     d.D = latency(p.n, hop, reassign);
     d.reassign = reassign ? 1 : 0;
@@ -373,7 +405,7 @@ void emspec_destroy(emspec_engine* e) {
     (void)hipFree(e->d_xlow);
     if (e->xlow_event) (void)hipEventDestroy(e->xlow_event);
     (void)hipFree(e->d_lut); (void)hipFree(e->d_hist); (void)hipFree(e->d_stage);
-    (void)hipFree(e->d_raw); (void)hipFree(e->d_post); (void)hipFree(e->d_peak);
+    (void)hipFree(e->d_raw); (void)hipFree(e->d_post); (void)hipFree(e->d_peak); (void)hipFree(e->d_mres);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     if (e->stream_in) (void)hipStreamDestroy(e->stream_in);
     if (e->stream_out) (void)hipStreamDestroy(e->stream_out);
@@ -406,15 +438,16 @@ const char* emspec_device_arch(const emspec_engine* e) { return e ? e->arch.c_st
 // when it does not serve this engine's shape or axis.  The axis is served when at most 6 % of a frame's bins lie below row
 // rl (on the default log axis at hop 256: rl = 448 of 1024 rows, 38 of 2,049 bins); each of those costs a device-scope
 // atomic, so a linear axis (44 % of the bins there) stays on round 4's kernel, which parks instead.
-static int exact_lr_rows(const emspec_engine* e, int n, const ExactPlanDev& pd) {
+// (row0: the plan's first row in the engine's table - a band plan of the multi-resolution batch; the Hz test is on its row rl)
+static int exact_lr_rows(const emspec_engine* e, int n, const ExactPlanDev& pd, int row0 = 0) {
 #ifdef EMSPEC_DIAG
     if (const char* ev = getenv("EMSPEC_EXACT_PARKED")) { if (ev[0] == '1') return -1; }   // A/B aid: round 4's kernel
 #endif
     const int rl = exact_fused_lr_low_rows(n, pd);
     if (rl <= 0) return rl;
     const double hz = e->custom_edges_hz.empty()
-                          ? (double)e->cfg.fmin_hz * spec_pow((double)e->cfg.fmax_hz / (double)e->cfg.fmin_hz, (double)rl / (double)e->cfg.rows)
-                          : (double)e->custom_edges_hz[rl];
+                          ? (double)e->cfg.fmin_hz * spec_pow((double)e->cfg.fmax_hz / (double)e->cfg.fmin_hz, (double)(row0 + rl) / (double)e->cfg.rows)
+                          : (double)e->custom_edges_hz[row0 + rl];
     const double share = hz / ((double)e->cfg.sample_rate * 0.5);
     return share <= 0.06 ? rl : -1;
 }
@@ -431,6 +464,8 @@ int emspec_uses_fused(const emspec_engine* e, int32_t n, int32_t hop, int32_t re
 }
 
 static void drop_plans(emspec_engine* e) {
+    for (auto& kv : e->band_plans) { (void)hipFree(kv.second.d_ebin); (void)hipFree(kv.second.d_ebin64); }   // (twiddles: the full plans')
+    e->band_plans.clear();
     for (auto& kv : e->plans) {
         (void)hipFree(kv.second.d_tw); (void)hipFree(kv.second.d_ebin);
         (void)hipFree(kv.second.d_tw64); (void)hipFree(kv.second.d_ebin64);
@@ -540,10 +575,11 @@ int emspec_get_tables(emspec_engine* e, int32_t n, float* edges, float* tw) {
 // at least 256 MiB, at most `cap` - a chunk only has to cover enough streams to fill the CUs, so a few GiB cost nothing
 // measurable, and a fixed 12 GiB (round 3) pinned that much HBM per EXACT engine for its lifetime.  When the allocation
 // fails all the same, the chunk is halved and tried again; one stream that does not fit is an out-of-memory error.
-static int grow_record_workspace(emspec_engine* e, size_t per_stream, size_t extra, size_t cap, int S, int* chunk_out) {
+// (grow_chunked: the same rule for any engine workspace *ptr; the multi-resolution batch sizes its band workspace by it)
+int emspec::grow_chunked(emspec_engine* e, void** ptr, size_t* have, size_t per_stream, size_t extra, size_t cap, int S, int* chunk_out) {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = cap * 4; }
-    size_t budget = (free_b + e->hist_bytes) / 4;
+    size_t budget = (free_b + *have) / 4;
     budget = budget < ((size_t)256 << 20) ? ((size_t)256 << 20) : (budget > cap ? cap : budget);
 #ifdef EMSPEC_DIAG
     if (const char* ev = getenv("EMSPEC_RECORD_BUDGET_MB")) budget = (size_t)atol(ev) << 20;   // test hook: force several stream-chunks
@@ -551,12 +587,15 @@ static int grow_record_workspace(emspec_engine* e, size_t per_stream, size_t ext
     int chunk = (int)(budget / per_stream);
     chunk = chunk < 1 ? 1 : (chunk > S ? S : chunk);
     for (;;) {
-        const int rc = grow(e, (void**)&e->d_hist, &e->hist_bytes, per_stream * (size_t)chunk + extra);
+        const int rc = grow(e, ptr, have, per_stream * (size_t)chunk + extra);
         if (rc == EMSPEC_OK) { *chunk_out = chunk; return EMSPEC_OK; }
         (void)hipGetLastError();
         if (rc != EMSPEC_ERR_OUT_OF_MEMORY || chunk == 1) return rc;
         chunk = (chunk + 1) / 2;
     }
+}
+static int grow_record_workspace(emspec_engine* e, size_t per_stream, size_t extra, size_t cap, int S, int* chunk_out) {
+    return grow_chunked(e, (void**)&e->d_hist, &e->hist_bytes, per_stream, extra, cap, S, chunk_out);
 }
 
 // columns of S device-resident streams -> dB / RGBA / index, no display post-process
@@ -564,7 +603,7 @@ static int run_columns(emspec_engine* e, const PlanDev& pd, const DbMap& m, cons
                        int32_t n, int32_t hop, int32_t reassign, int64_t C, float* db, uint8_t* rgba, uint8_t* index,
                        hipStream_t st) {
     int rc;
-    if (fused_supported(n, hop, e->cfg.rows, reassign)) {
+    if (fused_supported(n, hop, pd.rows, reassign)) {
         HIPCHK(e, launch_fused(n, pd, m, e->d_lut, pcm, L, S, C, db, rgba, index, st));
         return EMSPEC_OK;
     }
@@ -573,7 +612,7 @@ static int run_columns(emspec_engine* e, const PlanDev& pd, const DbMap& m, cons
     const size_t rec_per_stream = (size_t)C * (n / 2 + 2) * sizeof(uint2);   // frame stride K+1 (even)
     int chunk = 1;
     if ((rc = grow_record_workspace(e, rec_per_stream, 0, (size_t)4 << 30, S, &chunk))) return rc;
-    const size_t col_cells = (size_t)C * e->cfg.rows;
+    const size_t col_cells = (size_t)C * pd.rows;
     for (int s0 = 0; s0 < S; s0 += chunk) {
         const int sc = (S - s0 < chunk) ? S - s0 : chunk;
         FrameSinks sk;
@@ -609,7 +648,7 @@ static int run_columns_exact(emspec_engine* e, const Plan& p, const float* pcm, 
     int rc;
     const ExactPlanDev pd = exact_plan_dev(e, p, hop, reassign);
     const ExactDbMap m = exact_db_map(e, n, pd);
-    const int rl = exact_lr_rows(e, n, pd);
+    const int rl = exact_lr_rows(e, n, pd, p.row0);
     if (rl >= 0) {   // one kernel, no records, no parking (exact_fused_lr.hip.inc)
         if ((rc = exact_lr_prepare(e, n, pd, rl, S, C, st))) return rc;
         HIPCHK(e, launch_exact_fused_lr(n, pd, m, e->d_lut, pcm, L, S, C, rl, e->d_xlow, e->xlow_bytes, db, rgba, index, st));
@@ -626,7 +665,7 @@ static int run_columns_exact(emspec_engine* e, const Plan& p, const float* pcm, 
     // (8 GiB here, 4 GiB for the float32 records: the walking scatter reads a 2D-frame halo per segment, and a stream-chunk's
     // segments get longer with the streams it holds - five streams of configs[4] per chunk: 23 % halo, ten: 12 %; 67.5 -> 66.1 ms per step, and 16 GiB measured 67.0)
     if ((rc = grow_record_workspace(e, q_per_stream + key_per_stream, 256, (size_t)8 << 30, S, &chunk))) return rc;
-    const size_t col_cells = (size_t)C * e->cfg.rows;
+    const size_t col_cells = (size_t)C * pd.rows;
     // the scatter's low-row scratch (exact.hip.inc: a ring too large for LDS is walked with its sparse low rows in global
     // memory); cleared once per batch - the kernel leaves it zero, this only guards against a launch that was cut short
     const float* ebin_host = p.h_ebin.data();
@@ -657,6 +696,14 @@ static int run_columns_exact(emspec_engine* e, const Plan& p, const float* pcm, 
     if (low_need) HIPCHK(e, hipEventRecord(e->xlow_event, st));
     return EMSPEC_OK;
 }
+
+namespace emspec {
+int run_plan_columns(emspec_engine* e, const Plan& p, const float* pcm, int32_t S, int64_t L, int32_t hop, int32_t reassign,
+                     int64_t C, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st) {
+    if (e->exact()) return run_columns_exact(e, p, pcm, S, L, p.n, hop, reassign, C, db, rgba, index, st);
+    return run_columns(e, plan_dev(e, p, hop, reassign), db_map(e, p.n), pcm, S, L, p.n, hop, reassign, C, db, rgba, index, st);
+}
+}  // namespace emspec
 
 extern "C" {
 

@@ -9,12 +9,17 @@
 
 #include <map>
 #include <string>
+#include <tuple>
 #include <vector>
 
 struct emspec_engine;
 namespace emspec {
 struct Plan {
     int n = 0;
+    // the rows this plan serves: the engine's whole table (row0 = 0, rows = cfg.rows), or a band of it for the
+    // multi-resolution batch (emspec_multires.cpp) - h_ebin / d_ebin (/ d_ebin64, h_e0, h_eR) are then that slice of the
+    // full table, and d_tw / d_tw64 belong to the full plan of the same n
+    int row0 = 0, rows = 0;
     float2* d_tw = nullptr;
     float* d_ebin = nullptr;
     std::vector<float> h_tw, h_ebin;
@@ -51,6 +56,12 @@ struct LiveState {
 int latency(int n, int hop, int reassign);
 int check_shape(const emspec_engine* e, int n, int hop);
 int get_plan(emspec_engine* e, int n, Plan** out);
+int get_band_plan(emspec_engine* e, int n, int row0, int rows, Plan** out);   // rows [row0, row0 + rows) of the table
+// columns of S device-resident streams -> dB / RGBA / index of the plan's rows, no display post-process (emspec_api.cpp)
+int run_plan_columns(emspec_engine* e, const Plan& p, const float* pcm, int32_t S, int64_t L, int32_t hop, int32_t reassign,
+                     int64_t C, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st);
+// device workspace *ptr for `per_stream` bytes per stream (+ extra): streams per chunk by the records path's budget
+int grow_chunked(emspec_engine* e, void** ptr, size_t* have, size_t per_stream, size_t extra, size_t cap, int S, int* chunk_out);
 PlanDev plan_dev(const emspec_engine* e, const Plan& p, int hop, int reassign);
 ExactPlanDev exact_plan_dev(const emspec_engine* e, const Plan& p, int hop, int reassign);
 ExactDbMap exact_db_map(const emspec_engine* e, int n, const ExactPlanDev& pd);
@@ -74,6 +85,8 @@ struct emspec_engine {
     std::string arch;
     mutable std::string err;
     std::map<int, emspec::Plan> plans;
+    // band plans of the multi-resolution batch, keyed by (n, row0, rows): kept apart from `plans` (keyed by n only)
+    std::map<std::tuple<int, int, int>, emspec::Plan> band_plans;
     std::vector<float> custom_edges_hz;   // rows+1 entries when emspec_set_row_edges_hz was called
     uint8_t* d_lut = nullptr;
     // batch workspace (generic path per-bin records; host-API staging)
@@ -93,6 +106,8 @@ struct emspec_engine {
     float* d_raw = nullptr; size_t raw_bytes = 0;      // raw dB columns of a batch
     float* d_post = nullptr; size_t post_bytes = 0;    // post-processed dB when the caller wants none
     float* d_peak = nullptr; size_t peak_bytes = 0;    // column peaks + gains
+    // multi-resolution batch (emspec_multires.cpp): both bands' raw dB (+ the composed raw dB for the post-process)
+    float* d_mres = nullptr; size_t mres_bytes = 0;
     // streaming (emspec_live.cpp): the live multi-stream session, and the single-stream calls' own (emspec_column,
     // emspec_push_samples: the same machinery with one stream); independent of each other
     emspec::LiveState live, one;

@@ -130,6 +130,11 @@ hipError_t launch_fused(int n, const PlanDev& pl, const DbMap& m, const uint8_t*
 hipError_t launch_postprocess(const float* db, float* out_db, uint8_t* rgba, uint8_t* index, int S, int64_t C, int R,
                               float sm, float agc, float db_top, const DbMap& dm, const uint8_t* lut, float* peak,
                               float* gain, hipStream_t st);
+// multi-resolution batch (multires.hip.inc): [S][C][split] low-band and [S][C + 2 shift][R - split] high-band raw dB -> the
+// composed columns [S][C][R]: dB and / or palette index and RGBA (any output null)
+hipError_t launch_multires_compose(const float* lo, const float* hi, int S, int64_t C, int R, int split, int shift,
+                                   const DbMap& dm, const uint8_t* lut, float* db, uint8_t* rgba, uint8_t* index,
+                                   hipStream_t st);
 // live multi-stream calls (live_launch.hip.inc): flush of pending columns, display post-process of a launch's columns.
 // The frame launches themselves go through launch_frames / launch_exact_frames with sinks.live set and
 // nframes = (largest per-stream frame count) + 1.

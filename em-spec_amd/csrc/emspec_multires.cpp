@@ -1,0 +1,149 @@
+// emspec_multires.cpp — the multi-resolution batch (include/emspec.h: emspec_batch_multires*): a long FFT
+// for the rows below split_row, a short one above, on the long FFT's column grid.  Each band is an ordinary batch of its own
+// band plan (a slice of the engine's row table, get_band_plan) through the same run functions as emspec_batch_device, into an
+// engine workspace; multires.hip.inc's kernel composes the two into the caller's layout.
+#include "emspec_engine.h"
+
+#include <algorithm>
+#include <string>
+
+using namespace emspec;
+
+namespace {
+
+// null when (n_low, n_high, hop) is an accepted shape, else the rule it breaks
+const char* multires_shape_error(int n_low, int n_high, int hop) {
+    if (n_low != 8192 && n_low != 16384) return "n_low must be 8192 or 16384";
+    if (n_high != 1024 && n_high != 2048 && n_high != 4096) return "n_high must be 1024, 2048 or 4096";
+    if (hop < 1 || hop > n_high) return "hop must be in [1, n_high]";
+    if ((n_low - n_high) % (2 * hop)) return "(n_low - n_high) / (2 hop) must be an integer";
+    return nullptr;
+}
+
+int multires_check(emspec_engine* e, int32_t S, int64_t L, int32_t n_low, int32_t n_high, int32_t hop, int32_t split_row) {
+    if (const char* why = multires_shape_error(n_low, n_high, hop)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
+    if (split_row % 4 || split_row < 64 || split_row > e->cfg.rows - 64)
+        return fail(e, EMSPEC_ERR_INVALID_ARG, "split_row must be a multiple of 4 in [64, rows - 64]");
+    if (S < 1 || S > 65535) return fail(e, EMSPEC_ERR_INVALID_ARG, "need 1..65535 streams");
+    if (L < n_low) return fail(e, EMSPEC_ERR_INVALID_ARG, "need at least n_low samples per stream");
+    return EMSPEC_OK;
+}
+
+// S device-resident streams -> composed columns; streams in chunks so that the band workspace stays bounded (the records
+// path's budget rule).  Per chunk: the low band's C columns of rows [0, split), the high band's C + 2 shift columns of rows
+// [split, R), the composition (with the display post-process on: into a raw plane, then launch_postprocess over whole streams).
+int multires_run(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32_t n_low, int32_t n_high, int32_t hop,
+                 int32_t split, int32_t reassign, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st) {
+    int rc;
+    const int R = e->cfg.rows, Rh = R - split, shift = (n_low - n_high) / (2 * hop);
+    const int64_t C = emspec_num_columns(L, n_low, hop), Ch = emspec_num_columns(L, n_high, hop);   // Ch = C + 2 shift
+    Plan *pl, *ph;
+    if ((rc = get_band_plan(e, n_low, 0, split, &pl))) return rc;
+    if ((rc = get_band_plan(e, n_high, split, Rh, &ph))) return rc;
+    const bool post = e->smoothing > 0.0f || e->agc > 0.0f;
+    const size_t col_cells = (size_t)C * R, lo_s = (size_t)C * split * 4, hi_s = (size_t)Ch * Rh * 4, raw_s = post ? col_cells * 4 : 0;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    int chunk = 1;
+    if ((rc = grow_chunked(e, (void**)&e->d_mres, &e->mres_bytes, lo_s + hi_s + raw_s, 1024, (size_t)4 << 30, S, &chunk))) return rc;
+    if (post) {
+        if ((rc = grow(e, (void**)&e->d_peak, &e->peak_bytes, (size_t)chunk * C * 8 + 16))) return rc;
+        if (!db && (rc = grow(e, (void**)&e->d_post, &e->post_bytes, (size_t)chunk * col_cells * 4))) return rc;
+    }
+    float* wlo = e->d_mres;
+    float* whi = (float*)((char*)wlo + al(lo_s * chunk));
+    float* wraw = (float*)((char*)whi + al(hi_s * chunk));
+    // the dB -> index map: only lo / inv_range / gate are read, which every n shares (EXACT mode: its own rounding of lo)
+    DbMap dm = db_map(e, n_low);
+    if (e->exact()) {
+        const ExactDbMap xm = exact_db_map(e, n_low, exact_plan_dev(e, *pl, hop, reassign));
+        dm.lo = xm.lo; dm.inv_range = xm.inv_range; dm.gate = xm.gate;
+    }
+    for (int s0 = 0; s0 < S; s0 += chunk) {
+        const int sc = std::min(chunk, S - s0);
+        const float* in = pcm + (size_t)s0 * L;
+        if ((rc = run_plan_columns(e, *pl, in, sc, L, hop, reassign, C, wlo, nullptr, nullptr, st))) return rc;
+        if ((rc = run_plan_columns(e, *ph, in, sc, L, hop, reassign, Ch, whi, nullptr, nullptr, st))) return rc;
+        const size_t o = (size_t)s0 * col_cells;
+        if (!post) {
+            HIPCHK(e, launch_multires_compose(wlo, whi, sc, C, R, split, shift, dm, e->d_lut, db ? db + o : nullptr,
+                                              rgba ? rgba + 4 * o : nullptr, index ? index + o : nullptr, st));
+            continue;
+        }
+        HIPCHK(e, launch_multires_compose(wlo, whi, sc, C, R, split, shift, dm, e->d_lut, wraw, nullptr, nullptr, st));
+        HIPCHK(e, launch_postprocess(wraw, db ? db + o : e->d_post, rgba ? rgba + 4 * o : nullptr, index ? index + o : nullptr, sc,
+                                     C, R, e->smoothing, e->agc, e->cfg.db_top, db_map(e, n_low), e->d_lut, e->d_peak,
+                                     e->d_peak + (size_t)sc * C, st));
+    }
+    return EMSPEC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t emspec_multires_shift(int32_t n_low, int32_t n_high, int32_t hop) {
+    if (multires_shape_error(n_low, n_high, hop)) return -1;
+    return (n_low - n_high) / (2 * hop);
+}
+
+int64_t emspec_multires_columns(int64_t L, int32_t n_low, int32_t n_high, int32_t hop) {
+    if (multires_shape_error(n_low, n_high, hop)) return -1;
+    return emspec_num_columns(L, n_low, hop);
+}
+
+int emspec_batch_multires_device(emspec_engine* e, const float* pcm_dev, int32_t S, int64_t L, int32_t n_low, int32_t n_high,
+                                 int32_t hop, int32_t split_row, int32_t reassign, float* db_dev, uint8_t* rgba_dev,
+                                 uint8_t* index_dev, void* hip_stream) {
+    if (!e || !pcm_dev) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument");
+    int rc = multires_check(e, S, L, n_low, n_high, hop, split_row);
+    if (rc) return rc;
+    HIPCHK(e, hipSetDevice(e->device));
+    if (!db_dev && !rgba_dev && !index_dev) return EMSPEC_OK;
+    return multires_run(e, pcm_dev, S, L, n_low, n_high, hop, split_row, reassign, db_dev, rgba_dev, index_dev,
+                        (hipStream_t)hip_stream);
+}
+
+// host buffers: copy in, run, copy out, in chunks of streams (staging bounded at 4 GiB, like emspec_batch's plain path)
+int emspec_batch_multires(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32_t n_low, int32_t n_high, int32_t hop,
+                          int32_t split_row, int32_t reassign, const emspec_out* out) {
+    if (!e || !pcm || !out) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument");
+    int rc = multires_check(e, S, L, n_low, n_high, hop, split_row);
+    if (rc) return rc;
+    HIPCHK(e, hipSetDevice(e->device));
+    if (!out->db && !out->rgba && !out->index) return EMSPEC_OK;
+    const int64_t C = emspec_num_columns(L, n_low, hop);
+    const size_t col_cells = (size_t)C * e->cfg.rows;
+    const size_t in_s = (size_t)L * sizeof(float);
+    const size_t db_s = out->db ? col_cells * 4 : 0, rgba_s = out->rgba ? col_cells * 4 : 0, idx_s = out->index ? col_cells : 0;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t per_stream = al(in_s) + al(db_s) + al(rgba_s) + al(idx_s);
+    int chunk = (int)(((size_t)4 << 30) / per_stream);
+    chunk = chunk < 1 ? 1 : (chunk > S ? S : chunk);
+    if ((rc = grow(e, (void**)&e->d_stage, &e->stage_bytes, (size_t)chunk * per_stream + 1024))) return rc;
+    hipStream_t st = e->stream;
+    hipError_t herr = hipSuccess;
+    for (int s0 = 0; s0 < S && rc == EMSPEC_OK && herr == hipSuccess; s0 += chunk) {
+        const int sc = (S - s0 < chunk) ? S - s0 : chunk;
+        char* base = e->d_stage;
+        float* d_pcm = (float*)base; base += al(in_s) * chunk;
+        float* d_db = db_s ? (float*)base : nullptr; base += al(db_s) * chunk;
+        uint8_t* d_rgba = rgba_s ? (uint8_t*)base : nullptr; base += al(rgba_s) * chunk;
+        uint8_t* d_idx = idx_s ? (uint8_t*)base : nullptr;
+        herr = hipMemcpyAsync(d_pcm, pcm + (size_t)s0 * L, in_s * sc, hipMemcpyHostToDevice, st);
+        if (herr != hipSuccess) break;
+        rc = multires_run(e, d_pcm, sc, L, n_low, n_high, hop, split_row, reassign, d_db, d_rgba, d_idx, st);
+        if (rc != EMSPEC_OK) break;
+        if (db_s) herr = hipMemcpyAsync(out->db + (size_t)s0 * col_cells, d_db, db_s * sc, hipMemcpyDeviceToHost, st);
+        if (herr == hipSuccess && rgba_s) herr = hipMemcpyAsync(out->rgba + 4 * (size_t)s0 * col_cells, d_rgba, rgba_s * sc, hipMemcpyDeviceToHost, st);
+        if (herr == hipSuccess && idx_s) herr = hipMemcpyAsync(out->index + (size_t)s0 * col_cells, d_idx, idx_s * sc, hipMemcpyDeviceToHost, st);
+        if (herr == hipSuccess && s0 + chunk < S) herr = hipStreamSynchronize(st);   // the next chunk reuses the staging
+    }
+    const hipError_t s1 = hipStreamSynchronize(st);
+    if (rc != EMSPEC_OK) return rc;
+    HIPCHK(e, herr);
+    HIPCHK(e, s1);
+    if (read_kernel_error(true) > 0) return fail(e, EMSPEC_ERR_HIP, "a kernel's bounded wait timed out (protocol error): results invalid");
+    return EMSPEC_OK;
+}
+
+}  // extern "C"

@@ -39,6 +39,7 @@ SYMBOLS = [
     "emspec_comm_set_timeout", "emspec_batch_packed", "emspec_wire_unpack_host",
     "emspec_columns", "emspec_columns_flush", "emspec_push_columns_multi", "emspec_push_samples_multi",
     "emspec_reset_stream", "emspec_live_streams",
+    "emspec_multires_columns", "emspec_multires_shift", "emspec_batch_multires", "emspec_batch_multires_device",
 ]
 
 
@@ -159,6 +160,14 @@ def load(diag=False):
     lib.emspec_reset_stream.argtypes = [C.c_void_p, C.c_int32]
     lib.emspec_live_streams.argtypes = [C.c_void_p]
     lib.emspec_live_streams.restype = C.c_int32
+    lib.emspec_multires_columns.restype = C.c_int64
+    lib.emspec_multires_columns.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32]
+    lib.emspec_multires_shift.restype = C.c_int32
+    lib.emspec_multires_shift.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.emspec_batch_multires.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_int32, C.POINTER(Out)]
+    lib.emspec_batch_multires_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _libs[diag] = lib
     return lib
 
@@ -208,6 +217,18 @@ def default_config(**kw):
 
 def num_columns(L, n, hop):
     return int(load().emspec_num_columns(L, n, hop))
+
+
+def multires_columns(L, n_low, n_high, hop):
+    """Columns of a multi-resolution batch (emspec_multires_columns): num_columns(L, n_low, hop), -1 for a shape
+    (n_low, n_high, hop) that is not accepted."""
+    return int(load().emspec_multires_columns(L, n_low, n_high, hop))
+
+
+def multires_shift(n_low, n_high, hop):
+    """The high band's column shift (n_low - n_high) / (2 hop) of a multi-resolution batch, -1 for a shape that is not
+    accepted (emspec_multires_shift)."""
+    return int(load().emspec_multires_shift(n_low, n_high, hop))
 
 
 def warped_edges_hz(rows, fmin_hz, fmax_hz, low_end_boost=1.0, freq_scale=1.0):
@@ -377,6 +398,44 @@ class Engine:
             assert t is None or (t.is_cuda and t.is_contiguous())
         self._chk(self._lib.emspec_batch_device(self._h, ptr(pcm_t), S, L, n, hop, int(bool(reassign)), ptr(db),
                                                 ptr(rgba), ptr(index), C.c_void_p(st.cuda_stream)))
+
+    # -- multi-resolution batch: n_low below split_row, n_high from it up, one column grid --------
+    def split_row_for_hz(self, hz):
+        """The smallest admissible split_row (a multiple of 4 in [64, rows - 64]) whose lower edge is >= hz."""
+        edges = self.row_edges_hz()
+        for r in range(64, self.rows - 63, 4):
+            if edges[r] >= np.float32(hz):
+                return r
+        raise EmspecError(ERR_INVALID_ARG, f"no admissible split row at or above {hz} Hz")
+
+    def batch_multires(self, pcm, n_low, n_high, hop, split_row, reassign=True, want=("db",)):
+        """Host buffers in and out (emspec_batch_multires): [S][C][rows] outputs as in batch(), C = multires_columns."""
+        pcm = np.ascontiguousarray(pcm, np.float32)
+        if pcm.ndim == 1:
+            pcm = pcm[None]
+        S, L = pcm.shape
+        Cn = max(multires_columns(L, n_low, n_high, hop), 0)
+        db = np.empty((S, Cn, self.rows), np.float32) if "db" in want else None
+        rgba = np.empty((S, Cn, self.rows, 4), np.uint8) if "rgba" in want else None
+        idx = np.empty((S, Cn, self.rows), np.uint8) if "index" in want else None
+        out = Out(_np_ptr(db), _np_ptr(rgba), _np_ptr(idx))
+        self._chk(self._lib.emspec_batch_multires(self._h, _np_ptr(pcm), S, L, n_low, n_high, hop, split_row,
+                                                  int(bool(reassign)), C.byref(out)))
+        return {"db": db, "rgba": rgba, "index": idx}
+
+    def batch_multires_device(self, pcm_t, n_low, n_high, hop, split_row, reassign=True, db=None, rgba=None, index=None,
+                              stream=None):
+        """Device-resident torch tensors (emspec_batch_multires_device), as batch_device(); does not synchronise."""
+        import torch
+        assert pcm_t.is_cuda and pcm_t.dtype == torch.float32 and pcm_t.is_contiguous() and pcm_t.dim() == 2
+        S, L = pcm_t.shape
+        st = stream if stream is not None else torch.cuda.current_stream(pcm_t.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        for t in (db, rgba, index):
+            assert t is None or (t.is_cuda and t.is_contiguous())
+        self._chk(self._lib.emspec_batch_multires_device(self._h, ptr(pcm_t), S, L, n_low, n_high, hop, split_row,
+                                                         int(bool(reassign)), ptr(db), ptr(rgba), ptr(index),
+                                                         C.c_void_p(st.cuda_stream)))
 
     # -- multi-GPU: RCCL communicator + gather of finished palette-index columns ----
     def comm_init(self, comm_id, rank, world):

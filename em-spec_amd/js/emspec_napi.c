@@ -326,6 +326,45 @@ static napi_value Batch(napi_env env, napi_callback_info info) {
     return r;
 }
 
+/* batchMultires(handle, pcm:Float32Array(S*L), S, L, lowFftSize, fftSize, hop, splitRow, reassign, outDb[, outRgba, outIndex])
+ * -> columns.  emspec_batch_multires: lowFftSize below splitRow, fftSize from it up, on one column grid (synchronous). */
+static napi_value BatchMultires(napi_env env, napi_callback_info info) {
+    size_t argc = 12; napi_value argv[12];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 10) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "batchMultires(handle, pcm, S, L, lowFftSize, fftSize, hop, splitRow, reassign, outDb[, outRgba, outIndex])"); return NULL; }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    void* pcm; size_t plen;
+    if (!get_typed(env, argv[1], napi_float32_array, &pcm, &plen, 0)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "pcm must be a Float32Array"); return NULL; }
+    int32_t S, nl, nh, hop, split; int64_t L; bool reassign;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[2], &S));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[3], &L));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[4], &nl));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[5], &nh));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[6], &hop));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[7], &split));
+    NAPI_OK_OR_RETURN(env, napi_coerce_to_bool(env, argv[8], &argv[8]));
+    NAPI_OK_OR_RETURN(env, napi_get_value_bool(env, argv[8], &reassign));
+    if (S < 1 || L < 1 || (size_t)S * (size_t)L != plen) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "pcm.length must equal S*L"); return NULL; }
+    /* C <= 0: a shape (or L) the library rejects, with a message naming the rule, before it touches any output */
+    const int64_t C = emspec_multires_columns(L, nl, nh, hop);
+    size_t l0 = 0, l1 = 0, l2 = 0; void *p0 = NULL, *p1 = NULL, *p2 = NULL;
+    if (!get_typed(env, argv[9], napi_float32_array, &p0, &l0, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outDb must be a Float32Array"); return NULL; }
+    if (argc > 10 && !get_typed(env, argv[10], napi_uint8_array, &p1, &l1, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outRgba must be a Uint8Array"); return NULL; }
+    if (argc > 11 && !get_typed(env, argv[11], napi_uint8_array, &p2, &l2, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outIndex must be a Uint8Array"); return NULL; }
+    size_t cells = 0;
+    if (p0) cells = l0; else if (p1) cells = l1 / 4; else if (p2) cells = l2;
+    if (C > 0 && (cells != (size_t)S * (size_t)C * (size_t)h->rows || (p1 && l1 != 4 * cells) || (p2 && l2 != cells) || (p0 && l0 != cells))) {
+        napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "output arrays must hold exactly S*columns*rows cells, rows = the engine's row count (rgba: 4 bytes per cell)");
+        return NULL;
+    }
+    emspec_out out; memset(&out, 0, sizeof(out));
+    out.db = (float*)p0; out.rgba = (uint8_t*)p1; out.index = (uint8_t*)p2;
+    int rc = emspec_batch_multires(h->e, (const float*)pcm, S, L, nl, nh, hop, split, reassign ? 1 : 0, &out);
+    if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
+    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int64(env, C, &r));
+    return r;
+}
+
 /* batchPacked(handle, pcm:Float32Array(S*L), S, L, fftSize, hop, reassign, wire:Uint8Array, offsets:Float64Array(S+1)) -> columns
  * per stream.  emspec_batch_packed: the palette-index columns cross PCIe as one lossless wire image per stream; stream s
  * is wire.subarray(offsets[s], offsets[s+1]) (offsets as doubles: exact below 2^53). */
@@ -861,6 +900,20 @@ static napi_value NumColumns(napi_env env, napi_callback_info info) {
     return r;
 }
 
+/* multiresColumns(L, lowFftSize, fftSize, hop) -> columns of a multi-resolution batch, -1 for a shape it does not accept */
+static napi_value MultiresColumns(napi_env env, napi_callback_info info) {
+    size_t argc = 4; napi_value argv[4];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    int64_t L = 0; int32_t nl = 0, nh = 0, hop = 0;
+    if (argc < 4) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "multiresColumns(L, lowFftSize, fftSize, hop)"); return NULL; }
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[0], &L));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[1], &nl));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[2], &nh));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[3], &hop));
+    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int64(env, emspec_multires_columns(L, nl, nh, hop), &r));
+    return r;
+}
+
 static napi_value LatencyColumns(napi_env env, napi_callback_info info) {
     size_t argc = 3; napi_value argv[3];
     NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -982,6 +1035,8 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"allocPinned", NULL, AllocPinned, NULL, NULL, NULL, napi_default, NULL},
         {"numColumns", NULL, NumColumns, NULL, NULL, NULL, napi_default, NULL},
         {"latencyColumns", NULL, LatencyColumns, NULL, NULL, NULL, napi_default, NULL},
+        {"multiresColumns", NULL, MultiresColumns, NULL, NULL, NULL, napi_default, NULL},
+        {"batchMultires", NULL, BatchMultires, NULL, NULL, NULL, napi_default, NULL},
         {"commUniqueId", NULL, CommUniqueId, NULL, NULL, NULL, napi_default, NULL},
         {"commInit", NULL, CommInit, NULL, NULL, NULL, napi_default, NULL},
         {"batchGather", NULL, BatchGather, NULL, NULL, NULL, napi_default, NULL},

@@ -155,6 +155,29 @@ class Engine {
     return native.batchPackedAsync(this._h, pcm, S, L, fftSize, hop, !!reassign, wire, offsets);
   }
 
+  /**
+   * Multi-resolution columns (emspec_batch_multires, DESIGN.md §3.8): a long FFT (opts.lowFftSize, 8192 or 16384) for the
+   * rows below the split, the short one (opts.fftSize, 1024 ... 4096) from it up, on one column grid - bass notes a fraction
+   * of a short FFT's bin apart separate, transients above the split stay sharp.  opts: {fftSize, lowFftSize, hop,
+   * splitHz | splitRow, reassign = true}; splitHz picks the first admissible row whose lower edge is >= splitHz.  out as in
+   * computeColumns, S * C * rows cells with C = multiresColumns(L, lowFftSize, fftSize, hop).  Synchronous; returns C.
+   */
+  computeColumnsMultires(pcm, S, L, opts, out) {
+    const split = opts.splitRow !== undefined ? opts.splitRow : this.splitRowForHz(opts.splitHz);
+    const reassign = opts.reassign === undefined ? true : !!opts.reassign;
+    return native.batchMultires(this._h, pcm, S, L, opts.lowFftSize, opts.fftSize, opts.hop, split, reassign, out.db, out.rgba,
+                                out.index);
+  }
+
+  /** The smallest admissible split row (a multiple of 4 in [64, rows - 64]) whose lower edge is >= hz. */
+  splitRowForHz(hz) {
+    const e = this.getRowEdges();
+    for (let r = 64; r <= this.rows - 64; r += 4) if (e[r] >= Math.fround(hz)) return r;
+    const err = new Error(`no admissible split row at or above ${hz} Hz`);
+    err.code = 'EMSPEC_ERR_INVALID_ARG';
+    throw err;
+  }
+
   /** Same as computeColumns, off the JS thread: resolves with C.  Do not touch the arrays or this
    *  engine until the promise settles (an engine is not thread-safe). */
   computeColumnsAsync(pcm, S, L, fftSize, hop, reassign, out) {
@@ -265,6 +288,9 @@ module.exports = {
   /** Expand one wire image (Uint8Array) into out: Uint8Array(columns * rows) on the host's own cores - no device, no engine. */
   unpackWire: native.wireUnpack,
   latencyColumns: native.latencyColumns,
+  /** Columns of a multi-resolution batch (emspec_multires_columns): multiresColumns(L, lowFftSize, fftSize, hop), -1 for a
+   *  shape it does not accept. */
+  multiresColumns: native.multiresColumns,
   /** 'emspec abi=2 sources=<sha16> arch=gfx950': what the loaded libemspec was built from. */
   buildInfo: native.buildInfo,
 };

@@ -478,6 +478,36 @@ int emspec_uses_fused(const emspec_engine* e, int32_t n, int32_t hop, int32_t re
 /* Name of the device the engine runs on, e.g. "gfx950". */
 const char* emspec_device_arch(const emspec_engine* e);
 
+/*
+ * Multi-resolution batch: a long FFT (n_low) for the rows below split_row and a short one (n_high) for
+ * the rows from split_row up, on ONE column grid - two bass notes a fraction of a short FFT's bin apart separate, and
+ * transients in the upper rows stay sharp.  The image is defined as a stitch of two single-resolution batches on the same
+ * engine and row table (emspec_batch at n_low and at n_high, same hop and reassign):
+ *     image[s][c][r] = single(n_low)[s][c][r]           r <  split_row
+ *     image[s][c][r] = single(n_high)[s][c + shift][r]  r >= split_row
+ * for c in [0, columns): column c is centred at sample c * hop + n_low / 2 in both bands.  dB, palette index and RGBA are
+ * those bytes (EXACT mode: bit for bit); with the display post-process on (emspec_set_display) it runs once over the
+ * composed raw dB, by the law of a single-resolution batch.  Accepted shapes: n_low in {8192, 16384}, n_high in {1024, 2048,
+ * 4096}, 1 <= hop <= n_high, shift = (n_low - n_high) / (2 hop) an integer (e.g. 16384 / 4096 at hop 128 ... 1024,
+ * 8192 / 2048 at hop 128 or 256), split_row a multiple of 4 with 64 <= split_row <= rows - 64, L >= n_low; anything else is
+ * EMSPEC_ERR_INVALID_ARG with a message naming the rule.
+ * emspec_multires_shift: the shift, or -1 for a shape (n_low, n_high, hop) that is not accepted.
+ * emspec_multires_columns: the column count (= emspec_num_columns(L, n_low, hop)), 0 when L < n_low, -1 for a shape
+ *   that is not accepted.
+ * emspec_batch_multires: host buffers, page-locked or not ([S][L] in, [S][columns][rows] (+[4]) out, any output NULL):
+ *   copies in, runs, copies out, in chunks of streams; returns when the outputs are written.
+ * emspec_batch_multires_device: device buffers, enqueued on hip_stream (NULL = the default stream); does not synchronise.
+ * Both bands' raw dB live in an engine workspace bounded like the records path's (streams are processed in chunks).
+ * Single-resolution results on the same engine are not affected by a multi-resolution call.
+ */
+int64_t emspec_multires_columns(int64_t L, int32_t n_low, int32_t n_high, int32_t hop);
+int32_t emspec_multires_shift(int32_t n_low, int32_t n_high, int32_t hop);
+int emspec_batch_multires(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32_t n_low, int32_t n_high,
+                          int32_t hop, int32_t split_row, int32_t reassign, const emspec_out* out);
+int emspec_batch_multires_device(emspec_engine* e, const float* pcm_dev, int32_t S, int64_t L, int32_t n_low,
+                                 int32_t n_high, int32_t hop, int32_t split_row, int32_t reassign,
+                                 float* db_dev, uint8_t* rgba_dev, uint8_t* index_dev, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
