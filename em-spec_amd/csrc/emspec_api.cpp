@@ -16,9 +16,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <condition_variable>
-#include <mutex>
-#include <thread>
 #include <map>
 #include <new>
 #include <string>
@@ -883,396 +880,11 @@ int emspec_debug_phase_cycles(emspec_engine* e, const float* pcm_dev, int32_t S,
 
 }  // extern "C"
 
-// ---- host-buffer batch: a three-stage pipeline over chunks of streams.  H2D copies on their own HIP stream, every kernel on
-// the engine's compute stream (so the per-engine workspaces - EXACT records / low-row scratch, display post-process - are
-// used by one launch at a time, and no two fused launches share the chip), D2H copies on a third stream; kPipeSets staging
-// sets, events between the stages.  PCIe is full duplex: the H2D of chunk k+1, the kernels of chunk k and the D2H of chunk
-// k-1 are in flight together.  With `pk` the palette-index columns leave the device as the gather's lossless wire image
-// (pack.hip.inc: ~186 B instead of 1,024 B per column on the bench input), one image per stream, tightly packed into the
-// caller's buffer in stream order; the host learns each image's size from its 32-byte header, which is copied out behind the
-// pack, so the D2H stage of a chunk is enqueued kPipeLag chunks after its kernels.
-struct PackedOut { uint8_t* wire; int64_t capacity; int64_t* offsets; };
-static constexpr int kPipeSets = 3, kPipeLag = 2;
-
-static int pipe_setup(emspec_engine* e) {
-    if (!e->stream_in) HIPCHK(e, hipStreamCreateWithFlags(&e->stream_in, hipStreamNonBlocking));
-    if (!e->stream_out) HIPCHK(e, hipStreamCreateWithFlags(&e->stream_out, hipStreamNonBlocking));
-    for (int i = 0; i < 3 * kPipeSets; ++i)
-        if (!e->pipe_ev[i]) HIPCHK(e, hipEventCreateWithFlags(&e->pipe_ev[i], hipEventDisableTiming));
-    return EMSPEC_OK;
-}
-
-// One unit of the host pipelines: `sc` whole streams from stream s0 on - or, when the batch has fewer streams than the pipeline
-// needs units (BASELINE configs[1] is ONE stream), a run of columns [c0, c0 + cn) of one stream, computed as a batch of its own
-// from the frames that reach those columns: D more on either side (a bin moves at most D columns), whose own columns - `skip` in
-// front, the rest behind - are computed and left on the device.  Every frame that adds to a kept column is in the run and no
-// other frame can reach it, so the kept columns are the whole batch's (EXACT mode: the same bytes; float32: the same sums in
-// another order, as between any two launches).
-struct PipeItem { int s0, sc; int64_t c0, cn, first_sample, samples, skip, cols; };
-static constexpr int kNoThread = -1000, kNoPipeline = -1001;   // pipeline not taken (not EMSPEC_ERR_* values): no helper thread / one unit only
-
-// How many units a batch is cut into.  A unit costs ~0.2 ms (EXACT: 0.4) on the compute stream whatever its size: a launch of
-// the fused kernel takes 0.11-0.18 ms however few columns it has - a workgroup WALKS its segment, 2 D halo frames and the ring's
-// start-up before the first column leaves (emspec_batch_device on 49 columns: 113 us on the GPU, 5 us to enqueue) - the units'
-// kernels run one after the other, and each unit adds ~40 us of event waits and copy start-up.  Behind that, three stages
-// overlap: with u units a call takes about
-//     max(u x 0.2 ms,  M + (sum - M) / u),   M = the longest of [bytes in / 45 GB/s, kernel time, bytes out / 45 GB/s].
-// Until late round 6 the count was fixed (sixteen, or one per stream below that): 8 streams x 2^18 samples took 1.65 ms - eight
-// units - for 0.5 ms of copies and kernels.  The kernel rates are the bench line's, rounded; at most sixteen units.
-static int pipe_units(bool exact, int n, int64_t columns, size_t bytes_in, size_t bytes_out) {
-    const double rate = (n <= 1024 ? 3.4e8 : n <= 2048 ? 2.2e8 : n <= 4096 ? 1.15e8 : n <= 8192 ? 5e7 : 2.2e7) / (exact ? (n > 4096 ? 2.8 : 2.1) : 1.0);
-    const double t_in = (double)bytes_in / 45e9, t_out = (double)bytes_out / 45e9, t_k = (double)columns / rate;
-    const double longest = std::max(t_in, std::max(t_k, t_out)), sum = t_in + t_k + t_out, per_unit = exact ? 0.4e-3 : 0.2e-3;
-    int best = 1;
-    double best_t = sum + per_unit;
-    for (int u = 2; u <= 16; ++u) {
-        const double t = std::max(u * per_unit, longest + (sum - longest) / u);
-        if (t < best_t * 0.995) { best = u; best_t = t; }   // (not one unit more for nothing)
-    }
-#ifdef EMSPEC_DIAG
-    if (const char* ev = getenv("EMSPEC_PIPE_CHUNKS")) { const int v = atoi(ev); if (v >= 1) best = v; }   // A/B aid
-#endif
-    return best;
-}
-
-static std::vector<PipeItem> pipe_items(int S, int64_t L, int64_t C, int n, int hop, int D, size_t per_stream_bytes, bool by_time, int target) {
-    std::vector<PipeItem> items;
-    // runs of columns: when there are fewer than `target` streams; at least 16,384 columns per run - a unit costs ~0.2 ms
-    // (pipe_units) whatever its size, and 16 MB each way over PCIe take 0.35 ms (measured with 2,048-column runs: one stream
-    // of 2^22 samples 1.49 ms instead of 0.84 in one piece)
-    const int64_t pieces = by_time && S < target ? std::min<int64_t>((target + S - 1) / S, C / 16384) : 1;
-    if (pieces > 1) {
-        for (int s = 0; s < S; ++s)
-            for (int64_t t = 0; t < pieces; ++t) {
-                PipeItem it;
-                it.s0 = s; it.sc = 1;
-                it.c0 = C * t / pieces;
-                it.cn = C * (t + 1) / pieces - it.c0;
-                const int64_t f0 = std::max<int64_t>(it.c0 - D, 0), f1 = std::min<int64_t>(it.c0 + it.cn + D, C);   // frames [f0, f1)
-                it.first_sample = f0 * hop;
-                it.samples = (f1 - f0 - 1) * hop + n;
-                it.skip = it.c0 - f0;
-                it.cols = f1 - f0;
-                items.push_back(it);
-            }
-        return items;
-    }
-    // chunks of streams: about `target` per batch (pipe_units), bounded by 1 GiB of staging per set; a chunk of a few streams
-    // still fills the chip (segments are cut per launch)
-    int chunk = (S + target - 1) / target;
-    const int fit = (int)(((size_t)1 << 30) / per_stream_bytes);
-    chunk = chunk > fit ? fit : chunk;
-    chunk = chunk < 1 ? 1 : chunk;
-    for (int s0 = 0; s0 < S; s0 += chunk) items.push_back(PipeItem{s0, std::min(chunk, S - s0), 0, C, 0, L, 0, C});
-    return items;
-}
-
-static int batch_pipeline(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32_t n, int32_t hop, int32_t reassign,
-                          const emspec_out* out, const PackedOut* pk) {
-    int rc;
-    if ((rc = pipe_setup(e))) return rc;
-    const int64_t C = emspec_num_columns(L, n, hop);
-    const int R = e->cfg.rows;
-    const size_t col_cells = (size_t)C * R;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t in_s = (size_t)L * sizeof(float);
-    const bool want_db = out && out->db, want_rgba = out && out->rgba, want_idx = (out && out->index) || pk;
-    const size_t wire_s = pk ? (size_t)wire_bound_bytes(C, R) : 0;
-    const size_t per_stream = al(in_s) + al(want_db ? col_cells * 4 : 0) + al(want_rgba ? col_cells * 4 : 0) + al(want_idx ? col_cells : 0) + al(wire_s);
-    // (an image is one stream's whole run of columns, and the display post-process walks a stream in time order: whole streams there)
-    const bool post = e->smoothing > 0.0f || e->agc > 0.0f;
-    const int units = pipe_units(e->exact(), n, (int64_t)S * C, (size_t)S * in_s,
-                                 pk ? (size_t)S * col_cells / 5 : (size_t)S * col_cells * ((want_db ? 4 : 0) + (want_rgba ? 4 : 0) + (out && out->index ? 1 : 0)));
-    const std::vector<PipeItem> items = pipe_items(S, L, C, n, hop, latency(n, hop, reassign), per_stream, !pk && !post, units);
-    const int nchunks = (int)items.size();
-    if (nchunks < 2 && !pk) return kNoPipeline;   // one unit: nothing to overlap (the caller's plain path)
-    // the staging set: every array at the size its largest unit needs
-    size_t cap_in = 0, cap_cells = 0;
-    int chunk = 1;
-    for (const PipeItem& it : items) {
-        cap_in = std::max(cap_in, al((size_t)it.samples * 4 * it.sc));
-        cap_cells = std::max(cap_cells, (size_t)it.cols * R * it.sc);
-        chunk = std::max(chunk, it.sc);
-    }
-    const size_t cap_db = want_db ? al(cap_cells * 4) : 0, cap_rgba = want_rgba ? al(cap_cells * 4) : 0, cap_idx = want_idx ? al(cap_cells) : 0;
-    const size_t set_bytes = cap_in + cap_db + cap_rgba + cap_idx + al(wire_s) * chunk;
-    if ((rc = grow(e, (void**)&e->d_stage, &e->stage_bytes, kPipeSets * set_bytes + 1024))) return rc;
-    if (pk) {
-        if ((rc = grow(e, (void**)&e->d_packscratch, &e->packscratch_bytes, wire_scratch_bytes(C)))) return rc;
-        const size_t hb = (size_t)kPipeSets * chunk * 32;
-        if (hb > e->h_hdr_bytes) {
-            if (e->h_hdr) (void)hipHostFree(e->h_hdr);
-            e->h_hdr = nullptr; e->h_hdr_bytes = 0;
-            HIPCHK(e, hipHostMalloc((void**)&e->h_hdr, hb, hipHostMallocDefault));
-            e->h_hdr_bytes = hb;
-        }
-        pk->offsets[0] = 0;
-    }
-    hipEvent_t* ev_in = e->pipe_ev;
-    hipEvent_t* ev_comp = e->pipe_ev + kPipeSets;
-    hipEvent_t* ev_out = e->pipe_ev + 2 * kPipeSets;
-    struct Set { float* pcm; float* db; uint8_t* rgba; uint8_t* idx; uint8_t* wire; };
-    auto set_of = [&](int b) {
-        char* base = e->d_stage + (size_t)b * set_bytes;
-        Set q;
-        q.pcm = (float*)base; base += cap_in;
-        q.db = cap_db ? (float*)base : nullptr; base += cap_db;
-        q.rgba = cap_rgba ? (uint8_t*)base : nullptr; base += cap_rgba;
-        q.idx = cap_idx ? (uint8_t*)base : nullptr; base += cap_idx;
-        q.wire = wire_s ? (uint8_t*)base : nullptr;
-        return q;
+// the host-buffer entries run emspec_batch_device on each unit of the driver's pipeline (emspec_host.cpp)
+static HostRun batch_run(emspec_engine* e, int n, int hop, int reassign) {
+    return [=](const float* pcm, int sc, int64_t samples, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st) {
+        return emspec_batch_device(e, pcm, sc, samples, n, hop, reassign, db, rgba, index, st);
     };
-    hipError_t herr = hipSuccess;
-    rc = EMSPEC_OK;
-    std::string why;
-    // the D2H stage of unit f (its kernels are enqueued; with pk: wait for them, then the images' sizes are known)
-    auto drain = [&](int f) {
-        const PipeItem& it = items[f];
-        const int b = f % kPipeSets, s0 = it.s0, sc = it.sc;
-        const Set q = set_of(b);
-        if (!pk) {
-            const size_t from = (size_t)it.skip * R, to = ((size_t)s0 * C + (size_t)it.c0) * R, cells = (size_t)it.cn * R * sc;
-            herr = hipStreamWaitEvent(e->stream_out, ev_comp[b], 0);
-            if (herr == hipSuccess && want_db) herr = hipMemcpyAsync(out->db + to, q.db + from, cells * 4, hipMemcpyDeviceToHost, e->stream_out);
-            if (herr == hipSuccess && want_rgba) herr = hipMemcpyAsync(out->rgba + 4 * to, q.rgba + 4 * from, cells * 4, hipMemcpyDeviceToHost, e->stream_out);
-            if (herr == hipSuccess && out->index) herr = hipMemcpyAsync(out->index + to, q.idx + from, cells, hipMemcpyDeviceToHost, e->stream_out);
-        } else {
-            herr = hipEventSynchronize(ev_comp[b]);
-            for (int i = 0; i < sc && herr == hipSuccess && rc == EMSPEC_OK; ++i) {
-                const uint32_t* h = reinterpret_cast<const uint32_t*>(e->h_hdr + ((size_t)b * chunk + i) * 32);
-                const uint64_t hcols = (uint64_t)h[2] | ((uint64_t)h[3] << 32), hpay = (uint64_t)h[4] | ((uint64_t)h[5] << 32);
-                if (h[0] != 0x32574D45u || (int32_t)h[1] != R || hcols != (uint64_t)C || hpay > (uint64_t)col_cells) {
-                    rc = EMSPEC_ERR_HIP; why = "the packed image of a stream carries a bad header"; break;
-                }
-                const int64_t bytes = wire_fixed_bytes(C, R) + (int64_t)((hpay + 15) & ~(uint64_t)15);
-                const int64_t at = pk->offsets[s0 + i];
-                if (at + bytes > pk->capacity) {
-                    rc = EMSPEC_ERR_INVALID_ARG;
-                    why = "wire buffer too small (emspec_wire_bound(columns, rows) per stream always suffices)";
-                    break;
-                }
-                herr = hipMemcpyAsync(pk->wire + at, q.wire + (size_t)i * al(wire_s), (size_t)bytes, hipMemcpyDeviceToHost, e->stream_out);
-                // every image STARTS on a 16-byte boundary: the fixed part (32 + 4 C (1 + R/32) bytes) is a multiple of 4 only, so
-                // up to 12 bytes of slack follow an image (stream s occupies [offsets[s], offsets[s+1]), slack included; the
-                // unpackers take the image's real size from its header)
-                pk->offsets[s0 + i + 1] = (at + bytes + 15) & ~(int64_t)15;
-            }
-        }
-        if (herr == hipSuccess && rc == EMSPEC_OK) herr = hipEventRecord(ev_out[b], e->stream_out);
-    };
-    int drained = 0;
-    for (int ci = 0; ci < nchunks && rc == EMSPEC_OK && herr == hipSuccess; ++ci) {
-        const PipeItem& it = items[ci];
-        const int b = ci % kPipeSets, sc = it.sc;
-        const Set q = set_of(b);
-        // stage 1: samples in (the set's input is free once the kernels of unit ci - kPipeSets are done)
-        if (ci >= kPipeSets) herr = hipStreamWaitEvent(e->stream_in, ev_comp[b], 0);
-        if (herr == hipSuccess)
-            herr = hipMemcpyAsync(q.pcm, pcm + (size_t)it.s0 * L + (size_t)it.first_sample, (size_t)it.samples * 4 * sc, hipMemcpyHostToDevice, e->stream_in);
-        if (herr == hipSuccess) herr = hipEventRecord(ev_in[b], e->stream_in);
-        // stage 2: kernels (the set's outputs are free once unit ci - kPipeSets has been copied out)
-        if (herr == hipSuccess) herr = hipStreamWaitEvent(e->stream, ev_in[b], 0);
-        if (herr == hipSuccess && ci >= kPipeSets) herr = hipStreamWaitEvent(e->stream, ev_out[b], 0);
-        if (herr != hipSuccess) break;
-        rc = emspec_batch_device(e, q.pcm, sc, it.samples, n, hop, reassign, q.db, q.rgba, q.idx, e->stream);
-        if (rc != EMSPEC_OK) break;
-        if (pk) {
-            for (int i = 0; i < sc && herr == hipSuccess; ++i) {
-                uint8_t* w = q.wire + (size_t)i * al(wire_s);
-                herr = launch_wire_pack(q.idx + (size_t)i * col_cells, C, R, w, e->d_packscratch, e->stream);
-                if (herr == hipSuccess) herr = hipMemcpyAsync(e->h_hdr + ((size_t)b * chunk + i) * 32, w, 32, hipMemcpyDeviceToHost, e->stream);
-            }
-        }
-        if (herr == hipSuccess) herr = hipEventRecord(ev_comp[b], e->stream);
-        // stage 3, kPipeLag units behind when the host has to read the sizes first
-        const int lag = pk ? kPipeLag : 0;
-        while (herr == hipSuccess && rc == EMSPEC_OK && drained <= ci - lag) drain(drained++);
-    }
-    while (herr == hipSuccess && rc == EMSPEC_OK && drained < nchunks) drain(drained++);
-    const hipError_t s1 = hipStreamSynchronize(e->stream_in), s2 = hipStreamSynchronize(e->stream), s3 = hipStreamSynchronize(e->stream_out);
-    if (rc != EMSPEC_OK) return why.empty() ? rc : fail(e, rc, why);
-    HIPCHK(e, herr);
-    HIPCHK(e, s1);
-    HIPCHK(e, s2);
-    HIPCHK(e, s3);
-    if (read_kernel_error(true) > 0) return fail(e, EMSPEC_ERR_HIP, "a kernel's bounded wait timed out (protocol error): results invalid");
-    return EMSPEC_OK;
-}
-
-// Host buffers in ORDINARY (pageable) memory.  The runtime serves such copies itself (it pins the pages and streams them: ~45 GB/s
-// one way on this box) but the call returns only when the copy is done, so from one host thread the samples in, the kernels and the
-// columns out run one after the other.  Here the same chunks and staging sets as batch_pipeline, with a second host thread that does
-// nothing but the copies out: in, compute and out overlap as they do from page-locked memory.  Returns kNoThread (not an
-// EMSPEC_ERR_* value) when the thread cannot be started, before anything was done.
-static int batch_pipeline_pageable(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32_t n, int32_t hop, int32_t reassign,
-                                   const emspec_out* out) {
-    int rc;
-    if ((rc = pipe_setup(e))) return rc;
-    const int64_t C = emspec_num_columns(L, n, hop);
-    const int R = e->cfg.rows;
-    const size_t col_cells = (size_t)C * R;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t in_s = (size_t)L * sizeof(float);
-    const bool want_db = out->db != nullptr, want_rgba = out->rgba != nullptr, want_idx = out->index != nullptr;
-    const size_t per_stream = al(in_s) + al(want_db ? col_cells * 4 : 0) + al(want_rgba ? col_cells * 4 : 0) + al(want_idx ? col_cells : 0);
-    const bool post = e->smoothing > 0.0f || e->agc > 0.0f;
-    const int units = pipe_units(e->exact(), n, (int64_t)S * C, (size_t)S * in_s,
-                                 (size_t)S * col_cells * ((want_db ? 4 : 0) + (want_rgba ? 4 : 0) + (want_idx ? 1 : 0)));
-    const std::vector<PipeItem> items = pipe_items(S, L, C, n, hop, latency(n, hop, reassign), per_stream, !post, units);
-    const int nchunks = (int)items.size();
-    if (nchunks < 2) return kNoPipeline;   // one unit: nothing to overlap
-    size_t cap_in = 0, cap_cells = 0;
-    for (const PipeItem& it : items) {
-        cap_in = std::max(cap_in, al((size_t)it.samples * 4 * it.sc));
-        cap_cells = std::max(cap_cells, (size_t)it.cols * R * it.sc);
-    }
-    const size_t cap_db = want_db ? al(cap_cells * 4) : 0, cap_rgba = want_rgba ? al(cap_cells * 4) : 0, cap_idx = want_idx ? al(cap_cells) : 0;
-    const size_t set_bytes = cap_in + cap_db + cap_rgba + cap_idx;
-    if ((rc = grow(e, (void**)&e->d_stage, &e->stage_bytes, kPipeSets * set_bytes + 1024))) return rc;
-    hipEvent_t* ev_in = e->pipe_ev;
-    hipEvent_t* ev_comp = e->pipe_ev + kPipeSets;
-    struct Set { float* pcm; float* db; uint8_t* rgba; uint8_t* idx; };
-    auto set_of = [&](int b) {
-        char* base = e->d_stage + (size_t)b * set_bytes;
-        Set q;
-        q.pcm = (float*)base; base += cap_in;
-        q.db = cap_db ? (float*)base : nullptr; base += cap_db;
-        q.rgba = cap_rgba ? (uint8_t*)base : nullptr; base += cap_rgba;
-        q.idx = cap_idx ? (uint8_t*)base : nullptr;
-        return q;
-    };
-    // where unit f's kept columns go in the caller's arrays / come from in the set: cell offsets and count
-    auto span_of = [&](const PipeItem& it, size_t& from, size_t& to, size_t& cells) {
-        from = (size_t)it.skip * R;
-        to = ((size_t)it.s0 * C + (size_t)it.c0) * R;
-        cells = (size_t)it.cn * R * it.sc;
-    };
-    std::mutex mu;
-    std::condition_variable cv;
-    int launched = 0, drained = 0;      // chunks whose kernels are enqueued / whose columns are in the caller's memory
-    bool stop = false;
-    hipError_t herr_out = hipSuccess;
-    // A caller that allocates its result per call (np.empty, new Uint8Array) hands over pages that were never touched: the runtime's
-    // copy then takes a page fault per 4 KB on its one thread (1 GB of palette indices: 90 ms of a 114 ms call).  kTouchers threads
-    // write one byte into every page of a chunk's destination before the drainer copies the chunk there (every byte of the outputs
-    // is overwritten by the call anyway); on resident pages that costs nothing measurable.
-    constexpr int kTouchers = 3;
-    int touched[kTouchers] = {};
-    auto touch_all = [&](int t) {
-        auto touch = [&](void* base, size_t bytes) {
-            if (!base || !bytes) return;
-            volatile char* p = reinterpret_cast<volatile char*>(base);
-            const size_t lo = bytes * (size_t)t / kTouchers, hi = bytes * (size_t)(t + 1) / kTouchers;
-            for (size_t a = lo; a < hi; a += 4096) p[a] = 0;
-            if (t == kTouchers - 1) p[bytes - 1] = 0;
-        };
-        for (int f = 0; f < nchunks; ++f) {
-            size_t from, to, cells;
-            span_of(items[f], from, to, cells);
-            if (want_db) touch(out->db + to, cells * 4);
-            if (want_rgba) touch(out->rgba + 4 * to, cells * 4);
-            if (want_idx) touch(out->index + to, cells);
-            std::lock_guard<std::mutex> lk(mu);
-            touched[t] = f + 1;
-            cv.notify_all();
-            if (stop) break;
-        }
-    };
-    auto drain_all = [&] {
-        hipError_t r = hipSetDevice(e->device);
-        for (int f = 0; f < nchunks && r == hipSuccess; ++f) {
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] {
-                    bool ready = launched > f;
-                    for (int t = 0; t < kTouchers; ++t) ready = ready && touched[t] > f;
-                    return ready || stop;
-                });
-                if (launched <= f) break;
-                bool ready = true;
-                for (int t = 0; t < kTouchers; ++t) ready = ready && touched[t] > f;
-                if (!ready) break;
-            }
-            const int b = f % kPipeSets;
-            const Set q = set_of(b);
-            size_t from, to, cells;
-            span_of(items[f], from, to, cells);
-            r = hipStreamWaitEvent(e->stream_out, ev_comp[b], 0);
-            if (r == hipSuccess && want_db) r = hipMemcpyAsync(out->db + to, q.db + from, cells * 4, hipMemcpyDeviceToHost, e->stream_out);
-            if (r == hipSuccess && want_rgba) r = hipMemcpyAsync(out->rgba + 4 * to, q.rgba + 4 * from, cells * 4, hipMemcpyDeviceToHost, e->stream_out);
-            if (r == hipSuccess && want_idx) r = hipMemcpyAsync(out->index + to, q.idx + from, cells, hipMemcpyDeviceToHost, e->stream_out);
-            if (r == hipSuccess) r = hipStreamSynchronize(e->stream_out);
-            std::lock_guard<std::mutex> lk(mu);
-            drained = f + 1;
-            cv.notify_all();
-        }
-        std::lock_guard<std::mutex> lk(mu);
-        herr_out = r;
-        stop = true;
-        cv.notify_all();
-    };
-    std::thread drainer, touchers[kTouchers];
-    try {
-        drainer = std::thread(drain_all);
-    } catch (const std::exception&) {   // no thread to be had: the caller falls back to one chunk on its own thread
-        return kNoThread;
-    }
-    for (int t = 0; t < kTouchers; ++t) {
-        try {
-            touchers[t] = std::thread(touch_all, t);
-        } catch (const std::exception&) {   // (its share counts as touched: the runtime takes those faults itself)
-            std::lock_guard<std::mutex> lk(mu);
-            touched[t] = nchunks;
-            cv.notify_all();
-        }
-    }
-    hipError_t herr = hipSuccess;
-    rc = EMSPEC_OK;
-    for (int ci = 0; ci < nchunks && rc == EMSPEC_OK && herr == hipSuccess; ++ci) {
-        const PipeItem& it = items[ci];
-        const int b = ci % kPipeSets, sc = it.sc;
-        const Set q = set_of(b);
-        if (ci >= kPipeSets) {   // the set is free once unit ci - kPipeSets has left it
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return drained > ci - kPipeSets || stop; });
-            if (drained <= ci - kPipeSets) break;
-        }
-        herr = hipMemcpyAsync(q.pcm, pcm + (size_t)it.s0 * L + (size_t)it.first_sample, (size_t)it.samples * 4 * sc, hipMemcpyHostToDevice, e->stream_in);
-        if (herr == hipSuccess) herr = hipEventRecord(ev_in[b], e->stream_in);
-        if (herr == hipSuccess) herr = hipStreamWaitEvent(e->stream, ev_in[b], 0);
-        if (herr != hipSuccess) break;
-        rc = emspec_batch_device(e, q.pcm, sc, it.samples, n, hop, reassign, q.db, q.rgba, q.idx, e->stream);
-        if (rc != EMSPEC_OK) break;
-        herr = hipEventRecord(ev_comp[b], e->stream);
-        if (herr != hipSuccess) break;
-        std::lock_guard<std::mutex> lk(mu);
-        launched = ci + 1;
-        cv.notify_all();
-    }
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (launched < nchunks) stop = true;   // an error: the drainer finishes what was launched and leaves
-        cv.notify_all();
-    }
-    drainer.join();
-    for (auto& th : touchers)
-        if (th.joinable()) th.join();
-    const hipError_t s1 = hipStreamSynchronize(e->stream_in), s2 = hipStreamSynchronize(e->stream), s3 = hipStreamSynchronize(e->stream_out);
-    if (rc != EMSPEC_OK) return rc;
-    HIPCHK(e, herr);
-    HIPCHK(e, herr_out);
-    HIPCHK(e, s1);
-    HIPCHK(e, s2);
-    HIPCHK(e, s3);
-    if (read_kernel_error(true) > 0) return fail(e, EMSPEC_ERR_HIP, "a kernel's bounded wait timed out (protocol error): results invalid");
-    return EMSPEC_OK;
-}
-
-bool emspec::host_pinned(const void* p) {
-    if (!p) return true;
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return at.type == hipMemoryTypeHost;
 }
 
 extern "C" {
@@ -1285,50 +897,10 @@ int emspec_batch(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32
     if (S < 1 || L < n) return fail(e, EMSPEC_ERR_INVALID_ARG, "need at least one stream of at least fft-size samples");
     HIPCHK(e, hipSetDevice(e->device));
     if (!out->db && !out->rgba && !out->index) return EMSPEC_OK;
-    // Page-locked buffers (emspec_host_alloc): every copy is asynchronous, one host thread drives the three stages.  Pageable
-    // buffers: the runtime's copies block the calling thread, so a second thread takes the copies out (round 6: 2.15e7 -> 4.3e7
-    // columns/s on the bench shape, the page-locked rate; pinning the caller's buffers per call instead costs more than it
-    // saves: 49 ms vs 27 ms for 670 MB).  With fewer than sixteen streams the units are runs of a stream's columns (pipe_items);
-    // a batch too short for two units (one stream of < 32,768 columns) goes the plain way: one copy in, the kernels, one copy out.
-    if (host_pinned(pcm) && host_pinned(out->db) && host_pinned(out->rgba) && host_pinned(out->index))
-        rc = batch_pipeline(e, pcm, S, L, n, hop, reassign, out, nullptr);
-    else
-        rc = batch_pipeline_pageable(e, pcm, S, L, n, hop, reassign, out);
-    if (rc != kNoThread && rc != kNoPipeline) return rc;
-    const int64_t C = emspec_num_columns(L, n, hop);
-    const size_t col_cells = (size_t)C * e->cfg.rows;
-    const size_t in_s = (size_t)L * sizeof(float);
-    const size_t db_s = out->db ? col_cells * 4 : 0, rgba_s = out->rgba ? col_cells * 4 : 0, idx_s = out->index ? col_cells : 0;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    // one stream, chunks of streams one after the other so that the staging stays bounded (4 GiB) whatever S is
-    const size_t per_stream = al(in_s) + al(db_s) + al(rgba_s) + al(idx_s);
-    int chunk = (int)(((size_t)4 << 30) / per_stream);
-    chunk = chunk < 1 ? 1 : (chunk > S ? S : chunk);
-    if ((rc = grow(e, (void**)&e->d_stage, &e->stage_bytes, (size_t)chunk * per_stream + 1024))) return rc;
-    hipStream_t st = e->stream;
-    hipError_t herr = hipSuccess;
-    for (int s0 = 0; s0 < S && rc == EMSPEC_OK && herr == hipSuccess; s0 += chunk) {
-        const int sc = (S - s0 < chunk) ? S - s0 : chunk;
-        char* base = e->d_stage;
-        float* d_pcm = (float*)base; base += al(in_s) * chunk;
-        float* d_db = db_s ? (float*)base : nullptr; base += al(db_s) * chunk;
-        uint8_t* d_rgba = rgba_s ? (uint8_t*)base : nullptr; base += al(rgba_s) * chunk;
-        uint8_t* d_idx = idx_s ? (uint8_t*)base : nullptr;
-        herr = hipMemcpyAsync(d_pcm, pcm + (size_t)s0 * L, in_s * sc, hipMemcpyHostToDevice, st);
-        if (herr != hipSuccess) break;
-        rc = emspec_batch_device(e, d_pcm, sc, L, n, hop, reassign, d_db, d_rgba, d_idx, st);
-        if (rc != EMSPEC_OK) break;
-        if (db_s) herr = hipMemcpyAsync(out->db + (size_t)s0 * col_cells, d_db, db_s * sc, hipMemcpyDeviceToHost, st);
-        if (herr == hipSuccess && rgba_s) herr = hipMemcpyAsync(out->rgba + 4 * (size_t)s0 * col_cells, d_rgba, rgba_s * sc, hipMemcpyDeviceToHost, st);
-        if (herr == hipSuccess && idx_s) herr = hipMemcpyAsync(out->index + (size_t)s0 * col_cells, d_idx, idx_s * sc, hipMemcpyDeviceToHost, st);
-        if (herr == hipSuccess && s0 + chunk < S) herr = hipStreamSynchronize(st);   // the next chunk reuses the staging
-    }
-    const hipError_t s1 = hipStreamSynchronize(st);
-    if (rc != EMSPEC_OK) return rc;
-    HIPCHK(e, herr);
-    HIPCHK(e, s1);
-    if (read_kernel_error(true) > 0) return fail(e, EMSPEC_ERR_HIP, "a kernel's bounded wait timed out (protocol error): results invalid");
-    return EMSPEC_OK;
+    // With fewer than sixteen streams the units are runs of a stream's columns (pipe_items) - but the display post-process walks
+    // a stream in time order: whole streams there
+    const bool post = e->smoothing > 0.0f || e->agc > 0.0f;
+    return host_batch(e, pcm, S, L, n, hop, post ? -1 : latency(n, hop, reassign), 1, out, nullptr, batch_run(e, n, hop, reassign));
 }
 
 int emspec_batch_packed(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32_t n, int32_t hop, int32_t reassign,
@@ -1342,7 +914,8 @@ int emspec_batch_packed(emspec_engine* e, const float* pcm, int32_t S, int64_t L
     if (e->cfg.rows % 4) return fail(e, EMSPEC_ERR_INVALID_ARG, "the wire image needs rows % 4 == 0");
     HIPCHK(e, hipSetDevice(e->device));
     const PackedOut pk{wire, wire_capacity, offsets};
-    return batch_pipeline(e, pcm, S, L, n, hop, reassign, nullptr, &pk);
+    // (an image is one stream's whole run of columns: whole streams)
+    return host_batch(e, pcm, S, L, n, hop, -1, 1, nullptr, &pk, batch_run(e, n, hop, reassign));
 }
 
 int emspec_wire_unpack_host(const uint8_t* wire, int64_t wire_bytes, int64_t columns, int32_t rows, uint8_t* index_out) {

@@ -7,6 +7,7 @@
 #pragma GCC visibility pop
 #include "emspec_launch.h"
 
+#include <functional>
 #include <map>
 #include <string>
 #include <tuple>
@@ -67,6 +68,15 @@ ExactPlanDev exact_plan_dev(const emspec_engine* e, const Plan& p, int hop, int 
 ExactDbMap exact_db_map(const emspec_engine* e, int n, const ExactPlanDev& pd);
 DbMap db_map(const emspec_engine* e, int n);
 bool host_pinned(const void* p);   // p is null or page-locked host memory the device can address
+// emspec_host.cpp: the host-buffer path of emspec_batch, emspec_batch_packed and emspec_batch_multires.  S streams of L host
+// samples -> the columns of emspec_num_columns(L, n, hop) into host arrays (out), or one wire image per stream (pk), through
+// staging sets on the device; `run` computes one unit (sc streams of `samples` samples, staged) on the compute stream.  Units
+// are runs of a stream's columns with halo_D columns on either side, or whole streams when halo_D is -1; a unit of whole streams
+// holds at least min_streams of them (or all S).
+struct PackedOut { uint8_t* wire; int64_t capacity; int64_t* offsets; };
+using HostRun = std::function<int(const float* pcm, int sc, int64_t samples, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st)>;
+int host_batch(emspec_engine* e, const float* pcm, int S, int64_t L, int n, int hop, int halo_D, int min_streams,
+               const emspec_out* out, const PackedOut* pk, const HostRun& run);
 void live_destroy(emspec_engine* e);   // emspec_live.cpp: called by emspec_destroy
 void live_reset(emspec_engine* e);     // drops the live session's stream state (emspec_reset); buffers are kept
 bool live_pending(const emspec_engine* e);   // some stream of either session has fed frames whose columns were not emitted yet
@@ -76,7 +86,7 @@ struct emspec_engine {
     emspec_config cfg{};
     int device = 0;
     hipStream_t stream = nullptr;
-    // host-buffer batch pipeline (emspec_batch / emspec_batch_packed): H2D and D2H copy streams beside the compute stream,
+    // host-buffer pipeline (emspec_host.cpp): H2D and D2H copy streams beside the compute stream,
     // [in | computed | out] events per staging set, the packed images' headers in pinned host memory
     hipStream_t stream_in = nullptr, stream_out = nullptr;
     hipEvent_t pipe_ev[9] = {};

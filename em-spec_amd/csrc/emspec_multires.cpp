@@ -103,7 +103,8 @@ int emspec_batch_multires_device(emspec_engine* e, const float* pcm_dev, int32_t
                         (hipStream_t)hip_stream);
 }
 
-// host buffers: copy in, run, copy out, in chunks of streams (staging bounded at 4 GiB, like emspec_batch's plain path)
+// host buffers: the host-buffer pipeline of emspec_batch (emspec_host.cpp) over whole streams - the two bands' halos differ -
+// of at least four per unit (16 streams x 2^22 samples, index out, FAST: one stream per unit 26.3 ms, two 20.9, four 19.1)
 int emspec_batch_multires(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32_t n_low, int32_t n_high, int32_t hop,
                           int32_t split_row, int32_t reassign, const emspec_out* out) {
     if (!e || !pcm || !out) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument");
@@ -111,39 +112,10 @@ int emspec_batch_multires(emspec_engine* e, const float* pcm, int32_t S, int64_t
     if (rc) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     if (!out->db && !out->rgba && !out->index) return EMSPEC_OK;
-    const int64_t C = emspec_num_columns(L, n_low, hop);
-    const size_t col_cells = (size_t)C * e->cfg.rows;
-    const size_t in_s = (size_t)L * sizeof(float);
-    const size_t db_s = out->db ? col_cells * 4 : 0, rgba_s = out->rgba ? col_cells * 4 : 0, idx_s = out->index ? col_cells : 0;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t per_stream = al(in_s) + al(db_s) + al(rgba_s) + al(idx_s);
-    int chunk = (int)(((size_t)4 << 30) / per_stream);
-    chunk = chunk < 1 ? 1 : (chunk > S ? S : chunk);
-    if ((rc = grow(e, (void**)&e->d_stage, &e->stage_bytes, (size_t)chunk * per_stream + 1024))) return rc;
-    hipStream_t st = e->stream;
-    hipError_t herr = hipSuccess;
-    for (int s0 = 0; s0 < S && rc == EMSPEC_OK && herr == hipSuccess; s0 += chunk) {
-        const int sc = (S - s0 < chunk) ? S - s0 : chunk;
-        char* base = e->d_stage;
-        float* d_pcm = (float*)base; base += al(in_s) * chunk;
-        float* d_db = db_s ? (float*)base : nullptr; base += al(db_s) * chunk;
-        uint8_t* d_rgba = rgba_s ? (uint8_t*)base : nullptr; base += al(rgba_s) * chunk;
-        uint8_t* d_idx = idx_s ? (uint8_t*)base : nullptr;
-        herr = hipMemcpyAsync(d_pcm, pcm + (size_t)s0 * L, in_s * sc, hipMemcpyHostToDevice, st);
-        if (herr != hipSuccess) break;
-        rc = multires_run(e, d_pcm, sc, L, n_low, n_high, hop, split_row, reassign, d_db, d_rgba, d_idx, st);
-        if (rc != EMSPEC_OK) break;
-        if (db_s) herr = hipMemcpyAsync(out->db + (size_t)s0 * col_cells, d_db, db_s * sc, hipMemcpyDeviceToHost, st);
-        if (herr == hipSuccess && rgba_s) herr = hipMemcpyAsync(out->rgba + 4 * (size_t)s0 * col_cells, d_rgba, rgba_s * sc, hipMemcpyDeviceToHost, st);
-        if (herr == hipSuccess && idx_s) herr = hipMemcpyAsync(out->index + (size_t)s0 * col_cells, d_idx, idx_s * sc, hipMemcpyDeviceToHost, st);
-        if (herr == hipSuccess && s0 + chunk < S) herr = hipStreamSynchronize(st);   // the next chunk reuses the staging
-    }
-    const hipError_t s1 = hipStreamSynchronize(st);
-    if (rc != EMSPEC_OK) return rc;
-    HIPCHK(e, herr);
-    HIPCHK(e, s1);
-    if (read_kernel_error(true) > 0) return fail(e, EMSPEC_ERR_HIP, "a kernel's bounded wait timed out (protocol error): results invalid");
-    return EMSPEC_OK;
+    const auto run = [=](const float* d_pcm, int sc, int64_t samples, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st) {
+        return multires_run(e, d_pcm, sc, samples, n_low, n_high, hop, split_row, reassign, db, rgba, index, st);
+    };
+    return host_batch(e, pcm, S, L, n_low, hop, -1, 4, out, nullptr, run);
 }
 
 }  // extern "C"

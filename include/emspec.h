@@ -290,8 +290,8 @@ int32_t emspec_live_streams(const emspec_engine* e);
  * columns/s on the bench shape), a third of it into a fresh array.  With fewer than sixteen streams (one long recording) the
  * pipeline's units are runs of >= 16,384 columns of a stream, each computed from the frames that reach it - the same columns
  * (EXACT mode: the same bytes) as in one piece; a batch too short for two units takes one copy in, the kernels, one copy out.
- * With the display post-process on, units are whole streams.  Serves: the renderer-side batched computeColumns of the N-API
- * addon (em-spec_amd/js/index.js).
+ * With the display post-process on, units are whole streams.  On an error return the outputs are unspecified (partly written
+ * or page-touched).  Serves: the renderer-side batched computeColumns of the N-API addon (em-spec_amd/js/index.js).
  */
 int emspec_batch(emspec_engine* e, const float* pcm, int32_t S, int64_t L,
                  int32_t n, int32_t hop, int32_t reassign, const emspec_out* out);
@@ -495,7 +495,8 @@ const char* emspec_device_arch(const emspec_engine* e);
  * emspec_multires_columns: the column count (= emspec_num_columns(L, n_low, hop)), 0 when L < n_low, -1 for a shape
  *   that is not accepted.
  * emspec_batch_multires: host buffers, page-locked or not ([S][L] in, [S][columns][rows] (+[4]) out, any output NULL):
- *   copies in, runs, copies out, in chunks of streams; returns when the outputs are written.
+ *   runs the same pipeline as emspec_batch (units of whole streams), helper threads included; returns when the outputs are
+ *   written.
  * emspec_batch_multires_device: device buffers, enqueued on hip_stream (NULL = the default stream); does not synchronise.
  * Both bands' raw dB live in an engine workspace bounded like the records path's (streams are processed in chunks).
  * Single-resolution results on the same engine are not affected by a multi-resolution call.

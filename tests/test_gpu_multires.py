@@ -95,6 +95,41 @@ def test_exact_equals_the_engines_own_stitch_host_pinned_and_device():
             assert _same(t.cpu().numpy(), want[k]), ("device", k)
 
 
+def test_host_pipeline_with_display_postprocess_equals_the_device_entry():
+    """S = 8, L = 2^20, EXACT, display post-process on: the host entry cuts this batch into two units of four whole streams
+    (the post-process walks each stream on its own), from pageable arrays (helper threads) and from page-locked ones; both
+    give the bytes of the device entry's one launch over all eight streams."""
+    n_low, n_high, hop, S, L = 16384, 4096, 256, 8, 1 << 20
+    pcm = synth.streams(S, L)
+    with emspec.Engine(mode=emspec.MODE_EXACT) as e:
+        split = e.split_row_for_hz(250.0)
+        e.set_display(0.6, 0.8)
+        Cm = emspec.multires_columns(L, n_low, n_high, hop)
+        x = torch.from_numpy(pcm).cuda()
+        dev = {"db": torch.empty((S, Cm, e.rows), dtype=torch.float32, device="cuda"),
+               "rgba": torch.empty((S, Cm, e.rows, 4), dtype=torch.uint8, device="cuda"),
+               "index": torch.empty((S, Cm, e.rows), dtype=torch.uint8, device="cuda")}
+        e.batch_multires_device(x, n_low, n_high, hop, split, True, **dev)
+        torch.cuda.synchronize()
+        e.device_status()
+        want = {k: t.cpu().numpy() for k, t in dev.items()}
+        got = e.batch_multires(pcm, n_low, n_high, hop, split, True, want=WANT)
+        for k in WANT:
+            assert _same(got[k], want[k]), ("pageable", k)
+        pin = {"pcm": emspec.PinnedArray((S, L), np.float32), "db": emspec.PinnedArray((S, Cm, e.rows), np.float32),
+               "rgba": emspec.PinnedArray((S, Cm, e.rows, 4), np.uint8), "index": emspec.PinnedArray((S, Cm, e.rows), np.uint8)}
+        try:
+            pin["pcm"].array[:] = pcm
+            out = emspec.Out(pin["db"].array.ctypes.data, pin["rgba"].array.ctypes.data, pin["index"].array.ctypes.data)
+            e._chk(e._lib.emspec_batch_multires(e._h, C.c_void_p(pin["pcm"].array.ctypes.data), S, L, n_low, n_high, hop,
+                                                split, 1, C.byref(out)))
+            for k in WANT:
+                assert _same(pin[k].array, want[k]), ("pinned", k)
+        finally:
+            for p in pin.values():
+                p.close()
+
+
 @pytest.mark.parametrize("n_low,n_high,hop,L", [(16384, 4096, 256, 1 << 17), (8192, 2048, 128, 1 << 17),
                                                 (16384, 1024, 512, 1 << 18)])
 @pytest.mark.parametrize("boost", [None, BOOST], ids=["log", "warped"])

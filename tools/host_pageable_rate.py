@@ -2,8 +2,7 @@
 """emspec_batch / emspec_batch_packed from ORDINARY (pageable) host memory - what `new Float32Array` in Node or a numpy array
 hands over - on the bench shape (64 streams x 2^22 samples, FFT 4096, hop 256, reassignment ON), beside the same calls from
 page-locked memory.  Checks that both give the same bytes.
-   python tools/host_pageable_rate.py [libemspec.so] [--exact]
-(diagnostic build: EMSPEC_COPY_THREADS=k sets the number of copying threads)"""
+   python tools/host_pageable_rate.py [libemspec.so] [--exact]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "em-spec_amd")]

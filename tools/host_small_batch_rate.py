@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """emspec_batch from host buffers on SMALL and MID-SIZE batches (FFT 4096 / hop 256, palette index out; median of 30 calls): what a
 call costs when the copies and kernels are short beside the ~0.2 ms the host spends submitting a unit of the pipeline.  The number of
-units follows the batch (pipe_units, emspec_api.cpp) since late round 6; before: one unit per stream up to sixteen.
+units follows the batch (pipe_units, emspec_host.cpp) since late round 6; before: one unit per stream up to sixteen.
    python tools/host_small_batch_rate.py [libemspec.so] [--exact]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
