@@ -33,6 +33,12 @@ struct Plan {
 // S streams, each with its own sample position, sample ring and pending-column ring, advanced together by ONE launch per call.
 struct LiveState {
     int S = 0, n = 0, hop = 0, reassign = -1, D = 0;
+    // multi-resolution session (emspec_columns_multires / emspec_push_samples_multires): n / D / slots / d_cells
+    // are the long band's (rows [0, split) at n_low); the short band (rows [split, R) at n_high) has its own column ring,
+    // indexed by the emitted column.  Its frame count follows the long band's: 0 while fed is 0, fed + 2 shift after.
+    int n_high = 0, split = 0, shift = 0, D_high = 0;   // n_high == 0: a single-resolution session
+    int slots_high = 0;       // mmax + shift + D + D_high
+    void* d_cells_high = nullptr; size_t cells_high_bytes = 0;   // [S][slots_high][R - split]
     int form = 0;             // 0 none, 1 per-frame (emspec_columns), 2 per-sample-block (emspec_push_samples_multi)
     int slots = 0;            // column-ring slots per stream: 2 D + mmax
     int mmax = 0;             // frames per stream and launch, at most
@@ -42,7 +48,7 @@ struct LiveState {
     std::vector<int> pend;    // per stream: samples waiting in the staging block
     void* d_cells = nullptr; size_t cells_bytes = 0;    // [S][slots][rows] float32 (FAST) / u64 (EXACT)
     float* d_sring = nullptr; size_t sring_bytes = 0;   // [S][ring_mask + 1]
-    unsigned* d_done = nullptr; size_t done_bytes = 0;  // [S] arrival counters
+    unsigned* d_done = nullptr; size_t done_bytes = 0;  // [S] arrival counters (a multi-resolution session: [2][S], one set per band)
     float* d_raw = nullptr; size_t raw_bytes = 0;       // display post-process: raw dB [S][mmax][rows]
     float* d_pstate = nullptr; size_t pstate_bytes = 0; // display post-process: [S][rows + 4] (AGC level, initialised, -, -, previous column)
     // page-locked, device-visible host buffers: descriptors [S], staging samples [S][cap], staging outputs [S][mmax][rows]
@@ -77,6 +83,9 @@ struct PackedOut { uint8_t* wire; int64_t capacity; int64_t* offsets; };
 using HostRun = std::function<int(const float* pcm, int sc, int64_t samples, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st)>;
 int host_batch(emspec_engine* e, const float* pcm, int S, int64_t L, int n, int hop, int halo_D, int min_streams,
                const emspec_out* out, const PackedOut* pk, const HostRun& run);
+// emspec_multires.cpp: what the multi-resolution batch and the multi-resolution live session accept
+const char* multires_shape_error(int n_low, int n_high, int hop);   // null, or the rule the shape breaks
+int multires_check(emspec_engine* e, int32_t S, int32_t n_low, int32_t n_high, int32_t hop, int32_t split_row);
 void live_destroy(emspec_engine* e);   // emspec_live.cpp: called by emspec_destroy
 void live_reset(emspec_engine* e);     // drops the live session's stream state (emspec_reset); buffers are kept
 bool live_pending(const emspec_engine* e);   // some stream of either session has fed frames whose columns were not emitted yet

@@ -32,6 +32,15 @@ struct LiveSinks {
     float* out_db = nullptr;               // [S][out_cols][rows], or null
     uint32_t* out_rgba = nullptr;          // [S][out_cols][rows] RGBA8, or null
     int out_cols = 0;
+    // band geometry (multi-resolution live session; a single-resolution launch passes 0 / rows / 0 / 0 / 0):
+    // the launch's plan serves rows [row0, row0 + plan rows) of an output column of out_rows rows, and its ring is indexed by
+    // the EMITTED column: frame j of the band sits on column j - col_shift, and the band runs frame_shift frames ahead of the
+    // descriptors' (the long band's) frame count - frames 0 .. frame_shift all at once on a stream's first frame
+    int row0 = 0, out_rows = 0;
+    int frame_shift = 0;                   // 2 shift = (n_low - n_high) / hop for the short band
+    int col_shift = 0;                     // shift for the short band
+    int lat_extra = 0;                     // latency of the emitted column - the plan's own D (the short band: D_low - D_high)
+    int no_ingest = 0;                     // the other band's launch moves the new samples into the sample ring
     int empty_col = 0;                     // per-frame form: a frame that completes no column yet emits the empty column
     int defer_finalize = 0;                // the frame kernel only scatters; live_finalize_kernel (one workgroup per column) follows
     const uint32_t* lut = nullptr;

@@ -1,5 +1,7 @@
 // emspec_live.cpp — the streaming calls behind the C ABI (include/emspec.h): the live multi-stream session (emspec_columns,
-// emspec_columns_flush, emspec_push_samples_multi, emspec_push_columns_multi, emspec_reset_stream, emspec_live_streams) and,
+// emspec_columns_flush, emspec_push_samples_multi, emspec_push_columns_multi, emspec_reset_stream, emspec_live_streams; its
+// multi-resolution form emspec_columns_multires, emspec_push_samples_multires, emspec_push_columns_multires: two bands of the
+// row table, each with its own fft size, frame launch and column ring, one output column - DESIGN.md §3.8) and,
 // since round 6 on the same machinery with one stream, the renderer's own calls: emspec_column (= computeSpectrogramColumn),
 // emspec_column_flush, emspec_push_samples, emspec_push_columns.  Two independent sessions per engine: e->live and e->one.
 //
@@ -48,13 +50,21 @@ void* device_view(const void* p) {
 
 void live_forget(LiveState& lv) {
     lv.S = 0; lv.n = 0; lv.hop = 0; lv.reassign = -1; lv.D = 0; lv.form = 0; lv.slots = 0; lv.mmax = 0; lv.cap = 0; lv.ring_mask = 0;
+    lv.n_high = 0; lv.split = 0; lv.shift = 0; lv.D_high = 0; lv.slots_high = 0;
     lv.fed.clear(); lv.emitted.clear(); lv.seen.clear(); lv.newbase.clear(); lv.pend.clear();
 }
 
-// first call of a session: every allocation, then the state
-int live_open(emspec_engine* e, LiveState& lv, int S, int n, int hop, int reassign, int form) {
+// first call of a session: every allocation, then the state.  n_high != 0: a multi-resolution session (n = n_low; rows below
+// `split` from n, the rest from n_high).
+int live_open(emspec_engine* e, LiveState& lv, int S, int n, int hop, int reassign, int form, int n_high = 0, int split = 0) {
     const int R = e->cfg.rows;
     const int D = latency(n, hop, reassign);
+    const int Rl = n_high ? split : R;   // rows of the (long) band that d_cells holds
+    // The short band runs 2 shift frames ahead and its ring is indexed by the emitted column (its own column - shift).  A call
+    // that feeds long frames j .. j + m - 1 finds emitted columns >= j - D unfinalised, and its short frames, the last of them
+    // frame j + m - 1 + 2 shift = emitted column j + m - 1 + shift, add up to D_high columns further: m + shift + D + D_high
+    // columns are live at once (reassign on: D = D_high + shift, i.e. m + 2 shift + 2 D_high).
+    const int shift = n_high ? (n - n_high) / (2 * hop) : 0, D_high = n_high ? latency(n_high, hop, reassign) : 0;
     // (a staging block of at most 2^17 samples per stream: at a large hop fewer frames per launch instead of megabytes pinned)
     const int mmax = form == 1 ? 1 : std::max(1, std::min(live_frames_per_launch(S), (1 << 17) / hop));
     const int slots = 2 * D + mmax;
@@ -63,27 +73,37 @@ int live_open(emspec_engine* e, LiveState& lv, int S, int n, int hop, int reassi
     while (ring < n + cap) ring <<= 1;
     const size_t cellb = e->exact() ? 8 : 4;
     int rc;
-    if ((rc = grow(e, &lv.d_cells, &lv.cells_bytes, (size_t)S * slots * R * cellb))) return rc;
+    const int slots_high = n_high ? mmax + shift + D + D_high : 0;
+    if ((rc = grow(e, &lv.d_cells, &lv.cells_bytes, (size_t)S * slots * Rl * cellb))) return rc;
+    if (n_high && (rc = grow(e, &lv.d_cells_high, &lv.cells_high_bytes, (size_t)S * slots_high * (R - split) * cellb))) return rc;
     if (form == 2 && (rc = grow(e, (void**)&lv.d_sring, &lv.sring_bytes, (size_t)S * ring * 4))) return rc;
-    if ((rc = grow(e, (void**)&lv.d_done, &lv.done_bytes, (size_t)S * 4))) return rc;
+    if ((rc = grow(e, (void**)&lv.d_done, &lv.done_bytes, (size_t)S * 4 * (n_high ? 2 : 1)))) return rc;
     if ((rc = pinned_grow(e, &lv.h_desc, &lv.desc_bytes, (size_t)S * sizeof(LiveStream)))) return rc;
     if (form == 2 && (rc = pinned_grow(e, (void**)&lv.h_fresh, &lv.fresh_bytes, (size_t)S * cap * 4))) return rc;
-    HIPCHK(e, hipMemsetAsync(lv.d_cells, 0, (size_t)S * slots * R * cellb, e->stream));
-    HIPCHK(e, hipMemsetAsync(lv.d_done, 0, (size_t)S * 4, e->stream));
+    HIPCHK(e, hipMemsetAsync(lv.d_cells, 0, (size_t)S * slots * Rl * cellb, e->stream));
+    if (n_high) HIPCHK(e, hipMemsetAsync(lv.d_cells_high, 0, (size_t)S * slots_high * (R - split) * cellb, e->stream));
+    HIPCHK(e, hipMemsetAsync(lv.d_done, 0, (size_t)S * 4 * (n_high ? 2 : 1), e->stream));
     if (lv.d_pstate) HIPCHK(e, hipMemsetAsync(lv.d_pstate, 0, lv.pstate_bytes, e->stream));
     lv.S = S; lv.n = n; lv.hop = hop; lv.reassign = reassign; lv.D = D; lv.form = form; lv.slots = slots; lv.mmax = mmax;
     lv.cap = cap; lv.ring_mask = ring - 1;
+    lv.n_high = n_high; lv.split = n_high ? split : 0; lv.shift = shift; lv.D_high = D_high; lv.slots_high = slots_high;
     lv.fed.assign(S, 0); lv.emitted.assign(S, 0); lv.seen.assign(S, 0); lv.newbase.assign(S, 0); lv.pend.assign(S, 0);
     return EMSPEC_OK;
 }
 
-int live_check(emspec_engine* e, const LiveState& lv, int S, int n, int hop, int reassign, int rows, int form) {
-    int rc = check_shape(e, n, hop);
+int live_check(emspec_engine* e, const LiveState& lv, int S, int n, int hop, int reassign, int rows, int form, int n_high = 0,
+               int split = 0) {
+    int rc = n_high ? multires_check(e, S, n, n_high, hop, split) : check_shape(e, n, hop);
     if (rc) return rc;
     if (rows != e->cfg.rows) return fail(e, EMSPEC_ERR_INVALID_ARG, "rows does not match the engine configuration");
     if (S < 1 || S > 65535) return fail(e, EMSPEC_ERR_INVALID_ARG, "streams must be in 1..65535");
-    if (lv.form != 0 && (S != lv.S || n != lv.n || hop != lv.hop || reassign != lv.reassign || form != lv.form))
-        return fail(e, EMSPEC_ERR_STATE, "streams / fft size / hop / reassign / feeding mode changed mid-stream; call emspec_reset() first");
+    if (lv.form != 0 && (n_high != 0) != (lv.n_high != 0))
+        return fail(e, EMSPEC_ERR_STATE, lv.n_high ? "the live session is a multi-resolution one (emspec_columns_multires / emspec_push_samples_multires); call emspec_reset() first"
+                                                   : "the live session is a single-resolution one; call emspec_reset() before a multi-resolution call");
+    if (lv.form != 0 && (S != lv.S || n != lv.n || hop != lv.hop || reassign != lv.reassign || form != lv.form || n_high != lv.n_high ||
+                         split != lv.split))
+        return fail(e, EMSPEC_ERR_STATE, n_high ? "streams / fft sizes / hop / split row / reassign / feeding mode changed mid-stream; call emspec_reset() first"
+                                                : "streams / fft size / hop / reassign / feeding mode changed mid-stream; call emspec_reset() first");
     // A flush emits columns that later frames would still have added to: the stream is at its end.  Feeding it again would emit
     // those columns a second time, holding only the new frames' energy.
     for (int s = 0; s < lv.S; ++s)
@@ -111,9 +131,8 @@ int live_post_buffers(emspec_engine* e, LiveState& lv) {
 // caller's max_columns may be far larger than what a call completes.
 int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fresh_stride, int mlaunch, bool flush, float* dst_db,
                 uint8_t* dst_rgba, int out_cols, int raw_cols, bool empty_col) {
-    Plan* p;
     int rc;
-    if ((rc = get_plan(e, lv.n, &p))) return rc;
+    const int R = e->cfg.rows;
     const bool post = e->smoothing > 0.0f || e->agc > 0.0f;
     if (post && (rc = live_post_buffers(e, lv))) return rc;
     LiveSinks ls;
@@ -124,14 +143,17 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
     ls.ring_mask = lv.ring_mask;
     ls.done = lv.d_done;
     ls.out_cols = out_cols;
+    ls.out_rows = R;
     ls.empty_col = empty_col ? 1 : 0;
     ls.lut = reinterpret_cast<const uint32_t*>(e->d_lut);
+    bool priming = false;   // multi-resolution session: some stream's first frame, i.e. its short band's first 2 shift + 1
     {   // every stream in the same state: the descriptor goes into the kernel arguments
         const LiveStream* dsc = reinterpret_cast<const LiveStream*>(lv.h_desc);
         bool same = true;
         for (int s = 1; s < lv.S && same; ++s) same = std::memcmp(&dsc[s], &dsc[0], sizeof(LiveStream)) == 0;
         ls.uniform = same ? 1 : 0;
         ls.uni = dsc[0];
+        for (int s = 0; s < lv.S && !priming; ++s) priming = dsc[s].j0 == 0 && dsc[s].frames > 0;
     }
 #ifdef EMSPEC_DIAG
     ls.stamps = lv.stamps;
@@ -139,8 +161,8 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
     // with the post-process the frame kernel's columns are raw dB on the device, laid out like the destination
     if (post) {
         raw_cols = std::max(1, std::min(raw_cols, out_cols));
-        if ((size_t)lv.S * raw_cols * e->cfg.rows * 4 > lv.raw_bytes &&
-            (rc = grow(e, (void**)&lv.d_raw, &lv.raw_bytes, (size_t)lv.S * raw_cols * e->cfg.rows * 4))) return rc;
+        if ((size_t)lv.S * raw_cols * R * 4 > lv.raw_bytes &&
+            (rc = grow(e, (void**)&lv.d_raw, &lv.raw_bytes, (size_t)lv.S * raw_cols * R * 4))) return rc;
         ls.out_db = lv.d_raw;
         ls.out_rgba = nullptr;
         ls.out_cols = raw_cols;
@@ -150,37 +172,70 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
     }
     const DbMap m = db_map(e, lv.n);
     const bool exact = e->exact();
-    const ExactPlanDev xpd = exact ? exact_plan_dev(e, *p, lv.hop, lv.reassign) : ExactPlanDev{};
-    const ExactDbMap xm = exact ? exact_db_map(e, lv.n, xpd) : ExactDbMap{};
-    // many columns per stream: the frame kernel only scatters and a second kernel finalises them, one workgroup per column
-    // (inline they are one workgroup's serial round trips to the memory side, ~2 us per column)
-    // ... and so does a small transform: its workgroup has n / 16 (EXACT: n / 8) threads, and 1024 rows through 16 threads
-    // are 8 serial batches of round trips (emspec_column at N = 256: 32.6 us per call against 25.7 at N = 4096)
-    const bool defer = !flush && (mlaunch > kInlineFinalize || lv.n < 2048);
-    ls.defer_finalize = defer ? 1 : 0;
-    if (flush) {
-        HIPCHK(e, launch_live_flush(exact, ls, lv.d_cells, lv.slots, e->cfg.rows, lv.D, m, xm, lv.S, 1, e->stream));
-    } else if (exact) {
-        ExactSinks xs;
-        xs.hist = reinterpret_cast<unsigned long long*>(lv.d_cells);
-        xs.hist_slots = lv.slots; xs.total_cols = INT64_MAX; xs.ring = 1;
-        xs.live = ls;
-        xs.fin_map = xm;
-        HIPCHK(e, launch_exact_frames(lv.n, xpd, nullptr, 0, lv.S, 0, (int64_t)mlaunch + 1, xs, e->stream));
+    // One band: its frame launch (or, flush = true, the flush kernel) on rows [p.row0, p.row0 + p.rows) of the output column.
+    // A single-resolution session is one band of all rows; a multi-resolution one runs the long band, then the short band,
+    // each finalising its own rows of the same column in place (live.hip.inc: live_finalize_column).
+    // bl: the band's sinks; frames: the largest per-stream frame count of the band in this launch.
+    const auto band = [&](const Plan& p, const LiveSinks& bl, void* cells, int slots, int frames) -> int {
+        const DbMap bm = db_map(e, p.n);
+        const ExactPlanDev xpd = exact ? exact_plan_dev(e, p, lv.hop, lv.reassign) : ExactPlanDev{};
+        // (lo / inv_range / gate do not depend on the fft size: both bands index the palette as the batch's composition does)
+        const ExactDbMap xm = exact ? exact_db_map(e, p.n, xpd) : ExactDbMap{};
+        // many columns per stream: the frame kernel only scatters and a second kernel finalises them, one workgroup per column
+        // (inline they are one workgroup's serial round trips to the memory side, ~2 us per column)
+        // ... and so does a small transform: its workgroup has n / 16 (EXACT: n / 8) threads, and 1024 rows through 16 threads
+        // are 8 serial batches of round trips (emspec_column at N = 256: 32.6 us per call against 25.7 at N = 4096)
+        const bool defer = !flush && (mlaunch > kInlineFinalize || p.n < 2048);
+        LiveSinks bs = bl;
+        bs.defer_finalize = defer ? 1 : 0;
+        if (flush) {
+            HIPCHK(e, launch_live_flush(exact, bs, cells, slots, p.rows, lv.D, bm, xm, lv.S, 1, e->stream));
+        } else if (exact) {
+            ExactSinks xs;
+            xs.hist = reinterpret_cast<unsigned long long*>(cells);
+            xs.hist_slots = slots; xs.total_cols = INT64_MAX; xs.ring = 1;
+            xs.live = bs;
+            xs.fin_map = xm;
+            HIPCHK(e, launch_exact_frames(p.n, xpd, nullptr, 0, lv.S, 0, (int64_t)frames + 1, xs, e->stream));
+        } else {
+            FrameSinks sk;
+            sk.hist = reinterpret_cast<float*>(cells);
+            sk.hist_slots = slots; sk.total_cols = INT64_MAX; sk.ring = 1;
+            sk.live = bs;
+            sk.fin_map = bm;
+            HIPCHK(e, launch_frames(p.n, plan_dev(e, p, lv.hop, lv.reassign), nullptr, 0, lv.S, 0, (int64_t)frames + 1, sk, e->stream));
+        }
+        // (the columns a launch completes are the long band's frame count for either band)
+        if (defer) HIPCHK(e, launch_live_flush(exact, bs, cells, slots, p.rows, lv.D, bm, xm, lv.S, mlaunch, e->stream));
+        return EMSPEC_OK;
+    };
+    Plan* p;
+    if (!lv.n_high) {
+        if ((rc = get_plan(e, lv.n, &p))) return rc;
+        if ((rc = band(*p, ls, lv.d_cells, lv.slots, mlaunch))) return rc;
     } else {
-        FrameSinks sk;
-        sk.hist = reinterpret_cast<float*>(lv.d_cells);
-        sk.hist_slots = lv.slots; sk.total_cols = INT64_MAX; sk.ring = 1;
-        sk.live = ls;
-        sk.fin_map = m;
-        HIPCHK(e, launch_frames(lv.n, plan_dev(e, *p, lv.hop, lv.reassign), nullptr, 0, lv.S, 0, (int64_t)mlaunch + 1, sk, e->stream));
+        Plan* ph;
+        if ((rc = get_band_plan(e, lv.n, 0, lv.split, &p))) return rc;
+        if ((rc = get_band_plan(e, lv.n_high, lv.split, R - lv.split, &ph))) return rc;
+        if ((rc = band(*p, ls, lv.d_cells, lv.slots, mlaunch))) return rc;
+        // the short band: no launch when no stream has a frame (a block that only fills the sample ring: the long band's
+        // ingest workgroup did that)
+        if (flush || mlaunch > 0) {
+            LiveSinks hs = ls;
+            hs.row0 = lv.split;
+            hs.frame_shift = 2 * lv.shift;
+            hs.col_shift = lv.shift;
+            hs.lat_extra = lv.D - lv.D_high;
+            hs.no_ingest = 1;
+            hs.done = lv.d_done + lv.S;
+            if ((rc = band(*ph, hs, lv.d_cells_high, lv.slots_high, mlaunch + (priming ? 2 * lv.shift : 0)))) return rc;
+        }
     }
-    if (defer) HIPCHK(e, launch_live_flush(exact, ls, lv.d_cells, lv.slots, e->cfg.rows, lv.D, m, xm, lv.S, mlaunch, e->stream));
     if (post) {
         ls.out_db = dst_db;
         ls.out_rgba = reinterpret_cast<uint32_t*>(dst_rgba);
         ls.out_cols = out_cols;
-        HIPCHK(e, launch_live_post(ls, lv.d_raw, raw_cols, e->cfg.rows, lv.D, e->smoothing, e->agc, e->cfg.db_top, m, lv.d_pstate, lv.S, e->stream));
+        HIPCHK(e, launch_live_post(ls, lv.d_raw, raw_cols, R, lv.D, e->smoothing, e->agc, e->cfg.db_top, m, lv.d_pstate, lv.S, e->stream));
     }
     return EMSPEC_OK;
 }
@@ -208,14 +263,16 @@ int live_out_staging(emspec_engine* e, LiveState& lv, bool want_db, bool want_rg
 namespace {
 // ---- the calls, on one of the engine's two sessions ----
 
+// (n_high != 0: the multi-resolution form - n is n_low, the frames are n_low samples long and the short band reads the newest
+// n_high of them; on a stream's first frame it reads all of it, frames 0 .. 2 shift)
 int columns_impl(emspec_engine* e, LiveState& lv, const float* frames, int32_t streams, int32_t n, int32_t hop, int32_t reassign,
-                 float* out_db, uint8_t* out_rgba, int32_t rows, int64_t* out_columns) {
+                 float* out_db, uint8_t* out_rgba, int32_t rows, int64_t* out_columns, int32_t n_high = 0, int32_t split = 0) {
     if (!e || !frames) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument");
     reassign = reassign ? 1 : 0;
-    int rc = live_check(e, lv, streams, n, hop, reassign, rows, 1);
+    int rc = live_check(e, lv, streams, n, hop, reassign, rows, 1, n_high, split);
     if (rc) return rc;
     HIPCHK(e, hipSetDevice(e->device));
-    if (lv.form == 0 && (rc = live_open(e, lv, streams, n, hop, reassign, 1))) return rc;
+    if (lv.form == 0 && (rc = live_open(e, lv, streams, n, hop, reassign, 1, n_high, split))) return rc;
     const int S = lv.S, R = e->cfg.rows;
     // the frames: read by the kernel where they are when the caller's block is page-locked, else staged
     const float* src = reinterpret_cast<const float*>(device_view(frames));
@@ -291,20 +348,22 @@ int64_t push_columns_impl(const emspec_engine* e, const LiveState& lv, int64_t c
     return most;
 }
 
+// (n_high != 0: the multi-resolution form - n is n_low; max_columns then bounds what the block may complete whether or not an
+// output is given: it is the stride of every block the launch writes)
 int push_impl(emspec_engine* e, LiveState& lv, const float* samples, int32_t streams, int64_t count, int64_t stride, int32_t n,
               int32_t hop, int32_t reassign, float* out_db, uint8_t* out_rgba, int32_t rows, int64_t max_columns,
-              int64_t* out_counts, int64_t* out_first_columns) {
+              int64_t* out_counts, int64_t* out_first_columns, int32_t n_high = 0, int32_t split = 0) {
     if (!e || (!samples && count > 0) || count < 0 || stride < count) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument, negative count or stride < count");
     reassign = reassign ? 1 : 0;
-    int rc = live_check(e, lv, streams, n, hop, reassign, rows, 2);
+    int rc = live_check(e, lv, streams, n, hop, reassign, rows, 2, n_high, split);
     if (rc) return rc;
     if (max_columns < 0) return fail(e, EMSPEC_ERR_INVALID_ARG, "max_columns must be >= 0");
     const int64_t expect = push_columns_impl(e, lv, count, n, hop, reassign);
-    if ((out_db || out_rgba) && expect > max_columns)
+    if ((out_db || out_rgba || n_high) && expect > max_columns)
         return fail(e, EMSPEC_ERR_INVALID_ARG, "output holds fewer columns than this block completes (" + std::to_string(expect) +
                                                    "); size it with emspec_push_columns() / emspec_push_columns_multi()");
     HIPCHK(e, hipSetDevice(e->device));
-    if (lv.form == 0 && (rc = live_open(e, lv, streams, n, hop, reassign, 2))) return rc;
+    if (lv.form == 0 && (rc = live_open(e, lv, streams, n, hop, reassign, 2, n_high, split))) return rc;
     const int S = lv.S, R = e->cfg.rows, D = lv.D;
     float* ddb = reinterpret_cast<float*>(device_view(out_db));
     uint8_t* drgba = reinterpret_cast<uint8_t*>(device_view(out_rgba));
@@ -379,7 +438,7 @@ int push_impl(emspec_engine* e, LiveState& lv, const float* samples, int32_t str
 }
 
 void live_free(LiveState& lv) {
-    (void)hipFree(lv.d_cells); (void)hipFree(lv.d_sring); (void)hipFree(lv.d_done); (void)hipFree(lv.d_raw); (void)hipFree(lv.d_pstate);
+    (void)hipFree(lv.d_cells); (void)hipFree(lv.d_cells_high); (void)hipFree(lv.d_sring); (void)hipFree(lv.d_done); (void)hipFree(lv.d_raw); (void)hipFree(lv.d_pstate);
     if (lv.h_desc) (void)hipHostFree(lv.h_desc);
     if (lv.h_fresh) (void)hipHostFree(lv.h_fresh);
     if (lv.h_odb) (void)hipHostFree(lv.h_odb);
@@ -425,6 +484,33 @@ int emspec_push_samples_multi(emspec_engine* e, const float* samples, int32_t st
     if (!e) return EMSPEC_ERR_INVALID_ARG;
     return push_impl(e, e->live, samples, streams, count, stride, n, hop, reassign, out_db, out_rgba, rows, max_columns, out_counts,
                      out_first_columns);
+}
+
+// ---- the live session's multi-resolution form: rows below split_row from n_low, the rest from n_high, one
+// column per hop with the latency of n_low.  emspec_columns_flush / emspec_reset_stream / emspec_live_streams serve it as above.
+int emspec_columns_multires(emspec_engine* e, const float* frames, int32_t streams, int32_t n_low, int32_t n_high, int32_t hop,
+                            int32_t split_row, int32_t reassign, float* out_db, uint8_t* out_rgba, int32_t rows,
+                            int64_t* out_columns) {
+    if (!e) return EMSPEC_ERR_INVALID_ARG;
+    // (a shape the batch rejects is rejected with the same words, before n_high = 0 could pass for "single resolution")
+    if (const char* why = multires_shape_error(n_low, n_high, hop)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
+    return columns_impl(e, e->live, frames, streams, n_low, hop, reassign, out_db, out_rgba, rows, out_columns, n_high, split_row);
+}
+
+int64_t emspec_push_columns_multires(const emspec_engine* e, int64_t count, int32_t n_low, int32_t n_high, int32_t hop,
+                                     int32_t reassign) {
+    if (!e || multires_shape_error(n_low, n_high, hop)) return -1;
+    return push_columns_impl(e, e->live, count, n_low, hop, reassign);
+}
+
+int emspec_push_samples_multires(emspec_engine* e, const float* samples, int32_t streams, int64_t count, int64_t stride,
+                                 int32_t n_low, int32_t n_high, int32_t hop, int32_t split_row, int32_t reassign, float* out_db,
+                                 uint8_t* out_rgba, int32_t rows, int64_t max_columns, int64_t* out_counts,
+                                 int64_t* out_first_columns) {
+    if (!e) return EMSPEC_ERR_INVALID_ARG;
+    if (const char* why = multires_shape_error(n_low, n_high, hop)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
+    return push_impl(e, e->live, samples, streams, count, stride, n_low, hop, reassign, out_db, out_rgba, rows, max_columns,
+                     out_counts, out_first_columns, n_high, split_row);
 }
 
 // ---- the renderer's own calls: ONE stream, the same machinery on the engine's second session (e->one).  Until round 5
@@ -480,8 +566,13 @@ int emspec_reset_stream(emspec_engine* e, int32_t stream) {
     if (lv.form == 0) return fail(e, EMSPEC_ERR_STATE, "no live session");
     if (stream < 0 || stream >= lv.S) return fail(e, EMSPEC_ERR_INVALID_ARG, "stream out of range");
     HIPCHK(e, hipSetDevice(e->device));
-    const size_t cellb = e->exact() ? 8 : 4, per = (size_t)lv.slots * e->cfg.rows * cellb;
+    const int Rl = lv.n_high ? lv.split : e->cfg.rows;
+    const size_t cellb = e->exact() ? 8 : 4, per = (size_t)lv.slots * Rl * cellb;
     HIPCHK(e, hipMemsetAsync(reinterpret_cast<char*>(lv.d_cells) + (size_t)stream * per, 0, per, e->stream));
+    if (lv.n_high) {   // the short band's ring too
+        const size_t perh = (size_t)lv.slots_high * (e->cfg.rows - lv.split) * cellb;
+        HIPCHK(e, hipMemsetAsync(reinterpret_cast<char*>(lv.d_cells_high) + (size_t)stream * perh, 0, perh, e->stream));
+    }
     if (lv.d_pstate)
         HIPCHK(e, hipMemsetAsync(lv.d_pstate + (size_t)stream * (e->cfg.rows + 4), 0, (size_t)(e->cfg.rows + 4) * 4, e->stream));
     lv.fed[stream] = 0; lv.emitted[stream] = 0; lv.seen[stream] = 0; lv.newbase[stream] = 0; lv.pend[stream] = 0;

@@ -9,7 +9,7 @@
 
 using namespace emspec;
 
-namespace {
+namespace emspec {
 
 // null when (n_low, n_high, hop) is an accepted shape, else the rule it breaks
 const char* multires_shape_error(int n_low, int n_high, int hop) {
@@ -20,11 +20,21 @@ const char* multires_shape_error(int n_low, int n_high, int hop) {
     return nullptr;
 }
 
-int multires_check(emspec_engine* e, int32_t S, int64_t L, int32_t n_low, int32_t n_high, int32_t hop, int32_t split_row) {
+// shape, split row and stream count: the batch and the live session (emspec_live.cpp) accept the same
+int multires_check(emspec_engine* e, int32_t S, int32_t n_low, int32_t n_high, int32_t hop, int32_t split_row) {
     if (const char* why = multires_shape_error(n_low, n_high, hop)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
     if (split_row % 4 || split_row < 64 || split_row > e->cfg.rows - 64)
         return fail(e, EMSPEC_ERR_INVALID_ARG, "split_row must be a multiple of 4 in [64, rows - 64]");
     if (S < 1 || S > 65535) return fail(e, EMSPEC_ERR_INVALID_ARG, "need 1..65535 streams");
+    return EMSPEC_OK;
+}
+
+}  // namespace emspec
+
+namespace {
+
+int multires_check(emspec_engine* e, int32_t S, int64_t L, int32_t n_low, int32_t n_high, int32_t hop, int32_t split_row) {
+    if (int rc = emspec::multires_check(e, S, n_low, n_high, hop, split_row)) return rc;
     if (L < n_low) return fail(e, EMSPEC_ERR_INVALID_ARG, "need at least n_low samples per stream");
     return EMSPEC_OK;
 }

@@ -498,8 +498,8 @@ __global__ __launch_bounds__((1 << LOG2N) / 8) void exact_frames_kernel(ExactPla
         sink(N / 2, exact_core(pl, lk, N / 2, yt[4], yt[5], conj_d(yt[4])));
         sink.pads();
     }
-    if (live && live_last_arrival(sk.live, s, lb.d.frames, sre))
-        live_finalize<unsigned long long>(sk.live, lb.d, s, sk.hist, (int)sk.hist_slots, pl.rows, pl.D, T, LiveConvExact{sk.fin_map});
+    if (live && live_last_arrival(sk.live, s, lb.bframes, sre))
+        live_finalize<unsigned long long>(sk.live, lb.d, s, sk.hist, (int)sk.hist_slots, pl.rows, pl.D + sk.live.lat_extra, T, LiveConvExact{sk.fin_map});
 }
 
 
@@ -913,8 +913,8 @@ __global__ __launch_bounds__(1024) void exact_frames16384_kernel(ExactPlanDev pl
         sink(N / 2, exact_core(pl, lk, N / 2, wm, ev[0], conj_d(wm)));
         sink.pads();
     }
-    if (live && live_last_arrival(sk.live, s, lb.d.frames, sre))
-        live_finalize<unsigned long long>(sk.live, lb.d, s, sk.hist, (int)sk.hist_slots, pl.rows, pl.D, T, LiveConvExact{sk.fin_map});
+    if (live && live_last_arrival(sk.live, s, lb.bframes, sre))
+        live_finalize<unsigned long long>(sk.live, lb.d, s, sk.hist, (int)sk.hist_slots, pl.rows, pl.D + sk.live.lat_extra, T, LiveConvExact{sk.fin_map});
 }
 
 // records of all C frames of a stream chunk -> finished columns: workgroup (tile of `tile` columns, stream), u64 LDS

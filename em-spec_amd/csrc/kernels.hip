@@ -318,8 +318,8 @@ __global__ __launch_bounds__((1 << LOG2N) / 16) void frames_kernel(
     }
     if (t == 0) do_bin_general(N / 2);                             // the Nyquist bin
     if constexpr (SINK == 3) {
-        if (live_last_arrival(sk.live, s, lb.d.frames, sm))
-            live_finalize<float>(sk.live, lb.d, s, sk.hist, (int)sk.hist_slots, pl.rows, pl.D, T, LiveConvF32{sk.fin_map});
+        if (live_last_arrival(sk.live, s, lb.bframes, sm))
+            live_finalize<float>(sk.live, lb.d, s, sk.hist, (int)sk.hist_slots, pl.rows, pl.D + sk.live.lat_extra, T, LiveConvF32{sk.fin_map});
         live_stamp(sk.live, s, (int)f, 6);
         return;
     }

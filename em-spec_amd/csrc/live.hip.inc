@@ -32,10 +32,13 @@ __device__ __forceinline__ void live_stamp_after(const LiveSinks& lv, int s, int
 }
 
 struct LiveBlock {
-    LiveStream d;
+    LiveStream d;   // the stream's descriptor as the host wrote it (the long band's frame count: what the finalize emits)
+    long long bj0;  // this band's first frame in the launch ...
+    int bframes;    // ... and how many (they differ from d.j0 / d.frames for the short band of a multi-resolution session only)
     int s;          // stream
     int f;          // frame within the launch
     long long a0;   // absolute index of the frame's first sample
+    long long jc0;  // column of the band's first frame in the launch: the ring is indexed by the emitted column
     const float* fresh;
     const float* ring;
     int mask;
@@ -50,22 +53,26 @@ struct LiveBlock {
         mask = lv.ring_mask;
         fresh = lv.fresh + (size_t)s * (size_t)lv.fresh_stride;
         ring = lv.sring ? lv.sring + (size_t)s * (size_t)(mask + 1) : nullptr;
+        // short band of a multi-resolution session: frame_shift frames ahead, and frames 0 .. frame_shift with the first one
+        bj0 = d.j0 == 0 ? 0 : d.j0 + lv.frame_shift;
+        bframes = (d.j0 == 0 && d.frames > 0) ? d.frames + lv.frame_shift : d.frames;
         if (f == (int)gridDim.x - 1) {
-            if (lv.sring) {
+            if (lv.sring && !lv.no_ingest) {
                 float* w = lv.sring + (size_t)s * (size_t)(mask + 1);
                 for (int i = (int)threadIdx.x; i < d.newcount; i += nthreads) w[(d.newbase + i) & mask] = fresh[i];
             }
             return false;
         }
-        if (f >= d.frames) return false;
-        a0 = (d.j0 + f) * (long long)hop;
+        if (f >= bframes) return false;
+        a0 = (bj0 + f) * (long long)hop;
+        jc0 = bj0 - lv.col_shift;
         return true;
     }
     __device__ __forceinline__ float sample(int n) const {
         const long long a = a0 + n, rel = a - d.newbase;
         return rel >= 0 ? fresh[rel] : ring[a & mask];
     }
-    __device__ __forceinline__ long long column() const { return d.j0 + f; }
+    __device__ __forceinline__ long long column() const { return jc0 + f; }
 };
 
 // Ring slot of column jcol + dcol, |dcol| <= D < slots, from the slot of jcol: no 64-bit modulo per bin.
@@ -113,6 +120,9 @@ __device__ __forceinline__ bool live_last_arrival(const LiveSinks& lv, int s, in
 // Finalise the i-th of the columns this launch completed for stream s: column j0 - D + i (i < frames; flush form: i < flush).
 // Columns below 0 are skipped - or, in the per-frame form, emitted as the empty column.  CELL: float (FAST) or unsigned long long
 // (EXACT); conv(cell, db, index) is the mode's "dB + colour" stage.
+// rows: the launch's band (ring stride, loop bound); it fills rows [lv.row0, lv.row0 + rows) of the output column of lv.out_rows
+// rows in place - the other band of a multi-resolution session writes the rest of the same column from its own ring.
+// D: the latency of the EMITTED column (the long band's; the frame kernels pass their plan's D + lv.lat_extra).
 template <class CELL, class CONV>
 __device__ __forceinline__ void live_finalize_column(const LiveSinks& lv, const LiveStream& d, int s, int i, CELL* ring_all, int slots,
                                                      int rows, int D, int nthreads, const CONV& conv) {
@@ -122,8 +132,9 @@ __device__ __forceinline__ void live_finalize_column(const LiveSinks& lv, const 
     const long long below = d.j0 - D < 0 ? D - d.j0 : 0;
     const int oc = d.out_at + (lv.empty_col ? i : i - (int)(below < i ? below : i));
     CELL* ring = ring_all + (size_t)s * (size_t)slots * (size_t)rows;
-    float* odb = lv.out_db ? lv.out_db + ((size_t)s * (size_t)lv.out_cols + (size_t)oc) * (size_t)rows : nullptr;
-    uint32_t* orgba = lv.out_rgba ? lv.out_rgba + ((size_t)s * (size_t)lv.out_cols + (size_t)oc) * (size_t)rows : nullptr;
+    const size_t oat = ((size_t)s * (size_t)lv.out_cols + (size_t)oc) * (size_t)lv.out_rows + (size_t)lv.row0;
+    float* odb = lv.out_db ? lv.out_db + oat : nullptr;
+    uint32_t* orgba = lv.out_rgba ? lv.out_rgba + oat : nullptr;
     CELL* cells = c >= 0 ? ring + (size_t)(c % slots) * (size_t)rows : nullptr;
     // FIN rows of a thread in flight at once: each load is a round trip to the memory side (~2 us), and issued one per
     // loop iteration they were 4 serial round trips of the finalising workgroup (9.8 us of a 31 us kernel)

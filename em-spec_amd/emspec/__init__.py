@@ -40,7 +40,11 @@ SYMBOLS = [
     "emspec_columns", "emspec_columns_flush", "emspec_push_columns_multi", "emspec_push_samples_multi",
     "emspec_reset_stream", "emspec_live_streams",
     "emspec_multires_columns", "emspec_multires_shift", "emspec_batch_multires", "emspec_batch_multires_device",
+    "emspec_columns_multires", "emspec_push_columns_multires", "emspec_push_samples_multires",
 ]
+# the multi-resolution live session's entry points: a library built before they existed (tools/live_multires_rate.py times one
+# next to this build) loads without them
+OPTIONAL_SYMBOLS = SYMBOLS[-3:]
 
 
 class Config(C.Structure):
@@ -168,6 +172,14 @@ def load(diag=False):
                                           C.c_int32, C.c_int32, C.POINTER(Out)]
     lib.emspec_batch_multires_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                                  C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if all(hasattr(lib, sym) for sym in OPTIONAL_SYMBOLS):
+        lib.emspec_columns_multires.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        lib.emspec_push_columns_multires.restype = C.c_int64
+        lib.emspec_push_columns_multires.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        lib.emspec_push_samples_multires.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                                     C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
+                                                     C.c_void_p, C.c_void_p]
     _libs[diag] = lib
     return lib
 
@@ -645,6 +657,48 @@ class Engine:
         base = C.c_void_p(samples.ctypes.data + 4 * offset)
         self._chk(self._lib.emspec_push_samples_multi(self._h, base, S, count, width, n, hop, int(bool(reassign)), _np_ptr(db),
                                                       _np_ptr(rgba), self.rows, k, _np_ptr(counts), _np_ptr(firsts)))
+        return db, rgba, counts, firsts
+
+    # -- the live session's multi-resolution form: n_low below split_row, n_high above, one column per hop ------------
+    def columns_multires(self, frames, n_high, hop, split_row, reassign=True, want_db=True, want_rgba=False, db=None, rgba=None):
+        """Per-frame form (emspec_columns_multires): frames [S][n_low] -> (db [S][rows] or None, rgba or None, columns
+        int64 [S] (-1 = the empty column)); as `columns`."""
+        frames = frames if isinstance(frames, np.ndarray) and frames.dtype == np.float32 and frames.flags.c_contiguous \
+            else np.ascontiguousarray(frames, np.float32)
+        S, n_low = frames.shape
+        db, rgba = self._live_out(S, None, want_db, want_rgba, db, rgba)
+        cols = np.empty(S, np.int64)
+        self._chk(self._lib.emspec_columns_multires(self._h, _np_ptr(frames), S, n_low, n_high, hop, split_row, int(bool(reassign)),
+                                                    _np_ptr(db), _np_ptr(rgba), self.rows, _np_ptr(cols)))
+        return db, rgba, cols
+
+    def push_columns_multires(self, count, n_low, n_high, hop, reassign=True):
+        return int(self._lib.emspec_push_columns_multires(self._h, count, n_low, n_high, hop, int(bool(reassign))))
+
+    def push_samples_multires(self, samples, n_low, n_high, hop, split_row, reassign=True, want_db=True, want_rgba=False,
+                              db=None, rgba=None, count=None, offset=0, max_columns=None):
+        """Per-sample-block form (emspec_push_samples_multires): as `push_samples_multi`; max_columns overrides the output
+        capacity handed to the library (default: what the block completes, or the preallocated outputs' second dimension)."""
+        samples = samples if isinstance(samples, np.ndarray) and samples.dtype == np.float32 and samples.flags.c_contiguous \
+            else np.ascontiguousarray(samples, np.float32)
+        S, width = samples.shape
+        if count is None:
+            count = width - offset
+        assert 0 <= offset and offset + count <= width
+        k = self.push_columns_multires(count, n_low, n_high, hop, reassign)
+        if k < 0:   # (the call itself names the rule the shape breaks)
+            k = 0
+        if db is not None:
+            k = db.shape[1]
+        elif rgba is not None:
+            k = rgba.shape[1]
+        db, rgba = self._live_out(S, k, want_db, want_rgba, db, rgba)
+        counts, firsts = np.empty(S, np.int64), np.empty(S, np.int64)
+        base = C.c_void_p(samples.ctypes.data + 4 * offset)
+        self._chk(self._lib.emspec_push_samples_multires(self._h, base, S, count, width, n_low, n_high, hop, split_row,
+                                                         int(bool(reassign)), _np_ptr(db), _np_ptr(rgba), self.rows,
+                                                         k if max_columns is None else max_columns, _np_ptr(counts),
+                                                         _np_ptr(firsts)))
         return db, rgba, counts, firsts
 
     def reset_stream(self, stream):

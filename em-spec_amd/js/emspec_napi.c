@@ -616,8 +616,16 @@ static int get_f64_out(napi_env env, napi_value v, size_t want, double** out) {
 
 /* columns(handle, frames:Float32Array(S*fftSize), S, fftSize, hop, reassign, outDb?:Float32Array(S*rows),
  *         outRgba?:Uint8Array(4*S*rows), outColumns?:Float64Array(S)) : one frame of each of S streams -> their finished columns */
+/* Optional trailing pair of the live calls (columns, pushMulti): nHigh > 0 makes the call the multi-resolution one - fftSize is
+ * then n_low, and the rows from splitRow up come from nHigh (emspec_columns_multires / emspec_push_samples_multires). */
+static bool get_multires_pair(napi_env env, size_t argc, napi_value* argv, size_t at, int32_t* n_high, int32_t* split) {
+    *n_high = 0; *split = 0;
+    if (argc < at + 2) return true;
+    return napi_get_value_int32(env, argv[at], n_high) == napi_ok && napi_get_value_int32(env, argv[at + 1], split) == napi_ok;
+}
+
 static napi_value Columns(napi_env env, napi_callback_info info) {
-    size_t argc = 9; napi_value argv[9];
+    size_t argc = 11; napi_value argv[11];
     NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     if (argc < 6) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "columns(handle, frames, S, fftSize, hop, reassign[, outDb, outRgba, outColumns])"); return NULL; }
     handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
@@ -634,11 +642,14 @@ static napi_value Columns(napi_env env, napi_callback_info info) {
     if (argc > 6 && !get_typed(env, argv[6], napi_float32_array, &db, &dblen, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outDb must be a Float32Array"); return NULL; }
     if (argc > 7 && !get_typed(env, argv[7], napi_uint8_array, &rgba, &rgbalen, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outRgba must be a Uint8Array"); return NULL; }
     if (argc > 8 && !get_f64_out(env, argv[8], (size_t)S, &ocol)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outColumns must be a Float64Array(S)"); return NULL; }
+    int32_t n_high, split;
+    if (!get_multires_pair(env, argc, argv, 9, &n_high, &split)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "nHigh and splitRow must be integers"); return NULL; }
     const size_t cells = (size_t)S * (size_t)h->rows;
     if ((db && dblen != cells) || (rgba && rgbalen != 4 * cells)) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "outDb must hold S*rows floats, outRgba 4*S*rows bytes (rows = the engine's row count)"); return NULL; }
     int64_t* c64 = ocol ? (int64_t*)malloc((size_t)S * sizeof(int64_t)) : NULL;
     if (ocol && !c64) { napi_throw_error(env, "EMSPEC_ERR_OUT_OF_MEMORY", "malloc"); return NULL; }
-    int rc = emspec_columns(h->e, (const float*)fr, S, n, hop, reassign ? 1 : 0, (float*)db, (uint8_t*)rgba, h->rows, c64);
+    int rc = n_high > 0 ? emspec_columns_multires(h->e, (const float*)fr, S, n, n_high, hop, split, reassign ? 1 : 0, (float*)db, (uint8_t*)rgba, h->rows, c64)
+                        : emspec_columns(h->e, (const float*)fr, S, n, hop, reassign ? 1 : 0, (float*)db, (uint8_t*)rgba, h->rows, c64);
     if (rc == EMSPEC_OK && ocol) for (int32_t s = 0; s < S; ++s) ocol[s] = (double)c64[s];
     free(c64);
     if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
@@ -668,9 +679,9 @@ static napi_value ColumnsFlush(napi_env env, napi_callback_info info) {
 
 /* pushColumnsMulti(handle, count, fftSize, hop, reassign) -> the largest per-stream column count a block of `count` samples completes */
 static napi_value PushColumnsMulti(napi_env env, napi_callback_info info) {
-    size_t argc = 5; napi_value argv[5];
+    size_t argc = 6; napi_value argv[6];
     NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    if (argc < 5) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "pushColumnsMulti(handle, count, fftSize, hop, reassign)"); return NULL; }
+    if (argc < 5) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "pushColumnsMulti(handle, count, fftSize, hop, reassign[, nHigh])"); return NULL; }
     handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
     int64_t count; int32_t n, hop; bool reassign;
     NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[1], &count));
@@ -678,7 +689,10 @@ static napi_value PushColumnsMulti(napi_env env, napi_callback_info info) {
     NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[3], &hop));
     NAPI_OK_OR_RETURN(env, napi_coerce_to_bool(env, argv[4], &argv[4]));
     NAPI_OK_OR_RETURN(env, napi_get_value_bool(env, argv[4], &reassign));
-    const int64_t k = emspec_push_columns_multi(h->e, count, n, hop, reassign ? 1 : 0);
+    int32_t n_high = 0;   /* > 0: the multi-resolution session's count (fftSize = n_low) */
+    if (argc > 5) NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[5], &n_high));
+    const int64_t k = n_high > 0 ? emspec_push_columns_multires(h->e, count, n, n_high, hop, reassign ? 1 : 0)
+                                 : emspec_push_columns_multi(h->e, count, n, hop, reassign ? 1 : 0);
     if (k < 0) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "invalid count / fftSize / hop"); return NULL; }
     napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int64(env, k, &r));
     return r;
@@ -687,7 +701,7 @@ static napi_value PushColumnsMulti(napi_env env, napi_callback_info info) {
 /* pushMulti(handle, samples:Float32Array(S*count), S, fftSize, hop, reassign, maxColumns, outDb?:Float32Array(S*maxColumns*rows),
  *           outRgba?:Uint8Array(4*S*maxColumns*rows), outCounts?:Float64Array(S), outFirst?:Float64Array(S)) */
 static napi_value PushMulti(napi_env env, napi_callback_info info) {
-    size_t argc = 11; napi_value argv[11];
+    size_t argc = 13; napi_value argv[13];
     NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     if (argc < 7) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "pushMulti(handle, samples, S, fftSize, hop, reassign, maxColumns[, outDb, outRgba, outCounts, outFirst])"); return NULL; }
     handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
@@ -708,12 +722,16 @@ static napi_value PushMulti(napi_env env, napi_callback_info info) {
     if (argc > 8 && !get_typed(env, argv[8], napi_uint8_array, &rgba, &rgbalen, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outRgba must be a Uint8Array"); return NULL; }
     if (argc > 9 && !get_f64_out(env, argv[9], (size_t)S, &ocnt)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outCounts must be a Float64Array(S)"); return NULL; }
     if (argc > 10 && !get_f64_out(env, argv[10], (size_t)S, &ofirst)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outFirst must be a Float64Array(S)"); return NULL; }
+    int32_t n_high, split;
+    if (!get_multires_pair(env, argc, argv, 11, &n_high, &split)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "nHigh and splitRow must be integers"); return NULL; }
     const size_t cells = (size_t)S * (size_t)maxc * (size_t)h->rows;
     if ((db && dblen != cells) || (rgba && rgbalen != 4 * cells)) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "outDb must hold S*maxColumns*rows floats, outRgba 4x that in bytes"); return NULL; }
     int64_t* tmp = (int64_t*)malloc((size_t)S * 2 * sizeof(int64_t));
     if (!tmp) { napi_throw_error(env, "EMSPEC_ERR_OUT_OF_MEMORY", "malloc"); return NULL; }
-    int rc = emspec_push_samples_multi(h->e, (const float*)smp, S, count, count, n, hop, reassign ? 1 : 0, (float*)db, (uint8_t*)rgba,
-                                       h->rows, maxc, tmp, tmp + S);
+    int rc = n_high > 0 ? emspec_push_samples_multires(h->e, (const float*)smp, S, count, count, n, n_high, hop, split, reassign ? 1 : 0,
+                                                       (float*)db, (uint8_t*)rgba, h->rows, maxc, tmp, tmp + S)
+                        : emspec_push_samples_multi(h->e, (const float*)smp, S, count, count, n, hop, reassign ? 1 : 0, (float*)db,
+                                                    (uint8_t*)rgba, h->rows, maxc, tmp, tmp + S);
     if (rc == EMSPEC_OK) for (int32_t s = 0; s < S; ++s) { if (ocnt) ocnt[s] = (double)tmp[s]; if (ofirst) ofirst[s] = (double)tmp[S + s]; }
     free(tmp);
     if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);

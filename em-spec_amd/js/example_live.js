@@ -3,13 +3,15 @@
  * example_live.js — what a renderer that draws many streams does with the live multi-stream engine (INTEGRATION.md §2):
  * S streams, one hop of new samples each per audio callback, ONE call, and the finished RGBA columns of every stream come
  * back in a page-locked block.  Here the "audio callback" is a loop over synthetic audio and the "canvas" is a PPM file of
- * stream 0's scrolling image.   node example_live.js [streams] [seconds] [out.ppm]      (needs a gfx950 GPU)
+ * stream 0's scrolling image.   node example_live.js [streams] [seconds] [out.ppm] [multires]      (needs a gfx950 GPU)
+ * With a fifth argument "multires" the image is the multi-resolution one (FFT 16384 below 250 Hz, 4096 above: pushSamplesMultires).
  */
 const fs = require('fs');
 const em = require('./index.js');
 
 const S = +process.argv[2] || 8, seconds = +process.argv[3] || 2, out = process.argv[4] || '/tmp/emspec_live.ppm';
 const fs48 = 48000, fftSize = 4096, hop = 256;
+const multires = process.argv[5] === 'multires' ? { fftSize, lowFftSize: 16384, hop, splitHz: 250, wantRgba: true } : null;
 const engine = em.createEngine({ streams: S, gain: 3.5, dbRange: 58, gateDb: -65 });   // the sliders of the reference's settings panel
 engine.setColormap(em.makeColormap(0.44));
 const R = engine.rows, hops = Math.floor(seconds * fs48 / hop);
@@ -24,7 +26,8 @@ for (let j = 0; j < hops; j++) {
       block[s * hop + i] = 0.4 * Math.sin(phase[s]) + ((j * hop + i) % 24000 === 0 ? 0.8 : 0);
     }
   const c0 = process.hrtime.bigint();
-  const r = engine.pushSamplesMulti(block, fftSize, hop, true, true);   // one launch for all S streams
+  const r = multires ? engine.pushSamplesMultires(block, multires)      // one launch per band for all S streams
+                     : engine.pushSamplesMulti(block, fftSize, hop, true, true);   // one launch for all S streams
   inCall += process.hrtime.bigint() - c0;
   for (let i = 0; i < r.counts[0]; i++, drawn++) {        // stream 0's finished columns -> the image (row 0 at the bottom)
     const col = r.rgba.subarray(4 * i * R, 4 * (i + 1) * R);            // stream 0's block starts at 0: (0 * maxColumns + i)

@@ -87,6 +87,48 @@ class Engine {
     return { maxColumns: o.maxColumns, counts: o.counts, first: o.first, db: o.dbAll, rgba: wantRgba ? o.rgbaAll : undefined };
   }
 
+  /**
+   * The live calls' multi-resolution form (emspec_columns_multires / emspec_push_samples_multires, DESIGN.md §3.8): the image
+   * of computeColumnsMultires column by column - opts.lowFftSize below the split, opts.fftSize from it up, one column per hop
+   * at the latency of lowFftSize.  opts as in computeColumnsMultires ({fftSize, lowFftSize, hop, splitHz | splitRow,
+   * reassign = true}) plus wantRgba.  frames: Float32Array(S * lowFftSize).  Results, flushColumns() and resetStream() as for
+   * computeSpectrogramColumns; a session is one kind or the other until reset().
+   */
+  computeSpectrogramColumnsMultires(frames, opts) {
+    const m = this._multiresOpts(opts);
+    this._liveBlocks(opts.lowFftSize, m.wantRgba);
+    native.columns(this._h, frames, this.streams, opts.lowFftSize, opts.hop, m.reassign, this.columnsDb,
+      m.wantRgba ? this.columnsRgba : undefined, this.columnIndex, opts.fftSize, m.split);
+    return this.columnsDb;
+  }
+
+  /** pushSamplesMulti for a multi-resolution session: same return value, opts as in computeSpectrogramColumnsMultires. */
+  pushSamplesMultires(samples, opts) {
+    const m = this._multiresOpts(opts);
+    const S = this.streams, count = samples.length / S;
+    const maxColumns = native.pushColumnsMulti(this._h, count, opts.lowFftSize, opts.hop, m.reassign, opts.fftSize);
+    let o = this._push;
+    if (!o || o.maxColumns < maxColumns || (m.wantRgba && !o.rgbaAll)) {
+      const cap = Math.max(maxColumns, 1);
+      o = this._push = { maxColumns: cap, dbAll: new Float32Array(native.allocPinned(4 * S * cap * this.rows)),
+        rgbaAll: m.wantRgba ? new Uint8Array(native.allocPinned(4 * S * cap * this.rows)) : undefined,
+        counts: new Float64Array(S), first: new Float64Array(S) };
+    }
+    native.pushMulti(this._h, samples, S, opts.lowFftSize, opts.hop, m.reassign, o.maxColumns, o.dbAll,
+      m.wantRgba ? o.rgbaAll : undefined, o.counts, o.first, opts.fftSize, m.split);
+    return { maxColumns: o.maxColumns, counts: o.counts, first: o.first, db: o.dbAll, rgba: m.wantRgba ? o.rgbaAll : undefined };
+  }
+
+  /** (the split row of opts.splitHz is looked up once per frequency, not per call) */
+  _multiresOpts(opts) {
+    let split = opts.splitRow;
+    if (split === undefined) {
+      if (this._mrHz !== opts.splitHz) { this._mrSplit = this.splitRowForHz(opts.splitHz); this._mrHz = opts.splitHz; }
+      split = this._mrSplit;
+    }
+    return { split, reassign: opts.reassign === undefined ? true : !!opts.reassign, wantRgba: !!opts.wantRgba };
+  }
+
   /** A page-locked Float32Array(S * count) for pushSamplesMulti (kept per count). */
   sampleBlock(count) {
     if (!this._blk || this._blk.length !== this.streams * count) this._blk = new Float32Array(native.allocPinned(4 * this.streams * count));

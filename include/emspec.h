@@ -509,6 +509,35 @@ int emspec_batch_multires_device(emspec_engine* e, const float* pcm_dev, int32_t
                                  int32_t n_high, int32_t hop, int32_t split_row, int32_t reassign,
                                  float* db_dev, uint8_t* rgba_dev, uint8_t* index_dev, void* hip_stream);
 
+/*
+ * Multi-resolution LIVE session: the image above, column by column while the audio arrives.  These
+ * calls open the engine's live multi-stream session (the one emspec_columns / emspec_push_samples_multi open) as a
+ * multi-resolution session; streams = 1 is the one-stream renderer.  For a stream that was fed samples [0, L) and then
+ * flushed, the emspec_multires_columns(L, ...) emitted columns are those of emspec_batch_multires on the same samples
+ * (EXACT mode: bit for bit; FAST mode: sums in arrival order).  Latency: emspec_latency_columns(n_low, hop, reassign).
+ * The short band needs no samples of its own: frame j of n_low ends where frame j + 2 shift of n_high ends, so a call
+ * advances both bands by the same number of frames (a stream's first frame runs the short band's frames 0 .. 2 shift).
+ * Per call: one frame launch per band (each band's last workgroup of a stream writes its own rows of the output column in
+ * place), one host synchronisation.  With emspec_set_display on, the post-process runs once over the composed raw column.
+ * emspec_columns_multires: as emspec_columns, frames [streams][n_low].
+ * emspec_push_samples_multires: as emspec_push_samples_multi; max_columns must hold what the block completes
+ *   (emspec_push_columns_multires) even when both outputs are NULL - EMSPEC_ERR_INVALID_ARG otherwise, nothing fed.
+ * emspec_push_columns_multires: as emspec_push_columns_multi (-1 for a shape that is not accepted).
+ * emspec_columns_flush, emspec_reset_stream, emspec_reset and emspec_live_streams act on the session as on a
+ * single-resolution one.  Shapes, split rows and their messages: those of emspec_batch_multires.  EMSPEC_ERR_STATE until
+ * emspec_reset(): a single-resolution live call on a multi-resolution session or the reverse; a change of streams, n_low,
+ * n_high, hop, split_row, reassign or feeding form mid-session; feeding a flushed stream.
+ */
+int emspec_columns_multires(emspec_engine* e, const float* frames /* [streams][n_low] */, int32_t streams, int32_t n_low,
+                            int32_t n_high, int32_t hop, int32_t split_row, int32_t reassign, float* out_db,
+                            uint8_t* out_rgba, int32_t rows, int64_t* out_columns);
+int64_t emspec_push_columns_multires(const emspec_engine* e, int64_t count, int32_t n_low, int32_t n_high, int32_t hop,
+                                     int32_t reassign);
+int emspec_push_samples_multires(emspec_engine* e, const float* samples, int32_t streams, int64_t count, int64_t stride,
+                                 int32_t n_low, int32_t n_high, int32_t hop, int32_t split_row, int32_t reassign,
+                                 float* out_db, uint8_t* out_rgba, int32_t rows, int64_t max_columns, int64_t* out_counts,
+                                 int64_t* out_first_columns);
+
 #ifdef __cplusplus
 }
 #endif
