@@ -57,6 +57,13 @@ struct LiveState {
     float* h_odb = nullptr; size_t odb_bytes = 0;
     uint8_t* h_orgba = nullptr; size_t orgba_bytes = 0;
     unsigned long long* stamps = nullptr;   // diagnostic build: [S][8] page-locked, set by emspec_debug_live_stamps
+    // PCM session (emspec_push_samples_pcm; form 2 only): S = sources * views streams fed from raw interleaved frames.  The
+    // staging block holds the raw frames ([sources][cap] frames, page-locked; the decode kernel reads it in place) and the
+    // frame kernels read the decoded block on the device.  Every stream of the session has the same `pend`.
+    int pcm_views = 0;                    // 0: a float session
+    emspec_pcm_format pcm_fmt{};
+    uint8_t* h_raw = nullptr; size_t hraw_bytes = 0;     // [S / pcm_views][cap] frames
+    float* d_fresh = nullptr; size_t dfresh_bytes = 0;   // [S][cap] decoded samples
 };
 
 // emspec_api.cpp: the plan cache and the per-shape constants handed to the kernels
@@ -81,8 +88,17 @@ bool host_pinned(const void* p);   // p is null or page-locked host memory the d
 // holds at least min_streams of them (or all S).
 struct PackedOut { uint8_t* wire; int64_t capacity; int64_t* offsets; };
 using HostRun = std::function<int(const float* pcm, int sc, int64_t samples, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st)>;
-int host_batch(emspec_engine* e, const float* pcm, int S, int64_t L, int n, int hop, int halo_D, int min_streams,
-               const emspec_out* out, const PackedOut* pk, const HostRun& run);
+// `dec` (emspec_batch_pcm, emspec_batch_pcm_packed): pcm is raw interleaved frames, S SOURCES of L frames; the copy-in stage
+// moves those bytes, the decode kernel (pcm.hip.inc) fills the unit's float streams in front of `run`, which then sees
+// sc * dec->views streams, and the outputs are those of S * dec->views streams.  Null: pcm is float32 [S][L].
+int host_batch(emspec_engine* e, const void* pcm, int S, int64_t L, int n, int hop, int halo_D, int min_streams,
+               const emspec_out* out, const PackedOut* pk, const HostRun& run, const emspec_pcm_format* dec = nullptr);
+// emspec_pcm.cpp: null, or what is wrong with the format (names the field); bytes per interleaved frame of a valid format
+const char* pcm_format_error(const emspec_pcm_format* f);
+int pcm_frame_bytes(const emspec_pcm_format& f);
+// the decode kernel (pcm.hip.inc) for a valid format
+hipError_t pcm_decode(const void* src, const emspec_pcm_format& f, int sources, int64_t frames, int64_t src_stride_bytes, float* out,
+                      int64_t out_stride, hipStream_t st);
 // emspec_multires.cpp: what the multi-resolution batch and the multi-resolution live session accept
 const char* multires_shape_error(int n_low, int n_high, int hop);   // null, or the rule the shape breaks
 int multires_check(emspec_engine* e, int32_t S, int32_t n_low, int32_t n_high, int32_t hop, int32_t split_row);

@@ -91,27 +91,31 @@ std::vector<PipeItem> pipe_items(int S, int64_t L, int64_t C, int n, int hop, in
 
 size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
 
-struct Set { float* pcm; float* db; uint8_t* rgba; uint8_t* idx; uint8_t* wire; };
+struct Set { float* pcm; float* db; uint8_t* rgba; uint8_t* idx; uint8_t* wire; char* raw; };
 
 // The staging set: every array at the size the largest unit needs (the wire images: one slot of `wire` bytes per stream).
 struct Stage {
     size_t in = 0, db = 0, rgba = 0, idx = 0, wire = 0;
+    size_t raw = 0;  // PCM entries: the unit's raw frames, which the decode kernel turns into `in`
     int chunk = 1;   // streams in the largest unit
-    size_t bytes() const { return in + db + rgba + idx + wire * chunk; }
+    size_t bytes() const { return in + db + rgba + idx + wire * chunk + raw; }
     Set at(char* stage, int b) const {
         char* base = stage + (size_t)b * bytes();
         return Set{(float*)base, db ? (float*)(base + in) : nullptr, rgba ? (uint8_t*)(base + in + db) : nullptr,
-                   idx ? (uint8_t*)(base + in + db + rgba) : nullptr, wire ? (uint8_t*)(base + in + db + rgba + idx) : nullptr};
+                   idx ? (uint8_t*)(base + in + db + rgba) : nullptr, wire ? (uint8_t*)(base + in + db + rgba + idx) : nullptr,
+                   raw ? base + in + db + rgba + idx + wire * chunk : nullptr};
     }
 };
 
-Stage stage_layout(const std::vector<PipeItem>& items, int R, bool db, bool rgba, bool idx, size_t wire_s) {
+// (V streams per unit of PipeItem::sc, frame_bytes of raw input each: 1 and 0 for the float entries, whose units are streams)
+Stage stage_layout(const std::vector<PipeItem>& items, int R, bool db, bool rgba, bool idx, size_t wire_s, int V, int frame_bytes) {
     Stage g;
     size_t cells = 0;
     for (const PipeItem& it : items) {
-        g.in = std::max(g.in, al((size_t)it.samples * 4 * it.sc));
-        cells = std::max(cells, (size_t)it.cols * R * it.sc);
-        g.chunk = std::max(g.chunk, it.sc);
+        g.in = std::max(g.in, al((size_t)it.samples * 4 * it.sc * V));
+        g.raw = std::max(g.raw, frame_bytes ? al((size_t)it.samples * frame_bytes * it.sc) : 0);
+        cells = std::max(cells, (size_t)it.cols * R * it.sc * V);
+        g.chunk = std::max(g.chunk, it.sc * V);
     }
     g.db = db ? al(cells * 4) : 0;
     g.rgba = rgba ? al(cells * 4) : 0;
@@ -120,10 +124,13 @@ Stage stage_layout(const std::vector<PipeItem>& items, int R, bool db, bool rgba
     return g;
 }
 
-// Where a unit's kept columns come from in its set and go in the caller's arrays: cell offsets and count.
+// Where a unit's kept columns come from in its set and go in the caller's arrays: cell offsets and count.  A unit of whole
+// streams is one span; a run of columns is one span per stream (V > 1: the views of the unit's source).
 struct Span { size_t from, to, cells; };
-Span span_of(const PipeItem& it, int64_t C, int R) {
-    return Span{(size_t)it.skip * R, ((size_t)it.s0 * C + (size_t)it.c0) * R, (size_t)it.cn * R * it.sc};
+int spans_of(const PipeItem& it, int64_t C, int V) { return it.cn == C ? 1 : it.sc * V; }
+Span span_of(const PipeItem& it, int64_t C, int R, int V, int k) {
+    if (it.cn == C) return Span{0, (size_t)it.s0 * V * C * R, (size_t)it.cn * R * it.sc * V};
+    return Span{((size_t)k * it.cols + (size_t)it.skip) * R, (((size_t)it.s0 * V + k) * C + (size_t)it.c0) * R, (size_t)it.cn * R};
 }
 
 }  // namespace
@@ -135,8 +142,8 @@ bool emspec::host_pinned(const void* p) {
     return at.type == hipMemoryTypeHost;
 }
 
-int emspec::host_batch(emspec_engine* e, const float* pcm, int S, int64_t L, int n, int hop, int halo_D, int min_streams,
-                       const emspec_out* out, const PackedOut* pk, const HostRun& run) {
+int emspec::host_batch(emspec_engine* e, const void* pcm, int S, int64_t L, int n, int hop, int halo_D, int min_streams,
+                       const emspec_out* out, const PackedOut* pk, const HostRun& run, const emspec_pcm_format* dec) {
     if (!e->stream_in) HIPCHK(e, hipStreamCreateWithFlags(&e->stream_in, hipStreamNonBlocking));
     if (!e->stream_out) HIPCHK(e, hipStreamCreateWithFlags(&e->stream_out, hipStreamNonBlocking));
     for (hipEvent_t& ev : e->pipe_ev)
@@ -144,17 +151,20 @@ int emspec::host_batch(emspec_engine* e, const float* pcm, int S, int64_t L, int
     const int64_t C = emspec_num_columns(L, n, hop);
     const int R = e->cfg.rows;
     int rc;
-    const size_t col_cells = (size_t)C * R, in_s = (size_t)L * sizeof(float);
+    // dec: the S rows are SOURCES of interleaved frames (emspec_batch_pcm): fb bytes per frame in, V streams each out
+    const int V = dec ? dec->views : 1, fb = dec ? pcm_frame_bytes(*dec) : (int)sizeof(float);
+    const size_t col_cells = (size_t)C * R, in_s = (size_t)L * fb;
     const bool want_db = out && out->db, want_rgba = out && out->rgba, want_idx = (out && out->index) || pk;
     const size_t wire_s = pk ? (size_t)wire_bound_bytes(C, R) : 0;
-    const size_t per_stream = al(in_s) + al(want_db ? col_cells * 4 : 0) + al(want_rgba ? col_cells * 4 : 0) + al(want_idx ? col_cells : 0) + al(wire_s);
-    int units = pipe_units(e->exact(), n, (int64_t)S * C, (size_t)S * in_s,
-                           pk ? (size_t)S * col_cells / 5 : (size_t)S * col_cells * ((want_db ? 4 : 0) + (want_rgba ? 4 : 0) + (want_idx ? 1 : 0)));
+    const size_t per_stream = al(in_s) + (dec ? al((size_t)L * 4 * V) : 0) +
+                              V * (al(want_db ? col_cells * 4 : 0) + al(want_rgba ? col_cells * 4 : 0) + al(want_idx ? col_cells : 0) + al(wire_s));
+    int units = pipe_units(e->exact(), n, (int64_t)S * V * C, (size_t)S * in_s,
+                           pk ? (size_t)S * V * col_cells / 5 : (size_t)S * V * col_cells * ((want_db ? 4 : 0) + (want_rgba ? 4 : 0) + (want_idx ? 1 : 0)));
     if (halo_D < 0) units = std::min(units, std::max(S / min_streams, 1));   // whole streams: at least min_streams per unit
     const std::vector<PipeItem> items = pipe_items(S, L, C, n, hop, halo_D, per_stream, halo_D >= 0, units);
     const int nu = (int)items.size();
     const bool one = nu == 1;
-    const Stage g = stage_layout(items, R, want_db, want_rgba, want_idx, wire_s);
+    const Stage g = stage_layout(items, R, want_db, want_rgba, want_idx, wire_s, V, dec ? fb : 0);
     if ((rc = grow(e, (void**)&e->d_stage, &e->stage_bytes, std::min(nu, kPipeSets) * g.bytes() + 1024))) return rc;
     if (pk) {
         if ((rc = grow(e, (void**)&e->d_packscratch, &e->packscratch_bytes, wire_scratch_bytes(C)))) return rc;
@@ -171,12 +181,14 @@ int emspec::host_batch(emspec_engine* e, const float* pcm, int S, int64_t L, int
     hipEvent_t *ev_in = e->pipe_ev, *ev_comp = ev_in + kPipeSets, *ev_out = ev_comp + kPipeSets;   // per staging set
     // the only D2H copies of columns: unit f's kept columns into the caller's arrays, on `st` behind the unit's kernels
     auto copy_out = [&](int f, hipStream_t st) {
-        const Span sp = span_of(items[f], C, R);
         const Set q = g.at(e->d_stage, f % kPipeSets);
         hipError_t r = st == e->stream ? hipSuccess : hipStreamWaitEvent(st, ev_comp[f % kPipeSets], 0);
-        if (r == hipSuccess && want_db) r = hipMemcpyAsync(out->db + sp.to, q.db + sp.from, sp.cells * 4, hipMemcpyDeviceToHost, st);
-        if (r == hipSuccess && want_rgba) r = hipMemcpyAsync(out->rgba + 4 * sp.to, q.rgba + 4 * sp.from, sp.cells * 4, hipMemcpyDeviceToHost, st);
-        if (r == hipSuccess && want_idx) r = hipMemcpyAsync(out->index + sp.to, q.idx + sp.from, sp.cells, hipMemcpyDeviceToHost, st);
+        for (int k = 0; k < spans_of(items[f], C, V); ++k) {
+            const Span sp = span_of(items[f], C, R, V, k);
+            if (r == hipSuccess && want_db) r = hipMemcpyAsync(out->db + sp.to, q.db + sp.from, sp.cells * 4, hipMemcpyDeviceToHost, st);
+            if (r == hipSuccess && want_rgba) r = hipMemcpyAsync(out->rgba + 4 * sp.to, q.rgba + 4 * sp.from, sp.cells * 4, hipMemcpyDeviceToHost, st);
+            if (r == hipSuccess && want_idx) r = hipMemcpyAsync(out->index + sp.to, q.idx + sp.from, sp.cells, hipMemcpyDeviceToHost, st);
+        }
         return r;
     };
 
@@ -205,10 +217,12 @@ int emspec::host_batch(emspec_engine* e, const float* pcm, int S, int64_t L, int
             if (t == kTouchers - 1) p[bytes - 1] = 0;
         };
         for (int f = 0; f < nu; ++f) {
-            const Span sp = span_of(items[f], C, R);
-            if (want_db) touch(out->db + sp.to, sp.cells * 4);
-            if (want_rgba) touch(out->rgba + 4 * sp.to, sp.cells * 4);
-            if (want_idx) touch(out->index + sp.to, sp.cells);
+            for (int k = 0; k < spans_of(items[f], C, V); ++k) {
+                const Span sp = span_of(items[f], C, R, V, k);
+                if (want_db) touch(out->db + sp.to, sp.cells * 4);
+                if (want_rgba) touch(out->rgba + 4 * sp.to, sp.cells * 4);
+                if (want_idx) touch(out->index + sp.to, sp.cells);
+            }
             std::lock_guard<std::mutex> lk(mu);
             touched[t] = f + 1;
             cv.notify_all();
@@ -267,7 +281,7 @@ int emspec::host_batch(emspec_engine* e, const float* pcm, int S, int64_t L, int
         } else {
             const Set q = g.at(e->d_stage, b);
             herr = hipEventSynchronize(ev_comp[b]);
-            for (int i = 0; i < it.sc && herr == hipSuccess && rc == EMSPEC_OK; ++i) {
+            for (int i = 0; i < it.sc * V && herr == hipSuccess && rc == EMSPEC_OK; ++i) {
                 const uint32_t* h = reinterpret_cast<const uint32_t*>(e->h_hdr + ((size_t)b * g.chunk + i) * 32);
                 const uint64_t hcols = (uint64_t)h[2] | ((uint64_t)h[3] << 32), hpay = (uint64_t)h[4] | ((uint64_t)h[5] << 32);
                 if (h[0] != 0x32574D45u || (int32_t)h[1] != R || hcols != (uint64_t)C || hpay > (uint64_t)col_cells) {
@@ -275,7 +289,7 @@ int emspec::host_batch(emspec_engine* e, const float* pcm, int S, int64_t L, int
                     break;
                 }
                 const int64_t bytes = wire_fixed_bytes(C, R) + (int64_t)((hpay + 15) & ~(uint64_t)15);
-                const int64_t at = pk->offsets[it.s0 + i];
+                const int64_t at = pk->offsets[it.s0 * V + i];
                 if (at + bytes > pk->capacity) {
                     rc = fail(e, EMSPEC_ERR_INVALID_ARG, "wire buffer too small (emspec_wire_bound(columns, rows) per stream always suffices)");
                     break;
@@ -284,7 +298,7 @@ int emspec::host_batch(emspec_engine* e, const float* pcm, int S, int64_t L, int
                 // every image STARTS on a 16-byte boundary: the fixed part (32 + 4 C (1 + R/32) bytes) is a multiple of 4 only, so
                 // up to 12 bytes of slack follow an image (stream s occupies [offsets[s], offsets[s+1]), slack included; the
                 // unpackers take the image's real size from its header)
-                pk->offsets[it.s0 + i + 1] = (at + bytes + 15) & ~(int64_t)15;
+                pk->offsets[it.s0 * V + i + 1] = (at + bytes + 15) & ~(int64_t)15;
             }
         }
         if (herr == hipSuccess && rc == EMSPEC_OK && !one) herr = hipEventRecord(ev_out[b], s_out);
@@ -304,16 +318,18 @@ int emspec::host_batch(emspec_engine* e, const float* pcm, int S, int64_t L, int
             herr = hipStreamWaitEvent(s_in, ev_comp[b], 0);
             if (herr == hipSuccess) herr = hipStreamWaitEvent(e->stream, ev_out[b], 0);
         }
-        // 2. samples in
+        // 2. samples in (PCM entries: the raw frames, from a byte offset that is a multiple of the sample size only)
         if (herr == hipSuccess)
-            herr = hipMemcpyAsync(q.pcm, pcm + (size_t)it.s0 * L + (size_t)it.first_sample, (size_t)it.samples * 4 * it.sc, hipMemcpyHostToDevice, s_in);
+            herr = hipMemcpyAsync(dec ? (void*)q.raw : (void*)q.pcm, static_cast<const char*>(pcm) + ((size_t)it.s0 * L + (size_t)it.first_sample) * fb,
+                                  (size_t)it.samples * fb * it.sc, hipMemcpyHostToDevice, s_in);
         if (herr == hipSuccess && !one) herr = hipEventRecord(ev_in[b], s_in);
         if (herr == hipSuccess && !one) herr = hipStreamWaitEvent(e->stream, ev_in[b], 0);
         if (herr != hipSuccess) break;
-        // 3. kernels
-        if ((rc = run(q.pcm, it.sc, it.samples, q.db, q.rgba, q.idx, e->stream))) break;
+        // 3. kernels (PCM entries: the decode kernel first, raw frames -> the unit's sc * V float streams)
+        if (dec && (herr = pcm_decode(q.raw, *dec, it.sc, it.samples, it.samples * fb, q.pcm, it.samples, e->stream)) != hipSuccess) break;
+        if ((rc = run(q.pcm, it.sc * V, it.samples, q.db, q.rgba, q.idx, e->stream))) break;
         // 4. packed: each stream's image, its header to the host behind it
-        for (int i = 0; pk && i < it.sc && herr == hipSuccess; ++i) {
+        for (int i = 0; pk && i < it.sc * V && herr == hipSuccess; ++i) {
             uint8_t* w = q.wire + (size_t)i * g.wire;
             herr = launch_wire_pack(q.idx + (size_t)i * col_cells, C, R, w, e->d_packscratch, e->stream);
             if (herr == hipSuccess) herr = hipMemcpyAsync(e->h_hdr + ((size_t)b * g.chunk + i) * 32, w, 32, hipMemcpyDeviceToHost, e->stream);

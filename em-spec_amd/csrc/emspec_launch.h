@@ -158,6 +158,14 @@ int64_t wire_fixed_bytes(int64_t columns, int rows);
 size_t wire_scratch_bytes(int64_t columns);
 hipError_t launch_wire_pack(const uint8_t* index, int64_t columns, int rows, uint8_t* wire, void* scratch, hipStream_t st);
 hipError_t launch_wire_unpack(const uint8_t* wire, int64_t columns, int rows, uint8_t* index, hipStream_t st);
+// PCM front end (pcm.hip.inc): `frames` interleaved frames of `sources` sources (source i at src + i * src_stride_bytes, device
+// memory or page-locked host memory, any byte offset that is a multiple of the sample size) -> float32 streams, stream
+// i * views + v at out + (i * views + v) * out_stride.  sample_type: kPcmS16 .. kPcmF32 (the values of include/emspec.h's
+// EMSPEC_PCM_*; emspec_pcm.cpp asserts it), 1 .. kPcmMaxChannels channels, 1 .. kPcmMaxViews views, mix [views][channels].
+enum { kPcmS16 = 1, kPcmS24 = 2, kPcmS32 = 3, kPcmF32 = 4, kPcmMaxChannels = 8, kPcmMaxViews = 8 };
+struct PcmMix { float w[kPcmMaxViews * kPcmMaxChannels]; };   // [view][kPcmMaxChannels]
+hipError_t launch_pcm_decode(const void* src, int sample_type, int channels, int views, const float* mix, int sources, int64_t frames,
+                             int64_t src_stride_bytes, float* out, int64_t out_stride, hipStream_t st);
 bool fused_supported(int n, int hop, int rows, int reassign);
 int device_cus();           // compute units of the current device
 #ifdef EMSPEC_DIAG          // diagnostic build only (libemspec_diag.so, include/emspec_debug.h)

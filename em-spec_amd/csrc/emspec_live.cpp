@@ -50,13 +50,15 @@ void* device_view(const void* p) {
 
 void live_forget(LiveState& lv) {
     lv.S = 0; lv.n = 0; lv.hop = 0; lv.reassign = -1; lv.D = 0; lv.form = 0; lv.slots = 0; lv.mmax = 0; lv.cap = 0; lv.ring_mask = 0;
-    lv.n_high = 0; lv.split = 0; lv.shift = 0; lv.D_high = 0; lv.slots_high = 0;
+    lv.n_high = 0; lv.split = 0; lv.shift = 0; lv.D_high = 0; lv.slots_high = 0; lv.pcm_views = 0;
     lv.fed.clear(); lv.emitted.clear(); lv.seen.clear(); lv.newbase.clear(); lv.pend.clear();
 }
 
 // first call of a session: every allocation, then the state.  n_high != 0: a multi-resolution session (n = n_low; rows below
 // `split` from n, the rest from n_high).
-int live_open(emspec_engine* e, LiveState& lv, int S, int n, int hop, int reassign, int form, int n_high = 0, int split = 0) {
+// pcm: a PCM session - its staging block holds raw frames (live_open_pcm), not floats.
+int live_open(emspec_engine* e, LiveState& lv, int S, int n, int hop, int reassign, int form, int n_high = 0, int split = 0,
+              bool pcm = false) {
     const int R = e->cfg.rows;
     const int D = latency(n, hop, reassign);
     const int Rl = n_high ? split : R;   // rows of the (long) band that d_cells holds
@@ -79,7 +81,7 @@ int live_open(emspec_engine* e, LiveState& lv, int S, int n, int hop, int reassi
     if (form == 2 && (rc = grow(e, (void**)&lv.d_sring, &lv.sring_bytes, (size_t)S * ring * 4))) return rc;
     if ((rc = grow(e, (void**)&lv.d_done, &lv.done_bytes, (size_t)S * 4 * (n_high ? 2 : 1)))) return rc;
     if ((rc = pinned_grow(e, &lv.h_desc, &lv.desc_bytes, (size_t)S * sizeof(LiveStream)))) return rc;
-    if (form == 2 && (rc = pinned_grow(e, (void**)&lv.h_fresh, &lv.fresh_bytes, (size_t)S * cap * 4))) return rc;
+    if (form == 2 && !pcm && (rc = pinned_grow(e, (void**)&lv.h_fresh, &lv.fresh_bytes, (size_t)S * cap * 4))) return rc;
     HIPCHK(e, hipMemsetAsync(lv.d_cells, 0, (size_t)S * slots * Rl * cellb, e->stream));
     if (n_high) HIPCHK(e, hipMemsetAsync(lv.d_cells_high, 0, (size_t)S * slots_high * (R - split) * cellb, e->stream));
     HIPCHK(e, hipMemsetAsync(lv.d_done, 0, (size_t)S * 4 * (n_high ? 2 : 1), e->stream));
@@ -261,6 +263,44 @@ int live_out_staging(emspec_engine* e, LiveState& lv, bool want_db, bool want_rg
 }  // namespace
 
 namespace {
+// ---- PCM session (emspec_push_samples_pcm): raw frames staged on the host, decoded on the device at launch time ----
+bool pcm_same_format(const emspec_pcm_format& a, const emspec_pcm_format& b) {
+    return a.sample_type == b.sample_type && a.channels == b.channels && a.views == b.views &&
+           std::memcmp(a.mix, b.mix, sizeof(float) * a.views * a.channels) == 0;
+}
+
+// (behind live_open: the session's streams are sources * views)
+int live_open_pcm(emspec_engine* e, LiveState& lv, const emspec_pcm_format& fmt) {
+    int rc;
+    if ((rc = pinned_grow(e, (void**)&lv.h_raw, &lv.hraw_bytes, (size_t)(lv.S / fmt.views) * lv.cap * pcm_frame_bytes(fmt)))) return rc;
+    if ((rc = grow(e, (void**)&lv.d_fresh, &lv.dfresh_bytes, (size_t)lv.S * lv.cap * 4))) return rc;
+    lv.pcm_fmt = fmt;
+    lv.pcm_views = fmt.views;
+    return EMSPEC_OK;
+}
+
+// the staged raw frames (pend of them per source) -> d_fresh, on the engine's stream in front of the frame launch
+int live_decode_pending(emspec_engine* e, LiveState& lv) {
+    HIPCHK(e, pcm_decode(lv.h_raw, lv.pcm_fmt, lv.S / lv.pcm_views, lv.pend[0], lv.cap * pcm_frame_bytes(lv.pcm_fmt), lv.d_fresh,
+                                lv.cap, e->stream));
+    return EMSPEC_OK;
+}
+
+// Moves the staged frames of a PCM session into the device sample rings without a frame (they complete none: a block that
+// does is launched by the call that brings it).  emspec_reset_stream runs it first, so that the streams of a session never
+// differ in what they have staged - the raw block is per source.
+int live_pcm_drain(emspec_engine* e, LiveState& lv) {
+    if (!lv.pcm_views || lv.pend[0] == 0) return EMSPEC_OK;
+    int rc;
+    LiveStream* desc = reinterpret_cast<LiveStream*>(lv.h_desc);
+    for (int s = 0; s < lv.S; ++s) desc[s] = LiveStream{lv.fed[s], lv.newbase[s], 0, lv.pend[s], 0, 0};
+    if ((rc = live_decode_pending(e, lv))) return live_abandon(e, lv, rc);
+    if ((rc = live_launch(e, lv, lv.d_fresh, lv.cap, 0, false, nullptr, nullptr, 1, 1, false))) return live_abandon(e, lv, rc);
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return live_abandon(e, lv, fail(e, EMSPEC_ERR_HIP, "hipStreamSynchronize failed"));
+    for (int s = 0; s < lv.S; ++s) { lv.newbase[s] = lv.seen[s]; lv.pend[s] = 0; }
+    return EMSPEC_OK;
+}
+
 // ---- the calls, on one of the engine's two sessions ----
 
 // (n_high != 0: the multi-resolution form - n is n_low, the frames are n_low samples long and the short band reads the newest
@@ -350,20 +390,33 @@ int64_t push_columns_impl(const emspec_engine* e, const LiveState& lv, int64_t c
 
 // (n_high != 0: the multi-resolution form - n is n_low; max_columns then bounds what the block may complete whether or not an
 // output is given: it is the stride of every block the launch writes)
-int push_impl(emspec_engine* e, LiveState& lv, const float* samples, int32_t streams, int64_t count, int64_t stride, int32_t n,
+// (fmt != null: the PCM form - `block` holds raw interleaved frames, `count` of them per source, source i at block + i * stride
+// BYTES, and streams = sources * fmt->views; as for the multi-resolution form, max_columns always bounds what a block completes)
+int push_impl(emspec_engine* e, LiveState& lv, const void* block, int32_t streams, int64_t count, int64_t stride, int32_t n,
               int32_t hop, int32_t reassign, float* out_db, uint8_t* out_rgba, int32_t rows, int64_t max_columns,
-              int64_t* out_counts, int64_t* out_first_columns, int32_t n_high = 0, int32_t split = 0) {
-    if (!e || (!samples && count > 0) || count < 0 || stride < count) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument, negative count or stride < count");
+              int64_t* out_counts, int64_t* out_first_columns, int32_t n_high = 0, int32_t split = 0,
+              const emspec_pcm_format* fmt = nullptr) {
+    const float* samples = static_cast<const float*>(block);
+    const int fb = fmt ? pcm_frame_bytes(*fmt) : 1;   // (the float form's stride counts samples)
+    if (!e || (!block && count > 0) || count < 0 || stride / fb < count) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument, negative count or stride < count");
     reassign = reassign ? 1 : 0;
     int rc = live_check(e, lv, streams, n, hop, reassign, rows, 2, n_high, split);
     if (rc) return rc;
+    if (lv.form != 0 && (fmt != nullptr) != (lv.pcm_views != 0))
+        return fail(e, EMSPEC_ERR_STATE, lv.pcm_views ? "the live session is a PCM one (emspec_push_samples_pcm); call emspec_reset() before a float call"
+                                                      : "the live session is a float one; call emspec_reset() before a PCM call");
+    if (lv.form != 0 && fmt && !pcm_same_format(*fmt, lv.pcm_fmt))
+        return fail(e, EMSPEC_ERR_STATE, "the PCM format changed mid-stream; call emspec_reset() first");
     if (max_columns < 0) return fail(e, EMSPEC_ERR_INVALID_ARG, "max_columns must be >= 0");
     const int64_t expect = push_columns_impl(e, lv, count, n, hop, reassign);
-    if ((out_db || out_rgba || n_high) && expect > max_columns)
+    if ((out_db || out_rgba || n_high || fmt) && expect > max_columns)
         return fail(e, EMSPEC_ERR_INVALID_ARG, "output holds fewer columns than this block completes (" + std::to_string(expect) +
                                                    "); size it with emspec_push_columns() / emspec_push_columns_multi()");
     HIPCHK(e, hipSetDevice(e->device));
-    if (lv.form == 0 && (rc = live_open(e, lv, streams, n, hop, reassign, 2, n_high, split))) return rc;
+    if (lv.form == 0) {
+        if ((rc = live_open(e, lv, streams, n, hop, reassign, 2, n_high, split, fmt != nullptr))) return rc;
+        if (fmt && (rc = live_open_pcm(e, lv, *fmt))) { live_forget(lv); return rc; }
+    }
     const int S = lv.S, R = e->cfg.rows, D = lv.D;
     float* ddb = reinterpret_cast<float*>(device_view(out_db));
     uint8_t* drgba = reinterpret_cast<uint8_t*>(device_view(out_rgba));
@@ -388,8 +441,12 @@ int push_impl(emspec_engine* e, LiveState& lv, const float* samples, int32_t str
         int maxpend = 0;
         for (int s = 0; s < S; ++s) maxpend = std::max(maxpend, lv.pend[s]);
         const int64_t take = std::min<int64_t>(count - used, lv.cap - maxpend);
+        // (a PCM session: the raw frames of each source; every stream has the same pend - emspec_reset_stream sees to it)
+        for (int i = 0; fmt && i < S / lv.pcm_views; ++i)
+            std::memcpy(lv.h_raw + ((size_t)i * lv.cap + maxpend) * fb, static_cast<const char*>(block) + (size_t)i * stride + (size_t)used * fb,
+                        (size_t)take * fb);
         for (int s = 0; s < S; ++s) {
-            std::memcpy(lv.h_fresh + (size_t)s * lv.cap + lv.pend[s], samples + (size_t)s * stride + used, (size_t)take * 4);
+            if (!fmt) std::memcpy(lv.h_fresh + (size_t)s * lv.cap + lv.pend[s], samples + (size_t)s * stride + used, (size_t)take * 4);
             lv.pend[s] += (int)take;
             lv.seen[s] += take;
         }
@@ -408,7 +465,8 @@ int push_impl(emspec_engine* e, LiveState& lv, const float* samples, int32_t str
             desc[s] = LiveStream{lv.fed[s], lv.newbase[s], M[s], lv.pend[s], direct ? (int)produced[s] : 0, 0};
             if (nc[s] > 0 && first[s] < 0) first[s] = c0;
         }
-        if ((rc = live_launch(e, lv, lv.h_fresh, lv.cap, mx, false, ddb, drgba, direct ? (int)max_columns : lv.mmax,
+        if (fmt && (rc = live_decode_pending(e, lv))) return live_abandon(e, lv, rc);
+        if ((rc = live_launch(e, lv, fmt ? lv.d_fresh : lv.h_fresh, lv.cap, mx, false, ddb, drgba, direct ? (int)max_columns : lv.mmax,
                               direct ? (int)std::min<int64_t>(std::max<int64_t>(expect, 1), 0x7fffffff) : lv.mmax, false)))
             return live_abandon(e, lv, rc);
         inflight = true;
@@ -443,6 +501,8 @@ void live_free(LiveState& lv) {
     if (lv.h_fresh) (void)hipHostFree(lv.h_fresh);
     if (lv.h_odb) (void)hipHostFree(lv.h_odb);
     if (lv.h_orgba) (void)hipHostFree(lv.h_orgba);
+    if (lv.h_raw) (void)hipHostFree(lv.h_raw);
+    (void)hipFree(lv.d_fresh);
     lv = LiveState{};
 }
 }  // namespace
@@ -513,6 +573,29 @@ int emspec_push_samples_multires(emspec_engine* e, const float* samples, int32_t
                      out_counts, out_first_columns, n_high, split_row);
 }
 
+// ---- the live session fed raw interleaved frames (include/emspec.h, PCM front end): sources * views streams
+int emspec_push_samples_pcm(emspec_engine* e, const void* block, const emspec_pcm_format* fmt, int32_t sources, int64_t count,
+                            int64_t stride_bytes, int32_t n, int32_t hop, int32_t reassign, float* out_db, uint8_t* out_rgba,
+                            int32_t rows, int64_t max_columns, int64_t* out_counts, int64_t* out_first_columns) {
+    if (!e) return EMSPEC_ERR_INVALID_ARG;
+    if (const char* why = pcm_format_error(fmt)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
+    if (sources < 1 || sources > 65535) return fail(e, EMSPEC_ERR_INVALID_ARG, "sources * views (the session's streams) must be in 1..65535");
+    return push_impl(e, e->live, block, sources * fmt->views, count, stride_bytes, n, hop, reassign, out_db, out_rgba, rows, max_columns,
+                     out_counts, out_first_columns, 0, 0, fmt);
+}
+
+int emspec_push_samples_pcm_multires(emspec_engine* e, const void* block, const emspec_pcm_format* fmt, int32_t sources,
+                                     int64_t count, int64_t stride_bytes, int32_t n_low, int32_t n_high, int32_t hop,
+                                     int32_t split_row, int32_t reassign, float* out_db, uint8_t* out_rgba, int32_t rows,
+                                     int64_t max_columns, int64_t* out_counts, int64_t* out_first_columns) {
+    if (!e) return EMSPEC_ERR_INVALID_ARG;
+    if (const char* why = pcm_format_error(fmt)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
+    if (sources < 1 || sources > 65535) return fail(e, EMSPEC_ERR_INVALID_ARG, "sources * views (the session's streams) must be in 1..65535");
+    if (const char* why = multires_shape_error(n_low, n_high, hop)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
+    return push_impl(e, e->live, block, sources * fmt->views, count, stride_bytes, n_low, hop, reassign, out_db, out_rgba, rows,
+                     max_columns, out_counts, out_first_columns, n_high, split_row, fmt);
+}
+
 // ---- the renderer's own calls: ONE stream, the same machinery on the engine's second session (e->one).  Until round 5
 // these ran separate code: a frame copy + one to three launches per call (27.8 us, EXACT 39.7 us per emspec_column call).
 int emspec_column(emspec_engine* e, const float* frame, int32_t n, int32_t hop, int32_t reassign, float* out_db,
@@ -566,6 +649,7 @@ int emspec_reset_stream(emspec_engine* e, int32_t stream) {
     if (lv.form == 0) return fail(e, EMSPEC_ERR_STATE, "no live session");
     if (stream < 0 || stream >= lv.S) return fail(e, EMSPEC_ERR_INVALID_ARG, "stream out of range");
     HIPCHK(e, hipSetDevice(e->device));
+    if (int rc = live_pcm_drain(e, lv)) return rc;
     const int Rl = lv.n_high ? lv.split : e->cfg.rows;
     const size_t cellb = e->exact() ? 8 : 4, per = (size_t)lv.slots * Rl * cellb;
     HIPCHK(e, hipMemsetAsync(reinterpret_cast<char*>(lv.d_cells) + (size_t)stream * per, 0, per, e->stream));

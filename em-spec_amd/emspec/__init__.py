@@ -25,6 +25,8 @@ MODE_FAST, MODE_EXACT = 0, 1
 COMM_ID_BYTES = 128
 GATHER_LOOPBACK = 1
 GATHER_PACKED = 2
+PCM_S16, PCM_S24, PCM_S32, PCM_F32 = 1, 2, 3, 4
+PCM_MAX_CHANNELS = PCM_MAX_VIEWS = 8
 
 SYMBOLS = [
     "emspec_default_config", "emspec_create", "emspec_destroy", "emspec_last_error", "emspec_set_colormap",
@@ -40,6 +42,8 @@ SYMBOLS = [
     "emspec_columns", "emspec_columns_flush", "emspec_push_columns_multi", "emspec_push_samples_multi",
     "emspec_reset_stream", "emspec_live_streams",
     "emspec_multires_columns", "emspec_multires_shift", "emspec_batch_multires", "emspec_batch_multires_device",
+    "emspec_pcm_frame_bytes", "emspec_pcm_decode_device", "emspec_batch_pcm", "emspec_batch_pcm_packed",
+    "emspec_push_samples_pcm", "emspec_push_samples_pcm_multires",
     "emspec_columns_multires", "emspec_push_columns_multires", "emspec_push_samples_multires",
 ]
 # the multi-resolution live session's entry points: a library built before they existed (tools/live_multires_rate.py times one
@@ -55,6 +59,85 @@ class Config(C.Structure):
 
 class Out(C.Structure):
     _fields_ = [("db", C.c_void_p), ("rgba", C.c_void_p), ("index", C.c_void_p)]
+
+
+class PcmFormat(C.Structure):
+    """emspec_pcm_format: how raw interleaved frames become float32 streams (include/emspec.h, PCM front end)."""
+    _fields_ = [("sample_type", C.c_int32), ("channels", C.c_int32), ("views", C.c_int32), ("reserved", C.c_int32),
+                ("mix", C.c_float * (PCM_MAX_VIEWS * PCM_MAX_CHANNELS))]
+    TYPES = {"s16": PCM_S16, "s24": PCM_S24, "s32": PCM_S32, "f32": PCM_F32}
+
+    @staticmethod
+    def view_weights(name, channels):
+        """The weights of a named view - the same numbers in every binding: "left" / "right" = channel 0 / 1, "mid" / "side" =
+        0.5 (ch0 + ch1) / 0.5 (ch0 - ch1), "mono" = 1 / channels (rounded to binary32) on every channel."""
+        w = [0.0] * channels
+        if name == "mono":
+            return [float(np.float32(1.0) / np.float32(channels))] * channels
+        if name == "left":
+            w[0] = 1.0
+            return w
+        if channels < 2:
+            raise ValueError(f'view "{name}" needs at least two channels')
+        if name == "right":
+            w[1] = 1.0
+        elif name == "mid":
+            w[0], w[1] = 0.5, 0.5
+        elif name == "side":
+            w[0], w[1] = 0.5, -0.5
+        else:
+            raise ValueError(f'unknown view "{name}"')
+        return w
+
+    @classmethod
+    def make(cls, sample_type, channels, views=("mono",)):
+        """sample_type: PCM_* or "s16" / "s24" / "s32" / "f32"; views: a list of names ("left", "right", "mid", "side", "mono")
+        and / or rows of `channels` weights, or a [views][channels] matrix."""
+        f = cls()
+        f.sample_type = cls.TYPES.get(sample_type, sample_type) if isinstance(sample_type, str) else int(sample_type)
+        f.channels = int(channels)
+        rows = [cls.view_weights(v, channels) if isinstance(v, str) else [float(x) for x in v] for v in views]
+        if not 1 <= len(rows) <= PCM_MAX_VIEWS or not 1 <= channels <= PCM_MAX_CHANNELS or any(len(r) != channels for r in rows):
+            raise ValueError("1..8 views of `channels` (1..8) weights each")
+        f.views = len(rows)
+        flat = [x for r in rows for x in r]
+        for i, x in enumerate(flat):
+            f.mix[i] = x
+        return f
+
+    @property
+    def matrix(self):
+        return np.array(self.mix[:self.views * self.channels], np.float32).reshape(self.views, self.channels)
+
+    @property
+    def frame_bytes(self):
+        return pcm_frame_bytes(self)
+
+    @property
+    def dtype(self):
+        """numpy dtype of one raw sample (S24: uint8, three per sample)."""
+        return {PCM_S16: np.int16, PCM_S24: np.uint8, PCM_S32: np.int32, PCM_F32: np.float32}[self.sample_type]
+
+
+def pcm_frame_bytes(fmt, diag=False):
+    """Bytes per interleaved frame, -1 for an invalid format (emspec_pcm_frame_bytes; no engine, no device)."""
+    return int(load(diag).emspec_pcm_frame_bytes(C.byref(fmt) if fmt is not None else None))
+
+
+def _pcm_rows(src, fmt):
+    """src: [sources][frames * samples-per-frame] (or [sources][frames][channels]) array of the format's dtype, C order ->
+    (array, sources, frames)."""
+    src = np.asarray(src)
+    if src.dtype != fmt.dtype or not src.flags.c_contiguous:
+        raise EmspecError(ERR_INVALID_ARG, f"raw frames must be a C-contiguous {np.dtype(fmt.dtype).name} array")
+    if src.ndim == 1:
+        src = src[None]
+    sources = src.shape[0]
+    row = src.reshape(sources, -1).shape[1] * src.itemsize
+    fb = fmt.frame_bytes
+    if fb <= 0 or row % fb:
+        raise EmspecError(ERR_INVALID_ARG, "invalid format, or a row is not a whole number of frames")
+    return src, sources, row // fb
 
 
 def wire_unpack_host(image, columns, rows, out=None, diag=False):
@@ -170,6 +253,18 @@ def load(diag=False):
     lib.emspec_multires_shift.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     lib.emspec_batch_multires.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.c_int32, C.POINTER(Out)]
+    lib.emspec_pcm_frame_bytes.restype = C.c_int64
+    lib.emspec_pcm_frame_bytes.argtypes = [C.c_void_p]
+    lib.emspec_pcm_decode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.emspec_batch_pcm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                     C.POINTER(Out)]
+    lib.emspec_batch_pcm_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_void_p, C.c_int64, C.c_void_p]
+    lib.emspec_push_samples_pcm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.emspec_push_samples_pcm_multires.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                                     C.c_int64, C.c_void_p, C.c_void_p]
     lib.emspec_batch_multires_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                                  C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if all(hasattr(lib, sym) for sym in OPTIONAL_SYMBOLS):
@@ -396,6 +491,82 @@ class Engine:
         self._chk(self._lib.emspec_batch_packed(self._h, _np_ptr(pcm), S, L, n, hop, int(bool(reassign)), _np_ptr(wire),
                                                 C.c_int64(wire.size), offsets.ctypes.data_as(C.c_void_p)))
         return wire, offsets
+
+    # -- PCM front end: raw interleaved frames in (include/emspec.h) ---------------------------------
+    def pcm_decode_device(self, src_t, fmt, sources, frames, src_stride_bytes=None, offset_bytes=0, out=None, stream=None):
+        """The decode kernel by itself (emspec_pcm_decode_device).  src_t: a CUDA tensor holding the raw bytes (any dtype);
+        source i starts offset_bytes + i * src_stride_bytes into it.  Returns the float32 CUDA tensor [sources * views][frames];
+        enqueued on `stream` (default: the current torch stream), not synchronised."""
+        import torch
+        assert src_t.is_cuda and src_t.is_contiguous()
+        fb = fmt.frame_bytes
+        if src_stride_bytes is None:
+            src_stride_bytes = frames * max(fb, 0)
+        assert fb <= 0 or sources == 0 or offset_bytes + (sources - 1) * src_stride_bytes + frames * fb <= src_t.numel() * src_t.element_size()
+        if out is None:
+            out = torch.empty((sources * max(fmt.views, 0), frames), dtype=torch.float32, device=src_t.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+        st = stream if stream is not None else torch.cuda.current_stream(src_t.device)
+        self._chk(self._lib.emspec_pcm_decode_device(self._h, C.c_void_p(src_t.data_ptr() + offset_bytes), C.byref(fmt), sources,
+                                                     frames, src_stride_bytes, C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream)))
+        return out
+
+    def batch_pcm(self, src, fmt, n, hop, reassign=True, want=("db",)):
+        """emspec_batch from raw frames: src [sources][frames x channels] of fmt.dtype (S24: uint8, 3 per sample) ->
+        {"db", "rgba", "index"} laid out [sources * views][columns][rows]."""
+        src, sources, frames = _pcm_rows(src, fmt)
+        S, Cn = sources * fmt.views, num_columns(frames, n, hop)
+        db = np.empty((S, Cn, self.rows), np.float32) if "db" in want else None
+        rgba = np.empty((S, Cn, self.rows, 4), np.uint8) if "rgba" in want else None
+        idx = np.empty((S, Cn, self.rows), np.uint8) if "index" in want else None
+        out = Out(_np_ptr(db), _np_ptr(rgba), _np_ptr(idx))
+        self._chk(self._lib.emspec_batch_pcm(self._h, _np_ptr(src), C.byref(fmt), sources, frames, n, hop, int(bool(reassign)),
+                                             C.byref(out)))
+        return {"db": db, "rgba": rgba, "index": idx}
+
+    def batch_pcm_packed(self, src, fmt, n, hop, reassign=True, wire=None):
+        """emspec_batch_packed from raw frames: (wire uint8 array, offsets int64 [sources * views + 1]), as batch_packed."""
+        src, sources, frames = _pcm_rows(src, fmt)
+        S, Cn = sources * fmt.views, num_columns(frames, n, hop)
+        if wire is None:
+            wire = np.empty(S * wire_bound(Cn, self.rows), np.uint8)
+        offsets = np.zeros(S + 1, np.int64)
+        self._chk(self._lib.emspec_batch_pcm_packed(self._h, _np_ptr(src), C.byref(fmt), sources, frames, n, hop, int(bool(reassign)),
+                                                    _np_ptr(wire), C.c_int64(wire.size), offsets.ctypes.data_as(C.c_void_p)))
+        return wire, offsets
+
+    def push_samples_pcm(self, block, fmt, n, hop, reassign=True, n_high=0, split_row=0, want_db=True, want_rgba=False, db=None,
+                         rgba=None, count=None, offset=0, max_columns=None):
+        """Live session from raw frames (emspec_push_samples_pcm; n_high != 0: emspec_push_samples_pcm_multires with n = n_low).
+        block [sources][frames x channels] of fmt.dtype; the window of `count` frames from frame `offset` of every row is fed
+        -> (db [sources * views][k][rows], rgba, counts, first_columns) as push_samples_multi."""
+        block, sources, width = _pcm_rows(block, fmt)
+        fb = fmt.frame_bytes
+        if count is None:
+            count = width - offset
+        assert 0 <= offset and offset + count <= width
+        S = sources * fmt.views
+        k = self.push_columns_multires(count, n, n_high, hop, reassign) if n_high else self.push_columns_multi(count, n, hop, reassign)
+        if k < 0:   # (the call itself names the rule the shape breaks)
+            k = 0
+        if db is not None:
+            k = db.shape[1]
+        elif rgba is not None:
+            k = rgba.shape[1]
+        db, rgba = self._live_out(S, k, want_db, want_rgba, db, rgba)
+        counts, firsts = np.empty(S, np.int64), np.empty(S, np.int64)
+        base = C.c_void_p(block.ctypes.data + fb * offset)
+        cap = k if max_columns is None else max_columns
+        if n_high:
+            rc = self._lib.emspec_push_samples_pcm_multires(self._h, base, C.byref(fmt), sources, count, width * fb, n, n_high, hop,
+                                                            split_row, int(bool(reassign)), _np_ptr(db), _np_ptr(rgba), self.rows,
+                                                            cap, _np_ptr(counts), _np_ptr(firsts))
+        else:
+            rc = self._lib.emspec_push_samples_pcm(self._h, base, C.byref(fmt), sources, count, width * fb, n, hop,
+                                                   int(bool(reassign)), _np_ptr(db), _np_ptr(rgba), self.rows, cap,
+                                                   _np_ptr(counts), _np_ptr(firsts))
+        self._chk(rc)
+        return db, rgba, counts, firsts
 
     # -- batch, device-resident torch tensors ---------------------------------
     def batch_device(self, pcm_t, n, hop, reassign=True, db=None, rgba=None, index=None, stream=None):

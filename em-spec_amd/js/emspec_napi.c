@@ -738,6 +738,186 @@ static napi_value PushMulti(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* ---- PCM front end (include/emspec.h: emspec_pcm_format; index.js: pcmFormat) ----
+ * A format crosses as four arguments: sampleType (EMSPEC_PCM_*), channels, views, mix:Float32Array(views*channels).  They are
+ * handed to the library as they are (it names the field that is wrong); the raw frames are a typed array whose element type
+ * must be the format's: Int16Array (S16), Uint8Array (S24, three per sample), Int32Array (S32), Float32Array (F32). */
+static int get_pcm_format(napi_env env, napi_value* argv, emspec_pcm_format* fmt) {
+    memset(fmt, 0, sizeof(*fmt));
+    void* mix = NULL; size_t mlen = 0;
+    if (napi_get_value_int32(env, argv[0], &fmt->sample_type) != napi_ok || napi_get_value_int32(env, argv[1], &fmt->channels) != napi_ok ||
+        napi_get_value_int32(env, argv[2], &fmt->views) != napi_ok || !get_typed(env, argv[3], napi_float32_array, &mix, &mlen, 0)) {
+        napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "format: sampleType, channels, views must be integers and mix a Float32Array (use pcmFormat())");
+        return 0;
+    }
+    const size_t cap = EMSPEC_PCM_MAX_VIEWS * EMSPEC_PCM_MAX_CHANNELS;
+    if (fmt->channels >= 1 && fmt->channels <= EMSPEC_PCM_MAX_CHANNELS && fmt->views >= 1 && fmt->views <= EMSPEC_PCM_MAX_VIEWS &&
+        mlen != (size_t)fmt->channels * (size_t)fmt->views) {
+        napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "format.mix must hold views * channels weights");
+        return 0;
+    }
+    memcpy(fmt->mix, mix, sizeof(float) * (mlen < cap ? mlen : cap));
+    return 1;
+}
+
+/* the raw frames: data and byte length; throws EMSPEC_ERR_INVALID_ARG when the array's element type contradicts the format */
+static int get_pcm_source(napi_env env, napi_value v, const emspec_pcm_format* fmt, void** data, size_t* bytes) {
+    bool is = false;
+    napi_typedarray_type ty; napi_value ab; size_t off, len;
+    if (napi_is_typedarray(env, v, &is) != napi_ok || !is || napi_get_typedarray_info(env, v, &ty, &len, data, &ab, &off) != napi_ok) {
+        napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "raw frames must be an Int16Array, Int32Array, Float32Array or Uint8Array (S24)");
+        return 0;
+    }
+    napi_typedarray_type want; size_t esize;
+    switch (fmt->sample_type) {
+        case EMSPEC_PCM_S16: want = napi_int16_array; esize = 2; break;
+        case EMSPEC_PCM_S24: want = napi_uint8_array; esize = 1; break;
+        case EMSPEC_PCM_S32: want = napi_int32_array; esize = 4; break;
+        case EMSPEC_PCM_F32: want = napi_float32_array; esize = 4; break;
+        default: napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "format.sample_type is not one of EMSPEC_PCM_S16 / _S24 / _S32 / _F32"); return 0;
+    }
+    if (ty != want) {
+        napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "the typed array's element type contradicts format.type (s16: Int16Array, s24: Uint8Array, s32: Int32Array, f32: Float32Array)");
+        return 0;
+    }
+    *bytes = len * esize;
+    return 1;
+}
+
+/* pcmFrameBytes(sampleType, channels, views, mix) -> bytes per frame, -1 for an invalid format (emspec_pcm_frame_bytes) */
+static napi_value PcmFrameBytes(napi_env env, napi_callback_info info) {
+    size_t argc = 4; napi_value argv[4];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 4) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "pcmFrameBytes(sampleType, channels, views, mix)"); return NULL; }
+    emspec_pcm_format fmt;
+    if (!get_pcm_format(env, argv, &fmt)) return NULL;
+    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int64(env, emspec_pcm_frame_bytes(&fmt), &r));
+    return r;
+}
+
+/* (sources, frames) of a raw array: frames = bytes / (sources * frame bytes); 0 when the format is invalid (the library says why) */
+static int pcm_frames(napi_env env, const emspec_pcm_format* fmt, int32_t sources, size_t bytes, int64_t* frames) {
+    const int64_t fb = emspec_pcm_frame_bytes(fmt);
+    *frames = 0;
+    if (fb <= 0) return 1;
+    if (sources < 1 || bytes % ((size_t)sources * (size_t)fb) != 0) {
+        napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "the raw array must hold sources * frames whole frames");
+        return 0;
+    }
+    *frames = (int64_t)(bytes / ((size_t)sources * (size_t)fb));
+    return 1;
+}
+
+/* batchPcm(handle, src, sampleType, channels, views, mix, sources, fftSize, hop, reassign, outDb[, outRgba, outIndex]) -> columns.
+ * emspec_batch_pcm: src holds sources * frames interleaved frames; outputs for sources * views streams. */
+static napi_value BatchPcm(napi_env env, napi_callback_info info) {
+    size_t argc = 13; napi_value argv[13];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 11) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "batchPcm(handle, src, sampleType, channels, views, mix, sources, fftSize, hop, reassign, outDb[, outRgba, outIndex])"); return NULL; }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    emspec_pcm_format fmt; void* src; size_t bytes;
+    if (!get_pcm_format(env, argv + 2, &fmt) || !get_pcm_source(env, argv[1], &fmt, &src, &bytes)) return NULL;
+    int32_t sources, n, hop; int64_t frames; bool reassign;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[6], &sources));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[7], &n));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[8], &hop));
+    NAPI_OK_OR_RETURN(env, napi_coerce_to_bool(env, argv[9], &argv[9]));
+    NAPI_OK_OR_RETURN(env, napi_get_value_bool(env, argv[9], &reassign));
+    if (!pcm_frames(env, &fmt, sources, bytes, &frames)) return NULL;
+    size_t l0 = 0, l1 = 0, l2 = 0; void *p0 = NULL, *p1 = NULL, *p2 = NULL;
+    if (!get_typed(env, argv[10], napi_float32_array, &p0, &l0, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outDb must be a Float32Array"); return NULL; }
+    if (argc > 11 && !get_typed(env, argv[11], napi_uint8_array, &p1, &l1, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outRgba must be a Uint8Array"); return NULL; }
+    if (argc > 12 && !get_typed(env, argv[12], napi_uint8_array, &p2, &l2, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outIndex must be a Uint8Array"); return NULL; }
+    const int64_t C = frames > 0 ? emspec_num_columns(frames, n, hop) : 0;
+    size_t cells = 0;
+    if (p0) cells = l0; else if (p1) cells = l1 / 4; else if (p2) cells = l2;
+    /* (C <= 0: an invalid format or shape - the library rejects it with its message before it touches any output) */
+    if (C > 0 && (cells != (size_t)sources * (size_t)fmt.views * (size_t)C * (size_t)h->rows || (p1 && l1 != 4 * cells) || (p2 && l2 != cells) || (p0 && l0 != cells))) {
+        napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "output arrays must hold exactly sources*views*columns*rows cells, rows = the engine's row count (rgba: 4 bytes per cell)");
+        return NULL;
+    }
+    emspec_out out; memset(&out, 0, sizeof(out));
+    out.db = (float*)p0; out.rgba = (uint8_t*)p1; out.index = (uint8_t*)p2;
+    int rc = emspec_batch_pcm(h->e, src, &fmt, sources, frames, n, hop, reassign ? 1 : 0, &out);
+    if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
+    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int64(env, C, &r));
+    return r;
+}
+
+/* batchPcmPacked(handle, src, sampleType, channels, views, mix, sources, fftSize, hop, reassign, wire, offsets:Float64Array(sources*views+1)) -> columns */
+static napi_value BatchPcmPacked(napi_env env, napi_callback_info info) {
+    size_t argc = 12; napi_value argv[12];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 12) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "batchPcmPacked(handle, src, sampleType, channels, views, mix, sources, fftSize, hop, reassign, wire, offsets)"); return NULL; }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    emspec_pcm_format fmt; void* src; size_t bytes;
+    if (!get_pcm_format(env, argv + 2, &fmt) || !get_pcm_source(env, argv[1], &fmt, &src, &bytes)) return NULL;
+    int32_t sources, n, hop; int64_t frames; bool reassign;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[6], &sources));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[7], &n));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[8], &hop));
+    NAPI_OK_OR_RETURN(env, napi_coerce_to_bool(env, argv[9], &argv[9]));
+    NAPI_OK_OR_RETURN(env, napi_get_value_bool(env, argv[9], &reassign));
+    if (!pcm_frames(env, &fmt, sources, bytes, &frames)) return NULL;
+    void *wire = NULL, *offs = NULL; size_t wlen = 0, olen = 0;
+    if (!get_typed(env, argv[10], napi_uint8_array, &wire, &wlen, 0)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "wire must be a Uint8Array"); return NULL; }
+    const size_t S = frames > 0 ? (size_t)sources * (size_t)fmt.views : 0;
+    if (!get_typed(env, argv[11], napi_float64_array, &offs, &olen, 0) || (S && olen != S + 1)) {
+        napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "offsets must be a Float64Array(sources * views + 1)"); return NULL;
+    }
+    int64_t* o64 = (int64_t*)malloc(sizeof(int64_t) * (S + 1));
+    if (!o64) { napi_throw_error(env, "EMSPEC_ERR_OUT_OF_MEMORY", "out of host memory"); return NULL; }
+    int rc = emspec_batch_pcm_packed(h->e, src, &fmt, sources, frames, n, hop, reassign ? 1 : 0, (uint8_t*)wire, (int64_t)wlen, o64);
+    if (rc == EMSPEC_OK) for (size_t i = 0; i <= S; ++i) ((double*)offs)[i] = (double)o64[i];
+    free(o64);
+    if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
+    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int64(env, emspec_num_columns(frames, n, hop), &r));
+    return r;
+}
+
+/* pushPcm(handle, block, sampleType, channels, views, mix, sources, fftSize, hop, reassign, maxColumns, outDb?, outRgba?,
+ *         outCounts?:Float64Array(sources*views), outFirst?[, nHigh, splitRow]): emspec_push_samples_pcm / _pcm_multires; block holds
+ *         `count` frames of every source, source after source. */
+static napi_value PushPcm(napi_env env, napi_callback_info info) {
+    size_t argc = 17; napi_value argv[17];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 11) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "pushPcm(handle, block, sampleType, channels, views, mix, sources, fftSize, hop, reassign, maxColumns[, outDb, outRgba, outCounts, outFirst, nHigh, splitRow])"); return NULL; }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    emspec_pcm_format fmt; void* blk; size_t bytes;
+    if (!get_pcm_format(env, argv + 2, &fmt) || !get_pcm_source(env, argv[1], &fmt, &blk, &bytes)) return NULL;
+    int32_t sources, n, hop; int64_t maxc, count; bool reassign;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[6], &sources));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[7], &n));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[8], &hop));
+    NAPI_OK_OR_RETURN(env, napi_coerce_to_bool(env, argv[9], &argv[9]));
+    NAPI_OK_OR_RETURN(env, napi_get_value_bool(env, argv[9], &reassign));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[10], &maxc));
+    if (!pcm_frames(env, &fmt, sources, bytes, &count)) return NULL;
+    if (maxc < 0) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "maxColumns must be >= 0"); return NULL; }
+    const int64_t fb = emspec_pcm_frame_bytes(&fmt);
+    const size_t S = fb > 0 ? (size_t)sources * (size_t)fmt.views : 1;
+    void *db = NULL, *rgba = NULL; size_t dblen = 0, rgbalen = 0; double *ocnt = NULL, *ofirst = NULL;
+    if (argc > 11 && !get_typed(env, argv[11], napi_float32_array, &db, &dblen, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outDb must be a Float32Array"); return NULL; }
+    if (argc > 12 && !get_typed(env, argv[12], napi_uint8_array, &rgba, &rgbalen, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outRgba must be a Uint8Array"); return NULL; }
+    if (argc > 13 && !get_f64_out(env, argv[13], S, &ocnt)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outCounts must be a Float64Array(sources * views)"); return NULL; }
+    if (argc > 14 && !get_f64_out(env, argv[14], S, &ofirst)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outFirst must be a Float64Array(sources * views)"); return NULL; }
+    int32_t n_high, split;
+    if (!get_multires_pair(env, argc, argv, 15, &n_high, &split)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "nHigh and splitRow must be integers"); return NULL; }
+    const size_t cells = S * (size_t)maxc * (size_t)h->rows;
+    if (fb > 0 && ((db && dblen != cells) || (rgba && rgbalen != 4 * cells))) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "outDb must hold sources*views*maxColumns*rows floats, outRgba 4x that in bytes"); return NULL; }
+    int64_t* tmp = (int64_t*)malloc(S * 2 * sizeof(int64_t));
+    if (!tmp) { napi_throw_error(env, "EMSPEC_ERR_OUT_OF_MEMORY", "malloc"); return NULL; }
+    const int64_t stride = count * (fb > 0 ? fb : 0);
+    int rc = n_high > 0 ? emspec_push_samples_pcm_multires(h->e, blk, &fmt, sources, count, stride, n, n_high, hop, split, reassign ? 1 : 0,
+                                                           (float*)db, (uint8_t*)rgba, h->rows, maxc, tmp, tmp + S)
+                        : emspec_push_samples_pcm(h->e, blk, &fmt, sources, count, stride, n, hop, reassign ? 1 : 0, (float*)db,
+                                                  (uint8_t*)rgba, h->rows, maxc, tmp, tmp + S);
+    if (rc == EMSPEC_OK) for (size_t s = 0; s < S; ++s) { if (ocnt) ocnt[s] = (double)tmp[s]; if (ofirst) ofirst[s] = (double)tmp[S + s]; }
+    free(tmp);
+    if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
+    return NULL;
+}
+
 static napi_value ResetStream(napi_env env, napi_callback_info info) {
     size_t argc = 2; napi_value argv[2];
     NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -1067,6 +1247,10 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"pushColumnsMulti", NULL, PushColumnsMulti, NULL, NULL, NULL, napi_default, NULL},
         {"resetStream", NULL, ResetStream, NULL, NULL, NULL, napi_default, NULL},
         {"liveStreams", NULL, LiveStreams, NULL, NULL, NULL, napi_default, NULL},
+        {"pcmFrameBytes", NULL, PcmFrameBytes, NULL, NULL, NULL, napi_default, NULL},
+        {"batchPcm", NULL, BatchPcm, NULL, NULL, NULL, napi_default, NULL},
+        {"batchPcmPacked", NULL, BatchPcmPacked, NULL, NULL, NULL, napi_default, NULL},
+        {"pushPcm", NULL, PushPcm, NULL, NULL, NULL, napi_default, NULL},
     };
     napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
     return exports;

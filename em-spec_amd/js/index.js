@@ -119,6 +119,35 @@ class Engine {
     return { maxColumns: o.maxColumns, counts: o.counts, first: o.first, db: o.dbAll, rgba: m.wantRgba ? o.rgbaAll : undefined };
   }
 
+  /**
+   * Live session from raw interleaved frames (emspec_push_samples_pcm / _pcm_multires): the capture buffer in, the columns of
+   * sources * format.views streams out (stream = source * views + view; sources = engine.streams / format.views).
+   * block: `count` frames of every source, source after source, in the typed array of format.type (Int16Array, Int32Array,
+   * Float32Array; Uint8Array for s24) - another element type throws EMSPEC_ERR_INVALID_ARG.  opts: {fftSize, hop, reassign =
+   * true, wantRgba}; with fftSizeHigh + splitRow | splitHz the session is the multi-resolution one (fftSize is then the LOW
+   * band's size, as lowFftSize in pushSamplesMultires).  Returns what pushSamplesMulti returns; flushColumns(),
+   * resetStream(s) and reset() act as on any session.  A float live call on a PCM session (or the reverse), or another format
+   * mid-session, throws EMSPEC_ERR_STATE until reset().
+   */
+  pushSamplesPcm(block, format, opts) {
+    const S = this.streams, sources = S / format.views;
+    const high = opts.fftSizeHigh | 0;
+    const m = high ? this._multiresOpts(opts) : { split: 0, reassign: opts.reassign === undefined ? true : !!opts.reassign, wantRgba: !!opts.wantRgba };
+    const count = block.byteLength / (sources * format.frameBytes);
+    const maxColumns = high ? native.pushColumnsMulti(this._h, count, opts.fftSize, opts.hop, m.reassign, high)
+      : native.pushColumnsMulti(this._h, count, opts.fftSize, opts.hop, m.reassign);
+    let o = this._push;
+    if (!o || o.maxColumns < maxColumns || (m.wantRgba && !o.rgbaAll)) {
+      const cap = Math.max(maxColumns, 1);
+      o = this._push = { maxColumns: cap, dbAll: new Float32Array(native.allocPinned(4 * S * cap * this.rows)),
+        rgbaAll: m.wantRgba ? new Uint8Array(native.allocPinned(4 * S * cap * this.rows)) : undefined,
+        counts: new Float64Array(S), first: new Float64Array(S) };
+    }
+    native.pushPcm(this._h, block, format.sampleType, format.channels, format.views, format.mix, sources, opts.fftSize, opts.hop,
+      m.reassign, o.maxColumns, o.dbAll, m.wantRgba ? o.rgbaAll : undefined, o.counts, o.first, high, m.split);
+    return { maxColumns: o.maxColumns, counts: o.counts, first: o.first, db: o.dbAll, rgba: m.wantRgba ? o.rgbaAll : undefined };
+  }
+
   /** (the split row of opts.splitHz is looked up once per frequency, not per call) */
   _multiresOpts(opts) {
     let split = opts.splitRow;
@@ -190,6 +219,24 @@ class Engine {
    */
   computeColumnsPacked(pcm, S, L, fftSize, hop, reassign, wire, offsets) {
     return native.batchPacked(this._h, pcm, S, L, fftSize, hop, !!reassign, wire, offsets);
+  }
+
+  /**
+   * computeColumns from raw interleaved frames (emspec_batch_pcm): src = `sources` recordings of `frames` frames each, in the
+   * typed array of format.type (see pcmFormat); out as in computeColumns, for sources * format.views streams (stream = source *
+   * views + view).  The raw bytes cross PCIe; one kernel on the device converts and mixes them (DESIGN.md §3.9).  Returns C.
+   */
+  computeColumnsPcm(src, sources, frames, format, fftSize, hop, reassign, out) {
+    if (src.byteLength !== sources * frames * format.frameBytes) throw Object.assign(new Error('src must hold sources * frames frames'), { code: 'EMSPEC_ERR_INVALID_ARG' });
+    return native.batchPcm(this._h, src, format.sampleType, format.channels, format.views, format.mix, sources, fftSize, hop, !!reassign,
+      out.db, out.rgba, out.index);
+  }
+
+  /** computeColumnsPacked from raw interleaved frames (emspec_batch_pcm_packed); offsets: Float64Array(sources * format.views + 1). */
+  computeColumnsPcmPacked(src, sources, frames, format, fftSize, hop, reassign, wire, offsets) {
+    if (src.byteLength !== sources * frames * format.frameBytes) throw Object.assign(new Error('src must hold sources * frames frames'), { code: 'EMSPEC_ERR_INVALID_ARG' });
+    return native.batchPcmPacked(this._h, src, format.sampleType, format.channels, format.views, format.mix, sources, fftSize, hop,
+      !!reassign, wire, offsets);
   }
 
   /** computeColumnsPacked off the JS thread (libuv pool): resolves with C; offsets are filled when it settles. */
@@ -313,7 +360,40 @@ function computeSpectrogramColumn(audioFrame, fftSize, hop, reassign = true) {
   return defaultEngine.computeSpectrogramColumn(audioFrame, fftSize, hop, reassign);
 }
 
+/**
+ * pcmFormat({type: 's16' | 's24' | 's32' | 'f32', channels, views}) -> the format object the PCM calls take
+ * ({type, sampleType, channels, views, mix: Float32Array(views * channels), frameBytes}; emspec_pcm_format).  views: an array of
+ * names - 'left', 'right' (channel 0 / 1), 'mid', 'side' (0.5 (ch0 +- ch1)), 'mono' (1 / channels, rounded to float32, on every
+ * channel) - and / or arrays of `channels` weights; default ['mono'].  frameBytes is emspec_pcm_frame_bytes: -1 for an invalid
+ * format, which the calls then refuse with EMSPEC_ERR_INVALID_ARG naming the field.
+ */
+const PCM_TYPES = { s16: 1, s24: 2, s32: 3, f32: 4 };
+function pcmViewWeights(name, channels) {
+  const w = new Array(channels).fill(0);
+  if (name === 'mono') return w.fill(Math.fround(1 / channels));
+  if (name === 'left') { w[0] = 1; return w; }
+  if (channels < 2) throw new Error(`view "${name}" needs at least two channels`);
+  if (name === 'right') w[1] = 1;
+  else if (name === 'mid') { w[0] = 0.5; w[1] = 0.5; }
+  else if (name === 'side') { w[0] = 0.5; w[1] = -0.5; }
+  else throw new Error(`unknown view "${name}"`);
+  return w;
+}
+function pcmFormat({ type, channels, views = ['mono'] }) {
+  const sampleType = typeof type === 'string' ? (PCM_TYPES[type] || 0) : type | 0;
+  const rows = views.map((v) => (typeof v === 'string' ? pcmViewWeights(v, channels) : Array.from(v)));
+  const mix = new Float32Array(rows.length * channels);
+  rows.forEach((r, v) => {
+    if (r.length !== channels) throw new Error('every view needs `channels` weights');
+    mix.set(r, v * channels);
+  });
+  const f = { type, sampleType, channels: channels | 0, views: rows.length, mix };
+  f.frameBytes = native.pcmFrameBytes(f.sampleType, f.channels, f.views, f.mix);
+  return f;
+}
+
 module.exports = {
+  pcmFormat,
   Engine,
   createEngine: (config) => new Engine(config),
   computeSpectrogramColumn,

@@ -538,6 +538,89 @@ int emspec_push_samples_multires(emspec_engine* e, const float* samples, int32_t
                                  float* out_db, uint8_t* out_rgba, int32_t rows, int64_t max_columns, int64_t* out_counts,
                                  int64_t* out_first_columns);
 
+/*
+ * ---- PCM front end: the buffer an audio source really delivers - interleaved channels of int16,
+ * packed 24-bit, int32 or float32 samples - crosses PCIe as it is, and ONE kernel on the device converts and mixes it into
+ * the mono float32 streams every entry point above takes.  Serves: the reference's use ("optimized for music production and
+ * mixing", README.md) - the left, right, mid and side views of one stereo capture buffer or WAV file - without a
+ * de-interleave / convert / down-mix pass in JavaScript; [BUILD-DEFINED].  Little endian, signed; no resampling.
+ *
+ * A SOURCE is one interleaved recording ([frames][channels]); it yields `views` STREAMS, stream index = source * views + view,
+ * and every output is laid out [sources * views][columns][rows] exactly as emspec_batch lays out [S][columns][rows].
+ * Sample t of view v, with x_c the converted sample of channel c (EMSPEC_PCM_* below; the S16 and S24 conversions are exact):
+ *     acc = mix[v][0] * x_0;   then for c = 1 .. channels-1:   acc = acc + mix[v][c] * x_c
+ * every product and every sum rounded to binary32, channels in ascending order, no fused multiply-add: bit-reproducible
+ * (mid / side with weights +-0.5 is exact).  DEFINITION of every PCM entry point: its result is the result of the
+ * corresponding float entry point on the float32 array this decode yields.  The EXACT mode's input bound (|x| <= 4) applies
+ * to the MIXED value.
+ * Format errors are EMSPEC_ERR_INVALID_ARG with a message naming the field: sample_type not an EMSPEC_PCM_*, channels or views
+ * outside 1..8, reserved != 0, a weight among the first views * channels that is not finite.
+ */
+#define EMSPEC_PCM_S16 1   /* int16 little endian                          value = s * 2^-15 */
+#define EMSPEC_PCM_S24 2   /* 3 bytes little endian, packed (frame = 3*channels bytes)  s * 2^-23 */
+#define EMSPEC_PCM_S32 3   /* int32: (float)s rounded to nearest even, then * 2^-31 */
+#define EMSPEC_PCM_F32 4   /* float32, taken as is */
+#define EMSPEC_PCM_MAX_CHANNELS 8
+#define EMSPEC_PCM_MAX_VIEWS 8
+typedef struct emspec_pcm_format {
+    int32_t sample_type;   /* EMSPEC_PCM_* */
+    int32_t channels;      /* interleaved channels per frame, 1..8 */
+    int32_t views;         /* streams produced per source, 1..8 */
+    int32_t reserved;      /* 0 */
+    float mix[EMSPEC_PCM_MAX_VIEWS * EMSPEC_PCM_MAX_CHANNELS];   /* [views][channels], row-major, first views*channels used */
+} emspec_pcm_format;
+
+/* Bytes per interleaved frame (2 / 3 / 4 / 4 x channels); -1 for an invalid format or NULL.  No engine. */
+int64_t emspec_pcm_frame_bytes(const emspec_pcm_format* fmt);
+
+/*
+ * The decode kernel by itself, for callers that keep their audio on the device (with emspec_batch_device,
+ * emspec_batch_multires_device, emspec_parity_dump_device it gives the PCM form of every device entry).  src_dev: `frames`
+ * frames of each of `sources` sources, source i at src_dev + i * src_stride_bytes (src_stride_bytes >= frames * frame bytes;
+ * pointer and stride any multiple of the sample size - 1 for S24); device memory or page-locked host memory
+ * (emspec_host_alloc), which the kernel reads in place.  pcm_dev [sources * views][frames] float32 on the engine's device.
+ * Enqueued on hip_stream (NULL = the default stream); does not synchronise.  sources, frames >= 0.
+ */
+int emspec_pcm_decode_device(emspec_engine* e, const void* src_dev, const emspec_pcm_format* fmt, int32_t sources,
+                             int64_t frames, int64_t src_stride_bytes, float* pcm_dev, void* hip_stream);
+
+/*
+ * emspec_batch / emspec_batch_packed from raw frames.  src: host memory (page-locked or not), [sources][frames][channels]
+ * samples of fmt->sample_type, tightly packed.  Outputs / wire images as the float entries produce them for sources * views
+ * streams of `frames` samples (offsets: sources * views + 1 entries).  The same pipeline: its copy-in stage moves the raw
+ * bytes (frames * frame bytes per source instead of 4 bytes per stream sample - a sixteenth for four views of 16-bit stereo)
+ * and the decode kernel runs in front of each unit's kernels; units are whole sources, or runs of columns of one source when
+ * there are few.  Errors: those of the float entries, and the format's.
+ */
+int emspec_batch_pcm(emspec_engine* e, const void* src, const emspec_pcm_format* fmt, int32_t sources, int64_t frames,
+                     int32_t n, int32_t hop, int32_t reassign, const emspec_out* out);
+int emspec_batch_pcm_packed(emspec_engine* e, const void* src, const emspec_pcm_format* fmt, int32_t sources, int64_t frames,
+                            int32_t fft_size, int32_t hop, int32_t reassign, uint8_t* wire, int64_t wire_capacity,
+                            int64_t* offsets);
+
+/*
+ * Live session from raw frames: emspec_push_samples_multi / emspec_push_samples_multires for sources * views streams, fed
+ * `count` frames of every source per call, source i at block + i * stride_bytes (stride_bytes >= count * frame bytes; host
+ * memory, page-locked or not).  The session is the engine's live multi-stream session in its per-sample-block form; the
+ * format (sample type, channels, views, weights) is fixed by the first call.  The raw frames join a page-locked staging block
+ * (a block that completes no frame costs no launch); at launch time the decode kernel reads it in place and the frame kernels
+ * read the decoded block on the device.  Outputs, counts and first columns per STREAM, as emspec_push_samples_multi lays them
+ * out; max_columns must hold what the block completes (emspec_push_columns_multi / _multires) even when both outputs are NULL -
+ * EMSPEC_ERR_INVALID_ARG otherwise, nothing fed.  emspec_columns_flush, emspec_reset_stream (per view stream; the other views
+ * of its source continue), emspec_reset, emspec_live_streams (= sources * views) and emspec_push_columns_multi / _multires
+ * act as on any session.  EMSPEC_ERR_STATE until emspec_reset(): a float live call on a PCM session or the reverse, a change
+ * of format, sources or shape mid-session, feeding a flushed stream.  "The same format" means the same sample type, channels,
+ * views and the same BITS of the views * channels weights (-0.0 is not 0.0: the sign of a zero result can differ).
+ * sources * views, the session's streams, must be in 1..65535 as for every live session (EMSPEC_ERR_INVALID_ARG).
+ */
+int emspec_push_samples_pcm(emspec_engine* e, const void* block, const emspec_pcm_format* fmt, int32_t sources, int64_t count,
+                            int64_t stride_bytes, int32_t n, int32_t hop, int32_t reassign, float* out_db, uint8_t* out_rgba,
+                            int32_t rows, int64_t max_columns, int64_t* out_counts, int64_t* out_first_columns);
+int emspec_push_samples_pcm_multires(emspec_engine* e, const void* block, const emspec_pcm_format* fmt, int32_t sources,
+                                     int64_t count, int64_t stride_bytes, int32_t n_low, int32_t n_high, int32_t hop,
+                                     int32_t split_row, int32_t reassign, float* out_db, uint8_t* out_rgba, int32_t rows,
+                                     int64_t max_columns, int64_t* out_counts, int64_t* out_first_columns);
+
 #ifdef __cplusplus
 }
 #endif
