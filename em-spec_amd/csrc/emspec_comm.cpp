@@ -413,11 +413,18 @@ int emspec_gather_columns(emspec_engine* e, const uint8_t* index_dev, int64_t co
     {
     NCCLCHK_ABORT(e, c, ncclGroupStart());
     ncclResult_t nr = ncclSuccess;
-    if (i_send && c->h_sizes[2 * me] > 0) nr = ncclSend(c->d_wire, (size_t)c->h_sizes[2 * me], ncclUint8, root, c->comm, st);
+    // An image may be up to 4.8 GB (2^32 - 1 cells); one ncclSend / ncclRecv of more than 2^31 bytes arrived damaged (the
+    // gather of 2^22 - 1 columns x 1,024 rows, a 2.77 GB image: tests/test_gpu_sizes.py), so an image travels in pieces of at
+    // most 1 GiB - the same pieces on both sides, matched in order within the group.  An image under 1 GiB is one transfer, as before.
+    constexpr size_t kMaxTransfer = (size_t)1 << 30;
+    if (i_send)
+        for (size_t o = 0, nbytes = (size_t)c->h_sizes[2 * me]; o < nbytes && nr == ncclSuccess; o += kMaxTransfer)
+            nr = ncclSend(c->d_wire + o, std::min(kMaxTransfer, nbytes - o), ncclUint8, root, c->comm, st);
     if (is_root)
         for (int r = 0; r < world && nr == ncclSuccess; ++r)
-            if (c->h_sizes[2 * r] > 0 && (r != me || loopback))
-                nr = ncclRecv(recv_base + off[r], (size_t)c->h_sizes[2 * r], ncclUint8, r, c->comm, st);
+            if (r != me || loopback)
+                for (size_t o = 0, nbytes = (size_t)c->h_sizes[2 * r]; o < nbytes && nr == ncclSuccess; o += kMaxTransfer)
+                    nr = ncclRecv(recv_base + off[r] + o, std::min(kMaxTransfer, nbytes - o), ncclUint8, r, c->comm, st);
     const ncclResult_t ge = ncclGroupEnd();
     if (nr != ncclSuccess || ge != ncclSuccess) {
         abort_comm(c);
