@@ -117,17 +117,7 @@ __global__ __launch_bounds__(1024, 4) void fused4096_pp3_kernel(
                     const int cell = t << 2;
                     int sl = sk - 2 - D;
                     sl += sl < 0 ? SLOTS : 0;
-                    float4* cellp = reinterpret_cast<float4*>(ring + __umul24((unsigned)sl, (unsigned)R) + cell);
-                    const float4 e4 = *cellp;
-                    *cellp = make_float4(0.f, 0.f, 0.f, 0.f);
-                    const float d0 = cell_db_fast(dm, e4.x), d1 = cell_db_fast(dm, e4.y);
-                    const float d2 = cell_db_fast(dm, e4.z), d3 = cell_db_fast(dm, e4.w);
-                    const int i0 = cell_index(dm, d0), i1 = cell_index(dm, d1), i2 = cell_index(dm, d2), i3 = cell_index(dm, d3);
-                    const size_t o = ((size_t)s * C + col) * R + cell;
-                    if (db) *reinterpret_cast<float4*>(db + o) = make_float4(d0, d1, d2, d3);
-                    if (rgba) *reinterpret_cast<uint4*>(rgba + o) = make_uint4(slut[i0], slut[i1], slut[i2], slut[i3]);
-                    if (index) *reinterpret_cast<uint32_t*>(index + o) =
-                        (uint32_t)i0 | ((uint32_t)i1 << 8) | ((uint32_t)i2 << 16) | ((uint32_t)i3 << 24);
+                    finalize_ring_quad(ring, sl, R, cell, dm, slut, ((size_t)s * C + col) * R + cell, db, rgba, index);
                 }
             }
             EMSPEC_STAMP(0)
@@ -172,16 +162,7 @@ __global__ __launch_bounds__(1024, 4) void fused4096_pp3_kernel(
                 // per-bin stages: bins 4g .. 4g+3 from F(i) = Z[4g-1+i], M(i) = Z[N-4g+1-i], i = 0..5 (fused_r8.hip.inc)
                 __builtin_amdgcn_s_setprio(2);
                 float yr[6], yi[6], ur[6], tr[6];
-                {
-                    float2 f[6], m[6];     // all twelve spectrum reads issued before the first use (fused_r8.hip.inc)
-#pragma unroll
-                    for (int i = 0; i < 6; ++i) { f[i] = fb[fpos[i]]; m[i] = fb[mpos[i]]; }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int i = 0; i < 6; ++i) {
-                        yr[i] = f[i].x + m[i].x; yi[i] = f[i].y - m[i].y; ur[i] = f[i].x - m[i].x; tr[i] = f[i].y + m[i].y;   // ur = -Ti
-                    }
-                }
+                read_split6(fb, fpos, mpos, yr, yi, ur, tr);   // all twelve reads issued before the first use
                 // this wave's reads of the frame buffer are done (the LDS pipe serves one wave's operations in order, so
                 // the counter moves after them): tell the team
                 asm volatile("" ::: "memory");
@@ -193,42 +174,7 @@ __global__ __launch_bounds__(1024, 4) void fused4096_pp3_kernel(
                 const unsigned span = (unsigned)(c1 - c0);
                 const float Df = (float)D;
                 const float kf0 = (float)(4 * (((tt & 63) << 3) | (tt >> 6)));
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float Ar = twice_minus(yr[e + 1], yr[e] + yr[e + 2]), Ai = twice_minus(yi[e + 1], yi[e] + yi[e + 2]);
-                    const float Br = twice_minus(tr[e + 1], tr[e] + tr[e + 2]), Ui = twice_minus(ur[e + 1], ur[e] + ur[e + 2]);
-                    const float Dr = yr[e] - yr[e + 2], Di = yi[e] - yi[e + 2];
-                    const float den = __builtin_fmaf(Ar, Ar, Ai * Ai);
-                    const float P = den * 0.015625f;
-                    bool ok = (P >= pl.pfloor_abs) && (P <= kPowerMax);
-                    const float kf = kf0 + (float)e;
-                    float kh = kf;
-                    int d = DMAX;
-                    if (FAST || pl.reassign) {
-                        const float numT = __builtin_fmaf(Br, Ar, -(Ui * Ai));
-                        const float numF = __builtin_fmaf(Dr, Ar, Di * Ai);
-                        const float inv = FAST ? recip_normal(den) : 1.0f / den;
-                        const float cf = __builtin_floorf(__builtin_fmaf(numT * inv, pl.tscale, 0.5f));
-                        ok = ok && (__builtin_fabsf(cf) <= Df);
-                        d = (int)cf + DMAX;
-                        kh = kf + numF * inv;
-                    }
-                    const int rr = FAST ? lk.row_signed_log(kh) : lk.row_signed(kh);   // -1 / R when k-hat is off the frequency axis
-                    ok = ok && ((unsigned)rr < (unsigned)R);
-                    ok = ok && ((unsigned)(jrel + d - DMAX) < span);
-                    unsigned sl = (unsigned)(sbase + d);   // garbage when !ok: the cell is then never touched
-                    sl = min(sl, sl - (unsigned)SLOTS);
-                    cellp[e] = ring + __umul24(sl, (unsigned)R) + rr;
-                    pw[e] = P;
-                    okv[e] = ok;
-                }
-                // a lane's consecutive bins often share a cell: sum such runs in registers first
-#pragma unroll
-                for (int e = 0; e < 3; ++e) {
-                    const bool same = okv[e] && okv[e + 1] && (cellp[e] == cellp[e + 1]);
-                    pw[e + 1] = same ? pw[e + 1] + pw[e] : pw[e + 1];
-                    okv[e] = okv[e] && !same;
-                }
+                bins4<FAST>(pl.pfloor_abs, pl.reassign, pl.tscale, lk, yr, yi, ur, tr, kf0, sbase, jrel, span, Df, ring, R, DMAX, SLOTS, cellp, pw, okv);   // fused_common.hip.inc
                 EMSPEC_STAMP(2)
                 if constexpr (STAMP) {   // diagnostic build: slot 7 counts accumulate rounds (4 calls per frame)
                     acc_[7] += lds_accumulate_counted(cellp[0], pw[0], okv[0]);

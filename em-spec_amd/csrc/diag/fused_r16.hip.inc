@@ -254,17 +254,7 @@ __global__ __launch_bounds__(512, 2) void fused4096_kernel(
                     int sl = sj_even - D + cc;
                     sl += sl < 0 ? SLOTS : 0;
                     sl -= sl >= SLOTS ? SLOTS : 0;
-                    float4* cellp = reinterpret_cast<float4*>(ring + __umul24((unsigned)sl, (unsigned)R) + cell);
-                    const float4 e4 = *cellp;
-                    *cellp = make_float4(0.f, 0.f, 0.f, 0.f);
-                    const float d0 = cell_db_fast(dm, e4.x), d1 = cell_db_fast(dm, e4.y);
-                    const float d2 = cell_db_fast(dm, e4.z), d3 = cell_db_fast(dm, e4.w);
-                    const int i0 = cell_index(dm, d0), i1 = cell_index(dm, d1), i2 = cell_index(dm, d2), i3 = cell_index(dm, d3);
-                    const size_t o = ((size_t)s * C + col) * R + cell;
-                    if (db) *reinterpret_cast<float4*>(db + o) = make_float4(d0, d1, d2, d3);
-                    if (rgba) *reinterpret_cast<uint4*>(rgba + o) = make_uint4(slut[i0], slut[i1], slut[i2], slut[i3]);
-                    if (index) *reinterpret_cast<uint32_t*>(index + o) =
-                        (uint32_t)i0 | ((uint32_t)i1 << 8) | ((uint32_t)i2 << 16) | ((uint32_t)i3 << 24);
+                    finalize_ring_quad(ring, sl, R, cell, dm, slut, ((size_t)s * C + col) * R + cell, db, rgba, index);
                 }
             }
         }

@@ -67,9 +67,8 @@ static constexpr int fused_variant() { return 0; }
 static constexpr bool diag_no_fused() { return false; }
 #endif
 
-// the specialised (FAST) kernels: reassignment ON, log-spaced rows, and a power floor that keeps every accumulated
-// bin's 64 P inside the range of recip_normal (emspec_device.h)
-static bool fast_plan(const PlanDev& pl) { return pl.reassign && pl.log_rows && pl.pfloor_abs >= kFastMinFloor; }
+// (the specialised FAST kernels serve the plans of emspec_plan_is_fast, emspec_device.h: reassignment ON, log-spaced rows, and
+// a power floor that keeps every accumulated bin's 64 P inside the range of recip_normal)
 
 bool fused_supported(int n, int hop, int rows, int reassign) {
     if (diag_no_fused()) return false;
@@ -176,13 +175,10 @@ hipError_t launch_fused(int n, const PlanDev& pl, const DbMap& m, const uint8_t*
     if (stamp_groups) *stamp_groups = nseg * S;
     const uint32_t* l32 = reinterpret_cast<const uint32_t*>(lut);
     uint32_t* r32 = reinterpret_cast<uint32_t*>(rgba);
-    hipError_t e;
-#define EMSPEC_LAUNCH(kern, lds, ...)                                                   \
-    do {                                                                                \
-        if ((e = allow_max_lds(reinterpret_cast<const void*>(&kern))) != hipSuccess) return e; \
-        hipLaunchKernelGGL(kern, grid, block, lds, st, __VA_ARGS__);                    \
-        return hipGetLastError();                                                       \
-    } while (0)
+    const bool fast = emspec_plan_is_fast(pl);   // the usual case, specialised (one basic block per-bin stage)
+    auto go = [&](auto kernel, dim3 blk, size_t lds, auto... more) {
+        return launch_k(kernel, grid, blk, lds, st, pl, m, l32, pcm, L, C, sp, db, r32, index, more...);
+    };
     if (big_n) {
         if (stamp_groups && !stamps) return hipSuccess;            // sizing call of the diagnostic entry point
         return launch_fused16384(grid, pl, m, l32, pcm, L, C, sp, db, r32, index, st, stamps);
@@ -190,115 +186,57 @@ hipError_t launch_fused(int n, const PlanDev& pl, const DbMap& m, const uint8_t*
     if (small_n) {
         if (stamps || stamp_groups) return hipErrorNotSupported;   // no stamped build of this kernel
         const int slots = fused_small_slots(n, pl.D);
-        const size_t lds = fused_small_lds_bytes(pl.rows, slots);
+        auto go_small = [&](auto kernel) {
+            return launch_k(kernel, grid, block, fused_small_lds_bytes(pl.rows, slots), st, pl, m, l32, pcm, L, C, sp, slots, db, r32, index);
+        };
+        return pick_int<0, 1, 2>(n == 4096 ? 0 : (n == 2048 ? 1 : 2), [&](auto S_) { return pick_bool(fast, [&](auto FA) {
 #ifdef EMSPEC_DIAG
-        if (fused_variant() == 3) {   // the lock-step form (A/B)
-            if (fast_plan(pl)) {
-                if (n == 4096) EMSPEC_LAUNCH((fused_small_kernel<0, true>), lds, pl, m, l32, pcm, L, C, sp, slots, db, r32, index);
-                if (n == 2048) EMSPEC_LAUNCH((fused_small_kernel<1, true>), lds, pl, m, l32, pcm, L, C, sp, slots, db, r32, index);
-                EMSPEC_LAUNCH((fused_small_kernel<2, true>), lds, pl, m, l32, pcm, L, C, sp, slots, db, r32, index);
-            }
-            if (n == 4096) EMSPEC_LAUNCH((fused_small_kernel<0>), lds, pl, m, l32, pcm, L, C, sp, slots, db, r32, index);
-            if (n == 2048) EMSPEC_LAUNCH((fused_small_kernel<1>), lds, pl, m, l32, pcm, L, C, sp, slots, db, r32, index);
-            EMSPEC_LAUNCH((fused_small_kernel<2>), lds, pl, m, l32, pcm, L, C, sp, slots, db, r32, index);
-        }
+            if (fused_variant() == 3) return go_small(fused_small_kernel<S_(), FA()>);   // the lock-step form (A/B)
 #endif
-        if (fast_plan(pl)) {
-            if (n == 4096) EMSPEC_LAUNCH((fused_small_pp_kernel<0, true>), lds, pl, m, l32, pcm, L, C, sp, slots, db, r32, index);
-            if (n == 2048) EMSPEC_LAUNCH((fused_small_pp_kernel<1, true>), lds, pl, m, l32, pcm, L, C, sp, slots, db, r32, index);
-            EMSPEC_LAUNCH((fused_small_pp_kernel<2, true>), lds, pl, m, l32, pcm, L, C, sp, slots, db, r32, index);
-        }
-        if (n == 4096) EMSPEC_LAUNCH((fused_small_pp_kernel<0>), lds, pl, m, l32, pcm, L, C, sp, slots, db, r32, index);
-        if (n == 2048) EMSPEC_LAUNCH((fused_small_pp_kernel<1>), lds, pl, m, l32, pcm, L, C, sp, slots, db, r32, index);
-        EMSPEC_LAUNCH((fused_small_pp_kernel<2>), lds, pl, m, l32, pcm, L, C, sp, slots, db, r32, index);
+            return go_small(fused_small_pp_kernel<S_(), FA()>);
+        }); });
     }
     if (n == f13::N) {
         if (stamps || stamp_groups) return hipErrorNotSupported;   // no stamped build of this kernel
-        const size_t lds = fused8192_lds_bytes(pl.rows, pl.hop);
-        if (fast_plan(pl)) {
-            if (pl.hop == 512) EMSPEC_LAUNCH((fused8192_kernel<512, true>), lds, pl, m, l32, pcm, L, C, sp, db, r32, index);
-            EMSPEC_LAUNCH((fused8192_kernel<1024, true>), lds, pl, m, l32, pcm, L, C, sp, db, r32, index);
-        }
-        if (pl.hop == 512) EMSPEC_LAUNCH((fused8192_kernel<512>), lds, pl, m, l32, pcm, L, C, sp, db, r32, index);
-        EMSPEC_LAUNCH((fused8192_kernel<1024>), lds, pl, m, l32, pcm, L, C, sp, db, r32, index);
+        return pick_int<512, 1024>(pl.hop, [&](auto H) { return pick_bool(fast, [&](auto FA) {
+            return go(fused8192_kernel<H(), FA()>, block, fused8192_lds_bytes(pl.rows, pl.hop));
+        }); });
     }
+    // N = 4096 at hop 256 / 512 / 1024: a kernel family <HOP, STAMP, FAST>; name(H, ST, FA) gives the instantiation.  The
+    // stamped (diagnostic) builds exist for hop 256 only, and stamp_groups alone is the sizing call of their entry point.
+    auto family = [&](size_t lds, auto name) -> hipError_t {
 #ifdef EMSPEC_DIAG
-    if (fused_variant() == 2) {
+        if (stamps || stamp_groups) {
+            if (pl.hop != 256) return hipErrorNotSupported;
+            if (!stamps) return hipSuccess;
+            return pick_bool(fast, [&](auto FA) { return go(name(std::integral_constant<int, 256>{}, std::true_type{}, FA), block, lds, stamps); });
+        }
+#endif
+        return pick_int<256, 512, 1024>(pl.hop, [&](auto H) { return pick_bool(fast, [&](auto FA) {
+            return go(name(H, std::false_type{}, FA), block, lds, nullptr);
+        }); });
+    };
+#ifdef EMSPEC_DIAG
+    if (fused_variant() == 2) {   // decoupled teams (A/B)
         int* ef = fused_errflag();
         if (!ef) return hipErrorOutOfMemory;
-        if (stamps) EMSPEC_LAUNCH((fused4096_r8t_kernel<true>), fused_r8t_lds_bytes(pl.rows), pl, m, l32, pcm, L, C, sp, db, r32, index, stamps, ef);
+        if (stamps) return go(fused4096_r8t_kernel<true>, block, fused_r8t_lds_bytes(pl.rows), stamps, ef);
         if (stamp_groups) return hipSuccess;
-        EMSPEC_LAUNCH((fused4096_r8t_kernel<false>), fused_r8t_lds_bytes(pl.rows), pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr, ef);
+        return go(fused4096_r8t_kernel<false>, block, fused_r8t_lds_bytes(pl.rows), nullptr, ef);
     }
-    if (fused_variant() == 3) {   // the lock-step kernel (A/B)
-        const size_t l8 = fused_r8_lds_bytes(pl.rows, pl.hop);
-        if (stamps || stamp_groups) {
-            if (pl.hop != 256) return hipErrorNotSupported;
-            if (!stamps) return hipSuccess;
-            if (fast_plan(pl)) EMSPEC_LAUNCH((fused4096_r8_kernel<256, true, true>), l8, pl, m, l32, pcm, L, C, sp, db, r32, index, stamps);
-            EMSPEC_LAUNCH((fused4096_r8_kernel<256, true>), l8, pl, m, l32, pcm, L, C, sp, db, r32, index, stamps);
-        }
-        if (fast_plan(pl)) {
-            if (pl.hop == 256) EMSPEC_LAUNCH((fused4096_r8_kernel<256, false, true>), l8, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-            if (pl.hop == 512) EMSPEC_LAUNCH((fused4096_r8_kernel<512, false, true>), l8, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-            EMSPEC_LAUNCH((fused4096_r8_kernel<1024, false, true>), l8, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-        }
-        if (pl.hop == 256) EMSPEC_LAUNCH((fused4096_r8_kernel<256, false>), l8, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-        if (pl.hop == 512) EMSPEC_LAUNCH((fused4096_r8_kernel<512, false>), l8, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-        EMSPEC_LAUNCH((fused4096_r8_kernel<1024, false>), l8, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-    }
-    if (fused_variant() == 4 && fast_plan(pl)) {   // team barriers (A/B)
-        const size_t l4 = fused_pp_lds_bytes(pl.rows, pl.hop);
-        if (stamps || stamp_groups) {
-            if (pl.hop != 256) return hipErrorNotSupported;
-            if (!stamps) return hipSuccess;
-            EMSPEC_LAUNCH((fused4096_pp3_kernel<256, true, true, true>), l4, pl, m, l32, pcm, L, C, sp, db, r32, index, stamps);
-        }
-        if (pl.hop == 256) EMSPEC_LAUNCH((fused4096_pp3_kernel<256, false, true, true>), l4, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-        if (pl.hop == 512) EMSPEC_LAUNCH((fused4096_pp3_kernel<512, false, true, true>), l4, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-        EMSPEC_LAUNCH((fused4096_pp3_kernel<1024, false, true, true>), l4, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-    }
-    if (fused_variant() == 5) {   // round 3's form of the product kernel (A/B)
-        const size_t l5 = fused_pp_lds_bytes(pl.rows, pl.hop);
-        if (stamps || stamp_groups) {
-            if (pl.hop != 256) return hipErrorNotSupported;
-            if (!stamps) return hipSuccess;
-            if (fast_plan(pl)) EMSPEC_LAUNCH((fused4096_pp3_kernel<256, true, true>), l5, pl, m, l32, pcm, L, C, sp, db, r32, index, stamps);
-            EMSPEC_LAUNCH((fused4096_pp3_kernel<256, true>), l5, pl, m, l32, pcm, L, C, sp, db, r32, index, stamps);
-        }
-        if (fast_plan(pl)) {
-            if (pl.hop == 256) EMSPEC_LAUNCH((fused4096_pp3_kernel<256, false, true>), l5, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-            if (pl.hop == 512) EMSPEC_LAUNCH((fused4096_pp3_kernel<512, false, true>), l5, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-            EMSPEC_LAUNCH((fused4096_pp3_kernel<1024, false, true>), l5, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-        }
-        if (pl.hop == 256) EMSPEC_LAUNCH((fused4096_pp3_kernel<256, false>), l5, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-        if (pl.hop == 512) EMSPEC_LAUNCH((fused4096_pp3_kernel<512, false>), l5, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-        EMSPEC_LAUNCH((fused4096_pp3_kernel<1024, false>), l5, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-    }
-    if (fused_variant() == 1) {
-        const dim3 block(512);
-        if (stamps) EMSPEC_LAUNCH((fused4096_kernel<true>), fused_lds_bytes(pl.rows), pl, m, l32, pcm, L, C, sp, db, r32, index, stamps);
+    if (fused_variant() == 3)   // the lock-step kernel (A/B)
+        return family(fused_r8_lds_bytes(pl.rows, pl.hop), [](auto H, auto ST, auto FA) { return fused4096_r8_kernel<H(), ST(), FA()>; });
+    if (fused_variant() == 4 && fast)   // team barriers (A/B): built for fast plans only
+        return family(fused_pp_lds_bytes(pl.rows, pl.hop), [](auto H, auto ST, auto) { return fused4096_pp3_kernel<H(), ST(), true, true>; });
+    if (fused_variant() == 5)   // round 3's form of the product kernel (A/B)
+        return family(fused_pp_lds_bytes(pl.rows, pl.hop), [](auto H, auto ST, auto FA) { return fused4096_pp3_kernel<H(), ST(), FA()>; });
+    if (fused_variant() == 1) {   // 512 threads, radix 16 (A/B)
+        if (stamps) return go(fused4096_kernel<true>, dim3(512), fused_lds_bytes(pl.rows), stamps);
         if (stamp_groups) return hipSuccess;
-        EMSPEC_LAUNCH((fused4096_kernel<false>), fused_lds_bytes(pl.rows), pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-    }
-    if (stamps || stamp_groups) {
-        if (pl.hop != 256) return hipErrorNotSupported;   // the stamped (diagnostic) build exists for hop 256 only
-        if (!stamps) return hipSuccess;
-        if (fast_plan(pl))
-            EMSPEC_LAUNCH((fused4096_pp_kernel<256, true, true>), fused_pp_lds_bytes(pl.rows, pl.hop), pl, m, l32, pcm, L, C, sp, db, r32, index, stamps);
-        EMSPEC_LAUNCH((fused4096_pp_kernel<256, true>), fused_pp_lds_bytes(pl.rows, pl.hop), pl, m, l32, pcm, L, C, sp, db, r32, index, stamps);
+        return go(fused4096_kernel<false>, dim3(512), fused_lds_bytes(pl.rows), nullptr);
     }
 #endif
-    const size_t lp = fused_pp_lds_bytes(pl.rows, pl.hop);
-    if (fast_plan(pl)) {   // the usual case, specialised (one basic block per-bin stage)
-        if (pl.hop == 256) EMSPEC_LAUNCH((fused4096_pp_kernel<256, false, true>), lp, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-        if (pl.hop == 512) EMSPEC_LAUNCH((fused4096_pp_kernel<512, false, true>), lp, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-        EMSPEC_LAUNCH((fused4096_pp_kernel<1024, false, true>), lp, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-    }
-    if (pl.hop == 256) EMSPEC_LAUNCH((fused4096_pp_kernel<256, false>), lp, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-    if (pl.hop == 512) EMSPEC_LAUNCH((fused4096_pp_kernel<512, false>), lp, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-    EMSPEC_LAUNCH((fused4096_pp_kernel<1024, false>), lp, pl, m, l32, pcm, L, C, sp, db, r32, index, nullptr);
-#undef EMSPEC_LAUNCH
+    return family(fused_pp_lds_bytes(pl.rows, pl.hop), [](auto H, auto ST, auto FA) { return fused4096_pp_kernel<H(), ST(), FA()>; });
 }
 
 }  // namespace emspec

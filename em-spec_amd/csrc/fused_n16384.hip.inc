@@ -358,14 +358,7 @@ __global__ __launch_bounds__(1024) void fused16384_kernel(
         if (te < (R >> 2)) {
             const int sl = (int)((col - (jlo - D)) % slots);       // slot of column c: (c - (jlo - D)) mod slots
             const float4 e4 = reinterpret_cast<const float4*>(ring)[sl * (R >> 2) + te];
-            const float d0 = cell_db_fast(dm, e4.x), d1 = cell_db_fast(dm, e4.y);
-            const float d2 = cell_db_fast(dm, e4.z), d3 = cell_db_fast(dm, e4.w);
-            const int i0 = cell_index(dm, d0), i1 = cell_index(dm, d1), i2 = cell_index(dm, d2), i3 = cell_index(dm, d3);
-            const size_t o = ((size_t)s * C + col) * R + ((size_t)te << 2);
-            if (db) *reinterpret_cast<float4*>(db + o) = make_float4(d0, d1, d2, d3);
-            if (rgba) *reinterpret_cast<uint4*>(rgba + o) = make_uint4(slut[i0], slut[i1], slut[i2], slut[i3]);
-            if (index) *reinterpret_cast<uint32_t*>(index + o) =
-                (uint32_t)i0 | ((uint32_t)i1 << 8) | ((uint32_t)i2 << 16) | ((uint32_t)i3 << 24);
+            store_cells4<true>(dm, slut, e4, ((size_t)s * C + col) * R + ((size_t)te << 2), db, rgba, index);
         }
     }
     if constexpr (STAMP) {
@@ -383,34 +376,15 @@ __global__ __launch_bounds__(1024) void fused16384_kernel(
 static hipError_t launch_fused16384(dim3 grid, const PlanDev& pl, const DbMap& m, const uint32_t* lut, const float* pcm,
                                     int64_t L, int64_t C, SegPlan seg, float* db, uint32_t* rgba, uint8_t* index,
                                     hipStream_t st, unsigned long long* stamps) {
+    return pick_bool(emspec_plan_is_fast(pl), [&](auto FA) {
+        auto go = [&](auto kernel) {
+            return launch_k(kernel, grid, dim3(1024), fused16384_lds_bytes(pl.rows), st, pl, m, lut, pcm, L, C, seg, db, rgba, index, stamps);
+        };
 #ifdef EMSPEC_DIAG
-    if (stamps) {
-        if (pl.reassign && pl.log_rows && pl.pfloor_abs >= kFastMinFloor) {   // the stamped build of the kernel the product runs for this plan
-            const hipError_t e = allow_max_lds(reinterpret_cast<const void*>(&fused16384_kernel<true, true>));
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((fused16384_kernel<true, true>), grid, dim3(1024), fused16384_lds_bytes(pl.rows), st, pl, m, lut, pcm, L, C,
-                               seg, db, rgba, index, stamps);
-            return hipGetLastError();
-        }
-        const hipError_t e = allow_max_lds(reinterpret_cast<const void*>(&fused16384_kernel<true>));
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(fused16384_kernel<true>, grid, dim3(1024), fused16384_lds_bytes(pl.rows), st, pl, m, lut, pcm, L, C,
-                           seg, db, rgba, index, stamps);
-        return hipGetLastError();
-    }
+        if (stamps) return go(fused16384_kernel<true, FA()>);   // the stamped build of the kernel the product runs for this plan
 #endif
-    if (pl.reassign && pl.log_rows && pl.pfloor_abs >= kFastMinFloor) {
-        const hipError_t e = allow_max_lds(reinterpret_cast<const void*>(&fused16384_kernel<false, true>));
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((fused16384_kernel<false, true>), grid, dim3(1024), fused16384_lds_bytes(pl.rows), st, pl, m, lut, pcm, L, C, seg,
-                           db, rgba, index, nullptr);
-        return hipGetLastError();
-    }
-    const hipError_t e = allow_max_lds(reinterpret_cast<const void*>(&fused16384_kernel<false>));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(fused16384_kernel<false>, grid, dim3(1024), fused16384_lds_bytes(pl.rows), st, pl, m, lut, pcm, L, C, seg,
-                       db, rgba, index, nullptr);
-    return hipGetLastError();
+        return go(fused16384_kernel<false, FA()>);
+    });
 }
 
 }  // namespace emspec

@@ -1,5 +1,7 @@
 // fused_n8192.hip.inc — fused batch kernel for N = 8192 on the skeleton of fused_r8.hip.inc.
-// Included by kernels.hip after fused_r8.hip.inc (it reuses f8::swz / zpos / stages8 / TwLds).
+// Included by kernels.hip after fused_r8.hip.inc (it reuses f8::swz / zpos / stages8 / TwLds).  Its finalize, spectrum split
+// and four-bin stage are still spelled out here, in the order of fused_common.hip.inc's finalize_ring_quad, read_split6 and
+// bins4: calling them reschedules this kernel (profiles/refactor_fused_common_isa.txt), so that waits for an A/B measurement.
 //
 // The first stage of the canonical radix-2 DIF network splits an 8192-point frame into two
 // independent 4096-point transforms:

@@ -1,6 +1,9 @@
 // fused_pp.hip.inc — fused batch kernel for N = 4096 (hop 256, 512 or 1024), the two 8-wave teams HALF AN ITERATION
 // APART.  The product path since round 3; in its present form (spectrum reads in role 0) since round 4.
-// Included by fused.hip.inc after fused_r8.hip.inc (same arithmetic, LDS images, swizzle and helpers: namespace f8).
+// Included by fused.hip.inc after fused_r8.hip.inc (same LDS images, swizzle and FFT helpers: namespace f8).  The arithmetic
+// between the FFT and the output arrays is the one definition of fused_common.hip.inc (finalize_ring_quad, read_split6); the
+// four-bin stage is still spelled out here, in the order of fused_common's bins4 - calling it reschedules this kernel
+// (profiles/refactor_fused_common_isa.txt), so it waits for an A/B measurement.
 //
 // fused4096_r8_kernel runs its two frames in lock step: all 16 waves stream LDS in the FFT passes, then all 16 waves
 // issue VALU in the per-bin stage, with three workgroup barriers per two frames - and a timing-only build without those
@@ -180,17 +183,7 @@ __global__ __launch_bounds__(1024, 4) void fused4096_pp_kernel(
                 const int cell = t << 2;
                 int sl = sk - 2 - D;
                 sl += sl < 0 ? SLOTS : 0;
-                float4* cellp = reinterpret_cast<float4*>(ring + __umul24((unsigned)sl, (unsigned)R) + cell);
-                const float4 e4 = *cellp;
-                *cellp = make_float4(0.f, 0.f, 0.f, 0.f);
-                const float d0 = cell_db_fast(dm, e4.x), d1 = cell_db_fast(dm, e4.y);
-                const float d2 = cell_db_fast(dm, e4.z), d3 = cell_db_fast(dm, e4.w);
-                const int i0 = cell_index(dm, d0), i1 = cell_index(dm, d1), i2 = cell_index(dm, d2), i3 = cell_index(dm, d3);
-                const size_t o = ((size_t)s * C + col) * R + cell;
-                if (db) *reinterpret_cast<float4*>(db + o) = make_float4(d0, d1, d2, d3);
-                if (rgba) *reinterpret_cast<uint4*>(rgba + o) = make_uint4(slut[i0], slut[i1], slut[i2], slut[i3]);
-                if (index) *reinterpret_cast<uint32_t*>(index + o) =
-                    (uint32_t)i0 | ((uint32_t)i1 << 8) | ((uint32_t)i2 << 16) | ((uint32_t)i3 << 24);
+                finalize_ring_quad(ring, sl, R, cell, dm, slut, ((size_t)s * C + col) * R + cell, db, rgba, index);
             }
         }
         EMSPEC_STAMP(0)
@@ -202,18 +195,7 @@ __global__ __launch_bounds__(1024, 4) void fused4096_pp_kernel(
         }
         asm volatile("" ::: "memory");
         EMSPEC_STAMP(5)
-        {
-            // bins 4g .. 4g+3 from F(i) = Z[4g-1+i], M(i) = Z[N-4g+1-i], i = 0..5 (fused_r8.hip.inc); all twelve reads
-            // issued before the first use
-            float2 f[6], m[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) { f[i] = fb[fpos[i]]; m[i] = fb[mpos[i]]; }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                yr[i] = f[i].x + m[i].x; yi[i] = f[i].y - m[i].y; ur[i] = f[i].x - m[i].x; tr[i] = f[i].y + m[i].y;
-            }
-        }
+        read_split6(fb, fpos, mpos, yr, yi, ur, tr);   // all twelve reads issued before the first use
         EMSPEC_STAMP(4)
         __syncthreads();
         EMSPEC_STAMP(6)

@@ -217,17 +217,7 @@ __global__ __launch_bounds__(1024, 4) void fused4096_r8_kernel(
                 const int cell = t << 2;
                 int sl = sj_even - 2 - D + h;
                 sl += sl < 0 ? SLOTS : 0;
-                float4* cellp = reinterpret_cast<float4*>(ring + __umul24((unsigned)sl, (unsigned)R) + cell);
-                const float4 e4 = *cellp;
-                *cellp = make_float4(0.f, 0.f, 0.f, 0.f);
-                const float d0 = cell_db_fast(dm, e4.x), d1 = cell_db_fast(dm, e4.y);
-                const float d2 = cell_db_fast(dm, e4.z), d3 = cell_db_fast(dm, e4.w);
-                const int i0 = cell_index(dm, d0), i1 = cell_index(dm, d1), i2 = cell_index(dm, d2), i3 = cell_index(dm, d3);
-                const size_t o = ((size_t)s * C + col) * R + cell;
-                if (db) *reinterpret_cast<float4*>(db + o) = make_float4(d0, d1, d2, d3);
-                if (rgba) *reinterpret_cast<uint4*>(rgba + o) = make_uint4(slut[i0], slut[i1], slut[i2], slut[i3]);
-                if (index) *reinterpret_cast<uint32_t*>(index + o) =
-                    (uint32_t)i0 | ((uint32_t)i1 << 8) | ((uint32_t)i2 << 16) | ((uint32_t)i3 << 24);
+                finalize_ring_quad(ring, sl, R, cell, dm, slut, ((size_t)s * C + col) * R + cell, db, rgba, index);
             }
         }
         if (active) {
@@ -276,18 +266,7 @@ __global__ __launch_bounds__(1024, 4) void fused4096_r8_kernel(
             // of a frame at equal work.  (frames_kernel still reports it in the parity dump.)
             __builtin_amdgcn_s_setprio(3);
             float yr[6], yi[6], ur[6], tr[6];
-            {
-                // all twelve spectrum reads are issued before the first use (left alone the compiler reads them two at a
-                // time into the same registers, a full LDS round trip per pair)
-                float2 f[6], m[6];
-#pragma unroll
-                for (int i = 0; i < 6; ++i) { f[i] = fb[fpos[i]]; m[i] = fb[mpos[i]]; }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    yr[i] = f[i].x + m[i].x; yi[i] = f[i].y - m[i].y; ur[i] = f[i].x - m[i].x; tr[i] = f[i].y + m[i].y;   // ur = -Ti
-                }
-            }
+            read_split6(fb, fpos, mpos, yr, yi, ur, tr);   // all twelve reads issued before the first use
             int sbase = sj_even + h - DMAX;            // ring slot of column j-8
             sbase += sbase < 0 ? SLOTS : 0;
             const int jrel = (int)(j - c0);

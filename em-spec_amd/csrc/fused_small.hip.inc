@@ -1,6 +1,7 @@
 // fused_small.hip.inc — fused batch kernels for N = 2048 and N = 1024 (and, as S = 0, for N = 4096
 // at the hops fused_r8.hip.inc is not built for) on the skeleton of fused_r8.hip.inc.  Included by
-// kernels.hip after fused_r8.hip.inc (reuses f8::swz / zpos / tw_index8 / TwLds).
+// kernels.hip after fused_r8.hip.inc (reuses f8::swz / zpos / tw_index8 / TwLds); the finalize, the spectrum split and the
+// lock-step form's four-bin stage are fused_common.hip.inc's (the product form spells the bin stage out, see fused_pp.hip.inc).
 //
 // A 4096-point radix-2 DIF network whose first S stages are skipped is 2^S independent
 // (4096 >> S)-point networks side by side, and its twiddles are the small network's own
@@ -172,41 +173,7 @@ __global__ __launch_bounds__(1024, 4) void fused_small_kernel(
                 float* cellp[4];
                 float pw[4];
                 bool okv[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float Ar = twice_minus(yr[e + 1], yr[e] + yr[e + 2]), Ai = twice_minus(yi[e + 1], yi[e] + yi[e + 2]);
-                    const float Br = twice_minus(tr[e + 1], tr[e] + tr[e + 2]), Ui = twice_minus(ur[e + 1], ur[e] + ur[e + 2]);
-                    const float Dr = yr[e] - yr[e + 2], Di = yi[e] - yi[e + 2];
-                    const float den = __builtin_fmaf(Ar, Ar, Ai * Ai);
-                    const float P = den * 0.015625f;
-                    bool ok = (P >= pl.pfloor_abs) && (P <= kPowerMax);
-                    const float kf = kf0 + (float)e;
-                    float kh = kf;
-                    int d = D;
-                    if (FAST || pl.reassign) {
-                        const float numT = __builtin_fmaf(Br, Ar, -(Ui * Ai));
-                        const float numF = __builtin_fmaf(Dr, Ar, Di * Ai);
-                        const float inv = FAST ? recip_normal(den) : 1.0f / den;
-                        const float cf = __builtin_floorf(__builtin_fmaf(numT * inv, pl.tscale, 0.5f));
-                        ok = ok && (__builtin_fabsf(cf) <= Df);
-                        d = (int)cf + D;
-                        kh = kf + numF * inv;
-                    }
-                    const int rr = FAST ? lk.row_signed_log(kh) : lk.row_signed(kh);   // -1 / R when k-hat is off the frequency axis
-                    ok = ok && ((unsigned)rr < (unsigned)R);
-                    ok = ok && ((unsigned)(jrel + d - D) < span);
-                    unsigned sl = (unsigned)(sbase + d);   // garbage when !ok: the cell is then never touched
-                    sl = min(sl, sl - (unsigned)SLOTS);
-                    cellp[e] = ring + __umul24(sl, (unsigned)R) + rr;
-                    pw[e] = P;
-                    okv[e] = ok;
-                }
-#pragma unroll
-                for (int e = 0; e < 3; ++e) {
-                    const bool same = okv[e] && okv[e + 1] && (cellp[e] == cellp[e + 1]);
-                    pw[e + 1] = same ? pw[e + 1] + pw[e] : pw[e + 1];
-                    okv[e] = okv[e] && !same;
-                }
+                bins4<FAST>(pl.pfloor_abs, pl.reassign, pl.tscale, lk, yr, yi, ur, tr, kf0, sbase, jrel, span, Df, ring, R, D, SLOTS, cellp, pw, okv);   // fused_common.hip.inc
                 lds_accumulate(cellp[0], pw[0], okv[0]);
                 __builtin_amdgcn_s_setprio(2);
                 lds_accumulate(cellp[1], pw[1], okv[1]);
@@ -229,17 +196,7 @@ __global__ __launch_bounds__(1024, 4) void fused_small_kernel(
                     int sl = sj - D + cc;
                     sl += sl < 0 ? SLOTS : 0;
                     sl -= sl >= SLOTS ? SLOTS : 0;
-                    float4* cq = reinterpret_cast<float4*>(ring + __umul24((unsigned)sl, (unsigned)R) + cell);
-                    const float4 e4 = *cq;
-                    *cq = make_float4(0.f, 0.f, 0.f, 0.f);
-                    const float d0 = cell_db_fast(dm, e4.x), d1 = cell_db_fast(dm, e4.y);
-                    const float d2 = cell_db_fast(dm, e4.z), d3 = cell_db_fast(dm, e4.w);
-                    const int i0 = cell_index(dm, d0), i1 = cell_index(dm, d1), i2 = cell_index(dm, d2), i3 = cell_index(dm, d3);
-                    const size_t o = ((size_t)s * C + col) * R + cell;
-                    if (db) *reinterpret_cast<float4*>(db + o) = make_float4(d0, d1, d2, d3);
-                    if (rgba) *reinterpret_cast<uint4*>(rgba + o) = make_uint4(slut[i0], slut[i1], slut[i2], slut[i3]);
-                    if (index) *reinterpret_cast<uint32_t*>(index + o) =
-                        (uint32_t)i0 | ((uint32_t)i1 << 8) | ((uint32_t)i2 << 16) | ((uint32_t)i3 << 24);
+                    finalize_ring_quad(ring, sl, R, cell, dm, slut, ((size_t)s * C + col) * R + cell, db, rgba, index);
                 }
             }
         }
@@ -391,17 +348,7 @@ __global__ __launch_bounds__(1024, 4) void fused_small_pp_kernel(
                 if (col >= c0 && col < c1) {
                     int sl = sk - 2 * FPT - D + cc;
                     sl += sl < 0 ? SLOTS : 0;
-                    float4* cq = reinterpret_cast<float4*>(ring + __umul24((unsigned)sl, (unsigned)R) + cell);
-                    const float4 e4 = *cq;
-                    *cq = make_float4(0.f, 0.f, 0.f, 0.f);
-                    const float d0 = cell_db_fast(dm, e4.x), d1 = cell_db_fast(dm, e4.y);
-                    const float d2 = cell_db_fast(dm, e4.z), d3 = cell_db_fast(dm, e4.w);
-                    const int i0 = cell_index(dm, d0), i1 = cell_index(dm, d1), i2 = cell_index(dm, d2), i3 = cell_index(dm, d3);
-                    const size_t o = ((size_t)s * C + col) * R + cell;
-                    if (db) *reinterpret_cast<float4*>(db + o) = make_float4(d0, d1, d2, d3);
-                    if (rgba) *reinterpret_cast<uint4*>(rgba + o) = make_uint4(slut[i0], slut[i1], slut[i2], slut[i3]);
-                    if (index) *reinterpret_cast<uint32_t*>(index + o) =
-                        (uint32_t)i0 | ((uint32_t)i1 << 8) | ((uint32_t)i2 << 16) | ((uint32_t)i3 << 24);
+                    finalize_ring_quad(ring, sl, R, cell, dm, slut, ((size_t)s * C + col) * R + cell, db, rgba, index);
                 }
             }
         }
@@ -412,16 +359,7 @@ __global__ __launch_bounds__(1024, 4) void fused_small_pp_kernel(
             __builtin_amdgcn_s_sleep(1);
         }
         asm volatile("" ::: "memory");
-        {
-            float2 f[6], m[6];     // all twelve spectrum reads issued before the first use (fused_pp.hip.inc)
-#pragma unroll
-            for (int i = 0; i < 6; ++i) { f[i] = fb[fpos[i]]; m[i] = fb[mpos[i]]; }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                yr[i] = f[i].x + m[i].x; yi[i] = f[i].y - m[i].y; ur[i] = f[i].x - m[i].x; tr[i] = f[i].y + m[i].y;   // ur = -Ti
-            }
-        }
+        read_split6(fb, fpos, mpos, yr, yi, ur, tr);   // all twelve reads issued before the first use
         __syncthreads();
         // ================= role 1 at half-iteration k + 1: bins + scatter of block k, samples + pass A of block k + 2, its write
         {

@@ -12,12 +12,14 @@
 //   finalize_kernel        histogram -> dB / RGBA / palette index.
 //   fused kernels          see fused.hip.inc (LDS column ring, batch path).
 #include "emspec_launch.h"
+#include "fused_common.hip.inc"
 #include "live.hip.inc"
 
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
 #include <set>
+#include <type_traits>
 #include <utility>
 
 #ifndef EMSPEC_BINS_UNROLL
@@ -38,6 +40,24 @@ static hipError_t allow_max_lds(const void* fn) {
     if (e == hipSuccess) done.insert({dev, fn});
     return e;
 }
+// One launch: the LDS allowance, the launch, its error.  The arguments are converted to the kernel's parameter types.
+template <class... P, class... A>
+static hipError_t launch_k(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+    const hipError_t e = allow_max_lds(reinterpret_cast<const void*>(kernel));
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
+    return hipGetLastError();
+}
+// Run-time value -> template argument, once: f is called with std::integral_constant<int, V> for the V of the list that
+// equals v (with the last of the list when none does: the callers have checked the value), resp. with std::true_type /
+// std::false_type; inside f the constant is V() / B().  Only the listed values are instantiated.
+template <int V0, int... VS, class F>
+static hipError_t pick_int(int v, const F& f) {
+    if constexpr (sizeof...(VS) == 0) return f(std::integral_constant<int, V0>{});
+    else return v == V0 ? f(std::integral_constant<int, V0>{}) : pick_int<VS...>(v, f);
+}
+template <class F>
+static hipError_t pick_bool(bool b, const F& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 // Device word raised by a kernel whose bounded wait timed out (the arrival-counter polls of the fused kernels: a protocol
 // error - every wave arrives before it polls, so a timeout cannot happen in a correct build - after which the results
 // are invalid).  A symbol of the code object, so no kernel carries a pointer for it; emspec_device_status reads it.
@@ -337,24 +357,18 @@ static hipError_t launch_frames_t(const PlanDev& pl, const float* pcm, int64_t L
     const bool plain = !sk.hist;
     const int sink = sk.live.streams ? 3 : (plain && sk.power && !sk.records) ? 1 : ((plain && sk.records && !sk.power) ? 2 : 0);
     if (sink == 0) return hipErrorInvalidValue;   // (no caller mixes the sinks; the run-time form is not instantiated any more)
-    const bool fastc = emspec_plan_is_fast(pl);
-    const void* fn = sink == 1 ? (fastc ? reinterpret_cast<const void*>(&frames_kernel<LOG2N, 1, true>) : reinterpret_cast<const void*>(&frames_kernel<LOG2N, 1>))
-                   : sink == 2 ? (fastc ? reinterpret_cast<const void*>(&frames_kernel<LOG2N, 2, true>) : reinterpret_cast<const void*>(&frames_kernel<LOG2N, 2>))
-                               : (fastc ? reinterpret_cast<const void*>(&frames_kernel<LOG2N, 3, true>) : reinterpret_cast<const void*>(&frames_kernel<LOG2N, 3>));
+    void (*fn)(PlanDev, const float*, int64_t, int64_t, int64_t, FrameSinks) = nullptr;
+    (void)pick_int<1, 2, 3>(sink, [&](auto SINK) {
+        return pick_bool(emspec_plan_is_fast(pl), [&](auto FASTC) { fn = frames_kernel<LOG2N, SINK(), FASTC()>; return hipSuccess; });
+    });
     if (lds > 64 * 1024) {
-        const hipError_t e = allow_max_lds(fn);
+        const hipError_t e = allow_max_lds(reinterpret_cast<const void*>(fn));
         if (e != hipSuccess) return e;
     }
     // grid.x is limited to 2^31-1, grid.y to 65535
     if (nframes <= 0 || S <= 0) return hipSuccess;
     if (S > 65535 || nframes > 0x7fffffffLL) return hipErrorInvalidValue;
-    dim3 grid((unsigned)nframes, (unsigned)S), block(N / 16);
-    if (sink == 1 && fastc) hipLaunchKernelGGL((frames_kernel<LOG2N, 1, true>), grid, block, lds, st, pl, pcm, L, frame0, nframes, sk);
-    else if (sink == 1) hipLaunchKernelGGL((frames_kernel<LOG2N, 1>), grid, block, lds, st, pl, pcm, L, frame0, nframes, sk);
-    else if (sink == 2 && fastc) hipLaunchKernelGGL((frames_kernel<LOG2N, 2, true>), grid, block, lds, st, pl, pcm, L, frame0, nframes, sk);
-    else if (sink == 2) hipLaunchKernelGGL((frames_kernel<LOG2N, 2>), grid, block, lds, st, pl, pcm, L, frame0, nframes, sk);
-    else if (sink == 3 && fastc) hipLaunchKernelGGL((frames_kernel<LOG2N, 3, true>), grid, block, lds, st, pl, pcm, L, frame0, nframes, sk);
-    else hipLaunchKernelGGL((frames_kernel<LOG2N, 3>), grid, block, lds, st, pl, pcm, L, frame0, nframes, sk);
+    hipLaunchKernelGGL(fn, dim3((unsigned)nframes, (unsigned)S), dim3(N / 16), lds, st, pl, pcm, L, frame0, nframes, sk);
     return hipGetLastError();
 }
 
@@ -434,14 +448,7 @@ __global__ __launch_bounds__(1024) void tile_scatter_kernel(const uint2* __restr
     __syncthreads();
     const int ncell4 = span * R / 4;
     for (int q = tid; q < ncell4; q += 1024) {
-        const float4 e = reinterpret_cast<const float4*>(hist)[q];
-        const float d0 = cell_db(dm, e.x), d1 = cell_db(dm, e.y), d2 = cell_db(dm, e.z), d3 = cell_db(dm, e.w);
-        const int i0 = cell_index(dm, d0), i1 = cell_index(dm, d1), i2 = cell_index(dm, d2), i3 = cell_index(dm, d3);
-        const size_t o = ((size_t)s * C + c0) * R + (size_t)q * 4;
-        if (db) *reinterpret_cast<float4*>(db + o) = make_float4(d0, d1, d2, d3);
-        if (rgba) *reinterpret_cast<uint4*>(rgba + o) = make_uint4(slut[i0], slut[i1], slut[i2], slut[i3]);
-        if (index) *reinterpret_cast<uint32_t*>(index + o) =
-            (uint32_t)i0 | ((uint32_t)i1 << 8) | ((uint32_t)i2 << 16) | ((uint32_t)i3 << 24);
+        store_cells4<false>(dm, slut, reinterpret_cast<const float4*>(hist)[q], ((size_t)s * C + c0) * R + (size_t)q * 4, db, rgba, index);
     }
 }
 
@@ -449,15 +456,9 @@ template <int CH>
 static hipError_t launch_tile_scatter_t(const uint2* records, int n, const PlanDev& pl, const DbMap& m, const uint8_t* lut,
                                         int S, int64_t C, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st,
                                         int tile, size_t lds) {
-    {
-        const hipError_t e = allow_max_lds(reinterpret_cast<const void*>(&tile_scatter_kernel<CH>));
-        if (e != hipSuccess) return e;
-    }
     const int64_t ntiles = (C + tile - 1) / tile;
-    hipLaunchKernelGGL(tile_scatter_kernel<CH>, dim3((unsigned)ntiles, (unsigned)S), dim3(1024), lds, st, records,
-                       n / 2 + 1, pl.rows, pl.D, tile, m, reinterpret_cast<const uint32_t*>(lut), C, db,
-                       reinterpret_cast<uint32_t*>(rgba), index);
-    return hipGetLastError();
+    return launch_k(tile_scatter_kernel<CH>, dim3((unsigned)ntiles, (unsigned)S), dim3(1024), lds, st, records, n / 2 + 1,
+                    pl.rows, pl.D, tile, m, reinterpret_cast<const uint32_t*>(lut), C, db, reinterpret_cast<uint32_t*>(rgba), index);
 }
 
 // ---------------------------------------------------------------------------
@@ -527,13 +528,7 @@ __global__ __launch_bounds__(1024) void walk_scatter_kernel(const uint2* __restr
                 float4* cp = reinterpret_cast<float4*>(ring + sl * R + cell);
                 const float4 e = *cp;
                 *cp = make_float4(0.f, 0.f, 0.f, 0.f);
-                const float d0 = cell_db(dm, e.x), d1 = cell_db(dm, e.y), d2 = cell_db(dm, e.z), d3 = cell_db(dm, e.w);
-                const int i0 = cell_index(dm, d0), i1 = cell_index(dm, d1), i2 = cell_index(dm, d2), i3 = cell_index(dm, d3);
-                const size_t o = ((size_t)s * C + col) * R + cell;
-                if (db) *reinterpret_cast<float4*>(db + o) = make_float4(d0, d1, d2, d3);
-                if (rgba) *reinterpret_cast<uint4*>(rgba + o) = make_uint4(slut[i0], slut[i1], slut[i2], slut[i3]);
-                if (index) *reinterpret_cast<uint32_t*>(index + o) =
-                    (uint32_t)i0 | ((uint32_t)i1 << 8) | ((uint32_t)i2 << 16) | ((uint32_t)i3 << 24);
+                store_cells4<false>(dm, slut, e, ((size_t)s * C + col) * R + cell, db, rgba, index);
             }
         }
         __syncthreads();
@@ -544,26 +539,21 @@ template <int CH>
 static hipError_t launch_walk_scatter_t(const uint2* records, int n, const PlanDev& pl, const DbMap& m, const uint8_t* lut,
                                         int S, int64_t C, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st, int F,
                                         size_t lds) {
-    {
-        const hipError_t e = allow_max_lds(reinterpret_cast<const void*>(&walk_scatter_kernel<CH>));
-        if (e != hipSuccess) return e;
-    }
     int64_t seg = (S * C + 4 * device_cus() - 1) / (4 * device_cus());   // >= 4 workgroups per CU when there is enough work
     seg = seg < 128 ? 128 : (seg > 1024 ? 1024 : seg);
     seg = (seg + F - 1) / F * F;
     const int64_t nseg = (C + seg - 1) / seg;
-    hipLaunchKernelGGL(walk_scatter_kernel<CH>, dim3((unsigned)nseg, (unsigned)S), dim3(1024), lds, st, records, n / 2 + 1,
-                       pl.rows, pl.D, F, (int)seg, m, reinterpret_cast<const uint32_t*>(lut), C, db,
-                       reinterpret_cast<uint32_t*>(rgba), index);
-    return hipGetLastError();
+    return launch_k(walk_scatter_kernel<CH>, dim3((unsigned)nseg, (unsigned)S), dim3(1024), lds, st, records, n / 2 + 1,
+                    pl.rows, pl.D, F, (int)seg, m, reinterpret_cast<const uint32_t*>(lut), C, db, reinterpret_cast<uint32_t*>(rgba), index);
 }
 
 hipError_t launch_tile_scatter(const uint2* records, int n, const PlanDev& pl, const DbMap& m, const uint8_t* lut, int S,
                                int64_t C, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st) {
     if (S <= 0 || C <= 0) return hipSuccess;
     if (S > 65535) return hipErrorInvalidValue;
+    // chunk = consecutive bins per thread: wide enough that adjacent lanes rarely share a row
+    const int ch = n >= 8192 ? 32 : (n >= 2048 ? 8 : 4);
     {   // walking ring when it fits: F frames per step so that F * chunks-per-frame covers the 1024 threads
-        const int ch = n >= 8192 ? 32 : (n >= 2048 ? 8 : 4);
         const int nch = (n / 2 + 2 + ch - 1) / ch;
         int F = (1024 + nch - 1) / nch;
         F = F < 1 ? 1 : (F > 8 ? 8 : F);
@@ -576,20 +566,14 @@ hipError_t launch_tile_scatter(const uint2* records, int n, const PlanDev& pl, c
 #endif
         // measured: the walk wins when the tiles would re-read every record >= 2x (D >= 16: N=16384/512
         // 1.04e7 vs 0.94e7 col/s); for small D the tiles' independent workgroups win (N=1024: 1.8e8 vs 1.6e8)
-        if (use_walk && pl.D >= 16 && wl <= 156 * 1024) {
-            if (n >= 8192) return launch_walk_scatter_t<32>(records, n, pl, m, lut, S, C, db, rgba, index, st, F, wl);
-            if (n >= 2048) return launch_walk_scatter_t<8>(records, n, pl, m, lut, S, C, db, rgba, index, st, F, wl);
-            return launch_walk_scatter_t<4>(records, n, pl, m, lut, S, C, db, rgba, index, st, F, wl);
-        }
+        if (use_walk && pl.D >= 16 && wl <= 156 * 1024)
+            return pick_int<32, 8, 4>(ch, [&](auto CH) { return launch_walk_scatter_t<CH()>(records, n, pl, m, lut, S, C, db, rgba, index, st, F, wl); });
     }
     int tile = (int)((150 * 1024) / ((size_t)pl.rows * 4));
     tile = tile > 32 ? 32 : tile;
     if (tile < 1) return hipErrorInvalidValue;
     const size_t lds = (size_t)tile * pl.rows * 4 + 1024;
-    // chunk = consecutive bins per thread: wide enough that adjacent lanes rarely share a row
-    if (n >= 8192) return launch_tile_scatter_t<32>(records, n, pl, m, lut, S, C, db, rgba, index, st, tile, lds);
-    if (n >= 2048) return launch_tile_scatter_t<8>(records, n, pl, m, lut, S, C, db, rgba, index, st, tile, lds);
-    return launch_tile_scatter_t<4>(records, n, pl, m, lut, S, C, db, rgba, index, st, tile, lds);
+    return pick_int<32, 8, 4>(ch, [&](auto CH) { return launch_tile_scatter_t<CH()>(records, n, pl, m, lut, S, C, db, rgba, index, st, tile, lds); });
 }
 
 #ifdef EMSPEC_DIAG

@@ -26,9 +26,7 @@ __global__ __launch_bounds__(256) void multires_compose_kernel(const float* __re
             if (db) *reinterpret_cast<float4*>(db + o + 4 * q) = v;
             if (rgba || index) {
                 const int i0 = cell_index(dm, v.x), i1 = cell_index(dm, v.y), i2 = cell_index(dm, v.z), i3 = cell_index(dm, v.w);
-                if (rgba) *reinterpret_cast<uint4*>(rgba + o + 4 * q) = make_uint4(lut[i0], lut[i1], lut[i2], lut[i3]);
-                if (index) *reinterpret_cast<uint32_t*>(index + o + 4 * q) =
-                    (uint32_t)i0 | ((uint32_t)i1 << 8) | ((uint32_t)i2 << 16) | ((uint32_t)i3 << 24);
+                store_colour4(lut, i0, i1, i2, i3, o + 4 * q, rgba, index);
             }
         }
     }

@@ -90,9 +90,7 @@ __global__ __launch_bounds__(256) void smooth_apply_kernel(float* __restrict__ d
                 *reinterpret_cast<float4*>(out + o) = y;
                 if (rgba || index) {
                     const int i0 = cell_index(dm, y.x), i1 = cell_index(dm, y.y), i2 = cell_index(dm, y.z), i3 = cell_index(dm, y.w);
-                    if (rgba) *reinterpret_cast<uint4*>(rgba + o) = make_uint4(lut[i0], lut[i1], lut[i2], lut[i3]);
-                    if (index) *reinterpret_cast<uint32_t*>(index + o) =
-                        (uint32_t)i0 | ((uint32_t)i1 << 8) | ((uint32_t)i2 << 16) | ((uint32_t)i3 << 24);
+                    store_colour4(lut, i0, i1, i2, i3, o, rgba, index);
                 }
             }
         }
