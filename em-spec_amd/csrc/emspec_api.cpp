@@ -403,6 +403,7 @@ void emspec_destroy(emspec_engine* e) {
     if (e->xlow_event) (void)hipEventDestroy(e->xlow_event);
     (void)hipFree(e->d_lut); (void)hipFree(e->d_hist); (void)hipFree(e->d_stage);
     (void)hipFree(e->d_raw); (void)hipFree(e->d_post); (void)hipFree(e->d_peak); (void)hipFree(e->d_mres);
+    (void)hipFree(e->d_full);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     if (e->stream_in) (void)hipStreamDestroy(e->stream_in);
     if (e->stream_out) (void)hipStreamDestroy(e->stream_out);
@@ -702,16 +703,32 @@ int run_plan_columns(emspec_engine* e, const Plan& p, const float* pcm, int32_t 
 }
 }  // namespace emspec
 
-extern "C" {
+// Time reduction of a device entry: the full-rate columns of a chunk of streams - dB when the caller wants dB,
+// the palette index when it wants index or RGBA - go to the engine workspace d_full, sized by the records path's budget rule,
+// and one launch of reduce.hip.inc's kernel writes that chunk's reduced columns into the caller's arrays.
+int emspec::reduce_streams(emspec_engine* e, int32_t S, int64_t C, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st,
+                           const FullRun& full) {
+    const int R = e->cfg.rows, f = e->time_reduce;
+    const size_t cells = (size_t)C * R, rcells = (size_t)reduced_columns(C, f) * R;
+    const size_t db_s = db ? cells * 4 : 0, idx_s = (index || rgba) ? cells : 0;   // (cells is a multiple of 4: both stay 16-byte aligned ...
+    int chunk = 1, rc;
+    if ((rc = grow_chunked(e, (void**)&e->d_full, &e->full_bytes, db_s + idx_s, 256, (size_t)4 << 30, S, &chunk))) return rc;
+    float* wdb = db ? reinterpret_cast<float*>(e->d_full) : nullptr;
+    uint8_t* widx = idx_s ? reinterpret_cast<uint8_t*>(e->d_full) + ((db_s * chunk + 255) & ~(size_t)255) : nullptr;   // ... and this 256)
+    for (int s0 = 0; s0 < S; s0 += chunk) {
+        const int sc = std::min(chunk, S - s0);
+        if ((rc = full(s0, sc, wdb, widx))) return rc;
+        const size_t o = (size_t)s0 * rcells;
+        HIPCHK(e, launch_reduce_columns(wdb, widx, sc, C, R, f, cells, rcells, e->d_lut, db ? db + o : nullptr,
+                                        index ? index + o : nullptr, rgba ? rgba + 4 * o : nullptr, st));
+    }
+    return EMSPEC_OK;
+}
 
-int emspec_batch_device(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32_t n, int32_t hop,
-                        int32_t reassign, float* db, uint8_t* rgba, uint8_t* index, void* hip_stream) {
-    if (!e || !pcm) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument");
-    int rc = check_shape(e, n, hop);
-    if (rc) return rc;
+int emspec::batch_device_full(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32_t n, int32_t hop, int32_t reassign,
+                              float* db, uint8_t* rgba, uint8_t* index, hipStream_t st) {
+    int rc;
     if (S < 1 || S > 65535 || L < n) return fail(e, EMSPEC_ERR_INVALID_ARG, "need 1..65535 streams of at least fft-size samples");
-    HIPCHK(e, hipSetDevice(e->device));
-    hipStream_t st = (hipStream_t)hip_stream;   // NULL = the HIP default stream
     Plan* p;
     if ((rc = get_plan(e, n, &p))) return rc;
     const PlanDev pd = plan_dev(e, *p, hop, reassign);
@@ -733,6 +750,26 @@ int emspec_batch_device(emspec_engine* e, const float* pcm, int32_t S, int64_t L
     }
     if (e->exact()) return run_columns_exact(e, *p, pcm, S, L, n, hop, reassign, C, db, rgba, index, st);
     return run_columns(e, pd, m, pcm, S, L, n, hop, reassign, C, db, rgba, index, st);
+}
+
+extern "C" {
+
+int emspec_batch_device(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32_t n, int32_t hop,
+                        int32_t reassign, float* db, uint8_t* rgba, uint8_t* index, void* hip_stream) {
+    if (!e || !pcm) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument");
+    int rc = check_shape(e, n, hop);
+    if (rc) return rc;
+    if (S < 1 || S > 65535 || L < n) return fail(e, EMSPEC_ERR_INVALID_ARG, "need 1..65535 streams of at least fft-size samples");
+    HIPCHK(e, hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;   // NULL = the HIP default stream
+    if (!db && !rgba && !index) {   // (the shape's tables are still built: a row table that cannot be is reported)
+        Plan* p;
+        return get_plan(e, n, &p);
+    }
+    if (e->time_reduce == 1) return batch_device_full(e, pcm, S, L, n, hop, reassign, db, rgba, index, st);
+    return reduce_streams(e, S, emspec_num_columns(L, n, hop), db, rgba, index, st, [=](int s0, int sc, float* fdb, uint8_t* fidx) {
+        return batch_device_full(e, pcm + (size_t)s0 * L, sc, L, n, hop, reassign, fdb, nullptr, fidx, st);
+    });
 }
 
 #ifdef EMSPEC_DIAG   // diagnostic entry points (include/emspec_debug.h): libemspec_diag.so only
@@ -883,7 +920,7 @@ int emspec_debug_phase_cycles(emspec_engine* e, const float* pcm_dev, int32_t S,
 // the host-buffer entries run emspec_batch_device on each unit of the driver's pipeline (emspec_host.cpp)
 static HostRun batch_run(emspec_engine* e, int n, int hop, int reassign) {
     return [=](const float* pcm, int sc, int64_t samples, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st) {
-        return emspec_batch_device(e, pcm, sc, samples, n, hop, reassign, db, rgba, index, st);
+        return batch_device_full(e, pcm, sc, samples, n, hop, reassign, db, rgba, index, st);
     };
 }
 
@@ -909,7 +946,7 @@ int emspec_batch_packed(emspec_engine* e, const float* pcm, int32_t S, int64_t L
     int rc = check_shape(e, n, hop);
     if (rc) return rc;
     if (S < 1 || L < n) return fail(e, EMSPEC_ERR_INVALID_ARG, "need at least one stream of at least fft-size samples");
-    if ((uint64_t)emspec_num_columns(L, n, hop) * (uint64_t)e->cfg.rows >= (1ull << 32))
+    if ((uint64_t)reduced_columns(emspec_num_columns(L, n, hop), e->time_reduce) * (uint64_t)e->cfg.rows >= (1ull << 32))
         return fail(e, EMSPEC_ERR_INVALID_ARG, "at most 2^32 cells per stream");
     if (e->cfg.rows % 4) return fail(e, EMSPEC_ERR_INVALID_ARG, "the wire image needs rows % 4 == 0");
     HIPCHK(e, hipSetDevice(e->device));
@@ -1043,6 +1080,19 @@ int emspec_set_display(emspec_engine* e, float smoothing, float agc_strength) {
     e->smoothing = smoothing;
     e->agc = agc_strength;
     return EMSPEC_OK;
+}
+
+int emspec_set_time_reduce(emspec_engine* e, int32_t factor) {
+    if (!e) return EMSPEC_ERR_INVALID_ARG;
+    if (factor < 1 || factor > 65536) return fail(e, EMSPEC_ERR_INVALID_ARG, "the time reduction factor must be in [1, 65536]");
+    if (live_pending(e)) return fail(e, EMSPEC_ERR_STATE, "columns are pending; flush or reset before changing the time reduction");
+    e->time_reduce = factor;
+    return EMSPEC_OK;
+}
+int32_t emspec_time_reduce(const emspec_engine* e) { return e ? e->time_reduce : -1; }
+int64_t emspec_reduced_columns(int64_t columns, int32_t factor) {
+    if (columns < 0 || factor < 1 || factor > 65536) return -1;
+    return columns / factor + (columns % factor != 0);
 }
 
 int emspec_reset(emspec_engine* e) {

@@ -484,7 +484,8 @@ int emspec_batch_gather(emspec_engine* e, const float* pcm, int32_t S, int64_t L
     if (!has_comm(c)) return fail(e, EMSPEC_ERR_STATE, "no communicator: call emspec_comm_init first");
     if (root < 0 || root >= c->world) return fail(e, EMSPEC_ERR_INVALID_ARG, "root out of range");
     if (c->rank == root && !gathered_index) return fail(e, EMSPEC_ERR_INVALID_ARG, "the root needs the gathered buffer");
-    const int64_t C = emspec_num_columns(L, n, hop);
+    // (C: what emspec_batch_device delivers - the reduced columns when a time reduction is set)
+    const int64_t C = reduced_columns(emspec_num_columns(L, n, hop), e->time_reduce);
     if (S < 1 || C < 1) return fail(e, EMSPEC_ERR_INVALID_ARG, "need at least one stream of at least fft-size samples");
     HIPCHK(e, hipSetDevice(e->device));
     const size_t cells = (size_t)S * (size_t)C * (size_t)e->cfg.rows;

@@ -76,6 +76,15 @@ int run_plan_columns(emspec_engine* e, const Plan& p, const float* pcm, int32_t 
                      int64_t C, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st);
 // device workspace *ptr for `per_stream` bytes per stream (+ extra): streams per chunk by the records path's budget
 int grow_chunked(emspec_engine* e, void** ptr, size_t* have, size_t per_stream, size_t extra, size_t cap, int S, int* chunk_out);
+// emspec_api.cpp: emspec_batch_device at FULL rate whatever the engine's time reduction (the unit function of the host
+// pipeline, which reduces a unit's columns itself), and the device entries' reduced form: `full` computes the full-rate dB and /
+// or index columns [sc][C][rows] of streams [s0, s0 + sc) into the engine workspace, chunk after chunk of streams (grow_chunked),
+// and the reduction writes the caller's [S][ceil(C / f)][rows] arrays
+int batch_device_full(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32_t n, int32_t hop, int32_t reassign, float* db,
+                      uint8_t* rgba, uint8_t* index, hipStream_t st);
+using FullRun = std::function<int(int s0, int sc, float* db, uint8_t* index)>;
+int reduce_streams(emspec_engine* e, int32_t S, int64_t C, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st, const FullRun& full);
+inline int64_t reduced_columns(int64_t C, int f) { return (C + f - 1) / f; }
 PlanDev plan_dev(const emspec_engine* e, const Plan& p, int hop, int reassign);
 ExactPlanDev exact_plan_dev(const emspec_engine* e, const Plan& p, int hop, int reassign);
 ExactDbMap exact_db_map(const emspec_engine* e, int n, const ExactPlanDev& pd);
@@ -93,6 +102,8 @@ using HostRun = std::function<int(const float* pcm, int sc, int64_t samples, flo
 // sc * dec->views streams, and the outputs are those of S * dec->views streams.  Null: pcm is float32 [S][L].
 int host_batch(emspec_engine* e, const void* pcm, int S, int64_t L, int n, int hop, int halo_D, int min_streams,
                const emspec_out* out, const PackedOut* pk, const HostRun& run, const emspec_pcm_format* dec = nullptr);
+// (with the engine's time reduction f > 1, `run` still computes FULL-rate columns - dB and / or index, never RGBA - into the
+// unit's staging set; host_batch launches the reduction behind it and delivers ceil(columns / f) columns per stream)
 // emspec_pcm.cpp: null, or what is wrong with the format (names the field); bytes per interleaved frame of a valid format
 const char* pcm_format_error(const emspec_pcm_format* f);
 int pcm_frame_bytes(const emspec_pcm_format& f);
@@ -143,6 +154,10 @@ struct emspec_engine {
     float* d_peak = nullptr; size_t peak_bytes = 0;    // column peaks + gains
     // multi-resolution batch (emspec_multires.cpp): both bands' raw dB (+ the composed raw dB for the post-process)
     float* d_mres = nullptr; size_t mres_bytes = 0;
+    // time reduction (emspec_set_time_reduce): the factor, and the device entries' full-rate columns of a chunk
+    // of streams (dB and / or palette index), which reduce.hip.inc's kernel collapses into the caller's arrays
+    int time_reduce = 1;
+    char* d_full = nullptr; size_t full_bytes = 0;
     // streaming (emspec_live.cpp): the live multi-stream session, and the single-stream calls' own (emspec_column,
     // emspec_push_samples: the same machinery with one stream); independent of each other
     emspec::LiveState live, one;

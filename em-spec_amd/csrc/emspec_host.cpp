@@ -57,19 +57,21 @@ int pipe_units(bool exact, int n, int64_t columns, size_t bytes_in, size_t bytes
     return best;
 }
 
-std::vector<PipeItem> pipe_items(int S, int64_t L, int64_t C, int n, int hop, int D, size_t per_stream_bytes, bool by_time, int target) {
+// (f: the engine's time reduction.  A run starts on a multiple of f, so that every group of f columns lies in one unit - the
+// lengths are then multiples of f but for the stream's last run - and a batch of fewer than two groups per stream is not cut)
+std::vector<PipeItem> pipe_items(int S, int64_t L, int64_t C, int n, int hop, int D, size_t per_stream_bytes, bool by_time, int target, int f) {
     std::vector<PipeItem> items;
     // runs of columns: when there are fewer than `target` streams; at least 16,384 columns per run - a unit costs ~0.2 ms
     // (pipe_units) whatever its size, and 16 MB each way over PCIe take 0.35 ms (measured with 2,048-column runs: one stream
     // of 2^22 samples 1.49 ms instead of 0.84 in one piece)
-    const int64_t pieces = by_time && S < target ? std::min<int64_t>((target + S - 1) / S, C / 16384) : 1;
+    const int64_t pieces = by_time && S < target ? std::min<int64_t>((target + S - 1) / S, std::min(C / 16384, C / f)) : 1;
     if (pieces > 1) {
         for (int s = 0; s < S; ++s)
             for (int64_t t = 0; t < pieces; ++t) {
                 PipeItem it;
                 it.s0 = s; it.sc = 1;
-                it.c0 = C * t / pieces;
-                it.cn = C * (t + 1) / pieces - it.c0;
+                it.c0 = C * t / pieces / f * f;
+                it.cn = (t + 1 < pieces ? C * (t + 1) / pieces / f * f : C) - it.c0;
                 const int64_t f0 = std::max<int64_t>(it.c0 - D, 0), f1 = std::min<int64_t>(it.c0 + it.cn + D, C);   // frames [f0, f1)
                 it.first_sample = f0 * hop;
                 it.samples = (f1 - f0 - 1) * hop + n;
@@ -91,46 +93,70 @@ std::vector<PipeItem> pipe_items(int S, int64_t L, int64_t C, int n, int hop, in
 
 size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
 
-struct Set { float* pcm; float* db; uint8_t* rgba; uint8_t* idx; uint8_t* wire; char* raw; };
+// (db / rgba / idx: what the unit's kernels write; odb / orgba / oidx: what is delivered - the same arrays, or with a time
+// reduction the reduced columns beside them)
+struct Set { float* pcm; float* db; uint8_t* rgba; uint8_t* idx; uint8_t* wire; char* raw; float* odb; uint8_t* orgba; uint8_t* oidx; };
 
 // The staging set: every array at the size the largest unit needs (the wire images: one slot of `wire` bytes per stream).
 struct Stage {
     size_t in = 0, db = 0, rgba = 0, idx = 0, wire = 0;
     size_t raw = 0;  // PCM entries: the unit's raw frames, which the decode kernel turns into `in`
+    size_t rdb = 0, rrgba = 0, ridx = 0;   // time reduction: the unit's reduced columns (db / idx then hold the full-rate ones)
+    bool reduced = false;
     int chunk = 1;   // streams in the largest unit
-    size_t bytes() const { return in + db + rgba + idx + wire * chunk + raw; }
+    size_t bytes() const { return in + db + rgba + idx + wire * chunk + raw + rdb + rrgba + ridx; }
     Set at(char* stage, int b) const {
         char* base = stage + (size_t)b * bytes();
-        return Set{(float*)base, db ? (float*)(base + in) : nullptr, rgba ? (uint8_t*)(base + in + db) : nullptr,
-                   idx ? (uint8_t*)(base + in + db + rgba) : nullptr, wire ? (uint8_t*)(base + in + db + rgba + idx) : nullptr,
-                   raw ? base + in + db + rgba + idx + wire * chunk : nullptr};
+        Set q{(float*)base, db ? (float*)(base + in) : nullptr, rgba ? (uint8_t*)(base + in + db) : nullptr,
+              idx ? (uint8_t*)(base + in + db + rgba) : nullptr, wire ? (uint8_t*)(base + in + db + rgba + idx) : nullptr,
+              raw ? base + in + db + rgba + idx + wire * chunk : nullptr, nullptr, nullptr, nullptr};
+        char* r = base + in + db + rgba + idx + wire * chunk + raw;
+        q.odb = reduced ? (rdb ? (float*)r : nullptr) : q.db;
+        q.orgba = reduced ? (rrgba ? (uint8_t*)(r + rdb) : nullptr) : q.rgba;
+        q.oidx = reduced ? (ridx ? (uint8_t*)(r + rdb + rrgba) : nullptr) : q.idx;
+        return q;
     }
 };
 
 // (V streams per unit of PipeItem::sc, frame_bytes of raw input each: 1 and 0 for the float entries, whose units are streams)
-Stage stage_layout(const std::vector<PipeItem>& items, int R, bool db, bool rgba, bool idx, size_t wire_s, int V, int frame_bytes) {
+// (f > 1: dB and / or index at full rate - the index also when only RGBA is wanted - and the delivered arrays at the reduced rate)
+Stage stage_layout(const std::vector<PipeItem>& items, int R, bool db, bool rgba, bool idx, size_t wire_s, int V, int frame_bytes, int f) {
     Stage g;
-    size_t cells = 0;
+    size_t cells = 0, rcells = 0;
     for (const PipeItem& it : items) {
+        rcells = std::max(rcells, (size_t)((it.cn + f - 1) / f) * R * it.sc * V);
         g.in = std::max(g.in, al((size_t)it.samples * 4 * it.sc * V));
         g.raw = std::max(g.raw, frame_bytes ? al((size_t)it.samples * frame_bytes * it.sc) : 0);
         cells = std::max(cells, (size_t)it.cols * R * it.sc * V);
         g.chunk = std::max(g.chunk, it.sc * V);
     }
+    g.reduced = f > 1;
     g.db = db ? al(cells * 4) : 0;
-    g.rgba = rgba ? al(cells * 4) : 0;
-    g.idx = idx ? al(cells) : 0;
+    g.rgba = rgba && !g.reduced ? al(cells * 4) : 0;
+    g.idx = idx || (rgba && g.reduced) ? al(cells) : 0;
     g.wire = al(wire_s);
+    if (g.reduced) {
+        g.rdb = db ? al(rcells * 4) : 0;
+        g.rrgba = rgba ? al(rcells * 4) : 0;
+        g.ridx = idx ? al(rcells) : 0;
+    }
     return g;
 }
 
 // Where a unit's kept columns come from in its set and go in the caller's arrays: cell offsets and count.  A unit of whole
 // streams is one span; a run of columns is one span per stream (V > 1: the views of the unit's source).
+// (C: the columns a stream is computed at; f: the time reduction - Cr = ceil(C / f) columns of it are delivered, a run's
+// ceil(cn / f) from column c0 / f on, out of the unit's reduced array, which holds the kept columns only)
 struct Span { size_t from, to, cells; };
 int spans_of(const PipeItem& it, int64_t C, int V) { return it.cn == C ? 1 : it.sc * V; }
-Span span_of(const PipeItem& it, int64_t C, int R, int V, int k) {
-    if (it.cn == C) return Span{0, (size_t)it.s0 * V * C * R, (size_t)it.cn * R * it.sc * V};
-    return Span{((size_t)k * it.cols + (size_t)it.skip) * R, (((size_t)it.s0 * V + k) * C + (size_t)it.c0) * R, (size_t)it.cn * R};
+Span span_of(const PipeItem& it, int64_t C, int R, int V, int k, int f) {
+    if (f == 1) {
+        if (it.cn == C) return Span{0, (size_t)it.s0 * V * C * R, (size_t)it.cn * R * it.sc * V};
+        return Span{((size_t)k * it.cols + (size_t)it.skip) * R, (((size_t)it.s0 * V + k) * C + (size_t)it.c0) * R, (size_t)it.cn * R};
+    }
+    const size_t Cr = (size_t)((C + f - 1) / f), crn = (size_t)((it.cn + f - 1) / f);
+    if (it.cn == C) return Span{0, (size_t)it.s0 * V * Cr * R, crn * R * it.sc * V};
+    return Span{(size_t)k * crn * R, (((size_t)it.s0 * V + k) * Cr + (size_t)(it.c0 / f)) * R, crn * R};
 }
 
 }  // namespace
@@ -149,25 +175,30 @@ int emspec::host_batch(emspec_engine* e, const void* pcm, int S, int64_t L, int 
     for (hipEvent_t& ev : e->pipe_ev)
         if (!ev) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     const int64_t C = emspec_num_columns(L, n, hop);
-    const int R = e->cfg.rows;
+    const int R = e->cfg.rows, f = e->time_reduce;
+    const int64_t Cr = reduced_columns(C, f);   // columns per stream that are delivered (C are computed)
     int rc;
     // dec: the S rows are SOURCES of interleaved frames (emspec_batch_pcm): fb bytes per frame in, V streams each out
     const int V = dec ? dec->views : 1, fb = dec ? pcm_frame_bytes(*dec) : (int)sizeof(float);
-    const size_t col_cells = (size_t)C * R, in_s = (size_t)L * fb;
+    const size_t col_cells = (size_t)C * R, out_cells = (size_t)Cr * R, in_s = (size_t)L * fb;
     const bool want_db = out && out->db, want_rgba = out && out->rgba, want_idx = (out && out->index) || pk;
-    const size_t wire_s = pk ? (size_t)wire_bound_bytes(C, R) : 0;
-    const size_t per_stream = al(in_s) + (dec ? al((size_t)L * 4 * V) : 0) +
-                              V * (al(want_db ? col_cells * 4 : 0) + al(want_rgba ? col_cells * 4 : 0) + al(want_idx ? col_cells : 0) + al(wire_s));
+    const size_t wire_s = pk ? (size_t)wire_bound_bytes(Cr, R) : 0;
+    size_t per_stream = al(in_s) + (dec ? al((size_t)L * 4 * V) : 0) +
+                        V * (al(want_db ? col_cells * 4 : 0) + al(want_rgba ? col_cells * 4 : 0) + al(want_idx ? col_cells : 0) + al(wire_s));
+    if (f > 1)   // full-rate dB / index (no full-rate RGBA) and the reduced arrays
+        per_stream = al(in_s) + (dec ? al((size_t)L * 4 * V) : 0) +
+                     V * (al(want_db ? col_cells * 4 : 0) + al(want_idx || want_rgba ? col_cells : 0) + al(wire_s) +
+                          al(want_db ? out_cells * 4 : 0) + al(want_rgba ? out_cells * 4 : 0) + al(want_idx ? out_cells : 0));
     int units = pipe_units(e->exact(), n, (int64_t)S * V * C, (size_t)S * in_s,
-                           pk ? (size_t)S * V * col_cells / 5 : (size_t)S * V * col_cells * ((want_db ? 4 : 0) + (want_rgba ? 4 : 0) + (want_idx ? 1 : 0)));
+                           pk ? (size_t)S * V * out_cells / 5 : (size_t)S * V * out_cells * ((want_db ? 4 : 0) + (want_rgba ? 4 : 0) + (want_idx ? 1 : 0)));
     if (halo_D < 0) units = std::min(units, std::max(S / min_streams, 1));   // whole streams: at least min_streams per unit
-    const std::vector<PipeItem> items = pipe_items(S, L, C, n, hop, halo_D, per_stream, halo_D >= 0, units);
+    const std::vector<PipeItem> items = pipe_items(S, L, C, n, hop, halo_D, per_stream, halo_D >= 0, units, f);
     const int nu = (int)items.size();
     const bool one = nu == 1;
-    const Stage g = stage_layout(items, R, want_db, want_rgba, want_idx, wire_s, V, dec ? fb : 0);
+    const Stage g = stage_layout(items, R, want_db, want_rgba, want_idx, wire_s, V, dec ? fb : 0, f);
     if ((rc = grow(e, (void**)&e->d_stage, &e->stage_bytes, std::min(nu, kPipeSets) * g.bytes() + 1024))) return rc;
     if (pk) {
-        if ((rc = grow(e, (void**)&e->d_packscratch, &e->packscratch_bytes, wire_scratch_bytes(C)))) return rc;
+        if ((rc = grow(e, (void**)&e->d_packscratch, &e->packscratch_bytes, wire_scratch_bytes(Cr)))) return rc;
         const size_t hb = (size_t)kPipeSets * g.chunk * 32;
         if (hb > e->h_hdr_bytes) {
             if (e->h_hdr) (void)hipHostFree(e->h_hdr);
@@ -179,15 +210,16 @@ int emspec::host_batch(emspec_engine* e, const void* pcm, int S, int64_t L, int 
     }
     const hipStream_t s_in = one ? e->stream : e->stream_in, s_out = one ? e->stream : e->stream_out;
     hipEvent_t *ev_in = e->pipe_ev, *ev_comp = ev_in + kPipeSets, *ev_out = ev_comp + kPipeSets;   // per staging set
+    const int tr = f;   // (the lambdas below count units with `f`)
     // the only D2H copies of columns: unit f's kept columns into the caller's arrays, on `st` behind the unit's kernels
     auto copy_out = [&](int f, hipStream_t st) {
         const Set q = g.at(e->d_stage, f % kPipeSets);
         hipError_t r = st == e->stream ? hipSuccess : hipStreamWaitEvent(st, ev_comp[f % kPipeSets], 0);
         for (int k = 0; k < spans_of(items[f], C, V); ++k) {
-            const Span sp = span_of(items[f], C, R, V, k);
-            if (r == hipSuccess && want_db) r = hipMemcpyAsync(out->db + sp.to, q.db + sp.from, sp.cells * 4, hipMemcpyDeviceToHost, st);
-            if (r == hipSuccess && want_rgba) r = hipMemcpyAsync(out->rgba + 4 * sp.to, q.rgba + 4 * sp.from, sp.cells * 4, hipMemcpyDeviceToHost, st);
-            if (r == hipSuccess && want_idx) r = hipMemcpyAsync(out->index + sp.to, q.idx + sp.from, sp.cells, hipMemcpyDeviceToHost, st);
+            const Span sp = span_of(items[f], C, R, V, k, tr);
+            if (r == hipSuccess && want_db) r = hipMemcpyAsync(out->db + sp.to, q.odb + sp.from, sp.cells * 4, hipMemcpyDeviceToHost, st);
+            if (r == hipSuccess && want_rgba) r = hipMemcpyAsync(out->rgba + 4 * sp.to, q.orgba + 4 * sp.from, sp.cells * 4, hipMemcpyDeviceToHost, st);
+            if (r == hipSuccess && want_idx) r = hipMemcpyAsync(out->index + sp.to, q.oidx + sp.from, sp.cells, hipMemcpyDeviceToHost, st);
         }
         return r;
     };
@@ -218,7 +250,7 @@ int emspec::host_batch(emspec_engine* e, const void* pcm, int S, int64_t L, int 
         };
         for (int f = 0; f < nu; ++f) {
             for (int k = 0; k < spans_of(items[f], C, V); ++k) {
-                const Span sp = span_of(items[f], C, R, V, k);
+                const Span sp = span_of(items[f], C, R, V, k, tr);
                 if (want_db) touch(out->db + sp.to, sp.cells * 4);
                 if (want_rgba) touch(out->rgba + 4 * sp.to, sp.cells * 4);
                 if (want_idx) touch(out->index + sp.to, sp.cells);
@@ -284,11 +316,11 @@ int emspec::host_batch(emspec_engine* e, const void* pcm, int S, int64_t L, int 
             for (int i = 0; i < it.sc * V && herr == hipSuccess && rc == EMSPEC_OK; ++i) {
                 const uint32_t* h = reinterpret_cast<const uint32_t*>(e->h_hdr + ((size_t)b * g.chunk + i) * 32);
                 const uint64_t hcols = (uint64_t)h[2] | ((uint64_t)h[3] << 32), hpay = (uint64_t)h[4] | ((uint64_t)h[5] << 32);
-                if (h[0] != 0x32574D45u || (int32_t)h[1] != R || hcols != (uint64_t)C || hpay > (uint64_t)col_cells) {
+                if (h[0] != 0x32574D45u || (int32_t)h[1] != R || hcols != (uint64_t)Cr || hpay > (uint64_t)out_cells) {
                     rc = fail(e, EMSPEC_ERR_HIP, "the packed image of a stream carries a bad header");
                     break;
                 }
-                const int64_t bytes = wire_fixed_bytes(C, R) + (int64_t)((hpay + 15) & ~(uint64_t)15);
+                const int64_t bytes = wire_fixed_bytes(Cr, R) + (int64_t)((hpay + 15) & ~(uint64_t)15);
                 const int64_t at = pk->offsets[it.s0 * V + i];
                 if (at + bytes > pk->capacity) {
                     rc = fail(e, EMSPEC_ERR_INVALID_ARG, "wire buffer too small (emspec_wire_bound(columns, rows) per stream always suffices)");
@@ -328,10 +360,14 @@ int emspec::host_batch(emspec_engine* e, const void* pcm, int S, int64_t L, int 
         // 3. kernels (PCM entries: the decode kernel first, raw frames -> the unit's sc * V float streams)
         if (dec && (herr = pcm_decode(q.raw, *dec, it.sc, it.samples, it.samples * fb, q.pcm, it.samples, e->stream)) != hipSuccess) break;
         if ((rc = run(q.pcm, it.sc * V, it.samples, q.db, q.rgba, q.idx, e->stream))) break;
+        // 3b. time reduction: the unit's kept columns (a run: from column `skip` of its it.cols) -> the set's reduced arrays
+        if (f > 1 && (herr = launch_reduce_columns(q.db ? q.db + (size_t)it.skip * R : nullptr, q.idx ? q.idx + (size_t)it.skip * R : nullptr,
+                                                   it.sc * V, it.cn, R, f, (size_t)it.cols * R, (size_t)((it.cn + f - 1) / f) * R, e->d_lut,
+                                                   q.odb, q.oidx, q.orgba, e->stream)) != hipSuccess) break;
         // 4. packed: each stream's image, its header to the host behind it
         for (int i = 0; pk && i < it.sc * V && herr == hipSuccess; ++i) {
             uint8_t* w = q.wire + (size_t)i * g.wire;
-            herr = launch_wire_pack(q.idx + (size_t)i * col_cells, C, R, w, e->d_packscratch, e->stream);
+            herr = launch_wire_pack(q.oidx + (size_t)i * out_cells, Cr, R, w, e->d_packscratch, e->stream);
             if (herr == hipSuccess) herr = hipMemcpyAsync(e->h_hdr + ((size_t)b * g.chunk + i) * 32, w, 32, hipMemcpyDeviceToHost, e->stream);
         }
         // 5. computed

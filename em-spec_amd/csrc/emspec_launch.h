@@ -158,6 +158,12 @@ int64_t wire_fixed_bytes(int64_t columns, int rows);
 size_t wire_scratch_bytes(int64_t columns);
 hipError_t launch_wire_pack(const uint8_t* index, int64_t columns, int rows, uint8_t* wire, void* scratch, hipStream_t st);
 hipError_t launch_wire_unpack(const uint8_t* wire, int64_t columns, int rows, uint8_t* index, hipStream_t st);
+// time reduction (reduce.hip.inc): groups of f consecutive columns of each stream -> one, by maximum; [S] streams of C columns
+// of R cells, in_stride cells apart, -> ceil(C / f) columns, out_stride cells apart.  db_out needs db_in; idx_out and / or
+// rgba_out (= LUT[reduced index]) need idx_in; what is not asked for is not read.
+hipError_t launch_reduce_columns(const float* db_in, const uint8_t* idx_in, int S, int64_t C, int R, int f, size_t in_stride,
+                                 size_t out_stride, const uint8_t* lut, float* db_out, uint8_t* idx_out, uint8_t* rgba_out,
+                                 hipStream_t st);
 // PCM front end (pcm.hip.inc): `frames` interleaved frames of `sources` sources (source i at src + i * src_stride_bytes, device
 // memory or page-locked host memory, any byte offset that is a multiple of the sample size) -> float32 streams, stream
 // i * views + v at out + (i * views + v) * out_stride.  sample_type: kPcmS16 .. kPcmF32 (the values of include/emspec.h's

@@ -303,10 +303,14 @@ int live_pcm_drain(emspec_engine* e, LiveState& lv) {
 
 // ---- the calls, on one of the engine's two sessions ----
 
+// the time reduction (emspec_set_time_reduce) serves the batch entries only: every streaming call refuses while it is on
+const char* const kNoLiveReduce = "the streaming calls return full-rate columns: not available while a time reduction is set (emspec_set_time_reduce(e, 1) turns it off)";
+
 // (n_high != 0: the multi-resolution form - n is n_low, the frames are n_low samples long and the short band reads the newest
 // n_high of them; on a stream's first frame it reads all of it, frames 0 .. 2 shift)
 int columns_impl(emspec_engine* e, LiveState& lv, const float* frames, int32_t streams, int32_t n, int32_t hop, int32_t reassign,
                  float* out_db, uint8_t* out_rgba, int32_t rows, int64_t* out_columns, int32_t n_high = 0, int32_t split = 0) {
+    if (e && e->time_reduce > 1) return fail(e, EMSPEC_ERR_STATE, kNoLiveReduce);
     if (!e || !frames) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument");
     reassign = reassign ? 1 : 0;
     int rc = live_check(e, lv, streams, n, hop, reassign, rows, 1, n_high, split);
@@ -344,6 +348,7 @@ int columns_impl(emspec_engine* e, LiveState& lv, const float* frames, int32_t s
 
 int flush_impl(emspec_engine* e, LiveState& lv, float* out_db, uint8_t* out_rgba, int32_t rows, int64_t* out_columns) {
     if (!e) return EMSPEC_ERR_INVALID_ARG;
+    if (e->time_reduce > 1) return fail(e, EMSPEC_ERR_STATE, kNoLiveReduce);
     if (rows != e->cfg.rows) return fail(e, EMSPEC_ERR_INVALID_ARG, "rows does not match the engine configuration");
     bool any = false;
     for (int s = 0; s < lv.S; ++s) any = any || lv.emitted[s] < lv.fed[s];
@@ -396,6 +401,7 @@ int push_impl(emspec_engine* e, LiveState& lv, const void* block, int32_t stream
               int32_t hop, int32_t reassign, float* out_db, uint8_t* out_rgba, int32_t rows, int64_t max_columns,
               int64_t* out_counts, int64_t* out_first_columns, int32_t n_high = 0, int32_t split = 0,
               const emspec_pcm_format* fmt = nullptr) {
+    if (e && e->time_reduce > 1) return fail(e, EMSPEC_ERR_STATE, kNoLiveReduce);
     const float* samples = static_cast<const float*>(block);
     const int fb = fmt ? pcm_frame_bytes(*fmt) : 1;   // (the float form's stride counts samples)
     if (!e || (!block && count > 0) || count < 0 || stride / fb < count) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument, negative count or stride < count");

@@ -109,8 +109,12 @@ int emspec_batch_multires_device(emspec_engine* e, const float* pcm_dev, int32_t
     if (rc) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     if (!db_dev && !rgba_dev && !index_dev) return EMSPEC_OK;
-    return multires_run(e, pcm_dev, S, L, n_low, n_high, hop, split_row, reassign, db_dev, rgba_dev, index_dev,
-                        (hipStream_t)hip_stream);
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (e->time_reduce == 1) return multires_run(e, pcm_dev, S, L, n_low, n_high, hop, split_row, reassign, db_dev, rgba_dev, index_dev, st);
+    // time reduction: the composed full-rate columns of a chunk of streams into the engine workspace, reduced from there
+    return reduce_streams(e, S, emspec_num_columns(L, n_low, hop), db_dev, rgba_dev, index_dev, st, [=](int s0, int sc, float* fdb, uint8_t* fidx) {
+        return multires_run(e, pcm_dev + (size_t)s0 * L, sc, L, n_low, n_high, hop, split_row, reassign, fdb, nullptr, fidx, st);
+    });
 }
 
 // host buffers: the host-buffer pipeline of emspec_batch (emspec_host.cpp) over whole streams - the two bands' halos differ -

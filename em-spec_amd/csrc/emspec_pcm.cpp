@@ -53,10 +53,10 @@ int emspec_pcm_decode_device(emspec_engine* e, const void* src, const emspec_pcm
     return EMSPEC_OK;
 }
 
-// (the unit function of emspec_batch / emspec_batch_packed: emspec_batch_device on the decoded streams)
+// (the unit function of emspec_batch / emspec_batch_packed: the full-rate emspec_batch_device on the decoded streams)
 static HostRun pcm_batch_run(emspec_engine* e, int n, int hop, int reassign) {
     return [=](const float* pcm, int sc, int64_t samples, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st) {
-        return emspec_batch_device(e, pcm, sc, samples, n, hop, reassign, db, rgba, index, st);
+        return batch_device_full(e, pcm, sc, samples, n, hop, reassign, db, rgba, index, st);
     };
 }
 
@@ -88,7 +88,7 @@ int emspec_batch_pcm_packed(emspec_engine* e, const void* src, const emspec_pcm_
     if (!wire || !offsets || wire_capacity < 0) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument");
     int rc = pcm_batch_check(e, src, fmt, sources, frames, n, hop);
     if (rc) return rc;
-    if ((uint64_t)emspec_num_columns(frames, n, hop) * (uint64_t)e->cfg.rows >= (1ull << 32))
+    if ((uint64_t)reduced_columns(emspec_num_columns(frames, n, hop), e->time_reduce) * (uint64_t)e->cfg.rows >= (1ull << 32))
         return fail(e, EMSPEC_ERR_INVALID_ARG, "at most 2^32 cells per stream");
     if (e->cfg.rows % 4) return fail(e, EMSPEC_ERR_INVALID_ARG, "the wire image needs rows % 4 == 0");
     HIPCHK(e, hipSetDevice(e->device));

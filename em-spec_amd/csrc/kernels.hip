@@ -638,6 +638,7 @@ hipError_t launch_occupy(int groups, int usec, unsigned* sink, hipStream_t st) {
 #include "post.hip.inc"
 #include "multires.hip.inc"
 #include "pack.hip.inc"
+#include "reduce.hip.inc"
 #include "pcm.hip.inc"
 #include "exact.hip.inc"
 #include "exact_fused.hip.inc"

@@ -44,11 +44,14 @@ SYMBOLS = [
     "emspec_multires_columns", "emspec_multires_shift", "emspec_batch_multires", "emspec_batch_multires_device",
     "emspec_pcm_frame_bytes", "emspec_pcm_decode_device", "emspec_batch_pcm", "emspec_batch_pcm_packed",
     "emspec_push_samples_pcm", "emspec_push_samples_pcm_multires",
+    "emspec_set_time_reduce", "emspec_time_reduce", "emspec_reduced_columns",
     "emspec_columns_multires", "emspec_push_columns_multires", "emspec_push_samples_multires",
 ]
 # the multi-resolution live session's entry points: a library built before they existed (tools/live_multires_rate.py times one
 # next to this build) loads without them
 OPTIONAL_SYMBOLS = SYMBOLS[-3:]
+# the time reduction's: likewise (tools/overview_rate.py times the parent commit's library at factor 1)
+REDUCE_SYMBOLS = SYMBOLS[-6:-3]
 
 
 class Config(C.Structure):
@@ -275,6 +278,12 @@ def load(diag=False):
         lib.emspec_push_samples_multires.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                                      C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
                                                      C.c_void_p, C.c_void_p]
+    if all(hasattr(lib, sym) for sym in REDUCE_SYMBOLS):
+        lib.emspec_set_time_reduce.argtypes = [C.c_void_p, C.c_int32]
+        lib.emspec_time_reduce.argtypes = [C.c_void_p]
+        lib.emspec_time_reduce.restype = C.c_int32
+        lib.emspec_reduced_columns.restype = C.c_int64
+        lib.emspec_reduced_columns.argtypes = [C.c_int64, C.c_int32]
     _libs[diag] = lib
     return lib
 
@@ -324,6 +333,12 @@ def default_config(**kw):
 
 def num_columns(L, n, hop):
     return int(load().emspec_num_columns(L, n, hop))
+
+
+def reduced_columns(columns, factor, diag=False):
+    """Columns a batch call delivers per stream at time reduction `factor`: ceil(columns / factor), -1 for columns < 0 or a
+    factor outside 1..65536 (emspec_reduced_columns; no engine, no device)."""
+    return int(load(diag).emspec_reduced_columns(columns, factor))
 
 
 def multires_columns(L, n_low, n_high, hop):
@@ -442,6 +457,20 @@ class Engine:
         """Temporal smoothing in [0,0.95] and adaptive-brightness strength in [0,1]; (0,0) = off."""
         self._chk(self._lib.emspec_set_display(self._h, smoothing, agc_strength))
 
+    def set_time_reduce(self, factor):
+        """Time reduction of the batch entries (emspec_set_time_reduce): groups of `factor` finished columns
+        collapse into one by maximum, every batch call returns reduced_columns(C, factor) columns per stream.  1 = off."""
+        self._chk(self._lib.emspec_set_time_reduce(self._h, int(factor)))
+
+    @property
+    def time_reduce(self):
+        return int(self._lib.emspec_time_reduce(self._h)) if hasattr(self._lib, "emspec_time_reduce") else 1
+
+    def out_columns(self, columns):
+        """Columns per stream a batch call delivers for `columns` full-rate ones at the engine's time reduction."""
+        f = self.time_reduce
+        return columns if f == 1 else reduced_columns(columns, f)
+
     def set_row_edges_hz(self, edges_hz):
         """rows+1 strictly increasing edges in Hz, or None for the configured log axis."""
         if edges_hz is None:
@@ -467,7 +496,7 @@ class Engine:
         if pcm.ndim == 1:
             pcm = pcm[None]
         S, L = pcm.shape
-        Cn = num_columns(L, n, hop)
+        Cn = self.out_columns(num_columns(L, n, hop))
         db = (db_out if db_out is not None else np.empty((S, Cn, self.rows), np.float32)) if "db" in want else None
         assert db is None or (db.shape == (S, Cn, self.rows) and db.dtype == np.float32 and db.flags.c_contiguous)
         rgba = np.empty((S, Cn, self.rows, 4), np.uint8) if "rgba" in want else None
@@ -484,7 +513,7 @@ class Engine:
         if pcm.ndim == 1:
             pcm = pcm[None]
         S, L = pcm.shape
-        Cn = num_columns(L, n, hop)
+        Cn = self.out_columns(num_columns(L, n, hop))
         if wire is None:
             wire = np.empty(S * wire_bound(Cn, self.rows), np.uint8)
         offsets = np.zeros(S + 1, np.int64)
@@ -515,7 +544,7 @@ class Engine:
         """emspec_batch from raw frames: src [sources][frames x channels] of fmt.dtype (S24: uint8, 3 per sample) ->
         {"db", "rgba", "index"} laid out [sources * views][columns][rows]."""
         src, sources, frames = _pcm_rows(src, fmt)
-        S, Cn = sources * fmt.views, num_columns(frames, n, hop)
+        S, Cn = sources * fmt.views, self.out_columns(num_columns(frames, n, hop))
         db = np.empty((S, Cn, self.rows), np.float32) if "db" in want else None
         rgba = np.empty((S, Cn, self.rows, 4), np.uint8) if "rgba" in want else None
         idx = np.empty((S, Cn, self.rows), np.uint8) if "index" in want else None
@@ -527,7 +556,7 @@ class Engine:
     def batch_pcm_packed(self, src, fmt, n, hop, reassign=True, wire=None):
         """emspec_batch_packed from raw frames: (wire uint8 array, offsets int64 [sources * views + 1]), as batch_packed."""
         src, sources, frames = _pcm_rows(src, fmt)
-        S, Cn = sources * fmt.views, num_columns(frames, n, hop)
+        S, Cn = sources * fmt.views, self.out_columns(num_columns(frames, n, hop))
         if wire is None:
             wire = np.empty(S * wire_bound(Cn, self.rows), np.uint8)
         offsets = np.zeros(S + 1, np.int64)
@@ -597,7 +626,7 @@ class Engine:
         if pcm.ndim == 1:
             pcm = pcm[None]
         S, L = pcm.shape
-        Cn = max(multires_columns(L, n_low, n_high, hop), 0)
+        Cn = self.out_columns(max(multires_columns(L, n_low, n_high, hop), 0))
         db = np.empty((S, Cn, self.rows), np.float32) if "db" in want else None
         rgba = np.empty((S, Cn, self.rows, 4), np.uint8) if "rgba" in want else None
         idx = np.empty((S, Cn, self.rows), np.uint8) if "index" in want else None
@@ -672,7 +701,7 @@ class Engine:
         """Host buffers: this rank's streams -> (gathered index [world,S,C,rows] on root else None, own dB or None, wire bytes)."""
         pcm = np.ascontiguousarray(pcm, np.float32)
         S, L = pcm.shape
-        Cn = num_columns(L, n, hop)
+        Cn = self.out_columns(num_columns(L, n, hop))
         allidx = np.empty((self.comm_world, S, Cn, self.rows), np.uint8) if self.comm_rank == root else None
         db = np.empty((S, Cn, self.rows), np.float32) if want_db else None
         sent = C.c_int64(0)

@@ -290,6 +290,12 @@ static napi_value Reset(napi_env env, napi_callback_info info) {
 }
 
 /* batch(handle, pcm:Float32Array(S*L), S, L, fftSize, hop, reassign, outDb?, outRgba?, outIndex?) -> columns per stream */
+/* columns per stream a batch entry DELIVERS for `columns` full-rate ones: the engine's time reduction (emspec_set_time_reduce)
+ * collapses groups of that many columns into one; every output array of the batch calls below is sized by it */
+static int64_t out_columns(const handle_t* h, int64_t columns) {
+    return columns > 0 ? emspec_reduced_columns(columns, emspec_time_reduce(h->e)) : columns;
+}
+
 static napi_value Batch(napi_env env, napi_callback_info info) {
     size_t argc = 10; napi_value argv[10];
     NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -310,7 +316,7 @@ static napi_value Batch(napi_env env, napi_callback_info info) {
     if (!get_typed(env, argv[7], napi_float32_array, &p0, &l0, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outDb must be a Float32Array"); return NULL; }
     if (argc > 8 && !get_typed(env, argv[8], napi_uint8_array, &p1, &l1, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outRgba must be a Uint8Array"); return NULL; }
     if (argc > 9 && !get_typed(env, argv[9], napi_uint8_array, &p2, &l2, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outIndex must be a Uint8Array"); return NULL; }
-    int64_t C = emspec_num_columns(L, n, hop);
+    int64_t C = out_columns(h, emspec_num_columns(L, n, hop));
     /* sizes are checked against rows implied by the first output given */
     size_t cells = 0;
     if (p0) cells = l0; else if (p1) cells = l1 / 4; else if (p2) cells = l2;
@@ -346,7 +352,7 @@ static napi_value BatchMultires(napi_env env, napi_callback_info info) {
     NAPI_OK_OR_RETURN(env, napi_get_value_bool(env, argv[8], &reassign));
     if (S < 1 || L < 1 || (size_t)S * (size_t)L != plen) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "pcm.length must equal S*L"); return NULL; }
     /* C <= 0: a shape (or L) the library rejects, with a message naming the rule, before it touches any output */
-    const int64_t C = emspec_multires_columns(L, nl, nh, hop);
+    const int64_t C = out_columns(h, emspec_multires_columns(L, nl, nh, hop));
     size_t l0 = 0, l1 = 0, l2 = 0; void *p0 = NULL, *p1 = NULL, *p2 = NULL;
     if (!get_typed(env, argv[9], napi_float32_array, &p0, &l0, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outDb must be a Float32Array"); return NULL; }
     if (argc > 10 && !get_typed(env, argv[10], napi_uint8_array, &p1, &l1, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outRgba must be a Uint8Array"); return NULL; }
@@ -394,7 +400,7 @@ static napi_value BatchPacked(napi_env env, napi_callback_info info) {
     if (rc == EMSPEC_OK) for (int32_t i = 0; i <= S; ++i) ((double*)offs)[i] = (double)o64[i];
     free(o64);
     if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
-    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int64(env, emspec_num_columns(L, n, hop), &r));
+    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int64(env, out_columns(h, emspec_num_columns(L, n, hop)), &r));
     return r;
 }
 
@@ -489,7 +495,7 @@ static napi_value BatchAsync(napi_env env, napi_callback_info info) {
     if (!get_typed(env, argv[7], napi_float32_array, &p0, &l0, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outDb must be a Float32Array"); return NULL; }
     if (argc > 8 && !get_typed(env, argv[8], napi_uint8_array, &p1, &l1, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outRgba must be a Uint8Array"); return NULL; }
     if (argc > 9 && !get_typed(env, argv[9], napi_uint8_array, &p2, &l2, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outIndex must be a Uint8Array"); return NULL; }
-    int64_t C = emspec_num_columns(L, n, hop);
+    int64_t C = out_columns(h, emspec_num_columns(L, n, hop));
     size_t cells = p0 ? l0 : (p1 ? l1 / 4 : l2);
     if (C <= 0 || cells != (size_t)S * (size_t)C * (size_t)h->rows || (p1 && l1 != 4 * cells) || (p2 && l2 != cells) || (p0 && l0 != cells)) {
         napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "output arrays must hold exactly S*columns*rows cells, rows = the engine's row count (rgba: 4 bytes per cell)");
@@ -585,7 +591,7 @@ static napi_value BatchPackedAsync(napi_env env, napi_callback_info info) {
     if (j) j->o64 = (int64_t*)malloc(sizeof(int64_t) * ((size_t)S + 1));
     if (!j || !j->o64) { free(j); napi_throw_error(env, "EMSPEC_ERR_OUT_OF_MEMORY", "out of host memory"); return NULL; }
     j->e = h->e; j->pcm = (const float*)pcm; j->S = S; j->L = L; j->n = n; j->hop = hop; j->reassign = reassign ? 1 : 0;
-    j->C = emspec_num_columns(L, n, hop); j->wire = (uint8_t*)wire; j->wire_len = (int64_t)wlen; j->offs = (double*)offs;
+    j->C = out_columns(h, emspec_num_columns(L, n, hop)); j->wire = (uint8_t*)wire; j->wire_len = (int64_t)wlen; j->offs = (double*)offs;
     napi_value promise, name;
     if (napi_create_promise(env, &j->deferred, &promise) != napi_ok) { free(j->o64); free(j); napi_throw_error(env, "EMSPEC_NAPI", "napi_create_promise"); return NULL; }
     napi_create_reference(env, argv[1], 1, &j->refs[0]);
@@ -828,7 +834,7 @@ static napi_value BatchPcm(napi_env env, napi_callback_info info) {
     if (!get_typed(env, argv[10], napi_float32_array, &p0, &l0, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outDb must be a Float32Array"); return NULL; }
     if (argc > 11 && !get_typed(env, argv[11], napi_uint8_array, &p1, &l1, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outRgba must be a Uint8Array"); return NULL; }
     if (argc > 12 && !get_typed(env, argv[12], napi_uint8_array, &p2, &l2, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outIndex must be a Uint8Array"); return NULL; }
-    const int64_t C = frames > 0 ? emspec_num_columns(frames, n, hop) : 0;
+    const int64_t C = frames > 0 ? out_columns(h, emspec_num_columns(frames, n, hop)) : 0;
     size_t cells = 0;
     if (p0) cells = l0; else if (p1) cells = l1 / 4; else if (p2) cells = l2;
     /* (C <= 0: an invalid format or shape - the library rejects it with its message before it touches any output) */
@@ -871,7 +877,7 @@ static napi_value BatchPcmPacked(napi_env env, napi_callback_info info) {
     if (rc == EMSPEC_OK) for (size_t i = 0; i <= S; ++i) ((double*)offs)[i] = (double)o64[i];
     free(o64);
     if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
-    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int64(env, emspec_num_columns(frames, n, hop), &r));
+    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int64(env, out_columns(h, emspec_num_columns(frames, n, hop)), &r));
     return r;
 }
 
@@ -1044,6 +1050,36 @@ static napi_value SetDisplay(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* setTimeReduce(handle, factor): emspec_set_time_reduce (1 = off .. 65536); timeReduce(handle) -> the factor in force;
+ * reducedColumns(columns, factor) -> ceil(columns / factor), -1 on invalid arguments (no engine) */
+static napi_value SetTimeReduce(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    int32_t f = 0;
+    if (argc < 2 || napi_get_value_int32(env, argv[1], &f) != napi_ok) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "setTimeReduce(handle, factor)"); return NULL; }
+    int rc = emspec_set_time_reduce(h->e, f);
+    if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
+    return NULL;
+}
+static napi_value TimeReduce(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int32(env, emspec_time_reduce(h->e), &r));
+    return r;
+}
+static napi_value ReducedColumns(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    int64_t c = 0; int32_t f = 0;
+    if (argc < 2) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "reducedColumns(columns, factor)"); return NULL; }
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[0], &c));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[1], &f));
+    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int64(env, emspec_reduced_columns(c, f), &r));
+    return r;
+}
+
 /* setRowEdges(handle, Float32Array(rows+1) | null) ; getRowEdges(handle, Float32Array(rows+1)) */
 static napi_value SetRowEdges(napi_env env, napi_callback_info info) {
     size_t argc = 2; napi_value argv[2];
@@ -1169,7 +1205,7 @@ static napi_value BatchGather(napi_env env, napi_callback_info info) {
     void *pall = NULL, *pdb = NULL; size_t lall = 0, ldb = 0;
     if (argc > 8 && !get_typed(env, argv[8], napi_uint8_array, &pall, &lall, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outAllIndex must be a Uint8Array"); return NULL; }
     if (argc > 9 && !get_typed(env, argv[9], napi_float32_array, &pdb, &ldb, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outDb must be a Float32Array"); return NULL; }
-    const int64_t C = emspec_num_columns(L, n, hop);
+    const int64_t C = out_columns(h, emspec_num_columns(L, n, hop));
     const int32_t world = emspec_comm_world(h->e), rank = emspec_comm_rank(h->e);
     const size_t cells = (size_t)S * (size_t)(C > 0 ? C : 0) * (size_t)h->rows;
     if (world < 1) { napi_throw_error(env, "EMSPEC_ERR_STATE", "no communicator: call commInit first"); return NULL; }
@@ -1228,6 +1264,9 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"wireBound", NULL, WireBound, NULL, NULL, NULL, napi_default, NULL},
         {"setColormap", NULL, SetColormap, NULL, NULL, NULL, napi_default, NULL},
         {"setDisplay", NULL, SetDisplay, NULL, NULL, NULL, napi_default, NULL},
+        {"setTimeReduce", NULL, SetTimeReduce, NULL, NULL, NULL, napi_default, NULL},
+        {"timeReduce", NULL, TimeReduce, NULL, NULL, NULL, napi_default, NULL},
+        {"reducedColumns", NULL, ReducedColumns, NULL, NULL, NULL, napi_default, NULL},
         {"setRowEdges", NULL, SetRowEdges, NULL, NULL, NULL, napi_default, NULL},
         {"getRowEdges", NULL, GetRowEdges, NULL, NULL, NULL, napi_default, NULL},
         {"allocPinned", NULL, AllocPinned, NULL, NULL, NULL, napi_default, NULL},

@@ -14,18 +14,32 @@
 const native = require('./emspec.node');
 
 class Engine {
-  /** config: {device, rows, sampleRate, fminHz, fmaxHz, gain, dbTop, dbRange, gateDb, powerFloor, exact, streams}
+  /** config: {device, rows, sampleRate, fminHz, fmaxHz, gain, dbTop, dbRange, gateDb, powerFloor, exact, streams, timeReduce}
    *  exact: true = EMSPEC_MODE_EXACT (binary64 arithmetic, 64-bit fixed-point histogram; include/emspec.h)
    *  streams: S > 1 = a live multi-stream engine: computeSpectrogramColumns / pushSamplesMulti advance all S streams per
    *  call in ONE kernel launch; its frame / column blocks are page-locked (engine.frames, engine.columnsDb, ...), so the
-   *  kernel reads and writes them in place */
+   *  kernel reads and writes them in place
+   *  timeReduce: f > 1 = the batch calls (computeColumns, computeColumnsPacked, computeColumnsMultires, their PCM and async
+   *  forms) return ceil(columns / f) columns per stream, each the maximum of f consecutive finished columns (setTimeReduce) */
   constructor(config = {}) {
     this.rows = native.rows(config);
     this._h = native.create(config);
     this._db = new Float32Array(this.rows);
     this.streams = Math.max(1, config.streams | 0);
     this.columnIndex = new Float64Array(this.streams);   // per stream: index of the column the last call returned (-1: empty)
+    if (config.timeReduce !== undefined && config.timeReduce !== 1) this.setTimeReduce(config.timeReduce);
   }
+
+  /**
+   * Time reduction of the batch calls (emspec_set_time_reduce; the zoomed-out overview of a recording): groups of `factor`
+   * consecutive finished columns collapse into one by maximum, on the device - dB by value, palette index by value, RGBA =
+   * colour map at the reduced index.  Every batch call then takes output arrays of S * reducedColumns(C, factor) * rows cells
+   * (wire: S * wireBound(reducedColumns(C, factor), rows)) and returns that column count; column g covers the time of columns
+   * g * factor .. of the full-rate picture.  1 = off.  The live calls throw while factor > 1; setting it throws while a live
+   * session has columns pending.
+   */
+  setTimeReduce(factor) { native.setTimeReduce(this._h, factor | 0); }
+  get timeReduce() { return native.timeReduce(this._h); }
 
   /** Page-locked Float32Array / Uint8Array views for the live calls, (re)made when the shape changes. */
   _liveBlocks(fftSize, wantRgba) {
@@ -405,6 +419,8 @@ module.exports = {
   colormapStops,
   commUniqueId: native.commUniqueId,
   numColumns: native.numColumns,
+  /** Columns per stream a batch call delivers at time reduction f: ceil(columns / f); -1 on invalid arguments. */
+  reducedColumns: native.reducedColumns,
   /** Bytes that always hold the wire image of `columns` columns of `rows` rows (emspec_wire_bound). */
   wireBound: native.wireBound,
   /** Expand one wire image (Uint8Array) into out: Uint8Array(columns * rows) on the host's own cores - no device, no engine. */

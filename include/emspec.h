@@ -457,6 +457,37 @@ int emspec_batch_packed(emspec_engine* e, const float* pcm, int32_t streams, int
                         int32_t hop, int32_t reassign, uint8_t* wire, int64_t wire_capacity, int64_t* offsets);
 int emspec_wire_unpack_host(const uint8_t* wire, int64_t wire_bytes, int64_t columns, int32_t rows, uint8_t* index_out);
 
+/*
+ * Time reduction [BUILD-DEFINED]: the zoomed-out view of a recording - the reference's "Scroll Speed"
+ * (README.md:44) - computed on the device.  With factor f > 1 a batch call whose full-rate result would be C columns per stream
+ * delivers Cr = emspec_reduced_columns(C, f) = ceil(C / f) columns: groups of f consecutive finished columns collapse into one
+ * by maximum (peak hold: a click or a short tone stays visible at any zoom), the last group being the C - (Cr - 1) f columns
+ * that remain.  With full_* what the same call returns at f = 1 - the display post-process (emspec_set_display: smoothing and
+ * AGC run at full rate) and the multi-resolution composition included - for g in [0, Cr), r in [0, rows):
+ *     db   [s][g][r] = m,  where m = full_db[s][g f][r]; then for c = g f + 1 .. min((g + 1) f, C) - 1 in order:
+ *                          if (full_db[s][c][r] > m) m = full_db[s][c][r]
+ *     index[s][g][r] = max over the group of full_index[s][c][r]      (unsigned bytes)
+ *     rgba [s][g][r] = LUT[index[s][g][r]]
+ * exact in either arithmetic mode: the reduced bytes follow from the full-rate bytes.  Layouts are those of the entry with Cr in
+ * place of the column count; column g is centred in time on its group (the host maps pixels to time with f * hop).
+ * Honoured by emspec_batch_device, emspec_batch, emspec_batch_packed, emspec_batch_pcm, emspec_batch_pcm_packed,
+ * emspec_batch_multires, emspec_batch_multires_device and emspec_batch_gather (whose gathered layout is [world][S][Cr][rows]).
+ * The packed entries pack the REDUCED columns: the header's column count is Cr, wire_capacity = streams x emspec_wire_bound(Cr,
+ * rows) always suffices, and the 2^32-cell limit applies to Cr x rows.  The device entries keep a chunk of streams' full-rate
+ * columns in an engine workspace bounded like the records path's (1 byte per cell when only index / RGBA are asked for, 4 more
+ * with dB); the host entries reduce inside each unit's staging set, and their copies out shrink by f.
+ * Not affected: the parity dumps, emspec_pcm_decode_device, emspec_wire_*, emspec_gather_columns (its caller's column count
+ * rules).  The STREAMING calls - emspec_column, emspec_push_samples, emspec_columns*, emspec_push_samples_*, the flushes - return
+ * EMSPEC_ERR_STATE while f > 1 (a live host takes the maximum of a handful of 1 KB columns itself).
+ * emspec_set_time_reduce: factor in 1 (off, the default) .. 65536, else EMSPEC_ERR_INVALID_ARG; EMSPEC_ERR_STATE while a
+ *   streaming session has columns pending (as emspec_set_row_edges_hz).  A refusal changes nothing.
+ * emspec_time_reduce: the factor in force, -1 for NULL.
+ * emspec_reduced_columns: ceil(columns / factor); -1 for columns < 0 or a factor outside 1 .. 65536.  No engine needed.
+ */
+int emspec_set_time_reduce(emspec_engine* e, int32_t factor);
+int32_t emspec_time_reduce(const emspec_engine* e);
+int64_t emspec_reduced_columns(int64_t columns, int32_t factor);
+
 /* Copy out the tables the kernels use for (n): row edges in bin units
  * (rows+1 floats) and the twiddle table (n/2 complex = n floats, re,im
  * interleaved).  Either pointer may be NULL.  For table-parity tests. */
