@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <condition_variable>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -329,8 +330,11 @@ int emspec::host_batch(emspec_engine* e, const void* pcm, int S, int64_t L, int 
                 herr = hipMemcpyAsync(pk->wire + at, q.wire + (size_t)i * g.wire, (size_t)bytes, hipMemcpyDeviceToHost, s_out);
                 // every image STARTS on a 16-byte boundary: the fixed part (32 + 4 C (1 + R/32) bytes) is a multiple of 4 only, so
                 // up to 12 bytes of slack follow an image (stream s occupies [offsets[s], offsets[s+1]), slack included; the
-                // unpackers take the image's real size from its header)
-                pk->offsets[it.s0 * V + i + 1] = (at + bytes + 15) & ~(int64_t)15;
+                // unpackers take the image's real size from its header).  The slack is cleared: the bytes of wire[0 .. offsets[S])
+                // are then the same whatever the caller's buffer held before, as an image's own pad is (pack.hip.inc)
+                const int64_t end = (at + bytes + 15) & ~(int64_t)15;
+                if (std::min(end, pk->capacity) > at + bytes) std::memset(pk->wire + at + bytes, 0, (size_t)(std::min(end, pk->capacity) - (at + bytes)));
+                pk->offsets[it.s0 * V + i + 1] = end;
             }
         }
         if (herr == hipSuccess && rc == EMSPEC_OK && !one) herr = hipEventRecord(ev_out[b], s_out);

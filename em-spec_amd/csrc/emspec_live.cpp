@@ -161,8 +161,10 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
     ls.stamps = lv.stamps;
 #endif
     // with the post-process the frame kernel's columns are raw dB on the device, laid out like the destination
+    // (a call without outputs - a priming block - may complete more columns than its max_columns: out_cols bounds the raw
+    // block's stride only where it is an output's stride)
     if (post) {
-        raw_cols = std::max(1, std::min(raw_cols, out_cols));
+        raw_cols = std::max(1, (dst_db || dst_rgba) ? std::min(raw_cols, out_cols) : raw_cols);
         if ((size_t)lv.S * raw_cols * R * 4 > lv.raw_bytes &&
             (rc = grow(e, (void**)&lv.d_raw, &lv.raw_bytes, (size_t)lv.S * raw_cols * R * 4))) return rc;
         ls.out_db = lv.d_raw;

@@ -92,7 +92,9 @@ typedef struct emspec_config {
  *                      bytes do not depend on the host's C library; "(column,row) agree with a
  *                      float64 implementation on every bin" is a measured statement: 0 mismatches in > 10^8 values, where
  *                      two binary64 evaluations may still differ on a bin within ~1e-13 of an edge).  Inputs must stay
- *                      within |x| <= 4 (the fixed point covers 2^11 full-scale-sine powers per cell).  Same entry points;
+ *                      within |x| <= 4 (the fixed point covers 2^11 full-scale-sine powers per cell).  Cell sums are taken
+ *                      modulo 2^64: one bin carries at most 2^61 units (2^9 full-scale sines; louder bins are dropped), and a
+ *                      cell that receives more than 2^63 units is outside the guarantee (its sum wraps).  Same entry points;
  *                      emspec_parity_dump_exact replaces emspec_parity_dump.  Roughly 2.1x slower than the fast mode at N = 4096.
  */
 #define EMSPEC_MODE_FAST 0
@@ -221,6 +223,7 @@ int emspec_column_flush(emspec_engine* e, float* out_db, uint8_t* out_rgba,
  * emspec_push_columns() tells in advance how many columns a block of `count`
  * samples will complete (for sizing the outputs; -1 on invalid arguments); a
  * block that completes more than max_columns is rejected before any state changes.
+ * (With both outputs NULL - a priming call - max_columns is not consulted: the columns are completed and dropped.)
  * The D columns pending after the last block are drained with emspec_column_flush;
  * samples short of a hop are dropped by emspec_reset.  One stream must be fed
  * through either emspec_column or emspec_push_samples, not both (EMSPEC_ERR_STATE).
@@ -443,8 +446,9 @@ int emspec_wire_unpack(emspec_engine* e, const uint8_t* wire_dev, int64_t wire_b
  * what crosses PCIe is the lossless wire image above (~186 B instead of 1,024 B per column on typical audio), ONE IMAGE
  * PER STREAM, tightly packed into `wire` (host memory, pinned for full speed) in stream order: stream s occupies
  * wire[offsets[s] .. offsets[s+1]) (offsets: streams + 1 entries, offsets[0] = 0; every image STARTS on a 16-byte boundary,
- * so up to 12 bytes of unspecified slack may follow an image inside its slot - an image's own size is in its header, and
- * emspec_wire_unpack_host / emspec_wire_unpack accept the slot as it is).
+ * so up to 12 bytes of slack may follow an image inside its slot, cleared to zero - wire[0 .. offsets[streams]) holds the
+ * same bytes whatever the buffer held before; an image's own size is in its header, and emspec_wire_unpack_host /
+ * emspec_wire_unpack accept the slot as it is).
  * wire_capacity = streams x emspec_wire_bound(columns, rows) always suffices; EMSPEC_ERR_INVALID_ARG when the images do not
  * fit.  Runs the three-stage pipeline of emspec_batch (H2D | kernels + pack | D2H on three HIP streams); rows % 4 == 0.
  * Serves: the renderer-side batched computeColumns when the host keeps or forwards the columns compressed

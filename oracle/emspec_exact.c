@@ -281,7 +281,10 @@ int eo_batch_exact(const eo_cfg* c, const float* pcm, int32_t S, int64_t L, cons
         for (int64_t j = 0; j < C; ++j) {
             ex_frame(&p, c, x + j * c->hop, j, buf, NULL, cl, rw, qq);
             for (int k = 0; k < K; ++k)
-                if (rw[k] >= 0 && cl[k] >= 0 && cl[k] < C) hist[(size_t)cl[k] * R + rw[k]] += qq[k];
+                if (rw[k] >= 0 && cl[k] >= 0 && cl[k] < C) { /* the sum is taken modulo 2^64, as the kernels' u64 adds are */
+                    int64_t* cell = &hist[(size_t)cl[k] * R + rw[k]];
+                    *cell = (int64_t)((uint64_t)*cell + (uint64_t)qq[k]);
+                }
         }
         size_t base = (size_t)s * C * R;
         for (size_t i = 0; i < (size_t)C * R; ++i) {

@@ -246,3 +246,27 @@ def test_packed_batch_images_start_on_16_byte_boundaries_for_any_column_count(co
             finally:
                 if pinned:
                     pin.close(); pw.close()
+
+
+def test_packed_images_do_not_depend_on_what_the_buffer_held():
+    """emspec_batch_packed writes every byte of wire[0 .. offsets[S]): the images, their zero pad and the (up to 12) slack bytes
+    that bring the next image to a 16-byte boundary - over a buffer that held 0xAB the bytes equal those over a zeroed one.
+    (C = 497 columns of 1,024 rows: the fixed part of an image is 4 mod 16, so every image is followed by 12 bytes of slack.)"""
+    n, hop, S, L = 4096, 256, 3, 1 << 17
+    pcm = synth.streams(S, L)
+    Cn = emspec.num_columns(L, n, hop)
+    with emspec.Engine(mode=emspec.MODE_EXACT) as e:
+        cap = S * emspec.wire_bound(Cn, e.rows)
+        wa, oa = e.batch_packed(pcm, n, hop, True, wire=np.full(cap, 0xAB, np.uint8))
+        wb, ob = e.batch_packed(pcm, n, hop, True, wire=np.zeros(cap, np.uint8))
+        assert np.array_equal(oa, ob) and np.all(oa % 16 == 0)
+        assert np.array_equal(wa[:oa[-1]], wb[:ob[-1]])
+        assert np.all(wa[oa[-1]:] == 0xAB)                    # nothing past the last slot is touched
+        slack = 0
+        for s in range(S):
+            hdr = wa[oa[s]:oa[s] + 32].view(np.uint32)
+            size = 32 + Cn * 4 + Cn * (e.rows // 32) * 4 + ((int(hdr[4]) | int(hdr[5]) << 32) + 15) // 16 * 16
+            assert np.all(wa[oa[s] + size:oa[s + 1]] == 0)
+            slack += int(oa[s + 1] - oa[s]) - size
+            assert np.array_equal(emspec.wire_unpack_host(wa[oa[s]:oa[s + 1]], Cn, e.rows), emspec.wire_unpack_host(wb[ob[s]:ob[s + 1]], Cn, e.rows))
+        assert slack == 12 * S

@@ -347,3 +347,58 @@ def test_live_session_of_4000_hops_equals_the_batch_bits():
         blk.close(); out.close()
     assert seen == Cn and bad == 0, (seen, bad)
 
+
+
+def _push_abi(e, pcm, a, cnt, n, hop, out, max_columns):
+    """emspec_push_samples_multi through the ABI itself (the wrapper always sizes max_columns to what the block completes):
+    out = None passes NULL for both outputs.  Returns the per-stream counts."""
+    import ctypes as C
+    S, width = pcm.shape
+    counts, firsts = np.full(S, -7, np.int64), np.full(S, -7, np.int64)
+    rc = e._lib.emspec_push_samples_multi(e._h, C.c_void_p(pcm.ctypes.data + 4 * a), S, cnt, width, n, hop, 1,
+                                          C.c_void_p(out.ctypes.data) if out is not None else None, None, e.rows, max_columns,
+                                          C.c_void_p(counts.ctypes.data), C.c_void_p(firsts.ctypes.data))
+    e._chk(rc)
+    return counts, firsts
+
+
+@pytest.mark.parametrize("exact", [False, True], ids=["fast", "exact"])
+@pytest.mark.parametrize("display", [True, False], ids=["display", "raw"])
+@pytest.mark.parametrize("max_columns", [0, 8, 40])
+def test_priming_block_with_null_outputs(max_columns, display, exact):
+    """A priming call - both outputs NULL - is accepted whatever its max_columns (0: the block completes 8 columns more than
+    that; 8: exactly; 40: more room than needed), display post-process on or off, and the session goes on as if the
+    columns had been delivered: the next block's columns equal those of a session that received both blocks with outputs - with the
+    post-process on they depend on the smoothing / AGC state the priming columns left behind.  (With the post-process on the
+    frame kernels write the priming columns to a device block of the session's own: its stride is what the block completes, not
+    the caller's max_columns.)"""
+    S, n, hop = 3, 1024, 256
+    pcm = np.ascontiguousarray(synth.streams(S, n + hop * 15))
+    first, second = n + hop * 9, hop * 6                 # frames 0..9 -> columns 0..7; frames 10..15 -> columns 8..13
+    mode = emspec.MODE_EXACT if exact else emspec.MODE_FAST
+    outs = []
+    for prime in (True, False):
+        with emspec.Engine(mode=mode) as e:
+            if display:
+                e.set_display(0.6, 0.8)
+            assert e.push_columns_multi(first, n, hop, True) == 8
+            db1 = None if prime else np.empty((S, 8, 1024), np.float32)
+            counts, firsts = _push_abi(e, pcm, 0, first, n, hop, db1, max_columns if prime else 8)
+            assert np.all(counts == 8) and np.all(firsts == 0)
+            db2 = np.full((S, 6, 1024), np.nan, np.float32)
+            counts, firsts = _push_abi(e, pcm, first, second, n, hop, db2, 6)
+            assert np.all(counts == 6) and np.all(firsts == 8)
+            # the engine stays usable: the pending columns drain
+            _, _, cols = e.columns_flush()
+            assert np.all(cols == 14)
+            outs.append(db2)
+    primed, plain = outs
+    assert not np.isnan(primed).any()
+    if exact:
+        assert np.array_equal(primed.view(np.uint32), plain.view(np.uint32))
+    else:   # float32 sums in arrival order: the module's tolerances (2e-3 behind the post-process, as the display tests above)
+        assert np.max(np.abs(primed - plain)) < (2e-3 if display else TOL_DB)
+    # ... and they are the oracle's columns 8..13 when nothing is post-processed
+    if not display:
+        odb, _ = _oracle(n, hop, True, pcm, exact, want=("db",))
+        _same_db(primed, odb[:, 8:14], exact)
