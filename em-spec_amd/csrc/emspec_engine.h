@@ -96,12 +96,15 @@ bool host_pinned(const void* p);   // p is null or page-locked host memory the d
 // are runs of a stream's columns with halo_D columns on either side, or whole streams when halo_D is -1; a unit of whole streams
 // holds at least min_streams of them (or all S).
 struct PackedOut { uint8_t* wire; int64_t capacity; int64_t* offsets; };
+// emspec_batch_peaks: instead of columns, the k loudest peaks at or above min_db of every column, [S][columns][k] (f = 1 only)
+struct PeaksOut { emspec_peak* peaks; int k; float min_db; };
 using HostRun = std::function<int(const float* pcm, int sc, int64_t samples, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st)>;
 // `dec` (emspec_batch_pcm, emspec_batch_pcm_packed): pcm is raw interleaved frames, S SOURCES of L frames; the copy-in stage
 // moves those bytes, the decode kernel (pcm.hip.inc) fills the unit's float streams in front of `run`, which then sees
 // sc * dec->views streams, and the outputs are those of S * dec->views streams.  Null: pcm is float32 [S][L].
 int host_batch(emspec_engine* e, const void* pcm, int S, int64_t L, int n, int hop, int halo_D, int min_streams,
-               const emspec_out* out, const PackedOut* pk, const HostRun& run, const emspec_pcm_format* dec = nullptr);
+               const emspec_out* out, const PackedOut* pk, const HostRun& run, const emspec_pcm_format* dec = nullptr,
+               const PeaksOut* pko = nullptr);
 // (with the engine's time reduction f > 1, `run` still computes FULL-rate columns - dB and / or index, never RGBA - into the
 // unit's staging set; host_batch launches the reduction behind it and delivers ceil(columns / f) columns per stream)
 // emspec_pcm.cpp: null, or what is wrong with the format (names the field); bytes per interleaved frame of a valid format

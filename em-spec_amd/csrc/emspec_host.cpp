@@ -96,7 +96,8 @@ size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // (db / rgba / idx: what the unit's kernels write; odb / orgba / oidx: what is delivered - the same arrays, or with a time
 // reduction the reduced columns beside them)
-struct Set { float* pcm; float* db; uint8_t* rgba; uint8_t* idx; uint8_t* wire; char* raw; float* odb; uint8_t* orgba; uint8_t* oidx; };
+// (peaks: the unit's peak lists, emspec_batch_peaks)
+struct Set { float* pcm; float* db; uint8_t* rgba; uint8_t* idx; uint8_t* wire; char* raw; float* odb; uint8_t* orgba; uint8_t* oidx; emspec_peak* peaks; };
 
 // The staging set: every array at the size the largest unit needs (the wire images: one slot of `wire` bytes per stream).
 struct Stage {
@@ -104,24 +105,27 @@ struct Stage {
     size_t raw = 0;  // PCM entries: the unit's raw frames, which the decode kernel turns into `in`
     size_t rdb = 0, rrgba = 0, ridx = 0;   // time reduction: the unit's reduced columns (db / idx then hold the full-rate ones)
     bool reduced = false;
+    size_t peaks = 0;   // emspec_batch_peaks: k (pos, dB) pairs per kept column of the unit
     int chunk = 1;   // streams in the largest unit
-    size_t bytes() const { return in + db + rgba + idx + wire * chunk + raw + rdb + rrgba + ridx; }
+    size_t bytes() const { return in + db + rgba + idx + wire * chunk + raw + rdb + rrgba + ridx + peaks; }
     Set at(char* stage, int b) const {
         char* base = stage + (size_t)b * bytes();
         Set q{(float*)base, db ? (float*)(base + in) : nullptr, rgba ? (uint8_t*)(base + in + db) : nullptr,
               idx ? (uint8_t*)(base + in + db + rgba) : nullptr, wire ? (uint8_t*)(base + in + db + rgba + idx) : nullptr,
-              raw ? base + in + db + rgba + idx + wire * chunk : nullptr, nullptr, nullptr, nullptr};
+              raw ? base + in + db + rgba + idx + wire * chunk : nullptr, nullptr, nullptr, nullptr, nullptr};
         char* r = base + in + db + rgba + idx + wire * chunk + raw;
         q.odb = reduced ? (rdb ? (float*)r : nullptr) : q.db;
         q.orgba = reduced ? (rrgba ? (uint8_t*)(r + rdb) : nullptr) : q.rgba;
         q.oidx = reduced ? (ridx ? (uint8_t*)(r + rdb + rrgba) : nullptr) : q.idx;
+        q.peaks = peaks ? (emspec_peak*)(r + rdb + rrgba + ridx) : nullptr;
         return q;
     }
 };
 
 // (V streams per unit of PipeItem::sc, frame_bytes of raw input each: 1 and 0 for the float entries, whose units are streams)
 // (f > 1: dB and / or index at full rate - the index also when only RGBA is wanted - and the delivered arrays at the reduced rate)
-Stage stage_layout(const std::vector<PipeItem>& items, int R, bool db, bool rgba, bool idx, size_t wire_s, int V, int frame_bytes, int f) {
+// (peaks_k > 0: a region of peaks_k pairs per kept column)
+Stage stage_layout(const std::vector<PipeItem>& items, int R, bool db, bool rgba, bool idx, size_t wire_s, int V, int frame_bytes, int f, int peaks_k) {
     Stage g;
     size_t cells = 0, rcells = 0;
     for (const PipeItem& it : items) {
@@ -130,6 +134,7 @@ Stage stage_layout(const std::vector<PipeItem>& items, int R, bool db, bool rgba
         g.raw = std::max(g.raw, frame_bytes ? al((size_t)it.samples * frame_bytes * it.sc) : 0);
         cells = std::max(cells, (size_t)it.cols * R * it.sc * V);
         g.chunk = std::max(g.chunk, it.sc * V);
+        g.peaks = std::max(g.peaks, al((size_t)it.cn * it.sc * V * peaks_k * sizeof(emspec_peak)));
     }
     g.reduced = f > 1;
     g.db = db ? al(cells * 4) : 0;
@@ -170,7 +175,7 @@ bool emspec::host_pinned(const void* p) {
 }
 
 int emspec::host_batch(emspec_engine* e, const void* pcm, int S, int64_t L, int n, int hop, int halo_D, int min_streams,
-                       const emspec_out* out, const PackedOut* pk, const HostRun& run, const emspec_pcm_format* dec) {
+                       const emspec_out* out, const PackedOut* pk, const HostRun& run, const emspec_pcm_format* dec, const PeaksOut* pko) {
     if (!e->stream_in) HIPCHK(e, hipStreamCreateWithFlags(&e->stream_in, hipStreamNonBlocking));
     if (!e->stream_out) HIPCHK(e, hipStreamCreateWithFlags(&e->stream_out, hipStreamNonBlocking));
     for (hipEvent_t& ev : e->pipe_ev)
@@ -182,21 +187,25 @@ int emspec::host_batch(emspec_engine* e, const void* pcm, int S, int64_t L, int 
     // dec: the S rows are SOURCES of interleaved frames (emspec_batch_pcm): fb bytes per frame in, V streams each out
     const int V = dec ? dec->views : 1, fb = dec ? pcm_frame_bytes(*dec) : (int)sizeof(float);
     const size_t col_cells = (size_t)C * R, out_cells = (size_t)Cr * R, in_s = (size_t)L * fb;
-    const bool want_db = out && out->db, want_rgba = out && out->rgba, want_idx = (out && out->index) || pk;
+    // (pko: the dB columns are staged for the peaks kernel and stay on the device; only the peak lists are delivered)
+    const int pkk = pko ? pko->k : 0;
+    const bool want_db = out && out->db, stage_db = want_db || pko, want_rgba = out && out->rgba, want_idx = (out && out->index) || pk;
     const size_t wire_s = pk ? (size_t)wire_bound_bytes(Cr, R) : 0;
     size_t per_stream = al(in_s) + (dec ? al((size_t)L * 4 * V) : 0) +
-                        V * (al(want_db ? col_cells * 4 : 0) + al(want_rgba ? col_cells * 4 : 0) + al(want_idx ? col_cells : 0) + al(wire_s));
+                        V * (al(stage_db ? col_cells * 4 : 0) + al(want_rgba ? col_cells * 4 : 0) + al(want_idx ? col_cells : 0) + al(wire_s) +
+                             al((size_t)C * pkk * sizeof(emspec_peak)));
     if (f > 1)   // full-rate dB / index (no full-rate RGBA) and the reduced arrays
         per_stream = al(in_s) + (dec ? al((size_t)L * 4 * V) : 0) +
                      V * (al(want_db ? col_cells * 4 : 0) + al(want_idx || want_rgba ? col_cells : 0) + al(wire_s) +
                           al(want_db ? out_cells * 4 : 0) + al(want_rgba ? out_cells * 4 : 0) + al(want_idx ? out_cells : 0));
     int units = pipe_units(e->exact(), n, (int64_t)S * V * C, (size_t)S * in_s,
-                           pk ? (size_t)S * V * out_cells / 5 : (size_t)S * V * out_cells * ((want_db ? 4 : 0) + (want_rgba ? 4 : 0) + (want_idx ? 1 : 0)));
+                           pk ? (size_t)S * V * out_cells / 5 : (size_t)S * V * out_cells * ((want_db ? 4 : 0) + (want_rgba ? 4 : 0) + (want_idx ? 1 : 0)) +
+                                (size_t)S * V * C * pkk * sizeof(emspec_peak));
     if (halo_D < 0) units = std::min(units, std::max(S / min_streams, 1));   // whole streams: at least min_streams per unit
     const std::vector<PipeItem> items = pipe_items(S, L, C, n, hop, halo_D, per_stream, halo_D >= 0, units, f);
     const int nu = (int)items.size();
     const bool one = nu == 1;
-    const Stage g = stage_layout(items, R, want_db, want_rgba, want_idx, wire_s, V, dec ? fb : 0, f);
+    const Stage g = stage_layout(items, R, stage_db, want_rgba, want_idx, wire_s, V, dec ? fb : 0, f, pkk);
     if ((rc = grow(e, (void**)&e->d_stage, &e->stage_bytes, std::min(nu, kPipeSets) * g.bytes() + 1024))) return rc;
     if (pk) {
         if ((rc = grow(e, (void**)&e->d_packscratch, &e->packscratch_bytes, wire_scratch_bytes(Cr)))) return rc;
@@ -221,6 +230,9 @@ int emspec::host_batch(emspec_engine* e, const void* pcm, int S, int64_t L, int 
             if (r == hipSuccess && want_db) r = hipMemcpyAsync(out->db + sp.to, q.odb + sp.from, sp.cells * 4, hipMemcpyDeviceToHost, st);
             if (r == hipSuccess && want_rgba) r = hipMemcpyAsync(out->rgba + 4 * sp.to, q.orgba + 4 * sp.from, sp.cells * 4, hipMemcpyDeviceToHost, st);
             if (r == hipSuccess && want_idx) r = hipMemcpyAsync(out->index + sp.to, q.oidx + sp.from, sp.cells, hipMemcpyDeviceToHost, st);
+            // (peak lists: the set holds the unit's kept columns only, span after span)
+            if (r == hipSuccess && pko) r = hipMemcpyAsync(pko->peaks + sp.to / R * pkk, q.peaks + (size_t)k * (sp.cells / R) * pkk,
+                                                           sp.cells / R * pkk * sizeof(emspec_peak), hipMemcpyDeviceToHost, st);
         }
         return r;
     };
@@ -255,6 +267,7 @@ int emspec::host_batch(emspec_engine* e, const void* pcm, int S, int64_t L, int 
                 if (want_db) touch(out->db + sp.to, sp.cells * 4);
                 if (want_rgba) touch(out->rgba + 4 * sp.to, sp.cells * 4);
                 if (want_idx) touch(out->index + sp.to, sp.cells);
+                if (pko) touch(pko->peaks + sp.to / R * pkk, sp.cells / R * pkk * sizeof(emspec_peak));
             }
             std::lock_guard<std::mutex> lk(mu);
             touched[t] = f + 1;
@@ -287,7 +300,8 @@ int emspec::host_batch(emspec_engine* e, const void* pcm, int S, int64_t L, int 
         cv.notify_all();
     };
     std::thread drainer, touchers[kTouchers];
-    bool threaded = !pk && nu >= 2 && !(host_pinned(pcm) && host_pinned(out->db) && host_pinned(out->rgba) && host_pinned(out->index));
+    bool threaded = !pk && nu >= 2 && !(host_pinned(pcm) && (!out || (host_pinned(out->db) && host_pinned(out->rgba) && host_pinned(out->index))) &&
+                                        (!pko || host_pinned(pko->peaks)));
     try {
         if (threaded) drainer = std::thread(drain_all);
     } catch (const std::exception&) {   // no thread to be had: the caller's thread drains (its copies block it)
@@ -368,6 +382,12 @@ int emspec::host_batch(emspec_engine* e, const void* pcm, int S, int64_t L, int 
         if (f > 1 && (herr = launch_reduce_columns(q.db ? q.db + (size_t)it.skip * R : nullptr, q.idx ? q.idx + (size_t)it.skip * R : nullptr,
                                                    it.sc * V, it.cn, R, f, (size_t)it.cols * R, (size_t)((it.cn + f - 1) / f) * R, e->d_lut,
                                                    q.odb, q.oidx, q.orgba, e->stream)) != hipSuccess) break;
+        // 3c. peaks: the k loudest local maxima of every kept column (peaks.hip.inc), span after span into the set's peak lists
+        for (int k = 0; pko && k < spans_of(it, C, V) && herr == hipSuccess; ++k) {
+            const Span sp = span_of(it, C, R, V, k, 1);
+            herr = launch_peaks(q.db + sp.from, (int64_t)(sp.cells / R), R, pkk, pko->min_db, q.peaks + (size_t)k * (sp.cells / R) * pkk, e->stream);
+        }
+        if (herr != hipSuccess) break;
         // 4. packed: each stream's image, its header to the host behind it
         for (int i = 0; pk && i < it.sc * V && herr == hipSuccess; ++i) {
             uint8_t* w = q.wire + (size_t)i * g.wire;

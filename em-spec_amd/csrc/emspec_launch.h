@@ -164,6 +164,10 @@ hipError_t launch_wire_unpack(const uint8_t* wire, int64_t columns, int rows, ui
 hipError_t launch_reduce_columns(const float* db_in, const uint8_t* idx_in, int S, int64_t C, int R, int f, size_t in_stride,
                                  size_t out_stride, const uint8_t* lut, float* db_out, uint8_t* idx_out, uint8_t* rgba_out,
                                  hipStream_t st);
+// spectral peaks (peaks.hip.inc): per column of db [columns][R] the k loudest local maxima at or above min_db, loudest first, as
+// (position in row units, dB) pairs into peaks [columns][k] (8 bytes each; unused slots (-1, -inf)).  R % 4 == 0, 4 <= R <= 4096,
+// 1 <= k <= 32, min_db not NaN, db 16-byte and peaks 8-byte aligned; any number of columns (the grid strides, 64-bit offsets).
+hipError_t launch_peaks(const float* db, int64_t columns, int R, int k, float min_db, void* peaks, hipStream_t st);
 // PCM front end (pcm.hip.inc): `frames` interleaved frames of `sources` sources (source i at src + i * src_stride_bytes, device
 // memory or page-locked host memory, any byte offset that is a multiple of the sample size) -> float32 streams, stream
 // i * views + v at out + (i * views + v) * out_stride.  sample_type: kPcmS16 .. kPcmF32 (the values of include/emspec.h's

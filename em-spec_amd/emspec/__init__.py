@@ -44,6 +44,7 @@ SYMBOLS = [
     "emspec_multires_columns", "emspec_multires_shift", "emspec_batch_multires", "emspec_batch_multires_device",
     "emspec_pcm_frame_bytes", "emspec_pcm_decode_device", "emspec_batch_pcm", "emspec_batch_pcm_packed",
     "emspec_push_samples_pcm", "emspec_push_samples_pcm_multires",
+    "emspec_peaks_device", "emspec_peaks_host", "emspec_batch_peaks", "emspec_batch_peaks_device", "emspec_position_hz",
     "emspec_set_time_reduce", "emspec_time_reduce", "emspec_reduced_columns",
     "emspec_columns_multires", "emspec_push_columns_multires", "emspec_push_samples_multires",
 ]
@@ -52,6 +53,8 @@ SYMBOLS = [
 OPTIONAL_SYMBOLS = SYMBOLS[-3:]
 # the time reduction's: likewise (tools/overview_rate.py times the parent commit's library at factor 1)
 REDUCE_SYMBOLS = SYMBOLS[-6:-3]
+# the spectral peaks': likewise (tools/peaks_rate.py may time a library built before them next to this build)
+PEAKS_SYMBOLS = SYMBOLS[-11:-6]
 
 
 class Config(C.Structure):
@@ -154,6 +157,23 @@ def wire_unpack_host(image, columns, rows, out=None, diag=False):
     rc = lib.emspec_wire_unpack_host(_np_ptr(image), C.c_int64(image.size), C.c_int64(columns), C.c_int32(rows), _np_ptr(out))
     if rc != 0:
         raise EmspecError(rc, "emspec_wire_unpack_host: the image does not match (columns, rows) or is damaged")
+    return out
+
+
+def peaks_host(db, k, min_db, out=None, diag=False):
+    """The k loudest spectral peaks at or above min_db of every column of db [..., rows] float32 on the host's own cores
+    (emspec_peaks_host: plain C++, no device, no engine; the definition: include/emspec.h) ->
+    float32 [..., k, 2] of (position in row units, dB), loudest first; unused slots (-1, -inf)."""
+    db = np.ascontiguousarray(db, np.float32)
+    rows = db.shape[-1] if db.ndim else 0
+    columns = db.size // rows if rows else 0
+    if out is None:
+        out = np.empty(db.shape[:-1] + (int(k), 2), np.float32)
+    assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == columns * int(k) * 2
+    lib = load(diag=diag)
+    rc = lib.emspec_peaks_host(_np_ptr(db), columns, rows, int(k), float(min_db), _np_ptr(out))
+    if rc != 0:
+        raise EmspecError(rc, lib.emspec_last_error(None).decode())
     return out
 
 
@@ -284,6 +304,14 @@ def load(diag=False):
         lib.emspec_time_reduce.restype = C.c_int32
         lib.emspec_reduced_columns.restype = C.c_int64
         lib.emspec_reduced_columns.argtypes = [C.c_int64, C.c_int32]
+    if all(hasattr(lib, sym) for sym in PEAKS_SYMBOLS):
+        lib.emspec_peaks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
+        lib.emspec_peaks_host.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
+        lib.emspec_batch_peaks.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_float, C.c_void_p]
+        lib.emspec_batch_peaks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                                  C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
+        lib.emspec_position_hz.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
     _libs[diag] = lib
     return lib
 
@@ -610,6 +638,58 @@ class Engine:
             assert t is None or (t.is_cuda and t.is_contiguous())
         self._chk(self._lib.emspec_batch_device(self._h, ptr(pcm_t), S, L, n, hop, int(bool(reassign)), ptr(db),
                                                 ptr(rgba), ptr(index), C.c_void_p(st.cuda_stream)))
+
+    # -- spectral peaks: (position in row units, dB) pairs, float32 [..., k, 2] -----------------------
+    def peaks_device(self, db_t, k, min_db, out=None, stream=None):
+        """emspec_peaks_device: db_t a contiguous float32 CUDA tensor [..., rows] (any rows % 4 == 0 in 4 .. 4096) ->
+        CUDA tensor [..., k, 2], the k loudest peaks at or above min_db of every column.  Enqueues; does not synchronise."""
+        import torch
+        assert db_t.is_cuda and db_t.dtype == torch.float32 and db_t.is_contiguous() and db_t.dim() >= 1
+        rows = db_t.shape[-1]
+        columns = db_t.numel() // rows if rows else 0
+        if out is None:
+            out = torch.empty(tuple(db_t.shape[:-1]) + (int(k), 2), dtype=torch.float32, device=db_t.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == columns * int(k) * 2
+        st = stream if stream is not None else torch.cuda.current_stream(db_t.device)
+        self._chk(self._lib.emspec_peaks_device(self._h, C.c_void_p(db_t.data_ptr()), columns, rows, int(k), float(min_db),
+                                                C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream)))
+        return out
+
+    def batch_peaks_device(self, pcm_t, n, hop, reassign=True, k=8, min_db=-60.0, out=None, stream=None):
+        """emspec_batch_peaks_device: pcm_t a contiguous float32 CUDA tensor [S, L] -> CUDA tensor [S, columns, k, 2]: the
+        peaks of the dB batch_device would deliver.  Enqueues; does not synchronise."""
+        import torch
+        assert pcm_t.is_cuda and pcm_t.dtype == torch.float32 and pcm_t.is_contiguous() and pcm_t.dim() == 2
+        S, L = pcm_t.shape
+        Cn = num_columns(L, n, hop)
+        if out is None:
+            out = torch.empty((S, Cn, int(k), 2), dtype=torch.float32, device=pcm_t.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == S * Cn * int(k) * 2
+        st = stream if stream is not None else torch.cuda.current_stream(pcm_t.device)
+        self._chk(self._lib.emspec_batch_peaks_device(self._h, C.c_void_p(pcm_t.data_ptr()), S, L, n, hop, int(bool(reassign)),
+                                                      int(k), float(min_db), C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream)))
+        return out
+
+    def batch_peaks(self, pcm, n, hop, reassign=True, k=8, min_db=-60.0, out=None):
+        """emspec_batch_peaks: host samples [S, L] in, float32 [S, columns, k, 2] out (pageable, or a PinnedArray's array):
+        the pipeline of batch(), but only the peak lists cross PCIe on the way out."""
+        pcm = np.ascontiguousarray(pcm, np.float32)
+        if pcm.ndim == 1:
+            pcm = pcm[None]
+        S, L = pcm.shape
+        Cn = num_columns(L, n, hop)
+        if out is None:
+            out = np.empty((S, Cn, int(k), 2), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == S * Cn * int(k) * 2
+        self._chk(self._lib.emspec_batch_peaks(self._h, _np_ptr(pcm), S, L, n, hop, int(bool(reassign)), int(k), float(min_db),
+                                               _np_ptr(out)))
+        return out
+
+    def position_hz(self, pos):
+        """emspec_position_hz: a peak's position in row units -> Hz on the engine's row axis (log-interpolated inside the row)."""
+        hz = C.c_double(0.0)
+        self._chk(self._lib.emspec_position_hz(self._h, float(pos), C.byref(hz)))
+        return hz.value
 
     # -- multi-resolution batch (DESIGN.md §3.8): n_low below split_row, n_high from it up, one column grid --------
     def split_row_for_hz(self, hz):

@@ -1102,6 +1102,73 @@ static napi_value GetRowEdges(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* Spectral peaks (include/emspec.h).
+ * batchPeaks(handle, pcm:Float32Array(S*L), S, L, fftSize, hop, reassign, k, minDb, out:Float32Array(S*C*k*2)) -> columns per
+ *   stream: emspec_batch_peaks - only the peak lists cross PCIe on the way out
+ * peaksOf(db:Float32Array(columns*rows), columns, rows, k, minDb, out:Float32Array(columns*k*2)): emspec_peaks_host (no device,
+ *   no engine)
+ * positionHz(handle, pos) -> Hz: emspec_position_hz */
+static napi_value BatchPeaks(napi_env env, napi_callback_info info) {
+    size_t argc = 10; napi_value argv[10];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 10) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "batchPeaks(handle, pcm, S, L, fftSize, hop, reassign, k, minDb, out)"); return NULL; }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    void *pcm = NULL, *out = NULL; size_t plen = 0, olen = 0;
+    if (!get_typed(env, argv[1], napi_float32_array, &pcm, &plen, 0)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "pcm must be a Float32Array"); return NULL; }
+    int32_t S = 0, n = 0, hop = 0, k = 0; int64_t L = 0; bool reassign = true; double min_db = 0.0;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[2], &S));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[3], &L));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[4], &n));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[5], &hop));
+    NAPI_OK_OR_RETURN(env, napi_get_value_bool(env, argv[6], &reassign));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[7], &k));
+    NAPI_OK_OR_RETURN(env, napi_get_value_double(env, argv[8], &min_db));
+    if (!get_typed(env, argv[9], napi_float32_array, &out, &olen, 0)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "out must be a Float32Array"); return NULL; }
+    if (S < 1 || L < 1 || (size_t)S * (size_t)L != plen) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "pcm.length must equal S*L"); return NULL; }
+    const int64_t C = emspec_num_columns(L, n, hop);
+    /* (C <= 0 or k outside 1..32: the library rejects the call with its message before it touches the output) */
+    if (C > 0 && k >= 1 && k <= 32 && olen != (size_t)S * (size_t)C * (size_t)k * 2) {
+        napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "out must hold exactly S*columns*k*2 floats");
+        return NULL;
+    }
+    int rc = emspec_batch_peaks(h->e, (const float*)pcm, S, L, n, hop, reassign ? 1 : 0, k, (float)min_db, (emspec_peak*)out);
+    if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
+    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int64(env, C, &r));
+    return r;
+}
+static napi_value PeaksOf(napi_env env, napi_callback_info info) {
+    size_t argc = 6; napi_value argv[6];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 6) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "peaksOf(db, columns, rows, k, minDb, out)"); return NULL; }
+    void *db = NULL, *out = NULL; size_t dlen = 0, olen = 0;
+    if (!get_typed(env, argv[0], napi_float32_array, &db, &dlen, 0)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "db must be a Float32Array"); return NULL; }
+    int64_t columns = 0; int32_t rows = 0, k = 0; double min_db = 0.0;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[1], &columns));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[2], &rows));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[3], &k));
+    NAPI_OK_OR_RETURN(env, napi_get_value_double(env, argv[4], &min_db));
+    if (!get_typed(env, argv[5], napi_float32_array, &out, &olen, 0)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "out must be a Float32Array"); return NULL; }
+    if (columns >= 0 && rows >= 4 && k >= 1 && k <= 32 &&
+        (dlen != (size_t)columns * (size_t)rows || olen != (size_t)columns * (size_t)k * 2)) {
+        napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "db must hold columns*rows floats and out columns*k*2");
+        return NULL;
+    }
+    int rc = emspec_peaks_host((const float*)db, columns, rows, k, (float)min_db, (emspec_peak*)out);
+    if (rc != EMSPEC_OK) return throw_status(env, NULL, rc);
+    return NULL;
+}
+static napi_value PositionHz(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    double pos = 0.0, hz = 0.0;
+    if (argc < 2 || napi_get_value_double(env, argv[1], &pos) != napi_ok) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "positionHz(handle, pos)"); return NULL; }
+    int rc = emspec_position_hz(h->e, (float)pos, &hz);
+    if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
+    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_double(env, hz, &r));
+    return r;
+}
+
 /* allocPinned(byteLength) -> ArrayBuffer backed by page-locked host memory (emspec_host_alloc);
  * typed arrays over it make batch()/column() copies run at full PCIe speed.  Freed by the GC. */
 static void finalize_pinned(napi_env env, void* data, void* hint) { (void)env; (void)hint; emspec_host_free(data); }
@@ -1267,6 +1334,9 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"setTimeReduce", NULL, SetTimeReduce, NULL, NULL, NULL, napi_default, NULL},
         {"timeReduce", NULL, TimeReduce, NULL, NULL, NULL, napi_default, NULL},
         {"reducedColumns", NULL, ReducedColumns, NULL, NULL, NULL, napi_default, NULL},
+        {"batchPeaks", NULL, BatchPeaks, NULL, NULL, NULL, napi_default, NULL},
+        {"peaksOf", NULL, PeaksOf, NULL, NULL, NULL, napi_default, NULL},
+        {"positionHz", NULL, PositionHz, NULL, NULL, NULL, napi_default, NULL},
         {"setRowEdges", NULL, SetRowEdges, NULL, NULL, NULL, napi_default, NULL},
         {"getRowEdges", NULL, GetRowEdges, NULL, NULL, NULL, napi_default, NULL},
         {"allocPinned", NULL, AllocPinned, NULL, NULL, NULL, napi_default, NULL},

@@ -225,6 +225,24 @@ class Engine {
   }
 
   /**
+   * Spectral peaks (emspec_batch_peaks; include/emspec.h): pcm = Float32Array(S*L), S streams -> Float32Array laid out
+   * [S][C][k][2]: per column the k (1..32, default 8) loudest local maxima at or above minDb (default -60), loudest first, each
+   * as (position in row units, dB); unused slots are (-1, -Infinity).  Computed on the device from the dB columns computeColumns
+   * would return; only the lists cross PCIe on the way out (64 bytes per column at k = 8 instead of 4 * rows).  positionToHz maps
+   * a position to Hz, noteOf the Hz to a note.  Throws EMSPEC_ERR_STATE while timeReduce > 1.
+   */
+  computePeaks(pcm, streams, fftSize, hop, reassign, opts = {}) {
+    const k = opts.k === undefined ? 8 : opts.k | 0, minDb = opts.minDb === undefined ? -60 : +opts.minDb;
+    const L = Math.floor(pcm.length / streams);
+    const C = Math.max(0, native.numColumns(L, fftSize, hop));
+    const out = new Float32Array(streams * C * Math.min(32, Math.max(1, k)) * 2);
+    native.batchPeaks(this._h, pcm, streams, L, fftSize, hop, !!reassign, k, minDb, out);
+    return out;
+  }
+  /** A peak's position in row units -> Hz on this engine's row axis (emspec_position_hz): log-interpolated inside the row. */
+  positionToHz(pos) { return native.positionHz(this._h, pos); }
+
+  /**
    * Throughput entry with the palette-index columns kept compressed across PCIe (emspec_batch_packed): one lossless wire
    * image per stream, ~186 B instead of 1,024 B per column on typical audio.  wire: Uint8Array (allocPinned for full
    * speed; S * wireBound(C, rows) always suffices), offsets: Float64Array(S + 1).  Stream s is
@@ -406,6 +424,20 @@ function pcmFormat({ type, channels, views = ['mono'] }) {
   return f;
 }
 
+function peaksOf(db, columns, rows, k = 8, minDb = -60) {
+  const out = new Float32Array(Math.max(0, columns) * Math.min(32, Math.max(1, k | 0)) * 2);
+  native.peaksOf(db, columns, rows, k | 0, +minDb, out);
+  return out;
+}
+
+const NOTE_NAMES = ['C', 'C#', 'D', 'D#', 'E', 'F', 'F#', 'G', 'G#', 'A', 'A#', 'B'];
+function noteOf(hz) {
+  const semis = 12 * Math.log2(hz / 440);
+  const n = Math.floor(semis + 0.5);
+  const midi = 69 + n;
+  return { name: NOTE_NAMES[((midi % 12) + 12) % 12], octave: Math.floor(midi / 12) - 1, cents: 100 * (semis - n) };
+}
+
 module.exports = {
   pcmFormat,
   Engine,
@@ -425,6 +457,11 @@ module.exports = {
   wireBound: native.wireBound,
   /** Expand one wire image (Uint8Array) into out: Uint8Array(columns * rows) on the host's own cores - no device, no engine. */
   unpackWire: native.wireUnpack,
+  /** The host twin of computePeaks (emspec_peaks_host; no device, no engine): db = Float32Array(columns * rows), any dB columns
+   *  - a live call's, computeColumnsMultires's - -> Float32Array [columns][k][2]. */
+  peaksOf,
+  /** hz -> {name, octave, cents}: 12-tone equal temperament around A4 = 440 Hz, the nearest semitone, cents in [-50, 50). */
+  noteOf,
   latencyColumns: native.latencyColumns,
   /** Columns of a multi-resolution batch (emspec_multires_columns): multiresColumns(L, lowFftSize, fftSize, hop), -1 for a
    *  shape it does not accept. */

@@ -656,6 +656,66 @@ int emspec_push_samples_pcm_multires(emspec_engine* e, const void* block, const 
                                      int32_t split_row, int32_t reassign, float* out_db, uint8_t* out_rgba, int32_t rows,
                                      int64_t max_columns, int64_t* out_counts, int64_t* out_first_columns);
 
+/*
+ * ---- Spectral peaks: the k loudest local maxima of every finished column, computed where the dB
+ * columns already are.  Serves: the note and frequency read-out the reference shows on hover (README.md:39), a tuner line, a
+ * note overlay, melody or partial tracks - a peak list of k = 8 is 64 bytes per column where the dB column is 4 KB;
+ * [BUILD-DEFINED].
+ *
+ * DEFINITION.  The peaks of a column are a function of its dB values x[0 .. R) and of k (1 .. 32) and min_db (not NaN).  All
+ * arithmetic is binary32, one rounding per operation, no fused multiply-add; the division is the IEEE one.
+ *   1. Candidates.  L = x[r-1], or -inf at r = 0;  Rn = x[r+1], or -inf at r = R-1.  Row r is a peak iff
+ *          x[r] >= min_db && x[r] > L && x[r] >= Rn
+ *      by plain float comparisons: -0.0 equals +0.0; a NaN is never a peak and never beats a neighbour; a plateau reports its
+ *      first row.
+ *   2. Value.  db = x[r], the cell's own bits; the height is not interpolated.
+ *   3. Position, in row units; row r spans [r, r+1) of the engine's edge table (emspec_get_row_edges_hz).  At r = 0 and
+ *      r = R-1, pos = (float)r + 0.5f.  Elsewhere with a = L, b = x[r], c = Rn:
+ *          t = a - c;   u = (a - b) + (c - b);   d = (0.5f * t) / u;
+ *          if (d > 0.5f) d = 0.5f;   if (d < -0.5f) d = -0.5f;   if (d != d) d = 0.0f;
+ *          pos = ((float)r + 0.5f) + d;
+ *      - the vertex of the parabola through the three dB values, negative towards the louder left neighbour.
+ *   4. Selection.  The k candidates that come first by db descending (float comparison), ties by ascending row, in that order
+ *      into peaks[column][0 .. k); the slots that remain hold pos = -1.0f, db = -INFINITY.
+ * What the position resolves: with reassignment on, a steady tone falls into ONE row and its neighbours sit at the -200 dB
+ * floor, so d is about 0 and the resolution is the row width - 12 cents at the default 1,024 rows, 3 cents at 4,096.  The
+ * parabola matters with reassign = 0 and for modulated partials.
+ */
+typedef struct emspec_peak { float pos; float db; } emspec_peak;   /* 8 bytes */
+
+/*
+ * The peaks of any [columns][rows] float32 dB array on the engine's device - the output of emspec_batch_device or of
+ * emspec_batch_multires_device, streams x columns flattened (a column's peaks depend on that column alone) - into
+ * peaks_dev[columns][k].  rows % 4 == 0 and 4 <= rows <= 4096 (not necessarily the engine's); columns >= 0, 0 is a no-op;
+ * db_dev 16-byte and peaks_dev 8-byte aligned; no limit on columns * rows but memory.  One pass over the array.  Enqueued on
+ * hip_stream (NULL = the default stream); does not synchronise.
+ */
+int emspec_peaks_device(emspec_engine* e, const float* db_dev, int64_t columns, int32_t rows, int32_t k, float min_db,
+                        emspec_peak* peaks_dev, void* hip_stream);
+/* The same definition in plain C++ on host arrays: no engine, no device (the twin emspec_wire_unpack_host is for the wire
+ * image).  Serves the live calls' host columns and emspec_batch_multires.  The message of a refusal: emspec_last_error(NULL). */
+int emspec_peaks_host(const float* db, int64_t columns, int32_t rows, int32_t k, float min_db, emspec_peak* peaks_out);
+/*
+ * peaks[S][C][k], C = emspec_num_columns(L, n, hop): the peaks of exactly the dB emspec_batch_device / emspec_batch would
+ * deliver, display post-process included - without that dB leaving the device.  The device entry keeps the dB of a chunk of
+ * streams in an engine workspace bounded like the records path's; the host entry runs the pipeline of emspec_batch (pinned or
+ * pageable buffers, units of whole streams or runs of columns of a long stream) and copies out the peak lists only.
+ * The engine's rows must satisfy the rule of emspec_peaks_device.  EMSPEC_ERR_STATE while a time reduction is set
+ * (emspec_set_time_reduce; a host reduces 64-byte lists itself) - emspec_peaks_device / _host are not affected.
+ */
+int emspec_batch_peaks_device(emspec_engine* e, const float* pcm_dev, int32_t S, int64_t L, int32_t n, int32_t hop,
+                              int32_t reassign, int32_t k, float min_db, emspec_peak* peaks_dev, void* hip_stream);
+int emspec_batch_peaks(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32_t n, int32_t hop, int32_t reassign,
+                       int32_t k, float min_db, emspec_peak* peaks_out);
+/*
+ * A position in row units -> Hz on the engine's row axis: with i = floor(pos) clamped to [0, rows-1],
+ *     hz = edge[i] * (edge[i+1] / edge[i]) ^ (pos - i)
+ * in binary64 from the float table emspec_get_row_edges_hz returns.  pos outside [0, rows] (or NaN): EMSPEC_ERR_INVALID_ARG.
+ */
+int emspec_position_hz(emspec_engine* e, float pos, double* hz);
+/* Every refusal above is EMSPEC_ERR_INVALID_ARG with a message naming the rule - k outside 1 .. 32, a NaN min_db, rows breaking
+ * the rule, null or misaligned pointers - and leaves the engine usable. */
+
 #ifdef __cplusplus
 }
 #endif
