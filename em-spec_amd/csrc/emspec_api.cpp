@@ -568,6 +568,13 @@ int emspec_get_tables(emspec_engine* e, int32_t n, float* edges, float* tw) {
 
 }  // extern "C"
 
+bool emspec::host_pinned(const void* p) {
+    if (!p) return true;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return at.type == hipMemoryTypeHost;
+}
+
 // Per-bin record workspaces (the shapes without a fused kernel): streams are processed in chunks so that the workspace
 // stays bounded.  The budget follows the device: a quarter of what is free (counting what this engine already holds),
 // at least 256 MiB, at most `cap` - a chunk only has to cover enough streams to fill the CUs, so a few GiB cost nothing
@@ -623,12 +630,10 @@ static int run_columns(emspec_engine* e, const PlanDev& pd, const DbMap& m, cons
     return EMSPEC_OK;
 }
 
-// The low-row scratch of the no-parking EXACT kernel: grown on demand; a launch on another HIP stream than the previous one
-// waits for it (one scratch per engine: two launches must not run side by side on it)
-static int exact_lr_prepare(emspec_engine* e, int n, const ExactPlanDev& pd, int rl, int S, int64_t C, hipStream_t st) {
-    if (rl <= 0) return EMSPEC_OK;
+// The low-row scratch of the EXACT kernels, `need` bytes: grown on demand; a launch on another HIP stream than the previous
+// one waits for it (one scratch per engine: two launches must not run side by side on it)
+static int xlow_prepare(emspec_engine* e, size_t need, hipStream_t st) {
     int rc;
-    const size_t need = exact_fused_lr_scratch_bytes(n, pd, rl, S, C);
     if (need > e->xlow_bytes) {
         if (e->xlow_used) HIPCHK(e, hipEventSynchronize(e->xlow_event));      // the old buffer may still be in use
         if ((rc = grow(e, (void**)&e->d_xlow, &e->xlow_bytes, need))) return rc;
@@ -637,6 +642,10 @@ static int exact_lr_prepare(emspec_engine* e, int n, const ExactPlanDev& pd, int
     if (e->xlow_used) HIPCHK(e, hipStreamWaitEvent(st, e->xlow_event, 0));
     e->xlow_used = true;
     return EMSPEC_OK;
+}
+// (the no-parking kernel's: exact_fused_lr.hip.inc)
+static int exact_lr_prepare(emspec_engine* e, int n, const ExactPlanDev& pd, int rl, int S, int64_t C, hipStream_t st) {
+    return rl <= 0 ? EMSPEC_OK : xlow_prepare(e, exact_fused_lr_scratch_bytes(n, pd, rl, S, C), st);
 }
 
 // EXACT mode: per-bin (q, key) records (exact_frames_kernel) -> u64 LDS tiles (exact_tile_scatter_kernel), in chunks of
@@ -671,13 +680,7 @@ static int run_columns_exact(emspec_engine* e, const Plan& p, const float* pcm, 
     const size_t low_need = std::max(exact_scatter_scratch_bytes(n, pd, chunk, C, ebin_host),
                                      S % chunk ? exact_scatter_scratch_bytes(n, pd, S % chunk, C, ebin_host) : (size_t)0);
     if (low_need) {
-        if (low_need > e->xlow_bytes) {
-            if (e->xlow_used) HIPCHK(e, hipEventSynchronize(e->xlow_event));
-            if ((rc = grow(e, (void**)&e->d_xlow, &e->xlow_bytes, low_need))) return rc;
-        }
-        if (!e->xlow_event) HIPCHK(e, hipEventCreateWithFlags(&e->xlow_event, hipEventDisableTiming));
-        if (e->xlow_used) HIPCHK(e, hipStreamWaitEvent(st, e->xlow_event, 0));
-        e->xlow_used = true;
+        if ((rc = xlow_prepare(e, low_need, st))) return rc;
         HIPCHK(e, hipMemsetAsync(e->d_xlow, 0, low_need, st));
     }
     for (int s0 = 0; s0 < S; s0 += chunk) {
@@ -711,18 +714,15 @@ int emspec::reduce_streams(emspec_engine* e, int32_t S, int64_t C, float* db, ui
     const int R = e->cfg.rows, f = e->time_reduce;
     const size_t cells = (size_t)C * R, rcells = (size_t)reduced_columns(C, f) * R;
     const size_t db_s = db ? cells * 4 : 0, idx_s = (index || rgba) ? cells : 0;   // (cells is a multiple of 4: both stay 16-byte aligned ...
-    int chunk = 1, rc;
-    if ((rc = grow_chunked(e, (void**)&e->d_full, &e->full_bytes, db_s + idx_s, 256, (size_t)4 << 30, S, &chunk))) return rc;
-    float* wdb = db ? reinterpret_cast<float*>(e->d_full) : nullptr;
-    uint8_t* widx = idx_s ? reinterpret_cast<uint8_t*>(e->d_full) + ((db_s * chunk + 255) & ~(size_t)255) : nullptr;   // ... and this 256)
-    for (int s0 = 0; s0 < S; s0 += chunk) {
-        const int sc = std::min(chunk, S - s0);
-        if ((rc = full(s0, sc, wdb, widx))) return rc;
+    return for_stream_chunks(e, (void**)&e->d_full, &e->full_bytes, db_s + idx_s, 256, (size_t)4 << 30, S, [&](int s0, int sc, int chunk) -> int {
+        float* wdb = db ? reinterpret_cast<float*>(e->d_full) : nullptr;
+        uint8_t* widx = idx_s ? reinterpret_cast<uint8_t*>(e->d_full) + ((db_s * chunk + 255) & ~(size_t)255) : nullptr;   // ... and this 256)
+        if (int rc = full(s0, sc, wdb, widx)) return rc;
         const size_t o = (size_t)s0 * rcells;
         HIPCHK(e, launch_reduce_columns(wdb, widx, sc, C, R, f, cells, rcells, e->d_lut, db ? db + o : nullptr,
                                         index ? index + o : nullptr, rgba ? rgba + 4 * o : nullptr, st));
-    }
-    return EMSPEC_OK;
+        return EMSPEC_OK;
+    });
 }
 
 int emspec::batch_device_full(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32_t n, int32_t hop, int32_t reassign,
@@ -937,7 +937,12 @@ int emspec_batch(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32
     // With fewer than sixteen streams the units are runs of a stream's columns (pipe_items) - but the display post-process walks
     // a stream in time order: whole streams there
     const bool post = e->smoothing > 0.0f || e->agc > 0.0f;
-    return host_batch(e, pcm, S, L, n, hop, post ? -1 : latency(n, hop, reassign), 1, out, nullptr, batch_run(e, n, hop, reassign));
+    HostJob job;
+    job.src = pcm, job.S = S, job.L = L, job.n = n, job.hop = hop;
+    job.whole_streams = post, job.halo_D = latency(n, hop, reassign);
+    job.out = out;
+    job.run = batch_run(e, n, hop, reassign);
+    return host_batch(e, job);
 }
 
 int emspec_batch_packed(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32_t n, int32_t hop, int32_t reassign,
@@ -952,7 +957,12 @@ int emspec_batch_packed(emspec_engine* e, const float* pcm, int32_t S, int64_t L
     HIPCHK(e, hipSetDevice(e->device));
     const PackedOut pk{wire, wire_capacity, offsets};
     // (an image is one stream's whole run of columns: whole streams)
-    return host_batch(e, pcm, S, L, n, hop, -1, 1, nullptr, &pk, batch_run(e, n, hop, reassign));
+    HostJob job;
+    job.src = pcm, job.S = S, job.L = L, job.n = n, job.hop = hop;
+    job.whole_streams = true;
+    job.pk = &pk;
+    job.run = batch_run(e, n, hop, reassign);
+    return host_batch(e, job);
 }
 
 int emspec_wire_unpack_host(const uint8_t* wire, int64_t wire_bytes, int64_t columns, int32_t rows, uint8_t* index_out) {

@@ -76,6 +76,15 @@ int run_plan_columns(emspec_engine* e, const Plan& p, const float* pcm, int32_t 
                      int64_t C, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st);
 // device workspace *ptr for `per_stream` bytes per stream (+ extra): streams per chunk by the records path's budget
 int grow_chunked(emspec_engine* e, void** ptr, size_t* have, size_t per_stream, size_t extra, size_t cap, int S, int* chunk_out);
+// that workspace, then rc = body(s0, sc, chunk) for chunk after chunk of the S streams: sc <= chunk streams from s0 on
+template <class Body>
+int for_stream_chunks(emspec_engine* e, void** ptr, size_t* have, size_t per_stream, size_t extra, size_t cap, int S, Body&& body) {
+    int chunk = 1, rc;
+    if ((rc = grow_chunked(e, ptr, have, per_stream, extra, cap, S, &chunk))) return rc;
+    for (int s0 = 0; s0 < S; s0 += chunk)
+        if ((rc = body(s0, S - s0 < chunk ? S - s0 : chunk, chunk))) return rc;
+    return EMSPEC_OK;
+}
 // emspec_api.cpp: emspec_batch_device at FULL rate whatever the engine's time reduction (the unit function of the host
 // pipeline, which reduces a unit's columns itself), and the device entries' reduced form: `full` computes the full-rate dB and /
 // or index columns [sc][C][rows] of streams [s0, s0 + sc) into the engine workspace, chunk after chunk of streams (grow_chunked),
@@ -90,21 +99,34 @@ ExactPlanDev exact_plan_dev(const emspec_engine* e, const Plan& p, int hop, int 
 ExactDbMap exact_db_map(const emspec_engine* e, int n, const ExactPlanDev& pd);
 DbMap db_map(const emspec_engine* e, int n);
 bool host_pinned(const void* p);   // p is null or page-locked host memory the device can address
-// emspec_host.cpp: the host-buffer path of emspec_batch, emspec_batch_packed and emspec_batch_multires.  S streams of L host
-// samples -> the columns of emspec_num_columns(L, n, hop) into host arrays (out), or one wire image per stream (pk), through
-// staging sets on the device; `run` computes one unit (sc streams of `samples` samples, staged) on the compute stream.  Units
-// are runs of a stream's columns with halo_D columns on either side, or whole streams when halo_D is -1; a unit of whole streams
-// holds at least min_streams of them (or all S).
+// emspec_host.cpp: the host-buffer path of emspec_batch, emspec_batch_packed, emspec_batch_multires, the PCM and the peaks
+// entries.  S streams of L host samples -> the columns of emspec_num_columns(L, n, hop) into host arrays (out), or one wire image
+// per stream (pk), or peak lists (pko), through staging sets on the device; `run` computes one unit (sc streams of `samples`
+// samples, staged) on the compute stream.
 struct PackedOut { uint8_t* wire; int64_t capacity; int64_t* offsets; };
 // emspec_batch_peaks: instead of columns, the k loudest peaks at or above min_db of every column, [S][columns][k] (f = 1 only)
 struct PeaksOut { emspec_peak* peaks; int k; float min_db; };
 using HostRun = std::function<int(const float* pcm, int sc, int64_t samples, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st)>;
-// `dec` (emspec_batch_pcm, emspec_batch_pcm_packed): pcm is raw interleaved frames, S SOURCES of L frames; the copy-in stage
-// moves those bytes, the decode kernel (pcm.hip.inc) fills the unit's float streams in front of `run`, which then sees
-// sc * dec->views streams, and the outputs are those of S * dec->views streams.  Null: pcm is float32 [S][L].
-int host_batch(emspec_engine* e, const void* pcm, int S, int64_t L, int n, int hop, int halo_D, int min_streams,
-               const emspec_out* out, const PackedOut* pk, const HostRun& run, const emspec_pcm_format* dec = nullptr,
-               const PeaksOut* pko = nullptr);
+struct HostJob {
+    const void* src = nullptr;   // float32 [S][L] - or, with `dec`, raw interleaved frames: S SOURCES of L frames
+    int S = 0;
+    int64_t L = 0;
+    int n = 0, hop = 0;
+    // the unit rule: whole streams, at least min_streams of them per unit (or all S) - or runs of a stream's columns with halo_D
+    // columns on either side when the batch has too few streams
+    bool whole_streams = false;
+    int halo_D = 0, min_streams = 1;
+    // what is delivered: exactly one of out / pk / pko
+    const emspec_out* out = nullptr;
+    const PackedOut* pk = nullptr;
+    const PeaksOut* pko = nullptr;
+    // (emspec_batch_pcm, emspec_batch_pcm_packed): the copy-in stage moves the raw bytes, the decode kernel (pcm.hip.inc) fills
+    // the unit's float streams in front of `run`, which then sees sc * dec->views streams, and the outputs are those of
+    // S * dec->views streams
+    const emspec_pcm_format* dec = nullptr;
+    HostRun run;
+};
+int host_batch(emspec_engine* e, const HostJob& job);
 // (with the engine's time reduction f > 1, `run` still computes FULL-rate columns - dB and / or index, never RGBA - into the
 // unit's staging set; host_batch launches the reduction behind it and delivers ceil(columns / f) columns per stream)
 // emspec_pcm.cpp: null, or what is wrong with the format (names the field); bytes per interleaved frame of a valid format

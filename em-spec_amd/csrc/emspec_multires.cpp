@@ -53,23 +53,21 @@ int multires_run(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32
     const bool post = e->smoothing > 0.0f || e->agc > 0.0f;
     const size_t col_cells = (size_t)C * R, lo_s = (size_t)C * split * 4, hi_s = (size_t)Ch * Rh * 4, raw_s = post ? col_cells * 4 : 0;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    int chunk = 1;
-    if ((rc = grow_chunked(e, (void**)&e->d_mres, &e->mres_bytes, lo_s + hi_s + raw_s, 1024, (size_t)4 << 30, S, &chunk))) return rc;
-    if (post) {
-        if ((rc = grow(e, (void**)&e->d_peak, &e->peak_bytes, (size_t)chunk * C * 8 + 16))) return rc;
-        if (!db && (rc = grow(e, (void**)&e->d_post, &e->post_bytes, (size_t)chunk * col_cells * 4))) return rc;
-    }
-    float* wlo = e->d_mres;
-    float* whi = (float*)((char*)wlo + al(lo_s * chunk));
-    float* wraw = (float*)((char*)whi + al(hi_s * chunk));
     // the dB -> index map: only lo / inv_range / gate are read, which every n shares (EXACT mode: its own rounding of lo)
     DbMap dm = db_map(e, n_low);
     if (e->exact()) {
         const ExactDbMap xm = exact_db_map(e, n_low, exact_plan_dev(e, *pl, hop, reassign));
         dm.lo = xm.lo; dm.inv_range = xm.inv_range; dm.gate = xm.gate;
     }
-    for (int s0 = 0; s0 < S; s0 += chunk) {
-        const int sc = std::min(chunk, S - s0);
+    return for_stream_chunks(e, (void**)&e->d_mres, &e->mres_bytes, lo_s + hi_s + raw_s, 1024, (size_t)4 << 30, S, [&](int s0, int sc, int chunk) -> int {
+        int rc;
+        if (post && s0 == 0) {   // the post-process workspaces of a chunk, in front of the first one
+            if ((rc = grow(e, (void**)&e->d_peak, &e->peak_bytes, (size_t)chunk * C * 8 + 16))) return rc;
+            if (!db && (rc = grow(e, (void**)&e->d_post, &e->post_bytes, (size_t)chunk * col_cells * 4))) return rc;
+        }
+        float* wlo = e->d_mres;
+        float* whi = (float*)((char*)wlo + al(lo_s * chunk));
+        float* wraw = (float*)((char*)whi + al(hi_s * chunk));
         const float* in = pcm + (size_t)s0 * L;
         if ((rc = run_plan_columns(e, *pl, in, sc, L, hop, reassign, C, wlo, nullptr, nullptr, st))) return rc;
         if ((rc = run_plan_columns(e, *ph, in, sc, L, hop, reassign, Ch, whi, nullptr, nullptr, st))) return rc;
@@ -77,14 +75,14 @@ int multires_run(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32
         if (!post) {
             HIPCHK(e, launch_multires_compose(wlo, whi, sc, C, R, split, shift, dm, e->d_lut, db ? db + o : nullptr,
                                               rgba ? rgba + 4 * o : nullptr, index ? index + o : nullptr, st));
-            continue;
+            return EMSPEC_OK;
         }
         HIPCHK(e, launch_multires_compose(wlo, whi, sc, C, R, split, shift, dm, e->d_lut, wraw, nullptr, nullptr, st));
         HIPCHK(e, launch_postprocess(wraw, db ? db + o : e->d_post, rgba ? rgba + 4 * o : nullptr, index ? index + o : nullptr, sc,
                                      C, R, e->smoothing, e->agc, e->cfg.db_top, db_map(e, n_low), e->d_lut, e->d_peak,
                                      e->d_peak + (size_t)sc * C, st));
-    }
-    return EMSPEC_OK;
+        return EMSPEC_OK;
+    });
 }
 
 }  // namespace
@@ -126,10 +124,14 @@ int emspec_batch_multires(emspec_engine* e, const float* pcm, int32_t S, int64_t
     if (rc) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     if (!out->db && !out->rgba && !out->index) return EMSPEC_OK;
-    const auto run = [=](const float* d_pcm, int sc, int64_t samples, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st) {
+    HostJob job;
+    job.src = pcm, job.S = S, job.L = L, job.n = n_low, job.hop = hop;
+    job.whole_streams = true, job.min_streams = 4;
+    job.out = out;
+    job.run = [=](const float* d_pcm, int sc, int64_t samples, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st) {
         return multires_run(e, d_pcm, sc, samples, n_low, n_high, hop, split_row, reassign, db, rgba, index, st);
     };
-    return host_batch(e, pcm, S, L, n_low, hop, -1, 4, out, nullptr, run);
+    return host_batch(e, job);
 }
 
 }  // extern "C"

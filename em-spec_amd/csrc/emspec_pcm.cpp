@@ -79,8 +79,12 @@ int emspec_batch_pcm(emspec_engine* e, const void* src, const emspec_pcm_format*
     HIPCHK(e, hipSetDevice(e->device));
     if (!out->db && !out->rgba && !out->index) return EMSPEC_OK;
     const bool post = e->smoothing > 0.0f || e->agc > 0.0f;   // (whole streams then, as in emspec_batch)
-    return host_batch(e, src, sources, frames, n, hop, post ? -1 : latency(n, hop, reassign), 1, out, nullptr,
-                      pcm_batch_run(e, n, hop, reassign), fmt);
+    HostJob job;
+    job.src = src, job.S = sources, job.L = frames, job.n = n, job.hop = hop, job.dec = fmt;
+    job.whole_streams = post, job.halo_D = latency(n, hop, reassign);
+    job.out = out;
+    job.run = pcm_batch_run(e, n, hop, reassign);
+    return host_batch(e, job);
 }
 
 int emspec_batch_pcm_packed(emspec_engine* e, const void* src, const emspec_pcm_format* fmt, int32_t sources, int64_t frames,
@@ -93,7 +97,12 @@ int emspec_batch_pcm_packed(emspec_engine* e, const void* src, const emspec_pcm_
     if (e->cfg.rows % 4) return fail(e, EMSPEC_ERR_INVALID_ARG, "the wire image needs rows % 4 == 0");
     HIPCHK(e, hipSetDevice(e->device));
     const PackedOut pk{wire, wire_capacity, offsets};
-    return host_batch(e, src, sources, frames, n, hop, -1, 1, nullptr, &pk, pcm_batch_run(e, n, hop, reassign), fmt);
+    HostJob job;
+    job.src = src, job.S = sources, job.L = frames, job.n = n, job.hop = hop, job.dec = fmt;
+    job.whole_streams = true;
+    job.pk = &pk;
+    job.run = pcm_batch_run(e, n, hop, reassign);
+    return host_batch(e, job);
 }
 
 }  // extern "C"

@@ -115,15 +115,12 @@ int emspec_batch_peaks_device(emspec_engine* e, const float* pcm_dev, int32_t S,
     const int64_t C = emspec_num_columns(L, n, hop);
     // the dB of a chunk of streams goes to the engine workspace the time reduction's device entries use (never both: see the
     // check above), sized by the records path's budget rule; the kernel reads it from there, in stream order behind the batch
-    int chunk = 1;
-    if ((rc = grow_chunked(e, (void**)&e->d_full, &e->full_bytes, (size_t)C * R * 4, 256, (size_t)4 << 30, S, &chunk))) return rc;
-    float* wdb = reinterpret_cast<float*>(e->d_full);
-    for (int s0 = 0; s0 < S; s0 += chunk) {
-        const int sc = std::min(chunk, S - s0);
-        if ((rc = batch_device_full(e, pcm_dev + (size_t)s0 * L, sc, L, n, hop, reassign, wdb, nullptr, nullptr, st))) return rc;
+    return for_stream_chunks(e, (void**)&e->d_full, &e->full_bytes, (size_t)C * R * 4, 256, (size_t)4 << 30, S, [&](int s0, int sc, int) -> int {
+        float* wdb = reinterpret_cast<float*>(e->d_full);
+        if (int rc = batch_device_full(e, pcm_dev + (size_t)s0 * L, sc, L, n, hop, reassign, wdb, nullptr, nullptr, st)) return rc;
         HIPCHK(e, launch_peaks(wdb, (int64_t)sc * C, R, k, min_db, peaks_dev + (size_t)s0 * C * k, st));
-    }
-    return EMSPEC_OK;
+        return EMSPEC_OK;
+    });
 }
 
 int emspec_batch_peaks(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32_t n, int32_t hop, int32_t reassign, int32_t k,
@@ -132,13 +129,16 @@ int emspec_batch_peaks(emspec_engine* e, const float* pcm, int32_t S, int64_t L,
     if (rc) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     const PeaksOut pko{peaks_out, k, min_db};
-    const HostRun run = [=](const float* p, int sc, int64_t samples, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st) {
-        return batch_device_full(e, p, sc, samples, n, hop, reassign, db, rgba, index, st);
-    };
+    HostJob job;
+    job.src = pcm, job.S = S, job.L = L, job.n = n, job.hop = hop;
     // units as emspec_batch cuts them: runs of a stream's columns when there are few streams, whole streams for the display
     // post-process, which walks a stream in time order
-    const bool post = e->smoothing > 0.0f || e->agc > 0.0f;
-    return host_batch(e, pcm, S, L, n, hop, post ? -1 : latency(n, hop, reassign), 1, nullptr, nullptr, run, nullptr, &pko);
+    job.whole_streams = e->smoothing > 0.0f || e->agc > 0.0f, job.halo_D = latency(n, hop, reassign);
+    job.pko = &pko;
+    job.run = [=](const float* p, int sc, int64_t samples, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st) {
+        return batch_device_full(e, p, sc, samples, n, hop, reassign, db, rgba, index, st);
+    };
+    return host_batch(e, job);
 }
 
 int emspec_position_hz(emspec_engine* e, float pos, double* hz) {
