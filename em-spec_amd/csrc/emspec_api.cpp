@@ -43,181 +43,34 @@ int grow(emspec_engine* e, void** ptr, size_t* have, size_t want) {
 
 namespace emspec {   // (internal linkage is not needed: the library exports only what emspec.map lists; emspec_live.cpp uses these)
 
-void default_lut(uint8_t* lut) {
-    // 5-stop gradient measured from the reference's settings screenshot
-    // (assets/settings.png): 0/25/50/75/100 %.
-    static const int stops[5][3] = {{0, 0, 0}, {80, 0, 80}, {200, 50, 50}, {255, 150, 0}, {255, 255, 200}};
-    for (int i = 0; i < 256; ++i) {
-        const int pos = 4 * i;
-        const int seg = pos >= 3 * 255 ? 3 : pos / 255;
-        const int w1 = pos - seg * 255, w0 = 255 - w1;
-        for (int c = 0; c < 3; ++c) lut[4 * i + c] = (uint8_t)((stops[seg][c] * w0 + stops[seg + 1][c] * w1 + 127) / 255);
-        lut[4 * i + 3] = 255;
-    }
-}
-
-// (oracle/emspec_exact.c:ex_cos_sin states the same operations)
-/* cos and sin of a in [0, pi/4] by their Taylor series in Horner form, plain binary64 operations in this order (no
- * libm call: glibc's sincos(), which gcc substitutes for a cos()/sin() pair, and its separate cos()/sin() differ in the
- * last bit for some arguments, so a table built from libm depends on the compiler).  Truncation < 3e-18; result
- * within about one ulp. */
-void cos_sin_octant(double a, double* c, double* s) {
-    const double z = a * a;
-    double ps = -1.0 / 121645100408832000.0;       /* -1/19! */
-    ps = ps * z + 1.0 / 355687428096000.0;         /* +1/17! */
-    ps = ps * z - 1.0 / 1307674368000.0;           /* -1/15! */
-    ps = ps * z + 1.0 / 6227020800.0;              /* +1/13! */
-    ps = ps * z - 1.0 / 39916800.0;                /* -1/11! */
-    ps = ps * z + 1.0 / 362880.0;                  /* +1/9! */
-    ps = ps * z - 1.0 / 5040.0;                    /* -1/7! */
-    ps = ps * z + 1.0 / 120.0;                     /* +1/5! */
-    ps = ps * z - 1.0 / 6.0;                       /* -1/3! */
-    *s = a + a * (ps * z);
-    double pc = 1.0 / 6402373705728000.0;          /* +1/18! */
-    pc = pc * z - 1.0 / 20922789888000.0;          /* -1/16! */
-    pc = pc * z + 1.0 / 87178291200.0;             /* +1/14! */
-    pc = pc * z - 1.0 / 479001600.0;               /* -1/12! */
-    pc = pc * z + 1.0 / 3628800.0;                 /* +1/10! */
-    pc = pc * z - 1.0 / 40320.0;                   /* -1/8! */
-    pc = pc * z + 1.0 / 720.0;                     /* +1/6! */
-    pc = pc * z - 1.0 / 24.0;                      /* -1/4! */
-    pc = pc * z + 0.5;                             /* +1/2! */
-    *c = 1.0 - pc * z;
-}
-
-// (oracle/emspec_oracle.c: eo_spec_pow states the same operations)
-/* ratio^x by a SPECIFIED evaluation: exp2(x * log2(ratio)) from plain IEEE binary64 operations in this
- * order - no libm, whose pow() is not correctly rounded and differs between C libraries, so a table built from it would
- * depend on the host.  log2 by the atanh series on the mantissa folded into [1/sqrt2, sqrt2]; 2^f, |f| <= 1/2,
- * by the Taylor series of e^(f ln 2) in Horner form (truncation < 4e-18); scaling by 2^i is exact.  Within ~3 ulp of the
- * real value; what matters is that every build produces the same bits. */
-static double spec_log2(double x) {
-    uint64_t u;
-    memcpy(&u, &x, 8);
-    int e = (int)((u >> 52) & 0x7ff) - 1023;
-    u = (u & 0x000fffffffffffffULL) | 0x3ff0000000000000ULL;
-    double m;
-    memcpy(&m, &u, 8);
-    if (m > 1.4142135623730951) { m = m * 0.5; e += 1; }
-    const double s = (m - 1.0) / (m + 1.0);
-    const double z = s * s;
-    double pz = 1.0 / 21.0;
-    pz = pz * z + 1.0 / 19.0;
-    pz = pz * z + 1.0 / 17.0;
-    pz = pz * z + 1.0 / 15.0;
-    pz = pz * z + 1.0 / 13.0;
-    pz = pz * z + 1.0 / 11.0;
-    pz = pz * z + 1.0 / 9.0;
-    pz = pz * z + 1.0 / 7.0;
-    pz = pz * z + 1.0 / 5.0;
-    pz = pz * z + 1.0 / 3.0;
-    pz = pz * z + 1.0;
-    return (double)e + (s * pz) * 2.8853900817779268; /* 2 / ln 2 */
-}
-static double spec_exp2(double x) {
-    const double i = (double)(long long)(x < 0.0 ? x - 0.5 : x + 0.5); /* nearest integer (halves away from zero) */
-    const double t = (x - i) * 0.6931471805599453;                    /* x - i is exact; |t| <= 0.3466 */
-    double p = 1.0 / 87178291200.0;      /* 1/14! */
-    p = p * t + 1.0 / 6227020800.0;      /* 1/13! */
-    p = p * t + 1.0 / 479001600.0;       /* 1/12! */
-    p = p * t + 1.0 / 39916800.0;        /* 1/11! */
-    p = p * t + 1.0 / 3628800.0;         /* 1/10! */
-    p = p * t + 1.0 / 362880.0;          /* 1/9! */
-    p = p * t + 1.0 / 40320.0;           /* 1/8! */
-    p = p * t + 1.0 / 5040.0;            /* 1/7! */
-    p = p * t + 1.0 / 720.0;             /* 1/6! */
-    p = p * t + 1.0 / 120.0;             /* 1/5! */
-    p = p * t + 1.0 / 24.0;              /* 1/4! */
-    p = p * t + 1.0 / 6.0;               /* 1/3! */
-    p = p * t + 0.5;                     /* 1/2! */
-    p = p * t + 1.0;
-    p = p * t + 1.0;
-    const uint64_t su = (uint64_t)(1023 + (long long)i) << 52;        /* 2^i, |i| < 1000 */
-    double sd;
-    memcpy(&sd, &su, 8);
-    return p * sd;
-}
-static double spec_pow(double ratio, double x) {
-    if (x == 1.0) return ratio; /* the axis ends exactly at fmax (as pow(ratio, 1) would) */
-    return spec_exp2(x * spec_log2(ratio));
-}
-
-int latency(int n, int hop, int reassign) { return reassign ? (n + 2 * hop - 1) / (2 * hop) : 0; }
-
 int check_shape(const emspec_engine* e, int n, int hop) {
     if (!supported_fft(n)) return fail(e, EMSPEC_ERR_INVALID_ARG, "fft size must be a power of two in [256,16384]");
     if (hop < 1 || hop > n) return fail(e, EMSPEC_ERR_INVALID_ARG, "hop must be in [1, fft size]");
     return EMSPEC_OK;
 }
 
-// DESIGN.md §3 "Tables": evaluated in double, rounded once to float.
+// The shape's tables (emspec_tables.h; DESIGN.md §3 "Tables"), built on the host and uploaded.
 int get_plan(emspec_engine* e, int n, Plan** out) {
     auto it = e->plans.find(n);
     if (it != e->plans.end()) { *out = &it->second; return EMSPEC_OK; }
     Plan p;
     p.n = n;
-    p.rows = e->cfg.rows;
-    p.h_tw.resize(n);
-    const double pi = 3.14159265358979323846;
-    for (int q = 0; q < n / 2; ++q) {
-        const double a = 2.0 * pi * (double)q / (double)n;
-        p.h_tw[2 * q] = (float)std::cos(a);
-        p.h_tw[2 * q + 1] = (float)(-std::sin(a));
-    }
-    // Second quarter by symmetry: tw[q + N/4] = -j tw[q] = (tw[q].im, -tw[q].re).  With a correctly rounded libm this is
-    // what cos/sin give anyway (checked for every N here); writing it down makes it a property of the table that the
-    // kernels may rely on (fused_n16384.hip.inc loads 8 pass-1 twiddles instead of 15).  oracle/emspec_oracle.c does the same.
-    for (int q = 0; q < n / 4; ++q) {
-        p.h_tw[2 * (q + n / 4)] = p.h_tw[2 * q + 1];
-        p.h_tw[2 * (q + n / 4) + 1] = -p.h_tw[2 * q];
-    }
-    p.h_tw[2 * (n / 4)] = 0.0f;       // quarter turn is exact: (0,-1)
-    p.h_tw[2 * (n / 4) + 1] = -1.0f;
-    const int R = e->cfg.rows;
-    p.h_ebin.resize(R + 1);
-    const double ratio = (double)e->cfg.fmax_hz / (double)e->cfg.fmin_hz;
-    for (int r = 0; r <= R; ++r)
-        p.h_ebin[r] = e->custom_edges_hz.empty()
-                          ? (float)((double)e->cfg.fmin_hz * spec_pow(ratio, (double)r / (double)R) * (double)n /
-                                    (double)e->cfg.sample_rate)
-                          : (float)((double)e->custom_edges_hz[r] * (double)n / (double)e->cfg.sample_rate);
-    for (int r = 0; r < R; ++r)
-        if (!(p.h_ebin[r] < p.h_ebin[r + 1])) return fail(e, EMSPEC_ERR_INVALID_ARG, "row edges are not strictly increasing in float32 (too many rows for this range)");
+    const int R = p.rows = e->cfg.rows;
+    p.h_tw = twiddles32(n);
+    p.h_ebin64 = edges_bin64(axis_of(e->cfg, e->custom_edges_hz), n);
+    p.h_ebin = edges_bin32(p.h_ebin64);
+    if (const char* why = edges_error(p.h_ebin)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
     HIPCHK(e, hipMalloc(&p.d_tw, sizeof(float) * n));
     HIPCHK(e, hipMalloc(&p.d_ebin, sizeof(float) * (R + 1)));
     HIPCHK(e, hipMemcpy(p.d_tw, p.h_tw.data(), sizeof(float) * n, hipMemcpyHostToDevice));
     HIPCHK(e, hipMemcpy(p.d_ebin, p.h_ebin.data(), sizeof(float) * (R + 1), hipMemcpyHostToDevice));
-    if (e->exact()) {
-        // the same tables in binary64 (oracle/emspec_exact.c: ex_twiddle, eo_edges64)
-        std::vector<double> tw((size_t)n), eb((size_t)R + 1);
-        for (int q = 0; q <= n / 8; ++q) {   // first octant by the specified series, second by cos(pi/2 - x) = sin x
-            double c, sn;
-            cos_sin_octant(2.0 * pi * (double)q / (double)n, &c, &sn);
-            tw[2 * q] = c;
-            tw[2 * q + 1] = -sn;
-            if (q > 0) {
-                tw[2 * (n / 4 - q)] = sn;
-                tw[2 * (n / 4 - q) + 1] = -c;
-            }
-        }
-        for (int q = 0; q < n / 4; ++q) {
-            tw[2 * (q + n / 4)] = tw[2 * q + 1];
-            tw[2 * (q + n / 4) + 1] = -tw[2 * q];
-        }
-        tw[2 * (n / 4)] = 0.0;
-        tw[2 * (n / 4) + 1] = -1.0;
-        for (int r = 0; r <= R; ++r)
-            eb[r] = e->custom_edges_hz.empty()
-                        ? (double)e->cfg.fmin_hz * spec_pow(ratio, (double)r / (double)R) * (double)n / (double)e->cfg.sample_rate
-                        : (double)e->custom_edges_hz[r] * (double)n / (double)e->cfg.sample_rate;
-        for (int r = 0; r < R; ++r)
-            if (!(eb[r] < eb[r + 1])) return fail(e, EMSPEC_ERR_INVALID_ARG, "row edges are not strictly increasing");
-        p.h_e0 = eb[0];
-        p.h_eR = eb[R];
+    if (e->exact()) {   // the same tables in binary64
+        if (const char* why = edges_error(p.h_ebin64)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
+        const std::vector<double> tw = twiddles64(n);
         HIPCHK(e, hipMalloc(&p.d_tw64, sizeof(double) * n));
         HIPCHK(e, hipMalloc(&p.d_ebin64, sizeof(double) * (R + 1)));
         HIPCHK(e, hipMemcpy(p.d_tw64, tw.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-        HIPCHK(e, hipMemcpy(p.d_ebin64, eb.data(), sizeof(double) * (R + 1), hipMemcpyHostToDevice));
+        HIPCHK(e, hipMemcpy(p.d_ebin64, p.h_ebin64.data(), sizeof(double) * (R + 1), hipMemcpyHostToDevice));
     }
     auto ins = e->plans.emplace(n, std::move(p));
     *out = &ins.first->second;
@@ -242,31 +95,33 @@ int get_band_plan(emspec_engine* e, int n, int row0, int rows, Plan** out) {
     p.d_tw = full->d_tw;
     p.d_tw64 = full->d_tw64;
     p.h_ebin.assign(full->h_ebin.begin() + row0, full->h_ebin.begin() + row0 + rows + 1);
+    p.h_ebin64.assign(full->h_ebin64.begin() + row0, full->h_ebin64.begin() + row0 + rows + 1);
     HIPCHK(e, hipMalloc(&p.d_ebin, sizeof(float) * (rows + 1)));
     HIPCHK(e, hipMemcpy(p.d_ebin, p.h_ebin.data(), sizeof(float) * (rows + 1), hipMemcpyHostToDevice));
     if (e->exact()) {
         HIPCHK(e, hipMalloc(&p.d_ebin64, sizeof(double) * (rows + 1)));
-        HIPCHK(e, hipMemcpy(p.d_ebin64, full->d_ebin64 + row0, sizeof(double) * (rows + 1), hipMemcpyDeviceToDevice));
-        HIPCHK(e, hipMemcpy(&p.h_e0, full->d_ebin64 + row0, sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(e, hipMemcpy(&p.h_eR, full->d_ebin64 + row0 + rows, sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(e, hipMemcpy(p.d_ebin64, p.h_ebin64.data(), sizeof(double) * (rows + 1), hipMemcpyHostToDevice));
     }
     auto ins = e->band_plans.emplace(key, std::move(p));
     *out = &ins.first->second;
     return EMSPEC_OK;
 }
 
+static PlanScalars scalars_of(const emspec_engine* e, const Plan& p, int hop, int reassign) {
+    return plan_scalars(e->cfg, p.rows, e->custom_edges_hz.empty(), p.n, hop, reassign);
+}
 PlanDev plan_dev(const emspec_engine* e, const Plan& p, int hop, int reassign) {
+    const PlanScalars c = scalars_of(e, p, hop, reassign);
     PlanDev d;
     d.tw = p.d_tw;
     d.ebin = p.d_ebin;
-    d.rows = p.rows;
-    d.log_rows = e->custom_edges_hz.empty() ? 1 : 0;
-    d.D = latency(p.n, hop, reassign);
-    d.reassign = reassign ? 1 : 0;
-    d.hop = hop;
-    d.tscale = (float)((double)p.n / 2.0 / (double)hop);
-    const double pk = (double)p.n / 4.0;   // |X_h| of a full-scale sine
-    d.pfloor_abs = (float)((double)e->cfg.power_floor * pk * pk);
+    d.rows = c.rows;
+    d.log_rows = c.log_rows;
+    d.D = c.D;
+    d.reassign = c.reassign;
+    d.hop = c.hop;
+    d.tscale = c.tscale32;
+    d.pfloor_abs = c.pfloor_abs;
     // "shared" = 1: other kernels take CUs while a fused launch runs (a communicator with other ranks: RCCL transfers, the
     // gather's pack / expand) -> the shared-device segment plan.  2: this engine's own two-lane host pipeline (emspec_batch
     // runs neighbouring stream-chunks on two HIP streams): two fused launches share the chip, so segments are capped at
@@ -276,52 +131,38 @@ PlanDev plan_dev(const emspec_engine* e, const Plan& p, int hop, int reassign) {
     return d;
 }
 
-// EXACT mode: the plan and the dB map in binary64 (oracle/emspec_exact.c: explan_init, eo_batch_exact)
+// EXACT mode: the plan and the dB map in binary64
 ExactPlanDev exact_plan_dev(const emspec_engine* e, const Plan& p, int hop, int reassign) {
+    const PlanScalars c = scalars_of(e, p, hop, reassign);
+    const ExactScalars x = exact_scalars(p.n, c.rows, c.pfloor, p.h_ebin64.front(), p.h_ebin64.back());
     ExactPlanDev d;
     d.tw = p.d_tw64;
     d.ebin = p.d_ebin64;
-    d.rows = p.rows;
-    d.log_rows = e->custom_edges_hz.empty() ? 1 : 0;
-    d.D = latency(p.n, hop, reassign);
-    d.reassign = reassign ? 1 : 0;
-    d.hop = hop;
-    d.tscale = (double)p.n / 2.0 / (double)hop;
-    const double pk = (double)p.n / 4.0;
-    d.pfloor = (double)e->cfg.power_floor * pk * pk;
-    int log2n = 0;
-    while ((1 << log2n) < p.n) ++log2n;
-    d.qscale = std::ldexp(1.0, 52 - (2 * log2n - 4));
-    d.pmax = std::ldexp(1.0, 61) / d.qscale;
-    d.pfloor64 = 64.0 * d.pfloor;
-    d.pmax64 = 64.0 * d.pmax;
-    d.qscale64 = d.qscale / 64.0;
-    d.e0 = p.h_e0;
-    d.eR = p.h_eR;
-    d.l2e0 = std::log2((float)p.h_e0);
-    d.rscale = (float)d.rows / (std::log2((float)p.h_eR) - d.l2e0);
+    d.rows = c.rows;
+    d.log_rows = c.log_rows;
+    d.D = c.D;
+    d.reassign = c.reassign;
+    d.hop = c.hop;
+    d.tscale = c.tscale;
+    d.pfloor = c.pfloor;
+    d.pmax = x.pmax;
+    d.qscale = x.qscale;
+    d.pfloor64 = x.pfloor64;
+    d.pmax64 = x.pmax64;
+    d.qscale64 = x.qscale64;
+    d.e0 = p.h_ebin64.front();
+    d.eR = p.h_ebin64.back();
+    d.l2e0 = x.l2e0;
+    d.rscale = x.rscale;
     return d;
 }
 ExactDbMap exact_db_map(const emspec_engine* e, int n, const ExactPlanDev& pd) {
-    // (oracle/emspec_exact.c: eo_batch_exact states the same operations; every constant is rounded once to binary32)
-    ExactDbMap m;
-    const double nn = (double)n;
-    const double scale = 32.0 / (3.0 * nn * nn) * (double)e->cfg.gain * (double)e->cfg.gain;
-    m.sc = (float)(scale * (1.0 / pd.qscale));
-    m.lo = (float)((double)e->cfg.db_top - (double)e->cfg.db_range);
-    m.inv_range = (float)(1.0 / (double)e->cfg.db_range);
-    m.gate = e->cfg.gate_db;
-    return m;
+    const DbScalars m = exact_db_scalars(e->cfg, n, pd.qscale);
+    return ExactDbMap{m.scale, m.lo, m.inv_range, m.gate};
 }
-
 DbMap db_map(const emspec_engine* e, int n) {
-    DbMap m;
-    const double nn = (double)n;
-    m.scale = (float)(32.0 / (3.0 * nn * nn) * (double)e->cfg.gain * (double)e->cfg.gain);
-    m.lo = e->cfg.db_top - e->cfg.db_range;
-    m.inv_range = (float)(1.0 / (double)e->cfg.db_range);
-    m.gate = e->cfg.gate_db;
-    return m;
+    const DbScalars m = db_scalars(e->cfg, n);
+    return DbMap{m.scale, m.lo, m.inv_range, m.gate};
 }
 
 }  // namespace emspec
@@ -443,11 +284,7 @@ static int exact_lr_rows(const emspec_engine* e, int n, const ExactPlanDev& pd, 
 #endif
     const int rl = exact_fused_lr_low_rows(n, pd);
     if (rl <= 0) return rl;
-    const double hz = e->custom_edges_hz.empty()
-                          ? (double)e->cfg.fmin_hz * spec_pow((double)e->cfg.fmax_hz / (double)e->cfg.fmin_hz, (double)(row0 + rl) / (double)e->cfg.rows)
-                          : (double)e->custom_edges_hz[row0 + rl];
-    const double share = hz / ((double)e->cfg.sample_rate * 0.5);
-    return share <= 0.06 ? rl : -1;
+    return low_share_ok(axis_of(e->cfg, e->custom_edges_hz), row0 + rl) ? rl : -1;
 }
 extern "C" {
 int emspec_uses_fused(const emspec_engine* e, int32_t n, int32_t hop, int32_t reassign) {
@@ -496,34 +333,21 @@ int emspec_warped_edges_hz(int32_t rows, float fmin_hz, float fmax_hz, float low
                            float* out) {
     if (!out || rows < 1 || !(fmin_hz > 0.0f) || !(fmax_hz > fmin_hz) || !(low_end_boost > 0.0f) || !(freq_scale > 0.0f))
         return EMSPEC_ERR_INVALID_ARG;
-    const double span = std::log((double)fmax_hz / (double)fmin_hz) / (double)freq_scale;
-    for (int r = 0; r <= rows; ++r)
-        out[r] = (float)((double)fmin_hz * std::exp(span * std::pow((double)r / (double)rows, (double)low_end_boost)));
+    warped_edges_hz(rows, fmin_hz, fmax_hz, low_end_boost, freq_scale, out);
     return EMSPEC_OK;
 }
 
 int emspec_make_colormap(float brightness, uint8_t* out) {
     if (!out || !(brightness >= 0.0f)) return EMSPEC_ERR_INVALID_ARG;
-    static const double stops[5][3] = {{0, 0, 0}, {80, 0, 80}, {200, 50, 50}, {255, 150, 0}, {255, 255, 200}};
-    for (int i = 0; i < 256; ++i) {
-        const double v = std::min(1.0, ((double)i / 255.0) * ((double)brightness / 0.5));
-        const double t = v * 4.0;
-        const int s = std::min(3, (int)std::floor(t));
-        const double f = t - (double)s;
-        for (int c = 0; c < 3; ++c) out[4 * i + c] = (uint8_t)std::floor(stops[s][c] + f * (stops[s + 1][c] - stops[s][c]) + 0.5);
-        out[4 * i + 3] = 255;
-    }
+    make_colormap(brightness, out);
     return EMSPEC_OK;
 }
 
 int emspec_get_row_edges_hz(emspec_engine* e, float* edges_hz, int32_t count) {
     if (!e || !edges_hz) return EMSPEC_ERR_INVALID_ARG;
     if (count != e->cfg.rows + 1) return fail(e, EMSPEC_ERR_INVALID_ARG, "need room for rows+1 edges");
-    const int R = e->cfg.rows;
-    const double ratio = (double)e->cfg.fmax_hz / (double)e->cfg.fmin_hz;
-    for (int r = 0; r <= R; ++r)
-        edges_hz[r] = e->custom_edges_hz.empty() ? (float)((double)e->cfg.fmin_hz * spec_pow(ratio, (double)r / (double)R))
-                                                 : e->custom_edges_hz[r];
+    const Axis axis = axis_of(e->cfg, e->custom_edges_hz);
+    for (int r = 0; r <= axis.rows; ++r) edges_hz[r] = (float)edge_hz(axis, r);
     return EMSPEC_OK;
 }
 

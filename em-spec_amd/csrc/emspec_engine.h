@@ -6,6 +6,7 @@
 #include "../../include/emspec.h"
 #pragma GCC visibility pop
 #include "emspec_launch.h"
+#include "emspec_tables.h"
 
 #include <functional>
 #include <map>
@@ -18,16 +19,16 @@ namespace emspec {
 struct Plan {
     int n = 0;
     // the rows this plan serves: the engine's whole table (row0 = 0, rows = cfg.rows), or a band of it for the
-    // multi-resolution batch (emspec_multires.cpp) - h_ebin / d_ebin (/ d_ebin64, h_e0, h_eR) are then that slice of the
+    // multi-resolution batch (emspec_multires.cpp) - h_ebin / d_ebin (/ h_ebin64, d_ebin64) are then that slice of the
     // full table, and d_tw / d_tw64 belong to the full plan of the same n
     int row0 = 0, rows = 0;
     float2* d_tw = nullptr;
     float* d_ebin = nullptr;
     std::vector<float> h_tw, h_ebin;
+    std::vector<double> h_ebin64;   // the binary64 edge table (h_ebin is this one rounded once per entry)
     // EXACT mode (cfg.mode == EMSPEC_MODE_EXACT): the binary64 tables
     double2* d_tw64 = nullptr;
     double* d_ebin64 = nullptr;
-    double h_e0 = 0.0, h_eR = 0.0;   // ends of the binary64 edge table
 };
 // Live multi-stream streaming session (emspec_live.cpp; include/emspec.h: emspec_columns / emspec_push_samples_multi):
 // S streams, each with its own sample position, sample ring and pending-column ring, advanced together by ONE launch per call.
@@ -66,8 +67,7 @@ struct LiveState {
     float* d_fresh = nullptr; size_t dfresh_bytes = 0;   // [S][cap] decoded samples
 };
 
-// emspec_api.cpp: the plan cache and the per-shape constants handed to the kernels
-int latency(int n, int hop, int reassign);
+// emspec_api.cpp: the plan cache and the per-shape constants handed to the kernels (their arithmetic: emspec_tables.h, as latency())
 int check_shape(const emspec_engine* e, int n, int hop);
 int get_plan(emspec_engine* e, int n, Plan** out);
 int get_band_plan(emspec_engine* e, int n, int row0, int rows, Plan** out);   // rows [row0, row0 + rows) of the table

@@ -75,6 +75,11 @@ static void ex_twiddle(int n, double* tw) {
     tw[2 * (n / 4)] = 0.0;
     tw[2 * (n / 4) + 1] = -1.0;
 }
+int eo_twiddle64(int n, double* tw) {
+    if (n < 8 || (n & (n - 1)) || !tw) return -1;
+    ex_twiddle(n, tw);
+    return 0;
+}
 
 /* stage "STFT": the canonical radix-2 DIF network of the float32 bit model (emspec_oracle.c:fft_dif_f32), in binary64 */
 static void ex_fft_dif(int n, int log2n, double* re, double* im, const double* tw) {
@@ -263,7 +268,7 @@ int eo_batch_exact(const eo_cfg* c, const float* pcm, int32_t S, int64_t L, cons
     const int R = c->rows, K = p.K;
     const double nn = (double)c->n;
     const double scale = 32.0 / (3.0 * nn * nn) * (double)c->gain * (double)c->gain;
-    /* the stage's constants, each rounded once to binary32 (emspec_api.cpp: exact_db_map states the same operations) */
+    /* the stage's constants, each rounded once to binary32 (em-spec_amd/csrc/emspec_tables.h: exact_db_scalars states the same operations) */
     const float sc = (float)(scale * (1.0 / p.qscale));
     const float lo = (float)((double)c->db_top - (double)c->db_range), inv_range = (float)(1.0 / (double)c->db_range);
     const float gate = c->gate_db;

@@ -144,6 +144,13 @@ def edges64(cfg):
     return e
 
 
+def twiddle64(n):
+    """The EXACT mode's binary64 twiddle table: n doubles, (cos, -sin)(2 pi q / n) interleaved."""
+    tw = np.empty(n, np.float64)
+    assert lib().eo_twiddle64(C.c_int(n), _p(tw, C.c_double)) == 0
+    return tw
+
+
 def frames_exact(cfg, pcm, frame0, nframes):
     """EXACT-mode bit model, one stream: (power float64, col, row, q int64), each [nframes][n/2+1]."""
     pcm = np.ascontiguousarray(pcm, np.float32)

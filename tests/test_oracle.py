@@ -416,7 +416,7 @@ def test_reassignment_equals_phase_derivatives():
 def test_row_edges_come_from_a_specified_evaluation():
     """The log-spaced row edges are fmin * ratio^(r/R) with ratio^x evaluated by eo_spec_pow - plain IEEE operations in a
     fixed order (atanh-series log2, Taylor exp2), no libm pow, so the table does not depend on the host's C library
-    (ADVICE r03 / VERDICT r04 item 9; the library builds its tables with the same operations, emspec_api.cpp:spec_pow,
+    (ADVICE r03 / VERDICT r04 item 9; the library builds its tables with the same operations, emspec_tables.h:spec_pow,
     and tests/test_gpu_parity.py compares the two tables bit for bit on the GPU box).  Known answers pin the bits; the
     value stays within a few ulp of the real power."""
     import ctypes as C
