@@ -32,22 +32,17 @@ struct Plan {
 };
 // Live multi-stream streaming session (emspec_live.cpp; include/emspec.h: emspec_columns / emspec_push_samples_multi):
 // S streams, each with its own sample position, sample ring and pending-column ring, advanced together by ONE launch per call.
+// Geometry + counters (emspec_live_plan.h: their arithmetic and every buffer size) + the buffers, which outlive a reset.
+struct LivePcm {   // PCM session (emspec_push_samples_pcm; form 2 only): S = sources * views streams fed from raw interleaved frames
+    int views = 0;                        // 0: a float session
+    emspec_pcm_format fmt{};
+};
 struct LiveState {
-    int S = 0, n = 0, hop = 0, reassign = -1, D = 0;
-    // multi-resolution session (emspec_columns_multires / emspec_push_samples_multires): n / D / slots / d_cells
-    // are the long band's (rows [0, split) at n_low); the short band (rows [split, R) at n_high) has its own column ring,
-    // indexed by the emitted column.  Its frame count follows the long band's: 0 while fed is 0, fed + 2 shift after.
-    int n_high = 0, split = 0, shift = 0, D_high = 0;   // n_high == 0: a single-resolution session
-    int slots_high = 0;       // mmax + shift + D + D_high
-    void* d_cells_high = nullptr; size_t cells_high_bytes = 0;   // [S][slots_high][R - split]
-    int form = 0;             // 0 none, 1 per-frame (emspec_columns), 2 per-sample-block (emspec_push_samples_multi)
-    int slots = 0;            // column-ring slots per stream: 2 D + mmax
-    int mmax = 0;             // frames per stream and launch, at most
-    int64_t cap = 0;          // samples per stream the staging block holds (form 2: mmax * hop)
-    int ring_mask = 0;        // device sample ring per stream: ring_mask + 1 >= n + cap samples (form 2)
-    std::vector<int64_t> fed, emitted, seen, newbase;   // per stream: frames fed, columns emitted, samples received, samples in the device ring
-    std::vector<int> pend;    // per stream: samples waiting in the staging block
+    LiveGeometry g;
+    LiveCounters c;
+    LivePcm pcm;
     void* d_cells = nullptr; size_t cells_bytes = 0;    // [S][slots][rows] float32 (FAST) / u64 (EXACT)
+    void* d_cells_high = nullptr; size_t cells_high_bytes = 0;   // multi-resolution session, the short band: [S][slots_high][R - split]
     float* d_sring = nullptr; size_t sring_bytes = 0;   // [S][ring_mask + 1]
     unsigned* d_done = nullptr; size_t done_bytes = 0;  // [S] arrival counters (a multi-resolution session: [2][S], one set per band)
     float* d_raw = nullptr; size_t raw_bytes = 0;       // display post-process: raw dB [S][mmax][rows]
@@ -58,13 +53,11 @@ struct LiveState {
     float* h_odb = nullptr; size_t odb_bytes = 0;
     uint8_t* h_orgba = nullptr; size_t orgba_bytes = 0;
     unsigned long long* stamps = nullptr;   // diagnostic build: [S][8] page-locked, set by emspec_debug_live_stamps
-    // PCM session (emspec_push_samples_pcm; form 2 only): S = sources * views streams fed from raw interleaved frames.  The
-    // staging block holds the raw frames ([sources][cap] frames, page-locked; the decode kernel reads it in place) and the
-    // frame kernels read the decoded block on the device.  Every stream of the session has the same `pend`.
-    int pcm_views = 0;                    // 0: a float session
-    emspec_pcm_format pcm_fmt{};
-    uint8_t* h_raw = nullptr; size_t hraw_bytes = 0;     // [S / pcm_views][cap] frames
+    // PCM session: the staging block holds the raw frames ([sources][cap] frames, page-locked; the decode kernel reads it in
+    // place) and the frame kernels read the decoded block on the device.  Every stream of the session has the same `pend`.
+    uint8_t* h_raw = nullptr; size_t hraw_bytes = 0;     // [S / pcm.views][cap] frames
     float* d_fresh = nullptr; size_t dfresh_bytes = 0;   // [S][cap] decoded samples
+    LiveStream* desc() const { return reinterpret_cast<LiveStream*>(h_desc); }
 };
 
 // emspec_api.cpp: the plan cache and the per-shape constants handed to the kernels (their arithmetic: emspec_tables.h, as latency())

@@ -3,23 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "emspec_device.h"
+#include "emspec_live_plan.h"
 
 namespace emspec {
 
-// ---- live multi-stream streaming (emspec_columns / emspec_push_samples_multi; live.hip.inc) ----
-// One launch serves S live streams: grid = (frames per stream + 1, S).  Workgroup (f, s) with f < frames[s] transforms
-// frame j0[s] + f of stream s and scatters it into that stream's column ring in HBM (device-scope atomics); the LAST of a
-// stream's workgroups to finish (an arrival counter per stream) finalises the columns the launch completed, straight into the
-// caller's (page-locked) output, and clears their ring slots.  Workgroup (gridDim.x - 1, s) moves the stream's new samples
-// from the page-locked staging block into its device sample ring for later launches.
-struct LiveStream {        // per stream and launch; read by the kernel from page-locked host memory
-    long long j0;          // absolute index of the stream's first frame in this launch (= frames fed so far)
-    long long newbase;     // absolute index of fresh[s][0]: samples below it are in the device sample ring
-    int frames;            // frames of this stream in this launch (0 .. gridDim.x - 1)
-    int newcount;          // samples in fresh[s] to move into the sample ring
-    int out_at;            // first column slot of the stream's output block this launch writes
-    int flush;             // != 0: no frames; finalise `flush` pending columns starting at column j0 - D (emspec_columns_flush)
-};
+// ---- live multi-stream streaming: the launch and its per-stream descriptor LiveStream are described in emspec_live_plan.h ----
 struct LiveSinks {
     const LiveStream* streams = nullptr;   // [S]; null: not a live launch
     LiveStream uni{};                      // uniform != 0: every stream's descriptor (the kernel then does not read `streams`)

@@ -6,13 +6,16 @@
 // emspec_column_flush, emspec_push_samples, emspec_push_columns.  Two independent sessions per engine: e->live and e->one.
 //
 // What it serves: BASELINE.json configs[2] is "64 concurrent 48 kHz streams" and north_star's renderer call is per frame
-// (computeSpectrogramColumn(audioFrame, fftSize, hop, reassign)); /root/reference/README.md:36 ("automatically start
+// (computeSpectrogramColumn(audioFrame, fftSize, hop, reassign)); the reference's README.md:36 ("automatically start
 // visualizing your system audio") is the live case.  With one engine per stream that is S launches + S synchronisations
 // per hop on the host thread; here the S streams of one engine advance together: ONE kernel launch and ONE stream
 // synchronisation per call, samples read by the kernel from page-locked host memory, finished columns written by the kernel
 // into page-locked host memory (the caller's own buffers when they come from emspec_host_alloc) - no copy engine involved.
 // No reference file:line exists (the reference source is private, README.md:73); SURVEY.md §8(f) row 4 is the streaming glue.
 // Device side: live.hip.inc / live_launch.hip.inc.
+// This file holds the HIP side only: allocations, copies, launches, synchronisations, the ABI's checks and messages.  What a
+// session's buffers measure and which column a call's output slot holds - the geometry, the per-stream counters, the
+// descriptors of every launch - is emspec_live_plan.h, plain integer code that tests/test_live_plan_cpu.py runs on the CPU.
 #include "emspec_engine.h"
 #ifdef EMSPEC_DIAG
 #pragma GCC visibility push(default)
@@ -26,11 +29,7 @@
 using namespace emspec;
 
 namespace {
-// per-sample-block form: frames per stream and launch, at most - about 2,048 workgroups per launch, 8..64 per stream
-int live_frames_per_launch(int S) { return std::max(8, std::min(64, 2048 / std::max(1, S))); }
 constexpr int kInlineFinalize = 2;   // a launch that completes more columns per stream than this finalises them in a second kernel
-
-int64_t frames_after(int64_t total, int n, int hop) { return total >= n ? (total - n) / hop + 1 : 0; }
 
 int pinned_grow(emspec_engine* e, void** p, size_t* have, size_t want) {
     if (*have >= want) return EMSPEC_OK;
@@ -48,10 +47,11 @@ void* device_view(const void* p) {
     return d;
 }
 
+// drops the session; the buffers and their capacities stay
 void live_forget(LiveState& lv) {
-    lv.S = 0; lv.n = 0; lv.hop = 0; lv.reassign = -1; lv.D = 0; lv.form = 0; lv.slots = 0; lv.mmax = 0; lv.cap = 0; lv.ring_mask = 0;
-    lv.n_high = 0; lv.split = 0; lv.shift = 0; lv.D_high = 0; lv.slots_high = 0; lv.pcm_views = 0;
-    lv.fed.clear(); lv.emitted.clear(); lv.seen.clear(); lv.newbase.clear(); lv.pend.clear();
+    lv.g = LiveGeometry{};
+    lv.c = LiveCounters{};
+    lv.pcm = LivePcm{};
 }
 
 // first call of a session: every allocation, then the state.  n_high != 0: a multi-resolution session (n = n_low; rows below
@@ -59,57 +59,42 @@ void live_forget(LiveState& lv) {
 // pcm: a PCM session - its staging block holds raw frames (live_open_pcm), not floats.
 int live_open(emspec_engine* e, LiveState& lv, int S, int n, int hop, int reassign, int form, int n_high = 0, int split = 0,
               bool pcm = false) {
+    const LiveGeometry g = live_geometry(S, n, hop, reassign, form, n_high, split);
     const int R = e->cfg.rows;
-    const int D = latency(n, hop, reassign);
-    const int Rl = n_high ? split : R;   // rows of the (long) band that d_cells holds
-    // The short band runs 2 shift frames ahead and its ring is indexed by the emitted column (its own column - shift).  A call
-    // that feeds long frames j .. j + m - 1 finds emitted columns >= j - D unfinalised, and its short frames, the last of them
-    // frame j + m - 1 + 2 shift = emitted column j + m - 1 + shift, add up to D_high columns further: m + shift + D + D_high
-    // columns are live at once (reassign on: D = D_high + shift, i.e. m + 2 shift + 2 D_high).
-    const int shift = n_high ? (n - n_high) / (2 * hop) : 0, D_high = n_high ? latency(n_high, hop, reassign) : 0;
-    // (a staging block of at most 2^17 samples per stream: at a large hop fewer frames per launch instead of megabytes pinned)
-    const int mmax = form == 1 ? 1 : std::max(1, std::min(live_frames_per_launch(S), (1 << 17) / hop));
-    const int slots = 2 * D + mmax;
-    const int64_t cap = form == 1 ? n : (int64_t)mmax * hop;
-    int ring = 1;
-    while (ring < n + cap) ring <<= 1;
-    const size_t cellb = e->exact() ? 8 : 4;
+    const size_t cell = e->exact() ? 8 : 4;
     int rc;
-    const int slots_high = n_high ? mmax + shift + D + D_high : 0;
-    if ((rc = grow(e, &lv.d_cells, &lv.cells_bytes, (size_t)S * slots * Rl * cellb))) return rc;
-    if (n_high && (rc = grow(e, &lv.d_cells_high, &lv.cells_high_bytes, (size_t)S * slots_high * (R - split) * cellb))) return rc;
-    if (form == 2 && (rc = grow(e, (void**)&lv.d_sring, &lv.sring_bytes, (size_t)S * ring * 4))) return rc;
-    if ((rc = grow(e, (void**)&lv.d_done, &lv.done_bytes, (size_t)S * 4 * (n_high ? 2 : 1)))) return rc;
-    if ((rc = pinned_grow(e, &lv.h_desc, &lv.desc_bytes, (size_t)S * sizeof(LiveStream)))) return rc;
-    if (form == 2 && !pcm && (rc = pinned_grow(e, (void**)&lv.h_fresh, &lv.fresh_bytes, (size_t)S * cap * 4))) return rc;
-    HIPCHK(e, hipMemsetAsync(lv.d_cells, 0, (size_t)S * slots * Rl * cellb, e->stream));
-    if (n_high) HIPCHK(e, hipMemsetAsync(lv.d_cells_high, 0, (size_t)S * slots_high * (R - split) * cellb, e->stream));
-    HIPCHK(e, hipMemsetAsync(lv.d_done, 0, (size_t)S * 4 * (n_high ? 2 : 1), e->stream));
+    if ((rc = grow(e, &lv.d_cells, &lv.cells_bytes, g.rings_bytes(R, cell)))) return rc;
+    if (n_high && (rc = grow(e, &lv.d_cells_high, &lv.cells_high_bytes, g.rings_high_bytes(R, cell)))) return rc;
+    if (form == 2 && (rc = grow(e, (void**)&lv.d_sring, &lv.sring_bytes, g.sring_bytes()))) return rc;
+    if ((rc = grow(e, (void**)&lv.d_done, &lv.done_bytes, g.done_bytes()))) return rc;
+    if ((rc = pinned_grow(e, &lv.h_desc, &lv.desc_bytes, g.desc_bytes()))) return rc;
+    if (form == 2 && !pcm && (rc = pinned_grow(e, (void**)&lv.h_fresh, &lv.fresh_bytes, g.fresh_bytes()))) return rc;
+    HIPCHK(e, hipMemsetAsync(lv.d_cells, 0, g.rings_bytes(R, cell), e->stream));
+    if (n_high) HIPCHK(e, hipMemsetAsync(lv.d_cells_high, 0, g.rings_high_bytes(R, cell), e->stream));
+    HIPCHK(e, hipMemsetAsync(lv.d_done, 0, g.done_bytes(), e->stream));
     if (lv.d_pstate) HIPCHK(e, hipMemsetAsync(lv.d_pstate, 0, lv.pstate_bytes, e->stream));
-    lv.S = S; lv.n = n; lv.hop = hop; lv.reassign = reassign; lv.D = D; lv.form = form; lv.slots = slots; lv.mmax = mmax;
-    lv.cap = cap; lv.ring_mask = ring - 1;
-    lv.n_high = n_high; lv.split = n_high ? split : 0; lv.shift = shift; lv.D_high = D_high; lv.slots_high = slots_high;
-    lv.fed.assign(S, 0); lv.emitted.assign(S, 0); lv.seen.assign(S, 0); lv.newbase.assign(S, 0); lv.pend.assign(S, 0);
+    lv.g = g;
+    lv.c.open(S);
     return EMSPEC_OK;
 }
 
 int live_check(emspec_engine* e, const LiveState& lv, int S, int n, int hop, int reassign, int rows, int form, int n_high = 0,
                int split = 0) {
+    const LiveGeometry& g = lv.g;
     int rc = n_high ? multires_check(e, S, n, n_high, hop, split) : check_shape(e, n, hop);
     if (rc) return rc;
     if (rows != e->cfg.rows) return fail(e, EMSPEC_ERR_INVALID_ARG, "rows does not match the engine configuration");
     if (S < 1 || S > 65535) return fail(e, EMSPEC_ERR_INVALID_ARG, "streams must be in 1..65535");
-    if (lv.form != 0 && (n_high != 0) != (lv.n_high != 0))
-        return fail(e, EMSPEC_ERR_STATE, lv.n_high ? "the live session is a multi-resolution one (emspec_columns_multires / emspec_push_samples_multires); call emspec_reset() first"
-                                                   : "the live session is a single-resolution one; call emspec_reset() before a multi-resolution call");
-    if (lv.form != 0 && (S != lv.S || n != lv.n || hop != lv.hop || reassign != lv.reassign || form != lv.form || n_high != lv.n_high ||
-                         split != lv.split))
+    if (g.form != 0 && (n_high != 0) != (g.n_high != 0))
+        return fail(e, EMSPEC_ERR_STATE, g.n_high ? "the live session is a multi-resolution one (emspec_columns_multires / emspec_push_samples_multires); call emspec_reset() first"
+                                                  : "the live session is a single-resolution one; call emspec_reset() before a multi-resolution call");
+    if (g.form != 0 && (S != g.S || n != g.n || hop != g.hop || reassign != g.reassign || form != g.form || n_high != g.n_high ||
+                        split != g.split))
         return fail(e, EMSPEC_ERR_STATE, n_high ? "streams / fft sizes / hop / split row / reassign / feeding mode changed mid-stream; call emspec_reset() first"
                                                 : "streams / fft size / hop / reassign / feeding mode changed mid-stream; call emspec_reset() first");
-    // A flush emits columns that later frames would still have added to: the stream is at its end.  Feeding it again would emit
-    // those columns a second time, holding only the new frames' energy.
-    for (int s = 0; s < lv.S; ++s)
-        if (lv.emitted[s] > std::max<int64_t>(lv.fed[s] - lv.D, 0))
+    // Feeding a flushed stream again would emit its last columns a second time, holding only the new frames' energy.
+    for (int s = 0; s < g.S; ++s)
+        if (lv.c.flushed(s, g.D))
             return fail(e, EMSPEC_ERR_STATE, "stream " + std::to_string(s) + " was flushed: reset it (emspec_reset / emspec_reset_stream) before feeding it again");
     return EMSPEC_OK;
 }
@@ -118,8 +103,8 @@ int live_check(emspec_engine* e, const LiveState& lv, int S, int n, int hop, int
 int live_post_buffers(emspec_engine* e, LiveState& lv) {
     const int R = e->cfg.rows;
     int rc;
-    if ((rc = grow(e, (void**)&lv.d_raw, &lv.raw_bytes, (size_t)lv.S * lv.mmax * R * 4))) return rc;
-    const size_t want = (size_t)lv.S * (R + 4) * 4;
+    if ((rc = grow(e, (void**)&lv.d_raw, &lv.raw_bytes, lv.g.out_bytes(R, lv.g.mmax)))) return rc;
+    const size_t want = lv.g.S * LiveGeometry::pstate_bytes(R);
     if (lv.pstate_bytes < want) {
         if ((rc = grow(e, (void**)&lv.d_pstate, &lv.pstate_bytes, want))) return rc;
         HIPCHK(e, hipMemsetAsync(lv.d_pstate, 0, lv.pstate_bytes, e->stream));
@@ -134,29 +119,25 @@ int live_post_buffers(emspec_engine* e, LiveState& lv) {
 int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fresh_stride, int mlaunch, bool flush, float* dst_db,
                 uint8_t* dst_rgba, int out_cols, int raw_cols, bool empty_col) {
     int rc;
+    const LiveGeometry& g = lv.g;
     const int R = e->cfg.rows;
     const bool post = e->smoothing > 0.0f || e->agc > 0.0f;
     if (post && (rc = live_post_buffers(e, lv))) return rc;
     LiveSinks ls;
-    ls.streams = reinterpret_cast<const LiveStream*>(lv.h_desc);
+    ls.streams = lv.desc();
     ls.fresh = fresh;
     ls.fresh_stride = fresh_stride;
-    ls.sring = lv.form == 2 ? lv.d_sring : nullptr;
-    ls.ring_mask = lv.ring_mask;
+    ls.sring = g.form == 2 ? lv.d_sring : nullptr;
+    ls.ring_mask = g.ring_mask;
     ls.done = lv.d_done;
     ls.out_cols = out_cols;
     ls.out_rows = R;
     ls.empty_col = empty_col ? 1 : 0;
     ls.lut = reinterpret_cast<const uint32_t*>(e->d_lut);
-    bool priming = false;   // multi-resolution session: some stream's first frame, i.e. its short band's first 2 shift + 1
-    {   // every stream in the same state: the descriptor goes into the kernel arguments
-        const LiveStream* dsc = reinterpret_cast<const LiveStream*>(lv.h_desc);
-        bool same = true;
-        for (int s = 1; s < lv.S && same; ++s) same = std::memcmp(&dsc[s], &dsc[0], sizeof(LiveStream)) == 0;
-        ls.uniform = same ? 1 : 0;
-        ls.uni = dsc[0];
-        for (int s = 0; s < lv.S && !priming; ++s) priming = dsc[s].j0 == 0 && dsc[s].frames > 0;
-    }
+    // every stream in the same state: the descriptor goes into the kernel arguments
+    ls.uniform = live_uniform(lv.desc(), g.S) ? 1 : 0;
+    ls.uni = lv.desc()[0];
+    const bool priming = live_priming(lv.desc(), g.S);   // multi-resolution session: the short band's first 2 shift + 1 frames
 #ifdef EMSPEC_DIAG
     ls.stamps = lv.stamps;
 #endif
@@ -165,8 +146,7 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
     // block's stride only where it is an output's stride)
     if (post) {
         raw_cols = std::max(1, (dst_db || dst_rgba) ? std::min(raw_cols, out_cols) : raw_cols);
-        if ((size_t)lv.S * raw_cols * R * 4 > lv.raw_bytes &&
-            (rc = grow(e, (void**)&lv.d_raw, &lv.raw_bytes, (size_t)lv.S * raw_cols * R * 4))) return rc;
+        if (g.out_bytes(R, raw_cols) > lv.raw_bytes && (rc = grow(e, (void**)&lv.d_raw, &lv.raw_bytes, g.out_bytes(R, raw_cols)))) return rc;
         ls.out_db = lv.d_raw;
         ls.out_rgba = nullptr;
         ls.out_cols = raw_cols;
@@ -174,7 +154,7 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
         ls.out_db = dst_db;
         ls.out_rgba = reinterpret_cast<uint32_t*>(dst_rgba);
     }
-    const DbMap m = db_map(e, lv.n);
+    const DbMap m = db_map(e, g.n);
     const bool exact = e->exact();
     // One band: its frame launch (or, flush = true, the flush kernel) on rows [p.row0, p.row0 + p.rows) of the output column.
     // A single-resolution session is one band of all rows; a multi-resolution one runs the long band, then the short band,
@@ -182,7 +162,7 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
     // bl: the band's sinks; frames: the largest per-stream frame count of the band in this launch.
     const auto band = [&](const Plan& p, const LiveSinks& bl, void* cells, int slots, int frames) -> int {
         const DbMap bm = db_map(e, p.n);
-        const ExactPlanDev xpd = exact ? exact_plan_dev(e, p, lv.hop, lv.reassign) : ExactPlanDev{};
+        const ExactPlanDev xpd = exact ? exact_plan_dev(e, p, g.hop, g.reassign) : ExactPlanDev{};
         // (lo / inv_range / gate do not depend on the fft size: both bands index the palette as the batch's composition does)
         const ExactDbMap xm = exact ? exact_db_map(e, p.n, xpd) : ExactDbMap{};
         // many columns per stream: the frame kernel only scatters and a second kernel finalises them, one workgroup per column
@@ -193,53 +173,53 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
         LiveSinks bs = bl;
         bs.defer_finalize = defer ? 1 : 0;
         if (flush) {
-            HIPCHK(e, launch_live_flush(exact, bs, cells, slots, p.rows, lv.D, bm, xm, lv.S, 1, e->stream));
+            HIPCHK(e, launch_live_flush(exact, bs, cells, slots, p.rows, g.D, bm, xm, g.S, 1, e->stream));
         } else if (exact) {
             ExactSinks xs;
             xs.hist = reinterpret_cast<unsigned long long*>(cells);
             xs.hist_slots = slots; xs.total_cols = INT64_MAX; xs.ring = 1;
             xs.live = bs;
             xs.fin_map = xm;
-            HIPCHK(e, launch_exact_frames(p.n, xpd, nullptr, 0, lv.S, 0, (int64_t)frames + 1, xs, e->stream));
+            HIPCHK(e, launch_exact_frames(p.n, xpd, nullptr, 0, g.S, 0, (int64_t)frames + 1, xs, e->stream));
         } else {
             FrameSinks sk;
             sk.hist = reinterpret_cast<float*>(cells);
             sk.hist_slots = slots; sk.total_cols = INT64_MAX; sk.ring = 1;
             sk.live = bs;
             sk.fin_map = bm;
-            HIPCHK(e, launch_frames(p.n, plan_dev(e, p, lv.hop, lv.reassign), nullptr, 0, lv.S, 0, (int64_t)frames + 1, sk, e->stream));
+            HIPCHK(e, launch_frames(p.n, plan_dev(e, p, g.hop, g.reassign), nullptr, 0, g.S, 0, (int64_t)frames + 1, sk, e->stream));
         }
         // (the columns a launch completes are the long band's frame count for either band)
-        if (defer) HIPCHK(e, launch_live_flush(exact, bs, cells, slots, p.rows, lv.D, bm, xm, lv.S, mlaunch, e->stream));
+        if (defer) HIPCHK(e, launch_live_flush(exact, bs, cells, slots, p.rows, g.D, bm, xm, g.S, mlaunch, e->stream));
         return EMSPEC_OK;
     };
     Plan* p;
-    if (!lv.n_high) {
-        if ((rc = get_plan(e, lv.n, &p))) return rc;
-        if ((rc = band(*p, ls, lv.d_cells, lv.slots, mlaunch))) return rc;
+    if (!g.n_high) {
+        if ((rc = get_plan(e, g.n, &p))) return rc;
+        if ((rc = band(*p, ls, lv.d_cells, g.slots, mlaunch))) return rc;
     } else {
         Plan* ph;
-        if ((rc = get_band_plan(e, lv.n, 0, lv.split, &p))) return rc;
-        if ((rc = get_band_plan(e, lv.n_high, lv.split, R - lv.split, &ph))) return rc;
-        if ((rc = band(*p, ls, lv.d_cells, lv.slots, mlaunch))) return rc;
+        if ((rc = get_band_plan(e, g.n, 0, g.split, &p))) return rc;
+        if ((rc = get_band_plan(e, g.n_high, g.split, R - g.split, &ph))) return rc;
+        if ((rc = band(*p, ls, lv.d_cells, g.slots, mlaunch))) return rc;
         // the short band: no launch when no stream has a frame (a block that only fills the sample ring: the long band's
         // ingest workgroup did that)
         if (flush || mlaunch > 0) {
             LiveSinks hs = ls;
-            hs.row0 = lv.split;
-            hs.frame_shift = 2 * lv.shift;
-            hs.col_shift = lv.shift;
-            hs.lat_extra = lv.D - lv.D_high;
+            hs.row0 = g.split;
+            hs.frame_shift = 2 * g.shift;
+            hs.col_shift = g.shift;
+            hs.lat_extra = g.D - g.D_high;
             hs.no_ingest = 1;
-            hs.done = lv.d_done + lv.S;
-            if ((rc = band(*ph, hs, lv.d_cells_high, lv.slots_high, mlaunch + (priming ? 2 * lv.shift : 0)))) return rc;
+            hs.done = lv.d_done + g.S;
+            if ((rc = band(*ph, hs, lv.d_cells_high, g.slots_high, mlaunch + (priming ? 2 * g.shift : 0)))) return rc;
         }
     }
     if (post) {
         ls.out_db = dst_db;
         ls.out_rgba = reinterpret_cast<uint32_t*>(dst_rgba);
         ls.out_cols = out_cols;
-        HIPCHK(e, launch_live_post(ls, lv.d_raw, raw_cols, R, lv.D, e->smoothing, e->agc, e->cfg.db_top, m, lv.d_pstate, lv.S, e->stream));
+        HIPCHK(e, launch_live_post(ls, lv.d_raw, raw_cols, R, g.D, e->smoothing, e->agc, e->cfg.db_top, m, lv.d_pstate, g.S, e->stream));
     }
     return EMSPEC_OK;
 }
@@ -254,13 +234,53 @@ int live_abandon(emspec_engine* e, LiveState& lv, int code) {
     return code;
 }
 
-// staging for the outputs when the caller's buffers are not page-locked: [S][cols][rows] x 4 bytes each
-int live_out_staging(emspec_engine* e, LiveState& lv, bool want_db, bool want_rgba, int cols) {
-    const size_t bytes = (size_t)lv.S * cols * e->cfg.rows * 4;
-    int rc;
-    if (want_db && (rc = pinned_grow(e, (void**)&lv.h_odb, &lv.odb_bytes, bytes))) return rc;
-    if (want_rgba && (rc = pinned_grow(e, (void**)&lv.h_orgba, &lv.orgba_bytes, bytes))) return rc;
+// the synchronisation that ends a launch (or a round of launches), or the session with it
+int live_sync(emspec_engine* e, LiveState& lv) {
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return live_abandon(e, lv, fail(e, EMSPEC_ERR_HIP, "hipStreamSynchronize failed"));
     return EMSPEC_OK;
+}
+
+// Where a call's kernels write: the caller's buffers when they are page-locked, else the session's page-locked staging blocks
+// ([S][cols][rows] x 4 bytes each), copied back after the synchronisation.
+struct LiveDest {
+    float* db = nullptr;
+    uint8_t* rgba = nullptr;
+    bool stage_db = false, stage_rgba = false;
+    bool direct = false;   // nothing is staged, and the caller's layout may be the launch's (in_place_ok)
+};
+// together: every given output is staged unless all of them can be written in place; otherwise each output decides for itself
+int live_dest(emspec_engine* e, LiveState& lv, float* out_db, uint8_t* out_rgba, int cols, LiveDest& d, bool together = false,
+              bool in_place_ok = true) {
+    d.db = reinterpret_cast<float*>(device_view(out_db));
+    d.rgba = reinterpret_cast<uint8_t*>(device_view(out_rgba));
+    d.stage_db = out_db && !d.db;
+    d.stage_rgba = out_rgba && !d.rgba;
+    d.direct = !d.stage_db && !d.stage_rgba && in_place_ok;
+    if (together && !d.direct) { d.stage_db = out_db != nullptr; d.stage_rgba = out_rgba != nullptr; d.db = nullptr; d.rgba = nullptr; }
+    const size_t bytes = lv.g.out_bytes(e->cfg.rows, cols);
+    int rc;
+    if (d.stage_db && (rc = pinned_grow(e, (void**)&lv.h_odb, &lv.odb_bytes, bytes))) return rc;
+    if (d.stage_rgba && (rc = pinned_grow(e, (void**)&lv.h_orgba, &lv.orgba_bytes, bytes))) return rc;
+    if (d.stage_db) d.db = lv.h_odb;
+    if (d.stage_rgba) d.rgba = lv.h_orgba;
+    return EMSPEC_OK;
+}
+// The staged columns to the caller.  p == null: one column per stream, [S][rows] (emspec_columns, the flush); else the round's
+// columns of a push: p->nc[s] columns of stream s, from the front of its mmax staged columns to column p->produced[s] of its
+// max_columns.
+void live_copy_back(const LiveState& lv, const LiveDest& d, float* out_db, uint8_t* out_rgba, int R, const LivePush* p = nullptr,
+                    int64_t max_columns = 1) {
+    if (!p) {
+        if (d.stage_db) std::memcpy(out_db, lv.h_odb, lv.g.out_bytes(R, 1));
+        if (d.stage_rgba) std::memcpy(out_rgba, lv.h_orgba, lv.g.out_bytes(R, 1));
+        return;
+    }
+    for (int s = 0; s < lv.g.S; ++s) {
+        if (p->nc[s] <= 0) continue;
+        const size_t from = LiveGeometry::out_cell(R, lv.g.mmax, s, 0), to = LiveGeometry::out_cell(R, max_columns, s, p->produced[s]);
+        if (d.stage_db) std::memcpy(out_db + to, lv.h_odb + from, LiveGeometry::columns_bytes(R, p->nc[s]));
+        if (d.stage_rgba) std::memcpy(out_rgba + to * 4, lv.h_orgba + from * 4, LiveGeometry::columns_bytes(R, p->nc[s]));
+    }
 }
 }  // namespace
 
@@ -274,17 +294,16 @@ bool pcm_same_format(const emspec_pcm_format& a, const emspec_pcm_format& b) {
 // (behind live_open: the session's streams are sources * views)
 int live_open_pcm(emspec_engine* e, LiveState& lv, const emspec_pcm_format& fmt) {
     int rc;
-    if ((rc = pinned_grow(e, (void**)&lv.h_raw, &lv.hraw_bytes, (size_t)(lv.S / fmt.views) * lv.cap * pcm_frame_bytes(fmt)))) return rc;
-    if ((rc = grow(e, (void**)&lv.d_fresh, &lv.dfresh_bytes, (size_t)lv.S * lv.cap * 4))) return rc;
-    lv.pcm_fmt = fmt;
-    lv.pcm_views = fmt.views;
+    if ((rc = pinned_grow(e, (void**)&lv.h_raw, &lv.hraw_bytes, lv.g.raw_bytes(fmt.views, pcm_frame_bytes(fmt))))) return rc;
+    if ((rc = grow(e, (void**)&lv.d_fresh, &lv.dfresh_bytes, lv.g.decoded_bytes()))) return rc;
+    lv.pcm = LivePcm{fmt.views, fmt};
     return EMSPEC_OK;
 }
 
 // the staged raw frames (pend of them per source) -> d_fresh, on the engine's stream in front of the frame launch
 int live_decode_pending(emspec_engine* e, LiveState& lv) {
-    HIPCHK(e, pcm_decode(lv.h_raw, lv.pcm_fmt, lv.S / lv.pcm_views, lv.pend[0], lv.cap * pcm_frame_bytes(lv.pcm_fmt), lv.d_fresh,
-                                lv.cap, e->stream));
+    HIPCHK(e, pcm_decode(lv.h_raw, lv.pcm.fmt, lv.g.S / lv.pcm.views, lv.c.pcm_staged(), lv.g.raw_stride(pcm_frame_bytes(lv.pcm.fmt)),
+                         lv.d_fresh, lv.g.cap, e->stream));
     return EMSPEC_OK;
 }
 
@@ -292,14 +311,13 @@ int live_decode_pending(emspec_engine* e, LiveState& lv) {
 // does is launched by the call that brings it).  emspec_reset_stream runs it first, so that the streams of a session never
 // differ in what they have staged - the raw block is per source.
 int live_pcm_drain(emspec_engine* e, LiveState& lv) {
-    if (!lv.pcm_views || lv.pend[0] == 0) return EMSPEC_OK;
+    if (!lv.pcm.views || lv.c.pcm_staged() == 0) return EMSPEC_OK;
     int rc;
-    LiveStream* desc = reinterpret_cast<LiveStream*>(lv.h_desc);
-    for (int s = 0; s < lv.S; ++s) desc[s] = LiveStream{lv.fed[s], lv.newbase[s], 0, lv.pend[s], 0, 0};
+    live_drain_fill(lv.g, lv.c, lv.desc());
     if ((rc = live_decode_pending(e, lv))) return live_abandon(e, lv, rc);
-    if ((rc = live_launch(e, lv, lv.d_fresh, lv.cap, 0, false, nullptr, nullptr, 1, 1, false))) return live_abandon(e, lv, rc);
-    if (hipStreamSynchronize(e->stream) != hipSuccess) return live_abandon(e, lv, fail(e, EMSPEC_ERR_HIP, "hipStreamSynchronize failed"));
-    for (int s = 0; s < lv.S; ++s) { lv.newbase[s] = lv.seen[s]; lv.pend[s] = 0; }
+    if ((rc = live_launch(e, lv, lv.d_fresh, lv.g.cap, 0, false, nullptr, nullptr, 1, 1, false))) return live_abandon(e, lv, rc);
+    if ((rc = live_sync(e, lv))) return rc;
+    live_drain_commit(lv.g, lv.c);
     return EMSPEC_OK;
 }
 
@@ -318,33 +336,21 @@ int columns_impl(emspec_engine* e, LiveState& lv, const float* frames, int32_t s
     int rc = live_check(e, lv, streams, n, hop, reassign, rows, 1, n_high, split);
     if (rc) return rc;
     HIPCHK(e, hipSetDevice(e->device));
-    if (lv.form == 0 && (rc = live_open(e, lv, streams, n, hop, reassign, 1, n_high, split))) return rc;
-    const int S = lv.S, R = e->cfg.rows;
+    if (lv.g.form == 0 && (rc = live_open(e, lv, streams, n, hop, reassign, 1, n_high, split))) return rc;
     // the frames: read by the kernel where they are when the caller's block is page-locked, else staged
     const float* src = reinterpret_cast<const float*>(device_view(frames));
     if (!src) {
-        if ((rc = pinned_grow(e, (void**)&lv.h_fresh, &lv.fresh_bytes, (size_t)S * n * 4))) return rc;
-        std::memcpy(lv.h_fresh, frames, (size_t)S * n * 4);
+        if ((rc = pinned_grow(e, (void**)&lv.h_fresh, &lv.fresh_bytes, lv.g.fresh_bytes()))) return rc;
+        std::memcpy(lv.h_fresh, frames, lv.g.fresh_bytes());
         src = lv.h_fresh;
     }
-    float* ddb = reinterpret_cast<float*>(device_view(out_db));
-    uint8_t* drgba = reinterpret_cast<uint8_t*>(device_view(out_rgba));
-    const bool stage_db = out_db && !ddb, stage_rgba = out_rgba && !drgba;
-    if ((stage_db || stage_rgba) && (rc = live_out_staging(e, lv, stage_db, stage_rgba, 1))) return rc;
-    if (stage_db) ddb = lv.h_odb;
-    if (stage_rgba) drgba = lv.h_orgba;
-    LiveStream* desc = reinterpret_cast<LiveStream*>(lv.h_desc);
-    for (int s = 0; s < S; ++s) desc[s] = LiveStream{lv.fed[s], lv.fed[s] * (long long)hop, 1, 0, 0, 0};
-    if ((rc = live_launch(e, lv, src, n, 1, false, ddb, drgba, 1, 1, true))) return live_abandon(e, lv, rc);
-    if (hipStreamSynchronize(e->stream) != hipSuccess) return live_abandon(e, lv, fail(e, EMSPEC_ERR_HIP, "hipStreamSynchronize failed"));
-    if (stage_db) std::memcpy(out_db, lv.h_odb, (size_t)S * R * 4);
-    if (stage_rgba) std::memcpy(out_rgba, lv.h_orgba, (size_t)S * R * 4);
-    for (int s = 0; s < S; ++s) {
-        const int64_t c = lv.fed[s] - lv.D;
-        lv.fed[s] += 1;
-        if (c >= 0) lv.emitted[s] = c + 1;
-        if (out_columns) out_columns[s] = c >= 0 ? c : -1;
-    }
+    LiveDest d;   // (one column per stream: each output in place or staged on its own)
+    if ((rc = live_dest(e, lv, out_db, out_rgba, 1, d))) return rc;
+    live_frame_fill(lv.g, lv.c, lv.desc());
+    if ((rc = live_launch(e, lv, src, n, 1, false, d.db, d.rgba, 1, 1, true))) return live_abandon(e, lv, rc);
+    if ((rc = live_sync(e, lv))) return rc;
+    live_copy_back(lv, d, out_db, out_rgba, e->cfg.rows);
+    live_frame_commit(lv.g, lv.c, out_columns);
     return EMSPEC_OK;
 }
 
@@ -352,47 +358,22 @@ int flush_impl(emspec_engine* e, LiveState& lv, float* out_db, uint8_t* out_rgba
     if (!e) return EMSPEC_ERR_INVALID_ARG;
     if (e->time_reduce > 1) return fail(e, EMSPEC_ERR_STATE, kNoLiveReduce);
     if (rows != e->cfg.rows) return fail(e, EMSPEC_ERR_INVALID_ARG, "rows does not match the engine configuration");
-    bool any = false;
-    for (int s = 0; s < lv.S; ++s) any = any || lv.emitted[s] < lv.fed[s];
-    if (lv.form == 0 || !any) return fail(e, EMSPEC_ERR_STATE, "no pending column");
+    if (lv.g.form == 0 || !lv.c.any_pending()) return fail(e, EMSPEC_ERR_STATE, "no pending column");
     HIPCHK(e, hipSetDevice(e->device));
-    const int S = lv.S, R = e->cfg.rows;
     int rc;
-    float* ddb = reinterpret_cast<float*>(device_view(out_db));
-    uint8_t* drgba = reinterpret_cast<uint8_t*>(device_view(out_rgba));
-    const bool stage_db = out_db && !ddb, stage_rgba = out_rgba && !drgba;
-    if ((stage_db || stage_rgba) && (rc = live_out_staging(e, lv, stage_db, stage_rgba, lv.mmax))) return rc;
-    if (stage_db) ddb = lv.h_odb;
-    if (stage_rgba) drgba = lv.h_orgba;
-    LiveStream* desc = reinterpret_cast<LiveStream*>(lv.h_desc);
-    for (int s = 0; s < S; ++s) {
-        const bool has = lv.emitted[s] < lv.fed[s];
-        // (a stream with nothing pending emits the empty column: "column -1")
-        desc[s] = LiveStream{has ? lv.emitted[s] + lv.D : (long long)lv.D - 1, 0, 0, 0, 0, 1};
-    }
-    if ((rc = live_launch(e, lv, nullptr, 0, 0, true, ddb, drgba, 1, 1, true))) return live_abandon(e, lv, rc);
-    if (hipStreamSynchronize(e->stream) != hipSuccess) return live_abandon(e, lv, fail(e, EMSPEC_ERR_HIP, "hipStreamSynchronize failed"));
-    if (stage_db) std::memcpy(out_db, lv.h_odb, (size_t)S * R * 4);
-    if (stage_rgba) std::memcpy(out_rgba, lv.h_orgba, (size_t)S * R * 4);
-    for (int s = 0; s < S; ++s) {
-        const bool has = lv.emitted[s] < lv.fed[s];
-        if (out_columns) out_columns[s] = has ? lv.emitted[s] : -1;
-        if (has) lv.emitted[s] += 1;
-    }
+    LiveDest d;   // (as emspec_columns; the staging blocks are sized for a push's mmax columns at once)
+    if ((rc = live_dest(e, lv, out_db, out_rgba, lv.g.mmax, d))) return rc;
+    live_flush_fill(lv.g, lv.c, lv.desc());
+    if ((rc = live_launch(e, lv, nullptr, 0, 0, true, d.db, d.rgba, 1, 1, true))) return live_abandon(e, lv, rc);
+    if ((rc = live_sync(e, lv))) return rc;
+    live_copy_back(lv, d, out_db, out_rgba, e->cfg.rows);
+    live_flush_commit(lv.g, lv.c, out_columns);
     return EMSPEC_OK;
 }
 
 int64_t push_columns_impl(const emspec_engine* e, const LiveState& lv, int64_t count, int32_t n, int32_t hop, int32_t reassign) {
     if (!e || count < 0 || !supported_fft(n) || hop < 1 || hop > n) return -1;
-    const int D = latency(n, hop, reassign ? 1 : 0);
-    auto cols = [&](int64_t fed, int64_t seen) {
-        const int64_t after = frames_after(seen + count, n, hop);
-        return (after > D ? after - D : 0) - (fed > D ? fed - D : 0);
-    };
-    if (lv.form != 2) return cols(0, 0);
-    int64_t most = 0;
-    for (int s = 0; s < lv.S; ++s) most = std::max(most, cols(lv.fed[s], lv.seen[s]));
-    return most;
+    return live_push_columns(lv.g, lv.c, count, n, hop, reassign);
 }
 
 // (n_high != 0: the multi-resolution form - n is n_low; max_columns then bounds what the block may complete whether or not an
@@ -410,10 +391,10 @@ int push_impl(emspec_engine* e, LiveState& lv, const void* block, int32_t stream
     reassign = reassign ? 1 : 0;
     int rc = live_check(e, lv, streams, n, hop, reassign, rows, 2, n_high, split);
     if (rc) return rc;
-    if (lv.form != 0 && (fmt != nullptr) != (lv.pcm_views != 0))
-        return fail(e, EMSPEC_ERR_STATE, lv.pcm_views ? "the live session is a PCM one (emspec_push_samples_pcm); call emspec_reset() before a float call"
+    if (lv.g.form != 0 && (fmt != nullptr) != (lv.pcm.views != 0))
+        return fail(e, EMSPEC_ERR_STATE, lv.pcm.views ? "the live session is a PCM one (emspec_push_samples_pcm); call emspec_reset() before a float call"
                                                       : "the live session is a float one; call emspec_reset() before a PCM call");
-    if (lv.form != 0 && fmt && !pcm_same_format(*fmt, lv.pcm_fmt))
+    if (lv.g.form != 0 && fmt && !pcm_same_format(*fmt, lv.pcm.fmt))
         return fail(e, EMSPEC_ERR_STATE, "the PCM format changed mid-stream; call emspec_reset() first");
     if (max_columns < 0) return fail(e, EMSPEC_ERR_INVALID_ARG, "max_columns must be >= 0");
     const int64_t expect = push_columns_impl(e, lv, count, n, hop, reassign);
@@ -421,84 +402,46 @@ int push_impl(emspec_engine* e, LiveState& lv, const void* block, int32_t stream
         return fail(e, EMSPEC_ERR_INVALID_ARG, "output holds fewer columns than this block completes (" + std::to_string(expect) +
                                                    "); size it with emspec_push_columns() / emspec_push_columns_multi()");
     HIPCHK(e, hipSetDevice(e->device));
-    if (lv.form == 0) {
+    if (lv.g.form == 0) {
         if ((rc = live_open(e, lv, streams, n, hop, reassign, 2, n_high, split, fmt != nullptr))) return rc;
         if (fmt && (rc = live_open_pcm(e, lv, *fmt))) { live_forget(lv); return rc; }
     }
-    const int S = lv.S, R = e->cfg.rows, D = lv.D;
-    float* ddb = reinterpret_cast<float*>(device_view(out_db));
-    uint8_t* drgba = reinterpret_cast<uint8_t*>(device_view(out_rgba));
-    // page-locked outputs are written in place ([S][max_columns][rows]); others through a staging block per launch
-    const bool direct = (!out_db || ddb) && (!out_rgba || drgba) && max_columns <= 0x7fffffff;
-    if (!direct) {
-        if ((rc = live_out_staging(e, lv, out_db != nullptr, out_rgba != nullptr, lv.mmax))) return rc;
-        ddb = out_db ? lv.h_odb : nullptr;
-        drgba = out_rgba ? lv.h_orgba : nullptr;
-    }
-    std::vector<int64_t> produced(S, 0), first(S, -1), nc(S, 0);
-    std::vector<int> M(S, 0);
-    LiveStream* desc = reinterpret_cast<LiveStream*>(lv.h_desc);
-    int64_t used = 0;
+    const LiveGeometry& g = lv.g;
+    // Unlike the one-column calls, a push decides for both outputs together: page-locked outputs are written in place
+    // ([S][max_columns][rows], every round at the columns produced so far) only when BOTH are page-locked and max_columns fits
+    // the launch's int; otherwise both go through a staging block of mmax columns per launch.
+    LiveDest d;
+    if ((rc = live_dest(e, lv, out_db, out_rgba, g.mmax, d, true, max_columns <= 0x7fffffff))) return rc;
+    LivePush p(g.S);
     bool inflight = false;
-    while (used < count) {
+    while (p.used < count) {
         // the kernel of the previous round reads the staging block and the descriptors: wait before refilling them
-        if (inflight) {
-            if (hipStreamSynchronize(e->stream) != hipSuccess) return live_abandon(e, lv, fail(e, EMSPEC_ERR_HIP, "hipStreamSynchronize failed"));
-            inflight = false;
-        }
-        int maxpend = 0;
-        for (int s = 0; s < S; ++s) maxpend = std::max(maxpend, lv.pend[s]);
-        const int64_t take = std::min<int64_t>(count - used, lv.cap - maxpend);
+        if (inflight && (rc = live_sync(e, lv))) return rc;
+        inflight = false;
+        live_push_take(g, lv.c, p, count);
         // (a PCM session: the raw frames of each source; every stream has the same pend - emspec_reset_stream sees to it)
-        for (int i = 0; fmt && i < S / lv.pcm_views; ++i)
-            std::memcpy(lv.h_raw + ((size_t)i * lv.cap + maxpend) * fb, static_cast<const char*>(block) + (size_t)i * stride + (size_t)used * fb,
-                        (size_t)take * fb);
-        for (int s = 0; s < S; ++s) {
-            if (!fmt) std::memcpy(lv.h_fresh + (size_t)s * lv.cap + lv.pend[s], samples + (size_t)s * stride + used, (size_t)take * 4);
-            lv.pend[s] += (int)take;
-            lv.seen[s] += take;
-        }
-        used += take;
-        int mx = 0;
-        for (int s = 0; s < S; ++s) {
-            M[s] = (int)(frames_after(lv.seen[s], n, hop) - lv.fed[s]);
-            mx = std::max(mx, M[s]);
-        }
-        // A block that completes no frame (an audio worklet hands over 128 samples at a time) only joins the staging block:
-        // no launch, no synchronisation until a frame is due or the block is full.
-        if (mx == 0 && maxpend + take < lv.cap) continue;
-        for (int s = 0; s < S; ++s) {
-            const int64_t c0 = std::max<int64_t>(lv.fed[s] - D, 0), c1 = lv.fed[s] + M[s] - D;
-            nc[s] = c1 > c0 ? c1 - c0 : 0;
-            desc[s] = LiveStream{lv.fed[s], lv.newbase[s], M[s], lv.pend[s], direct ? (int)produced[s] : 0, 0};
-            if (nc[s] > 0 && first[s] < 0) first[s] = c0;
-        }
+        for (int i = 0; fmt && i < g.S / lv.pcm.views; ++i)
+            std::memcpy(lv.h_raw + g.raw_at(i, p.maxpend, fb), static_cast<const char*>(block) + (size_t)i * stride + (size_t)p.used * fb,
+                        (size_t)p.take * fb);
+        for (int s = 0; !fmt && s < g.S; ++s)
+            std::memcpy(lv.h_fresh + g.fresh_at(s, lv.c.pend[s]), samples + (size_t)s * stride + p.used, (size_t)p.take * 4);
+        if (!live_push_round(g, lv.c, p, d.direct, lv.desc())) continue;   // no frame is due and the staging block has room
         if (fmt && (rc = live_decode_pending(e, lv))) return live_abandon(e, lv, rc);
-        if ((rc = live_launch(e, lv, fmt ? lv.d_fresh : lv.h_fresh, lv.cap, mx, false, ddb, drgba, direct ? (int)max_columns : lv.mmax,
-                              direct ? (int)std::min<int64_t>(std::max<int64_t>(expect, 1), 0x7fffffff) : lv.mmax, false)))
+        if ((rc = live_launch(e, lv, fmt ? lv.d_fresh : lv.h_fresh, g.cap, p.mx, false, d.db, d.rgba, d.direct ? (int)max_columns : g.mmax,
+                              d.direct ? (int)std::min<int64_t>(std::max<int64_t>(expect, 1), 0x7fffffff) : g.mmax, false)))
             return live_abandon(e, lv, rc);
         inflight = true;
-        if (!direct && (out_db || out_rgba)) {
-            if (hipStreamSynchronize(e->stream) != hipSuccess) return live_abandon(e, lv, fail(e, EMSPEC_ERR_HIP, "hipStreamSynchronize failed"));
+        if (d.stage_db || d.stage_rgba) {
+            if ((rc = live_sync(e, lv))) return rc;
             inflight = false;
-            for (int s = 0; s < S; ++s) {
-                if (nc[s] <= 0) continue;
-                const size_t from = (size_t)s * lv.mmax * R, to = ((size_t)s * max_columns + produced[s]) * R;
-                if (out_db) std::memcpy(out_db + to, lv.h_odb + from, (size_t)nc[s] * R * 4);
-                if (out_rgba) std::memcpy(out_rgba + to * 4, lv.h_orgba + from * 4, (size_t)nc[s] * R * 4);
-            }
+            live_copy_back(lv, d, out_db, out_rgba, e->cfg.rows, &p, max_columns);
         }
-        for (int s = 0; s < S; ++s) {
-            lv.newbase[s] = lv.seen[s];
-            lv.pend[s] = 0;
-            lv.fed[s] += M[s];
-            if (nc[s] > 0) { produced[s] += nc[s]; lv.emitted[s] = lv.fed[s] - D; }
-        }
+        live_push_commit(g, lv.c, p);
     }
-    if (inflight && hipStreamSynchronize(e->stream) != hipSuccess) return live_abandon(e, lv, fail(e, EMSPEC_ERR_HIP, "hipStreamSynchronize failed"));
-    for (int s = 0; s < S; ++s) {
-        if (out_counts) out_counts[s] = produced[s];
-        if (out_first_columns) out_first_columns[s] = first[s];
+    if (inflight && (rc = live_sync(e, lv))) return rc;
+    for (int s = 0; s < g.S; ++s) {
+        if (out_counts) out_counts[s] = p.produced[s];
+        if (out_first_columns) out_first_columns[s] = p.first[s];
     }
     return EMSPEC_OK;
 }
@@ -519,17 +462,14 @@ namespace emspec {
 void live_destroy(emspec_engine* e) { live_free(e->live); live_free(e->one); }
 void live_reset(emspec_engine* e) { live_forget(e->live); live_forget(e->one); }
 bool live_pending(const emspec_engine* e) {
-    for (const LiveState* lv : {&e->live, &e->one})
-        for (int s = 0; s < lv->S; ++s)
-            if (lv->fed[s] > lv->emitted[s]) return true;
-    return false;
+    return e->live.c.any_pending() || e->one.c.any_pending();
 }
 }  // namespace emspec
 
 extern "C" {
 
 // ---- the live multi-stream session (e->live)
-int32_t emspec_live_streams(const emspec_engine* e) { return e ? e->live.S : 0; }
+int32_t emspec_live_streams(const emspec_engine* e) { return e ? e->live.g.S : 0; }
 
 int emspec_columns(emspec_engine* e, const float* frames, int32_t streams, int32_t n, int32_t hop, int32_t reassign,
                    float* out_db, uint8_t* out_rgba, int32_t rows, int64_t* out_columns) {
@@ -582,12 +522,17 @@ int emspec_push_samples_multires(emspec_engine* e, const float* samples, int32_t
 }
 
 // ---- the live session fed raw interleaved frames (include/emspec.h, PCM front end): sources * views streams
-int emspec_push_samples_pcm(emspec_engine* e, const void* block, const emspec_pcm_format* fmt, int32_t sources, int64_t count,
-                            int64_t stride_bytes, int32_t n, int32_t hop, int32_t reassign, float* out_db, uint8_t* out_rgba,
-                            int32_t rows, int64_t max_columns, int64_t* out_counts, int64_t* out_first_columns) {
+static int pcm_entry_check(emspec_engine* e, const emspec_pcm_format* fmt, int32_t sources) {
     if (!e) return EMSPEC_ERR_INVALID_ARG;
     if (const char* why = pcm_format_error(fmt)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
     if (sources < 1 || sources > 65535) return fail(e, EMSPEC_ERR_INVALID_ARG, "sources * views (the session's streams) must be in 1..65535");
+    return EMSPEC_OK;
+}
+
+int emspec_push_samples_pcm(emspec_engine* e, const void* block, const emspec_pcm_format* fmt, int32_t sources, int64_t count,
+                            int64_t stride_bytes, int32_t n, int32_t hop, int32_t reassign, float* out_db, uint8_t* out_rgba,
+                            int32_t rows, int64_t max_columns, int64_t* out_counts, int64_t* out_first_columns) {
+    if (int rc = pcm_entry_check(e, fmt, sources)) return rc;
     return push_impl(e, e->live, block, sources * fmt->views, count, stride_bytes, n, hop, reassign, out_db, out_rgba, rows, max_columns,
                      out_counts, out_first_columns, 0, 0, fmt);
 }
@@ -596,9 +541,7 @@ int emspec_push_samples_pcm_multires(emspec_engine* e, const void* block, const 
                                      int64_t count, int64_t stride_bytes, int32_t n_low, int32_t n_high, int32_t hop,
                                      int32_t split_row, int32_t reassign, float* out_db, uint8_t* out_rgba, int32_t rows,
                                      int64_t max_columns, int64_t* out_counts, int64_t* out_first_columns) {
-    if (!e) return EMSPEC_ERR_INVALID_ARG;
-    if (const char* why = pcm_format_error(fmt)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
-    if (sources < 1 || sources > 65535) return fail(e, EMSPEC_ERR_INVALID_ARG, "sources * views (the session's streams) must be in 1..65535");
+    if (int rc = pcm_entry_check(e, fmt, sources)) return rc;
     if (const char* why = multires_shape_error(n_low, n_high, hop)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
     return push_impl(e, e->live, block, sources * fmt->views, count, stride_bytes, n_low, hop, reassign, out_db, out_rgba, rows,
                      max_columns, out_counts, out_first_columns, n_high, split_row, fmt);
@@ -654,20 +597,17 @@ int emspec_debug_live_stamps(emspec_engine* e, uint64_t* stamps) {
 int emspec_reset_stream(emspec_engine* e, int32_t stream) {
     if (!e) return EMSPEC_ERR_INVALID_ARG;
     LiveState& lv = e->live;
-    if (lv.form == 0) return fail(e, EMSPEC_ERR_STATE, "no live session");
-    if (stream < 0 || stream >= lv.S) return fail(e, EMSPEC_ERR_INVALID_ARG, "stream out of range");
+    if (lv.g.form == 0) return fail(e, EMSPEC_ERR_STATE, "no live session");
+    if (stream < 0 || stream >= lv.g.S) return fail(e, EMSPEC_ERR_INVALID_ARG, "stream out of range");
     HIPCHK(e, hipSetDevice(e->device));
     if (int rc = live_pcm_drain(e, lv)) return rc;
-    const int Rl = lv.n_high ? lv.split : e->cfg.rows;
-    const size_t cellb = e->exact() ? 8 : 4, per = (size_t)lv.slots * Rl * cellb;
-    HIPCHK(e, hipMemsetAsync(reinterpret_cast<char*>(lv.d_cells) + (size_t)stream * per, 0, per, e->stream));
-    if (lv.n_high) {   // the short band's ring too
-        const size_t perh = (size_t)lv.slots_high * (e->cfg.rows - lv.split) * cellb;
-        HIPCHK(e, hipMemsetAsync(reinterpret_cast<char*>(lv.d_cells_high) + (size_t)stream * perh, 0, perh, e->stream));
-    }
-    if (lv.d_pstate)
-        HIPCHK(e, hipMemsetAsync(lv.d_pstate + (size_t)stream * (e->cfg.rows + 4), 0, (size_t)(e->cfg.rows + 4) * 4, e->stream));
-    lv.fed[stream] = 0; lv.emitted[stream] = 0; lv.seen[stream] = 0; lv.newbase[stream] = 0; lv.pend[stream] = 0;
+    const int R = e->cfg.rows;
+    const size_t cell = e->exact() ? 8 : 4, per = lv.g.ring_bytes(R, cell), perh = lv.g.ring_high_bytes(R, cell), perp = LiveGeometry::pstate_bytes(R);
+    HIPCHK(e, hipMemsetAsync(reinterpret_cast<char*>(lv.d_cells) + stream * per, 0, per, e->stream));
+    if (lv.g.n_high)   // the short band's ring too
+        HIPCHK(e, hipMemsetAsync(reinterpret_cast<char*>(lv.d_cells_high) + stream * perh, 0, perh, e->stream));
+    if (lv.d_pstate) HIPCHK(e, hipMemsetAsync(reinterpret_cast<char*>(lv.d_pstate) + stream * perp, 0, perp, e->stream));
+    lv.c.reset_stream(stream);
     return EMSPEC_OK;
 }
 

@@ -1,0 +1,239 @@
+// emspec_live_plan.h — internal: the host arithmetic of a streaming session (emspec_live.cpp): the descriptor the
+// kernels read per stream, the session's geometry with every byte size derived from it, the per-stream counters, and the steps
+// of each call that decide which column an output slot holds.  Integer arithmetic only.  No HIP, nothing of the engine:
+// tests/test_live_plan_cpu.py runs it through a stand-alone program (tests/cdriver/live_plan_driver.cpp) without a GPU.
+#pragma once
+#include "emspec_tables.h"
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <type_traits>
+#include <vector>
+
+namespace emspec {
+
+// ---- live multi-stream streaming (emspec_columns / emspec_push_samples_multi; live.hip.inc) ----
+// One launch serves S live streams: grid = (frames per stream + 1, S).  Workgroup (f, s) with f < frames[s] transforms
+// frame j0[s] + f of stream s and scatters it into that stream's column ring in HBM (device-scope atomics); the LAST of a
+// stream's workgroups to finish (an arrival counter per stream) finalises the columns the launch completed, straight into the
+// caller's (page-locked) output, and clears their ring slots.  Workgroup (gridDim.x - 1, s) moves the stream's new samples
+// from the page-locked staging block into its device sample ring for later launches.
+struct LiveStream {        // per stream and launch; read by the kernel from page-locked host memory
+    long long j0;          // absolute index of the stream's first frame in this launch (= frames fed so far)
+    long long newbase;     // absolute index of fresh[s][0]: samples below it are in the device sample ring
+    int frames;            // frames of this stream in this launch (0 .. gridDim.x - 1)
+    int newcount;          // samples in fresh[s] to move into the sample ring
+    int out_at;            // first column slot of the stream's output block this launch writes
+    int flush;             // != 0: no frames; finalise `flush` pending columns starting at column j0 - D (emspec_columns_flush)
+};
+// (the kernel reads it from page-locked memory and from the kernel arguments: the layout is part of the launch)
+static_assert(sizeof(LiveStream) == 32 && std::is_trivially_copyable<LiveStream>::value, "LiveStream: 32 bytes, copied as bytes");
+static_assert(offsetof(LiveStream, j0) == 0 && offsetof(LiveStream, newbase) == 8 && offsetof(LiveStream, frames) == 16 &&
+                  offsetof(LiveStream, newcount) == 20 && offsetof(LiveStream, out_at) == 24 && offsetof(LiveStream, flush) == 28,
+              "LiveStream: field offsets");
+
+// per-sample-block form: frames per stream and launch, at most - about 2,048 workgroups per launch, 8..64 per stream
+inline int live_frames_per_launch(int S) { return std::max(8, std::min(64, 2048 / std::max(1, S))); }
+// whole frames in `total` samples
+inline int64_t frames_after(int64_t total, int n, int hop) { return total >= n ? (total - n) / hop + 1 : 0; }
+
+// ---- the session's geometry: fixed by its first call ----
+struct LiveGeometry {
+    int S = 0, n = 0, hop = 0, reassign = -1, D = 0;
+    int form = 0;             // 0 none, 1 per-frame (emspec_columns), 2 per-sample-block (emspec_push_samples_multi)
+    int mmax = 0;             // frames per stream and launch, at most
+    int slots = 0;            // column-ring slots per stream: 2 D + mmax
+    int64_t cap = 0;          // samples per stream the staging block holds (form 1: n; form 2: mmax * hop)
+    int ring_mask = 0;        // device sample ring per stream: ring_mask + 1 >= n + cap samples, a power of two (form 2)
+    // multi-resolution session (emspec_columns_multires / emspec_push_samples_multires): n / D / slots are the
+    // long band's (rows [0, split) at n_low); the short band (rows [split, R) at n_high) has its own column ring, indexed by the
+    // emitted column.  Its frame count follows the long band's: 0 while fed is 0, fed + 2 shift after.
+    int n_high = 0, split = 0, shift = 0, D_high = 0;   // n_high == 0: a single-resolution session
+    int slots_high = 0;       // mmax + shift + D + D_high
+
+    // rows of the long band's ring / of the short band's, of an engine with R rows
+    int rows_low(int R) const { return n_high ? split : R; }
+    int rows_high(int R) const { return n_high ? R - split : 0; }
+    // Every size below is in bytes.  Column rings, per stream, `cell` bytes per cell (FAST 4, EXACT 8): [slots][rows]
+    size_t ring_bytes(int R, size_t cell) const { return (size_t)slots * rows_low(R) * cell; }
+    size_t ring_high_bytes(int R, size_t cell) const { return (size_t)slots_high * rows_high(R) * cell; }
+    size_t rings_bytes(int R, size_t cell) const { return (size_t)S * ring_bytes(R, cell); }             // ... of all S streams
+    size_t rings_high_bytes(int R, size_t cell) const { return (size_t)S * ring_high_bytes(R, cell); }
+    size_t sring_bytes() const { return (size_t)S * ((size_t)ring_mask + 1) * 4; }   // [S][ring_mask + 1] float32
+    size_t done_bytes() const { return (size_t)S * 4 * (n_high ? 2 : 1); }           // arrival counters, one set per band
+    size_t desc_bytes() const { return (size_t)S * sizeof(LiveStream); }
+    size_t fresh_bytes() const { return (size_t)S * cap * 4; }                       // staging samples [S][cap] float32
+    size_t decoded_bytes() const { return fresh_bytes(); }                           // PCM session: the same block on the device
+    size_t raw_bytes(int views, int frame_bytes) const { return (size_t)(S / views) * cap * frame_bytes; }   // [sources][cap] frames
+    size_t raw_stride(int frame_bytes) const { return (size_t)cap * frame_bytes; }                           // ... one source's
+    size_t out_bytes(int R, int64_t cols) const { return (size_t)S * cols * R * 4; }  // [S][cols][R] float32 or RGBA8
+    // ... in it, the CELL (4 bytes) where column `col` of stream s starts, and the bytes of `count` columns
+    static size_t out_cell(int R, int64_t cols, int s, int64_t col) { return ((size_t)s * cols + col) * R; }
+    static size_t columns_bytes(int R, int64_t count) { return (size_t)count * R * 4; }
+    static size_t pstate_bytes(int R) { return (size_t)(R + 4) * 4; }                 // post-process state, per stream
+    // where a stream's samples go in the staging block: float samples, or bytes of raw frames (per SOURCE) of a PCM session
+    size_t fresh_at(int s, int pend) const { return (size_t)s * cap + pend; }
+    size_t raw_at(int source, int pend, int frame_bytes) const { return ((size_t)source * cap + pend) * frame_bytes; }
+};
+
+// n_high != 0: a multi-resolution session (n = n_low; rows below `split` from n, the rest from n_high)
+inline LiveGeometry live_geometry(int S, int n, int hop, int reassign, int form, int n_high = 0, int split = 0) {
+    LiveGeometry g;
+    g.S = S; g.n = n; g.hop = hop; g.reassign = reassign; g.form = form;
+    g.D = latency(n, hop, reassign);
+    // The short band runs 2 shift frames ahead and its ring is indexed by the emitted column (its own column - shift).  A call
+    // that feeds long frames j .. j + m - 1 finds emitted columns >= j - D unfinalised, and its short frames, the last of them
+    // frame j + m - 1 + 2 shift = emitted column j + m - 1 + shift, add up to D_high columns further: m + shift + D + D_high
+    // columns are live at once (reassign on: D = D_high + shift, i.e. m + 2 shift + 2 D_high).
+    g.n_high = n_high;
+    g.split = n_high ? split : 0;
+    g.shift = n_high ? (n - n_high) / (2 * hop) : 0;
+    g.D_high = n_high ? latency(n_high, hop, reassign) : 0;
+    // (a staging block of at most 2^17 samples per stream: at a large hop fewer frames per launch instead of megabytes pinned)
+    g.mmax = form == 1 ? 1 : std::max(1, std::min(live_frames_per_launch(S), (1 << 17) / hop));
+    g.slots = 2 * g.D + g.mmax;
+    g.cap = form == 1 ? n : (int64_t)g.mmax * hop;
+    int ring = 1;
+    while (ring < n + g.cap) ring <<= 1;
+    g.ring_mask = ring - 1;
+    g.slots_high = n_high ? g.mmax + g.shift + g.D + g.D_high : 0;
+    return g;
+}
+
+// ---- per stream: frames fed, columns emitted, samples received, samples in the device ring, samples in the staging block ----
+struct LiveCounters {
+    std::vector<int64_t> fed, emitted, seen, newbase;
+    std::vector<int> pend;
+    void open(int S) { fed.assign(S, 0); emitted.assign(S, 0); seen.assign(S, 0); newbase.assign(S, 0); pend.assign(S, 0); }
+    void reset_stream(int s) { fed[s] = 0; emitted[s] = 0; seen[s] = 0; newbase[s] = 0; pend[s] = 0; }
+    int streams() const { return (int)fed.size(); }
+    // A flush emits columns that later frames would still have added to: the stream is at its end.
+    bool flushed(int s, int D) const { return emitted[s] > std::max<int64_t>(fed[s] - D, 0); }
+    bool pending(int s) const { return fed[s] > emitted[s]; }   // frames fed whose columns were not emitted yet
+    bool any_pending() const {
+        for (int s = 0; s < streams(); ++s)
+            if (pending(s)) return true;
+        return false;
+    }
+    // a PCM session keeps every stream's `pend` equal (the raw block is per source): that count
+    int pcm_staged() const { return pend[0]; }
+};
+
+// emspec_push_columns*: the most columns a block of `count` samples completes on any stream (no session of the block form: on a
+// fresh stream)
+inline int64_t live_push_columns(const LiveGeometry& g, const LiveCounters& c, int64_t count, int n, int hop, int reassign) {
+    const int D = latency(n, hop, reassign ? 1 : 0);
+    auto cols = [&](int64_t fed, int64_t seen) {
+        const int64_t after = frames_after(seen + count, n, hop);
+        return (after > D ? after - D : 0) - (fed > D ? fed - D : 0);
+    };
+    if (g.form != 2) return cols(0, 0);
+    int64_t most = 0;
+    for (int s = 0; s < g.S; ++s) most = std::max(most, cols(c.fed[s], c.seen[s]));
+    return most;
+}
+
+// ---- the descriptors of a launch ----
+// every stream in the same state: the descriptor goes into the kernel arguments
+inline bool live_uniform(const LiveStream* d, int S) {
+    for (int s = 1; s < S; ++s)
+        if (std::memcmp(&d[s], &d[0], sizeof(LiveStream)) != 0) return false;
+    return true;
+}
+// multi-resolution session: some stream's first frame, i.e. its short band's first 2 shift + 1
+inline bool live_priming(const LiveStream* d, int S) {
+    for (int s = 0; s < S; ++s)
+        if (d[s].j0 == 0 && d[s].frames > 0) return true;
+    return false;
+}
+
+// ---- emspec_columns: one frame per stream ----
+inline void live_frame_fill(const LiveGeometry& g, const LiveCounters& c, LiveStream* d) {
+    for (int s = 0; s < g.S; ++s) d[s] = LiveStream{c.fed[s], c.fed[s] * (long long)g.hop, 1, 0, 0, 0};
+}
+// after the launch: out_columns[s] (may be null) = the column stream s emitted, or -1
+inline void live_frame_commit(const LiveGeometry& g, LiveCounters& c, int64_t* out_columns) {
+    for (int s = 0; s < g.S; ++s) {
+        const int64_t col = c.fed[s] - g.D;
+        c.fed[s] += 1;
+        if (col >= 0) c.emitted[s] = col + 1;
+        if (out_columns) out_columns[s] = col >= 0 ? col : -1;
+    }
+}
+
+// ---- emspec_columns_flush: one pending column per stream ----
+inline void live_flush_fill(const LiveGeometry& g, const LiveCounters& c, LiveStream* d) {
+    for (int s = 0; s < g.S; ++s)   // (a stream with nothing pending emits the empty column: "column -1")
+        d[s] = LiveStream{c.pending(s) ? c.emitted[s] + g.D : (long long)g.D - 1, 0, 0, 0, 0, 1};
+}
+inline void live_flush_commit(const LiveGeometry& g, LiveCounters& c, int64_t* out_columns) {
+    for (int s = 0; s < g.S; ++s) {
+        const bool has = c.pending(s);
+        if (out_columns) out_columns[s] = has ? c.emitted[s] : -1;
+        if (has) c.emitted[s] += 1;
+    }
+}
+
+// ---- emspec_push_samples*: a block of `count` samples per stream, in rounds of at most one staging block ----
+struct LivePush {
+    std::vector<int64_t> produced, first, nc;   // per stream: columns so far, the first of them (-1: none), this round's
+    std::vector<int> M;                         // per stream: this round's frames
+    int64_t used = 0;                           // samples of the block taken so far
+    int64_t take = 0;                           // this round's samples per stream
+    int maxpend = 0;                            // the fullest stream's staged samples before the round (a PCM session: every stream's)
+    int mx = 0;                                 // the most frames any stream has in this round
+    explicit LivePush(int S) : produced(S, 0), first(S, -1), nc(S, 0), M(S, 0) {}
+};
+// step 1: how much of the block this round takes.  Stream s's samples are then copied to g.fresh_at(s, c.pend[s]) (a PCM
+// session: source i's frames to g.raw_at(i, p.maxpend, frame bytes)) from offset p.used of its block - before step 2.
+inline void live_push_take(const LiveGeometry& g, const LiveCounters& c, LivePush& p, int64_t count) {
+    p.maxpend = 0;
+    for (int s = 0; s < g.S; ++s) p.maxpend = std::max(p.maxpend, c.pend[s]);
+    p.take = std::min<int64_t>(count - p.used, g.cap - p.maxpend);
+}
+// step 2: the samples are staged; the round's frames, columns and descriptors (direct: the kernel writes the caller's block, at
+// the columns produced so far; else a staging block from 0).  false: no launch -
+// a block that completes no frame (an audio worklet hands over 128 samples at a time) only joins the staging block: no launch,
+// no synchronisation until a frame is due or the block is full.
+inline bool live_push_round(const LiveGeometry& g, LiveCounters& c, LivePush& p, bool direct, LiveStream* d) {
+    for (int s = 0; s < g.S; ++s) {
+        c.pend[s] += (int)p.take;
+        c.seen[s] += p.take;
+    }
+    p.used += p.take;
+    p.mx = 0;
+    for (int s = 0; s < g.S; ++s) {
+        p.M[s] = (int)(frames_after(c.seen[s], g.n, g.hop) - c.fed[s]);
+        p.mx = std::max(p.mx, p.M[s]);
+    }
+    if (p.mx == 0 && p.maxpend + p.take < g.cap) return false;
+    for (int s = 0; s < g.S; ++s) {
+        const int64_t c0 = std::max<int64_t>(c.fed[s] - g.D, 0), c1 = c.fed[s] + p.M[s] - g.D;
+        p.nc[s] = c1 > c0 ? c1 - c0 : 0;
+        d[s] = LiveStream{c.fed[s], c.newbase[s], p.M[s], c.pend[s], direct ? (int)p.produced[s] : 0, 0};
+        if (p.nc[s] > 0 && p.first[s] < 0) p.first[s] = c0;
+    }
+    return true;
+}
+// step 3: after the launch (and after the round's columns were copied out of a staging block: p.nc[s] of them to column
+// p.produced[s] of the caller's)
+inline void live_push_commit(const LiveGeometry& g, LiveCounters& c, LivePush& p) {
+    for (int s = 0; s < g.S; ++s) {
+        c.newbase[s] = c.seen[s];
+        c.pend[s] = 0;
+        c.fed[s] += p.M[s];
+        if (p.nc[s] > 0) { p.produced[s] += p.nc[s]; c.emitted[s] = c.fed[s] - g.D; }
+    }
+}
+
+// ---- PCM session: the staged samples into the device sample rings, no frame ----
+inline void live_drain_fill(const LiveGeometry& g, const LiveCounters& c, LiveStream* d) {
+    for (int s = 0; s < g.S; ++s) d[s] = LiveStream{c.fed[s], c.newbase[s], 0, c.pend[s], 0, 0};
+}
+inline void live_drain_commit(const LiveGeometry& g, LiveCounters& c) {
+    for (int s = 0; s < g.S; ++s) { c.newbase[s] = c.seen[s]; c.pend[s] = 0; }
+}
+
+}  // namespace emspec

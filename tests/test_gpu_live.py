@@ -402,3 +402,64 @@ def test_priming_block_with_null_outputs(max_columns, display, exact):
     if not display:
         odb, _ = _oracle(n, hop, True, pcm, exact, want=("db",))
         _same_db(primed, odb[:, 8:14], exact)
+
+
+def test_hop_blocks_one_block_and_irregular_blocks_give_the_same_bytes():
+    """The same samples of 3 streams (N = 1024, hop 256, reassigned, 90 frames) through emspec_push_samples_multi three ways, EXACT
+    mode (the sums do not depend on their order, so bytes must match): (i) one hop per call into page-locked outputs (written in
+    place), (ii) everything in one block into ordinary outputs (staged; the staging block holds 64 frames = 16,384 samples per
+    stream, so the call runs several rounds and copies each round's columns back), (iii) seeded irregular blocks of 1 .. 3,000
+    samples into outputs sized by emspec_push_columns_multi.  Then the flush.  Every column's dB bits and RGBA, the counts and
+    the first columns are the same."""
+    S, n, hop, frames = 3, 1024, 256, 90
+    L = n + hop * (frames - 1)
+    pcm = np.ascontiguousarray(synth.streams(S, L))
+    D = emspec.latency_columns(n, hop, True)
+    rng = np.random.default_rng(1024256)
+    irregular = []
+    while sum(irregular) < L:
+        irregular.append(int(min(rng.integers(1, 3001), L - sum(irregular))))
+    assert L > 16384 and len(irregular) > 8
+    pin_db, pin_rgba = emspec.PinnedArray((S, 1, 1024), np.float32), emspec.PinnedArray((S, 1, 1024, 4), np.uint8)
+
+    def session(blocks, pinned):
+        db_all = np.full((S, frames, 1024), np.nan, np.float32)
+        rgba_all = np.zeros((S, frames, 1024, 4), np.uint8)
+        nxt, first_seen = np.zeros(S, np.int64), np.full(S, -1, np.int64)
+        with emspec.Engine(mode=emspec.MODE_EXACT) as e:
+            a = 0
+            for cnt in blocks:
+                k = e.push_columns_multi(cnt, n, hop, True)
+                out = dict(db=pin_db.array, rgba=pin_rgba.array) if pinned else {}
+                assert k <= 1 or not pinned
+                db, rgba, counts, firsts = e.push_samples_multi(pcm, n, hop, True, want_rgba=True, count=cnt, offset=a, **out)
+                a += cnt
+                assert np.all(counts == k)
+                for s in range(S):
+                    c = int(counts[s])
+                    assert firsts[s] == (nxt[s] if c else -1)
+                    if c and first_seen[s] < 0:
+                        first_seen[s] = firsts[s]
+                    db_all[s, nxt[s]:nxt[s] + c], rgba_all[s, nxt[s]:nxt[s] + c] = db[s, :c], rgba[s, :c]
+                    nxt[s] += c
+            assert a == L
+            pushed = nxt.copy()
+            flushed = []
+            for _ in range(D):
+                db, rgba, cols = e.columns_flush(want_rgba=True)
+                flushed.append(cols.copy())
+                for s in range(S):
+                    db_all[s, cols[s]], rgba_all[s, cols[s]] = db[s], rgba[s]
+        return db_all, rgba_all, pushed, first_seen, np.stack(flushed)
+
+    try:
+        runs = [session([hop] * (L // hop), True), session([L], False), session(irregular, False)]
+    finally:
+        pin_db.close(); pin_rgba.close()
+    assert L % hop == 0
+    db0, rgba0, pushed0, first0, flushed0 = runs[0]
+    assert np.all(pushed0 == frames - D) and np.all(first0 == 0) and not np.isnan(db0).any()
+    assert np.array_equal(flushed0, np.stack([np.full(S, frames - D + i) for i in range(D)]))
+    for db, rgba, pushed, first, flushed in runs[1:]:
+        assert np.array_equal(db.view(np.uint32), db0.view(np.uint32)) and np.array_equal(rgba, rgba0)
+        assert np.array_equal(pushed, pushed0) and np.array_equal(first, first0) and np.array_equal(flushed, flushed0)

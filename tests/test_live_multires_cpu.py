@@ -107,7 +107,7 @@ def test_schedule_facts_hold_for_every_accepted_shape(reassign):
             for pattern in ([mmax] * (span // mmax + 1), [1] * span, [1, mmax, 0, 2 if mmax > 1 else 1] * (span // 4)):
                 pattern = [min(m, mmax) for m in pattern]
                 worst, shift, Dl, Dh = simulate(n_low, n_high, hop, reassign, pattern)
-                slots = mmax + shift + Dl + Dh          # emspec_live.cpp: live_open
+                slots = mmax + shift + Dl + Dh          # emspec_live_plan.h: live_geometry
                 if reassign:
                     assert slots == mmax + 2 * shift + 2 * Dh
                 # fact 2: the ring bound is never exceeded
