@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "emspec_seg_plan.h"
+
 namespace emspec {
 
 // Per-(N,hop,config) constants handed to every kernel by value.
@@ -27,19 +29,8 @@ struct PlanDev {
                          // engine's own second pipeline lane (emspec_batch): segments capped at 1,024 columns
 };
 
-// How a launch of a fused (walking) kernel cuts every stream into segments.
-//   uniform plan (short_last = 0): grid = (segments, streams); segment g covers columns [g * seglen, (g + 1) * seglen).
-//   shared-device plan (short_last = 1): grid = (streams, segments); segment g covers
-//     [g * seglen, (g + 1) * seglen) for g < nlong, then pieces of `tail` columns.  Workgroups are dispatched in linear
-//     block order, so with blockIdx.y = segment all streams' long segments start first and the launch ends on the
-//     short ones: when another kernel (a collective, the gather's pack / expand) holds some CUs and the workgroups no
-//     longer fill whole rounds, what is left over at the end is short.  Stream s takes the segment order rotated by s
-//     (long and short segments each among themselves).
-//   The uniform plan keeps round 1's dispatch order on purpose: with grid = (streams, segments) the N = 16384 kernel,
-//   which re-reads its 64 KB sample window every frame and relies on L2 for it, fetched 56 KB instead of 2.8 KB per
-//   column from beyond L2 (FETCH_SIZE, with and without the rotation; same speed).  The N = 4096 kernel reads every
-//   sample once and is unaffected (6.2 KB per column either way), and it is the one the N > 1 bench runs.
-struct SegPlan { int seglen; int nlong; int tail; int short_last; };
+// (SegPlan - how a launch of a fused (walking) kernel cuts every stream into segments - and the rules that choose it:
+// emspec_seg_plan.h)
 __device__ __forceinline__ bool seg_of_block(const SegPlan& sp, int64_t C, int& s, int64_t& c0, int64_t& c1) {
     if (!sp.short_last) {
         s = (int)blockIdx.y;

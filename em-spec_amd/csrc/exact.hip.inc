@@ -1220,58 +1220,17 @@ hipError_t launch_exact_frames(int n, const ExactPlanDev& pl, const float* pcm, 
 
 int exact_record_stride(int n) { return ex::rec_stride(n); }
 
-// How the records of (n, plan) are scattered: the walking ring whole (rl = 0), the walking ring with its rows < rl in a global
-// scratch (rl > 0; ebin_f32 = the plan's float32 edge table in DFT-bin units, on the host: the axis is served when at most 6 %
-// of the bins lie below row rl), or 16-column tiles (F = 0).
-struct ExactScatterPlan { int F, rl, seg; int64_t nseg; size_t lds, scratch_per_group; };
+// (ExactScatterPlan - walking ring whole, walking ring with its low rows in a global scratch, or tiles - and its segment rule:
+// emspec_seg_plan.h)
 static ExactScatterPlan exact_scatter_plan(int n, const ExactPlanDev& pl, int S, int64_t C, const float* ebin_f32) {
-    ExactScatterPlan sp{0, 0, 0, 0, 0, 0};
-    const int nch = ex::rec_stride(n) / 4;
-    int F = (1024 + nch - 1) / nch;
-    F = F < 1 ? 1 : (F > 8 ? 8 : F);
-    int rl = 0;
-    size_t wl = (size_t)(2 * pl.D + F) * pl.rows * 8 + 1024;
-    if (wl > 158 * 1024) {
-        // the row split: six frames per step (two barriers per step; 2D + 6 slots), as many rows in LDS as fit
-        if (!ebin_f32 || pl.rows % 4) return sp;
-        F = 6;
-        const int slots = 2 * pl.D + F;
-        const size_t mask = (size_t)slots * ((pl.rows + 31) >> 5) * 4;   // (sized for the worst case, rl = rows)
-        int rh = (int)(((size_t)158 * 1024 - 1024 - mask) / ((size_t)slots * 8)) & ~3;
-        if (rh >= pl.rows || rh < 64) return sp;
-        rl = pl.rows - rh;
-        if (!((double)ebin_f32[rl] / (double)(n / 2) <= 0.06)) return sp;
-        wl = (size_t)slots * rh * 8 + 1024 + mask;
-    }
-    // Segment length by ROUNDS of workgroups (round 5; exact_lr_seglen's reasoning): the ring takes most of a CU's LDS, so the
-    // workgroups of a launch run in rounds of (CUs x workgroups that fit a CU), and a launch costs rounds x (segment + its
-    // 2D-frame halo + pipeline fill).  The former rule (a fixed lower bound of 8D columns) gave configs[4]'s stream-chunks of
-    // five streams 62 segments each = 310 workgroups on 256 CUs: two rounds, the second a fifth full.
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, (int64_t)((size_t)160 * 1024 / wl)));
-    const int64_t places = device_cus() * per_cu;
-    const int64_t over = 2 * pl.D + F;
-    int64_t seg = (C + F - 1) / F * F;
-    double best = -1.0;
-    for (int r = 1; r <= 8; ++r) {
-        const int64_t ns = std::max<int64_t>(1, (int64_t)r * places / S);
-        int64_t sg = ((C + ns - 1) / ns + F - 1) / F * F;
-        sg = sg < F ? F : sg;
-        const int64_t nsg = (C + sg - 1) / sg;
-        const double rounds = std::ceil((double)S * (double)nsg / (double)places);
-        const double cost = rounds * (double)(sg + over);
-        if (best < 0.0 || cost < best * 0.999) { best = cost; seg = sg; }
-    }
-    sp.F = F; sp.rl = rl; sp.seg = (int)seg; sp.nseg = (C + seg - 1) / seg; sp.lds = wl;
-    sp.scratch_per_group = (size_t)(2 * pl.D + F) * rl * 8;
-    return sp;
+    return exact_scatter_plan(device_cus(), ex::rec_stride(n), n, pl.rows, pl.D, S, C, ebin_f32);
 }
 // bytes of low-row scratch a batch of S streams needs (0: none); the launcher runs the streams in groups that fit what it gets
 size_t exact_scatter_scratch_bytes(int n, const ExactPlanDev& pl, int S, int64_t C, const float* ebin_f32) {
     if (S <= 0 || C <= 0) return 0;
     const ExactScatterPlan sp = exact_scatter_plan(n, pl, S, C, ebin_f32);
     if (!sp.F || !sp.rl) return 0;
-    const int64_t groups = std::max<int64_t>(sp.nseg, std::min<int64_t>(2048, sp.nseg * (int64_t)S));
-    return (size_t)groups * sp.scratch_per_group;
+    return (size_t)scratch_groups(sp.nseg, S) * sp.scratch_per_group;
 }
 
 hipError_t launch_exact_tile_scatter(const long long* rec_q, const uint32_t* rec_key, int n, const ExactPlanDev& pl,
@@ -1282,11 +1241,11 @@ hipError_t launch_exact_tile_scatter(const long long* rec_q, const uint32_t* rec
     if (S > 65535) return hipErrorInvalidValue;
     {
         ExactScatterPlan sp = exact_scatter_plan(n, pl, S, C, ebin_f32);
-        if (sp.F && sp.rl && (!low || low_bytes < sp.scratch_per_group * (size_t)sp.nseg)) sp.F = 0;   // no scratch: tiles
+        if (sp.F && sp.rl && (!low || !scratch_holds_a_stream(low_bytes, sp.scratch_per_group, sp.nseg))) sp.F = 0;   // no scratch: tiles
         if (sp.F) {
             const hipError_t e = allow_max_lds(reinterpret_cast<const void*>(&ex::exact_walk_scatter_kernel));
             if (e != hipSuccess) return e;
-            const int64_t s_per = sp.rl ? std::max<int64_t>(1, std::min<int64_t>(S, (int64_t)(low_bytes / sp.scratch_per_group) / sp.nseg)) : S;
+            const int64_t s_per = streams_per_launch(S, sp.nseg, low_bytes, sp.scratch_per_group);
             int walk_abl = 0;
 #ifdef EMSPEC_DIAG
             if (const char* ev = getenv("EMSPEC_WALK_ABL")) walk_abl = atoi(ev);   // timing-only ablations
@@ -1305,15 +1264,12 @@ hipError_t launch_exact_tile_scatter(const long long* rec_q, const uint32_t* rec
             return hipSuccess;
         }
     }
-    int tile = (int)((150 * 1024) / ((size_t)pl.rows * 8));
-    tile = tile > 16 ? 16 : tile;
-    if (tile < 1) return hipErrorInvalidValue;
-    const size_t lds = (size_t)tile * pl.rows * 8 + 1024;
+    const TilePlan tp = tile_scatter_plan(pl.rows, C, 8, 16);
+    if (!tp.ok) return hipErrorInvalidValue;
     const hipError_t e = allow_max_lds(reinterpret_cast<const void*>(&ex::exact_tile_scatter_kernel));
     if (e != hipSuccess) return e;
-    const int64_t ntiles = (C + tile - 1) / tile;
-    hipLaunchKernelGGL(ex::exact_tile_scatter_kernel, dim3((unsigned)ntiles, (unsigned)S), dim3(1024), lds, st, rec_q, rec_key,
-                       ex::rec_stride(n), pl.rows, pl.D, tile, m, reinterpret_cast<const uint32_t*>(lut), C, db,
+    hipLaunchKernelGGL(ex::exact_tile_scatter_kernel, dim3((unsigned)tp.ntiles, (unsigned)S), dim3(1024), tp.lds, st, rec_q, rec_key,
+                       ex::rec_stride(n), pl.rows, pl.D, tp.tile, m, reinterpret_cast<const uint32_t*>(lut), C, db,
                        reinterpret_cast<uint32_t*>(rgba), index);
     return hipGetLastError();
 }

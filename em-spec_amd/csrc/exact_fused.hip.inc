@@ -413,28 +413,10 @@ hipError_t launch_exact_fused(int n, const ExactPlanDev& pl, const ExactDbMap& m
 #ifndef EMSPEC_DIAG
     if (stamps || stamp_groups) return hipErrorNotSupported;
 #endif
-    // Segments as in launch_fused's exclusive-device plan: r = 1..4 rounds of workgroups, chosen by the fill of the last
-    // round times the share of a workgroup's frames that are not halo (2D per segment + 3 half-iterations of pipeline fill)
-    const int64_t ncu = device_cus();
-    const int64_t seg_min = std::max<int64_t>(64, 4 * pl.D);
-    double best = -1.0;
-    int64_t seg = std::max<int64_t>(seg_min, (C + 3) / 4);
-    for (int r = 1; r <= 4; ++r) {
-        int64_t ns = std::max<int64_t>(1, (int64_t)r * ncu / S);
-        ns = std::min<int64_t>(ns, std::max<int64_t>(1, (C + seg_min - 1) / seg_min));
-        const int64_t sl = (C + ns - 1) / ns;
-        ns = (C + sl - 1) / sl;
-        const double groups = (double)S * (double)ns;
-        const double rounds = std::ceil(groups / (double)ncu);
-        const double eff = groups / (rounds * (double)ncu) * (double)sl / ((double)sl + 2.0 * pl.D + 3.0);
-        if (eff > best * 1.002) { best = eff; seg = sl; }
-    }
-#ifdef EMSPEC_DIAG
-    if (const char* ev = getenv("EMSPEC_SEGLEN")) { const long v = atol(ev); if (v >= 2) seg = v; }
-#endif
-    seg = seg < 1 ? 1 : seg;
+    // segments: the rounds-by-efficiency choice with this kernel's floor (emspec_seg_plan.h)
+    const int64_t seg = exact_fused_seglen(device_cus(), S, C, pl.D, diag_seglen());
     const int64_t nseg = (C + seg - 1) / seg;
-    if (nseg > 65535 || seg > 0x3fffffff) return hipErrorInvalidValue;
+    if (!exact_fused_grid_ok(nseg, seg)) return hipErrorInvalidValue;
     const SegPlan sp{(int)seg, 1 << 30, (int)seg, 0};
     const int slots = exf::exact_fused_slots(pl.D);
     const size_t lds = exf::exact_fused_lds_bytes(pl.rows, slots);

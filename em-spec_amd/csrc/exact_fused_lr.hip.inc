@@ -606,39 +606,16 @@ int exact_fused_lr_low_rows(int n, const ExactPlanDev& pl) {
     return rl;
 }
 
-// Segments as in launch_exact_fused's exclusive-device plan: r = 1..4 rounds of workgroups, chosen by the fill of the last
-// round times the share of a workgroup's frames that are not halo (2D per segment + 3 half-iterations of pipeline fill)
+// segments: the rounds-by-efficiency choice with this kernel's floor and pipeline fill (emspec_seg_plan.h)
 static int64_t exact_lr_seglen(int n, const ExactPlanDev& pl, int S, int64_t C) {
-    const int64_t ncu = device_cus();
-    const double fill = 3.0 * (double)(4096 / n);   // half-iterations of pipeline fill, in frames
-    const int64_t seg_min = std::max<int64_t>(16, 2 * pl.D);   // (as launch_fused: short batches are latency cases)
-    double best = -1.0;
-    int64_t seg = std::max<int64_t>(seg_min, (C + 3) / 4);
-    for (int r = 1; r <= 4; ++r) {
-        int64_t ns = std::max<int64_t>(1, (int64_t)r * ncu / S);
-        ns = std::min<int64_t>(ns, std::max<int64_t>(1, (C + seg_min - 1) / seg_min));
-        const int64_t sl = (C + ns - 1) / ns;
-        ns = (C + sl - 1) / sl;
-        const double groups = (double)S * (double)ns;
-        const double rounds = std::ceil(groups / (double)ncu);
-        const double eff = groups / (rounds * (double)ncu) * (double)sl / ((double)sl + 2.0 * pl.D + fill);
-        if (eff > best * 1.002) { best = eff; seg = sl; }
-    }
-#ifdef EMSPEC_DIAG
-    if (const char* ev = getenv("EMSPEC_SEGLEN")) { const long v = atol(ev); if (v >= 2) seg = v; }
-#endif
-    return seg < 1 ? 1 : seg;
+    return exact_lr_seglen(device_cus(), n, S, C, pl.D, diag_seglen());
 }
 
-// workgroups per launch are capped so that the low-row scratch stays small (launches of one stream are serialised anyway)
-static constexpr int64_t kExactLrMaxGroups = 2048;
 size_t exact_fused_lr_scratch_bytes(int n, const ExactPlanDev& pl, int rl, int S, int64_t C) {
     if (rl <= 0 || S <= 0 || C <= 0 || exact_lr_skip(n) < 0) return 0;
     const int slots = exl::lr_slots(exact_lr_skip(n), pl.D);
     const int64_t seg = exact_lr_seglen(n, pl, S, C);
-    const int64_t nseg = (C + seg - 1) / seg;
-    const int64_t groups = std::max<int64_t>(nseg, std::min<int64_t>(kExactLrMaxGroups, nseg * (int64_t)S));   // >= one stream's
-    return (size_t)groups * (size_t)slots * (size_t)rl * 8;
+    return (size_t)scratch_groups((C + seg - 1) / seg, S) * (size_t)slots * (size_t)rl * 8;
 }
 
 hipError_t launch_exact_fused_lr(int n, const ExactPlanDev& pl, const ExactDbMap& m, const uint8_t* lut, const float* pcm,
@@ -656,10 +633,9 @@ hipError_t launch_exact_fused_lr(int n, const ExactPlanDev& pl, const ExactDbMap
     const int slots = exl::lr_slots(skip, pl.D);
     const int rh = pl.rows - rl;
     if (rl < 0 || (rl & 3) || rh < 8 || exl::lds_bytes(pl.rows, rh, slots) > (size_t)160 * 1024) return hipErrorInvalidValue;
-    int64_t seg = exact_lr_seglen(n, pl, S, C);
-    seg = seg < 1 ? 1 : seg;
+    const int64_t seg = exact_lr_seglen(n, pl, S, C);
     const int64_t nseg = (C + seg - 1) / seg;
-    if (nseg > 65535 || seg > 0x3fffffff) return hipErrorInvalidValue;
+    if (!exact_fused_grid_ok(nseg, seg)) return hipErrorInvalidValue;
     if (stamp_groups) *stamp_groups = nseg * S;
 #ifdef EMSPEC_DIAG
     if ((stamps || stamp_groups) && !stamps) return hipSuccess;
@@ -672,14 +648,10 @@ hipError_t launch_exact_fused_lr(int n, const ExactPlanDev& pl, const ExactDbMap
 #ifdef EMSPEC_DIAG
     if (const char* ev = getenv("EMSPEC_EXACT_NOFAST")) fast = fast && ev[0] != '1';   // A/B aid
 #endif
-    // streams per launch: the low-row scratch holds kExactLrMaxGroups workgroups' worth ([group][slots][rl])
+    // streams per launch: as many as the low-row scratch has slices for ([group][slots][rl]; emspec_seg_plan.h)
     const size_t per_group = (size_t)slots * (size_t)rl * 8;
-    int64_t groups_cap = 65535 * (int64_t)65535;
-    if (rl > 0) {
-        if (!low || low_bytes < per_group * (size_t)nseg) return hipErrorInvalidValue;
-        groups_cap = (int64_t)(low_bytes / per_group);
-    }
-    const int64_t s_per = std::max<int64_t>(1, std::min<int64_t>(S, groups_cap / nseg));
+    if (rl > 0 && (!low || !scratch_holds_a_stream(low_bytes, per_group, nseg))) return hipErrorInvalidValue;
+    const int64_t s_per = streams_per_launch(S, nseg, low_bytes, per_group);
     if (stamps && s_per < S) return hipErrorNotSupported;   // the stamped build runs one launch
     hipError_t e;
     const void* fn = fast ? reinterpret_cast<const void*>(&exl::exact_fused4096_lr_kernel<false, true>)

@@ -62,9 +62,11 @@ static bool diag_no_fused() {
     if (off < 0) { const char* e = getenv("EMSPEC_NO_FUSED"); off = (e && e[0] == '1') ? 1 : 0; }   // A/B aid
     return off != 0;
 }
+static int64_t diag_seglen() { const char* e = getenv("EMSPEC_SEGLEN"); return e ? atol(e) : 0; }   // tuning aid: a segment length (>= 2)
 #else
 static constexpr int fused_variant() { return 0; }
 static constexpr bool diag_no_fused() { return false; }
+static constexpr int64_t diag_seglen() { return 0; }
 #endif
 
 // (the specialised FAST kernels serve the plans of emspec_plan_is_fast, emspec_device.h: reassignment ON, log-spaced rows, and
@@ -99,79 +101,17 @@ hipError_t launch_fused(int n, const PlanDev& pl, const DbMap& m, const uint8_t*
 #ifndef EMSPEC_DIAG
     if (stamps || stamp_groups) return hipErrorNotSupported;   // stamped builds live in libemspec_diag.so only
 #endif
-    // Segments: as long as possible (every segment recomputes a 2D-frame halo) while the launch still
-    // has at least one workgroup per CU, and - as long as segments stay >= 256 columns - about four:
-    //   nseg = max(ceil(CUs/S), min(floor(4 CUs/S), ceil(C/256)), ceil(C/1024)) per stream.
-    // Equal segments and a workgroup count near a multiple of the CU count keep the last round of workgroups
-    // full (256 CUs: 64 streams -> 16 x 1024 columns = 1024 workgroups; 16 streams -> 64 x 256 = 1024;
-    // 1 stream -> 256 x 64).  Several rounds matter when another kernel (an RCCL send/recv) holds a
-    // few CUs: a workgroup fills its CU, so a one-round launch would then take two rounds
-    // (tools/occupancy_probe.py: 8 chunks of 256 workgroups 13.4 -> 26.8 ms; 1024 per launch -> 16.3).
-    const int64_t ncu = device_cus();
-    int64_t nseg_want = (ncu + S - 1) / S;
-    const int64_t nseg_min = (C + 1023) / 1024;
-    // (rounded down: S x nseg <= 4 CUs, so stream counts that do not divide the CU count - 34, 36, 70 - never start a
-    // nearly empty fifth round)
-    const int64_t nseg_rounds = std::min<int64_t>(std::max<int64_t>(1, 4 * ncu / S), (C + 255) / 256);
-    if (nseg_want < nseg_rounds) nseg_want = nseg_rounds;
-    if (nseg_want < nseg_min) nseg_want = nseg_min;
-    int64_t seg = (C + nseg_want - 1) / nseg_want;
-    // shortest segment: as many columns as a segment has halo frames (2D; at least 16 / 32) - the choice below weighs halo
-    // against idle CUs, and a batch that cannot fill the chip with longer segments is a LATENCY case: a workgroup walks its
-    // segment frame after frame, so one stream of 4,081 columns took 0.18 ms as 64 segments of 64 (until late round 6 the
-    // floor: 64 columns; 8D at N = 16384) and takes 0.08 ms as 256 segments of 16.  The small-N kernel has a short reach and
-    // 4-8 frames per iteration: its floor was always low.
-    const int64_t seg_min = small_n ? std::max<int64_t>(16, 4 * pl.D) : (big_n ? std::max<int64_t>(32, 2 * pl.D) : std::max<int64_t>(16, 2 * pl.D));
-    seg = seg < seg_min ? seg_min : seg;
-    bool shared = pl.shared == 1;
+    // the segment plan (the four-round rule, the exclusive-device choice, the shared-device tail cut): emspec_seg_plan.h
+    int force_shared = -1;
 #ifdef EMSPEC_DIAG
-    if (const char* ev = getenv("EMSPEC_SHARED")) shared = ev[0] == '1';   // lets one GPU exercise the plan
+    if (const char* ev = getenv("EMSPEC_SHARED")) force_shared = ev[0] == '1';   // lets one GPU exercise the plan
 #endif
-    if (!shared) {
-        // The device is this launch's alone: nothing takes CUs away mid-launch, so the rule above (about four rounds of
-        // workgroups) only buys halo.  Choose the number of rounds r = 1..4 by what it costs: the fill of the last round
-        // (S x nseg workgroups over r x CUs) times the share of a workgroup's frames that are not halo (2D per segment
-        // + ~3 frames of pipeline fill), fewer rounds winning ties.  64 streams x 16,369 columns: 256 workgroups of 4,096
-        // columns instead of 1,024 of 1,024 (measured 9.21 vs 9.29 ms); 16 streams: 256 x 1,024 instead of 1,024 x 256.
-        double best = -1.0;
-        int64_t best_seg = seg;
-        for (int r = 1; r <= 4; ++r) {
-            int64_t ns = std::max<int64_t>(1, (int64_t)r * ncu / S);
-            ns = std::min<int64_t>(ns, std::max<int64_t>(1, (C + seg_min - 1) / seg_min));   // (ceil: 16,369 columns still make 256 segments of 64)
-            const int64_t sl = (C + ns - 1) / ns;
-            ns = (C + sl - 1) / sl;
-            const double groups = (double)S * (double)ns;
-            const double rounds = std::ceil(groups / (double)ncu);
-            const double eff = groups / (rounds * (double)ncu) * (double)sl / ((double)sl + 2.0 * pl.D + 3.0);
-            if (eff > best * 1.002) { best = eff; best_seg = sl; }
-        }
-        seg = best_seg < seg_min ? seg_min : best_seg;
-        if (pl.shared == 2 && seg > 1024) seg = 1024;   // two launches share the chip (emspec_batch's two-lane pipeline)
-    }
-#ifdef EMSPEC_DIAG
-    if (const char* ev = getenv("EMSPEC_SEGLEN")) {   // tuning aid
-        const long v = atol(ev);
-        if (v >= 2) seg = v;
-    }
-#endif
-    seg = (seg + 1) & ~(int64_t)1;
-    // Shared device (the engine has a communicator with other ranks, so RCCL transfers and the gather's pack / expand
-    // kernels take CUs while this launch runs): the last quarter of every stream is cut into quarter-length pieces and
-    // the grid becomes (streams, segments), so all long segments are dispatched first - the launch ends on short
-    // workgroups instead of on a mostly empty extra round (a workgroup fills its CU: losing 8 CUs turned 4 rounds into 5).
-    SegPlan sp{(int)seg, 1 << 30, (int)seg, 0};
-    int64_t nseg = (C + seg - 1) / seg;
-    if (shared) {
-        const int64_t tail = ((seg / 4) + 1) & ~(int64_t)1;
-        if (tail >= seg_min && nseg >= 2) {
-            const int64_t nlong = nseg - (nseg + 3) / 4;              // the last quarter (at least one segment) is cut finer
-            const int64_t rest = C - nlong * seg;
-            sp = SegPlan{(int)seg, (int)nlong, (int)tail, 1};
-            nseg = nlong + (rest + tail - 1) / tail;
-        }
-    }
-    if (nseg > 65535) return hipErrorInvalidValue;
-    const dim3 grid = sp.short_last ? dim3((unsigned)S, (unsigned)nseg) : dim3((unsigned)nseg, (unsigned)S), block(1024);
+    const FusedSegPlan fp = fused_seg_plan(device_cus(), S, C, pl.D, small_n ? FusedKind::small_n : (big_n ? FusedKind::big_n : FusedKind::n4096_8192),
+                                           pl.shared, force_shared, diag_seglen());
+    if (!fp.ok) return hipErrorInvalidValue;
+    const SegPlan sp = fp.sp;
+    const int64_t nseg = fp.nseg;
+    const dim3 grid = fp.streams_first ? dim3((unsigned)S, (unsigned)nseg) : dim3((unsigned)nseg, (unsigned)S), block(1024);
     if (stamp_groups) *stamp_groups = nseg * S;
     const uint32_t* l32 = reinterpret_cast<const uint32_t*>(lut);
     uint32_t* r32 = reinterpret_cast<uint32_t*>(rgba);

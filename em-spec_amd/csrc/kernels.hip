@@ -455,10 +455,9 @@ __global__ __launch_bounds__(1024) void tile_scatter_kernel(const uint2* __restr
 template <int CH>
 static hipError_t launch_tile_scatter_t(const uint2* records, int n, const PlanDev& pl, const DbMap& m, const uint8_t* lut,
                                         int S, int64_t C, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st,
-                                        int tile, size_t lds) {
-    const int64_t ntiles = (C + tile - 1) / tile;
-    return launch_k(tile_scatter_kernel<CH>, dim3((unsigned)ntiles, (unsigned)S), dim3(1024), lds, st, records, n / 2 + 1,
-                    pl.rows, pl.D, tile, m, reinterpret_cast<const uint32_t*>(lut), C, db, reinterpret_cast<uint32_t*>(rgba), index);
+                                        const TilePlan& tp) {
+    return launch_k(tile_scatter_kernel<CH>, dim3((unsigned)tp.ntiles, (unsigned)S), dim3(1024), tp.lds, st, records, n / 2 + 1,
+                    pl.rows, pl.D, tp.tile, m, reinterpret_cast<const uint32_t*>(lut), C, db, reinterpret_cast<uint32_t*>(rgba), index);
 }
 
 // ---------------------------------------------------------------------------
@@ -537,43 +536,28 @@ __global__ __launch_bounds__(1024) void walk_scatter_kernel(const uint2* __restr
 
 template <int CH>
 static hipError_t launch_walk_scatter_t(const uint2* records, int n, const PlanDev& pl, const DbMap& m, const uint8_t* lut,
-                                        int S, int64_t C, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st, int F,
-                                        size_t lds) {
-    int64_t seg = (S * C + 4 * device_cus() - 1) / (4 * device_cus());   // >= 4 workgroups per CU when there is enough work
-    seg = seg < 128 ? 128 : (seg > 1024 ? 1024 : seg);
-    seg = (seg + F - 1) / F * F;
-    const int64_t nseg = (C + seg - 1) / seg;
-    return launch_k(walk_scatter_kernel<CH>, dim3((unsigned)nseg, (unsigned)S), dim3(1024), lds, st, records, n / 2 + 1,
-                    pl.rows, pl.D, F, (int)seg, m, reinterpret_cast<const uint32_t*>(lut), C, db, reinterpret_cast<uint32_t*>(rgba), index);
+                                        int S, int64_t C, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st,
+                                        const ScatterPlan& sp) {
+    return launch_k(walk_scatter_kernel<CH>, dim3((unsigned)sp.nseg, (unsigned)S), dim3(1024), sp.walk_lds, st, records, n / 2 + 1,
+                    pl.rows, pl.D, sp.F, (int)sp.seg, m, reinterpret_cast<const uint32_t*>(lut), C, db, reinterpret_cast<uint32_t*>(rgba), index);
 }
 
 hipError_t launch_tile_scatter(const uint2* records, int n, const PlanDev& pl, const DbMap& m, const uint8_t* lut, int S,
                                int64_t C, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st) {
     if (S <= 0 || C <= 0) return hipSuccess;
     if (S > 65535) return hipErrorInvalidValue;
-    // chunk = consecutive bins per thread: wide enough that adjacent lanes rarely share a row
-    const int ch = n >= 8192 ? 32 : (n >= 2048 ? 8 : 4);
-    {   // walking ring when it fits: F frames per step so that F * chunks-per-frame covers the 1024 threads
-        const int nch = (n / 2 + 2 + ch - 1) / ch;
-        int F = (1024 + nch - 1) / nch;
-        F = F < 1 ? 1 : (F > 8 ? 8 : F);
-        const size_t wl = (size_t)(2 * pl.D + F) * pl.rows * 4 + 1024;
+    // the walking ring when it fits and pays, else tiles; chunk width, F, segments and LDS: emspec_seg_plan.h
 #ifdef EMSPEC_DIAG
-        static int use_walk = -1;
-        if (use_walk < 0) { const char* ev = getenv("EMSPEC_NO_WALK"); use_walk = (ev && ev[0] == '1') ? 0 : 1; }   // A/B aid
+    static int use_walk = -1;
+    if (use_walk < 0) { const char* ev = getenv("EMSPEC_NO_WALK"); use_walk = (ev && ev[0] == '1') ? 0 : 1; }   // A/B aid
 #else
-        constexpr bool use_walk = true;
+    constexpr bool use_walk = true;
 #endif
-        // measured: the walk wins when the tiles would re-read every record >= 2x (D >= 16: N=16384/512
-        // 1.04e7 vs 0.94e7 col/s); for small D the tiles' independent workgroups win (N=1024: 1.8e8 vs 1.6e8)
-        if (use_walk && pl.D >= 16 && wl <= 156 * 1024)
-            return pick_int<32, 8, 4>(ch, [&](auto CH) { return launch_walk_scatter_t<CH()>(records, n, pl, m, lut, S, C, db, rgba, index, st, F, wl); });
-    }
-    int tile = (int)((150 * 1024) / ((size_t)pl.rows * 4));
-    tile = tile > 32 ? 32 : tile;
-    if (tile < 1) return hipErrorInvalidValue;
-    const size_t lds = (size_t)tile * pl.rows * 4 + 1024;
-    return pick_int<32, 8, 4>(ch, [&](auto CH) { return launch_tile_scatter_t<CH()>(records, n, pl, m, lut, S, C, db, rgba, index, st, tile, lds); });
+    const ScatterPlan sp = scatter_plan(device_cus(), n, pl.rows, pl.D, S, C, use_walk != 0);
+    if (sp.walk)
+        return pick_int<32, 8, 4>(sp.ch, [&](auto CH) { return launch_walk_scatter_t<CH()>(records, n, pl, m, lut, S, C, db, rgba, index, st, sp); });
+    if (!sp.tiles.ok) return hipErrorInvalidValue;
+    return pick_int<32, 8, 4>(sp.ch, [&](auto CH) { return launch_tile_scatter_t<CH()>(records, n, pl, m, lut, S, C, db, rgba, index, st, sp.tiles); });
 }
 
 #ifdef EMSPEC_DIAG

@@ -190,6 +190,55 @@ def test_shared_device_segment_plan(n, hop, frames, S, monkeypatch):
     palette_close(out["index"], oidx)
 
 
+def test_launchers_use_the_planned_segments(tmp_path, monkeypatch):
+    """The launchers take their grids from emspec_seg_plan.h: the sizing call of emspec_debug_phase_cycles (cycles = NULL: no
+    kernel runs) reports segments x streams of the launch, and that is what the CPU driver of tests/test_seg_plan_cpu.py prints for
+    the same case and this device's CU count - N = 4096 at hop 256, 3 streams of 700 columns: the float32 kernel, the EXACT
+    no-parking kernel, and the float32 kernel's shared-device plan."""
+    import ctypes as C
+    import torch
+    import emspec
+    from test_seg_plan_cpu import build_driver, run_driver
+    import json
+    n, hop, S, cols, long_cols = 4096, 256, 3, 700, 16369
+    length = lambda c: n + (c - 1) * hop
+    exe = build_driver(tmp_path, "seg_plan_driver", sanitize=False)   # (sanitizer builds run in the CPU suite only)
+    torch.cuda.init()
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    pcm = torch.zeros(max(S * length(cols), length(long_cols)), dtype=torch.float32, device="cuda:0")   # (sized, never read)
+    lib = emspec.load(diag=True)
+    f = lib.emspec_debug_phase_cycles
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                  C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+
+    def sized(eng, streams, c):
+        groups, waves = C.c_int64(0), C.c_int32(0)
+        assert emspec.num_columns(length(c), n, hop) == c
+        assert f(eng._h, pcm.data_ptr(), streams, length(c), n, hop, 1, None, None, None, C.byref(groups), C.byref(waves)) == 0
+        return groups.value
+
+    def planned(*case):
+        (p,) = json.loads(run_driver(exe, *case))
+        assert p["ok"]
+        return p
+
+    monkeypatch.delenv("EMSPEC_SHARED", raising=False)
+    monkeypatch.delenv("EMSPEC_SEGLEN", raising=False)
+    fast, exact = emspec.Engine(diag=True), emspec.Engine(diag=True, mode=emspec.MODE_EXACT)
+    try:
+        assert sized(fast, S, cols) == planned("fused", ncu, S, cols, 8, 0, 0, -1, 0)["nseg"] * S
+        assert sized(exact, S, cols) == planned("exact_lr", ncu, n, S, cols, 8, 448, 0)["nseg"] * S
+        alone = planned("fused", ncu, 1, long_cols, 8, 0, 0, -1, 0)
+        monkeypatch.setenv("EMSPEC_SHARED", "1")
+        assert sized(fast, S, cols) == planned("fused", ncu, S, cols, 8, 0, 0, 1, 0)["nseg"] * S
+        # (a stream long enough that the shared-device plan cuts its tail finer: a count the exclusive plan does not give)
+        cut = planned("fused", ncu, 1, long_cols, 8, 0, 0, 1, 0)
+        assert cut["short_last"] and cut["nseg"] != alone["nseg"] and sized(fast, 1, long_cols) == cut["nseg"]
+    finally:
+        fast.close()
+        exact.close()
+
+
 def test_generic_records_path_still_serves_n16384_small_hop(engine):
     """N = 16384 at hop 256 needs 65 ring slots: not fused, stays on per-bin records + walk/tile scatter."""
     n, hop, frames = 16384, 256, 80
