@@ -285,6 +285,13 @@ __device__ __forceinline__ XBinF exact_core_fast(const ExactPlanDev& pl, const d
 static bool exact_fast_plan(const ExactPlanDev& pl) {
     return pl.reassign && pl.log_rows && pl.pfloor >= kFastMinFloor64 && pl.pmax <= kFastMaxPower64 && pl.rows >= 4;
 }
+// every EXACT launcher's FASTX: the plan qualifies (read per call; the diagnostic build can force the generic core)
+static bool exact_fast(const ExactPlanDev& pl) {
+#ifdef EMSPEC_DIAG
+    if (const char* ev = getenv("EMSPEC_EXACT_NOFAST")) if (ev[0] == '1') return false;   // A/B aid
+#endif
+    return exact_fast_plan(pl);
+}
 
 // stage "dB + colour" with a specified binary32 evaluation of 10 log10 (oracle/emspec_exact.c:eo_exact_db32 / eo_exact_sum32: the
 // same IEEE operations in the same order).  Round 5: binary32 - a binary64 vector instruction occupies the SIMD four times as
@@ -1127,95 +1134,53 @@ __global__ __launch_bounds__(1024) void exact_walk_scatter_kernel(const long lon
 
 }  // namespace ex
 
+// LDS of a frame kernel: its planes, and the binary64 row edges when they fit beside them (else read from global memory)
+static size_t exact_frames_lds(size_t planes, int rows, ExactSinks& sk) {
+    const size_t edges = (size_t)(rows + 1) * sizeof(double);
+    sk.edges_lds = planes + edges <= 160 * 1024 ? 1 : 0;
+    return planes + (sk.edges_lds ? edges : 0);
+}
+
+// (a live multi-stream launch, LIVE: nframes = the largest per-stream frame count + 1, the ingest workgroup)
 template <int LOG2N>
 static hipError_t launch_exact_frames_t(const ExactPlanDev& pl, const float* pcm, int64_t L, int S, int64_t frame0,
                                         int64_t nframes, const ExactSinks& sk, hipStream_t st) {
     constexpr int N = 1 << LOG2N;
-    const size_t planes = (size_t)2 * PaddedSize<N>::value * sizeof(double), edges = (size_t)(pl.rows + 1) * sizeof(double);
     ExactSinks sk2 = sk;
-    sk2.edges_lds = planes + edges <= 160 * 1024 ? 1 : 0;      // otherwise the row edges are read from global memory
-    const size_t lds = planes + (sk2.edges_lds ? edges : 0);
+    const size_t lds = exact_frames_lds((size_t)2 * PaddedSize<N>::value * sizeof(double), pl.rows, sk2);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    bool fast = ex::exact_fast_plan(pl);
-#ifdef EMSPEC_DIAG
-    if (const char* ev = getenv("EMSPEC_EXACT_NOFAST")) fast = fast && ev[0] != '1';   // A/B aid
-#endif
-    if (lds > 64 * 1024) {
-        const hipError_t e = allow_max_lds(fast ? reinterpret_cast<const void*>(&ex::exact_frames_kernel<LOG2N, true>)
-                                                : reinterpret_cast<const void*>(&ex::exact_frames_kernel<LOG2N, false>));
-        if (e != hipSuccess) return e;
-    }
-    if (sk.live.streams) {   // live multi-stream launch: nframes = the largest per-stream frame count + 1 (the ingest workgroup)
-        if (lds > 64 * 1024) {
-            const hipError_t e = allow_max_lds(fast ? reinterpret_cast<const void*>(&ex::exact_frames_kernel<LOG2N, true, true>)
-                                                    : reinterpret_cast<const void*>(&ex::exact_frames_kernel<LOG2N, false, true>));
-            if (e != hipSuccess) return e;
-        }
-        if (fast) hipLaunchKernelGGL((ex::exact_frames_kernel<LOG2N, true, true>), dim3((unsigned)nframes, (unsigned)S), dim3(N / 8), lds, st, pl, pcm, L, frame0, nframes, sk2);
-        else hipLaunchKernelGGL((ex::exact_frames_kernel<LOG2N, false, true>), dim3((unsigned)nframes, (unsigned)S), dim3(N / 8), lds, st, pl, pcm, L, frame0, nframes, sk2);
-        return hipGetLastError();
-    }
-    if (fast) hipLaunchKernelGGL((ex::exact_frames_kernel<LOG2N, true>), dim3((unsigned)nframes, (unsigned)S), dim3(N / 8), lds, st, pl, pcm, L, frame0, nframes, sk2);
-    else hipLaunchKernelGGL((ex::exact_frames_kernel<LOG2N, false>), dim3((unsigned)nframes, (unsigned)S), dim3(N / 8), lds, st, pl, pcm, L, frame0, nframes, sk2);
-    return hipGetLastError();
+    return pick_bool(ex::exact_fast(pl), [&](auto FASTX) { return pick_bool(sk.live.streams != nullptr, [&](auto LIVE) {
+        return launch_k(ex::exact_frames_kernel<LOG2N, FASTX(), LIVE()>, dim3((unsigned)nframes, (unsigned)S), dim3(N / 8), lds, st, pl, pcm, L, frame0, nframes, sk2);
+    }); });
 }
 
 hipError_t launch_exact_frames(int n, const ExactPlanDev& pl, const float* pcm, int64_t L, int S, int64_t frame0,
                                int64_t nframes, const ExactSinks& sk, hipStream_t st) {
     if (nframes <= 0 || S <= 0) return hipSuccess;
     if (S > 65535 || nframes > 0x7fffffffLL) return hipErrorInvalidValue;
-    switch (n) {
-        case 256: return launch_exact_frames_t<8>(pl, pcm, L, S, frame0, nframes, sk, st);
-        case 512: return launch_exact_frames_t<9>(pl, pcm, L, S, frame0, nframes, sk, st);
-        case 1024: return launch_exact_frames_t<10>(pl, pcm, L, S, frame0, nframes, sk, st);
-        case 2048: return launch_exact_frames_t<11>(pl, pcm, L, S, frame0, nframes, sk, st);
-        case 4096: {
-            // the persistent kernel when its 80 KB fit twice per CU (rows <= 1024) and the launch is a batch
-            const size_t lds = (size_t)2 * 4096 * 8 + (size_t)(7 * 64 + 7 * 8) * 16 + (size_t)(pl.rows + 1) * 8;
-            const bool dump_only = sk.power && !sk.rec_q && !sk.hist, rec_only = sk.rec_q && !sk.power && !sk.hist;
-            if (lds <= 80 * 1024 && S * nframes >= 64 && (dump_only || rec_only)) {
-                const void* fn = dump_only ? reinterpret_cast<const void*>(&ex::exact_frames4096_kernel<1>)
-                                           : reinterpret_cast<const void*>(&ex::exact_frames4096_kernel<2>);
-                const hipError_t e = allow_max_lds(fn);
-                if (e != hipSuccess) return e;
-                const int64_t want = (int64_t)2 * device_cus();
-                const int64_t g = std::min<int64_t>(want, (int64_t)S * nframes);
-                if (dump_only) hipLaunchKernelGGL(ex::exact_frames4096_kernel<1>, dim3((unsigned)g), dim3(512), lds, st, pl, pcm, L, frame0, nframes, S, sk);
-                else hipLaunchKernelGGL(ex::exact_frames4096_kernel<2>, dim3((unsigned)g), dim3(512), lds, st, pl, pcm, L, frame0, nframes, S, sk);
-                return hipGetLastError();
-            }
-            return launch_exact_frames_t<12>(pl, pcm, L, S, frame0, nframes, sk, st);
+    if (n == 4096) {
+        // the persistent kernel when its 80 KB fit twice per CU (rows <= 1024) and the launch is a batch
+        const size_t lds = (size_t)2 * 4096 * 8 + (size_t)(7 * 64 + 7 * 8) * 16 + (size_t)(pl.rows + 1) * 8;
+        const bool dump_only = sk.power && !sk.rec_q && !sk.hist, rec_only = sk.rec_q && !sk.power && !sk.hist;
+        if (lds <= 80 * 1024 && S * nframes >= 64 && (dump_only || rec_only)) {
+            const int64_t g = std::min<int64_t>((int64_t)2 * device_cus(), (int64_t)S * nframes);
+            return pick_int<1, 2>(dump_only ? 1 : 2, [&](auto SINK) {
+                return launch_k(ex::exact_frames4096_kernel<SINK()>, dim3((unsigned)g), dim3(512), lds, st, pl, pcm, L, frame0, nframes, S, sk);
+            });
         }
-        case 8192: return launch_exact_frames_t<13>(pl, pcm, L, S, frame0, nframes, sk, st);
-        case 16384: {
-            const size_t planes = (size_t)2 * 8192 * sizeof(double) + (size_t)4 * (128 + 16 + 2) * sizeof(double2);   // swizzled, unpadded
-            const size_t edges = (size_t)(pl.rows + 1) * sizeof(double);
-            ExactSinks sk2 = sk;
-            sk2.edges_lds = planes + edges <= 160 * 1024 ? 1 : 0;
-            const size_t lds = planes + (sk2.edges_lds ? edges : 0);
-            bool fast = ex::exact_fast_plan(pl);
-#ifdef EMSPEC_DIAG
-            if (const char* ev = getenv("EMSPEC_EXACT_NOFAST")) fast = fast && ev[0] != '1';   // A/B aid
-#endif
-            if (sk.live.streams) {
-                const void* lfn = fast ? reinterpret_cast<const void*>(&ex::exact_frames16384_kernel<true, true>)
-                                       : reinterpret_cast<const void*>(&ex::exact_frames16384_kernel<false, true>);
-                const hipError_t le = allow_max_lds(lfn);
-                if (le != hipSuccess) return le;
-                if (fast) hipLaunchKernelGGL((ex::exact_frames16384_kernel<true, true>), dim3((unsigned)nframes, (unsigned)S), dim3(1024), lds, st, pl, pcm, L, frame0, nframes, sk2);
-                else hipLaunchKernelGGL((ex::exact_frames16384_kernel<false, true>), dim3((unsigned)nframes, (unsigned)S), dim3(1024), lds, st, pl, pcm, L, frame0, nframes, sk2);
-                return hipGetLastError();
-            }
-            const void* fn = fast ? reinterpret_cast<const void*>(&ex::exact_frames16384_kernel<true>)
-                                  : reinterpret_cast<const void*>(&ex::exact_frames16384_kernel<false>);
-            const hipError_t e = allow_max_lds(fn);
-            if (e != hipSuccess) return e;
-            if (fast) hipLaunchKernelGGL(ex::exact_frames16384_kernel<true>, dim3((unsigned)nframes, (unsigned)S), dim3(1024), lds, st, pl, pcm, L, frame0, nframes, sk2);
-            else hipLaunchKernelGGL(ex::exact_frames16384_kernel<false>, dim3((unsigned)nframes, (unsigned)S), dim3(1024), lds, st, pl, pcm, L, frame0, nframes, sk2);
-            return hipGetLastError();
-        }
-        default: return hipErrorInvalidValue;
     }
+    if (n == 16384) {
+        ExactSinks sk2 = sk;
+        const size_t planes = (size_t)2 * 8192 * sizeof(double) + (size_t)4 * (128 + 16 + 2) * sizeof(double2);   // swizzled, unpadded
+        const size_t lds = exact_frames_lds(planes, pl.rows, sk2);
+        return pick_bool(ex::exact_fast(pl), [&](auto FASTX) { return pick_bool(sk.live.streams != nullptr, [&](auto LIVE) {
+            return launch_k(ex::exact_frames16384_kernel<FASTX(), LIVE()>, dim3((unsigned)nframes, (unsigned)S), dim3(1024), lds, st, pl, pcm, L, frame0, nframes, sk2);
+        }); });
+    }
+    if (!supported_fft(n)) return hipErrorInvalidValue;
+    return pick_int<8, 9, 10, 11, 12, 13>(__builtin_ctz((unsigned)n), [&](auto LOG2N) {
+        return launch_exact_frames_t<LOG2N()>(pl, pcm, L, S, frame0, nframes, sk, st);
+    });
 }
 
 int exact_record_stride(int n) { return ex::rec_stride(n); }
@@ -1243,8 +1208,6 @@ hipError_t launch_exact_tile_scatter(const long long* rec_q, const uint32_t* rec
         ExactScatterPlan sp = exact_scatter_plan(n, pl, S, C, ebin_f32);
         if (sp.F && sp.rl && (!low || !scratch_holds_a_stream(low_bytes, sp.scratch_per_group, sp.nseg))) sp.F = 0;   // no scratch: tiles
         if (sp.F) {
-            const hipError_t e = allow_max_lds(reinterpret_cast<const void*>(&ex::exact_walk_scatter_kernel));
-            if (e != hipSuccess) return e;
             const int64_t s_per = streams_per_launch(S, sp.nseg, low_bytes, sp.scratch_per_group);
             int walk_abl = 0;
 #ifdef EMSPEC_DIAG
@@ -1253,26 +1216,21 @@ hipError_t launch_exact_tile_scatter(const long long* rec_q, const uint32_t* rec
             const size_t Kp = (size_t)ex::rec_stride(n), cells = (size_t)C * pl.rows;
             for (int64_t s0 = 0; s0 < S; s0 += s_per) {
                 const int sc = (int)std::min<int64_t>(s_per, S - s0);
-                hipLaunchKernelGGL(ex::exact_walk_scatter_kernel, dim3((unsigned)sp.nseg, (unsigned)sc), dim3(1024), sp.lds, st,
-                                   rec_q + (size_t)s0 * C * Kp, rec_key + (size_t)s0 * C * Kp, (int)Kp, pl.rows, pl.D, sp.F, sp.seg, m,
-                                   reinterpret_cast<const uint32_t*>(lut), C, db ? db + (size_t)s0 * cells : nullptr,
-                                   rgba ? reinterpret_cast<uint32_t*>(rgba) + (size_t)s0 * cells : nullptr,
-                                   index ? index + (size_t)s0 * cells : nullptr, sp.rl, low, walk_abl);
-                const hipError_t le = hipGetLastError();
-                if (le != hipSuccess) return le;
+                const hipError_t e = launch_k(ex::exact_walk_scatter_kernel, dim3((unsigned)sp.nseg, (unsigned)sc), dim3(1024), sp.lds, st,
+                                              rec_q + (size_t)s0 * C * Kp, rec_key + (size_t)s0 * C * Kp, Kp, pl.rows, pl.D, sp.F, sp.seg, m,
+                                              reinterpret_cast<const uint32_t*>(lut), C, db ? db + (size_t)s0 * cells : nullptr,
+                                              rgba ? reinterpret_cast<uint32_t*>(rgba) + (size_t)s0 * cells : nullptr,
+                                              index ? index + (size_t)s0 * cells : nullptr, sp.rl, low, walk_abl);
+                if (e != hipSuccess) return e;
             }
             return hipSuccess;
         }
     }
     const TilePlan tp = tile_scatter_plan(pl.rows, C, 8, 16);
     if (!tp.ok) return hipErrorInvalidValue;
-    const hipError_t e = allow_max_lds(reinterpret_cast<const void*>(&ex::exact_tile_scatter_kernel));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ex::exact_tile_scatter_kernel, dim3((unsigned)tp.ntiles, (unsigned)S), dim3(1024), tp.lds, st, rec_q, rec_key,
-                       ex::rec_stride(n), pl.rows, pl.D, tp.tile, m, reinterpret_cast<const uint32_t*>(lut), C, db,
-                       reinterpret_cast<uint32_t*>(rgba), index);
-    return hipGetLastError();
+    return launch_k(ex::exact_tile_scatter_kernel, dim3((unsigned)tp.ntiles, (unsigned)S), dim3(1024), tp.lds, st, rec_q, rec_key,
+                    ex::rec_stride(n), pl.rows, pl.D, tp.tile, m, reinterpret_cast<const uint32_t*>(lut), C, db,
+                    reinterpret_cast<uint32_t*>(rgba), index);
 }
-
 
 }  // namespace emspec

@@ -424,38 +424,25 @@ hipError_t launch_exact_fused(int n, const ExactPlanDev& pl, const ExactDbMap& m
     if (stamp_groups) *stamp_groups = nseg * S;
     const uint32_t* l32 = reinterpret_cast<const uint32_t*>(lut);
     uint32_t* r32 = reinterpret_cast<uint32_t*>(rgba);
-    hipError_t e;
     // the branch-free per-bin core needs reassignment ON, log-spaced rows and a gate that keeps 64 P inside recip_normal64's range
-    bool fast = ex::exact_fast_plan(pl);
+    const bool fast = ex::exact_fast(pl);
+    auto go = [&](auto STAMP, auto FASTX, auto SYNC) {   // SYNC: true = arrival counters (1), false = workgroup barriers (0)
+        return launch_k(exf::exact_fused4096_kernel<STAMP(), FASTX(), SYNC()>, grid, block, lds, st, pl, m, l32, pcm, L, C, sp, slots,
+                        db, r32, index, STAMP() ? stamps : nullptr);
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
 #ifdef EMSPEC_DIAG
-    if (const char* ev = getenv("EMSPEC_EXACT_NOFAST")) fast = fast && ev[0] != '1';   // A/B aid
-#endif
-    int sync = 1;
-#ifdef EMSPEC_DIAG
-    if (const char* ev = getenv("EMSPEC_EXACT_SYNC")) sync = ev[0] == '0' ? 0 : 1;   // A/B aid: 0 = workgroup barriers only
-#endif
-    (void)sync;
-#define EXF_LAUNCH(kern, stp)                                                                      \
-    do {                                                                                           \
-        if ((e = allow_max_lds(reinterpret_cast<const void*>(&kern))) != hipSuccess) return e;     \
-        hipLaunchKernelGGL(kern, grid, block, lds, st, pl, m, l32, pcm, L, C, sp, slots, db, r32, index, stp); \
-        return hipGetLastError();                                                                  \
-    } while (0)
-#ifdef EMSPEC_DIAG
+    const char* ev = getenv("EMSPEC_EXACT_SYNC");   // A/B aid: 0 = workgroup barriers only
+    const bool sync = !(ev && ev[0] == '0');
     if (stamps || stamp_groups) {
         if (!stamps) return hipSuccess;
-        if (fast && sync) EXF_LAUNCH((exf::exact_fused4096_kernel<true, true, 1>), stamps);
-        if (fast) EXF_LAUNCH((exf::exact_fused4096_kernel<true, true, 0>), stamps);
-        EXF_LAUNCH((exf::exact_fused4096_kernel<true, false, 1>), stamps);
+        if (!fast) return go(yes, no, yes);   // (the generic core has no stamped build on barriers)
+        return pick_bool(sync, [&](auto SYNC) { return go(yes, yes, SYNC); });
     }
-    if (!sync) {
-        if (fast) EXF_LAUNCH((exf::exact_fused4096_kernel<false, true, 0>), nullptr);
-        EXF_LAUNCH((exf::exact_fused4096_kernel<false, false, 0>), nullptr);
-    }
+    if (!sync) return pick_bool(fast, [&](auto FASTX) { return go(no, FASTX, no); });
 #endif
-    if (fast) EXF_LAUNCH((exf::exact_fused4096_kernel<false, true, 1>), nullptr);
-    EXF_LAUNCH((exf::exact_fused4096_kernel<false, false, 1>), nullptr);
-#undef EXF_LAUNCH
+    return pick_bool(fast, [&](auto FASTX) { return go(no, FASTX, yes); });
 }
 
 }  // namespace emspec

@@ -644,72 +644,43 @@ hipError_t launch_exact_fused_lr(int n, const ExactPlanDev& pl, const ExactDbMap
     const size_t lds = exl::lds_bytes(pl.rows, rh, slots);
     const uint32_t* l32 = reinterpret_cast<const uint32_t*>(lut);
     uint32_t* r32 = reinterpret_cast<uint32_t*>(rgba);
-    bool fast = ex::exact_fast_plan(pl);
-#ifdef EMSPEC_DIAG
-    if (const char* ev = getenv("EMSPEC_EXACT_NOFAST")) fast = fast && ev[0] != '1';   // A/B aid
-#endif
     // streams per launch: as many as the low-row scratch has slices for ([group][slots][rl]; emspec_seg_plan.h)
     const size_t per_group = (size_t)slots * (size_t)rl * 8;
     if (rl > 0 && (!low || !scratch_holds_a_stream(low_bytes, per_group, nseg))) return hipErrorInvalidValue;
     const int64_t s_per = streams_per_launch(S, nseg, low_bytes, per_group);
     if (stamps && s_per < S) return hipErrorNotSupported;   // the stamped build runs one launch
-    hipError_t e;
-    const void* fn = fast ? reinterpret_cast<const void*>(&exl::exact_fused4096_lr_kernel<false, true>)
-                          : reinterpret_cast<const void*>(&exl::exact_fused4096_lr_kernel<false, false>);
-    if (skip == 1) fn = fast ? reinterpret_cast<const void*>(&exl::exact_fused4096_lr_kernel<false, true, false, 0, 1>)
-                             : reinterpret_cast<const void*>(&exl::exact_fused4096_lr_kernel<false, false, false, 0, 1>);
-    if (skip == 2) fn = fast ? reinterpret_cast<const void*>(&exl::exact_fused4096_lr_kernel<false, true, false, 0, 2>)
-                             : reinterpret_cast<const void*>(&exl::exact_fused4096_lr_kernel<false, false, false, 0, 2>);
-#ifdef EMSPEC_DIAG
-    if (stamps) fn = fast ? reinterpret_cast<const void*>(&exl::exact_fused4096_lr_kernel<true, true>)
-                          : reinterpret_cast<const void*>(&exl::exact_fused4096_lr_kernel<true, false>);
-#endif
-    if ((e = allow_max_lds(fn)) != hipSuccess) return e;
     const size_t col_cells = (size_t)C * pl.rows;
-    for (int64_t s0 = 0; s0 < S; s0 += s_per) {
-        const int sc = (int)std::min<int64_t>(s_per, S - s0);
-        if (rl > 0 && (e = hipMemsetAsync(low, 0, per_group * (size_t)nseg * (size_t)sc, st)) != hipSuccess) return e;
-        const dim3 grid((unsigned)nseg, (unsigned)sc), block(1024);
-        const float* px = pcm + (size_t)s0 * L;
-        float* dbx = db ? db + (size_t)s0 * col_cells : nullptr;
-        uint32_t* rx = r32 ? r32 + (size_t)s0 * col_cells : nullptr;
-        uint8_t* ix = index ? index + (size_t)s0 * col_cells : nullptr;
-        if (skip > 0) {   // N = 2048 / 1024: two / four frames per team and half-iteration
-            if (skip == 1 && fast) hipLaunchKernelGGL((exl::exact_fused4096_lr_kernel<false, true, false, 0, 1>), grid, block, lds, st, pl, m, l32, px, L, C, sp, slots, rl, low, dbx, rx, ix, nullptr);
-            else if (skip == 1) hipLaunchKernelGGL((exl::exact_fused4096_lr_kernel<false, false, false, 0, 1>), grid, block, lds, st, pl, m, l32, px, L, C, sp, slots, rl, low, dbx, rx, ix, nullptr);
-            else if (fast) hipLaunchKernelGGL((exl::exact_fused4096_lr_kernel<false, true, false, 0, 2>), grid, block, lds, st, pl, m, l32, px, L, C, sp, slots, rl, low, dbx, rx, ix, nullptr);
-            else hipLaunchKernelGGL((exl::exact_fused4096_lr_kernel<false, false, false, 0, 2>), grid, block, lds, st, pl, m, l32, px, L, C, sp, slots, rl, low, dbx, rx, ix, nullptr);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-            continue;
+    auto run = [&](auto kernel) -> hipError_t {   // (`stamps` is null unless the kernel is the stamped build)
+        for (int64_t s0 = 0; s0 < S; s0 += s_per) {
+            const int sc = (int)std::min<int64_t>(s_per, S - s0);
+            hipError_t e;
+            if (rl > 0 && (e = hipMemsetAsync(low, 0, per_group * (size_t)nseg * (size_t)sc, st)) != hipSuccess) return e;
+            e = launch_k(kernel, dim3((unsigned)nseg, (unsigned)sc), dim3(1024), lds, st, pl, m, l32, pcm + (size_t)s0 * L, L, C, sp, slots,
+                         rl, low, db ? db + (size_t)s0 * col_cells : nullptr, r32 ? r32 + (size_t)s0 * col_cells : nullptr,
+                         index ? index + (size_t)s0 * col_cells : nullptr, stamps);
+            if (e != hipSuccess) return e;
         }
+        return hipSuccess;
+    };
 #ifdef EMSPEC_DIAG
-        if (stamps) {
-            if (fast) hipLaunchKernelGGL((exl::exact_fused4096_lr_kernel<true, true>), grid, block, lds, st, pl, m, l32, px, L, C, sp, slots, rl, low, dbx, rx, ix, stamps);
-            else hipLaunchKernelGGL((exl::exact_fused4096_lr_kernel<true, false>), grid, block, lds, st, pl, m, l32, px, L, C, sp, slots, rl, low, dbx, rx, ix, stamps);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-            continue;
+    // timing builds of the fast N = 4096 kernel (A/B aids): 1 = PAF, 2 .. 5 = ABL 1 .. 4; the first name set wins
+    static const char* const variant_env[] = {"EMSPEC_EXL_PAF", "EMSPEC_EXL_ABL1", "EMSPEC_EXL_ABL2", "EMSPEC_EXL_ABL3", "EMSPEC_EXL_ABL4"};
+    int variant = 0;
+    for (int i = 0; i < 5 && !variant; ++i) variant = getenv(variant_env[i]) ? i + 1 : 0;
+#endif
+    // SKIP = 1 / 2 (N = 2048 / 1024): two / four frames per team and half-iteration
+    return pick_int<0, 1, 2>(skip, [&](auto SKIP) { return pick_bool(ex::exact_fast(pl), [&](auto FASTX) {
+#ifdef EMSPEC_DIAG
+        if constexpr (SKIP() == 0) {
+            if (stamps) return run(exl::exact_fused4096_lr_kernel<true, FASTX()>);
+            if constexpr (FASTX()) {
+                if (variant == 1) return run(exl::exact_fused4096_lr_kernel<false, true, true>);
+                if (variant) return pick_int<1, 2, 3, 4>(variant - 1, [&](auto ABL) { return run(exl::exact_fused4096_lr_kernel<false, true, false, ABL()>); });
+            }
         }
 #endif
-#ifdef EMSPEC_DIAG
-#define EXL_VARIANT(env, ...)                                                                                               \
-        if (fast && getenv(env)) {                                                                                        \
-            if ((e = allow_max_lds(reinterpret_cast<const void*>(&exl::exact_fused4096_lr_kernel<__VA_ARGS__>))) != hipSuccess) return e; \
-            hipLaunchKernelGGL((exl::exact_fused4096_lr_kernel<__VA_ARGS__>), grid, block, lds, st, pl, m, l32, px, L, C, sp, slots, rl, low, dbx, rx, ix, nullptr); \
-            if ((e = hipGetLastError()) != hipSuccess) return e;                                                          \
-            continue;                                                                                                     \
-        }
-        EXL_VARIANT("EMSPEC_EXL_PAF", false, true, true)
-        EXL_VARIANT("EMSPEC_EXL_ABL1", false, true, false, 1)
-        EXL_VARIANT("EMSPEC_EXL_ABL2", false, true, false, 2)
-        EXL_VARIANT("EMSPEC_EXL_ABL3", false, true, false, 3)
-        EXL_VARIANT("EMSPEC_EXL_ABL4", false, true, false, 4)
-#undef EXL_VARIANT
-#endif
-        if (fast) hipLaunchKernelGGL((exl::exact_fused4096_lr_kernel<false, true>), grid, block, lds, st, pl, m, l32, px, L, C, sp, slots, rl, low, dbx, rx, ix, nullptr);
-        else hipLaunchKernelGGL((exl::exact_fused4096_lr_kernel<false, false>), grid, block, lds, st, pl, m, l32, px, L, C, sp, slots, rl, low, dbx, rx, ix, nullptr);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    return hipSuccess;
+        return run(exl::exact_fused4096_lr_kernel<false, FASTX(), false, 0, SKIP()>);
+    }); });
 }
 
 }  // namespace emspec

@@ -357,33 +357,20 @@ static hipError_t launch_frames_t(const PlanDev& pl, const float* pcm, int64_t L
     const bool plain = !sk.hist;
     const int sink = sk.live.streams ? 3 : (plain && sk.power && !sk.records) ? 1 : ((plain && sk.records && !sk.power) ? 2 : 0);
     if (sink == 0) return hipErrorInvalidValue;   // (no caller mixes the sinks; the run-time form is not instantiated any more)
-    void (*fn)(PlanDev, const float*, int64_t, int64_t, int64_t, FrameSinks) = nullptr;
-    (void)pick_int<1, 2, 3>(sink, [&](auto SINK) {
-        return pick_bool(emspec_plan_is_fast(pl), [&](auto FASTC) { fn = frames_kernel<LOG2N, SINK(), FASTC()>; return hipSuccess; });
-    });
-    if (lds > 64 * 1024) {
-        const hipError_t e = allow_max_lds(reinterpret_cast<const void*>(fn));
-        if (e != hipSuccess) return e;
-    }
     // grid.x is limited to 2^31-1, grid.y to 65535
     if (nframes <= 0 || S <= 0) return hipSuccess;
     if (S > 65535 || nframes > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(fn, dim3((unsigned)nframes, (unsigned)S), dim3(N / 16), lds, st, pl, pcm, L, frame0, nframes, sk);
-    return hipGetLastError();
+    return pick_int<1, 2, 3>(sink, [&](auto SINK) { return pick_bool(emspec_plan_is_fast(pl), [&](auto FASTC) {
+        return launch_k(frames_kernel<LOG2N, SINK(), FASTC()>, dim3((unsigned)nframes, (unsigned)S), dim3(N / 16), lds, st, pl, pcm, L, frame0, nframes, sk);
+    }); });
 }
 
 hipError_t launch_frames(int n, const PlanDev& pl, const float* pcm, int64_t L, int S, int64_t frame0,
                          int64_t nframes, const FrameSinks& sk, hipStream_t st) {
-    switch (n) {
-        case 256: return launch_frames_t<8>(pl, pcm, L, S, frame0, nframes, sk, st);
-        case 512: return launch_frames_t<9>(pl, pcm, L, S, frame0, nframes, sk, st);
-        case 1024: return launch_frames_t<10>(pl, pcm, L, S, frame0, nframes, sk, st);
-        case 2048: return launch_frames_t<11>(pl, pcm, L, S, frame0, nframes, sk, st);
-        case 4096: return launch_frames_t<12>(pl, pcm, L, S, frame0, nframes, sk, st);
-        case 8192: return launch_frames_t<13>(pl, pcm, L, S, frame0, nframes, sk, st);
-        case 16384: return launch_frames_t<14>(pl, pcm, L, S, frame0, nframes, sk, st);
-        default: return hipErrorInvalidValue;
-    }
+    if (!supported_fft(n)) return hipErrorInvalidValue;
+    return pick_int<8, 9, 10, 11, 12, 13, 14>(__builtin_ctz((unsigned)n), [&](auto LOG2N) {
+        return launch_frames_t<LOG2N()>(pl, pcm, L, S, frame0, nframes, sk, st);
+    });
 }
 
 // ---------------------------------------------------------------------------
