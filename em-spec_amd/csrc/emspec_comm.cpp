@@ -480,6 +480,8 @@ int emspec_gather_packed_layout(const emspec_engine* e, int32_t rank, int64_t* o
 int emspec_batch_gather(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32_t n, int32_t hop, int32_t reassign,
                         int32_t root, uint8_t* gathered_index, float* db_local, int64_t* wire_bytes_sent) {
     if (!e || !pcm) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument");
+    if (e->wave_out)
+        return fail(e, EMSPEC_ERR_STATE, "the gather delivers no waveform envelope: not available while emspec_set_wave_out is set (NULL clears it)");
     emspec_comm_state* c = e->comm;
     if (!has_comm(c)) return fail(e, EMSPEC_ERR_STATE, "no communicator: call emspec_comm_init first");
     if (root < 0 || root >= c->world) return fail(e, EMSPEC_ERR_INVALID_ARG, "root out of range");

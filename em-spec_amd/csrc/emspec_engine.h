@@ -109,7 +109,8 @@ struct HostJob {
     // columns on either side when the batch has too few streams
     bool whole_streams = false;
     int halo_D = 0, min_streams = 1;
-    // what is delivered: exactly one of out / pk / pko
+    // what is delivered: exactly one of out / pk / pko (and beside it, while emspec_set_wave_out is set, the envelope of the
+    // streams' samples: emspec_engine::wave_out)
     const emspec_out* out = nullptr;
     const PackedOut* pk = nullptr;
     const PeaksOut* pko = nullptr;
@@ -176,6 +177,8 @@ struct emspec_engine {
     // of streams (dB and / or palette index), which reduce.hip.inc's kernel collapses into the caller's arrays
     int time_reduce = 1;
     char* d_full = nullptr; size_t full_bytes = 0;
+    // waveform envelope (emspec_set_wave_out): the caller's pair array the host pipeline also fills, or null
+    emspec_wave* wave_out = nullptr; int64_t wave_capacity = 0;
     // streaming (emspec_live.cpp): the live multi-stream session, and the single-stream calls' own (emspec_column,
     // emspec_push_samples: the same machinery with one stream); independent of each other
     emspec::LiveState live, one;

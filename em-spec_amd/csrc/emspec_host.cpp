@@ -43,13 +43,15 @@ struct Pipe {   // what the three parts of host_batch share
 int plan_pipe(Pipe& p) {
     emspec_engine* e = p.e;
     const HostJob& j = p.j;
-    if (!e->stream_in) HIPCHK(e, hipStreamCreateWithFlags(&e->stream_in, hipStreamNonBlocking));
-    if (!e->stream_out) HIPCHK(e, hipStreamCreateWithFlags(&e->stream_out, hipStreamNonBlocking));
-    for (hipEvent_t& ev : e->pipe_ev) if (!ev) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     p.R = e->cfg.rows; p.f = e->time_reduce;
     p.C = emspec_num_columns(j.L, j.n, j.hop); p.Cr = reduced_columns(p.C, p.f);
     // dec: the S rows are SOURCES of interleaved frames (emspec_batch_pcm): fb bytes per frame in, V streams each out
     p.V = j.dec ? j.dec->views : 1; p.fb = j.dec ? pcm_frame_bytes(*j.dec) : (int)sizeof(float);
+    if (e->wave_out && (int64_t)j.S * p.V * p.Cr > e->wave_capacity)
+        return fail(e, EMSPEC_ERR_INVALID_ARG, "the envelope set with emspec_set_wave_out is too small: it needs streams x delivered columns pairs");
+    if (!e->stream_in) HIPCHK(e, hipStreamCreateWithFlags(&e->stream_in, hipStreamNonBlocking));
+    if (!e->stream_out) HIPCHK(e, hipStreamCreateWithFlags(&e->stream_out, hipStreamNonBlocking));
+    for (hipEvent_t& ev : e->pipe_ev) if (!ev) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     // what is delivered (pk: the index is staged for the images; pko: the dB columns are staged for the peaks kernel and stay
     // on the device, only the peak lists are delivered)
     const emspec_out none{}, &o = j.out ? *j.out : none;
@@ -57,6 +59,7 @@ int plan_pipe(Pipe& p) {
     p.outs[kRgba] = OutRow{(char*)o.rgba, o.rgba ? (size_t)4 : 0};
     p.outs[kIdx] = OutRow{(char*)o.index, o.index || j.pk ? (size_t)1 : 0};
     p.outs[kPeaks] = OutRow{j.pko ? (char*)j.pko->peaks : nullptr, j.pko ? j.pko->k * sizeof(emspec_peak) : 0};
+    p.outs[kWave] = OutRow{(char*)e->wave_out, e->wave_out ? sizeof(emspec_wave) : 0};   // (beside any of them: emspec_set_wave_out)
     const size_t wire_s = j.pk ? (size_t)wire_bound_bytes(p.Cr, p.R) : 0, in_s = (size_t)j.L * p.fb;
     const size_t per_stream = per_stream_bytes(p.outs, in_s, j.dec ? (size_t)j.L * 4 * p.V : 0, p.V, p.C, p.Cr, p.R, wire_s, p.f);
     int units = pipe_units(e->exact(), j.n, (int64_t)j.S * p.V * p.C, (size_t)j.S * in_s, bytes_out_estimate(p.outs, j.pk != nullptr, (size_t)j.S * p.V, p.C, p.Cr, p.R));
@@ -86,7 +89,8 @@ int plan_pipe(Pipe& p) {
 }
 
 // What unit u delivers: fn(where in the caller's array, byte offset in the unit's set, bytes) for every span of every row that
-// is copied out.  (The peak lists count in columns, and a set holds those of the unit's kept columns only, span after span.)
+// is copied out.  (The peak lists count in columns, and a set holds those of the unit's kept columns only, span after span; so
+// do the envelope's pairs, in delivered columns: wave_span_of.)
 template <class F>
 void for_pieces(const Pipe& p, int u, F&& fn) {
     for (int k = 0; k < spans_of(p.items[u], p.C, p.V); ++k) {
@@ -94,15 +98,18 @@ void for_pieces(const Pipe& p, int u, F&& fn) {
         for (int w = 0; w < kOutRows; ++w) {
             const OutRow& o = p.outs[w];
             const size_t cols = sp.cells / p.R, off = p.g.out_off(w);
-            if (o.host && w != kPeaks) fn(o.host + sp.to * o.unit, off + sp.from * o.unit, sp.cells * o.unit);
+            if (o.host && w == kWave) {
+                const Span ws = wave_span_of(p.items[u], p.C, p.V, k, p.f);
+                fn(o.host + ws.to * o.unit, off + ws.from * o.unit, ws.cells * o.unit);
+            } else if (o.host && w != kPeaks) fn(o.host + sp.to * o.unit, off + sp.from * o.unit, sp.cells * o.unit);
             if (o.host && w == kPeaks) fn(o.host + sp.to / p.R * o.unit, off + k * cols * o.unit, cols * o.unit);
         }
     }
 }
 // the only D2H copies of columns: unit u's kept columns into the caller's arrays, on `st` behind the unit's kernels
-hipError_t copy_out(const Pipe& p, int u, hipStream_t st) {
+hipError_t copy_out(const Pipe& p, int u, hipStream_t st, bool computed = false) {   // (computed: the host has waited for the kernels)
     const char* set = p.e->d_stage + (size_t)(u % kPipeSets) * p.g.bytes();
-    hipError_t r = st == p.e->stream ? hipSuccess : hipStreamWaitEvent(st, p.ev_comp[u % kPipeSets], 0);
+    hipError_t r = st == p.e->stream || computed ? hipSuccess : hipStreamWaitEvent(st, p.ev_comp[u % kPipeSets], 0);
     for_pieces(p, u, [&](char* to, size_t from, size_t bytes) {
         if (r == hipSuccess) r = hipMemcpyAsync(to, set + from, bytes, hipMemcpyDeviceToHost, st);
     });
@@ -209,6 +216,8 @@ void drain(Pipe& p, int u) {
             if (std::min(end, pk->capacity) > at + bytes) std::memset(pk->wire + at + bytes, 0, (size_t)(std::min(end, pk->capacity) - (at + bytes)));
             pk->offsets[it.s0 * p.V + i + 1] = end;
         }
+        // (the index has no host array with pk: what is left to copy out is the envelope's pairs, beside the images)
+        if (p.ok()) p.herr = copy_out(p, u, p.s_out, true);
     }
     if (p.ok() && !p.one) p.herr = hipEventRecord(p.ev_out[b], p.s_out);
 }
@@ -248,6 +257,11 @@ void run_units(Pipe& p) {
         for (int k = 0; j.pko && k < spans_of(it, p.C, V) && herr == hipSuccess; ++k) {
             const Span sp = span_of(it, p.C, R, V, k, 1);
             herr = launch_peaks(q.db + sp.from, (int64_t)(sp.cells / R), R, j.pko->k, j.pko->min_db, q.peaks + (size_t)k * (sp.cells / R) * j.pko->k, e->stream);
+        }
+        // 3d. envelope: the samples under the unit's kept columns, in groups of f (wave.hip.inc), into the set's pairs
+        if (q.wave && herr == hipSuccess) {
+            const WaveRun wr = wave_run_of(it, j.n, j.hop, f);
+            herr = launch_wave(q.pcm, it.sc * V, it.samples, wr.first, wr.cols, j.hop, f, q.wave, wr.pairs, e->stream);
         }
         if (herr != hipSuccess) break;
         // 4. packed: each stream's image, its header to the host behind it

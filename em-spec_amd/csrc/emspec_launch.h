@@ -156,6 +156,12 @@ hipError_t launch_reduce_columns(const float* db_in, const uint8_t* idx_in, int 
 // (position in row units, dB) pairs into peaks [columns][k] (8 bytes each; unused slots (-1, -inf)).  R % 4 == 0, 4 <= R <= 4096,
 // 1 <= k <= 32, min_db not NaN, db 16-byte and peaks 8-byte aligned; any number of columns (the grid strides, 64-bit offsets).
 hipError_t launch_peaks(const float* db, int64_t columns, int R, int k, float min_db, void* peaks, hipStream_t st);
+// waveform envelope (wave.hip.inc): per stream (S of them, `stride` samples apart, 4-byte aligned) and group of f columns of `hop`
+// samples, from `first` samples into the stream on, `cols` columns in all, the pair (lo, hi) of the group's samples in the total
+// order of the floats (-0.0 < +0.0, NaN skipped, none: (+inf, -inf)) into out [S] x ceil(cols / f) pairs of 8 bytes, out_stride
+// pairs apart, 8-byte aligned.  The caller guarantees first + cols * hop <= the samples a stream holds.
+hipError_t launch_wave(const float* pcm, int S, int64_t stride, int64_t first, int64_t cols, int hop, int f, void* out, int64_t out_stride,
+                       hipStream_t st);
 // PCM front end (pcm.hip.inc): `frames` interleaved frames of `sources` sources (source i at src + i * src_stride_bytes, device
 // memory or page-locked host memory, any byte offset that is a multiple of the sample size) -> float32 streams, stream
 // i * views + v at out + (i * views + v) * out_stride.  sample_type: kPcmS16 .. kPcmF32 (the values of include/emspec.h's

@@ -56,10 +56,12 @@ inline std::vector<PipeItem> pipe_items(int S, int64_t L, int64_t C, int n, int 
 inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
 // What a call delivers: one row per array, in the order of a set's layout.  `host`: the caller's array (null: not copied out -
 // the packed entries stage the index for the wire images only); `unit`: bytes per cell - peaks: per column, k pairs - or 0
-// without that array.  Where the unit's copy lies in a staging set: Stage::out_off.
-enum { kDb, kRgba, kIdx, kPeaks, kOutRows };
+// without that array.  Where the unit's copy lies in a staging set: Stage::out_off.  kWave: the waveform envelope of the samples
+// (emspec_set_wave_out), one pair per DELIVERED column.
+enum { kDb, kRgba, kIdx, kPeaks, kWave, kOutRows };
 struct OutRow { char* host; size_t unit; };
 // The bytes `streams` streams leave the device with (pipe_units): the rows' - or the wire images', about a fifth of the index
+// (the envelope's 8 bytes per delivered column are not counted: a batch is cut the same way with and without it)
 inline size_t bytes_out_estimate(const OutRow* o, bool packed, size_t streams, int64_t C, int64_t Cr, int R) {
     const size_t cell = o[kDb].unit + o[kRgba].unit + o[kIdx].unit;
     return packed ? streams * Cr * R / 5 : streams * Cr * R * cell + streams * C * o[kPeaks].unit;
@@ -67,33 +69,37 @@ inline size_t bytes_out_estimate(const OutRow* o, bool packed, size_t streams, i
 
 // (db / rgba / idx: what the unit's kernels write; odb / orgba / oidx: what is delivered - the same arrays, or with a time
 // reduction the reduced columns beside them; peaks: the unit's peak lists, emspec_batch_peaks)
-struct Set { float* pcm; float* db; uint8_t* rgba; uint8_t* idx; uint8_t* wire; char* raw; float* odb; uint8_t* orgba; uint8_t* oidx; emspec_peak* peaks; };
+struct Set { float* pcm; float* db; uint8_t* rgba; uint8_t* idx; uint8_t* wire; char* raw; float* odb; uint8_t* orgba; uint8_t* oidx; emspec_peak* peaks; emspec_wave* wave; };
 // The staging set: every array at the size the largest unit needs, in the order of off()'s list.
 struct Stage {
     size_t in = 0, db = 0, rgba = 0, idx = 0, wire = 0;   // (wire: one slot of that many bytes per stream of the unit)
     size_t raw = 0;                                       // PCM entries: the unit's raw frames, which the decode kernel turns into `in`
     size_t rdb = 0, rrgba = 0, ridx = 0;                  // time reduction: the reduced columns (db / idx then hold the full-rate ones)
     size_t peaks = 0;                                     // emspec_batch_peaks: k (pos, dB) pairs per kept column of the unit
+    size_t wave = 0;                                      // emspec_set_wave_out: a pair per delivered column of the unit; the LAST array,
+                                                          // so that a job without an envelope keeps every offset and size
     bool reduced = false; int chunk = 1;                  // (chunk: streams in the largest unit)
     size_t off(int a) const {   // byte offset in a set of its a-th array
-        const size_t s[10] = {in, db, rgba, idx, wire * chunk, raw, rdb, rrgba, ridx, peaks};
+        const size_t s[11] = {in, db, rgba, idx, wire * chunk, raw, rdb, rrgba, ridx, peaks, wave};
         return std::accumulate(s, s + a, (size_t)0);
     }
-    size_t bytes() const { return off(10); }
+    size_t bytes() const { return off(11); }
     // ... of row w's delivered copy: the reduced array, or without a reduction what the kernels wrote
-    size_t out_off(int w) const { return off(w == kPeaks ? 9 : reduced ? 6 + w : 1 + w); }
+    size_t out_off(int w) const { return off(w == kWave ? 10 : w == kPeaks ? 9 : reduced ? 6 + w : 1 + w); }
     Set at(char* stage, int b) const {
         char* base = stage + (size_t)b * bytes();
         auto p = [&](size_t have, size_t o) { return have ? base + o : nullptr; };
         return Set{(float*)base, (float*)p(db, off(1)), (uint8_t*)p(rgba, off(2)), (uint8_t*)p(idx, off(3)), (uint8_t*)p(wire, off(4)), p(raw, off(5)),
                    (float*)p(reduced ? rdb : db, out_off(kDb)), (uint8_t*)p(reduced ? rrgba : rgba, out_off(kRgba)),
-                   (uint8_t*)p(reduced ? ridx : idx, out_off(kIdx)), (emspec_peak*)p(peaks, out_off(kPeaks))};
+                   (uint8_t*)p(reduced ? ridx : idx, out_off(kIdx)), (emspec_peak*)p(peaks, out_off(kPeaks)),
+                   (emspec_wave*)p(wave, out_off(kWave))};
     }
 };
 
-// The arrays of a set behind its input, for `cells` full-rate cells, `rcells` reduced ones and the peak lists of `cols` columns.
+// The arrays of a set behind its input, for `cells` full-rate cells, `rcells` reduced ones, the peak lists of `cols` columns and
+// the envelope pairs of `rcols` delivered columns.
 // Full rate: the rows' own arrays, but the dB also for the peaks kernel, and with f > 1 the index in place of RGBA.
-inline Stage stage_arrays(const OutRow* o, int f, size_t cells, size_t rcells, size_t cols, size_t wire_s) {
+inline Stage stage_arrays(const OutRow* o, int f, size_t cells, size_t rcells, size_t cols, size_t rcols, size_t wire_s) {
     Stage g;
     g.reduced = f > 1;
     g.db = o[kDb].unit || o[kPeaks].unit ? al(cells * 4) : 0;
@@ -102,24 +108,26 @@ inline Stage stage_arrays(const OutRow* o, int f, size_t cells, size_t rcells, s
     g.wire = al(wire_s);
     if (g.reduced) { g.rdb = al(rcells * o[kDb].unit); g.rrgba = al(rcells * o[kRgba].unit); g.ridx = al(rcells * o[kIdx].unit); }
     g.peaks = al(cols * o[kPeaks].unit);
+    g.wave = al(rcols * o[kWave].unit);
     return g;
 }
 // Staging bytes per stream (pipe_items' 1 GiB cap): the input (`dec_s`: a PCM source's decoded floats) and each view's arrays
 inline size_t per_stream_bytes(const OutRow* o, size_t in_s, size_t dec_s, int V, int64_t C, int64_t Cr, int R, size_t wire_s, int f) {
-    return al(in_s) + (dec_s ? al(dec_s) : 0) + V * stage_arrays(o, f, (size_t)C * R, (size_t)Cr * R, (size_t)C, wire_s).bytes();
+    return al(in_s) + (dec_s ? al(dec_s) : 0) + V * stage_arrays(o, f, (size_t)C * R, (size_t)Cr * R, (size_t)C, (size_t)Cr, wire_s).bytes();
 }
 // The set of a batch (V streams per unit of PipeItem::sc, frame_bytes of raw input each: 1 and 0 for the float entries)
 inline Stage stage_layout(const std::vector<PipeItem>& items, int R, const OutRow* o, size_t wire_s, int V, int frame_bytes, int f) {
-    size_t in = 0, raw = 0, cells = 0, rcells = 0, cols = 0; int chunk = 1;
+    size_t in = 0, raw = 0, cells = 0, rcells = 0, cols = 0, rcols = 0; int chunk = 1;
     for (const PipeItem& it : items) {
         in = std::max(in, al((size_t)it.samples * 4 * it.sc * V));
         raw = std::max(raw, frame_bytes ? al((size_t)it.samples * frame_bytes * it.sc) : 0);
         cells = std::max(cells, (size_t)it.cols * R * it.sc * V);
         rcells = std::max(rcells, (size_t)((it.cn + f - 1) / f) * R * it.sc * V);
         cols = std::max(cols, (size_t)it.cn * it.sc * V);
+        rcols = std::max(rcols, (size_t)((it.cn + f - 1) / f) * it.sc * V);
         chunk = std::max(chunk, it.sc * V);
     }
-    Stage g = stage_arrays(o, f, cells, rcells, cols, wire_s);
+    Stage g = stage_arrays(o, f, cells, rcells, cols, rcols, wire_s);
     g.in = in; g.raw = raw; g.chunk = chunk;
     return g;
 }
@@ -137,5 +145,20 @@ inline Span span_of(const PipeItem& it, int64_t C, int R, int V, int k, int f) {
     const size_t Cr = (size_t)((C + f - 1) / f), crn = (size_t)((it.cn + f - 1) / f);
     if (it.cn == C) return Span{0, (size_t)it.s0 * V * Cr * R, crn * R * it.sc * V};
     return Span{(size_t)k * crn * R, (((size_t)it.s0 * V + k) * Cr + (size_t)(it.c0 / f)) * R, crn * R};
+}
+
+// The waveform envelope of a unit (wave.hip.inc), in pairs = delivered columns.  Its kernel reads the unit's
+// staged samples: the first window starts WaveRun::first samples into each of the unit's streams (off = n / 2 - hop / 2 past
+// the first sample of the unit's first kept column), `cols` = the kept columns in groups of f - a run starts on a multiple of
+// f, so its groups are the stream's - and writes ceil(cn / f) pairs per stream, stream after stream, into the set's array.
+struct WaveRun { int64_t first, cols, pairs; };
+inline WaveRun wave_run_of(const PipeItem& it, int n, int hop, int f) {
+    return WaveRun{it.skip * hop + (n / 2 - hop / 2), it.cn, (it.cn + f - 1) / f};
+}
+// ... and which pairs span k of the unit delivers (spans_of): from the set's pair array to the caller's [streams][Cr]
+inline Span wave_span_of(const PipeItem& it, int64_t C, int V, int k, int f) {
+    const size_t Cr = (size_t)((C + f - 1) / f), crn = (size_t)((it.cn + f - 1) / f);
+    if (it.cn == C) return Span{0, (size_t)it.s0 * V * Cr, crn * it.sc * V};
+    return Span{(size_t)k * crn, ((size_t)it.s0 * V + k) * Cr + (size_t)(it.c0 / f), crn};
 }
 }  // namespace emspec

@@ -44,6 +44,7 @@ SYMBOLS = [
     "emspec_multires_columns", "emspec_multires_shift", "emspec_batch_multires", "emspec_batch_multires_device",
     "emspec_pcm_frame_bytes", "emspec_pcm_decode_device", "emspec_batch_pcm", "emspec_batch_pcm_packed",
     "emspec_push_samples_pcm", "emspec_push_samples_pcm_multires",
+    "emspec_wave_device", "emspec_wave_host", "emspec_set_wave_out",
     "emspec_peaks_device", "emspec_peaks_host", "emspec_batch_peaks", "emspec_batch_peaks_device", "emspec_position_hz",
     "emspec_set_time_reduce", "emspec_time_reduce", "emspec_reduced_columns",
     "emspec_columns_multires", "emspec_push_columns_multires", "emspec_push_samples_multires",
@@ -55,6 +56,8 @@ OPTIONAL_SYMBOLS = SYMBOLS[-3:]
 REDUCE_SYMBOLS = SYMBOLS[-6:-3]
 # the spectral peaks': likewise (tools/peaks_rate.py may time a library built before them next to this build)
 PEAKS_SYMBOLS = SYMBOLS[-11:-6]
+# the waveform envelope's: likewise (tools/wave_rate.py times the parent commit's library next to this build)
+WAVE_SYMBOLS = SYMBOLS[-14:-11]
 
 
 class Config(C.Structure):
@@ -172,6 +175,25 @@ def peaks_host(db, k, min_db, out=None, diag=False):
     assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == columns * int(k) * 2
     lib = load(diag=diag)
     rc = lib.emspec_peaks_host(_np_ptr(db), columns, rows, int(k), float(min_db), _np_ptr(out))
+    if rc != 0:
+        raise EmspecError(rc, lib.emspec_last_error(None).decode())
+    return out
+
+
+def wave_host(pcm, n, hop, factor=1, out=None, diag=False):
+    """The waveform envelope of pcm [S, L] (or [L]) float32 on the host's own cores (emspec_wave_host: plain C++, no device, no
+    engine; the definition: include/emspec.h) -> float32 [S, Cr, 2] of (lo, hi), Cr = reduced_columns(
+    num_columns(L, n, hop), factor): the smallest and the largest sample under each delivered column, with their own bits."""
+    pcm = np.ascontiguousarray(pcm, np.float32)
+    if pcm.ndim == 1:
+        pcm = pcm[None]
+    S, L = pcm.shape
+    lib = load(diag=diag)
+    Cr = max(int(lib.emspec_reduced_columns(max(int(lib.emspec_num_columns(L, n, hop)), 0), factor)), 0)
+    if out is None:
+        out = np.empty((S, Cr, 2), np.float32)
+    assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == S * Cr * 2
+    rc = lib.emspec_wave_host(_np_ptr(pcm), S, L, n, hop, int(factor), _np_ptr(out))
     if rc != 0:
         raise EmspecError(rc, lib.emspec_last_error(None).decode())
     return out
@@ -312,6 +334,11 @@ def load(diag=False):
         lib.emspec_batch_peaks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                                   C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
         lib.emspec_position_hz.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
+    if all(hasattr(lib, sym) for sym in WAVE_SYMBOLS):
+        lib.emspec_wave_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                           C.c_void_p]
+        lib.emspec_wave_host.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+        lib.emspec_set_wave_out.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     _libs[diag] = lib
     return lib
 
@@ -690,6 +717,36 @@ class Engine:
         hz = C.c_double(0.0)
         self._chk(self._lib.emspec_position_hz(self._h, float(pos), C.byref(hz)))
         return hz.value
+
+    # -- waveform envelope: (lo, hi) pairs of the samples under each delivered column, float32 [..., 2] ----
+    def wave_device(self, pcm_t, n, hop, factor=1, out=None, stream=None):
+        """emspec_wave_device: pcm_t a contiguous float32 CUDA tensor [S, L] (4-byte aligned) -> CUDA tensor [S, Cr, 2],
+        Cr = reduced_columns(num_columns(L, n, hop), factor).  `factor` is the call's own: the engine's time reduction plays no
+        part.  Enqueues; does not synchronise."""
+        import torch
+        assert pcm_t.is_cuda and pcm_t.dtype == torch.float32 and pcm_t.is_contiguous() and pcm_t.dim() == 2
+        S, L = pcm_t.shape
+        Cr = max(reduced_columns(max(num_columns(L, n, hop), 0), factor), 0)
+        if out is None:
+            out = torch.empty((S, Cr, 2), dtype=torch.float32, device=pcm_t.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == S * Cr * 2
+        st = stream if stream is not None else torch.cuda.current_stream(pcm_t.device)
+        self._chk(self._lib.emspec_wave_device(self._h, C.c_void_p(pcm_t.data_ptr()), S, L, n, hop, int(factor),
+                                               C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream)))
+        return out
+
+    def set_wave_out(self, wave):
+        """emspec_set_wave_out: while set, batch(), batch_packed(), batch_pcm(), batch_pcm_packed(), batch_multires() and
+        batch_peaks() also write the envelope of their streams to `wave`, a C-contiguous float32 numpy array of
+        streams x delivered columns x 2 values or more (pageable, or a PinnedArray's array); None clears it.  The engine keeps a
+        reference to the array while it is set."""
+        if wave is None:
+            self._chk(self._lib.emspec_set_wave_out(self._h, None, 0))
+            self._wave_out = None
+            return
+        assert isinstance(wave, np.ndarray) and wave.dtype == np.float32 and wave.flags.c_contiguous and wave.flags.writeable
+        self._chk(self._lib.emspec_set_wave_out(self._h, _np_ptr(wave), wave.size // 2))
+        self._wave_out = wave
 
     # -- multi-resolution batch (DESIGN.md §3.8): n_low below split_row, n_high from it up, one column grid --------
     def split_row_for_hz(self, hz):

@@ -44,12 +44,16 @@ static napi_value throw_status(napi_env env, emspec_engine* e, int rc) {
     return NULL;
 }
 
-typedef struct { emspec_engine* e; int32_t rows; } handle_t;   /* rows: the engine's row count, for output-size checks */
+/* rows: the engine's row count, for output-size checks; wave: the array given to setWaveOut, referenced while it is set */
+typedef struct { emspec_engine* e; int32_t rows; napi_ref wave; } handle_t;
 
+static void drop_wave(napi_env env, handle_t* h) {
+    if (h->wave) { napi_delete_reference(env, h->wave); h->wave = NULL; }
+}
 static void finalize_handle(napi_env env, void* data, void* hint) {
-    (void)env; (void)hint;
+    (void)hint;
     handle_t* h = (handle_t*)data;
-    if (h) { if (h->e) emspec_destroy(h->e); free(h); }
+    if (h) { if (h->e) emspec_destroy(h->e); drop_wave(env, h); free(h); }
 }
 
 static int get_number_prop(napi_env env, napi_value obj, const char* name, double* out) {
@@ -126,6 +130,7 @@ static napi_value Create(napi_env env, napi_callback_info info) {
     if (!h) { emspec_destroy(e); napi_throw_error(env, "EMSPEC_ERR_OUT_OF_MEMORY", "malloc"); return NULL; }
     h->e = e;
     h->rows = cfg.rows;
+    h->wave = NULL;
     napi_value ext;
     if (napi_create_external(env, h, finalize_handle, NULL, &ext) != napi_ok) {
         finalize_handle(env, h, NULL);
@@ -142,6 +147,7 @@ static napi_value Destroy(napi_env env, napi_callback_info info) {
     if (argc >= 1 && napi_get_value_external(env, argv[0], &p) == napi_ok && p) {
         handle_t* h = (handle_t*)p;
         if (h->e) { emspec_destroy(h->e); h->e = NULL; }
+        drop_wave(env, h);
     }
     return NULL;
 }
@@ -1157,6 +1163,53 @@ static napi_value PeaksOf(napi_env env, napi_callback_info info) {
     if (rc != EMSPEC_OK) return throw_status(env, NULL, rc);
     return NULL;
 }
+/* Waveform envelope (include/emspec.h).
+ * setWaveOut(handle, wave:Float32Array | null): emspec_set_wave_out with capacity wave.length / 2 pairs - while set, the batch
+ *   calls that run the host pipeline also fill it; the addon references the array until it is replaced, cleared or the engine
+ *   is destroyed
+ * waveOf(pcm:Float32Array(S*L), S, L, fftSize, hop, factor, out:Float32Array(S*Cr*2)): emspec_wave_host (no device, no engine) */
+static napi_value SetWaveOut(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "setWaveOut(handle, wave)"); return NULL; }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    void* wave = NULL; size_t wlen = 0;
+    if (!get_typed(env, argv[1], napi_float32_array, &wave, &wlen, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "wave must be a Float32Array or null"); return NULL; }
+    napi_ref ref = NULL;
+    if (wave) NAPI_OK_OR_RETURN(env, napi_create_reference(env, argv[1], 1, &ref));
+    int rc = emspec_set_wave_out(h->e, (emspec_wave*)wave, wave ? (int64_t)(wlen / 2) : 0);
+    if (rc != EMSPEC_OK) {
+        if (ref) napi_delete_reference(env, ref);
+        return throw_status(env, h->e, rc);
+    }
+    drop_wave(env, h);
+    h->wave = ref;
+    return NULL;
+}
+static napi_value WaveOf(napi_env env, napi_callback_info info) {
+    size_t argc = 7; napi_value argv[7];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 7) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "waveOf(pcm, S, L, fftSize, hop, factor, out)"); return NULL; }
+    void *pcm = NULL, *out = NULL; size_t plen = 0, olen = 0;
+    if (!get_typed(env, argv[0], napi_float32_array, &pcm, &plen, 0)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "pcm must be a Float32Array"); return NULL; }
+    int32_t S = 0, n = 0, hop = 0, factor = 0; int64_t L = 0;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[1], &S));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[2], &L));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[3], &n));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[4], &hop));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[5], &factor));
+    if (!get_typed(env, argv[6], napi_float32_array, &out, &olen, 0)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "out must be a Float32Array"); return NULL; }
+    if (S < 0 || L < 0 || (size_t)S * (size_t)L != plen) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "pcm.length must equal S*L"); return NULL; }
+    /* (a shape the library rejects: it does so with its message before it touches the output) */
+    const int64_t C = emspec_num_columns(L, n, hop), Cr = C >= 0 ? emspec_reduced_columns(C, factor) : -1;
+    if (Cr >= 0 && olen != (size_t)S * (size_t)Cr * 2) {
+        napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "out must hold exactly S*reducedColumns*2 floats");
+        return NULL;
+    }
+    int rc = emspec_wave_host((const float*)pcm, S, L, n, hop, factor, (emspec_wave*)out);
+    if (rc != EMSPEC_OK) return throw_status(env, NULL, rc);
+    return NULL;
+}
 static napi_value PositionHz(napi_env env, napi_callback_info info) {
     size_t argc = 2; napi_value argv[2];
     NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -1336,6 +1389,8 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"reducedColumns", NULL, ReducedColumns, NULL, NULL, NULL, napi_default, NULL},
         {"batchPeaks", NULL, BatchPeaks, NULL, NULL, NULL, napi_default, NULL},
         {"peaksOf", NULL, PeaksOf, NULL, NULL, NULL, napi_default, NULL},
+        {"setWaveOut", NULL, SetWaveOut, NULL, NULL, NULL, napi_default, NULL},
+        {"waveOf", NULL, WaveOf, NULL, NULL, NULL, napi_default, NULL},
         {"positionHz", NULL, PositionHz, NULL, NULL, NULL, napi_default, NULL},
         {"setRowEdges", NULL, SetRowEdges, NULL, NULL, NULL, napi_default, NULL},
         {"getRowEdges", NULL, GetRowEdges, NULL, NULL, NULL, napi_default, NULL},

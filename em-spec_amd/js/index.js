@@ -41,6 +41,15 @@ class Engine {
   setTimeReduce(factor) { native.setTimeReduce(this._h, factor | 0); }
   get timeReduce() { return native.timeReduce(this._h); }
 
+  /**
+   * Waveform envelope (emspec_set_wave_out; DESIGN.md §3.12): while set, computeColumns*, computeColumnsPacked,
+   * computeColumnsPcm*, the multi-resolution batch and batchPeaks also write (lo, hi) of the samples under each delivered column
+   * to `wave`: a Float32Array of streams x delivered columns x 2 values or more (streams = sources x views for PCM), lo and hi
+   * with the samples' own bits.  null clears it.  The addon keeps the array alive until it is replaced, cleared or the engine
+   * is destroyed.
+   */
+  setWaveOut(wave) { native.setWaveOut(this._h, wave === undefined ? null : wave); }
+
   /** Page-locked Float32Array / Uint8Array views for the live calls, (re)made when the shape changes. */
   _liveBlocks(fftSize, wantRgba) {
     const S = this.streams, R = this.rows;
@@ -424,6 +433,19 @@ function pcmFormat({ type, channels, views = ['mono'] }) {
   return f;
 }
 
+/**
+ * The waveform envelope of pcm (Float32Array, S streams of L samples) on the host's own cores (emspec_wave_host: no device, no
+ * engine): Float32Array of S x ceil(columns / factor) x (lo, hi), the smallest and the largest sample under each delivered
+ * column in the total order of the floats (-0 below +0, NaN skipped; none: +Infinity, -Infinity).
+ */
+function waveOf(pcm, S, L, fftSize, hop, factor = 1) {
+  const C = L >= fftSize && hop >= 1 ? Math.floor((L - fftSize) / hop) + 1 : 0;
+  const f = Math.min(65536, Math.max(1, factor | 0));
+  const out = new Float32Array(Math.max(0, S) * Math.ceil(C / f) * 2);
+  native.waveOf(pcm, S, L, fftSize, hop, factor | 0, out);
+  return out;
+}
+
 function peaksOf(db, columns, rows, k = 8, minDb = -60) {
   const out = new Float32Array(Math.max(0, columns) * Math.min(32, Math.max(1, k | 0)) * 2);
   native.peaksOf(db, columns, rows, k | 0, +minDb, out);
@@ -460,6 +482,7 @@ module.exports = {
   /** The host twin of computePeaks (emspec_peaks_host; no device, no engine): db = Float32Array(columns * rows), any dB columns
    *  - a live call's, computeColumnsMultires's - -> Float32Array [columns][k][2]. */
   peaksOf,
+  waveOf,
   /** hz -> {name, octave, cents}: 12-tone equal temperament around A4 = 440 Hz, the nearest semitone, cents in [-50, 50). */
   noteOf,
   latencyColumns: native.latencyColumns,

@@ -716,6 +716,52 @@ int emspec_position_hz(emspec_engine* e, float pos, double* hz);
 /* Every refusal above is EMSPEC_ERR_INVALID_ARG with a message naming the rule - k outside 1 .. 32, a NaN min_db, rows breaking
  * the rule, null or misaligned pointers - and leaves the engine usable. */
 
+/*
+ * ---- Waveform envelope: the smallest and the largest sample under each delivered column, computed
+ * where the samples already are.  Serves: the waveform lane a viewer draws beside the spectrogram, also zoomed out
+ * (emspec_set_time_reduce) and for the views of a PCM source, whose float streams exist in no host buffer; [BUILD-DEFINED].
+ *
+ * DEFINITION.  A stream of L samples, FFT size n, hop (1 <= hop <= n), factor f (1 .. 65536); C = emspec_num_columns(L, n, hop),
+ * Cr = emspec_reduced_columns(C, f), off = n / 2 - hop / 2 (integer divisions).  The envelope is Cr pairs; pair g covers
+ *     W(g) = [ g f hop + off,  min((g + 1) f, C) hop + off )
+ * - at f = 1 the hop samples centred on column g's centre g hop + n / 2.  The windows tile [off, off + C hop) without gap or
+ * overlap, and each lies inside the frames of its own columns (off + hop <= n).
+ *   Order.  For a sample that is not NaN, u its 32 bits:  key = (u & 0x80000000) ? ~u : (u | 0x80000000), unsigned - the total
+ *   order of the floats with -0.0 below +0.0.  lo is the sample of W(g) with the smallest key, hi the one with the largest, each
+ *   with its own bits.  NaN samples are skipped; a window without a sample that is not NaN gives lo = +INFINITY, hi = -INFINITY.
+ * The pair is a function of the window's bits alone: it does not depend on the order of evaluation, on how the work is split,
+ * or on the engine's mode, and the pair at factor f is the key-min / key-max of the f = 1 pairs of its group (the peak-hold
+ * rule of the reduced columns it sits under).  For the PCM entries the samples are the decoded, mixed float32 values of the
+ * views; for emspec_batch_multires the column grid is the long band's, n = n_low.
+ * NOT for the live calls (emspec_columns, emspec_push_samples*): a live host holds the hop it has just pushed, and the pair of
+ * column c would have to be kept D columns until c is emitted.  No RMS or other sum: a float sum depends on its order.
+ */
+typedef struct emspec_wave { float lo; float hi; } emspec_wave;   /* 8 bytes */
+
+/*
+ * The envelope of S device-resident streams, pcm_dev [S][L] laid out as for emspec_batch_device but 4-byte aligned only, into
+ * wave_dev [S][Cr] (8-byte aligned).  S in 0 .. 65535; S = 0 or C = 0 (L < n) is a no-op; n follows the FFT-size rule of the
+ * batch entries, hop in 1 .. n, factor in 1 .. 65536 - its own argument: the engine's time reduction and mode play no part.
+ * One pass over the samples.  Enqueued on hip_stream (NULL = the default stream); does not synchronise.  It is what a caller of
+ * the device batch entries uses; those entries do not change.
+ */
+int emspec_wave_device(emspec_engine* e, const float* pcm_dev, int32_t S, int64_t L, int32_t n, int32_t hop, int32_t factor,
+                       emspec_wave* wave_dev, void* hip_stream);
+/* The same definition in plain C++ on host arrays: no engine, no device.  The message of a refusal: emspec_last_error(NULL). */
+int emspec_wave_host(const float* pcm, int32_t S, int64_t L, int32_t n, int32_t hop, int32_t factor, emspec_wave* wave_out);
+/*
+ * While set, every entry that runs the host pipeline - emspec_batch, _packed, _pcm, _pcm_packed, _multires and
+ * emspec_batch_peaks - also writes the envelope of its streams to wave_out[streams][Cr], in the same pass, from each unit's
+ * staged samples: f = the engine's time reduction, streams = S, or sources x views for the PCM entries.  capacity counts
+ * pairs; a call with streams x Cr > capacity returns EMSPEC_ERR_INVALID_ARG before anything runs.  wave_out is 4-byte aligned
+ * host memory, page-locked or pageable, and must stay valid while set; its contents are undefined after an error return.
+ * NULL clears it.  emspec_batch_gather returns EMSPEC_ERR_STATE while it is set; device entries and streaming calls are not
+ * affected.
+ */
+int emspec_set_wave_out(emspec_engine* e, emspec_wave* wave_out, int64_t capacity /* pairs */);
+/* Every refusal above is EMSPEC_ERR_INVALID_ARG with a message naming the rule - a factor outside 1 .. 65536, a hop outside
+ * 1 .. n, an unsupported n, S outside 0 .. 65535, null or misaligned pointers, a negative capacity - and leaves the engine usable. */
+
 #ifdef __cplusplus
 }
 #endif
