@@ -790,37 +790,8 @@ int emspec_batch_packed(emspec_engine* e, const float* pcm, int32_t S, int64_t L
 }
 
 int emspec_wire_unpack_host(const uint8_t* wire, int64_t wire_bytes, int64_t columns, int32_t rows, uint8_t* index_out) {
-    if (!wire || !index_out || columns < 1 || rows < 1 || wire_bytes < 32) return EMSPEC_ERR_INVALID_ARG;
-    uint32_t h[8];
-    memcpy(h, wire, 32);
-    const uint64_t hcols = (uint64_t)h[2] | ((uint64_t)h[3] << 32), hpay = (uint64_t)h[4] | ((uint64_t)h[5] << 32);
-    const int mw = (rows + 31) >> 5;
-    const int64_t fixed = 32 + columns * 4 + columns * (int64_t)mw * 4;
-    if (h[0] != 0x32574D45u || (int32_t)h[1] != rows || hcols != (uint64_t)columns || hpay > (uint64_t)columns * (uint64_t)rows ||
-        wire_bytes < fixed + (int64_t)hpay)
-        return EMSPEC_ERR_INVALID_ARG;
-    const uint8_t* offp = wire + 32;
-    const uint8_t* maskp = offp + columns * 4;
-    const uint8_t* pay = wire + fixed;
-    for (int64_t c = 0; c < columns; ++c) {
-        uint32_t off;
-        memcpy(&off, offp + c * 4, 4);
-        uint8_t* dst = index_out + c * (int64_t)rows;
-        memset(dst, 0, (size_t)rows);
-        uint64_t at = off;
-        for (int w = 0; w < mw; ++w) {
-            uint32_t m;
-            memcpy(&m, maskp + (c * mw + w) * 4, 4);
-            while (m) {
-                const int bit = __builtin_ctz(m);
-                m &= m - 1;
-                const int r = w * 32 + bit;
-                if (r >= rows || at >= hpay) return EMSPEC_ERR_INVALID_ARG;   // a damaged image must not write or read out of range
-                dst[r] = pay[at++];
-            }
-        }
-    }
-    return EMSPEC_OK;
+    if (!wire || !index_out || columns < 1 || rows < 1) return EMSPEC_ERR_INVALID_ARG;
+    return wire_unpack_host(wire, wire_bytes, columns, rows, index_out) ? EMSPEC_OK : EMSPEC_ERR_INVALID_ARG;
 }
 
 int emspec_parity_dump_device(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32_t n, int32_t hop,
@@ -856,7 +827,6 @@ int emspec_parity_dump(emspec_engine* e, const float* pcm, int32_t S, int64_t L,
     HIPCHK(e, hipSetDevice(e->device));
     const size_t nb = (size_t)S * nframes * (n / 2 + 1);
     const size_t b_pcm = (size_t)S * L * sizeof(float);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     if ((rc = grow(e, (void**)&e->d_stage, &e->stage_bytes, al(b_pcm) + 3 * al(nb * 4) + 256))) return rc;
     char* base = e->d_stage;
     float* d_pcm = (float*)base; base += al(b_pcm);
@@ -888,7 +858,6 @@ int emspec_parity_dump_exact(emspec_engine* e, const float* pcm, int32_t S, int6
     const ExactPlanDev pd = exact_plan_dev(e, *p, hop, reassign);
     const size_t nb = (size_t)S * nframes * (n / 2 + 1);
     const size_t b_pcm = (size_t)S * L * sizeof(float);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     if ((rc = grow(e, (void**)&e->d_stage, &e->stage_bytes, al(b_pcm) + 2 * al(nb * 8) + 2 * al(nb * 4) + 256))) return rc;
     char* base = e->d_stage;
     float* d_pcm = (float*)base; base += al(b_pcm);

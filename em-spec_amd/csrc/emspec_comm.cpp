@@ -39,9 +39,42 @@
 
 using namespace emspec;
 
-namespace emspec {
-uint64_t* wire_total_ptr(void* scratch, int64_t columns);
-}  // namespace emspec
+#ifdef EMSPEC_DIAG
+namespace { struct MockGroup; }   // the in-process stand-in for the communicator, below
+#endif
+
+struct emspec_comm_state {
+    ncclComm_t comm = nullptr;
+#ifdef EMSPEC_DIAG
+    std::shared_ptr<MockGroup> mock;                        // set instead of comm under EMSPEC_COMM_MOCK=1
+#endif
+    int rank = 0, world = 1;
+    // device workspaces, grown on demand
+    uint8_t* d_wire = nullptr; size_t wire_bytes = 0;        // this rank's packed image
+    void* d_scratch = nullptr; size_t scratch_bytes = 0;     // pack / unpack scan workspace
+    uint8_t* d_recv = nullptr; size_t recv_bytes = 0;        // root: the other ranks' images, back to back
+    uint64_t* d_sizes = nullptr;                             // [world][2] (image bytes, columns) after the all-gather
+    uint64_t* h_sizes = nullptr;                             // page-locked copy
+    // directory of the last EMSPEC_GATHER_PACKED gather on the root: per rank (offset in gathered_dev, image bytes, columns, 0)
+    std::vector<uint64_t> packed_layout;
+    uint64_t* h_dir = nullptr;                               // page-locked directories (kDirSlots of them, used in rotation: the
+    unsigned dir_next = 0;                                   //  copy to the head of gathered_dev is still in flight at return)
+    double timeout_s = 120.0;                                // bound on the one host wait of a gather (0: wait for ever)
+};
+static constexpr unsigned kDirSlots = 8;
+
+namespace {
+
+#define NCCLCHK(e, call)                                                                      \
+    do {                                                                                      \
+        ncclResult_t _r = (call);                                                             \
+        if (_r != ncclSuccess)                                                                \
+            return fail((e), EMSPEC_ERR_COMM, std::string(#call) + ": " + ncclGetErrorString(_r)); \
+    } while (0)
+
+// the one text of a size exchange that ran out of time (either transport)
+const char* const kExchangeTimedOut = "the size exchange of the gather did not complete within the communicator's timeout "
+                                      "(a peer rank is missing); communicator aborted";
 
 #ifdef EMSPEC_DIAG
 // Diagnostic build only (libemspec_diag.so, EMSPEC_COMM_MOCK=1): an in-process stand-in for the RCCL communicator, so that
@@ -70,38 +103,53 @@ struct MockGroup {
         return true;
     }
 };
-static std::mutex g_mock_mu;
-static std::map<std::string, std::shared_ptr<MockGroup>> g_mock_groups;
+// the group is dead for every rank (cf. ncclCommAbort), and this engine has no communicator any more
+void mock_abort(emspec_comm_state* c) {
+    if (!c || !c->mock) return;
+    { std::lock_guard<std::mutex> g(c->mock->mu); c->mock->broken = true; }
+    c->mock->cv.notify_all();
+    c->mock.reset();
+}
+std::mutex g_mock_mu;
+std::map<std::string, std::shared_ptr<MockGroup>> g_mock_groups;
+// size exchange: this rank's pair to the host, then through the group
+int exchange_sizes_mock(emspec_engine* e, emspec_comm_state* c, const uint64_t* d_total, hipStream_t st) {
+    uint64_t mine[2];
+    HIPCHK(e, hipMemcpyAsync(mine, d_total, sizeof(mine), hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    auto grp = c->mock;
+    const int me = c->rank;
+    { std::lock_guard<std::mutex> g(grp->mu); grp->pairs[2 * me] = mine[0]; grp->pairs[2 * me + 1] = mine[1]; grp->wire[me] = c->d_wire; }
+    if (!grp->barrier(c->timeout_s)) {
+        mock_abort(c);
+        return fail(e, EMSPEC_ERR_COMM, kExchangeTimedOut);
+    }
+    { std::lock_guard<std::mutex> g(grp->mu); for (int r = 0; r < 2 * c->world; ++r) c->h_sizes[r] = grp->pairs[r]; }
+    return EMSPEC_OK;
+}
+// image movement: the root copies every sender's image device-to-device, then everybody meets again
+int move_images_mock(emspec_engine* e, emspec_comm_state* c, const GatherRoles& ro, const GatherLayout& lay, uint8_t* recv_base, hipStream_t st) {
+    auto grp = c->mock;
+    hipError_t he = hipSuccess;
+    if (ro.is_root) {
+        for (int r = 0; r < c->world && he == hipSuccess; ++r)
+            if (c->h_sizes[2 * r] > 0 && (r != c->rank || ro.loopback)) {
+                const uint8_t* src;
+                { std::lock_guard<std::mutex> g(grp->mu); src = grp->wire[r]; }
+                he = hipMemcpyAsync(recv_base + lay.off[r], src, (size_t)c->h_sizes[2 * r], hipMemcpyDeviceToDevice, st);
+            }
+        if (he == hipSuccess) he = hipStreamSynchronize(st);      // the senders may reuse their images after the barrier below
+    }
+    const bool met = grp->barrier(c->timeout_s);
+    if (he != hipSuccess || !met) {
+        mock_abort(c);
+        return fail(e, EMSPEC_ERR_COMM, he != hipSuccess ? std::string("mock transfer: ") + hipGetErrorString(he)
+                                                         : std::string("a peer rank left the gather; communicator aborted"));
+    }
+    return EMSPEC_OK;
+}
 #endif
 
-struct emspec_comm_state {
-    ncclComm_t comm = nullptr;
-#ifdef EMSPEC_DIAG
-    std::shared_ptr<MockGroup> mock;                        // set instead of comm under EMSPEC_COMM_MOCK=1
-#endif
-    int rank = 0, world = 1;
-    // device workspaces, grown on demand
-    uint8_t* d_wire = nullptr; size_t wire_bytes = 0;        // this rank's packed image
-    void* d_scratch = nullptr; size_t scratch_bytes = 0;     // pack / unpack scan workspace
-    uint8_t* d_recv = nullptr; size_t recv_bytes = 0;        // root: the other ranks' images, back to back
-    uint64_t* d_sizes = nullptr;                             // [world][2] (image bytes, columns) after the all-gather
-    uint64_t* h_sizes = nullptr;                             // page-locked copy
-    // layout of the last EMSPEC_GATHER_PACKED gather on the root: per rank (offset in gathered_dev, image bytes, columns)
-    std::vector<uint64_t> packed_layout;
-    uint64_t* h_dir = nullptr;                               // page-locked directories (kDirSlots of them, used in rotation: the
-    unsigned dir_next = 0;                                   //  copy to the head of gathered_dev is still in flight at return)
-    double timeout_s = 120.0;                                // bound on the one host wait of a gather (0: wait for ever)
-};
-static constexpr unsigned kDirSlots = 8;
-
-namespace {
-
-#define NCCLCHK(e, call)                                                                      \
-    do {                                                                                      \
-        ncclResult_t _r = (call);                                                             \
-        if (_r != ncclSuccess)                                                                \
-            return fail((e), EMSPEC_ERR_COMM, std::string(#call) + ": " + ncclGetErrorString(_r)); \
-    } while (0)
 
 // A communicator that returned an error, or whose peers did not show up, is in an undefined state: tear it down
 // (ncclCommAbort also ends the kernels it still has in flight) so that later calls fail at once with EMSPEC_ERR_STATE
@@ -112,11 +160,7 @@ void abort_comm(emspec_comm_state* c) {
         c->comm = nullptr;
     }
 #ifdef EMSPEC_DIAG
-    if (c && c->mock) {
-        { std::lock_guard<std::mutex> g(c->mock->mu); c->mock->broken = true; }
-        c->mock->cv.notify_all();
-        c->mock.reset();
-    }
+    mock_abort(c);
 #endif
 }
 bool has_comm(const emspec_comm_state* c) {
@@ -134,8 +178,60 @@ bool has_comm(const emspec_comm_state* c) {
         }                                                                                     \
     } while (0)
 
-// the rank-local part of a gather that can fail before the size exchange
-constexpr uint64_t kRankFailed = ~0ull;   // in the (bytes, columns) pair of the size exchange: "this rank cannot take part"
+// ---- the two steps of a gather that talk to the other ranks, each in an RCCL form here and (diagnostic build) a mock form above ----
+// Size exchange: the pair at d_total (image bytes or kRankFailed, columns) of every rank -> c->h_sizes[world][2].  RCCL counts
+// must match on both sides of a send/recv and shards may differ in size (a host that gives the root fewer streams balances its
+// extra expand work), so everybody learns everybody's.  The one host wait of a gather, bounded: a peer that never enters the
+// collective must not hang this rank for ever.
+int exchange_sizes_rccl(emspec_engine* e, emspec_comm_state* c, const uint64_t* d_total, hipStream_t st) {
+    NCCLCHK_ABORT(e, c, ncclAllGather(d_total, c->d_sizes, 2, ncclUint64, c->comm, st));
+    HIPCHK(e, hipMemcpyAsync(c->h_sizes, c->d_sizes, sizeof(uint64_t) * 2 * (size_t)c->world, hipMemcpyDeviceToHost, st));
+    const auto t0 = std::chrono::steady_clock::now();
+    hipError_t q;
+    while ((q = hipStreamQuery(st)) == hipErrorNotReady) {
+        if (c->timeout_s > 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > c->timeout_s) {
+            abort_comm(c);
+            return fail(e, EMSPEC_ERR_COMM, kExchangeTimedOut);
+        }
+        std::this_thread::sleep_for(std::chrono::microseconds(20));
+    }
+    HIPCHK(e, q);
+    return EMSPEC_OK;
+}
+// Image movement: one grouped set of point-to-point transfers, every sender -> root (rank r's image to recv_base + lay.off[r]),
+// each image in the pieces of for_transfer_pieces - the same on both sides, matched in order within the group.
+int move_images_rccl(emspec_engine* e, emspec_comm_state* c, const GatherRoles& ro, int root, const GatherLayout& lay, uint8_t* recv_base,
+                     hipStream_t st) {
+    NCCLCHK_ABORT(e, c, ncclGroupStart());
+    ncclResult_t nr = ncclSuccess;
+    bool ok = !ro.i_send || for_transfer_pieces((size_t)c->h_sizes[2 * c->rank], [&](size_t o, size_t n) {
+        return (nr = ncclSend(c->d_wire + o, n, ncclUint8, root, c->comm, st)) == ncclSuccess;
+    });
+    for (int r = 0; ro.is_root && r < c->world && ok; ++r)
+        if (r != c->rank || ro.loopback)
+            ok = for_transfer_pieces((size_t)c->h_sizes[2 * r], [&](size_t o, size_t n) {
+                return (nr = ncclRecv(recv_base + lay.off[r] + o, n, ncclUint8, r, c->comm, st)) == ncclSuccess;
+            });
+    const ncclResult_t ge = ncclGroupEnd();
+    if (nr != ncclSuccess || ge != ncclSuccess) {
+        abort_comm(c);
+        return fail(e, EMSPEC_ERR_COMM, std::string("ncclSend/ncclRecv: ") + ncclGetErrorString(nr != ncclSuccess ? nr : ge) + " (communicator aborted)");
+    }
+    return EMSPEC_OK;
+}
+
+int exchange_sizes(emspec_engine* e, emspec_comm_state* c, const uint64_t* d_total, hipStream_t st) {
+#ifdef EMSPEC_DIAG
+    if (c->mock) return exchange_sizes_mock(e, c, d_total, st);
+#endif
+    return exchange_sizes_rccl(e, c, d_total, st);
+}
+int move_images(emspec_engine* e, emspec_comm_state* c, const GatherRoles& ro, int root, const GatherLayout& lay, uint8_t* recv_base, hipStream_t st) {
+#ifdef EMSPEC_DIAG
+    if (c->mock) return move_images_mock(e, c, ro, lay, recv_base, st);
+#endif
+    return move_images_rccl(e, c, ro, root, lay, recv_base, st);
+}
 
 int ensure_wire_buffers(emspec_engine* e, emspec_comm_state* c, int64_t columns) {
     int rc;
@@ -261,13 +357,11 @@ int emspec_wire_unpack(emspec_engine* e, const uint8_t* wire_dev, int64_t wire_b
     hipStream_t st = (hipStream_t)hip_stream;
     // validate the header before trusting the image (an image from another configuration would index out of range)
     uint32_t h[8];
-    if (wire_bytes < 32) return fail(e, EMSPEC_ERR_INVALID_ARG, "wire image shorter than its header");
+    if (wire_bytes < kWireHeader) return fail(e, EMSPEC_ERR_INVALID_ARG, "wire image shorter than its header");
     HIPCHK(e, hipMemcpyAsync(h, wire_dev, sizeof(h), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipStreamSynchronize(st));
-    const uint64_t hcols = (uint64_t)h[2] | ((uint64_t)h[3] << 32), hpay = (uint64_t)h[4] | ((uint64_t)h[5] << 32);
-    const int64_t need = wire_fixed_bytes(columns, e->cfg.rows) + (int64_t)((hpay + 15) & ~(uint64_t)15);
-    if (h[0] != 0x32574D45u /* "EMW2" */ || (int32_t)h[1] != e->cfg.rows || hcols != (uint64_t)columns || hpay > (uint64_t)columns * e->cfg.rows ||
-        wire_bytes < need)
+    const WireHeader hd = wire_header(h);
+    if (!wire_header_matches(hd, columns, e->cfg.rows) || wire_bytes < wire_padded_bytes(columns, e->cfg.rows, hd.payload))
         return fail(e, EMSPEC_ERR_INVALID_ARG, "wire image does not match this engine's rows / the column count");
     HIPCHK(e, launch_wire_unpack(wire_dev, columns, e->cfg.rows, index_dev, st));
     return EMSPEC_OK;
@@ -281,42 +375,37 @@ int emspec_gather_columns(emspec_engine* e, const uint8_t* index_dev, int64_t co
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const int R = e->cfg.rows, world = c->world, me = c->rank;
-    const bool is_root = me == root;
-    const bool loopback = (flags & EMSPEC_GATHER_LOOPBACK) != 0;   // the root's own columns take the wire too (tests)
-    const bool packed = (flags & EMSPEC_GATHER_PACKED) != 0;       // the root keeps the images packed (no expand)
-    const size_t col_bytes = (size_t)columns * R;
-    const bool i_send = !is_root || loopback;
-    const bool i_pack = i_send || packed;                          // packed: the root's own columns become an image too
+    // ---- 1. roles
+    const GatherRoles ro = gather_roles(me, root, flags);
     if (wire_bytes_sent) *wire_bytes_sent = 0;
 
-    // ---- everything that can fail on THIS rank alone happens before the size exchange, and a failure does not return:
-    // the rank still enters the all-gather, with kRankFailed in place of its image size, so that every rank learns of it
-    // in the same collective and all of them return together (a rank that simply returned would leave its peers blocked
+    // ---- 2. local checks.  Everything that can fail on THIS rank alone happens before the size exchange, and a failure does
+    // not return: the rank still enters the exchange, with kRankFailed in place of its image size, so that every rank learns
+    // of it in the same collective and all of them return together (a rank that simply returned would leave its peers blocked
     // in the all-gather for ever).
     int local_rc = EMSPEC_OK;
     std::string local_msg;
     auto local_fail = [&](int code, const std::string& msg) { if (local_rc == EMSPEC_OK) { local_rc = code; local_msg = msg; } };
-    if (!index_dev || columns < 1) local_fail(EMSPEC_ERR_INVALID_ARG, "null argument / no columns");
-    else if (root < 0 || root >= world) local_fail(EMSPEC_ERR_INVALID_ARG, "root out of range");
-    else if (is_root && !gathered_dev) local_fail(EMSPEC_ERR_INVALID_ARG, "the root needs the gathered buffer");
-    else if ((uint64_t)columns * (uint64_t)R >= (1ull << 32)) local_fail(EMSPEC_ERR_INVALID_ARG, "at most 2^32 cells per call");
+    const PlanError bad_arg = gather_arg_error(index_dev != nullptr, columns, root, world, ro.is_root, gathered_dev != nullptr, R);
+    if (bad_arg.code != EMSPEC_OK) local_fail(bad_arg.code, bad_arg.msg);
 #ifdef EMSPEC_DIAG
     if (const char* ev = getenv("EMSPEC_GATHER_FAIL_RANK"))        // test hook: this rank "runs out of memory" before the exchange
         if (atoi(ev) == me) local_fail(EMSPEC_ERR_OUT_OF_MEMORY, "injected failure before the size exchange (EMSPEC_GATHER_FAIL_RANK)");
 #endif
-    // ---- this rank's wire image
+    // ---- 3. pack: this rank's wire image
     uint64_t* d_total = c->d_sizes + 2 * (size_t)world;            // spare pair behind the gathered sizes: used when nothing was packed
     if (local_rc == EMSPEC_OK) {
-        int rc = i_pack ? ensure_wire_buffers(e, c, columns) : grow(e, &c->d_scratch, &c->scratch_bytes, wire_scratch_bytes(columns));
+        int rc = ro.i_pack ? ensure_wire_buffers(e, c, columns) : grow(e, &c->d_scratch, &c->scratch_bytes, wire_scratch_bytes(columns));
         if (rc != EMSPEC_OK) local_fail(rc, e->err);
     }
-    if (local_rc == EMSPEC_OK && i_pack) {
+    if (local_rc == EMSPEC_OK && ro.i_pack) {
         const hipError_t he = launch_wire_pack(index_dev, columns, R, c->d_wire, c->d_scratch, st);
         if (he != hipSuccess) local_fail(EMSPEC_ERR_HIP, std::string("wire pack launch: ") + hipGetErrorString(he));
     }
+    // ---- 4. announce: the pair (image bytes, columns) - or the error mark - at d_total on the device
     if (local_rc == EMSPEC_OK) {
         d_total = wire_total_ptr(c->d_scratch, columns);
-        if (!i_pack) HIPCHK(e, hipMemsetAsync(d_total, 0, sizeof(uint64_t), st));   // the root sends nothing
+        if (!ro.i_pack) HIPCHK(e, hipMemsetAsync(d_total, 0, sizeof(uint64_t), st));   // the root sends nothing
         c->h_sizes[2 * world] = (uint64_t)columns;                 // page-locked: read by the async copy below
         HIPCHK(e, hipMemcpyAsync(d_total + 1, &c->h_sizes[2 * world], sizeof(uint64_t), hipMemcpyHostToDevice, st));
     } else {
@@ -324,144 +413,51 @@ int emspec_gather_columns(emspec_engine* e, const uint8_t* index_dev, int64_t co
         c->h_sizes[2 * world + 1] = 0;
         HIPCHK(e, hipMemcpyAsync(d_total, &c->h_sizes[2 * world], 2 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     }
-    // ---- everybody learns everybody's image size and column count (RCCL counts must match on both sides of a
-    // send/recv; shards may differ in size: a host that gives the root fewer streams balances its extra expand work)
-#ifdef EMSPEC_DIAG
-    if (c->mock) {   // in-process stand-in: this rank's pair to the host, then through the group
-        uint64_t mine[2];
-        HIPCHK(e, hipMemcpyAsync(mine, d_total, sizeof(mine), hipMemcpyDeviceToHost, st));
-        HIPCHK(e, hipStreamSynchronize(st));
-        auto grp = c->mock;
-        { std::lock_guard<std::mutex> g(grp->mu); grp->pairs[2 * me] = mine[0]; grp->pairs[2 * me + 1] = mine[1]; grp->wire[me] = c->d_wire; }
-        if (!grp->barrier(c->timeout_s)) {
-            abort_comm(c);
-            return fail(e, EMSPEC_ERR_COMM, "the size exchange of the gather did not complete within the communicator's timeout "
-                                            "(a peer rank is missing); communicator aborted");
-        }
-        { std::lock_guard<std::mutex> g(grp->mu); for (int r = 0; r < 2 * world; ++r) c->h_sizes[r] = grp->pairs[r]; }
-    } else
-#endif
-    {
-    NCCLCHK_ABORT(e, c, ncclAllGather(d_total, c->d_sizes, 2, ncclUint64, c->comm, st));
-    HIPCHK(e, hipMemcpyAsync(c->h_sizes, c->d_sizes, sizeof(uint64_t) * 2 * (size_t)world, hipMemcpyDeviceToHost, st));
-    {   // the one host wait of the call, bounded: a peer that never enters the collective must not hang this rank for ever
-        const auto t0 = std::chrono::steady_clock::now();
-        hipError_t q;
-        while ((q = hipStreamQuery(st)) == hipErrorNotReady) {
-            if (c->timeout_s > 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > c->timeout_s) {
-                abort_comm(c);
-                return fail(e, EMSPEC_ERR_COMM, "the size exchange of the gather did not complete within the communicator's timeout "
-                                                "(a peer rank is missing); communicator aborted");
-            }
-            std::this_thread::sleep_for(std::chrono::microseconds(20));
-        }
-        HIPCHK(e, q);
-    }
-    }
-    if (local_rc != EMSPEC_OK) return fail(e, local_rc, local_msg);          // (the peers return EMSPEC_ERR_COMM below)
-    for (int r = 0; r < world; ++r)
-        if (c->h_sizes[2 * r] == kRankFailed)
-            return fail(e, EMSPEC_ERR_COMM, "rank " + std::to_string(r) + " failed before the exchange: no columns were transferred");
+    // ---- 5. the size exchange
     int rc;
-    for (int r = 0; r < world; ++r) {
-        const uint64_t bytes_r = c->h_sizes[2 * r], cols_r = c->h_sizes[2 * r + 1];
-        if (cols_r < 1 || cols_r * (uint64_t)R >= (1ull << 32) || bytes_r > (uint64_t)wire_bound_bytes((int64_t)cols_r, R))
-            return fail(e, EMSPEC_ERR_COMM, "a rank announced an impossible wire image (column count / size)");
-    }
+    if ((rc = exchange_sizes(e, c, d_total, st))) return rc;
+    // ---- 6. validate
+    if (local_rc != EMSPEC_OK) return fail(e, local_rc, local_msg);          // (the peers return EMSPEC_ERR_COMM below)
+    const int bad_pair = gather_pairs_check(c->h_sizes, world, R);
+    if (bad_pair >= 0) return fail(e, EMSPEC_ERR_COMM, "rank " + std::to_string(bad_pair) + " failed before the exchange: no columns were transferred");
+    if (bad_pair == kPairsImpossible) return fail(e, EMSPEC_ERR_COMM, "a rank announced an impossible wire image (column count / size)");
     if (wire_bytes_sent) *wire_bytes_sent = (int64_t)c->h_sizes[2 * me];
 
-    // ---- the exchange: one grouped set of point-to-point transfers, every rank -> root
-    std::vector<size_t> off((size_t)world + 1, 0), dst_off((size_t)world + 1, 0);
-    const size_t dir_bytes = packed ? ((sizeof(uint64_t) * 4 * (size_t)world + 255) & ~(size_t)255) : 0;
-    if (is_root) {
-        for (int r = 0; r < world; ++r) {
-            off[r + 1] = off[r] + (((size_t)c->h_sizes[2 * r] + 255) & ~(size_t)255);
-            dst_off[r + 1] = dst_off[r] + (size_t)c->h_sizes[2 * r + 1] * R;
-        }
-        if (!packed && (rc = grow(e, (void**)&c->d_recv, &c->recv_bytes, off[world] + 256))) return rc;
+    // ---- 7. layout.  A gathered buffer that cannot hold the announced shards is the root's error alone: the transfers still
+    // run (into the root's own receive buffer), so that the other ranks' sends complete, and only the expand is skipped.
+    // Packed and fitting, the images land where they stay.
+    const GatherLayout lay = gather_layout(c->h_sizes, world, R, ro.is_root, ro.packed, gathered_capacity);
+    uint8_t* recv_base = nullptr;
+    if (ro.is_root && ro.packed && lay.fits) recv_base = gathered_dev + lay.dir_bytes;
+    else if (ro.is_root) {
+        if ((rc = grow(e, (void**)&c->d_recv, &c->recv_bytes, lay.recv_bytes))) return rc;
+        recv_base = c->d_recv;
     }
-    // a gathered buffer that cannot hold the announced shards is the root's error alone: the transfers below still run
-    // (into the root's own receive buffer), so that the other ranks' sends complete, and only the expand is skipped
-    const size_t need_cap = packed ? dir_bytes + off[world] : dst_off[world];
-    const bool fits = !is_root || need_cap <= (size_t)(gathered_capacity > 0 ? gathered_capacity : 0);
-    uint8_t* recv_base = c->d_recv;
-    if (is_root && packed) {
-        if (fits) recv_base = gathered_dev + dir_bytes;            // the images land where they stay
-        else if ((rc = grow(e, (void**)&c->d_recv, &c->recv_bytes, off[world] + 256))) return rc; else recv_base = c->d_recv;
-    }
-#ifdef EMSPEC_DIAG
-    if (c->mock) {   // "send/recv": the root copies every sender's image device-to-device, then everybody meets again
-        auto grp = c->mock;
-        hipError_t he = hipSuccess;
-        if (is_root) {
-            for (int r = 0; r < world && he == hipSuccess; ++r)
-                if (c->h_sizes[2 * r] > 0 && (r != me || loopback)) {
-                    const uint8_t* src;
-                    { std::lock_guard<std::mutex> g(grp->mu); src = grp->wire[r]; }
-                    he = hipMemcpyAsync(recv_base + off[r], src, (size_t)c->h_sizes[2 * r], hipMemcpyDeviceToDevice, st);
-                }
-            if (he == hipSuccess) he = hipStreamSynchronize(st);      // the senders may reuse their images after the barrier below
-        }
-        const bool met = grp->barrier(c->timeout_s);
-        if (he != hipSuccess || !met) {
-            abort_comm(c);
-            return fail(e, EMSPEC_ERR_COMM, he != hipSuccess ? std::string("mock transfer: ") + hipGetErrorString(he)
-                                                             : std::string("a peer rank left the gather; communicator aborted"));
-        }
-    } else
-#endif
-    {
-    NCCLCHK_ABORT(e, c, ncclGroupStart());
-    ncclResult_t nr = ncclSuccess;
-    // An image may be up to 4.8 GB (2^32 - 1 cells); one ncclSend / ncclRecv of more than 2^31 bytes arrived damaged (the
-    // gather of 2^22 - 1 columns x 1,024 rows, a 2.77 GB image: tests/test_gpu_sizes.py), so an image travels in pieces of at
-    // most 1 GiB - the same pieces on both sides, matched in order within the group.  An image under 1 GiB is one transfer, as before.
-    constexpr size_t kMaxTransfer = (size_t)1 << 30;
-    if (i_send)
-        for (size_t o = 0, nbytes = (size_t)c->h_sizes[2 * me]; o < nbytes && nr == ncclSuccess; o += kMaxTransfer)
-            nr = ncclSend(c->d_wire + o, std::min(kMaxTransfer, nbytes - o), ncclUint8, root, c->comm, st);
-    if (is_root)
-        for (int r = 0; r < world && nr == ncclSuccess; ++r)
-            if (r != me || loopback)
-                for (size_t o = 0, nbytes = (size_t)c->h_sizes[2 * r]; o < nbytes && nr == ncclSuccess; o += kMaxTransfer)
-                    nr = ncclRecv(recv_base + off[r] + o, std::min(kMaxTransfer, nbytes - o), ncclUint8, r, c->comm, st);
-    const ncclResult_t ge = ncclGroupEnd();
-    if (nr != ncclSuccess || ge != ncclSuccess) {
-        abort_comm(c);
-        return fail(e, EMSPEC_ERR_COMM, std::string("ncclSend/ncclRecv: ") + ncclGetErrorString(nr != ncclSuccess ? nr : ge) + " (communicator aborted)");
-    }
-    }
+    // ---- 8. the images, every rank -> root
+    if ((rc = move_images(e, c, ro, root, lay, recv_base, st))) return rc;
+    if (!lay.fits) return fail(e, EMSPEC_ERR_INVALID_ARG, "the gathered buffer is smaller than the shards the ranks announced");
 
-    if (!fits) return fail(e, EMSPEC_ERR_INVALID_ARG, "the gathered buffer is smaller than the shards the ranks announced");
-
-    // ---- root: expand every image into its rank's block of the gathered buffer (blocks in rank order, each as long as
-    // that rank's shard); its own columns are a device copy
-    if (is_root && packed) {
-        // directory (per rank: offset from the start of gathered_dev, image bytes, columns, 0) + the images, 256-byte
-        // aligned, in rank order; the root's own image is a device copy of what it packed above.  Expand any of them
-        // later with emspec_wire_unpack(gathered_dev + offset, bytes, columns, ...): emspec_gather_packed_layout.
-        c->packed_layout.assign((size_t)world * 3, 0);
+    // ---- 9. root: the directory, or the expand
+    if (ro.is_root && ro.packed) {
+        // directory + the images, 256-byte aligned, in rank order; the root's own image is a device copy of what it packed
+        // above.  Expand any of them later with emspec_wire_unpack(gathered_dev + offset, bytes, columns, ...):
+        // emspec_gather_packed_layout.
+        c->packed_layout = gather_directory(lay, c->h_sizes, world);
         uint64_t* dir = c->h_dir + (size_t)(c->dir_next++ % kDirSlots) * 4 * (size_t)world;
-        for (int r = 0; r < world; ++r) {
-            dir[4 * r] = c->packed_layout[3 * r] = (uint64_t)(dir_bytes + off[r]);
-            dir[4 * r + 1] = c->packed_layout[3 * r + 1] = c->h_sizes[2 * r];
-            dir[4 * r + 2] = c->packed_layout[3 * r + 2] = c->h_sizes[2 * r + 1];
-            dir[4 * r + 3] = 0;
-        }
+        std::copy(c->packed_layout.begin(), c->packed_layout.end(), dir);
         HIPCHK(e, hipMemcpyAsync(gathered_dev, dir, sizeof(uint64_t) * 4 * (size_t)world, hipMemcpyHostToDevice, st));
-        if (!loopback)
-            HIPCHK(e, hipMemcpyAsync(gathered_dev + dir_bytes + off[me], c->d_wire, (size_t)c->h_sizes[2 * me], hipMemcpyDeviceToDevice, st));
+        if (!ro.loopback)
+            HIPCHK(e, hipMemcpyAsync(gathered_dev + lay.dir_bytes + lay.off[me], c->d_wire, (size_t)c->h_sizes[2 * me], hipMemcpyDeviceToDevice, st));
         return EMSPEC_OK;
     }
-    if (is_root) {
-        for (int r = 0; r < world; ++r) {
-            uint8_t* dst = gathered_dev + dst_off[r];
-            if (r == me && !loopback) {
-                if (dst != index_dev) HIPCHK(e, hipMemcpyAsync(dst, index_dev, col_bytes, hipMemcpyDeviceToDevice, st));
-                continue;
-            }
-            HIPCHK(e, launch_wire_unpack(c->d_recv + off[r], (int64_t)c->h_sizes[2 * r + 1], R, dst, st));
+    // expand every image into its rank's block of the gathered buffer; the root's own columns are a device copy
+    for (int r = 0; ro.is_root && r < world; ++r) {
+        uint8_t* dst = gathered_dev + lay.dst_off[r];
+        if (r == me && !ro.loopback) {
+            if (dst != index_dev) HIPCHK(e, hipMemcpyAsync(dst, index_dev, (size_t)columns * R, hipMemcpyDeviceToDevice, st));
+            continue;
         }
+        HIPCHK(e, launch_wire_unpack(c->d_recv + lay.off[r], (int64_t)c->h_sizes[2 * r + 1], R, dst, st));
     }
     return EMSPEC_OK;
 }
@@ -469,11 +465,11 @@ int emspec_gather_columns(emspec_engine* e, const uint8_t* index_dev, int64_t co
 int emspec_gather_packed_layout(const emspec_engine* e, int32_t rank, int64_t* offset, int64_t* bytes, int64_t* columns) {
     if (!e || !has_comm(e->comm)) return fail(e, EMSPEC_ERR_STATE, "no communicator");
     const emspec_comm_state* c = e->comm;
-    if (rank < 0 || rank >= c->world || c->packed_layout.size() != (size_t)c->world * 3)
+    if (rank < 0 || rank >= c->world || c->packed_layout.size() != (size_t)c->world * 4)
         return fail(e, EMSPEC_ERR_STATE, "no EMSPEC_GATHER_PACKED gather has completed on this engine as the root");
-    if (offset) *offset = (int64_t)c->packed_layout[3 * rank];
-    if (bytes) *bytes = (int64_t)c->packed_layout[3 * rank + 1];
-    if (columns) *columns = (int64_t)c->packed_layout[3 * rank + 2];
+    if (offset) *offset = (int64_t)c->packed_layout[4 * rank];
+    if (bytes) *bytes = (int64_t)c->packed_layout[4 * rank + 1];
+    if (columns) *columns = (int64_t)c->packed_layout[4 * rank + 2];
     return EMSPEC_OK;
 }
 
@@ -491,17 +487,14 @@ int emspec_batch_gather(emspec_engine* e, const float* pcm, int32_t S, int64_t L
     if (S < 1 || C < 1) return fail(e, EMSPEC_ERR_INVALID_ARG, "need at least one stream of at least fft-size samples");
     HIPCHK(e, hipSetDevice(e->device));
     const size_t cells = (size_t)S * (size_t)C * (size_t)e->cfg.rows;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const bool is_root = c->rank == root;
-    const size_t need = al((size_t)S * L * 4) + al(cells) + (db_local ? al(cells * 4) : 0) + (is_root ? al(cells * c->world) : 0) + 256;
+    const GatherStage g = gather_stage((size_t)S * L * 4, cells, db_local != nullptr, is_root, c->world);
     int rc;
-    if ((rc = grow(e, (void**)&e->d_stage, &e->stage_bytes, need))) return rc;
-    char* base = e->d_stage;
-    float* d_pcm = (float*)base; base += al((size_t)S * L * 4);
-    uint8_t* d_idx = (uint8_t*)base; base += al(cells);
-    float* d_db = nullptr;
-    if (db_local) { d_db = (float*)base; base += al(cells * 4); }
-    uint8_t* d_all = is_root ? (uint8_t*)base : nullptr;
+    if ((rc = grow(e, (void**)&e->d_stage, &e->stage_bytes, g.bytes))) return rc;
+    float* d_pcm = (float*)(e->d_stage + g.pcm);
+    uint8_t* d_idx = (uint8_t*)(e->d_stage + g.idx);
+    float* d_db = db_local ? (float*)(e->d_stage + g.db) : nullptr;
+    uint8_t* d_all = is_root ? (uint8_t*)(e->d_stage + g.all) : nullptr;
     HIPCHK(e, hipMemcpyAsync(d_pcm, pcm, (size_t)S * L * 4, hipMemcpyHostToDevice, e->stream));
     if ((rc = emspec_batch_device(e, d_pcm, S, L, n, hop, reassign, d_db, nullptr, d_idx, e->stream))) return rc;
     if ((rc = emspec_gather_columns(e, d_idx, (int64_t)S * C, root, d_all, (int64_t)(cells * c->world), 0, e->stream, wire_bytes_sent))) return rc;

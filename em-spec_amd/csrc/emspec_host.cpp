@@ -74,7 +74,7 @@ int plan_pipe(Pipe& p) {
     if (int rc = grow(e, (void**)&e->d_stage, &e->stage_bytes, std::min(p.nu, kPipeSets) * p.g.bytes() + 1024)) return rc;
     if (j.pk) {
         if (int rc = grow(e, (void**)&e->d_packscratch, &e->packscratch_bytes, wire_scratch_bytes(p.Cr))) return rc;
-        const size_t hb = (size_t)kPipeSets * p.g.chunk * 32;
+        const size_t hb = (size_t)kPipeSets * p.g.chunk * kWireHeader;
         if (hb > e->h_hdr_bytes) {
             if (e->h_hdr) (void)hipHostFree(e->h_hdr);
             e->h_hdr = nullptr; e->h_hdr_bytes = 0;
@@ -196,13 +196,12 @@ void drain(Pipe& p, int u) {
         const uint8_t* wire = p.g.at(e->d_stage, b).wire;
         p.herr = hipEventSynchronize(p.ev_comp[b]);
         for (int i = 0; i < it.sc * p.V && p.ok(); ++i) {
-            const uint32_t* h = reinterpret_cast<const uint32_t*>(e->h_hdr + ((size_t)b * p.g.chunk + i) * 32);
-            const uint64_t hcols = (uint64_t)h[2] | ((uint64_t)h[3] << 32), hpay = (uint64_t)h[4] | ((uint64_t)h[5] << 32);
-            if (h[0] != 0x32574D45u || (int32_t)h[1] != p.R || hcols != (uint64_t)p.Cr || hpay > (uint64_t)p.Cr * p.R) {
+            const WireHeader h = wire_header(e->h_hdr + ((size_t)b * p.g.chunk + i) * kWireHeader);
+            if (!wire_header_matches(h, p.Cr, p.R)) {
                 p.rc = fail(e, EMSPEC_ERR_HIP, "the packed image of a stream carries a bad header");
                 break;
             }
-            const int64_t bytes = wire_fixed_bytes(p.Cr, p.R) + (int64_t)((hpay + 15) & ~(uint64_t)15);
+            const int64_t bytes = wire_padded_bytes(p.Cr, p.R, h.payload);
             const int64_t at = pk->offsets[it.s0 * p.V + i];
             if (at + bytes > pk->capacity) {
                 p.rc = fail(e, EMSPEC_ERR_INVALID_ARG, "wire buffer too small (emspec_wire_bound(columns, rows) per stream always suffices)");
@@ -268,7 +267,7 @@ void run_units(Pipe& p) {
         for (int i = 0; j.pk && i < it.sc * V && herr == hipSuccess; ++i) {
             uint8_t* w = q.wire + (size_t)i * p.g.wire;
             herr = launch_wire_pack(q.oidx + (size_t)i * p.Cr * R, p.Cr, R, w, e->d_packscratch, e->stream);
-            if (herr == hipSuccess) herr = hipMemcpyAsync(e->h_hdr + ((size_t)b * p.g.chunk + i) * 32, w, 32, hipMemcpyDeviceToHost, e->stream);
+            if (herr == hipSuccess) herr = hipMemcpyAsync(e->h_hdr + ((size_t)b * p.g.chunk + i) * kWireHeader, w, kWireHeader, hipMemcpyDeviceToHost, e->stream);
         }
         // 5. computed
         if (herr == hipSuccess && (j.pk || !one)) herr = hipEventRecord(p.ev_comp[b], e->stream);

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "emspec_device.h"
 #include "emspec_live_plan.h"
+#include "emspec_wire_plan.h"
 
 namespace emspec {
 
@@ -140,10 +141,9 @@ hipError_t launch_live_flush(bool exact, const LiveSinks& lv, void* cells, int s
                              const ExactDbMap& xm, int S, int ncol, hipStream_t st);
 hipError_t launch_live_post(const LiveSinks& lv, const float* raw, int raw_cols, int rows, int D, float sm, float agc, float db_top,
                             const DbMap& dm, float* pstate, int S, hipStream_t st);
-// the gather's wire image (pack.hip.inc)
-int64_t wire_bound_bytes(int64_t columns, int rows);
-int64_t wire_fixed_bytes(int64_t columns, int rows);
-size_t wire_scratch_bytes(int64_t columns);
+// the gather's wire image (pack.hip.inc; its sizes and the pack workspace `scratch` of wire_scratch_bytes: emspec_wire_plan.h).
+// wire_total_ptr: where in the workspace the pack leaves the image's size
+uint64_t* wire_total_ptr(void* scratch, int64_t columns);
 hipError_t launch_wire_pack(const uint8_t* index, int64_t columns, int rows, uint8_t* wire, void* scratch, hipStream_t st);
 hipError_t launch_wire_unpack(const uint8_t* wire, int64_t columns, int rows, uint8_t* index, hipStream_t st);
 // time reduction (reduce.hip.inc): groups of f consecutive columns of each stream -> one, by maximum; [S] streams of C columns

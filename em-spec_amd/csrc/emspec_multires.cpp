@@ -52,7 +52,6 @@ int multires_run(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32
     if ((rc = get_band_plan(e, n_high, split, Rh, &ph))) return rc;
     const bool post = e->smoothing > 0.0f || e->agc > 0.0f;
     const size_t col_cells = (size_t)C * R, lo_s = (size_t)C * split * 4, hi_s = (size_t)Ch * Rh * 4, raw_s = post ? col_cells * 4 : 0;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     // the dB -> index map: only lo / inv_range / gate are read, which every n shares (EXACT mode: its own rounding of lo)
     DbMap dm = db_map(e, n_low);
     if (e->exact()) {

@@ -2,6 +2,7 @@
 // unit's arrays lie in a staging set, which cells each unit delivers.  No HIP, nothing of the engine: tests/test_pipe_plan_cpu.py.
 #pragma once
 #include "../../include/emspec.h"
+#include "emspec_wire_plan.h"   // al
 #include <algorithm>
 #include <numeric>
 #include <vector>
@@ -53,7 +54,6 @@ inline std::vector<PipeItem> pipe_items(int S, int64_t L, int64_t C, int n, int 
     return items;
 }
 
-inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
 // What a call delivers: one row per array, in the order of a set's layout.  `host`: the caller's array (null: not copied out -
 // the packed entries stage the index for the wire images only); `unit`: bytes per cell - peaks: per column, k pairs - or 0
 // without that array.  Where the unit's copy lies in a staging set: Stage::out_off.  kWave: the waveform envelope of the samples

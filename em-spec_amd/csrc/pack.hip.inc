@@ -12,12 +12,8 @@
 // popcount / prefix-sum passes on the root, which expands world-1 images per gather and is the critical path).
 // On the bench input 5-7 % of the cells are non-zero: ~186 B per column instead of 1024.
 // The reference has no counterpart (no GPU path, no collectives: SURVEY.md §2); format is [BUILD-DEFINED].
+// (kWireMagic, kWireHeader, wire_mask_words and every size of an image or of the pack workspace: emspec_wire_plan.h)
 namespace emspec {
-
-constexpr uint32_t kWireMagic = 0x32574D45u;   // "EMW2" little-endian
-constexpr int kWireHeader = 32;
-
-__host__ __device__ inline int wire_mask_words(int rows) { return (rows + 31) >> 5; }
 
 // nz4: 4-bit mask of the non-zero bytes of a dword
 __device__ __forceinline__ unsigned nz4(uint32_t w) {
@@ -311,44 +307,31 @@ __global__ __launch_bounds__(1024) void wire_scan_b_kernel(uint32_t* __restrict_
 }
 
 // ---- host side ----
-int64_t wire_fixed_bytes(int64_t columns, int rows) {      // header + offsets + masks
-    return kWireHeader + columns * 4 + columns * (int64_t)wire_mask_words(rows) * 4;
-}
-// (+ 32: the payload's zero padding to 16 B, and the <= 12 B of slack that bring an image's END to a 16-byte boundary when
-// images are laid one after the other - the fixed part is a multiple of 4 only: emspec_batch_packed)
-int64_t wire_bound_bytes(int64_t columns, int rows) { return wire_fixed_bytes(columns, rows) + columns * (int64_t)rows + 32; }
-size_t wire_scratch_bytes(int64_t columns) {   // counts/local offsets + block sums + total (pack side only)
-    return (((size_t)columns * 4 + 255) & ~(size_t)255) + (((size_t)((columns + 1023) / 1024) * 4 + 255) & ~(size_t)255) + 256;
-}
-struct WireScratch { uint32_t* local; uint32_t* bsum; uint64_t* total; };
-static WireScratch wire_scratch_split(void* scratch, int64_t columns) {
-    char* p = static_cast<char*>(scratch);
-    WireScratch w;
-    w.local = reinterpret_cast<uint32_t*>(p); p += ((size_t)columns * 4 + 255) & ~(size_t)255;
-    w.bsum = reinterpret_cast<uint32_t*>(p); p += ((size_t)((columns + 1023) / 1024) * 4 + 255) & ~(size_t)255;
-    w.total = reinterpret_cast<uint64_t*>(p);
-    return w;
-}
-uint64_t* wire_total_ptr(void* scratch, int64_t columns) { return wire_scratch_split(scratch, columns).total; }
+template <class T>
+static T* wire_scratch_at(void* scratch, size_t offset) { return reinterpret_cast<T*>(static_cast<char*>(scratch) + offset); }
+uint64_t* wire_total_ptr(void* scratch, int64_t columns) { return wire_scratch_at<uint64_t>(scratch, wire_scratch_split(columns).total); }
 static bool wire_fast(int rows) { return rows % 32 == 0 && rows <= 1024; }
 
 // index[columns][rows] -> wire image at `wire` (capacity wire_bound_bytes); the image's size lands in
 // *wire_total_ptr(scratch) on the device.  Everything is enqueued on st; nothing synchronises.
 hipError_t launch_wire_pack(const uint8_t* index, int64_t columns, int rows, uint8_t* wire, void* scratch, hipStream_t st) {
     if (columns <= 0 || rows % 4 || (uint64_t)columns * (uint64_t)rows >= (1ull << 32)) return hipErrorInvalidValue;
-    const WireScratch ws = wire_scratch_split(scratch, columns);
+    const WireScratch o = wire_scratch_split(columns);
+    uint32_t* local = wire_scratch_at<uint32_t>(scratch, o.local);
+    uint32_t* bsum = wire_scratch_at<uint32_t>(scratch, o.bsum);
+    uint64_t* total = wire_scratch_at<uint64_t>(scratch, o.total);
     uint32_t* offsets = reinterpret_cast<uint32_t*>(wire + kWireHeader);
     uint32_t* masks = offsets + columns;
     const int64_t fixed = wire_fixed_bytes(columns, rows);
     const int64_t nb = (columns + 1023) / 1024;
     const unsigned g1 = (unsigned)((columns + 3) / 4), g4 = (unsigned)((columns + 4 * kWireNC - 1) / (4 * kWireNC));
     uint8_t* idx = const_cast<uint8_t*>(index);
-    if (wire_fast(rows)) hipLaunchKernelGGL(wire_count16_kernel, dim3(g4), dim3(256), 0, st, index, columns, rows, masks, ws.local);
-    else hipLaunchKernelGGL(wire_count_kernel, dim3(g1), dim3(256), 0, st, index, columns, rows, masks, ws.local);
-    hipLaunchKernelGGL(wire_scan_a_kernel, dim3((unsigned)nb), dim3(1024), 0, st, ws.local, columns, ws.local, ws.bsum);
-    hipLaunchKernelGGL(wire_scan_b_kernel, dim3(1), dim3(1024), 0, st, ws.bsum, nb, fixed, ws.total, wire, rows, columns);
-    if (wire_fast(rows)) hipLaunchKernelGGL(wire_pack16_kernel, dim3(g4), dim3(256), 0, st, index, columns, rows, ws.local, ws.bsum, offsets, wire + fixed);
-    else hipLaunchKernelGGL(wire_move_kernel<true>, dim3(g1), dim3(256), 0, st, idx, columns, rows, masks, ws.local, ws.bsum, offsets, wire + fixed);
+    if (wire_fast(rows)) hipLaunchKernelGGL(wire_count16_kernel, dim3(g4), dim3(256), 0, st, index, columns, rows, masks, local);
+    else hipLaunchKernelGGL(wire_count_kernel, dim3(g1), dim3(256), 0, st, index, columns, rows, masks, local);
+    hipLaunchKernelGGL(wire_scan_a_kernel, dim3((unsigned)nb), dim3(1024), 0, st, local, columns, local, bsum);
+    hipLaunchKernelGGL(wire_scan_b_kernel, dim3(1), dim3(1024), 0, st, bsum, nb, fixed, total, wire, rows, columns);
+    if (wire_fast(rows)) hipLaunchKernelGGL(wire_pack16_kernel, dim3(g4), dim3(256), 0, st, index, columns, rows, local, bsum, offsets, wire + fixed);
+    else hipLaunchKernelGGL(wire_move_kernel<true>, dim3(g1), dim3(256), 0, st, idx, columns, rows, masks, local, bsum, offsets, wire + fixed);
     return hipGetLastError();
 }
 // wire image (header validated by the caller: rows / columns match) -> index[columns][rows]: one kernel, no workspace

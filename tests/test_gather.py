@@ -217,9 +217,15 @@ def test_gather_many_ranks_on_one_gpu(world, packed, monkeypatch):
                 got = out.view(total_cols, rows).cpu().numpy()
             if r == 0 and packed:
                 blocks = []
+                # the directory on the device: per rank (offset, bytes, columns, 0) as u64, the offsets the 256-aligned running
+                # sum of the images behind the directory itself
+                directory = out[:32 * world].cpu().numpy().view(np.uint64).reshape(world, 4)
+                run = (32 * world + 255) // 256 * 256
                 for q in range(world):
                     off, nb, cols = e.gather_packed_layout(q)
                     assert cols == counts[q] * frames and off % 256 == 0 and nb > 32
+                    assert tuple(int(v) for v in directory[q]) == (off, nb, cols, 0) and off == run
+                    run += (nb + 255) // 256 * 256
                     back = torch.empty((cols, rows), dtype=torch.uint8, device=dev)
                     e.wire_unpack(out[off:], nb, back, stream=st)
                     st.synchronize()
