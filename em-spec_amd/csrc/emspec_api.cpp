@@ -273,27 +273,18 @@ int emspec_device_status(emspec_engine* e) {
 }
 const char* emspec_device_arch(const emspec_engine* e) { return e ? e->arch.c_str() : ""; }
 }  // extern "C"
-// EXACT mode, N = 4096 / 2048 / 1024: rows of the ring that the no-parking kernel (exact_fused_lr.hip.inc) keeps in global memory, or -1
-// when it does not serve this engine's shape or axis.  The axis is served when at most 6 % of a frame's bins lie below row
-// rl (on the default log axis at hop 256: rl = 448 of 1024 rows, 38 of 2,049 bins); each of those costs a device-scope
-// atomic, so a linear axis (44 % of the bins there) stays on round 4's kernel, which parks instead.
-// (row0: the plan's first row in the engine's table - a band plan of the multi-resolution batch; the Hz test is on its row rl)
-static int exact_lr_rows(const emspec_engine* e, int n, const ExactPlanDev& pd, int row0 = 0) {
-#ifdef EMSPEC_DIAG
-    if (const char* ev = getenv("EMSPEC_EXACT_PARKED")) { if (ev[0] == '1') return -1; }   // A/B aid: round 4's kernel
-#endif
-    const int rl = exact_fused_lr_low_rows(n, pd);
-    if (rl <= 0) return rl;
-    return low_share_ok(axis_of(e->cfg, e->custom_edges_hz), row0 + rl) ? rl : -1;
+// EXACT mode: the kernel family that serves plan p of this engine (the shape, and for the no-parking kernel the axis)
+static Route exact_route_of(const emspec_engine* e, int n, const ExactPlanDev& pd, int row0 = 0) {
+    return exact_route(n, pd, row0, axis_of(e->cfg, e->custom_edges_hz));
 }
 extern "C" {
 int emspec_uses_fused(const emspec_engine* e, int32_t n, int32_t hop, int32_t reassign) {
     if (!e || n < 1 || hop < 1) return 0;
-    if (e->exact()) {   // only the shape decides (exact_fused_supported reads rows and D)
+    if (e->exact()) {   // only the shape and the axis decide (the route reads rows and D)
         ExactPlanDev pd{};
         pd.rows = e->cfg.rows;
         pd.D = latency(n, hop, reassign);
-        return (exact_lr_rows(e, n, pd) >= 0 || exact_fused_supported(n, pd)) ? 1 : 0;
+        return is_records(exact_route_of(e, n, pd)) ? 0 : 1;
     }
     return fused_supported(n, hop, e->cfg.rows, reassign) ? 1 : 0;
 }
@@ -408,19 +399,16 @@ bool emspec::host_pinned(const void* p) {
 int emspec::grow_chunked(emspec_engine* e, void** ptr, size_t* have, size_t per_stream, size_t extra, size_t cap, int S, int* chunk_out) {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = cap * 4; }
-    size_t budget = (free_b + *have) / 4;
-    budget = budget < ((size_t)256 << 20) ? ((size_t)256 << 20) : (budget > cap ? cap : budget);
+    int64_t budget_mb = -1;
 #ifdef EMSPEC_DIAG
-    if (const char* ev = getenv("EMSPEC_RECORD_BUDGET_MB")) budget = (size_t)atol(ev) << 20;   // test hook: force several stream-chunks
+    if (const char* ev = getenv("EMSPEC_RECORD_BUDGET_MB")) budget_mb = atol(ev);   // test hook: force several stream-chunks
 #endif
-    int chunk = (int)(budget / per_stream);
-    chunk = chunk < 1 ? 1 : (chunk > S ? S : chunk);
-    for (;;) {
-        const int rc = grow(e, ptr, have, per_stream * (size_t)chunk + extra);
-        if (rc == EMSPEC_OK) { *chunk_out = chunk; return EMSPEC_OK; }
+    // the budget, the first chunk and the halving: emspec_kernel_plan.h
+    for (ChunkPlan cp = first_chunk(free_b, *have, per_stream, extra, cap, S, budget_mb);; cp = next_chunk(cp, per_stream, extra)) {
+        const int rc = grow(e, ptr, have, cp.bytes);
+        if (rc == EMSPEC_OK) { *chunk_out = cp.chunk; return EMSPEC_OK; }
         (void)hipGetLastError();
-        if (rc != EMSPEC_ERR_OUT_OF_MEMORY || chunk == 1) return rc;
-        chunk = (chunk + 1) / 2;
+        if (rc != EMSPEC_ERR_OUT_OF_MEMORY || cp.chunk == 1) return rc;
     }
 }
 static int grow_record_workspace(emspec_engine* e, size_t per_stream, size_t extra, size_t cap, int S, int* chunk_out) {
@@ -438,9 +426,8 @@ static int run_columns(emspec_engine* e, const PlanDev& pd, const DbMap& m, cons
     }
     // generic path: per-bin records (frames_kernel) -> 32-column LDS tiles (tile_scatter_kernel),
     // in chunks of streams so the record workspace stays bounded
-    const size_t rec_per_stream = (size_t)C * (n / 2 + 2) * sizeof(uint2);   // frame stride K+1 (even)
     int chunk = 1;
-    if ((rc = grow_record_workspace(e, rec_per_stream, 0, (size_t)4 << 30, S, &chunk))) return rc;
+    if ((rc = grow_record_workspace(e, f32_record_bytes(n, C), 0, (size_t)4 << 30, S, &chunk))) return rc;
     const size_t col_cells = (size_t)C * pd.rows;
     for (int s0 = 0; s0 < S; s0 += chunk) {
         const int sc = (S - s0 < chunk) ? S - s0 : chunk;
@@ -479,23 +466,23 @@ static int run_columns_exact(emspec_engine* e, const Plan& p, const float* pcm, 
     int rc;
     const ExactPlanDev pd = exact_plan_dev(e, p, hop, reassign);
     const ExactDbMap m = exact_db_map(e, n, pd);
-    const int rl = exact_lr_rows(e, n, pd, p.row0);
-    if (rl >= 0) {   // one kernel, no records, no parking (exact_fused_lr.hip.inc)
+    const Route route = exact_route_of(e, n, pd, p.row0);
+    if (route.kind == RouteKind::exact_lr) {   // one kernel, no records, no parking (exact_fused_lr.hip.inc)
+        const int rl = route.rl;
         if ((rc = exact_lr_prepare(e, n, pd, rl, S, C, st))) return rc;
         HIPCHK(e, launch_exact_fused_lr(n, pd, m, e->d_lut, pcm, L, S, C, rl, e->d_xlow, e->xlow_bytes, db, rgba, index, st));
         if (rl > 0) HIPCHK(e, hipEventRecord(e->xlow_event, st));
         return EMSPEC_OK;
     }
-    if (exact_fused_supported(n, pd)) {   // one kernel with the ring parked under the planes (exact_fused.hip.inc): any axis
+    if (route.kind == RouteKind::exact_parked) {   // one kernel with the ring parked under the planes (exact_fused.hip.inc): any axis
         HIPCHK(e, launch_exact_fused(n, pd, m, e->d_lut, pcm, L, S, C, db, rgba, index, st));
         return EMSPEC_OK;
     }
-    const size_t Kp = (size_t)exact_record_stride(n);
-    const size_t q_per_stream = (size_t)C * Kp * sizeof(long long), key_per_stream = (size_t)C * Kp * sizeof(uint32_t);
+    const ExactRecords rec = exact_record_bytes(n, C);
     int chunk = 1;
     // (8 GiB here, 4 GiB for the float32 records: the walking scatter reads a 2D-frame halo per segment, and a stream-chunk's
     // segments get longer with the streams it holds - five streams of configs[4] per chunk: 23 % halo, ten: 12 %; 67.5 -> 66.1 ms per step, and 16 GiB measured 67.0)
-    if ((rc = grow_record_workspace(e, q_per_stream + key_per_stream, 256, (size_t)8 << 30, S, &chunk))) return rc;
+    if ((rc = grow_record_workspace(e, rec.per_stream, kChunkPad, (size_t)8 << 30, S, &chunk))) return rc;
     const size_t col_cells = (size_t)C * pd.rows;
     // the scatter's low-row scratch (exact.hip.inc: a ring too large for LDS is walked with its sparse low rows in global
     // memory); cleared once per batch - the kernel leaves it zero, this only guards against a launch that was cut short
@@ -511,7 +498,7 @@ static int run_columns_exact(emspec_engine* e, const Plan& p, const float* pcm, 
         const int sc = (S - s0 < chunk) ? S - s0 : chunk;
         ExactSinks sk;
         sk.rec_q = reinterpret_cast<long long*>(e->d_hist);
-        sk.rec_key = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(e->d_hist) + ((q_per_stream * chunk + 255) & ~(size_t)255));
+        sk.rec_key = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(e->d_hist) + second_array_offset(rec.q_per_stream, chunk));
         HIPCHK(e, launch_exact_frames(n, pd, pcm + (size_t)s0 * L, L, sc, 0, C, sk, st));
         HIPCHK(e, launch_exact_tile_scatter(sk.rec_q, sk.rec_key, n, pd, m, e->d_lut, sc, C, db ? db + s0 * col_cells : nullptr,
                                             rgba ? rgba + 4 * s0 * col_cells : nullptr,
@@ -538,9 +525,9 @@ int emspec::reduce_streams(emspec_engine* e, int32_t S, int64_t C, float* db, ui
     const int R = e->cfg.rows, f = e->time_reduce;
     const size_t cells = (size_t)C * R, rcells = (size_t)reduced_columns(C, f) * R;
     const size_t db_s = db ? cells * 4 : 0, idx_s = (index || rgba) ? cells : 0;   // (cells is a multiple of 4: both stay 16-byte aligned ...
-    return for_stream_chunks(e, (void**)&e->d_full, &e->full_bytes, db_s + idx_s, 256, (size_t)4 << 30, S, [&](int s0, int sc, int chunk) -> int {
+    return for_stream_chunks(e, (void**)&e->d_full, &e->full_bytes, db_s + idx_s, kChunkPad, (size_t)4 << 30, S, [&](int s0, int sc, int chunk) -> int {
         float* wdb = db ? reinterpret_cast<float*>(e->d_full) : nullptr;
-        uint8_t* widx = idx_s ? reinterpret_cast<uint8_t*>(e->d_full) + ((db_s * chunk + 255) & ~(size_t)255) : nullptr;   // ... and this 256)
+        uint8_t* widx = idx_s ? reinterpret_cast<uint8_t*>(e->d_full) + second_array_offset(db_s, chunk) : nullptr;   // ... and this 256)
         if (int rc = full(s0, sc, wdb, widx)) return rc;
         const size_t o = (size_t)s0 * rcells;
         HIPCHK(e, launch_reduce_columns(wdb, widx, sc, C, R, f, cells, rcells, e->d_lut, db ? db + o : nullptr,
@@ -684,58 +671,46 @@ int emspec_debug_phase_cycles(emspec_engine* e, const float* pcm_dev, int32_t S,
     Plan* p;
     int rc;
     if ((rc = get_plan(e, n, &p))) return rc;
-    if (e->exact()) {   // the stamped build of exact_fused4096_kernel (waves: 16; slots: exact_fused.hip.inc)
+    // sizing call (stamps null: *groups), allocate, stamped launch, copy back, free
+    auto stamped = [&](int wpg, auto&& launch) -> int {
+        HIPCHK(e, launch(nullptr));
+        if (waves) *waves = wpg;
+        if (!cycles) return EMSPEC_OK;
+        unsigned long long* d = nullptr;
+        const size_t bytes = (size_t)(*groups) * wpg * 8 * sizeof(unsigned long long);
+        HIPCHK(e, hipMalloc(&d, bytes));
+        hipError_t r = launch(d);
+        if (r == hipSuccess) r = hipMemcpyAsync(cycles, d, bytes, hipMemcpyDeviceToHost, e->stream);
+        if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
+        (void)hipFree(d);
+        HIPCHK(e, r);
+        return EMSPEC_OK;
+    };
+    const int64_t C = emspec_num_columns(L, n, hop);
+    if (e->exact()) {   // the stamped builds of the two EXACT fused kernels (waves: 16; slots: exact_fused.hip.inc, exact_fused_lr.hip.inc)
         const ExactPlanDev xpd = exact_plan_dev(e, *p, hop, reassign);
         const ExactDbMap xm = exact_db_map(e, n, xpd);
-        const int64_t Cx = emspec_num_columns(L, n, hop);
-        const int xrl = exact_lr_rows(e, n, xpd);
-        if (xrl >= 0) {   // the stamped build of exact_fused4096_lr_kernel (slots: exact_fused_lr.hip.inc)
-            if ((rc = exact_lr_prepare(e, n, xpd, xrl, S, Cx, e->stream))) return rc;
-            HIPCHK(e, launch_exact_fused_lr(n, xpd, xm, e->d_lut, pcm_dev, L, S, Cx, xrl, e->d_xlow, e->xlow_bytes, db_dev, nullptr, index_dev, e->stream, nullptr, groups));
-            if (xrl > 0) HIPCHK(e, hipEventRecord(e->xlow_event, e->stream));   // (every launch on the scratch: later ones on other streams wait for it)
-            if (waves) *waves = 16;
-            if (!cycles) return EMSPEC_OK;
-            unsigned long long* dl = nullptr;
-            const size_t lbytes = (size_t)(*groups) * 16 * 8 * sizeof(unsigned long long);
-            HIPCHK(e, hipMalloc(&dl, lbytes));
-            hipError_t lr = launch_exact_fused_lr(n, xpd, xm, e->d_lut, pcm_dev, L, S, Cx, xrl, e->d_xlow, e->xlow_bytes, db_dev, nullptr, index_dev, e->stream, dl, groups);
-            if (lr == hipSuccess && xrl > 0) lr = hipEventRecord(e->xlow_event, e->stream);
-            if (lr == hipSuccess) lr = hipMemcpyAsync(cycles, dl, lbytes, hipMemcpyDeviceToHost, e->stream);
-            if (lr == hipSuccess) lr = hipStreamSynchronize(e->stream);
-            (void)hipFree(dl);
-            HIPCHK(e, lr);
-            return EMSPEC_OK;
+        const Route route = exact_route_of(e, n, xpd);
+        if (route.kind == RouteKind::exact_lr) {
+            const int xrl = route.rl;
+            if ((rc = exact_lr_prepare(e, n, xpd, xrl, S, C, e->stream))) return rc;
+            return stamped(16, [&](unsigned long long* stamps) {
+                hipError_t r = launch_exact_fused_lr(n, xpd, xm, e->d_lut, pcm_dev, L, S, C, xrl, e->d_xlow, e->xlow_bytes, db_dev, nullptr, index_dev, e->stream, stamps, groups);
+                if (r == hipSuccess && xrl > 0) r = hipEventRecord(e->xlow_event, e->stream);   // (every launch on the scratch: later ones on other streams wait for it)
+                return r;
+            });
         }
-        if (!exact_fused_supported(n, xpd)) return fail(e, EMSPEC_ERR_INVALID_ARG, "no fused exact kernel for this shape");
-        HIPCHK(e, launch_exact_fused(n, xpd, xm, e->d_lut, pcm_dev, L, S, Cx, db_dev, nullptr, index_dev, e->stream, nullptr, groups));
-        if (waves) *waves = 16;
-        if (!cycles) return EMSPEC_OK;
-        unsigned long long* dx = nullptr;
-        const size_t xbytes = (size_t)(*groups) * 16 * 8 * sizeof(unsigned long long);
-        HIPCHK(e, hipMalloc(&dx, xbytes));
-        hipError_t xr = launch_exact_fused(n, xpd, xm, e->d_lut, pcm_dev, L, S, Cx, db_dev, nullptr, index_dev, e->stream, dx, groups);
-        if (xr == hipSuccess) xr = hipMemcpyAsync(cycles, dx, xbytes, hipMemcpyDeviceToHost, e->stream);
-        if (xr == hipSuccess) xr = hipStreamSynchronize(e->stream);
-        (void)hipFree(dx);
-        HIPCHK(e, xr);
-        return EMSPEC_OK;
+        if (route.kind != RouteKind::exact_parked) return fail(e, EMSPEC_ERR_INVALID_ARG, "no fused exact kernel for this shape");
+        return stamped(16, [&](unsigned long long* stamps) {
+            return launch_exact_fused(n, xpd, xm, e->d_lut, pcm_dev, L, S, C, db_dev, nullptr, index_dev, e->stream, stamps, groups);
+        });
     }
     if (!fused_supported(n, hop, e->cfg.rows, reassign)) return fail(e, EMSPEC_ERR_INVALID_ARG, "no fused kernel for this shape");
     const PlanDev pd = plan_dev(e, *p, hop, reassign);
     const DbMap m = db_map(e, n);
-    const int64_t C = emspec_num_columns(L, n, hop);
-    HIPCHK(e, launch_fused(n, pd, m, e->d_lut, pcm_dev, L, S, C, db_dev, nullptr, index_dev, e->stream, nullptr, groups));
-    if (waves) *waves = fused_waves_per_group();
-    if (!cycles) return EMSPEC_OK;
-    unsigned long long* d = nullptr;
-    const size_t bytes = (size_t)(*groups) * fused_waves_per_group() * 8 * sizeof(unsigned long long);
-    HIPCHK(e, hipMalloc(&d, bytes));
-    hipError_t r = launch_fused(n, pd, m, e->d_lut, pcm_dev, L, S, C, db_dev, nullptr, index_dev, e->stream, d, groups);
-    if (r == hipSuccess) r = hipMemcpyAsync(cycles, d, bytes, hipMemcpyDeviceToHost, e->stream);
-    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-    (void)hipFree(d);
-    HIPCHK(e, r);
-    return EMSPEC_OK;
+    return stamped(fused_waves_per_group(), [&](unsigned long long* stamps) {
+        return launch_fused(n, pd, m, e->d_lut, pcm_dev, L, S, C, db_dev, nullptr, index_dev, e->stream, stamps, groups);
+    });
 }
 #endif  // EMSPEC_DIAG
 
@@ -827,12 +802,13 @@ int emspec_parity_dump(emspec_engine* e, const float* pcm, int32_t S, int64_t L,
     HIPCHK(e, hipSetDevice(e->device));
     const size_t nb = (size_t)S * nframes * (n / 2 + 1);
     const size_t b_pcm = (size_t)S * L * sizeof(float);
-    if ((rc = grow(e, (void**)&e->d_stage, &e->stage_bytes, al(b_pcm) + 3 * al(nb * 4) + 256))) return rc;
+    const DumpStage ds = dump_stage(b_pcm, nb, false);
+    if ((rc = grow(e, (void**)&e->d_stage, &e->stage_bytes, ds.bytes))) return rc;
     char* base = e->d_stage;
-    float* d_pcm = (float*)base; base += al(b_pcm);
-    float* d_pw = (float*)base; base += al(nb * 4);
-    int32_t* d_col = (int32_t*)base; base += al(nb * 4);
-    int32_t* d_row = (int32_t*)base;
+    float* d_pcm = (float*)(base + ds.pcm);
+    float* d_pw = (float*)(base + ds.power);
+    int32_t* d_col = (int32_t*)(base + ds.col);
+    int32_t* d_row = (int32_t*)(base + ds.row);
     HIPCHK(e, hipMemcpyAsync(d_pcm, pcm, b_pcm, hipMemcpyHostToDevice, e->stream));
     if ((rc = emspec_parity_dump_device(e, d_pcm, S, L, n, hop, reassign, frame0, nframes, d_pw, d_col, d_row, e->stream))) return rc;
     HIPCHK(e, hipMemcpyAsync(power, d_pw, nb * 4, hipMemcpyDeviceToHost, e->stream));
@@ -858,14 +834,15 @@ int emspec_parity_dump_exact(emspec_engine* e, const float* pcm, int32_t S, int6
     const ExactPlanDev pd = exact_plan_dev(e, *p, hop, reassign);
     const size_t nb = (size_t)S * nframes * (n / 2 + 1);
     const size_t b_pcm = (size_t)S * L * sizeof(float);
-    if ((rc = grow(e, (void**)&e->d_stage, &e->stage_bytes, al(b_pcm) + 2 * al(nb * 8) + 2 * al(nb * 4) + 256))) return rc;
+    const DumpStage ds = dump_stage(b_pcm, nb, true);
+    if ((rc = grow(e, (void**)&e->d_stage, &e->stage_bytes, ds.bytes))) return rc;
     char* base = e->d_stage;
-    float* d_pcm = (float*)base; base += al(b_pcm);
+    float* d_pcm = (float*)(base + ds.pcm);
     ExactSinks sk;
-    sk.power = (double*)base; base += al(nb * 8);
-    sk.q = (long long*)base; base += al(nb * 8);
-    sk.col = (int32_t*)base; base += al(nb * 4);
-    sk.row = (int32_t*)base;
+    sk.power = (double*)(base + ds.power);
+    sk.q = (long long*)(base + ds.q);
+    sk.col = (int32_t*)(base + ds.col);
+    sk.row = (int32_t*)(base + ds.row);
     HIPCHK(e, hipMemcpyAsync(d_pcm, pcm, b_pcm, hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, launch_exact_frames(n, pd, d_pcm, L, S, frame0, nframes, sk, e->stream));
     HIPCHK(e, hipMemcpyAsync(power, sk.power, nb * 8, hipMemcpyDeviceToHost, e->stream));

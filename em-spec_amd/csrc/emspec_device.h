@@ -85,7 +85,7 @@ __device__ __forceinline__ float2 cmul_tw(float2 d, float2 w) {
 // LDS index padding for the in-place exchange buffer: one complex slot of pad
 // per 16 keeps the stride-2^b accesses of every pass off a single bank pair.
 __device__ __forceinline__ constexpr int padi(int p) { return p + (p >> 4); }
-template <int N> struct PaddedSize { static constexpr int value = N + (N >> 4); };
+// (PaddedSize<N>, the buffer's size: emspec_kernel_plan.h)
 
 // Orders this wave's earlier LDS writes before its later LDS reads.  The LDS pipe executes one
 // wave's instructions in order, so nothing is waited for; this only stops the compiler from

@@ -64,7 +64,7 @@ struct ExactSinks {
     int32_t* col = nullptr;
     int32_t* row = nullptr;
     long long* q = nullptr;
-    // per-bin records for exact_tile_scatter_kernel: [stream][frame][exact_record_stride(n)] of the bin's fixed-point
+    // per-bin records for exact_tile_scatter_kernel: [stream][frame][ex::rec_stride(n)] of the bin's fixed-point
     // energy and key = (dcol+32768)<<16 | row, or 0xFFFFFFFF when dropped
     long long* rec_q = nullptr;
     uint32_t* rec_key = nullptr;
@@ -80,7 +80,6 @@ struct ExactSinks {
 };
 hipError_t launch_exact_frames(int n, const ExactPlanDev& pl, const float* pcm, int64_t L, int S, int64_t frame0,
                                int64_t nframes, const ExactSinks& sinks, hipStream_t st);
-int exact_record_stride(int n);
 // (ebin_f32 / low / low_bytes: the plan's float32 edge table on the host and a zeroed u64 scratch of
 // exact_scatter_scratch_bytes - with them a ring that does not fit LDS is walked with its sparse low rows in that scratch,
 // every record read once; without them, or on an axis with > 6 % of the bins down there: 16-column tiles, records read 3x)
@@ -89,15 +88,16 @@ hipError_t launch_exact_tile_scatter(const long long* rec_q, const uint32_t* rec
                                      const ExactDbMap& m, const uint8_t* lut, int S, int64_t C, float* db, uint8_t* rgba,
                                      uint8_t* index, hipStream_t st, const float* ebin_f32 = nullptr,
                                      unsigned long long* low = nullptr, size_t low_bytes = 0);
+// EXACT mode: the kernel family that serves the plan (emspec_kernel_plan.h: exact_route, with the diagnostic build's switches) -
+// the no-parking kernel with Route::rl low rows, the parking kernel, or per-bin records.  row0: the plan's first row in the
+// engine's table, axis: the engine's
+Route exact_route(int n, const ExactPlanDev& pl, int row0, const Axis& axis);
 // EXACT mode, one kernel (exact_fused.hip.inc): N = 4096 at every hop whose u64 column ring fits in LDS
-bool exact_fused_supported(int n, const ExactPlanDev& pl);
 hipError_t launch_exact_fused(int n, const ExactPlanDev& pl, const ExactDbMap& m, const uint8_t* lut, const float* pcm,
                               int64_t L, int S, int64_t C, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st,
                               unsigned long long* stamps = nullptr, int64_t* stamp_groups = nullptr);
 // EXACT mode, one kernel without parking (exact_fused_lr.hip.inc): the ring's rows >= rl in LDS beside the planes, rows < rl
-// in a per-workgroup scratch in global memory (device-scope atomics only).  exact_fused_lr_low_rows: rl for the shape
-// (rows, D), or -1 when the shape is not served; whether the AXIS is (few bins below row rl) is the caller's decision.
-int exact_fused_lr_low_rows(int n, const ExactPlanDev& pl);
+// in a per-workgroup scratch in global memory (device-scope atomics only); rl is the route's.
 size_t exact_fused_lr_scratch_bytes(int n, const ExactPlanDev& pl, int rl, int S, int64_t C);
 hipError_t launch_exact_fused_lr(int n, const ExactPlanDev& pl, const ExactDbMap& m, const uint8_t* lut, const float* pcm,
                                  int64_t L, int S, int64_t C, int rl, unsigned long long* low, size_t low_bytes, float* db,
@@ -170,6 +170,9 @@ enum { kPcmS16 = 1, kPcmS24 = 2, kPcmS32 = 3, kPcmF32 = 4, kPcmMaxChannels = 8, 
 struct PcmMix { float w[kPcmMaxViews * kPcmMaxChannels]; };   // [view][kPcmMaxChannels]
 hipError_t launch_pcm_decode(const void* src, int sample_type, int channels, int views, const float* mix, int sources, int64_t frames,
                              int64_t src_stride_bytes, float* out, int64_t out_stride, hipStream_t st);
+// FAST mode: the kernel family that serves the shape (emspec_kernel_plan.h: fast_route, with the diagnostic build's switches);
+// fused_supported: it is not the records path
+Route fused_route(int n, int hop, int rows, int reassign);
 bool fused_supported(int n, int hop, int rows, int reassign);
 int device_cus();           // compute units of the current device
 #ifdef EMSPEC_DIAG          // diagnostic build only (libemspec_diag.so, include/emspec_debug.h)

@@ -5,6 +5,7 @@
 // build, their getenv switches.  No HIP: tests/test_seg_plan_cpu.py runs it through a stand-alone program
 // (tests/cdriver/seg_plan_driver.cpp) without a GPU and pins every plan to tests/golden/seg_plans.json.
 #pragma once
+#include "emspec_kernel_plan.h"   // kLdsBytes, RouteKind
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -53,6 +54,7 @@ inline int64_t seglen_by_rounds(int64_t ncu, int S, int64_t C, int D, int64_t se
 
 // ---- the fused float32 kernels (fused.hip.inc: launch_fused) ----
 enum class FusedKind { n4096_8192, small_n, big_n };   // the N = 4096 / 8192 families, fused_small, N = 16384: only seg_min differs
+inline FusedKind fused_kind(RouteKind k) { return k == RouteKind::fused_small ? FusedKind::small_n : (k == RouteKind::fused_16384 ? FusedKind::big_n : FusedKind::n4096_8192); }
 // nseg: segments per stream; streams_first: grid = (streams, segments) - the shared-device plan - instead of (segments, streams);
 // ok false: more segments than a grid dimension holds (the launcher returns hipErrorInvalidValue)
 struct FusedSegPlan { SegPlan sp; int64_t nseg; bool streams_first; bool ok; };
@@ -197,7 +199,7 @@ inline ExactScatterPlan exact_scatter_plan(int64_t ncu, int rec_stride, int n, i
     // workgroups of a launch run in rounds of (CUs x workgroups that fit a CU), and a launch costs rounds x (segment + its
     // 2D-frame halo + pipeline fill).  The former rule (a fixed lower bound of 8D columns) gave configs[4]'s stream-chunks of
     // five streams 62 segments each = 310 workgroups on 256 CUs: two rounds, the second a fifth full.
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, (int64_t)((size_t)160 * 1024 / wl)));
+    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, (int64_t)(kLdsBytes / wl)));
     const int64_t places = ncu * per_cu;
     const int64_t over = 2 * D + F;
     int64_t seg = (C + F - 1) / F * F;

@@ -329,7 +329,7 @@ __device__ __forceinline__ CellOut exact_cell(const ExactDbMap& m, unsigned long
     return CellOut{d, (int)(v * 255.0f + 0.5f)};
 }
 
-constexpr int rec_stride(int n) { return n / 2 + 4; }   // records per frame: K = n/2+1 bins + 3 pads (16-byte chunks of 4)
+// (rec_stride, records per frame: emspec_kernel_plan.h)
 
 // SINK: 0 = whatever the ExactSinks say at run time; 1 = parity dump only; 2 = records only (compile-time, so that the four
 // bins of a thread stay in one basic block - the run-time form tests three sink pointers per bin)
@@ -1134,23 +1134,18 @@ __global__ __launch_bounds__(1024) void exact_walk_scatter_kernel(const long lon
 
 }  // namespace ex
 
-// LDS of a frame kernel: its planes, and the binary64 row edges when they fit beside them (else read from global memory)
-static size_t exact_frames_lds(size_t planes, int rows, ExactSinks& sk) {
-    const size_t edges = (size_t)(rows + 1) * sizeof(double);
-    sk.edges_lds = planes + edges <= 160 * 1024 ? 1 : 0;
-    return planes + (sk.edges_lds ? edges : 0);
-}
-
+// (LDS of a frame kernel - its planes, and the binary64 row edges when they fit beside them: exact_frames_lds, emspec_kernel_plan.h)
 // (a live multi-stream launch, LIVE: nframes = the largest per-stream frame count + 1, the ingest workgroup)
 template <int LOG2N>
 static hipError_t launch_exact_frames_t(const ExactPlanDev& pl, const float* pcm, int64_t L, int S, int64_t frame0,
                                         int64_t nframes, const ExactSinks& sk, hipStream_t st) {
     constexpr int N = 1 << LOG2N;
     ExactSinks sk2 = sk;
-    const size_t lds = exact_frames_lds((size_t)2 * PaddedSize<N>::value * sizeof(double), pl.rows, sk2);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const ExactFramesLds lds = exact_frames_lds(exact_frames_planes(N), pl.rows);
+    sk2.edges_lds = lds.edges_lds;
+    if (lds.bytes > kLdsBytes) return hipErrorInvalidValue;
     return pick_bool(ex::exact_fast(pl), [&](auto FASTX) { return pick_bool(sk.live.streams != nullptr, [&](auto LIVE) {
-        return launch_k(ex::exact_frames_kernel<LOG2N, FASTX(), LIVE()>, dim3((unsigned)nframes, (unsigned)S), dim3(N / 8), lds, st, pl, pcm, L, frame0, nframes, sk2);
+        return launch_k(ex::exact_frames_kernel<LOG2N, FASTX(), LIVE()>, dim3((unsigned)nframes, (unsigned)S), dim3(N / 8), lds.bytes, st, pl, pcm, L, frame0, nframes, sk2);
     }); });
 }
 
@@ -1160,9 +1155,9 @@ hipError_t launch_exact_frames(int n, const ExactPlanDev& pl, const float* pcm, 
     if (S > 65535 || nframes > 0x7fffffffLL) return hipErrorInvalidValue;
     if (n == 4096) {
         // the persistent kernel when its 80 KB fit twice per CU (rows <= 1024) and the launch is a batch
-        const size_t lds = (size_t)2 * 4096 * 8 + (size_t)(7 * 64 + 7 * 8) * 16 + (size_t)(pl.rows + 1) * 8;
+        const size_t lds = exact_frames4096_lds_bytes(pl.rows);
         const bool dump_only = sk.power && !sk.rec_q && !sk.hist, rec_only = sk.rec_q && !sk.power && !sk.hist;
-        if (lds <= 80 * 1024 && S * nframes >= 64 && (dump_only || rec_only)) {
+        if (exact_frames4096_persistent(pl.rows, S, nframes) && (dump_only || rec_only)) {
             const int64_t g = std::min<int64_t>((int64_t)2 * device_cus(), (int64_t)S * nframes);
             return pick_int<1, 2>(dump_only ? 1 : 2, [&](auto SINK) {
                 return launch_k(ex::exact_frames4096_kernel<SINK()>, dim3((unsigned)g), dim3(512), lds, st, pl, pcm, L, frame0, nframes, S, sk);
@@ -1171,10 +1166,10 @@ hipError_t launch_exact_frames(int n, const ExactPlanDev& pl, const float* pcm, 
     }
     if (n == 16384) {
         ExactSinks sk2 = sk;
-        const size_t planes = (size_t)2 * 8192 * sizeof(double) + (size_t)4 * (128 + 16 + 2) * sizeof(double2);   // swizzled, unpadded
-        const size_t lds = exact_frames_lds(planes, pl.rows, sk2);
+        const ExactFramesLds lds = exact_frames_lds(exact_frames_planes(n), pl.rows);
+        sk2.edges_lds = lds.edges_lds;
         return pick_bool(ex::exact_fast(pl), [&](auto FASTX) { return pick_bool(sk.live.streams != nullptr, [&](auto LIVE) {
-            return launch_k(ex::exact_frames16384_kernel<FASTX(), LIVE()>, dim3((unsigned)nframes, (unsigned)S), dim3(1024), lds, st, pl, pcm, L, frame0, nframes, sk2);
+            return launch_k(ex::exact_frames16384_kernel<FASTX(), LIVE()>, dim3((unsigned)nframes, (unsigned)S), dim3(1024), lds.bytes, st, pl, pcm, L, frame0, nframes, sk2);
         }); });
     }
     if (!supported_fft(n)) return hipErrorInvalidValue;
@@ -1182,8 +1177,6 @@ hipError_t launch_exact_frames(int n, const ExactPlanDev& pl, const float* pcm, 
         return launch_exact_frames_t<LOG2N()>(pl, pcm, L, S, frame0, nframes, sk, st);
     });
 }
-
-int exact_record_stride(int n) { return ex::rec_stride(n); }
 
 // (ExactScatterPlan - walking ring whole, walking ring with its low rows in a global scratch, or tiles - and its segment rule:
 // emspec_seg_plan.h)

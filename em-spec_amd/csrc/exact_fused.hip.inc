@@ -38,8 +38,7 @@ __device__ __forceinline__ void bar_only() { asm volatile("s_barrier" ::: "memor
 using ex::XTwLds4;
 using ex::tw4_slot;
 
-__host__ __device__ inline int region_cells(int rows, int slots) { return slots * rows > 2 * N ? slots * rows : 2 * N; }
-__host__ __device__ inline int edge_cells(int rows) { return (rows + 2) & ~1; }
+// (region_cells, edge_cells - the sizes of the region the ring and the planes share and of the edge table: emspec_kernel_plan.h)
 
 using ex::recip_normal64;
 using ex::kFastMinFloor64;
@@ -369,11 +368,7 @@ __global__ __launch_bounds__(1024, 4) void exact_fused4096_kernel(
     }
 }
 #undef EXF_STAMP
-
-static int exact_fused_slots(int D) { return 2 * D + 2 > 3 ? 2 * D + 2 : 3; }
-static size_t exact_fused_lds_bytes(int rows, int slots) {
-    return ((size_t)region_cells(rows, slots) + (size_t)edge_cells(rows)) * 8 + (size_t)(4 * 64 + 4 * 8) * 16 + 1024 + 32;
-}
+// (ring slots and dynamic LDS: exact_fused_slots, exact_fused_lds_bytes, emspec_kernel_plan.h)
 }  // namespace exf
 
 #ifdef EMSPEC_DIAG
@@ -389,20 +384,21 @@ hipError_t launch_recip64_probe(const double* d, int64_t count, double* out_shor
     hipLaunchKernelGGL(recip64_probe_kernel, dim3(1024), dim3(256), 0, st, d, count, out_short, out_ieee);
     return hipGetLastError();
 }
-static bool diag_exact_records() {   // A/B aid: EMSPEC_EXACT_RECORDS=1 forces the two-kernel records path of rounds 2-3
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("EMSPEC_EXACT_RECORDS"); on = (e && e[0] == '1') ? 1 : 0; }
-    return on != 0;
+// A/B aids: EMSPEC_EXACT_RECORDS=1 forces the two-kernel records path of rounds 2-3 (read once), EMSPEC_EXACT_PARKED=1 round 4's
+// parking kernel where the no-parking one would serve (read at every call)
+static ExactSwitches diag_exact_switches() {
+    static int rec = -1;
+    if (rec < 0) { const char* e = getenv("EMSPEC_EXACT_RECORDS"); rec = (e && e[0] == '1') ? 1 : 0; }
+    const char* pk = getenv("EMSPEC_EXACT_PARKED");
+    return ExactSwitches{pk && pk[0] == '1', rec != 0};
 }
 #else
-static constexpr bool diag_exact_records() { return false; }
+static constexpr ExactSwitches diag_exact_switches() { return ExactSwitches{}; }
 #endif
 
-bool exact_fused_supported(int n, const ExactPlanDev& pl) {
-    if (diag_exact_records()) return false;
-    if (n != exf::N || pl.rows % 4 || pl.rows < 64 || pl.rows > 1024 || pl.D < 0 || pl.D > 1024) return false;
-    return exf::exact_fused_lds_bytes(pl.rows, exf::exact_fused_slots(pl.D)) <= (size_t)160 * 1024;
-}
+// the kernel family that serves the plan with this build's switches (emspec_kernel_plan.h: exact_route)
+Route exact_route(int n, const ExactPlanDev& pl, int row0, const Axis& axis) { return exact_route(n, pl.rows, pl.D, row0, axis, diag_exact_switches()); }
+static bool exact_fused_supported(int n, const ExactPlanDev& pl) { return !diag_exact_switches().records && exact_parked_fits(n, pl.rows, pl.D); }
 
 hipError_t launch_exact_fused(int n, const ExactPlanDev& pl, const ExactDbMap& m, const uint8_t* lut, const float* pcm,
                               int64_t L, int S, int64_t C, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st,
@@ -418,8 +414,8 @@ hipError_t launch_exact_fused(int n, const ExactPlanDev& pl, const ExactDbMap& m
     const int64_t nseg = (C + seg - 1) / seg;
     if (!exact_fused_grid_ok(nseg, seg)) return hipErrorInvalidValue;
     const SegPlan sp{(int)seg, 1 << 30, (int)seg, 0};
-    const int slots = exf::exact_fused_slots(pl.D);
-    const size_t lds = exf::exact_fused_lds_bytes(pl.rows, slots);
+    const int slots = exact_fused_slots(pl.D);
+    const size_t lds = exact_fused_lds_bytes(pl.rows, slots);
     const dim3 grid((unsigned)nseg, (unsigned)S), block(1024);
     if (stamp_groups) *stamp_groups = nseg * S;
     const uint32_t* l32 = reinterpret_cast<const uint32_t*>(lut);

@@ -94,9 +94,8 @@ __device__ __forceinline__ const int4* lrpos_row(int tt) {
     else if constexpr (S == 1) return reinterpret_cast<const int4*>(&g_lrpos1.v[tt][0]);
     else return reinterpret_cast<const int4*>(&g_lrpos2.v[tt][0]);
 }
-// ring slots: 2 D + 2 FPT columns are live at once (at half-iteration k the F team scatters block k - 2 and takes the FPT
-// columns of block k - 3, shifted by D, out)
-__host__ __device__ inline int lr_slots(int S, int D) { return S == 0 ? (2 * D + 2 > 3 ? 2 * D + 2 : 3) : 2 * D + (2 << S); }
+// (lr_slots, the ring's slots, and ring_cells / mask_words of the LDS budget - planes + ring + edges + pass twiddles + LUT +
+// counters + one bit per low-row cell: emspec_kernel_plan.h)
 // stages U0..2 of a radix-8 register pass (pass A of the small sizes skips the carrier's first S stages)
 template <int U0, class W>
 __device__ __forceinline__ void xstages8_from(double (&vr)[8], double (&vi)[8], const W& w) {
@@ -105,14 +104,6 @@ __device__ __forceinline__ void xstages8_from(double (&vr)[8], double (&vi)[8], 
     ex::xstage8<2>(vr, vi, w);
 }
 
-// LDS budget: planes + ring + edges + pass twiddles + LUT + counters
-__host__ __device__ inline int ring_cells(int rh, int slots) { return slots * rh > 1024 ? slots * rh : 1024; }
-// (+ one bit per low-row cell, [slots][mask_words]: which cells of the global scratch took an add - only those are swapped out)
-__host__ __device__ inline int mask_words(int rl) { return (rl + 31) >> 5; }
-static size_t lds_bytes(int rows, int rh, int slots) {
-    return ((size_t)2 * N + (size_t)ring_cells(rh, slots) + (size_t)edge_cells(rows)) * 8 + (size_t)(4 * 64 + 4 * 8) * 16 + 1024 + 32 +
-           (size_t)slots * mask_words(rows - rh) * 4;
-}
 
 #define EXL_STAMP(slot)                                                            \
     if constexpr (STAMP) {                                                         \
@@ -579,32 +570,10 @@ __global__ __launch_bounds__(1024, 4) void exact_fused4096_lr_kernel(
 }
 #undef EXL_STAMP
 
-// How many of the R rows stay in LDS beside the planes (a multiple of 8; R when the whole ring fits)
-static int rows_in_lds(int rows, int slots) {
-    const size_t fixed = lds_bytes(rows, 0, slots) - (size_t)ring_cells(0, slots) * 8;
-    const size_t avail = (size_t)160 * 1024 > fixed ? (size_t)160 * 1024 - fixed : 0;
-    int rh = (int)(avail / ((size_t)slots * 8));
-    rh = rh > rows ? rows : (rh & ~7);
-    while (rh > 0 && lds_bytes(rows, rh, slots) > (size_t)160 * 1024) rh -= 8;
-    return rh < 0 ? 0 : rh;
-}
 }  // namespace exl
 
-// The shapes this kernel serves: N = 4096, rows a multiple of 4.  Returns RL, the number of low rows per slot that live in
-// the global scratch (0: the whole ring fits in LDS beside the planes), or -1.  Whether an AXIS is served is the caller's
-// decision: each of the frame's bins that lands below row RL costs a device-scope atomic instead of an LDS one
-// (emspec_api.cpp: exact_lr_rows - at most 6 % of the bins).
-static int exact_lr_skip(int n) { return n == 4096 ? 0 : (n == 2048 ? 1 : (n == 1024 ? 2 : -1)); }   // the kernel's S
-int exact_fused_lr_low_rows(int n, const ExactPlanDev& pl) {
-    if (diag_exact_records()) return -1;
-    const int sk = exact_lr_skip(n);
-    if (sk < 0 || pl.rows % 4 || pl.rows < 64 || pl.rows > 1024 || pl.D < 0 || pl.D > 1024) return -1;
-    const int slots = exl::lr_slots(sk, pl.D);
-    const int rh = exl::rows_in_lds(pl.rows, slots);
-    const int rl = pl.rows - rh;
-    if (rh < 8 || (rl & 3)) return -1;
-    return rl;
-}
+// (The shapes this kernel serves - N = 4096 / 2048 / 1024, rows a multiple of 4 - the rows that stay in LDS and RL, the low rows
+// per slot that live in the global scratch, and whether an AXIS is served: exact_lr_low_rows and exact_route, emspec_kernel_plan.h)
 
 // segments: the rounds-by-efficiency choice with this kernel's floor and pipeline fill (emspec_seg_plan.h)
 static int64_t exact_lr_seglen(int n, const ExactPlanDev& pl, int S, int64_t C) {
@@ -632,7 +601,7 @@ hipError_t launch_exact_fused_lr(int n, const ExactPlanDev& pl, const ExactDbMap
     if (skip > 0 && (stamps || stamp_groups)) return hipErrorNotSupported;   // the stamped build exists for N = 4096 only
     const int slots = exl::lr_slots(skip, pl.D);
     const int rh = pl.rows - rl;
-    if (rl < 0 || (rl & 3) || rh < 8 || exl::lds_bytes(pl.rows, rh, slots) > (size_t)160 * 1024) return hipErrorInvalidValue;
+    if (!exact_lr_split_ok(pl.rows, rl, slots)) return hipErrorInvalidValue;
     const int64_t seg = exact_lr_seglen(n, pl, S, C);
     const int64_t nseg = (C + seg - 1) / seg;
     if (!exact_fused_grid_ok(nseg, seg)) return hipErrorInvalidValue;
@@ -641,7 +610,7 @@ hipError_t launch_exact_fused_lr(int n, const ExactPlanDev& pl, const ExactDbMap
     if ((stamps || stamp_groups) && !stamps) return hipSuccess;
 #endif
     const SegPlan sp{(int)seg, 1 << 30, (int)seg, 0};
-    const size_t lds = exl::lds_bytes(pl.rows, rh, slots);
+    const size_t lds = exact_lr_lds_bytes(pl.rows, rh, slots);
     const uint32_t* l32 = reinterpret_cast<const uint32_t*>(lut);
     uint32_t* r32 = reinterpret_cast<uint32_t*>(rgba);
     // streams per launch: as many as the low-row scratch has slices for ([group][slots][rl]; emspec_seg_plan.h)

@@ -72,30 +72,15 @@ static constexpr int64_t diag_seglen() { return 0; }
 // (the specialised FAST kernels serve the plans of emspec_plan_is_fast, emspec_device.h: reassignment ON, log-spaced rows, and
 // a power floor that keeps every accumulated bin's 64 P inside the range of recip_normal)
 
-bool fused_supported(int n, int hop, int rows, int reassign) {
-    if (diag_no_fused()) return false;
-    // the default (r8) kernel is built for hop 256, 512 and 1024 (the diagnostic A/B variants for hop 256 only);
-    // N = 8192 (fused_n8192.hip.inc) for hop 512 and 1024; N = 16384 for any hop whose ring fits the register park
-    const bool rows_ok = rows % 4 == 0 && rows >= 64 && rows <= 1024;
-    if (n == f14::N) return fused_variant() == 0 && fused16384_supported(hop, rows, reassign);
-    if (n == f13::N) return fused_variant() == 0 && (hop == 512 || hop == 1024) && rows_ok;
-    const bool r8_hop = hop == 256 || ((fused_variant() == 0 || fused_variant() >= 3) && (hop == 512 || hop == 1024));
-    if (n == f8::N && r8_hop) return rows_ok;
-    if (n == 4096 || n == 2048 || n == 1024) {   // fused_small.hip.inc: any hop whose ring (2D + F column slots) fits in LDS
-        const int D = reassign ? (n + 2 * hop - 1) / (2 * hop) : 0;
-        return (fused_variant() == 0 || fused_variant() == 3) && rows_ok && hop >= 1 && hop <= n &&
-               fused_small_lds_bytes(rows, fused_small_slots(n, D)) <= (size_t)160 * 1024;
-    }
-    return false;
-}
+// the kernel family that serves the shape with this build's switches, or the records path (emspec_kernel_plan.h: fast_route)
+Route fused_route(int n, int hop, int rows, int reassign) { return fast_route(n, hop, rows, reassign, FastSwitches{diag_no_fused(), fused_variant()}); }
+bool fused_supported(int n, int hop, int rows, int reassign) { return !is_records(fused_route(n, hop, rows, reassign)); }
 
 hipError_t launch_fused(int n, const PlanDev& pl, const DbMap& m, const uint8_t* lut, const float* pcm, int64_t L,
                         int S, int64_t C, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st,
                         unsigned long long* stamps, int64_t* stamp_groups) {
-    const bool big_n = n == f14::N;
-    const bool r8_shape = n == f8::N && (pl.hop == 256 || pl.hop == 512 || pl.hop == 1024);
-    const bool small_n = (n == 4096 || n == 2048 || n == 1024) && !r8_shape;   // fused_small: ring sized from pl.D at run time
-    if (!fused_supported(n, pl.hop, pl.rows, pl.reassign) || (!small_n && !big_n && pl.D > n / (2 * pl.hop))) return hipErrorNotSupported;
+    const RouteKind kind = fused_route(n, pl.hop, pl.rows, pl.reassign).kind;
+    if (kind == RouteKind::records_f32 || !fused_reach_ok(kind, n, pl.hop, pl.D)) return hipErrorNotSupported;
     if (S <= 0 || C <= 0) return hipSuccess;
     if (S > 65535) return hipErrorInvalidValue;
 #ifndef EMSPEC_DIAG
@@ -106,8 +91,7 @@ hipError_t launch_fused(int n, const PlanDev& pl, const DbMap& m, const uint8_t*
 #ifdef EMSPEC_DIAG
     if (const char* ev = getenv("EMSPEC_SHARED")) force_shared = ev[0] == '1';   // lets one GPU exercise the plan
 #endif
-    const FusedSegPlan fp = fused_seg_plan(device_cus(), S, C, pl.D, small_n ? FusedKind::small_n : (big_n ? FusedKind::big_n : FusedKind::n4096_8192),
-                                           pl.shared, force_shared, diag_seglen());
+    const FusedSegPlan fp = fused_seg_plan(device_cus(), S, C, pl.D, fused_kind(kind), pl.shared, force_shared, diag_seglen());
     if (!fp.ok) return hipErrorInvalidValue;
     const SegPlan sp = fp.sp;
     const int64_t nseg = fp.nseg;
@@ -119,11 +103,11 @@ hipError_t launch_fused(int n, const PlanDev& pl, const DbMap& m, const uint8_t*
     auto go = [&](auto kernel, dim3 blk, size_t lds, auto... more) {
         return launch_k(kernel, grid, blk, lds, st, pl, m, l32, pcm, L, C, sp, db, r32, index, more...);
     };
-    if (big_n) {
+    switch (kind) {
+    case RouteKind::fused_16384:
         if (stamp_groups && !stamps) return hipSuccess;            // sizing call of the diagnostic entry point
         return launch_fused16384(grid, pl, m, l32, pcm, L, C, sp, db, r32, index, st, stamps);
-    }
-    if (small_n) {
+    case RouteKind::fused_small: {
         if (stamps || stamp_groups) return hipErrorNotSupported;   // no stamped build of this kernel
         const int slots = fused_small_slots(n, pl.D);
         auto go_small = [&](auto kernel) {
@@ -136,11 +120,12 @@ hipError_t launch_fused(int n, const PlanDev& pl, const DbMap& m, const uint8_t*
             return go_small(fused_small_pp_kernel<S_(), FA()>);
         }); });
     }
-    if (n == f13::N) {
+    case RouteKind::fused_8192:
         if (stamps || stamp_groups) return hipErrorNotSupported;   // no stamped build of this kernel
         return pick_int<512, 1024>(pl.hop, [&](auto H) { return pick_bool(fast, [&](auto FA) {
             return go(fused8192_kernel<H(), FA()>, block, fused8192_lds_bytes(pl.rows, pl.hop));
         }); });
+    default: break;   // fused_pp, below
     }
     // N = 4096 at hop 256 / 512 / 1024: a kernel family <HOP, STAMP, FAST>; name(H, ST, FA) gives the instantiation.  The
     // stamped (diagnostic) builds exist for hop 256 only, and stamp_groups alone is the sizing call of their entry point.

@@ -26,29 +26,9 @@
 // bandwidth (2 x 128 KB per frame) that nothing overlaps; without the conversion 23.8 ms.
 namespace emspec {
 
-namespace f14 {
-constexpr int LOG2N = 14, N = 16384, T = 1024;
-constexpr int NQ = 8;    // 8 float4 per thread park the 32 x 1024 ring cells that share the transform's region
-constexpr int FFT_BYTES = PaddedSize<N>::value * (int)sizeof(float2);
-// The ring starts RING_OFF bytes into the region, so that exactly NQ * 4096 cells (128 KB) lie inside the padded
-// transform buffer (136 KB) and the rest - up to 1024 cells, the 33rd slot at hop 512 - lies in RES_BYTES of its own
-// right behind it: resident, never parked (it used to take a 33rd register and the only spill of the frame loop).
-constexpr int PARKED_CELLS = NQ * 4 * 1024;
-constexpr int RING_OFF = FFT_BYTES - PARKED_CELLS * 4;
-constexpr int RES_BYTES = 4096;
-static_assert(RING_OFF >= 0 && RING_OFF % 16 == 0, "ring offset");
-}  // namespace f14
-
-static bool fused16384_supported(int hop, int rows, int reassign) {
-    if (hop < 1 || hop > f14::N) return false;
-    if (rows % 4 || rows < 64 || rows > 1024) return false;
-    const int D = reassign ? (f14::N + 2 * hop - 1) / (2 * hop) : 0;
-    const int64_t cells = (int64_t)(2 * D + 1) * rows;
-    return cells <= (int64_t)f14::PARKED_CELLS + f14::RES_BYTES / 4;
-}
-static size_t fused16384_lds_bytes(int rows) {
-    return (size_t)f14::FFT_BYTES + f14::RES_BYTES + (size_t)mid_tw_entries(f14::LOG2N) * sizeof(float2) + (size_t)(rows + 4) * 4 + 1024;
-}
+// (the f14:: sizes - the parked cells, the resident slot, where the ring starts in the transform's region - and the shapes and
+// dynamic LDS that follow from them: emspec_kernel_plan.h)
+static_assert(f14::FFT_BYTES == PaddedSize<f14::N>::value * (int)sizeof(float2), "the transform's region");
 
 namespace f14 {
 // (padded) position of spectrum sample Z[k] in the in-place buffer: bit-reversed

@@ -265,10 +265,6 @@ __global__ __launch_bounds__(1024, 4) void fused8192_kernel(
     finalize(jstop - 1 - D, sj - 1 - D, tid);          // the last frame's column (the loop's last barrier is behind us)
 }
 
-static size_t fused8192_lds_bytes(int rows, int hop) {
-    const int slots = 2 * (f13::N / (2 * hop)) + 1;
-    return (size_t)2 * f13::M * sizeof(float2) + (size_t)slots * rows * 4 + (size_t)(rows + 4) * 4 + 1024 +
-           (size_t)(7 * 64 + 7 * 8) * sizeof(float2);
-}
+// (dynamic LDS: fused8192_lds_bytes, emspec_kernel_plan.h)
 
 }  // namespace emspec

@@ -300,7 +300,6 @@ __global__ __launch_bounds__(1024, 4) void fused4096_pp_kernel(
     }
 }
 #undef EMSPEC_STAMP
-
-static size_t fused_pp_lds_bytes(int rows, int hop) { return fused_r8_lds_bytes(rows, hop) + 16; }
+// (dynamic LDS: fused_pp_lds_bytes, emspec_kernel_plan.h)
 
 }  // namespace emspec

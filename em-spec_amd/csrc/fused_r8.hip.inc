@@ -346,11 +346,6 @@ __global__ __launch_bounds__(1024, 4) void fused4096_r8_kernel(
     }
 }
 #undef EMSPEC_STAMP
-
-static size_t fused_r8_lds_bytes(int rows, int hop) {
-    const int slots = 2 * (f8::N / (2 * hop)) + 2;
-    return (size_t)2 * f8::N * sizeof(float2) + (size_t)slots * rows * 4 + (size_t)(rows + 4) * 4 + 1024 +
-           (size_t)(7 * 64 + 7 * 8) * sizeof(float2);
-}
+// (dynamic LDS: fused_r8_lds_bytes, emspec_kernel_plan.h)
 
 }  // namespace emspec

@@ -434,11 +434,7 @@ __global__ __launch_bounds__(1024, 4) void fused_small_pp_kernel(
     if (!h) __syncthreads();
 }
 
-// ring slots the kernel needs for reach D, and the dynamic LDS that takes
-static int fused_small_slots(int n, int D) { return 2 * D + 2 * (4096 / n); }   // n = 4096, 2048, 1024
-static size_t fused_small_lds_bytes(int rows, int slots) {
-    return (size_t)2 * 4096 * sizeof(float2) + (size_t)slots * rows * 4 + (size_t)(rows + 4) * 4 + 1024 +
-           (size_t)(7 * 64 + 7 * 8) * sizeof(float2) + 16;   // + the two arrival counters of the product form
-}
+// (ring slots the kernel needs for reach D, and the dynamic LDS that takes: fused_small_slots, fused_small_lds_bytes,
+// emspec_kernel_plan.h)
 
 }  // namespace emspec

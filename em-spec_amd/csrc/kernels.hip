@@ -36,7 +36,7 @@ static hipError_t allow_max_lds(const void* fn) {
     (void)hipGetDevice(&dev);
     std::lock_guard<std::mutex> g(mu);
     if (done.count({dev, fn})) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
     if (e == hipSuccess) done.insert({dev, fn});
     return e;
 }
@@ -108,11 +108,7 @@ __device__ __forceinline__ int natpos(int k) {
     else return k;
 }
 
-constexpr int mid_tw_entries(int log2n) {
-    int s0 = 4, n = 0;
-    while (log2n - s0 > 4) { n += 15 << (log2n - s0 - 4); s0 += 4; }
-    return (n + 1) & ~1;   // keep the next region 16-byte aligned
-}
+// (mid_tw_entries, their count: emspec_kernel_plan.h)
 template <int LOG2N, int S0>
 __device__ __forceinline__ void stage_mid_twiddles(float2* stw, const float2* __restrict__ tw, int t, int nthreads) {
     if constexpr (LOG2N - S0 > 4) {
@@ -351,8 +347,8 @@ template <int LOG2N>
 static hipError_t launch_frames_t(const PlanDev& pl, const float* pcm, int64_t L, int S, int64_t frame0,
                                   int64_t nframes, const FrameSinks& sk, hipStream_t st) {
     constexpr int N = 1 << LOG2N;
-    const size_t lds = (size_t)(PaddedSize<N>::value + mid_tw_entries(LOG2N)) * sizeof(float2) + (size_t)(pl.rows + 1) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const size_t lds = frames_lds_bytes(LOG2N, pl.rows);
+    if (lds > kLdsBytes) return hipErrorInvalidValue;
     // the sink combination picks the build: dump only, records only, or the run-time form
     const bool plain = !sk.hist;
     const int sink = sk.live.streams ? 3 : (plain && sk.power && !sk.records) ? 1 : ((plain && sk.records && !sk.power) ? 2 : 0);
