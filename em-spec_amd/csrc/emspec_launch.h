@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "emspec_band_plan.h"
 #include "emspec_device.h"
 #include "emspec_live_plan.h"
 #include "emspec_wire_plan.h"
@@ -133,6 +134,15 @@ hipError_t launch_postprocess(const float* db, float* out_db, uint8_t* rgba, uin
 hipError_t launch_multires_compose(const float* lo, const float* hi, int S, int64_t C, int R, int split, int shift,
                                    const DbMap& dm, const uint8_t* lut, float* db, uint8_t* rgba, uint8_t* index,
                                    hipStream_t st);
+// multi-band batch (multiband.hip.inc): up to kMaxBands bands' raw dB -> the composed columns [S][C][R], outputs as above.  Band k's
+// plane is [S][C + 2 shift[k]][rows[k]] and serves the quads of rows from q0[k] on, up to the next band's q0; an unused slot has
+// q0 = R / 4 (no quad reaches it) and any valid plane
+struct BandSrc {
+    const float* plane[kMaxBands];
+    int shift[kMaxBands], rows[kMaxBands], q0[kMaxBands];
+};
+hipError_t launch_multiband_compose(const BandSrc& b, int S, int64_t C, int R, const DbMap& dm, const uint8_t* lut, float* db,
+                                    uint8_t* rgba, uint8_t* index, hipStream_t st);
 // live multi-stream calls (live_launch.hip.inc): flush of pending columns, display post-process of a launch's columns.
 // The frame launches themselves go through launch_frames / launch_exact_frames with sinks.live set and
 // nframes = (largest per-stream frame count) + 1.

@@ -58,6 +58,9 @@ REDUCE_SYMBOLS = SYMBOLS[-6:-3]
 PEAKS_SYMBOLS = SYMBOLS[-11:-6]
 # the waveform envelope's: likewise (tools/wave_rate.py times the parent commit's library next to this build)
 WAVE_SYMBOLS = SYMBOLS[-14:-11]
+# the multi-band batch's: likewise (tools/multiband_rate.py may load a library built before them); appended behind the slices above
+MULTIBAND_SYMBOLS = ["emspec_multiband_shifts", "emspec_multiband_columns", "emspec_batch_multiband", "emspec_batch_multiband_device"]
+SYMBOLS = SYMBOLS + MULTIBAND_SYMBOLS
 
 
 class Config(C.Structure):
@@ -339,6 +342,14 @@ def load(diag=False):
                                            C.c_void_p]
         lib.emspec_wave_host.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         lib.emspec_set_wave_out.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    if all(hasattr(lib, sym) for sym in MULTIBAND_SYMBOLS):
+        lib.emspec_multiband_shifts.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        lib.emspec_multiband_columns.restype = C.c_int64
+        lib.emspec_multiband_columns.argtypes = [C.c_int64, C.c_int32, C.c_void_p, C.c_int32]
+        lib.emspec_batch_multiband.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                               C.c_int32, C.c_int32, C.POINTER(Out)]
+        lib.emspec_batch_multiband_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                                      C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _libs[diag] = lib
     return lib
 
@@ -406,6 +417,28 @@ def multires_shift(n_low, n_high, hop):
     """The high band's column shift (n_low - n_high) / (2 hop) of a multi-resolution batch, -1 for a shape that is not
     accepted (emspec_multires_shift)."""
     return int(load().emspec_multires_shift(n_low, n_high, hop))
+
+
+def _i32(values):
+    """A ctypes int32 array of the values (kept alive by the caller for the length of the call)."""
+    values = [int(v) for v in values]
+    return (C.c_int32 * max(len(values), 1))(*values)
+
+
+def multiband_shifts(n, hop):
+    """The column shifts (n[0] - n[k]) / (2 hop) of a multi-band batch's bands as a tuple, None for a shape (sizes, hop) that is
+    not accepted (emspec_multiband_shifts)."""
+    n = list(n)
+    out = (C.c_int32 * max(len(n), 1))()
+    if load().emspec_multiband_shifts(len(n), _i32(n), hop, out) != 0:
+        return None
+    return tuple(out[:len(n)])
+
+
+def multiband_columns(L, n, hop):
+    """Columns of a multi-band batch (emspec_multiband_columns): num_columns(L, n[0], hop), -1 for a shape that is not accepted."""
+    n = list(n)
+    return int(load().emspec_multiband_columns(L, len(n), _i32(n), hop))
 
 
 def warped_edges_hz(rows, fmin_hz, fmax_hz, low_end_boost=1.0, freq_scale=1.0):
@@ -736,7 +769,7 @@ class Engine:
         return out
 
     def set_wave_out(self, wave):
-        """emspec_set_wave_out: while set, batch(), batch_packed(), batch_pcm(), batch_pcm_packed(), batch_multires() and
+        """emspec_set_wave_out: while set, batch(), batch_packed(), batch_pcm(), batch_pcm_packed(), batch_multires(), batch_multiband() and
         batch_peaks() also write the envelope of their streams to `wave`, a C-contiguous float32 numpy array of
         streams x delivered columns x 2 values or more (pageable, or a PinnedArray's array); None clears it.  The engine keeps a
         reference to the array while it is set."""
@@ -785,6 +818,37 @@ class Engine:
         self._chk(self._lib.emspec_batch_multires_device(self._h, ptr(pcm_t), S, L, n_low, n_high, hop, split_row,
                                                          int(bool(reassign)), ptr(db), ptr(rgba), ptr(index),
                                                          C.c_void_p(st.cuda_stream)))
+
+    # -- multi-band batch: up to four FFT sizes n[0] > n[1] > ..., band k from split_rows[k - 1] up ---------
+    def batch_multiband(self, pcm, n, split_rows, hop, reassign=True, want=("db",)):
+        """Host buffers in and out (emspec_batch_multiband): [S][C][rows] outputs as in batch(), C = multiband_columns."""
+        pcm = np.ascontiguousarray(pcm, np.float32)
+        if pcm.ndim == 1:
+            pcm = pcm[None]
+        S, L = pcm.shape
+        n, split_rows = list(n), list(split_rows)
+        Cn = self.out_columns(max(multiband_columns(L, n, hop), 0))
+        db = np.empty((S, Cn, self.rows), np.float32) if "db" in want else None
+        rgba = np.empty((S, Cn, self.rows, 4), np.uint8) if "rgba" in want else None
+        idx = np.empty((S, Cn, self.rows), np.uint8) if "index" in want else None
+        out = Out(_np_ptr(db), _np_ptr(rgba), _np_ptr(idx))
+        self._chk(self._lib.emspec_batch_multiband(self._h, _np_ptr(pcm), S, L, len(n), _i32(n), _i32(split_rows), hop,
+                                                   int(bool(reassign)), C.byref(out)))
+        return {"db": db, "rgba": rgba, "index": idx}
+
+    def batch_multiband_device(self, pcm_t, n, split_rows, hop, reassign=True, db=None, rgba=None, index=None, stream=None):
+        """Device-resident torch tensors (emspec_batch_multiband_device), as batch_device(); does not synchronise."""
+        import torch
+        assert pcm_t.is_cuda and pcm_t.dtype == torch.float32 and pcm_t.is_contiguous() and pcm_t.dim() == 2
+        S, L = pcm_t.shape
+        n, split_rows = list(n), list(split_rows)
+        st = stream if stream is not None else torch.cuda.current_stream(pcm_t.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        for t in (db, rgba, index):
+            assert t is None or (t.is_cuda and t.is_contiguous())
+        self._chk(self._lib.emspec_batch_multiband_device(self._h, ptr(pcm_t), S, L, len(n), _i32(n), _i32(split_rows), hop,
+                                                          int(bool(reassign)), ptr(db), ptr(rgba), ptr(index),
+                                                          C.c_void_p(st.cuda_stream)))
 
     # -- multi-GPU: RCCL communicator + gather of finished palette-index columns ----
     def comm_init(self, comm_id, rank, world):

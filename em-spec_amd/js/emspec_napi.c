@@ -377,6 +377,54 @@ static napi_value BatchMultires(napi_env env, napi_callback_info info) {
     return r;
 }
 
+/* An Int32Array of 1..8 values (FFT sizes or split rows of the multi-band batch) -> vals[8], *count; the library judges the count. */
+static int get_int32_list(napi_env env, napi_value v, int32_t* vals, int32_t* count) {
+    void* p; size_t len;
+    if (!get_typed(env, v, napi_int32_array, &p, &len, 0) || len > 8) return 0;
+    memset(vals, 0, 8 * sizeof(int32_t));
+    if (len) memcpy(vals, p, len * sizeof(int32_t));
+    *count = (int32_t)len;
+    return 1;
+}
+
+/* batchMultiband(handle, pcm:Float32Array(S*L), S, L, fftSizes:Int32Array(K), splitRows:Int32Array(K-1), hop, reassign, outDb[, outRgba,
+ * outIndex]) -> columns.  emspec_batch_multiband: fftSizes[k] for the rows from splitRows[k-1] up, on one column grid (synchronous). */
+static napi_value BatchMultiband(napi_env env, napi_callback_info info) {
+    size_t argc = 11; napi_value argv[11];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 9) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "batchMultiband(handle, pcm, S, L, fftSizes, splitRows, hop, reassign, outDb[, outRgba, outIndex])"); return NULL; }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    void* pcm; size_t plen;
+    if (!get_typed(env, argv[1], napi_float32_array, &pcm, &plen, 0)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "pcm must be a Float32Array"); return NULL; }
+    int32_t S, hop, K = 0, nsplit = 0, n[8], split[8]; int64_t L; bool reassign;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[2], &S));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[3], &L));
+    if (!get_int32_list(env, argv[4], n, &K) || !get_int32_list(env, argv[5], split, &nsplit)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "fftSizes and splitRows must be Int32Arrays of at most 8 values"); return NULL; }
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[6], &hop));
+    NAPI_OK_OR_RETURN(env, napi_coerce_to_bool(env, argv[7], &argv[7]));
+    NAPI_OK_OR_RETURN(env, napi_get_value_bool(env, argv[7], &reassign));
+    if (S < 1 || L < 1 || (size_t)S * (size_t)L != plen) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "pcm.length must equal S*L"); return NULL; }
+    if (K >= 2 && K <= 4 && nsplit != K - 1) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "splitRows must hold one row fewer than fftSizes"); return NULL; }
+    /* C <= 0: a shape (or L) the library rejects, with a message naming the rule, before it touches any output */
+    const int64_t C = out_columns(h, emspec_multiband_columns(L, K, n, hop));
+    size_t l0 = 0, l1 = 0, l2 = 0; void *p0 = NULL, *p1 = NULL, *p2 = NULL;
+    if (!get_typed(env, argv[8], napi_float32_array, &p0, &l0, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outDb must be a Float32Array"); return NULL; }
+    if (argc > 9 && !get_typed(env, argv[9], napi_uint8_array, &p1, &l1, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outRgba must be a Uint8Array"); return NULL; }
+    if (argc > 10 && !get_typed(env, argv[10], napi_uint8_array, &p2, &l2, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outIndex must be a Uint8Array"); return NULL; }
+    size_t cells = 0;
+    if (p0) cells = l0; else if (p1) cells = l1 / 4; else if (p2) cells = l2;
+    if (C > 0 && (cells != (size_t)S * (size_t)C * (size_t)h->rows || (p1 && l1 != 4 * cells) || (p2 && l2 != cells) || (p0 && l0 != cells))) {
+        napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "output arrays must hold exactly S*columns*rows cells, rows = the engine's row count (rgba: 4 bytes per cell)");
+        return NULL;
+    }
+    emspec_out out; memset(&out, 0, sizeof(out));
+    out.db = (float*)p0; out.rgba = (uint8_t*)p1; out.index = (uint8_t*)p2;
+    int rc = emspec_batch_multiband(h->e, (const float*)pcm, S, L, K, n, split, hop, reassign ? 1 : 0, &out);
+    if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
+    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int64(env, C, &r));
+    return r;
+}
+
 /* batchPacked(handle, pcm:Float32Array(S*L), S, L, fftSize, hop, reassign, wire:Uint8Array, offsets:Float64Array(S+1)) -> columns
  * per stream.  emspec_batch_packed: the palette-index columns cross PCIe as one lossless wire image per stream; stream s
  * is wire.subarray(offsets[s], offsets[s+1]) (offsets as doubles: exact below 2^53). */
@@ -1268,6 +1316,34 @@ static napi_value MultiresColumns(napi_env env, napi_callback_info info) {
     return r;
 }
 
+/* multibandColumns(L, fftSizes:Int32Array, hop) -> columns of a multi-band batch, -1 for a shape it does not accept */
+static napi_value MultibandColumns(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    int64_t L = 0; int32_t hop = 0, K = 0, n[8];
+    if (argc < 3 || !get_int32_list(env, argv[1], n, &K)) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "multibandColumns(L, fftSizes:Int32Array, hop)"); return NULL; }
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[0], &L));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[2], &hop));
+    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int64(env, emspec_multiband_columns(L, K, n, hop), &r));
+    return r;
+}
+
+/* multibandShifts(fftSizes:Int32Array, hop) -> Int32Array of the bands' column shifts, null for a shape that is not accepted */
+static napi_value MultibandShifts(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    int32_t hop = 0, K = 0, n[8], shifts[8];
+    if (argc < 2 || !get_int32_list(env, argv[0], n, &K)) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "multibandShifts(fftSizes:Int32Array, hop)"); return NULL; }
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[1], &hop));
+    napi_value r;
+    if (emspec_multiband_shifts(K, n, hop, shifts) != 0) { NAPI_OK_OR_RETURN(env, napi_get_null(env, &r)); return r; }
+    napi_value ab; void* data;
+    NAPI_OK_OR_RETURN(env, napi_create_arraybuffer(env, (size_t)K * sizeof(int32_t), &data, &ab));
+    memcpy(data, shifts, (size_t)K * sizeof(int32_t));
+    NAPI_OK_OR_RETURN(env, napi_create_typedarray(env, napi_int32_array, (size_t)K, ab, 0, &r));
+    return r;
+}
+
 static napi_value LatencyColumns(napi_env env, napi_callback_info info) {
     size_t argc = 3; napi_value argv[3];
     NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -1399,6 +1475,9 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"latencyColumns", NULL, LatencyColumns, NULL, NULL, NULL, napi_default, NULL},
         {"multiresColumns", NULL, MultiresColumns, NULL, NULL, NULL, napi_default, NULL},
         {"batchMultires", NULL, BatchMultires, NULL, NULL, NULL, napi_default, NULL},
+        {"multibandColumns", NULL, MultibandColumns, NULL, NULL, NULL, napi_default, NULL},
+        {"multibandShifts", NULL, MultibandShifts, NULL, NULL, NULL, napi_default, NULL},
+        {"batchMultiband", NULL, BatchMultiband, NULL, NULL, NULL, napi_default, NULL},
         {"commUniqueId", NULL, CommUniqueId, NULL, NULL, NULL, napi_default, NULL},
         {"commInit", NULL, CommInit, NULL, NULL, NULL, napi_default, NULL},
         {"batchGather", NULL, BatchGather, NULL, NULL, NULL, napi_default, NULL},

@@ -299,6 +299,20 @@ class Engine {
                                 out.index);
   }
 
+  /**
+   * Multi-band columns (emspec_batch_multiband, DESIGN.md §3.13): two to four FFT sizes, opts.fftSizes[0] > fftSizes[1] > ...
+   * (each 1024 ... 16384), fftSizes[k] for the rows from the k-th split up, on the longest FFT's column grid - e.g.
+   * [16384, 4096, 1024] with splitHz [250, 2000].  opts: {fftSizes, splitHz | splitRows (one fewer than fftSizes), hop,
+   * reassign = true}; each splitHz picks the first admissible row whose lower edge is >= it.  out as in computeColumns,
+   * S * C * rows cells with C = multibandColumns(L, fftSizes, hop).  Synchronous; returns C.
+   */
+  computeColumnsMultiband(pcm, S, L, opts, out) {
+    const splits = opts.splitRows !== undefined ? opts.splitRows : Array.from(opts.splitHz, (hz) => this.splitRowForHz(hz));
+    const reassign = opts.reassign === undefined ? true : !!opts.reassign;
+    return native.batchMultiband(this._h, pcm, S, L, Int32Array.from(opts.fftSizes), Int32Array.from(splits), opts.hop, reassign,
+                                 out.db, out.rgba, out.index);
+  }
+
   /** The smallest admissible split row (a multiple of 4 in [64, rows - 64]) whose lower edge is >= hz. */
   splitRowForHz(hz) {
     const e = this.getRowEdges();
@@ -489,6 +503,12 @@ module.exports = {
   /** Columns of a multi-resolution batch (emspec_multires_columns): multiresColumns(L, lowFftSize, fftSize, hop), -1 for a
    *  shape it does not accept. */
   multiresColumns: native.multiresColumns,
+  /** Columns of a multi-band batch (emspec_multiband_columns): multibandColumns(L, fftSizes, hop), -1 for a shape that is not
+   *  accepted. */
+  multibandColumns: (L, fftSizes, hop) => native.multibandColumns(L, Int32Array.from(fftSizes), hop),
+  /** The bands' column shifts (fftSizes[0] - fftSizes[k]) / (2 hop) as an Array, null for a shape that is not accepted
+   *  (emspec_multiband_shifts). */
+  multibandShifts: (fftSizes, hop) => { const r = native.multibandShifts(Int32Array.from(fftSizes), hop); return r ? Array.from(r) : null; },
   /** 'emspec abi=2 sources=<sha16> arch=gfx950': what the loaded libemspec was built from. */
   buildInfo: native.buildInfo,
 };

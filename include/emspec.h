@@ -475,7 +475,8 @@ int emspec_wire_unpack_host(const uint8_t* wire, int64_t wire_bytes, int64_t col
  * exact in either arithmetic mode: the reduced bytes follow from the full-rate bytes.  Layouts are those of the entry with Cr in
  * place of the column count; column g is centred in time on its group (the host maps pixels to time with f * hop).
  * Honoured by emspec_batch_device, emspec_batch, emspec_batch_packed, emspec_batch_pcm, emspec_batch_pcm_packed,
- * emspec_batch_multires, emspec_batch_multires_device and emspec_batch_gather (whose gathered layout is [world][S][Cr][rows]).
+ * emspec_batch_multires, emspec_batch_multires_device, emspec_batch_multiband, emspec_batch_multiband_device and
+ * emspec_batch_gather (whose gathered layout is [world][S][Cr][rows]).
  * The packed entries pack the REDUCED columns: the header's column count is Cr, wire_capacity = streams x emspec_wire_bound(Cr,
  * rows) always suffices, and the 2^32-cell limit applies to Cr x rows.  The device entries keep a chunk of streams' full-rate
  * columns in an engine workspace bounded like the records path's (1 byte per cell when only index / RGBA are asked for, 4 more
@@ -543,6 +544,39 @@ int emspec_batch_multires(emspec_engine* e, const float* pcm, int32_t S, int64_t
 int emspec_batch_multires_device(emspec_engine* e, const float* pcm_dev, int32_t S, int64_t L, int32_t n_low,
                                  int32_t n_high, int32_t hop, int32_t split_row, int32_t reassign,
                                  float* db_dev, uint8_t* rgba_dev, uint8_t* index_dev, void* hip_stream);
+
+/*
+ * Multi-band batch: the image above with up to four FFT sizes, the constant-Q-like ladder - e.g. 16384 below
+ * 250 Hz, 4096 up to 2 kHz and 1024 above, so that the bass resolves to 3 Hz while a hi-hat keeps its column.  `bands` = K,
+ * 2 <= K <= 4, FFT sizes n[0] > n[1] > ... > n[K-1], each in {1024, 2048, 4096, 8192, 16384}; ONE hop and ONE reassign for all
+ * bands; K - 1 split rows split_rows[0] < ... < split_rows[K-2].  Band k owns the rows [lo_k, hi_k), lo_0 = 0, lo_k =
+ * split_rows[k-1], hi_k = split_rows[k], hi_{K-1} = rows, and with shift[k] = (n[0] - n[k]) / (2 hop)
+ *     image[s][c][r] = single(n[k])[s][c + shift[k]][r]      for lo_k <= r < hi_k,  c in [0, columns)
+ * where columns = emspec_num_columns(L, n[0], hop) and single(n) is what emspec_batch delivers at that n on the same engine and
+ * row table (same hop and reassign): column c is centred at sample c * hop + n[0] / 2 in every band.  dB, palette index and RGBA
+ * are single(n[k])'s bytes (EXACT mode: bit for bit); with the display post-process on (emspec_set_display) it runs once over
+ * the composed raw dB, by the law of a single-resolution batch.  For K = 2 the image is that of emspec_batch_multires.
+ * Accepted: K in 2..4; sizes from the set above, strictly decreasing; 1 <= hop <= n[K-1]; every shift[k] an integer; every split
+ * row a multiple of 4; every band at least 64 rows high (split_rows[0] >= 64, split_rows[k] - split_rows[k-1] >= 64, rows -
+ * split_rows[K-2] >= 64); L >= n[0]; S in 1..65535.  Anything else is EMSPEC_ERR_INVALID_ARG with a message naming the rule; the
+ * engine stays usable.
+ * emspec_multiband_shifts: 0 and, when shifts_out is not NULL, the K shifts - or -1 for a shape (bands, n, hop) not accepted.
+ * emspec_multiband_columns: the column count, 0 when L < n[0], -1 for a shape that is not accepted.
+ * emspec_batch_multiband / _device: as emspec_batch_multires / _device in every other respect - any output NULL; the device entry
+ *   is enqueued on hip_stream and does not synchronise; the host entry takes page-locked or pageable buffers and runs the host
+ *   pipeline over units of whole streams.  Both honour emspec_set_time_reduce and emspec_set_display; the host entry honours
+ *   emspec_set_wave_out with the envelope on the n[0] column grid.  The bands' raw dB share the two-band batch's engine workspace.
+ * Single-resolution and two-band results on the same engine are not affected by a multi-band call.
+ * Not offered: a live multi-band session (the live session stays two-band); a multi-band form of emspec_batch_gather, of the
+ * packed entries and of the PCM entries; more than four bands; per-band hops.
+ */
+int emspec_multiband_shifts(int32_t bands, const int32_t* n, int32_t hop, int32_t* shifts_out /* [bands], may be NULL */);
+int64_t emspec_multiband_columns(int64_t L, int32_t bands, const int32_t* n, int32_t hop);
+int emspec_batch_multiband_device(emspec_engine* e, const float* pcm_dev, int32_t S, int64_t L, int32_t bands, const int32_t* n,
+                                  const int32_t* split_rows /* [bands-1] */, int32_t hop, int32_t reassign, float* db_dev,
+                                  uint8_t* rgba_dev, uint8_t* index_dev, void* hip_stream);
+int emspec_batch_multiband(emspec_engine* e, const float* pcm, int32_t S, int64_t L, int32_t bands, const int32_t* n,
+                           const int32_t* split_rows, int32_t hop, int32_t reassign, const emspec_out* out);
 
 /*
  * Multi-resolution LIVE session: the image above, column by column while the audio arrives.  These
@@ -732,7 +766,8 @@ int emspec_position_hz(emspec_engine* e, float pos, double* hz);
  * The pair is a function of the window's bits alone: it does not depend on the order of evaluation, on how the work is split,
  * or on the engine's mode, and the pair at factor f is the key-min / key-max of the f = 1 pairs of its group (the peak-hold
  * rule of the reduced columns it sits under).  For the PCM entries the samples are the decoded, mixed float32 values of the
- * views; for emspec_batch_multires the column grid is the long band's, n = n_low.
+ * views; for emspec_batch_multires the column grid is the long band's, n = n_low
+ * (emspec_batch_multiband: n = n[0]).
  * NOT for the live calls (emspec_columns, emspec_push_samples*): a live host holds the hop it has just pushed, and the pair of
  * column c would have to be kept D columns until c is emitted.  No RMS or other sum: a float sum depends on its order.
  */
@@ -750,7 +785,7 @@ int emspec_wave_device(emspec_engine* e, const float* pcm_dev, int32_t S, int64_
 /* The same definition in plain C++ on host arrays: no engine, no device.  The message of a refusal: emspec_last_error(NULL). */
 int emspec_wave_host(const float* pcm, int32_t S, int64_t L, int32_t n, int32_t hop, int32_t factor, emspec_wave* wave_out);
 /*
- * While set, every entry that runs the host pipeline - emspec_batch, _packed, _pcm, _pcm_packed, _multires and
+ * While set, every entry that runs the host pipeline - emspec_batch, _packed, _pcm, _pcm_packed, _multires, _multiband and
  * emspec_batch_peaks - also writes the envelope of its streams to wave_out[streams][Cr], in the same pass, from each unit's
  * staged samples: f = the engine's time reduction, streams = S, or sources x views for the PCM entries.  capacity counts
  * pairs; a call with streams x Cr > capacity returns EMSPEC_ERR_INVALID_ARG before anything runs.  wave_out is 4-byte aligned
