@@ -519,15 +519,14 @@ def test_exact_n16384_full_size_spot_checks_against_bit_model(xengine):
     assert chk == (int(idx.sum(dtype=torch.int64).item()), float(db.double().sum().item()))
 
 
-@pytest.mark.parametrize("n,hop,S,frames", [(16384, 512, 5, 70), (8192, 512, 4, 90), (4096, 128, 3, 120)])
-def test_exact_record_path_stream_chunks(n, hop, S, frames, monkeypatch):
+@pytest.mark.parametrize("n,hop", [(16384, 512), (8192, 512), (4096, 128)])
+def test_exact_record_path_stream_chunks(n, hop, monkeypatch):
     """The shapes that still run as two kernels with per-bin records in HBM (N != 4096, or N = 4096 at a hop whose u64 ring does
-    not fit in LDS) process their streams in chunks so that the record workspace stays bounded; with a forced 64 MB budget the
-    batch below takes several chunks (one or two streams each) - bytes equal to the bit model across the chunk boundaries."""
-    monkeypatch.setenv("EMSPEC_RECORD_BUDGET_MB", "64")
-    pcm = _pcm(n, hop, frames, S=S, extra=3)
-    with emspec.Engine(mode=emspec.MODE_EXACT, diag=True) as e:
-        assert not e.fused(n, hop, True)
-        out = e.batch(pcm, n, hop, True, want=("db", "index"))
-    odb, _, oidx, _ = O.batch_exact(O.make_cfg(n, hop, True), pcm, want=("db", "index"))
-    assert np.array_equal(out["index"], oidx) and np.array_equal(out["db"].view(np.uint32), odb.view(np.uint32))
+    not fit in LDS) process their streams in chunks so that the record workspace stays bounded.  Five streams of 25 - 31 columns
+    at a budget that holds 2.25 - 2.75 of them run as chunks (2, 2, 1), at budget 0 as five chunks of one: dB bits, index and RGBA
+    equal to the bit model and to the unbudgeted run across the chunk boundaries.  (Until this test was rewritten it forced a
+    64 MB budget on 3 - 5 streams of 2.8 - 6.6 MiB of records each: one chunk.)  The cases are tests/test_gpu_chunks.py's, which
+    prints the chunk lists and checks first that the diagnostic library - the only one that reads the budget - is loaded."""
+    import test_gpu_chunks
+    test_gpu_chunks.test_the_diagnostic_library_is_the_one_loaded()
+    test_gpu_chunks.run_exact_records(n, hop, monkeypatch)
