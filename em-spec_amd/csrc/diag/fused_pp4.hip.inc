@@ -1,45 +1,9 @@
-// fused_pp.hip.inc — fused batch kernel for N = 4096 (hop 256, 512 or 1024), the two 8-wave teams HALF AN ITERATION
-// APART.  The product path since round 3; in its present form (spectrum reads in role 0) since round 4.
-// Included by fused.hip.inc after fused_r8.hip.inc (same LDS images, swizzle and FFT helpers: namespace f8).  The arithmetic
-// between the FFT and the output arrays is the one definition of fused_common.hip.inc (finalize_ring_quad, read_split6); the
-// four-bin stage is still spelled out here, in the order of fused_common's bins4 - calling it reschedules this kernel
-// (profiles/refactor_fused_common_isa.txt), so it waits for an A/B measurement.
-//
-// fused4096_r8_kernel runs its two frames in lock step: all 16 waves stream LDS in the FFT passes, then all 16 waves
-// issue VALU in the per-bin stage, with three workgroup barriers per two frames - and a timing-only build without those
-// barriers runs 21 % faster (docs/HISTORY.md §4.1e): what the barriers cost is not the instruction but the coupling of
-// sixteen waves to the slowest one three times per iteration, and the loss of overlap between LDS-bound and VALU-bound
-// phases.  Here team h = 0 (waves 0-7, even frames) and team 1 (odd frames) alternate roles every half-iteration k:
-//     role 0 (k + h even): passes B, C, D of frame j0 + k | arrive | finalise column j0 + k - 2 - D (the team's first four
-//                          waves) | wait for the team | the 12 spectrum reads of the thread's bins + conjugate split
-//     role 1 (k + h odd) : per-bin stage of frame j0 + k - 1 FROM REGISTERS, scatter, pass A of frame j0 + k + 1 and its write
-// so every SIMD always holds two waves of each kind.  One workgroup barrier per half-iteration orders write -> pass B (the
-// team leaving role 1) and spectrum reads -> pass-A write (the team leaving role 0: its buffer is free the moment it enters
-// role 1).  The third ordering, pass D -> spectrum reads, is inside role 0 of one team: an arrival counter in LDS (one
-// ds_add per wave after its pass-D stores, one poll before its reads; the finalize sits between the two; every wave of the
-// team arrives before it polls, so the wait always ends - the spin is bounded all the same).
-// The split spectra (24 floats: Y and T at the thread's six positions) cross the barrier in registers.  The loop body is one
-// (role 0, role 1) pair per team - team 1 enters through one extra barrier, team 0 leaves through one - so that array is
-// local to the body and nothing is carried around the loop for it (123 VGPRs, no scratch).
-// Round 3's form read the spectra at the start of role 1 (arrival counter between those reads and the pass-A write): role 1
-// was the long role (5.4 k cycles against 4.4 k), and its first instructions were twelve LDS reads queued behind the other
-// team's passes.  Moving the reads - not more: handing over the stencils or the dot products instead (24 or 12 floats)
-// measured 9.14 / 9.15 ms against 9.04 - A/B on one box: 9.32 -> 9.02 ms, bit-identical palette indices
-// (diag/fused_pp3.hip.inc keeps the old form as variant "pp3").
-// Passes B, C and D issue their stores as their data is ready (f8::pass8_store_as_you_go, fused_r8.hip.inc): two ds_write_b64
-// behind each pair of the last stage instead of the four to eight back to back the compiler otherwise leaves at a pass's end,
-// in front of the next pass's reads.  The same instructions in another order: 9.06 -> 8.93 ms, A/B on one box;
-// diag/fused_pp4.hip.inc keeps the stores-at-the-end form as variant "pp4".  Pass A's write in role 1 stays clustered in front
-// of the barrier: spreading it as well measured no gain alone (9.05) and 8.97 together with the others (docs/HISTORY.md §20).
-// Ring: at half-iteration k the column j0 + k - 2 - D is finalised by the role-0 team (its last contributor, frame
-// j0 + k - 2, was scattered by that team at k - 1) while the role-1 team scatters frame j0 + k - 1, which reaches no
-// lower than column j0 + k - 1 - D: 2D + 2 slots, as in the lock-step kernel.
-// Measured and not kept (rounds 3-4, on the round-3 form): pass A of the OTHER team's next frame at the end of role 0
-// (9.78 vs 9.15 ms); the finished column's cells two per thread over all eight waves of the role-0 team (9.55 vs 9.15 ms - the
-// first four waves finish passes B, C, D ahead of the other four anyway, so the finalize fills their lead); deferring a
-// thread's fourth accumulate to its team's next role with a 2D + 3 slot ring (no change - the wait is the VARIANCE of the
-// slowest of sixteen waves, not the difference of the means); the halo spectra by DPP: not built - with the lanes of a wave
-// 32 bins apart (worth 4.6 %, fused_r8) the neighbouring group lives in another WAVE.
+// diag/fused_pp4.hip.inc — fused4096_pp_kernel as it was the product from round 4 until passes B, C and D began to issue
+// their stores pair by pair (fused_pp.hip.inc, f8::pass8_store_as_you_go), kept as A/B variant "pp4": every pass computes its
+// eight points with stages8 / fft_stages and then stores them, and the compiler clusters those stores at the pass's end (three
+// or four back to back, twice per pass, the last four in front of the next pass's reads).  Same arithmetic, LDS images, ring
+// schedule, roles and syncs as the product kernel - fused_pp.hip.inc describes them; the two differ in the order of
+// independent instructions only.
 namespace emspec {
 
 // stamped (diagnostic) build, slots: 0 finalize | 1 passes B C D | 2 bins | 3 scatter + next pass A | 4 spectrum reads +
@@ -51,7 +15,7 @@ namespace emspec {
         last_ = now_;                                                             \
     }
 template <int HOP, bool STAMP, bool FAST = false>
-__global__ __launch_bounds__(1024, 4) void fused4096_pp_kernel(
+__global__ __launch_bounds__(1024, 4) void fused4096_pp4_kernel(
     PlanDev pl, DbMap dm, const uint32_t* __restrict__ lut, const float* __restrict__ pcm, int64_t L, int64_t C,
     SegPlan sp, float* __restrict__ db, uint32_t* __restrict__ rgba, uint8_t* __restrict__ index,
     unsigned long long* __restrict__ stamps) {
@@ -156,17 +120,23 @@ __global__ __launch_bounds__(1024, 4) void fused4096_pp_kernel(
             // pass B = stages 3..5 : p = hi*512 + i*64 + lo
 #pragma unroll
             for (int i = 0; i < 8; ++i) v[i] = fb[posB[i]];
-            pass8_store_as_you_go(bfly8(v, TwLdsSym<64>{stwB + (tt & 63)}), [&](int i) { fb[posB[i]] = v[i]; });
+            stages8(v, TwLdsSym<64>{stwB + (tt & 63)});
+#pragma unroll
+            for (int i = 0; i < 8; ++i) fb[posB[i]] = v[i];
             wave_lds_sync();
             // pass C = stages 6..8 : p = hi*64 + i*8 + lo   (same wave's sub-FFT)
 #pragma unroll
             for (int i = 0; i < 8; ++i) v[i] = fb[posC[i]];
-            pass8_store_as_you_go(bfly8(v, TwLdsSym<8>{stwC + (tt & 7)}), [&](int i) { fb[posC[i]] = v[i]; });
+            stages8(v, TwLdsSym<8>{stwC + (tt & 7)});
+#pragma unroll
+            for (int i = 0; i < 8; ++i) fb[posC[i]] = v[i];
             wave_lds_sync();
             // pass D = stages 9..11 : p = 8*t + i, in place; Z[k] ends at position bitrev12(k)
 #pragma unroll
             for (int i = 0; i < 8; ++i) v[i] = fb[swz((tt << 3) + i)];
-            pass8_store_as_you_go(BflyD{v}, [&](int i) { fb[swz((tt << 3) + i)] = v[i]; });
+            fft_stages<LOG2N, 9, 3>(v, 0, pl.tw);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) fb[swz((tt << 3) + i)] = v[i];
         }
         // this wave's pass-D stores are issued (the LDS pipe serves one wave's operations in order, so the counter moves
         // after them): tell the team

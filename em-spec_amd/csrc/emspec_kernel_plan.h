@@ -130,7 +130,7 @@ enum class RouteKind { fused_pp, fused_small, fused_8192, fused_16384, records_f
 struct Route { RouteKind kind; int rl; };   // rl: exact_lr's rows per slot in the global scratch (0: the whole ring in LDS)
 inline bool is_records(Route r) { return r.kind == RouteKind::records_f32 || r.kind == RouteKind::exact_records; }
 // the diagnostic build's switches (the product: all off).  variant: EMSPEC_FUSED_VARIANT, 0 the product kernel, 1 r16, 2 r8t,
-// 3 r8, 4 ppt, 5 pp3 (fused.hip.inc)
+// 3 r8, 4 ppt, 5 pp3, 6 pp4 (fused.hip.inc)
 struct FastSwitches { bool no_fused = false; int variant = 0; };       // EMSPEC_NO_FUSED, EMSPEC_FUSED_VARIANT
 struct ExactSwitches { bool parked = false; bool records = false; };   // EMSPEC_EXACT_PARKED, EMSPEC_EXACT_RECORDS
 

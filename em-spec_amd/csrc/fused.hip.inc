@@ -7,7 +7,8 @@
 //   fused_small_pp_kernel<S>   N = 4096/2048/1024 at any hop whose ring fits in LDS    (fused_small.hip.inc; same schedule)
 //   fused16384_kernel          N = 16384 (ring parked in registers while the FFT owns LDS) (fused_n16384.hip.inc)
 // Diagnostic builds (-DEMSPEC_DIAG -> libemspec_diag.so) add the stamped builds and the
-// A/B variants r8 (lock step) / pp3, ppt (round 3's schedule) / r16 / r8t (diag/*.inc), selectable with EMSPEC_FUSED_VARIANT;
+// A/B variants r8 (lock step) / pp3, ppt (round 3's schedule) / pp4 (stores at the end of each FFT pass) / r16 / r8t (diag/*.inc),
+// selectable with EMSPEC_FUSED_VARIANT;
 // none of that is in libemspec.so.
 #include "fused_r8.hip.inc"
 #include "fused_n8192.hip.inc"
@@ -18,6 +19,7 @@
 #include "diag/fused_r16.hip.inc"
 #include "diag/fused_r8t.hip.inc"
 #include "diag/fused_pp3.hip.inc"
+#include "diag/fused_pp4.hip.inc"
 #endif
 namespace emspec {
 
@@ -26,7 +28,8 @@ namespace emspec {
 // 1 = 512-thread radix-16 variant ("r16"), 2 = 1024-thread radix-8 with decoupled teams ("r8t"),
 // 3 = the lock-step form of the product kernel ("r8": the default until round 3),
 // 4 = round 3's form of the product kernel (spectrum reads at the start of role 1) with per-team software barriers
-//     instead of the workgroup barrier ("ppt"), 5 = that form as it was the product in rounds 3-4 ("pp3")
+//     instead of the workgroup barrier ("ppt"), 5 = that form as it was the product in rounds 3-4 ("pp3"),
+// 6 = the product kernel with every FFT pass's stores behind the whole pass, as it was until the stores went pair by pair ("pp4")
 static int fused_variant() {
     static int v = -1;
     if (v < 0) {
@@ -37,6 +40,7 @@ static int fused_variant() {
         if (e && e[0] == 'r' && e[1] == '8' && e[2] != 't') v = 3;
         if (e && e[0] == 'p' && e[1] == 'p' && e[2] == 't') v = 4;
         if (e && e[0] == 'p' && e[1] == 'p' && e[2] == '3') v = 5;
+        if (e && e[0] == 'p' && e[1] == 'p' && e[2] == '4') v = 6;
     }
     return v;
 }
@@ -155,6 +159,8 @@ hipError_t launch_fused(int n, const PlanDev& pl, const DbMap& m, const uint8_t*
         return family(fused_pp_lds_bytes(pl.rows, pl.hop), [](auto H, auto ST, auto) { return fused4096_pp3_kernel<H(), ST(), true, true>; });
     if (fused_variant() == 5)   // round 3's form of the product kernel (A/B)
         return family(fused_pp_lds_bytes(pl.rows, pl.hop), [](auto H, auto ST, auto FA) { return fused4096_pp3_kernel<H(), ST(), FA()>; });
+    if (fused_variant() == 6)   // the product kernel before store-as-you-go passes (A/B)
+        return family(fused_pp_lds_bytes(pl.rows, pl.hop), [](auto H, auto ST, auto FA) { return fused4096_pp4_kernel<H(), ST(), FA()>; });
     if (fused_variant() == 1) {   // 512 threads, radix 16 (A/B)
         if (stamps) return go(fused4096_kernel<true>, dim3(512), fused_lds_bytes(pl.rows), stamps);
         if (stamp_groups) return hipSuccess;

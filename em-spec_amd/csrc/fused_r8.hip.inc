@@ -94,9 +94,68 @@ struct TwLdsSym {
         return sym8_rot(e) ? make_float2(x.y, -x.x) : x;
     }
 };
+
+// ---- store-as-you-go form of a radix-8 pass (fused4096_pp_kernel's passes B, C, D only; stages8 and fft_stages keep their
+// schedules).  A ds_write_b64 costs the LDS store path about 6 cycles per wave-instruction and a wave's LDS operations issue
+// in order, so a pass that ends in eight stores back to back puts about 48 cycles of store path per wave in front of the
+// next pass's reads, while the wave has nothing else to issue.  Here the pass's last stage
+// runs pair by pair, each pair's two stores behind its own butterfly, and the second quad of the middle stage is sunk
+// between the first quad's pairs: the stores are spread over the last ~48 VALU of the pass, two at a time.
+// Same butterflies on the same operands as stages8 / fft_stages<12, 9, 3> (the butterflies of one stage are independent,
+// so their order among themselves is free); the fences pin the order, which the scheduler otherwise undoes (it clusters stores).
+// A fence lets scalar and global-memory instructions pass (0x4 | 0x10), nothing else.
+struct Bfly8 {   // butterfly I of local stage U of stages8(v, w), the seven twiddle slots w(e) in registers
+    float2 (&v)[8];
+    float2 tw[7];
+    template <int U, int I>
+    __device__ __forceinline__ void run() const {
+        constexpr int mloc = 4 >> U;
+        const float2 a = v[I], b = v[I + mloc];
+        v[I] = cadd(a, b);
+        v[I + mloc] = cmul_tw(csub(a, b), tw[8 - 2 * mloc + (I & (mloc - 1))]);
+    }
+};
+// The slots are read once, in front of the pass: a table read behind one of the pass's own stores could not be merged with
+// the same slot's earlier read (the store may alias it), and the pass would read its LDS twiddles again and wait for them.
+template <class W>
+__device__ __forceinline__ Bfly8 bfly8(float2 (&v)[8], const W& w) {
+    return Bfly8{v, {w(0), w(1), w(2), w(3), w(4), w(5), w(6)}};
+}
+struct BflyD {   // butterfly I of stage 9 + U of fft_stages<LOG2N, 9, 3>(v, 0, tw): the twiddles are compile-time constants
+    float2 (&v)[8];
+    template <int U, int I>
+    __device__ __forceinline__ void run() const {
+        constexpr int mloc = 4 >> U, q = (I & (mloc - 1)) << (9 + U);
+        static_assert(q == 0 || q == N / 8 || q == N / 4 || q == 3 * (N / 8), "pass D has these four twiddles only");
+        constexpr float kC8 = 0.70710677f;   // tw[N/8] = (c, -c), tw[3N/8] = (-c, -c): see fft_stages
+        const float2 a = v[I], b = v[I + mloc];
+        v[I] = cadd(a, b);
+        const float2 d = csub(a, b);
+        if constexpr (q == 0) v[I + mloc] = d;
+        else if constexpr (q == N / 4) v[I + mloc] = make_float2(d.y, -d.x);
+        else if constexpr (q == N / 8) v[I + mloc] = cmul_tw(d, make_float2(kC8, -kC8));
+        else v[I + mloc] = cmul_tw(d, make_float2(-kC8, -kC8));
+    }
+};
+#define EMSPEC_STORE_FENCE() __builtin_amdgcn_sched_barrier(0x4 | 0x10)
+template <class B, class St>
+__device__ __forceinline__ void pass8_store_as_you_go(const B& bf, const St& st) {   // st(i) stores register i
+    bf.template run<0, 0>(); bf.template run<0, 1>(); bf.template run<0, 2>(); bf.template run<0, 3>();
+    bf.template run<1, 0>(); bf.template run<1, 1>();
+    bf.template run<2, 0>(); st(0); st(1);
+    EMSPEC_STORE_FENCE();
+    bf.template run<1, 4>();
+    bf.template run<2, 2>(); st(2); st(3);
+    EMSPEC_STORE_FENCE();
+    bf.template run<1, 5>();
+    bf.template run<2, 4>(); st(4); st(5);
+    EMSPEC_STORE_FENCE();
+    bf.template run<2, 6>(); st(6); st(7);
+}
+#undef EMSPEC_STORE_FENCE
 }  // namespace f8
 
-#define EMSPEC_STAMP(slot)                                                        \
+#define EMSPEC_STAMP(slot)                                                       \
     if constexpr (STAMP) {                                                        \
         const unsigned long long now_ = __builtin_readcyclecounter();             \
         acc_[slot] += now_ - last_;                                               \
