@@ -584,15 +584,6 @@ int emspec_batch_device(emspec_engine* e, const float* pcm, int32_t S, int64_t L
 }
 
 #ifdef EMSPEC_DIAG   // diagnostic entry points (include/emspec_debug.h): libemspec_diag.so only
-// Diagnostic: non-zero if a bounded spin of the decoupled-team fused kernel ever timed out on this device.
-int emspec_debug_fused_error(emspec_engine* e) {
-    if (!e) return EMSPEC_ERR_INVALID_ARG;
-    if (hipSetDevice(e->device) != hipSuccess) return EMSPEC_ERR_HIP;
-    (void)hipDeviceSynchronize();
-    return fused_read_errflag();
-}
-
-
 // Diagnostic: enqueue a kernel that keeps `groups` workgroups resident for ~usec microseconds on hip_stream.
 int emspec_debug_occupy(emspec_engine* e, int32_t groups, int32_t usec, void* hip_stream) {
     if (!e || groups < 1 || groups > 4096 || usec < 1 || usec > 2000000) return fail(e, EMSPEC_ERR_INVALID_ARG, "bad argument");
@@ -708,7 +699,7 @@ int emspec_debug_phase_cycles(emspec_engine* e, const float* pcm_dev, int32_t S,
     if (!fused_supported(n, hop, e->cfg.rows, reassign)) return fail(e, EMSPEC_ERR_INVALID_ARG, "no fused kernel for this shape");
     const PlanDev pd = plan_dev(e, *p, hop, reassign);
     const DbMap m = db_map(e, n);
-    return stamped(fused_waves_per_group(), [&](unsigned long long* stamps) {
+    return stamped(16, [&](unsigned long long* stamps) {
         return launch_fused(n, pd, m, e->d_lut, pcm_dev, L, S, C, db_dev, nullptr, index_dev, e->stream, stamps, groups);
     });
 }

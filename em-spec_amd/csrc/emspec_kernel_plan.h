@@ -81,8 +81,7 @@ inline size_t frames_lds_bytes(int log2n, int rows) {
 inline size_t fused_ring_lds_bytes(int rows, int slots) {
     return (size_t)2 * 4096 * 8 + (size_t)slots * rows * 4 + (size_t)(rows + 4) * 4 + 1024 + kTw8Entries * 8;
 }
-inline size_t fused_r8_lds_bytes(int rows, int hop) { return fused_ring_lds_bytes(rows, fused_pp_slots(hop)); }
-inline size_t fused_pp_lds_bytes(int rows, int hop) { return fused_r8_lds_bytes(rows, hop) + 16; }   // + the two arrival counters
+inline size_t fused_pp_lds_bytes(int rows, int hop) { return fused_ring_lds_bytes(rows, fused_pp_slots(hop)) + 16; }   // + the two arrival counters
 inline size_t fused_small_lds_bytes(int rows, int slots) { return fused_ring_lds_bytes(rows, slots) + 16; }
 inline size_t fused8192_lds_bytes(int rows, int hop) { return fused_ring_lds_bytes(rows, fused8192_slots(hop)); }
 inline size_t fused16384_lds_bytes(int rows) {
@@ -129,12 +128,11 @@ inline bool exact_lr_split_ok(int rows, int rl, int slots) {
 enum class RouteKind { fused_pp, fused_small, fused_8192, fused_16384, records_f32, exact_lr, exact_parked, exact_records };
 struct Route { RouteKind kind; int rl; };   // rl: exact_lr's rows per slot in the global scratch (0: the whole ring in LDS)
 inline bool is_records(Route r) { return r.kind == RouteKind::records_f32 || r.kind == RouteKind::exact_records; }
-// the diagnostic build's switches (the product: all off).  variant: EMSPEC_FUSED_VARIANT, 0 the product kernel, 1 r16, 2 r8t,
-// 3 r8, 4 ppt, 5 pp3, 6 pp4 (fused.hip.inc)
-struct FastSwitches { bool no_fused = false; int variant = 0; };       // EMSPEC_NO_FUSED, EMSPEC_FUSED_VARIANT
+// the diagnostic build's switches (the product: all off)
+struct FastSwitches { bool no_fused = false; };                        // EMSPEC_NO_FUSED
 struct ExactSwitches { bool parked = false; bool records = false; };   // EMSPEC_EXACT_PARKED, EMSPEC_EXACT_RECORDS
 
-// FAST: the N = 4096 family is built for hop 256, 512 and 1024 (the diagnostic A/B variants r16 / r8t for hop 256 only), N = 8192
+// FAST: the N = 4096 family is built for hop 256, 512 and 1024, N = 8192
 // for hop 512 and 1024, N = 16384 for any hop whose ring fits the register park, fused_small for N = 4096 / 2048 / 1024 at any
 // hop whose ring (2D + F column slots) fits in LDS; everything else goes through per-bin records.
 inline Route fast_route(int n, int hop, int rows, int reassign, FastSwitches sw = {}) {
@@ -142,12 +140,11 @@ inline Route fast_route(int n, int hop, int rows, int reassign, FastSwitches sw 
     auto serves = [&](bool yes, RouteKind k) { return yes ? Route{k, 0} : records; };
     if (sw.no_fused) return records;
     const int D = latency(n, hop < 1 ? 1 : hop, reassign);
-    if (n == 16384) return serves(sw.variant == 0 && hop >= 1 && hop <= n && ring_rows_ok(rows) && fused16384_ring_fits(rows, D), RouteKind::fused_16384);
-    if (n == 8192) return serves(sw.variant == 0 && (hop == 512 || hop == 1024) && ring_rows_ok(rows), RouteKind::fused_8192);
-    const bool pp_hop = hop == 256 || ((sw.variant == 0 || sw.variant >= 3) && (hop == 512 || hop == 1024));
-    if (n == 4096 && pp_hop) return serves(ring_rows_ok(rows), RouteKind::fused_pp);
+    if (n == 16384) return serves(hop >= 1 && hop <= n && ring_rows_ok(rows) && fused16384_ring_fits(rows, D), RouteKind::fused_16384);
+    if (n == 8192) return serves((hop == 512 || hop == 1024) && ring_rows_ok(rows), RouteKind::fused_8192);
+    if (n == 4096 && (hop == 256 || hop == 512 || hop == 1024)) return serves(ring_rows_ok(rows), RouteKind::fused_pp);
     if (n == 4096 || n == 2048 || n == 1024)
-        return serves((sw.variant == 0 || sw.variant == 3) && ring_rows_ok(rows) && hop >= 1 && hop <= n &&
+        return serves(ring_rows_ok(rows) && hop >= 1 && hop <= n &&
                           fused_small_lds_bytes(rows, fused_small_slots(n, D)) <= kLdsBytes, RouteKind::fused_small);
     return records;
 }

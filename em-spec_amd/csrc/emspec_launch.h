@@ -186,8 +186,6 @@ Route fused_route(int n, int hop, int rows, int reassign);
 bool fused_supported(int n, int hop, int rows, int reassign);
 int device_cus();           // compute units of the current device
 #ifdef EMSPEC_DIAG          // diagnostic build only (libemspec_diag.so, include/emspec_debug.h)
-int fused_waves_per_group();
-int fused_read_errflag();   // non-zero if a bounded spin of the decoupled-team kernel ever timed out
 hipError_t launch_row_lookup_probe(const float* ebin, int rows, const float* kh, int64_t count, int32_t* out_hint,
                                    int32_t* out_exact, hipStream_t st);
 hipError_t launch_occupy(int groups, int usec, unsigned* sink, hipStream_t st);

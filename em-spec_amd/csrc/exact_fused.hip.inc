@@ -18,7 +18,8 @@
 // so in every half-iteration exactly one team touches the ring and the planes and the other one only computes.  The four
 // '|' are ARRIVAL COUNTERS of the F team (one ds_add per wave and phase, then a poll): the V team never stops at them and
 // meets the F team at ONE workgroup barrier per half-iteration (with workgroup barriers for all five the V team's chunks have
-// to match the F team's phases: 25.4 vs 23.4 ms).  The finished column's binary64 dB + colour runs on the first four F
+// to match the F team's phases: 25.4 vs 23.4 ms; that form was the timing build EMSPEC_EXACT_SYNC=0 until it was retired,
+// docs/HISTORY.md "Retired kernel forms").  The finished column's binary64 dB + colour runs on the first four F
 // waves between their arrival and their wait at the second sync - they finish every phase ahead of the other four (the LDS
 // queue serves them first) and would only wait.  A thread parks exactly the cells its own pass-A stores overwrite and
 // restores them itself, so parking needs no sync of its own (one wave's LDS operations execute in order).
@@ -53,10 +54,12 @@ using ex::exact_core_fast;
         last_ = now_;                                                              \
     }
 
-// SYNC: how the F team orders its own phases.  0: workgroup barriers that the V team passes through as well (five per
-// half-iteration); 1: arrival counters in LDS that only the eight F waves touch (one ds_add per wave and phase, then a
-// poll with s_sleep) - the V team computes straight through its half-iteration and meets the F team once, at its end.
-template <bool STAMP, bool FASTX, int SYNC>
+// The F team orders its own phases with arrival counters in LDS that only its eight waves touch (one ds_add per wave and
+// phase, then a poll with s_sleep) - the V team computes straight through its half-iteration and meets the F team once, at
+// its end.  Stamped build, slots: 0-4 the F phases | 5 the F team's sync waits | 6 role V's work | 7 its barrier wait (low
+// word; the three stamps inside role V mark where the retired barrier form stopped and add next to nothing), 100 MHz
+// ticks (high word) - tools/phase_cycles_exact.py.
+template <bool STAMP, bool FASTX>
 __global__ __launch_bounds__(1024, 4) void exact_fused4096_kernel(
     ExactPlanDev pl, ExactDbMap dm, const uint32_t* __restrict__ lut, const float* __restrict__ pcm, int64_t L, int64_t C,
     SegPlan sp, int slots, float* __restrict__ db, uint32_t* __restrict__ rgba, uint8_t* __restrict__ index,
@@ -73,7 +76,7 @@ __global__ __launch_bounds__(1024, 4) void exact_fused4096_kernel(
     double2* stwB = reinterpret_cast<double2*>(seb + edge_cells(R));   // [4][64]
     double2* stwC = stwB + 4 * 64;                                      // [4][8]
     uint32_t* slut = reinterpret_cast<uint32_t*>(stwC + 4 * 8);         // [256]
-    unsigned* cnt = slut + 256;                                         // [2 teams][4 phases] arrival counters (SYNC == 1)
+    unsigned* cnt = slut + 256;                                         // [2 teams][4 phases] arrival counters
 
     const int tid = threadIdx.x, h = tid >> 9, t = tid & 511;
     int s;
@@ -124,23 +127,17 @@ __global__ __launch_bounds__(1024, 4) void exact_fused4096_kernel(
     // arrives before it polls, so the wait always ends; the spin is bounded all the same and a timeout raises g_kernel_error
     // (kernels.hip), which emspec_device_status reports.
     auto team_arrive = [&](int ph, int lane) {
-        if constexpr (SYNC == 1) {
-            asm volatile("" ::: "memory");
-            if (lane == 0) __hip_atomic_fetch_add(cnt + 4 * h + ph, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            asm volatile("" ::: "memory");
-        }
+        asm volatile("" ::: "memory");
+        if (lane == 0) __hip_atomic_fetch_add(cnt + 4 * h + ph, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        asm volatile("" ::: "memory");
     };
     auto team_wait = [&](int ph) {
-        if constexpr (SYNC == 0) {
-            bar_lds();
-        } else {
-            unsigned spins = 0;
-            while ((int)(__hip_atomic_load(cnt + 4 * h + ph, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) - 8u * visits) < 0) {
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > (1u << 20)) { g_kernel_error = 1; break; }
-            }
-            asm volatile("" ::: "memory");
+        unsigned spins = 0;
+        while ((int)(__hip_atomic_load(cnt + 4 * h + ph, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) - 8u * visits) < 0) {
+            __builtin_amdgcn_s_sleep(1);
+            if (++spins > (1u << 20)) { g_kernel_error = 1; break; }
         }
+        asm volatile("" ::: "memory");
     };
     auto team_sync = [&](int ph, int lane) { team_arrive(ph, lane); team_wait(ph); };
 
@@ -311,12 +308,10 @@ __global__ __launch_bounds__(1024, 4) void exact_fused4096_kernel(
                 rq[e] = ok ? o.q : 0ll;
             };
             EXF_STAMP(6)
-            if constexpr (SYNC == 0) bar_only();
             EXF_STAMP(7)
             bin(0);
             __builtin_amdgcn_sched_barrier(0);
             EXF_STAMP(6)
-            if constexpr (SYNC == 0) bar_only();
             EXF_STAMP(7)
             bin(1);
             bin(2);
@@ -342,7 +337,6 @@ __global__ __launch_bounds__(1024, 4) void exact_fused4096_kernel(
             ex::xfft_stages<LOG2N, 0, 3>(vr, vi, tt, pl.tw);
             __builtin_amdgcn_sched_barrier(0);
             EXF_STAMP(6)
-            if constexpr (SYNC == 0) { bar_only(); bar_only(); }
             EXF_STAMP(7)
 #pragma unroll
             for (int i = 0; i < 8; ++i) { carry[i] = vr[i]; carry[8 + i] = vi[i]; }
@@ -422,23 +416,17 @@ hipError_t launch_exact_fused(int n, const ExactPlanDev& pl, const ExactDbMap& m
     uint32_t* r32 = reinterpret_cast<uint32_t*>(rgba);
     // the branch-free per-bin core needs reassignment ON, log-spaced rows and a gate that keeps 64 P inside recip_normal64's range
     const bool fast = ex::exact_fast(pl);
-    auto go = [&](auto STAMP, auto FASTX, auto SYNC) {   // SYNC: true = arrival counters (1), false = workgroup barriers (0)
-        return launch_k(exf::exact_fused4096_kernel<STAMP(), FASTX(), SYNC()>, grid, block, lds, st, pl, m, l32, pcm, L, C, sp, slots,
+    auto go = [&](auto STAMP, auto FASTX) {
+        return launch_k(exf::exact_fused4096_kernel<STAMP(), FASTX()>, grid, block, lds, st, pl, m, l32, pcm, L, C, sp, slots,
                         db, r32, index, STAMP() ? stamps : nullptr);
     };
-    constexpr std::true_type yes{};
-    constexpr std::false_type no{};
 #ifdef EMSPEC_DIAG
-    const char* ev = getenv("EMSPEC_EXACT_SYNC");   // A/B aid: 0 = workgroup barriers only
-    const bool sync = !(ev && ev[0] == '0');
     if (stamps || stamp_groups) {
         if (!stamps) return hipSuccess;
-        if (!fast) return go(yes, no, yes);   // (the generic core has no stamped build on barriers)
-        return pick_bool(sync, [&](auto SYNC) { return go(yes, yes, SYNC); });
+        return pick_bool(fast, [&](auto FASTX) { return go(std::true_type{}, FASTX); });
     }
-    if (!sync) return pick_bool(fast, [&](auto FASTX) { return go(no, FASTX, no); });
 #endif
-    return pick_bool(fast, [&](auto FASTX) { return go(no, FASTX, yes); });
+    return pick_bool(fast, [&](auto FASTX) { return go(std::false_type{}, FASTX); });
 }
 
 }  // namespace emspec

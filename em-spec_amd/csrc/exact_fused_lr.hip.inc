@@ -113,12 +113,10 @@ __device__ __forceinline__ void xstages8_from(double (&vr)[8], double (&vi)[8], 
     }
 
 // RL: rows [0, RL) of every slot live in `low` (global, [blocks][slots][RL]); RH = R - RL rows in LDS.  RL % 4 == 0.
-// PAF: pass A (conversion, ramp, stages 0..2) of a frame runs at the head of its role F instead of at the tail of the team's
-// preceding role V, which then only fetches the samples (A/B: with the parking gone the V team is the longer one)
-// ABL (diagnostic, WRONG results): 1 = role V without its four bins, 2 = role F without passes C and D, 3 = no dB + colour,
-// 4 = role F's passes and spectrum reads without their LDS accesses (same arithmetic on whatever the registers hold)
 // S: the size, N = 4096 >> S (0, 1, 2): FPT = 2^S frames per team and half-iteration (see make_lrpos)
-template <bool STAMP, bool FASTX, bool PAF = false, int ABL = 0, int S = 0>
+// (The timing builds this kernel had - pass A at the head of role F, and four ablations with wrong results by design - are
+// retired: docs/HISTORY.md "Retired kernel forms".)
+template <bool STAMP, bool FASTX, int S = 0>
 __global__ __launch_bounds__(1024, 4) void exact_fused4096_lr_kernel(
     ExactPlanDev pl, ExactDbMap dm, const uint32_t* __restrict__ lut, const float* __restrict__ pcm, int64_t L, int64_t C,
     SegPlan sp, int slots, int RL, unsigned long long* __restrict__ lowbase, float* __restrict__ db,
@@ -127,7 +125,7 @@ __global__ __launch_bounds__(1024, 4) void exact_fused4096_lr_kernel(
     constexpr int NS = N >> S;          // FFT size
     constexpr int FPT = 1 << S;         // frames per team and half-iteration
     constexpr int RPF = 8 >> S;         // sample registers per frame (512 samples each)
-    static_assert(S >= 0 && S <= 2 && (S == 0 || (!STAMP && !PAF && ABL == 0)), "the diagnostic forms exist for N = 4096 only");
+    static_assert(S >= 0 && S <= 2 && (S == 0 || !STAMP), "the stamped build exists for N = 4096 only");
     unsigned long long acc_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long last_ = 0;
     extern __shared__ double smemd[];
@@ -199,7 +197,7 @@ __global__ __launch_bounds__(1024, 4) void exact_fused4096_lr_kernel(
             vr[i] = xv;
             vi[i] = xv * ((double)(t + T * (i % RPF) - NS / 2) * rs);
         }
-        if constexpr (!PAF) xstages8_from<S>(vr, vi, XTwRegs4{twA});
+        xstages8_from<S>(vr, vi, XTwRegs4{twA});
 #pragma unroll
         for (int i = 0; i < 8; ++i) { carry[i] = vr[i]; carry[8 + i] = vi[i]; }
     }
@@ -324,17 +322,8 @@ __global__ __launch_bounds__(1024, 4) void exact_fused4096_lr_kernel(
             EXL_STAMP(0)
             {
                 const int a0 = f8::swz(tt), a1 = a0 ^ 8;   // swz(tt + 512 i) = (swz(tt) ^ 8 (i & 1)) + 512 i
-                if constexpr (PAF) {
-                    double vr[8], vi[8];
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) { vr[i] = carry[i]; vi[i] = carry[i] * ((double)(tt + T * i - N / 2) * rs); }
-                    ex::xstages8(vr, vi, XTwRegs4{twA});
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) { const int p = ((i & 1) ? a1 : a0) + T * i; sre[p] = vr[i]; sim[p] = vi[i]; }
-                } else if constexpr (ABL != 4) {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) { const int p = ((i & 1) ? a1 : a0) + T * i; sre[p] = carry[i]; sim[p] = carry[8 + i]; }
-                }
+                for (int i = 0; i < 8; ++i) { const int p = ((i & 1) ? a1 : a0) + T * i; sre[p] = carry[i]; sim[p] = carry[8 + i]; }
             }
             EXL_STAMP(1)
             team_arrive(1, tt & 63);
@@ -350,7 +339,7 @@ __global__ __launch_bounds__(1024, 4) void exact_fused4096_lr_kernel(
             // stage "dB + colour" of the column taken out above, between this wave's arrival and its wait: the rows that came
             // from LDS here, the low rows (whose swaps are still in flight) at the second sync
             if constexpr (S == 0) {
-                if (finlds && ABL != 3) finish(cfin, 4 * tt, f0, f1, f2, f3);
+                if (finlds) finish(cfin, 4 * tt, f0, f1, f2, f3);
             } else {
                 const int hq = RH >> 2;   // LDS quads per column
                 for (int q = tt; q < FPT * hq; q += T) {
@@ -402,37 +391,35 @@ __global__ __launch_bounds__(1024, 4) void exact_fused4096_lr_kernel(
                 {   // pass B = stages 3..5: p = hi*512 + i*64 + lo
                     double vr[8], vi[8];
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) { const int p = pa.x ^ (f8::cswz(i << 6) << 3); if constexpr (ABL != 4) { vr[i] = re_at(p); vi[i] = im_at(p); } else { vr[i] = carry[i] + (double)p; vi[i] = carry[8 + i]; } }
+                    for (int i = 0; i < 8; ++i) { const int p = pa.x ^ (f8::cswz(i << 6) << 3); vr[i] = re_at(p); vi[i] = im_at(p); }
                     ex::xstages8(vr, vi, XTwLds4<64>{stwB + (tt & 63)});
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) { const int p = pa.x ^ (f8::cswz(i << 6) << 3); if constexpr (ABL != 4) { re_at(p) = vr[i]; im_at(p) = vi[i]; } else { carry[i] = vr[i]; carry[8 + i] = vi[i]; } }
+                    for (int i = 0; i < 8; ++i) { const int p = pa.x ^ (f8::cswz(i << 6) << 3); re_at(p) = vr[i]; im_at(p) = vi[i]; }
                     wave_lds_sync();
                 }
-                if constexpr (ABL != 2) {
                 {   // pass C = stages 6..8: p = (t >> 3)*64 + i*8 + (t & 7)
                     double vr[8], vi[8];
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) { const int p = pa.y ^ (f8::cswz(i << 3) << 3); if constexpr (ABL != 4) { vr[i] = re_at(p); vi[i] = im_at(p); } else { vr[i] = carry[i] + (double)p; vi[i] = carry[8 + i]; } }
+                    for (int i = 0; i < 8; ++i) { const int p = pa.y ^ (f8::cswz(i << 3) << 3); vr[i] = re_at(p); vi[i] = im_at(p); }
                     ex::xstages8(vr, vi, XTwLds4<8>{stwC + (tt & 7)});
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) { const int p = pa.y ^ (f8::cswz(i << 3) << 3); if constexpr (ABL != 4) { re_at(p) = vr[i]; im_at(p) = vi[i]; } else { carry[i] = vr[i]; carry[8 + i] = vi[i]; } }
+                    for (int i = 0; i < 8; ++i) { const int p = pa.y ^ (f8::cswz(i << 3) << 3); re_at(p) = vr[i]; im_at(p) = vi[i]; }
                     wave_lds_sync();
                 }
                 {   // pass D = stages 9..11: p = 8 t + i, twiddles are constants
                     double vr[8], vi[8];
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) { const int p = pa.z ^ (i << 3); if constexpr (ABL != 4) { vr[i] = re_at(p); vi[i] = im_at(p); } else { vr[i] = carry[i] + (double)p; vi[i] = carry[8 + i]; } }
+                    for (int i = 0; i < 8; ++i) { const int p = pa.z ^ (i << 3); vr[i] = re_at(p); vi[i] = im_at(p); }
                     ex::xfft_stages<LOG2N - S, 9 - S, 3>(vr, vi, 0, pl.tw);   // the last three stages of the NS-point network
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) { const int p = pa.z ^ (i << 3); if constexpr (ABL != 4) { re_at(p) = vr[i]; im_at(p) = vi[i]; } else { carry[i] = vr[i]; carry[8 + i] = vi[i]; } }
-                }
+                    for (int i = 0; i < 8; ++i) { const int p = pa.z ^ (i << 3); re_at(p) = vr[i]; im_at(p) = vi[i]; }
                 }
             }
             EXL_STAMP(2)
             team_arrive(2, tt & 63);
             // (laundered: the compiler otherwise starts the cells' arithmetic - and so the wait for the swaps - where they were issued)
             asm volatile("" : "+v"(g0), "+v"(g1), "+v"(g2), "+v"(g3));
-            if (finlow && ABL != 3) finish(lcol, lcell, g0, g1, g2, g3);
+            if (finlow) finish(lcol, lcell, g0, g1, g2, g3);
             team_wait(2);
             EXL_STAMP(5)
             // -- phase 3: the spectrum values of this thread's bins 4 bg .. 4 bg + 3 (lanes 32 bins apart): F(i) = Z[4bg-1+i],
@@ -448,12 +435,8 @@ __global__ __launch_bounds__(1024, 4) void exact_fused4096_lr_kernel(
                 const int pm[6] = {S ? mB ^ c1b : mB + c1b, mB, S ? mL ^ c3b : mL + c3b, S ? mL ^ c2b : mL + c2b, S ? mL ^ c1b : mL + c1b, mL};
 #pragma unroll
                 for (int i = 0; i < 6; ++i) {
-                    if constexpr (ABL != 4) {
-                        carry[4 * i] = re_at(pf[i]); carry[4 * i + 1] = im_at(pf[i]);
-                        carry[4 * i + 2] = re_at(pm[i]); carry[4 * i + 3] = im_at(pm[i]);
-                    } else {
-                        carry[4 * i] += (double)pf[i]; carry[4 * i + 2] += (double)pm[i];
-                    }
+                    carry[4 * i] = re_at(pf[i]); carry[4 * i + 1] = im_at(pf[i]);
+                    carry[4 * i + 2] = re_at(pm[i]); carry[4 * i + 3] = im_at(pm[i]);
                 }
             }
             EXL_STAMP(3)
@@ -515,15 +498,10 @@ __global__ __launch_bounds__(1024, 4) void exact_fused4096_lr_kernel(
                 rq[e] = ok ? o.q : 0ll;
             };
             EXL_STAMP(6)
-            if constexpr (ABL == 1) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { rc[e] = -1; rq[e] = (long long)__double_as_longlong(yt[e].yr); }
-            } else {
-                bin(0);
-                bin(1);
-                bin(2);
-                bin(3);
-            }
+            bin(0);
+            bin(1);
+            bin(2);
+            bin(3);
             // a lane's consecutive bins often share a cell: sum such runs first (integer adds: any order gives the same sum)
 #pragma unroll
             for (int e = 0; e < 3; ++e) {
@@ -543,7 +521,7 @@ __global__ __launch_bounds__(1024, 4) void exact_fused4096_lr_kernel(
                 vi[i] = xv * (ramp0 + rstep * (double)(i % RPF));   // = (n - NS/2) 2/NS exactly, n = t + 512 (i mod RPF)
             }
             if constexpr (!FASTX) load_twA(tt);
-            if constexpr (!PAF) xstages8_from<S>(vr, vi, XTwRegs4{twA});
+            xstages8_from<S>(vr, vi, XTwRegs4{twA});
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 0; i < 8; ++i) { carry[i] = vr[i]; carry[8 + i] = vi[i]; }
@@ -631,24 +609,14 @@ hipError_t launch_exact_fused_lr(int n, const ExactPlanDev& pl, const ExactDbMap
         }
         return hipSuccess;
     };
-#ifdef EMSPEC_DIAG
-    // timing builds of the fast N = 4096 kernel (A/B aids): 1 = PAF, 2 .. 5 = ABL 1 .. 4; the first name set wins
-    static const char* const variant_env[] = {"EMSPEC_EXL_PAF", "EMSPEC_EXL_ABL1", "EMSPEC_EXL_ABL2", "EMSPEC_EXL_ABL3", "EMSPEC_EXL_ABL4"};
-    int variant = 0;
-    for (int i = 0; i < 5 && !variant; ++i) variant = getenv(variant_env[i]) ? i + 1 : 0;
-#endif
     // SKIP = 1 / 2 (N = 2048 / 1024): two / four frames per team and half-iteration
     return pick_int<0, 1, 2>(skip, [&](auto SKIP) { return pick_bool(ex::exact_fast(pl), [&](auto FASTX) {
 #ifdef EMSPEC_DIAG
         if constexpr (SKIP() == 0) {
             if (stamps) return run(exl::exact_fused4096_lr_kernel<true, FASTX()>);
-            if constexpr (FASTX()) {
-                if (variant == 1) return run(exl::exact_fused4096_lr_kernel<false, true, true>);
-                if (variant) return pick_int<1, 2, 3, 4>(variant - 1, [&](auto ABL) { return run(exl::exact_fused4096_lr_kernel<false, true, false, ABL()>); });
-            }
         }
 #endif
-        return run(exl::exact_fused4096_lr_kernel<false, FASTX(), false, 0, SKIP()>);
+        return run(exl::exact_fused4096_lr_kernel<false, FASTX(), SKIP()>);
     }); });
 }
 

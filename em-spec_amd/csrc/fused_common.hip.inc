@@ -55,57 +55,4 @@ __device__ __forceinline__ void read_split6(const float2* fb, const int (&fpos)[
     }
 }
 
-// The per-bin stage of bins 4g .. 4g+3 from the split spectra at positions 4g-1 .. 4g+4: spectral Hann identities, power
-// gate, time and frequency reassignment, row lookup, segment test, ring slot; then runs of bins that share a cell are
-// summed in registers (a lane's consecutive bins often do), so okv[] marks one accumulate per distinct cell.
-// This is the second statement of reassign_core / reassign_core_fast (emspec_device.h): same results bit for bit, other
-// operand layout - the six positions arrive as arrays instead of three YT records, T's imaginary part is carried negated
-// (ur = -Ti, exact, hence -(Ui * Ai)), and the outcome is a ring cell and a predicate instead of a BinOut.  Branch-free and
-// unrolled so the four bins' dependency chains (reassign -> edge-table read -> accumulate) overlap.
-// kf0 = (float)(4g); sbase = ring slot of column j - dmax; jrel = j - c0; span = c1 - c0; dmax = the ring's reach (a
-// compile-time constant of the kernel, or pl.D), slots = its slot count (likewise); Df = (float)pl.D.
-// The accumulates, and the s_setprio steps between them, stay in each kernel: they are schedule.
-template <bool FAST>
-__device__ __forceinline__ void bins4(const float pfloor_abs, const int reassign, const float tscale, const HintLookup& lk,
-                                      const float (&yr)[6], const float (&yi)[6], const float (&ur)[6], const float (&tr)[6],
-                                      const float kf0, const int sbase,
-                                      const int jrel, const unsigned span, const float Df, float* ring, const int R,
-                                      const int dmax, const int slots, float* (&cellp)[4], float (&pw)[4], bool (&okv)[4]) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float Ar = twice_minus(yr[e + 1], yr[e] + yr[e + 2]), Ai = twice_minus(yi[e + 1], yi[e] + yi[e + 2]);
-        const float Br = twice_minus(tr[e + 1], tr[e] + tr[e + 2]), Ui = twice_minus(ur[e + 1], ur[e] + ur[e + 2]);
-        const float Dr = yr[e] - yr[e + 2], Di = yi[e] - yi[e + 2];
-        const float den = __builtin_fmaf(Ar, Ar, Ai * Ai);
-        const float P = den * 0.015625f;
-        bool ok = (P >= pfloor_abs) && (P <= kPowerMax);
-        const float kf = kf0 + (float)e;
-        float kh = kf;
-        int d = dmax;
-        if (FAST || reassign) {
-            const float numT = __builtin_fmaf(Br, Ar, -(Ui * Ai));
-            const float numF = __builtin_fmaf(Dr, Ar, Di * Ai);
-            const float inv = FAST ? recip_normal(den) : 1.0f / den;
-            const float cf = __builtin_floorf(__builtin_fmaf(numT * inv, tscale, 0.5f));
-            ok = ok && (__builtin_fabsf(cf) <= Df);
-            d = (int)cf + dmax;
-            kh = kf + numF * inv;
-        }
-        const int rr = FAST ? lk.row_signed_log(kh) : lk.row_signed(kh);   // -1 / R when k-hat is off the frequency axis
-        ok = ok && ((unsigned)rr < (unsigned)R);
-        ok = ok && ((unsigned)(jrel + d - dmax) < span);
-        unsigned sl = (unsigned)(sbase + d);   // garbage when !ok: the cell is then never touched
-        sl = min(sl, sl - (unsigned)slots);
-        cellp[e] = ring + __umul24(sl, (unsigned)R) + rr;   // 24-bit multiply: full rate (v_mul_lo_u32 is quarter rate)
-        pw[e] = P;
-        okv[e] = ok;
-    }
-#pragma unroll
-    for (int e = 0; e < 3; ++e) {
-        const bool same = okv[e] && okv[e + 1] && (cellp[e] == cellp[e + 1]);
-        pw[e + 1] = same ? pw[e + 1] + pw[e] : pw[e + 1];
-        okv[e] = okv[e] && !same;
-    }
-}
-
 }  // namespace emspec

@@ -1,7 +1,9 @@
 // fused_n8192.hip.inc — fused batch kernel for N = 8192 on the skeleton of fused_r8.hip.inc.
-// Included by kernels.hip after fused_r8.hip.inc (it reuses f8::swz / zpos / stages8 / TwLds).  Its finalize, spectrum split
-// and four-bin stage are still spelled out here, in the order of fused_common.hip.inc's finalize_ring_quad, read_split6 and
-// bins4: calling them reschedules this kernel (profiles/refactor_fused_common_isa.txt), so that waits for an A/B measurement.
+// Included by kernels.hip after fused_r8.hip.inc (it reuses f8::swz / zpos / stages8 / TwLdsSym).  Its finalize and spectrum
+// split are spelled out here, in the order of fused_common.hip.inc's finalize_ring_quad and read_split6, and its four-bin
+// stage in the order fused_pp.hip.inc's header gives (Hann identities, power gate, reassignment, row lookup, segment test,
+// ring slot, then the run sums).  Calling shared functions for them rescheduled this kernel
+// (profiles/refactor_fused_common_isa.txt), so that waits for an A/B measurement.
 //
 // The first stage of the canonical radix-2 DIF network splits an 8192-point frame into two
 // independent 4096-point transforms:
@@ -37,7 +39,7 @@ template <int HOP, bool FAST = false>   // FAST: reassignment ON + log-spaced ed
 __global__ __launch_bounds__(1024, 4) void fused8192_kernel(
     PlanDev pl, DbMap dm, const uint32_t* __restrict__ lut, const float* __restrict__ pcm, int64_t L, int64_t C,
     SegPlan sp, float* __restrict__ db, uint32_t* __restrict__ rgba, uint8_t* __restrict__ index) {
-    using namespace f8;   // the 4096-point sub-network: swz, zpos, stages8, tw_index8, TwRegs, TwLds
+    using namespace f8;   // the 4096-point sub-network: swz, zpos, stages8, tw_index8, TwRegsSym, TwLdsSym
     constexpr int N = f13::N, M = f13::M, T = f13::T;
     constexpr int DMAX = f13::Geo<HOP>::DMAX, SLOTS = f13::Geo<HOP>::SLOTS, SH = f13::Geo<HOP>::SH;
     extern __shared__ float4 smem4[];

@@ -2,10 +2,16 @@
 // APART.  The product path since round 3; in its present form (spectrum reads in role 0) since round 4.
 // Included by fused.hip.inc after fused_r8.hip.inc (same LDS images, swizzle and FFT helpers: namespace f8).  The arithmetic
 // between the FFT and the output arrays is the one definition of fused_common.hip.inc (finalize_ring_quad, read_split6); the
-// four-bin stage is still spelled out here, in the order of fused_common's bins4 - calling it reschedules this kernel
-// (profiles/refactor_fused_common_isa.txt), so it waits for an A/B measurement.
+// four-bin stage is spelled out in each kernel (here, fused_n8192, fused_small, diag/fused_pp4), the same text in the same
+// order: per bin the spectral Hann identities, the power gate, time and frequency reassignment, the row lookup, the segment
+// test and the ring slot; then runs of a lane's consecutive bins that share a cell are summed in registers, so okv[] marks
+// one accumulate per distinct cell.  It is the second statement of reassign_core / reassign_core_fast (emspec_device.h):
+// same results bit for bit, other operand layout (six positions as arrays, ur = -Ti carried negated, a ring cell and a
+// predicate instead of a BinOut).  A shared function for it (bins4, until it lost its last caller) rescheduled these kernels
+// (profiles/refactor_fused_common_isa.txt), so sharing it waits for an A/B measurement per kernel.
 //
-// fused4096_r8_kernel runs its two frames in lock step: all 16 waves stream LDS in the FFT passes, then all 16 waves
+// The lock-step kernel this one replaced (fused4096_r8_kernel, docs/HISTORY.md "Retired kernel forms") ran its two frames
+// together: all 16 waves stream LDS in the FFT passes, then all 16 waves
 // issue VALU in the per-bin stage, with three workgroup barriers per two frames - and a timing-only build without those
 // barriers runs 21 % faster (docs/HISTORY.md §4.1e): what the barriers cost is not the instruction but the coupling of
 // sixteen waves to the slowest one three times per iteration, and the loss of overlap between LDS-bound and VALU-bound
@@ -25,7 +31,7 @@
 // was the long role (5.4 k cycles against 4.4 k), and its first instructions were twelve LDS reads queued behind the other
 // team's passes.  Moving the reads - not more: handing over the stencils or the dot products instead (24 or 12 floats)
 // measured 9.14 / 9.15 ms against 9.04 - A/B on one box: 9.32 -> 9.02 ms, bit-identical palette indices
-// (diag/fused_pp3.hip.inc keeps the old form as variant "pp3").
+// (the old form was A/B variant "pp3" until it was retired, docs/HISTORY.md "Retired kernel forms").
 // Passes B, C and D issue their stores as their data is ready (f8::pass8_store_as_you_go, fused_r8.hip.inc): two ds_write_b64
 // behind each pair of the last stage instead of the four to eight back to back the compiler otherwise leaves at a pass's end,
 // in front of the next pass's reads.  The same instructions in another order: 9.06 -> 8.93 ms, A/B on one box;

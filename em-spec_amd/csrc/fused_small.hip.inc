@@ -1,19 +1,18 @@
-// fused_small.hip.inc — fused batch kernels for N = 2048 and N = 1024 (and, as S = 0, for N = 4096
-// at the hops fused_r8.hip.inc is not built for) on the skeleton of fused_r8.hip.inc.  Included by
-// kernels.hip after fused_r8.hip.inc (reuses f8::swz / zpos / tw_index8 / TwLds); the finalize, the spectrum split and the
-// lock-step form's four-bin stage are fused_common.hip.inc's (the product form spells the bin stage out, see fused_pp.hip.inc).
+// fused_small.hip.inc — the fused batch kernel for N = 2048 and N = 1024 (and, as S = 0, for N = 4096 at the hops
+// fused_pp.hip.inc is not built for) on the 4096-point carrier network of fused_r8.hip.inc.  Included by kernels.hip after
+// fused_r8.hip.inc (reuses f8::swz / zpos / tw_index8 / TwLdsSym); the finalize and the spectrum split are
+// fused_common.hip.inc's, the four-bin stage is spelled out in the order fused_pp.hip.inc describes.
 //
 // A 4096-point radix-2 DIF network whose first S stages are skipped is 2^S independent
 // (4096 >> S)-point networks side by side, and its twiddles are the small network's own
 // (tw_n[q] == tw4096[q << S]: the double argument is identical).  So each 512-thread team runs
 // FPT = 2^S consecutive frames through its 4096-point buffer at once — S = 1: two 2048-point
 // frames, S = 2: four 1024-point frames — with pass A reduced to stages S..2 and passes B, C, D
-// unchanged; F = 2 * FPT frames per iteration.  Frame slot fs of a team lives in buffer part fs,
-// and its spectrum sample Z[m] ends at zpos((m << S) | bitrev_S(fs)).  The per-bin stage runs on
-// all 1024 threads (F frames x (512 >> S) groups of 4 bins = 1024 groups); the lanes of a wave
-// are (16 >> S) groups apart, which is the swizzle's conflict-free read pattern.  The hop is a
-// run-time value: samples are reloaded every iteration (frames of one iteration overlap, so the
-// loads hit L1/L2), and the ring has 2D + F column slots, whatever fits in LDS.
+// unchanged.  Frame slot fs of a team lives in buffer part fs, and its spectrum sample Z[m] ends at
+// zpos((m << S) | bitrev_S(fs)).  The hop is a run-time value: samples are reloaded for every block (consecutive
+// frames overlap, so the loads hit L1/L2), and the ring has 2D + 2 FPT column slots, whatever fits in LDS.
+// (The lock-step form of this kernel, fused_small_kernel, was the product until round 3 and an A/B form after it:
+// docs/HISTORY.md "Retired kernel forms".)
 namespace emspec {
 
 namespace fsm {
@@ -38,174 +37,7 @@ template <> __device__ __forceinline__ int brev_s<1>(int x) { return x; }
 template <> __device__ __forceinline__ int brev_s<2>(int x) { return ((x & 1) << 1) | (x >> 1); }
 }  // namespace fsm
 
-template <int S, bool FAST = false>   // FAST: reassignment ON + log-spaced edges known at compile time (fused_r8.hip.inc)
-__global__ __launch_bounds__(1024, 4) void fused_small_kernel(
-    PlanDev pl, DbMap dm, const uint32_t* __restrict__ lut, const float* __restrict__ pcm, int64_t L, int64_t C,
-    SegPlan sp, int slots, float* __restrict__ db, uint32_t* __restrict__ rgba, uint8_t* __restrict__ index) {
-    using namespace f8;   // the 4096-point carrier network: swz, zpos, tw_index8, TwRegs, TwLds
-    constexpr int NS = 4096 >> S;          // FFT size
-    constexpr int FPT = 1 << S, F = 2 * FPT;   // frames per team, per iteration
-    constexpr int RPF = 8 >> S;            // sample registers per frame (512 samples each)
-    extern __shared__ float4 smem4[];
-    const int R = pl.rows, D = pl.D, HOP = pl.hop, SLOTS = slots;
-    float2* fbuf = reinterpret_cast<float2*>(smem4);            // [2][4096] complex
-    float* ring = reinterpret_cast<float*>(fbuf + 2 * 4096);     // [SLOTS][R]
-    float* seb = ring + SLOTS * R;                                // [R+1] (+3 pad)
-    uint32_t* slut = reinterpret_cast<uint32_t*>(seb + R + 4);   // [256]
-    float2* stwB = reinterpret_cast<float2*>(slut + 256);        // [7][64] pass-B twiddles
-    float2* stwC = stwB + 7 * 64;                                 // [7][8]  pass-C twiddles
-
-    const int tid = threadIdx.x, h = tid >> 9, t = tid & 511;
-    float2* fb = fbuf + h * 4096;
-    int s;
-    int64_t c0, c1;
-    if (!seg_of_block(sp, C, s, c0, c1)) return;
-    const int64_t j0 = (c0 - D > 0 ? c0 - D : 0) & ~(int64_t)(F - 1);
-    const int64_t jstop = c1 + D;
-    const float* x0 = pcm + (size_t)s * L;
-
-    // ---- workgroup set-up (pl.tw is the NS-point table: carrier index >> S)
-    for (int q = tid; q < SLOTS * R / 4; q += 1024) reinterpret_cast<float4*>(ring)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int r = tid; r <= R; r += 1024) seb[r] = pl.ebin[r];
-    if (tid < 256) slut[tid] = lut[tid];
-    if (tid < 7 * 64) stwB[tid] = pl.tw[tw_index8<3>(tid >> 6, tid & 63) >> S];
-    else if (tid < 7 * 64 + 7 * 8) stwC[tid - 7 * 64] = pl.tw[tw_index8<6>((tid - 7 * 64) >> 3, (tid - 7 * 64) & 7) >> S];
-    float2 twA[7];   // only the slots of stages S..2 are used
-#pragma unroll
-    for (int e = 0; e < 7; ++e) twA[e] = (e >= (S == 0 ? 0 : (S == 1 ? 4 : 6))) ? pl.tw[tw_index8<0>(e, t) >> S] : make_float2(0.f, 0.f);
-    const float r0 = (float)(t - NS / 2) * (2.0f / (float)NS);   // ramp of a frame's register 0; register ii adds ii*1024/NS
-    HintLookup lk;
-    lk.init(seb, pl.ebin, R, pl.log_rows);
-    // Bin groups: F frames x (512 >> S) groups of 4 bins; wave w takes frame w mod F, and the lanes of a
-    // wave are (16 >> S) groups apart.
-    const int wv = tid >> 6;
-    const int bf = wv & (F - 1);                                   // frame slot of this thread's bins, 0..F-1
-    const int bg = ((tid & 63) << (3 - S)) | (wv >> (S + 1));      // bin group within the frame
-    const int bpart = fsm::brev_s<S>(bf & (FPT - 1));              // low bits of the carrier index
-    float2* bbuf = fbuf + (bf >> S) * 4096;                        // the team buffer holding that frame
-    int fpos[6], mpos[6];     // positions of Z[4g-1+i] and Z[NS-4g+1-i] of that frame
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        fpos[i] = zpos((((4 * bg - 1 + i) & (NS - 1)) << S) | bpart);
-        mpos[i] = zpos((((NS - 4 * bg + 1 - i) & (NS - 1)) << S) | bpart);
-    }
-    int sj = (int)(j0 % SLOTS);   // ring slot of column jb
-    __syncthreads();
-
-    // frame slot and in-frame sample offset of sample register i
-    auto load_frames = [&](int64_t jb, float (&x)[8], int tq) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int64_t j = jb + h * FPT + (i / RPF);
-            const int64_t idx = j * HOP + tq + 512 * (i % RPF);
-            x[i] = idx < L ? x0[idx] : 0.0f;
-        }
-    };
-    float2 v[8];
-    auto pass_a = [&](const float (&x)[8]) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = make_float2(x[i], x[i] * (r0 + (float)(i % RPF) * (1024.0f / (float)NS)));
-        fsm::stages8_from<S>(v, TwRegs{twA});
-    };
-    {
-        float x[8];
-        load_frames(j0, x, t);
-        pass_a(x);
-    }
-#pragma unroll 1
-    for (int64_t jb = j0; jb < jstop; jb += F) {
-        const bool active = jb + h * FPT < C;          // the team's first frame exists
-        int tt = t, tw_ = tid;
-        asm volatile("" : "+v"(tt));
-        asm volatile("" : "+v"(tw_));
-        float xn[8];
-        load_frames(jb + F, xn, tt);                   // next iteration's samples (consumed by pass_a below)
-
-        if (active) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) fb[swz(tt) ^ cswz(512 * i)] = v[i];   // swz(P + (i << b)) = swz(P) ^ cswz(i << b), fused_r8.hip.inc
-        }
-        __syncthreads();
-        if (active) {
-            __builtin_amdgcn_s_setprio(3);
-            // pass B = carrier stages 3..5 : p = hi*512 + i*64 + lo   (wave-local from here on)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = fb[swz(((tt >> 6) << 9) + (tt & 63)) ^ cswz(i << 6)];
-            stages8(v, TwLds<64>{stwB + (tt & 63)});
-#pragma unroll
-            for (int i = 0; i < 8; ++i) fb[swz(((tt >> 6) << 9) + (tt & 63)) ^ cswz(i << 6)] = v[i];
-            wave_lds_sync();
-            __builtin_amdgcn_s_setprio(2);
-            // pass C = stages 6..8 : p = hi*64 + i*8 + lo
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = fb[swz(((tt >> 3) << 6) + (tt & 7)) ^ cswz(i << 3)];
-            stages8(v, TwLds<8>{stwC + (tt & 7)});
-#pragma unroll
-            for (int i = 0; i < 8; ++i) fb[swz(((tt >> 3) << 6) + (tt & 7)) ^ cswz(i << 3)] = v[i];
-            wave_lds_sync();
-            __builtin_amdgcn_s_setprio(1);
-            // pass D = stages 9..11 of the carrier = the last three stages of the NS-point network
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = fb[swz(tt << 3) ^ i];
-            fft_stages<12 - S, 9 - S, 3>(v, 0, pl.tw);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) fb[swz(tt << 3) ^ i] = v[i];
-            __builtin_amdgcn_s_setprio(0);
-        }
-        __syncthreads();
-        {
-            const int64_t j = jb + bf;                 // this thread's bins belong to frame j
-            if (j < C) {
-                __builtin_amdgcn_s_setprio(3);
-                float yr[6], yi[6], ur[6], tr[6];
-#pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    const float2 f = bbuf[fpos[i]], m = bbuf[mpos[i]];
-                    yr[i] = f.x + m.x; yi[i] = f.y - m.y; ur[i] = f.x - m.x; tr[i] = f.y + m.y;   // ur = -Ti
-                }
-                int sbase = sj + bf - D;                   // ring slot of column j-D
-                sbase -= sbase >= SLOTS ? SLOTS : 0;
-                sbase += sbase < 0 ? SLOTS : 0;
-                const int jrel = (int)(j - c0);
-                const unsigned span = (unsigned)(c1 - c0);
-                const float Df = (float)D;
-                const float kf0 = (float)(4 * (((tw_ & 63) << (3 - S)) | ((tw_ >> 6) >> (S + 1))));
-                float* cellp[4];
-                float pw[4];
-                bool okv[4];
-                bins4<FAST>(pl.pfloor_abs, pl.reassign, pl.tscale, lk, yr, yi, ur, tr, kf0, sbase, jrel, span, Df, ring, R, D, SLOTS, cellp, pw, okv);   // fused_common.hip.inc
-                lds_accumulate(cellp[0], pw[0], okv[0]);
-                __builtin_amdgcn_s_setprio(2);
-                lds_accumulate(cellp[1], pw[1], okv[1]);
-                __builtin_amdgcn_s_setprio(1);
-                lds_accumulate(cellp[2], pw[2], okv[2]);
-                lds_accumulate(cellp[3], pw[3], okv[3]);
-                __builtin_amdgcn_s_setprio(0);
-            }
-        }
-        pass_a(xn);                                     // next iteration's pass A, before the barrier
-        __syncthreads();
-        // ---- columns jb-D .. jb-D+F-1 can no longer be reached: finalise, store, clear
-        {
-            const int qpc = R >> 2;   // float4 quads per column
-            for (int q = tid; q < F * qpc; q += 1024) {
-                const int cc = q / qpc;
-                const int cell = (q - cc * qpc) << 2;
-                const int64_t col = jb - D + cc;
-                if (col >= c0 && col < c1) {
-                    int sl = sj - D + cc;
-                    sl += sl < 0 ? SLOTS : 0;
-                    sl -= sl >= SLOTS ? SLOTS : 0;
-                    finalize_ring_quad(ring, sl, R, cell, dm, slut, ((size_t)s * C + col) * R + cell, db, rgba, index);
-                }
-            }
-        }
-        sj += F;
-        sj -= sj >= SLOTS ? SLOTS : 0;
-    }
-}
-
-// ---- the product form since round 3: the two teams HALF AN ITERATION APART (the schedule of fused_pp.hip.inc, DESIGN.md
+// The two teams run HALF AN ITERATION APART (the schedule of fused_pp.hip.inc, DESIGN.md
 // §4.1, with FPT frames per team and half-iteration instead of one; like it with the spectrum reads in role 0 since round 4).
 // Team h takes the blocks b = k of FPT consecutive frames with (k + h) even; at half-iteration k
 //     role 0 (k + h even): passes B, C, D of block k | arrive | finalise the FPT columns no later block reaches | wait for the
@@ -217,12 +49,12 @@ __global__ __launch_bounds__(1024, 4) void fused_small_kernel(
 // (8 >> S) groups apart (the swizzle's conflict-free read pattern).
 // Ring: at k the role-0 team finalises columns j0 + (k-2) FPT - D .. + FPT - 1 (last contributor: block k - 2, scattered
 // by that team at k - 1) while the role-1 team scatters block k - 1, which reaches no lower than column
-// j0 + (k-1) FPT - D, and no higher than j0 + k FPT - 1 + D: 2 D + 2 FPT slots, as in the lock-step form.
-template <int S, bool FAST = false>
+// j0 + (k-1) FPT - D, and no higher than j0 + k FPT - 1 + D: 2 D + 2 FPT slots.
+template <int S, bool FAST = false>   // FAST: reassignment ON + log-spaced edges known at compile time (fused_r8.hip.inc)
 __global__ __launch_bounds__(1024, 4) void fused_small_pp_kernel(
     PlanDev pl, DbMap dm, const uint32_t* __restrict__ lut, const float* __restrict__ pcm, int64_t L, int64_t C,
     SegPlan sp, int slots, float* __restrict__ db, uint32_t* __restrict__ rgba, uint8_t* __restrict__ index) {
-    using namespace f8;   // the 4096-point carrier network: swz, zpos, tw_index8, TwRegs, TwLds
+    using namespace f8;   // the 4096-point carrier network: swz, zpos, tw_index8, TwRegsSym, TwLdsSym
     constexpr int NS = 4096 >> S;          // FFT size
     constexpr int FPT = 1 << S;            // frames per team and half-iteration
     constexpr int RPF = 8 >> S;            // sample registers per frame (512 samples each)

@@ -34,10 +34,6 @@ int emspec_debug_phase_cycles(emspec_engine* e, const float* pcm_dev, int32_t S,
                               uint8_t* index_dev, uint64_t* cycles, int64_t* groups,
                               int32_t* waves);
 
-/* Synchronises the device and returns non-zero if a bounded spin of the decoupled-team fused
- * kernel (EMSPEC_FUSED_VARIANT=r8t) ever timed out: a protocol bug, results are then invalid. */
-int emspec_debug_fused_error(emspec_engine* e);
-
 /* Enqueue on hip_stream a kernel that keeps `groups` 256-thread workgroups resident for about
  * `usec` microseconds (bounded spin): a stand-in for a communication kernel holding compute
  * units while the column kernels run on another stream (tools/occupancy_probe.py). */

@@ -43,7 +43,7 @@ def test_diag_library_adds_only_the_debug_header():
     assert "emspec_debug_row_lookup" in dbg and "emspec_debug_phase_cycles" in dbg and "emspec_debug_recip" in dbg and "emspec_debug_recip64" in dbg
     assert exported_functions(emspec.DIAG_LIB_PATH) == sorted(set(declared_functions("emspec.h")) | set(dbg))
     out = subprocess.run(["strings", "-n", "6", emspec.LIB_PATH], capture_output=True, text=True).stdout
-    for needle in ("EMSPEC_FUSED_VARIANT", "EMSPEC_NO_FUSED", "EMSPEC_SEGLEN", "EMSPEC_NO_WALK", "fused4096_r8t", "fused4096_r8_kernel", "occupy_kernel"):
+    for needle in ("EMSPEC_FUSED_VARIANT", "EMSPEC_NO_FUSED", "EMSPEC_SEGLEN", "EMSPEC_NO_WALK", "fused4096_pp4", "recip64_probe_kernel", "occupy_kernel"):
         assert needle not in out, f"{needle} is diagnostic and must not be in libemspec.so"
 
 
@@ -162,8 +162,8 @@ def test_flagship_kernels_do_not_spill():
     xseen = 0
     for m in re.finditer(r"\.name:\s+(\S+)\n", text):
         name = m.group(1)
-        # (exact_fused4096_lr_kernel<STAMP = false, FASTX, PAF = false, ABL = 0, S>: both per-bin cores, all three sizes)
-        if not any(k in name for k in ("exact_fused4096_lr_kernelILb0ELb1ELb0ELi0E", "exact_fused4096_lr_kernelILb0ELb0ELb0ELi0E",
+        # (exact_fused4096_lr_kernel<STAMP = false, FASTX, S>: both per-bin cores, all three sizes)
+        if not any(k in name for k in ("exact_fused4096_lr_kernelILb0ELb1ELi", "exact_fused4096_lr_kernelILb0ELb0ELi",
                                        "exact_frames16384_kernelILb1ELb0", "exact_frames16384_kernelILb0ELb0")):
             continue
         blk = text[m.start() - 400:m.start() + 1600]

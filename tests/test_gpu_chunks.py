@@ -18,7 +18,6 @@ reduction, the cell count being that of the full-rate image.
 Columns per case: the fewest >= 25 at which an integer number of MiB meets the budget rule (chunk_ref.columns_and_budget) - 25
 to 33 for the records shapes, 41 to 97 for the composed entries and the time reduction, 387 where a stream needs only C x rows
 bytes (index or RGBA alone behind the time reduction).  The whole file runs in about four seconds."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -46,11 +45,9 @@ LADDERS = {"3x512": ((8192, 2048, 1024), 512, (368, 668)), "4x128": ((16384, 819
 def test_the_diagnostic_library_is_the_one_loaded():
     """EMSPEC_RECORD_BUDGET_MB is read by the diagnostic build only: without it every case below would run one chunk."""
     lib = emspec.load(diag=True)
-    assert hasattr(lib, "emspec_debug_fused_error") and not hasattr(emspec.load(), "emspec_debug_fused_error")
+    assert hasattr(lib, "emspec_debug_row_lookup") and not hasattr(emspec.load(), "emspec_debug_row_lookup")
     with emspec.Engine(diag=True) as e:
         assert e._lib is lib
-        lib.emspec_debug_fused_error.argtypes = [C.c_void_p]
-        assert lib.emspec_debug_fused_error(e._h) == 0
 
 
 def case(entry, shape, exact, **kw):

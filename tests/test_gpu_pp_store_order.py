@@ -4,7 +4,8 @@ kept in libemspec_diag.so as A/B variant `pp4`.  Only the order of independent i
 
  - the product kernel must still match the oracle (dB within 8.7e-4, palette index within one step: the comparison and the
    tolerances of tests/test_gpu_golden.py and test_fused_segments_match_oracle), and
- - it must agree with the kept variant on the same input as the other A/B variants do (test_fused_ab_variants_match_the_product:
+ - it must agree with the kept variant on the same input as every A/B variant had to (the bounds of the retired
+   test_fused_ab_variants_match_the_product, docs/HISTORY.md "Retired kernel forms":
    live dB within 1e-3 - the float32 histogram sums in arrival order -, index within one step on at most 1e-3 of the cells),
    with a clean emspec_device_status.
 

@@ -74,7 +74,7 @@ def test_kernel_plans_match_the_recorded_answers(tmp_path):
     assert {w["case"]["reassign"] for w in plain} == {0, 1} == {w["case"]["reassign"] for w in xplain}
     for n in sizes:
         assert {w["case"]["hop"] for w in plain if w["case"]["n"] == n} >= {1, 256, n}
-    assert {w["case"]["variant"] for w in fast} == {0, 1, 2, 3, 4, 5} and any(w["case"]["no_fused"] for w in fast)
+    assert {w["case"]["variant"] for w in fast} == {0} and any(w["case"]["no_fused"] for w in fast)
     assert {(w["case"]["parked"], w["case"]["records"]) for w in exact} == {(0, 0), (1, 0), (0, 1), (1, 1)}
     assert {w["case"]["axis"] for w in exact} == {0, 1, 2} and any(w["case"]["row0"] > 0 and w["rl"] > 0 for w in exact)
     # a ring's hop threshold: neighbouring hops, the same rows, one served by fused_small and one not, the size on either side of LDS

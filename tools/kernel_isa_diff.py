@@ -4,7 +4,7 @@
 generated code (one that only adds kernels, or a refactor of shared device code) left every existing kernel alone.
 
 The listings come from `make -C em-spec_amd/csrc asm` (the product build, kernels.s) and `make -C em-spec_amd/csrc asm-diag`
-(the diagnostic build with its A/B variants and stamped kernels, kernels_diag.s); compare like with like:
+(the diagnostic build with its A/B form and stamped kernels, kernels_diag.s); compare like with like:
 
     python tools/kernel_isa_diff.py parent_kernels.s kernels.s
     python tools/kernel_isa_diff.py parent_kernels_diag.s kernels_diag.s
