@@ -113,6 +113,20 @@ inline FusedSegPlan fused_seg_plan(int64_t ncu, int S, int64_t C, int D, FusedKi
     return p;
 }
 
+// The longest segment fused_seg_plan can return: every rule above cuts a stream into at least one segment, so without an
+// override the length is at most max(seg_min, C) rounded up to even - one segment that is the whole stream (more streams than
+// four rounds of CUs hold) - and an override is taken as given.  Nothing in the planner bounds C.
+inline int64_t fused_seglen_max(int64_t C, int D, FusedKind kind, int64_t seglen_override) {
+    const int64_t seg_min = kind == FusedKind::small_n ? std::max<int64_t>(16, 4 * D) : (kind == FusedKind::big_n ? std::max<int64_t>(32, 2 * D) : std::max<int64_t>(16, 2 * D));
+    return (std::max(std::max(seg_min, C), seglen_override >= 2 ? seglen_override : 0) + 1) & ~(int64_t)1;
+}
+// fused4096_pp_kernel keeps its column bookkeeping in int, relative to the segment's first frame: half-iteration indices up
+// to seglen + 2D + 3, and a remaining-samples count that starts at most at INT_MAX and falls by 2 hop per pair of
+// half-iterations, hop (seglen + 2D + 5) in all; it has to stay above a thread's largest offset (under 8192) when it started
+// clamped, and inside int when it did not.  2^30 samples per segment leave both a wide margin (and SegPlan holds ints).
+constexpr int64_t kFusedPpMaxWalk = (int64_t)1 << 30;
+inline bool fused_pp_walk_ok(int64_t seglen, int D, int hop) { return seglen >= 1 && (seglen + 2 * D + 5) * hop <= kFusedPpMaxWalk; }
+
 // ---- the EXACT fused kernels (exact_fused.hip.inc, exact_fused_lr.hip.inc): exclusive-device plans, uniform grids ----
 // Segment lengths by seglen_by_rounds, clamped only to >= 1 (seg_min bounds the candidates, not the result); seglen_override as
 // above.  (Both launchers once started from max(seg_min, (C + 3) / 4): dead, round 1 always replaced it.)

@@ -62,6 +62,9 @@ hipError_t launch_fused(int n, const PlanDev& pl, const DbMap& m, const uint8_t*
 #endif
     const FusedSegPlan fp = fused_seg_plan(device_cus(), S, C, pl.D, fused_kind(kind), pl.shared, force_shared, diag_seglen());
     if (!fp.ok) return hipErrorInvalidValue;
+    // SegPlan holds ints, and the N = 4096 kernel counts its walk in int (emspec_seg_plan.h: fused_pp_walk_ok)
+    if (fused_seglen_max(C, pl.D, fused_kind(kind), diag_seglen()) > 0x7fffffff) return hipErrorInvalidValue;
+    if (kind == RouteKind::fused_pp && !fused_pp_walk_ok(fp.sp.seglen, pl.D, pl.hop)) return hipErrorInvalidValue;
     const SegPlan sp = fp.sp;
     const int64_t nseg = fp.nseg;
     const dim3 grid = fp.streams_first ? dim3((unsigned)S, (unsigned)nseg) : dim3((unsigned)nseg, (unsigned)S), block(1024);

@@ -26,7 +26,7 @@
 // team arrives before it polls, so the wait always ends - the spin is bounded all the same).
 // The split spectra (24 floats: Y and T at the thread's six positions) cross the barrier in registers.  The loop body is one
 // (role 0, role 1) pair per team - team 1 enters through one extra barrier, team 0 leaves through one - so that array is
-// local to the body and nothing is carried around the loop for it (123 VGPRs, no scratch).
+// local to the body and nothing is carried around the loop for it (119 VGPRs, no scratch).
 // Round 3's form read the spectra at the start of role 1 (arrival counter between those reads and the pass-A write): role 1
 // was the long role (5.4 k cycles against 4.4 k), and its first instructions were twelve LDS reads queued behind the other
 // team's passes.  Moving the reads - not more: handing over the stencils or the dot products instead (24 or 12 floats)
@@ -140,21 +140,39 @@ __global__ __launch_bounds__(1024, 4) void fused4096_pp_kernel(
     // find their frames and columns outside the segment and do nothing.
     const int klast = (int)(c1 + 1 + D - j0);
     const int P = (klast + 2) >> 1;
-    int sk = (int)((j0 + h) % SLOTS);    // ring slot of column j0 + k
+    // Column bookkeeping in 32 bits, relative to the segment's first frame j0 (the launcher refuses a segment whose walk
+    // does not fit: fused_pp_walk_ok, emspec_seg_plan.h - every difference below is at most seglen + 2D + 3, and the
+    // samples a segment walks stay far inside an int).  What is the same for both teams is carried per pair in scalar
+    // registers; the team's h is added.  As 64-bit vector arithmetic per half-iteration (j against C and jstop, the column
+    // against c0 and c1, the prefetch's sample index against L, the output offset by two multiplies and a 64-bit
+    // multiply-add) the same tests cost 14 more VALU per pair, several at quarter rate: 8.86 -> 8.76 ms, A/B on one box
+    // (docs/HISTORY.md §22; diag/fused_pp4.hip.inc keeps the 64-bit form).
+    const int kact = (int)((C < jstop ? C : jstop) - j0);   // frame j0 + k is walked for k < kact
+    const int kfin = (int)(c0 + 2 + D - j0);                // column c0 is finalised at half-iteration kfin, c0 + i at kfin + i
+    const unsigned span = (unsigned)(c1 - c0);
+    const int jrel0 = (int)(j0 - c0);
+    int sk0 = (int)(j0 % SLOTS);         // ring slot of column j0 + 2p: even, so the team's + h never wraps
+    // the finalize's output offset of column j0 + 2p - 2 - D, cell 0 (wraps below column 0, where it is not used)
+    size_t ocol = ((size_t)s * (size_t)C + (size_t)(j0 - 2 - D)) * (size_t)R;
+    // the sample prefetch of frame j0 + 2p + 2 + h: a row pointer and the samples that remain from it, counted in int
+    // (clamped: a count that large stays above every offset for the whole walk), and the thread's offset from it
+    const float* xrow = x0 + (j0 + 2) * HOP;
+    const int64_t rem0 = L - (j0 + 2) * HOP;
+    int xrem = rem0 < 0x7fffffff ? (int)rem0 : 0x7fffffff;
     unsigned arrivals = 0;               // role-0 visits of this team so far x 8 waves = the counter's target
     __syncthreads();
     unsigned long long real0_ = 0;
     if constexpr (STAMP) { last_ = __builtin_readcyclecounter(); real0_ = __builtin_amdgcn_s_memrealtime(); }
     if (h) __syncthreads();
-    int k = h;
 #pragma unroll 1
-    for (int p = 0; p < P; ++p, k += 2) {
+    for (int p = 0; p < P; ++p) {
         // Launder t once per pair: every LDS address below is then recomputed (1-3 VALU each) instead of being hoisted
         // out of the loop, which would pin ~50 VGPRs.
         int tt = t;
         asm volatile("" : "+v"(tt));
-        const int64_t j = j0 + k;
-        const bool active = j < C && j < jstop;
+        const int k = 2 * p + h;             // this team's half-iteration in role 0: frame j = j0 + k
+        const int sk = sk0 + h;              // ring slot of column j
+        const bool active = k < kact;
         float yr[6], yi[6], ur[6], tr[6];   // Y = Z + conj W, T = -j (Z - conj W) at the six positions (ur = -Ti): role 0 -> role 1
         // ================= role 0 at half-iteration k: passes B, C, D of frame j, finalise column j-2-D, spectrum reads
         if (active) {
@@ -183,12 +201,11 @@ __global__ __launch_bounds__(1024, 4) void fused4096_pp_kernel(
         EMSPEC_STAMP(1)
         {
             const int qpc = R >> 2;   // float4 quads per column
-            const int64_t col = j - 2 - D;
-            if (t < qpc && col >= c0 && col < c1) {
+            if (t < qpc && (unsigned)(k - kfin) < span) {   // column j - 2 - D lies in [c0, c1)
                 const int cell = t << 2;
                 int sl = sk - 2 - D;
                 sl += sl < 0 ? SLOTS : 0;
-                finalize_ring_quad(ring, sl, R, cell, dm, slut, ((size_t)s * C + col) * R + cell, db, rgba, index);
+                finalize_ring_quad(ring, sl, R, cell, dm, slut, ocol + (unsigned)(h * R + cell), db, rgba, index);
             }
         }
         EMSPEC_STAMP(0)
@@ -206,11 +223,10 @@ __global__ __launch_bounds__(1024, 4) void fused4096_pp_kernel(
         EMSPEC_STAMP(6)
         // ================= role 1 at half-iteration k + 1: bins + scatter of frame j, pass A of frame j + 2 and its write
         {
-            const int64_t jn = j + 2;
-            const int64_t nx = jn * HOP + t + 512 * (8 - SH);  // first new sample register of frame jn
+            const int xo = h * HOP + t + 512 * (8 - SH);       // first new sample register of frame jn = j + 2, from xrow
             float xn[SH];
 #pragma unroll
-            for (int q = 0; q < SH; ++q) xn[q] = (nx + 512 * q < L) ? x0[nx + 512 * q] : 0.0f;
+            for (int q = 0; q < SH; ++q) xn[q] = (xo + 512 * q < xrem) ? xrow[xo + 512 * q] : 0.0f;
             if (active) {
                 __builtin_amdgcn_s_setprio(2);
                 float* cellp[4];
@@ -218,8 +234,7 @@ __global__ __launch_bounds__(1024, 4) void fused4096_pp_kernel(
                 bool okv[4];
                 int sbase = sk - DMAX;                 // ring slot of column j-DMAX
                 sbase += sbase < 0 ? SLOTS : 0;
-                const int jrel = (int)(j - c0);
-                const unsigned span = (unsigned)(c1 - c0);
+                const int jrel = jrel0 + k;            // j - c0
                 const float Df = (float)D;
                 const float kf0 = (float)(4 * (((tt & 63) << 3) | (tt >> 6)));
 #pragma unroll
@@ -283,7 +298,7 @@ __global__ __launch_bounds__(1024, 4) void fused4096_pp_kernel(
             for (int i = 0; i < 8; ++i) v[i] = make_float2(xs[i], xs[i] * (r0 + 0.25f * (float)i));
             stages8(v, TwRegsSym{twA});
             EMSPEC_STAMP(3)
-            if (jn < C && jn < jstop) {   // the team read this buffer's spectra before the barrier above: it is free
+            if (k + 2 < kact) {   // frame j + 2 is walked; the team read this buffer's spectra before the barrier above: it is free
                 float2* const w0 = fb + swz(tt);
                 float2* const w1 = fb + (swz(tt) ^ 8);
 #pragma unroll
@@ -292,8 +307,11 @@ __global__ __launch_bounds__(1024, 4) void fused4096_pp_kernel(
         }
         __syncthreads();
         EMSPEC_STAMP(6)
-        sk += 2;
-        sk -= sk >= SLOTS ? SLOTS : 0;
+        sk0 += 2;
+        sk0 -= sk0 >= SLOTS ? SLOTS : 0;
+        ocol += 2 * (size_t)R;
+        xrow += 2 * HOP;
+        xrem -= 2 * HOP;
     }
     if (!h) __syncthreads();
     if constexpr (STAMP) {
