@@ -57,6 +57,13 @@ struct LiveState {
     // place) and the frame kernels read the decoded block on the device.  Every stream of the session has the same `pend`.
     uint8_t* h_raw = nullptr; size_t hraw_bytes = 0;     // [S / pcm.views][cap] frames
     float* d_fresh = nullptr; size_t dfresh_bytes = 0;   // [S][cap] decoded samples
+    // overlays (emspec_set_live_peaks / emspec_set_live_wave; live_overlay.hip.inc), allocated by the first launch that needs them:
+    // the post-processed dB on the device while peaks and the display post-process are both on (without the post-process d_raw
+    // holds the delivered dB), the envelope's pair ring [S][wslots], page-locked staging of pageable outputs [S][cols][k] / [S][cols]
+    float* d_pdb = nullptr; size_t pdb_bytes = 0;
+    void* d_wring = nullptr; size_t wring_bytes = 0;
+    void* h_opeaks = nullptr; size_t opeaks_bytes = 0;
+    void* h_owave = nullptr; size_t owave_bytes = 0;
     LiveStream* desc() const { return reinterpret_cast<LiveStream*>(h_desc); }
 };
 
@@ -179,6 +186,10 @@ struct emspec_engine {
     char* d_full = nullptr; size_t full_bytes = 0;
     // waveform envelope (emspec_set_wave_out): the caller's pair array the host pipeline also fills, or null
     emspec_wave* wave_out = nullptr; int64_t wave_capacity = 0;
+    // overlays of the streaming calls (emspec_set_live_peaks / emspec_set_live_wave), for both sessions below: the caller's
+    // arrays (null: off) and their capacities in pairs
+    emspec_peak* live_peaks = nullptr; int64_t live_peaks_capacity = 0; int live_peaks_k = 0; float live_peaks_min_db = 0.0f;
+    emspec_wave* live_wave = nullptr; int64_t live_wave_capacity = 0;
     // streaming (emspec_live.cpp): the live multi-stream session, and the single-stream calls' own (emspec_column,
     // emspec_push_samples: the same machinery with one stream); independent of each other
     emspec::LiveState live, one;

@@ -151,6 +151,23 @@ hipError_t launch_live_flush(bool exact, const LiveSinks& lv, void* cells, int s
                              const ExactDbMap& xm, int S, int ncol, hipStream_t st);
 hipError_t launch_live_post(const LiveSinks& lv, const float* raw, int raw_cols, int rows, int D, float sm, float agc, float db_top,
                             const DbMap& dm, float* pstate, int S, hipStream_t st);
+// The overlays of a live launch (live_overlay.hip.inc; emspec_set_live_peaks / emspec_set_live_wave): one kernel behind the
+// launch's last kernel, on the same descriptors.  lv.out_db / lv.out_cols: the CALLER's dB destination and the stride of every
+// block below; `units`: the most frames (flush form: columns) any stream has in the launch.
+struct LiveOverlay {
+    // spectral peaks (k == 0: off): the delivered dB on the device, [S][out_cols][rows] - the frame / flush / post kernels wrote
+    // it there instead of the caller's block, which this kernel fills from its LDS copy - and peaks [S][out_cols][k] pairs
+    const float* db = nullptr;
+    float2* peaks = nullptr;
+    int k = 0, rows = 0;
+    float min_db = 0.0f;
+    // waveform envelope (wave == null: off): wave [S][out_cols] pairs; the pair ring [S][wslots] (emspec_live_plan.h)
+    uint2* wave = nullptr;
+    uint2* wring = nullptr;
+    int wslots = 0, hop = 0, off = 0;
+    int D = 0;   // latency of the emitted column
+};
+hipError_t launch_live_overlay(const LiveSinks& lv, const LiveOverlay& ov, int S, int units, hipStream_t st);
 // the gather's wire image (pack.hip.inc; its sizes and the pack workspace `scratch` of wire_scratch_bytes: emspec_wire_plan.h).
 // wire_total_ptr: where in the workspace the pack leaves the image's size
 uint64_t* wire_total_ptr(void* scratch, int64_t columns);

@@ -116,13 +116,24 @@ int live_post_buffers(emspec_engine* e, LiveState& lv) {
 // the post kernel behind it.  dst_db / dst_rgba: device-visible destinations laid out [S][out_cols][rows].
 // raw_cols: an upper bound of the output slots any stream uses (out_at + the columns it emits): the stride of the raw block - the
 // caller's max_columns may be far larger than what a call completes.
+// dst_peaks / dst_wave: the overlays' device-visible destinations ([S][out_cols][k] and [S][out_cols] pairs; null: off) - the
+// overlay kernel goes behind the launch's last kernel.  While peaks are wanted the delivered dB goes to a device block laid out
+// like the destination (d_raw, or d_pdb behind the post kernel) and the overlay kernel writes dst_db from its copy of it.
 int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fresh_stride, int mlaunch, bool flush, float* dst_db,
-                uint8_t* dst_rgba, int out_cols, int raw_cols, bool empty_col) {
+                uint8_t* dst_rgba, int out_cols, int raw_cols, bool empty_col, emspec_peak* dst_peaks = nullptr,
+                emspec_wave* dst_wave = nullptr) {
     int rc;
     const LiveGeometry& g = lv.g;
     const int R = e->cfg.rows;
     const bool post = e->smoothing > 0.0f || e->agc > 0.0f;
     if (post && (rc = live_post_buffers(e, lv))) return rc;
+    // (a launch without a frame - one that only moves samples into the ring - completes no column: no overlay)
+    const bool overlay = (dst_peaks || dst_wave) && (flush || mlaunch > 0), peaks = overlay && dst_peaks;
+    if (peaks) {
+        const size_t want = g.out_bytes(R, std::max(out_cols, 1));
+        if (post ? (rc = grow(e, (void**)&lv.d_pdb, &lv.pdb_bytes, want)) : (rc = grow(e, (void**)&lv.d_raw, &lv.raw_bytes, want))) return rc;
+    }
+    if (overlay && dst_wave && (rc = grow(e, &lv.d_wring, &lv.wring_bytes, live_wave_ring_bytes(g)))) return rc;
     LiveSinks ls;
     ls.streams = lv.desc();
     ls.fresh = fresh;
@@ -145,13 +156,13 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
     // (a call without outputs - a priming block - may complete more columns than its max_columns: out_cols bounds the raw
     // block's stride only where it is an output's stride)
     if (post) {
-        raw_cols = std::max(1, (dst_db || dst_rgba) ? std::min(raw_cols, out_cols) : raw_cols);
+        raw_cols = std::max(1, (dst_db || dst_rgba || overlay) ? std::min(raw_cols, out_cols) : raw_cols);
         if (g.out_bytes(R, raw_cols) > lv.raw_bytes && (rc = grow(e, (void**)&lv.d_raw, &lv.raw_bytes, g.out_bytes(R, raw_cols)))) return rc;
         ls.out_db = lv.d_raw;
         ls.out_rgba = nullptr;
         ls.out_cols = raw_cols;
     } else {
-        ls.out_db = dst_db;
+        ls.out_db = peaks ? lv.d_raw : dst_db;
         ls.out_rgba = reinterpret_cast<uint32_t*>(dst_rgba);
     }
     const DbMap m = db_map(e, g.n);
@@ -216,10 +227,31 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
         }
     }
     if (post) {
-        ls.out_db = dst_db;
+        ls.out_db = peaks ? lv.d_pdb : dst_db;
         ls.out_rgba = reinterpret_cast<uint32_t*>(dst_rgba);
         ls.out_cols = out_cols;
         HIPCHK(e, launch_live_post(ls, lv.d_raw, raw_cols, R, g.D, e->smoothing, e->agc, e->cfg.db_top, m, lv.d_pstate, g.S, e->stream));
+    }
+    if (overlay) {
+        LiveOverlay ov;
+        if (peaks) {
+            ov.db = post ? lv.d_pdb : lv.d_raw;
+            ov.peaks = reinterpret_cast<float2*>(dst_peaks);
+            ov.k = e->live_peaks_k;
+            ov.rows = R;
+            ov.min_db = e->live_peaks_min_db;
+        }
+        if (dst_wave) {
+            ov.wave = reinterpret_cast<uint2*>(dst_wave);
+            ov.wring = reinterpret_cast<uint2*>(lv.d_wring);
+            ov.wslots = live_wave_slots(g);
+            ov.hop = g.hop;
+            ov.off = live_wave_offset(g);
+        }
+        ov.D = g.D;
+        ls.out_db = dst_db;
+        ls.out_cols = out_cols;
+        HIPCHK(e, launch_live_overlay(ls, ov, g.S, flush ? 1 : mlaunch, e->stream));
     }
     return EMSPEC_OK;
 }
@@ -247,18 +279,35 @@ struct LiveDest {
     uint8_t* rgba = nullptr;
     bool stage_db = false, stage_rgba = false;
     bool direct = false;   // nothing is staged, and the caller's layout may be the launch's (in_place_ok)
+    // the overlays (emspec_set_live_peaks / emspec_set_live_wave; null: off), as the outputs above
+    emspec_peak* peaks = nullptr;
+    emspec_wave* wave = nullptr;
+    bool stage_peaks = false, stage_wave = false;
 };
+// (the overlay kernel stores whole pairs: a page-locked array that is not 8-byte aligned is staged like a pageable one)
+void* device_view8(const void* p) { return reinterpret_cast<uintptr_t>(p) % 8 ? nullptr : device_view(p); }
 // together: every given output is staged unless all of them can be written in place; otherwise each output decides for itself
 int live_dest(emspec_engine* e, LiveState& lv, float* out_db, uint8_t* out_rgba, int cols, LiveDest& d, bool together = false,
               bool in_place_ok = true) {
     d.db = reinterpret_cast<float*>(device_view(out_db));
     d.rgba = reinterpret_cast<uint8_t*>(device_view(out_rgba));
+    d.peaks = reinterpret_cast<emspec_peak*>(device_view8(e->live_peaks));
+    d.wave = reinterpret_cast<emspec_wave*>(device_view8(e->live_wave));
     d.stage_db = out_db && !d.db;
     d.stage_rgba = out_rgba && !d.rgba;
-    d.direct = !d.stage_db && !d.stage_rgba && in_place_ok;
-    if (together && !d.direct) { d.stage_db = out_db != nullptr; d.stage_rgba = out_rgba != nullptr; d.db = nullptr; d.rgba = nullptr; }
+    d.stage_peaks = e->live_peaks && !d.peaks;
+    d.stage_wave = e->live_wave && !d.wave;
+    d.direct = !d.stage_db && !d.stage_rgba && !d.stage_peaks && !d.stage_wave && in_place_ok;
+    if (together && !d.direct) {
+        d.stage_db = out_db != nullptr; d.stage_rgba = out_rgba != nullptr; d.db = nullptr; d.rgba = nullptr;
+        d.stage_peaks = e->live_peaks != nullptr; d.stage_wave = e->live_wave != nullptr;
+    }
     const size_t bytes = lv.g.out_bytes(e->cfg.rows, cols);
     int rc;
+    if (d.stage_peaks && (rc = pinned_grow(e, &lv.h_opeaks, &lv.opeaks_bytes, live_peaks_bytes(lv.g, cols, e->live_peaks_k)))) return rc;
+    if (d.stage_wave && (rc = pinned_grow(e, &lv.h_owave, &lv.owave_bytes, live_wave_bytes(lv.g, cols)))) return rc;
+    if (d.stage_peaks) d.peaks = reinterpret_cast<emspec_peak*>(lv.h_opeaks);
+    if (d.stage_wave) d.wave = reinterpret_cast<emspec_wave*>(lv.h_owave);
     if (d.stage_db && (rc = pinned_grow(e, (void**)&lv.h_odb, &lv.odb_bytes, bytes))) return rc;
     if (d.stage_rgba && (rc = pinned_grow(e, (void**)&lv.h_orgba, &lv.orgba_bytes, bytes))) return rc;
     if (d.stage_db) d.db = lv.h_odb;
@@ -268,11 +317,15 @@ int live_dest(emspec_engine* e, LiveState& lv, float* out_db, uint8_t* out_rgba,
 // The staged columns to the caller.  p == null: one column per stream, [S][rows] (emspec_columns, the flush); else the round's
 // columns of a push: p->nc[s] columns of stream s, from the front of its mmax staged columns to column p->produced[s] of its
 // max_columns.
-void live_copy_back(const LiveState& lv, const LiveDest& d, float* out_db, uint8_t* out_rgba, int R, const LivePush* p = nullptr,
-                    int64_t max_columns = 1) {
+// The staged overlays go the same way, k pairs and one pair per column, to the arrays the engine's settings name.
+void live_copy_back(const emspec_engine* e, const LiveState& lv, const LiveDest& d, float* out_db, uint8_t* out_rgba, int R,
+                    const LivePush* p = nullptr, int64_t max_columns = 1) {
+    const int k = e->live_peaks_k;
     if (!p) {
         if (d.stage_db) std::memcpy(out_db, lv.h_odb, lv.g.out_bytes(R, 1));
         if (d.stage_rgba) std::memcpy(out_rgba, lv.h_orgba, lv.g.out_bytes(R, 1));
+        if (d.stage_peaks) std::memcpy(e->live_peaks, lv.h_opeaks, live_peaks_bytes(lv.g, 1, k));
+        if (d.stage_wave) std::memcpy(e->live_wave, lv.h_owave, live_wave_bytes(lv.g, 1));
         return;
     }
     for (int s = 0; s < lv.g.S; ++s) {
@@ -280,6 +333,11 @@ void live_copy_back(const LiveState& lv, const LiveDest& d, float* out_db, uint8
         const size_t from = LiveGeometry::out_cell(R, lv.g.mmax, s, 0), to = LiveGeometry::out_cell(R, max_columns, s, p->produced[s]);
         if (d.stage_db) std::memcpy(out_db + to, lv.h_odb + from, LiveGeometry::columns_bytes(R, p->nc[s]));
         if (d.stage_rgba) std::memcpy(out_rgba + to * 4, lv.h_orgba + from * 4, LiveGeometry::columns_bytes(R, p->nc[s]));
+        const int64_t pfrom = live_overlay_pair(lv.g.mmax, s, 0), pto = live_overlay_pair(max_columns, s, p->produced[s]);
+        if (d.stage_peaks)
+            std::memcpy(e->live_peaks + pto * k, reinterpret_cast<const emspec_peak*>(lv.h_opeaks) + pfrom * k, (size_t)p->nc[s] * k * sizeof(emspec_peak));
+        if (d.stage_wave)
+            std::memcpy(e->live_wave + pto, reinterpret_cast<const emspec_wave*>(lv.h_owave) + pfrom, (size_t)p->nc[s] * sizeof(emspec_wave));
     }
 }
 }  // namespace
@@ -323,6 +381,15 @@ int live_pcm_drain(emspec_engine* e, LiveState& lv) {
 
 // ---- the calls, on one of the engine's two sessions ----
 
+// the overlays' capacity rule: a call that delivers [S][cols][rows] writes S cols k peaks and S cols envelope pairs
+int live_overlay_check(emspec_engine* e, int S, int64_t cols) {
+    if (e->live_peaks && !live_overlay_fits(S, cols, e->live_peaks_k, e->live_peaks_capacity))
+        return fail(e, EMSPEC_ERR_INVALID_ARG, "the array set with emspec_set_live_peaks is too small: the call needs streams x columns x k pairs");
+    if (e->live_wave && !live_overlay_fits(S, cols, 1, e->live_wave_capacity))
+        return fail(e, EMSPEC_ERR_INVALID_ARG, "the array set with emspec_set_live_wave is too small: the call needs streams x columns pairs");
+    return EMSPEC_OK;
+}
+
 // the time reduction (emspec_set_time_reduce) serves the batch entries only: every streaming call refuses while it is on
 const char* const kNoLiveReduce = "the streaming calls return full-rate columns: not available while a time reduction is set (emspec_set_time_reduce(e, 1) turns it off)";
 
@@ -335,6 +402,7 @@ int columns_impl(emspec_engine* e, LiveState& lv, const float* frames, int32_t s
     reassign = reassign ? 1 : 0;
     int rc = live_check(e, lv, streams, n, hop, reassign, rows, 1, n_high, split);
     if (rc) return rc;
+    if ((rc = live_overlay_check(e, streams, 1))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     if (lv.g.form == 0 && (rc = live_open(e, lv, streams, n, hop, reassign, 1, n_high, split))) return rc;
     // the frames: read by the kernel where they are when the caller's block is page-locked, else staged
@@ -347,9 +415,9 @@ int columns_impl(emspec_engine* e, LiveState& lv, const float* frames, int32_t s
     LiveDest d;   // (one column per stream: each output in place or staged on its own)
     if ((rc = live_dest(e, lv, out_db, out_rgba, 1, d))) return rc;
     live_frame_fill(lv.g, lv.c, lv.desc());
-    if ((rc = live_launch(e, lv, src, n, 1, false, d.db, d.rgba, 1, 1, true))) return live_abandon(e, lv, rc);
+    if ((rc = live_launch(e, lv, src, n, 1, false, d.db, d.rgba, 1, 1, true, d.peaks, d.wave))) return live_abandon(e, lv, rc);
     if ((rc = live_sync(e, lv))) return rc;
-    live_copy_back(lv, d, out_db, out_rgba, e->cfg.rows);
+    live_copy_back(e, lv, d, out_db, out_rgba, e->cfg.rows);
     live_frame_commit(lv.g, lv.c, out_columns);
     return EMSPEC_OK;
 }
@@ -359,14 +427,15 @@ int flush_impl(emspec_engine* e, LiveState& lv, float* out_db, uint8_t* out_rgba
     if (e->time_reduce > 1) return fail(e, EMSPEC_ERR_STATE, kNoLiveReduce);
     if (rows != e->cfg.rows) return fail(e, EMSPEC_ERR_INVALID_ARG, "rows does not match the engine configuration");
     if (lv.g.form == 0 || !lv.c.any_pending()) return fail(e, EMSPEC_ERR_STATE, "no pending column");
-    HIPCHK(e, hipSetDevice(e->device));
     int rc;
+    if ((rc = live_overlay_check(e, lv.g.S, 1))) return rc;
+    HIPCHK(e, hipSetDevice(e->device));
     LiveDest d;   // (as emspec_columns; the staging blocks are sized for a push's mmax columns at once)
     if ((rc = live_dest(e, lv, out_db, out_rgba, lv.g.mmax, d))) return rc;
     live_flush_fill(lv.g, lv.c, lv.desc());
-    if ((rc = live_launch(e, lv, nullptr, 0, 0, true, d.db, d.rgba, 1, 1, true))) return live_abandon(e, lv, rc);
+    if ((rc = live_launch(e, lv, nullptr, 0, 0, true, d.db, d.rgba, 1, 1, true, d.peaks, d.wave))) return live_abandon(e, lv, rc);
     if ((rc = live_sync(e, lv))) return rc;
-    live_copy_back(lv, d, out_db, out_rgba, e->cfg.rows);
+    live_copy_back(e, lv, d, out_db, out_rgba, e->cfg.rows);
     live_flush_commit(lv.g, lv.c, out_columns);
     return EMSPEC_OK;
 }
@@ -398,9 +467,11 @@ int push_impl(emspec_engine* e, LiveState& lv, const void* block, int32_t stream
         return fail(e, EMSPEC_ERR_STATE, "the PCM format changed mid-stream; call emspec_reset() first");
     if (max_columns < 0) return fail(e, EMSPEC_ERR_INVALID_ARG, "max_columns must be >= 0");
     const int64_t expect = push_columns_impl(e, lv, count, n, hop, reassign);
-    if ((out_db || out_rgba || n_high || fmt) && expect > max_columns)
+    // (an overlay is an output too: its slots are the columns of [S][max_columns])
+    if ((out_db || out_rgba || n_high || fmt || e->live_peaks || e->live_wave) && expect > max_columns)
         return fail(e, EMSPEC_ERR_INVALID_ARG, "output holds fewer columns than this block completes (" + std::to_string(expect) +
                                                    "); size it with emspec_push_columns() / emspec_push_columns_multi()");
+    if ((rc = live_overlay_check(e, streams, max_columns))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     if (lv.g.form == 0) {
         if ((rc = live_open(e, lv, streams, n, hop, reassign, 2, n_high, split, fmt != nullptr))) return rc;
@@ -409,9 +480,11 @@ int push_impl(emspec_engine* e, LiveState& lv, const void* block, int32_t stream
     const LiveGeometry& g = lv.g;
     // Unlike the one-column calls, a push decides for both outputs together: page-locked outputs are written in place
     // ([S][max_columns][rows], every round at the columns produced so far) only when BOTH are page-locked and max_columns fits
-    // the launch's int; otherwise both go through a staging block of mmax columns per launch.
+    // the launch's int; otherwise both go through a staging block of mmax columns per launch.  The overlays' arrays count as
+    // outputs here; and while peaks are set the delivered dB also lives in a device block with the launch's layout, so a block
+    // of more than mmax columns is staged.
     LiveDest d;
-    if ((rc = live_dest(e, lv, out_db, out_rgba, g.mmax, d, true, max_columns <= 0x7fffffff))) return rc;
+    if ((rc = live_dest(e, lv, out_db, out_rgba, g.mmax, d, true, max_columns <= (e->live_peaks ? g.mmax : 0x7fffffff)))) return rc;
     LivePush p(g.S);
     bool inflight = false;
     while (p.used < count) {
@@ -428,13 +501,13 @@ int push_impl(emspec_engine* e, LiveState& lv, const void* block, int32_t stream
         if (!live_push_round(g, lv.c, p, d.direct, lv.desc())) continue;   // no frame is due and the staging block has room
         if (fmt && (rc = live_decode_pending(e, lv))) return live_abandon(e, lv, rc);
         if ((rc = live_launch(e, lv, fmt ? lv.d_fresh : lv.h_fresh, g.cap, p.mx, false, d.db, d.rgba, d.direct ? (int)max_columns : g.mmax,
-                              d.direct ? (int)std::min<int64_t>(std::max<int64_t>(expect, 1), 0x7fffffff) : g.mmax, false)))
+                              d.direct ? (int)std::min<int64_t>(std::max<int64_t>(expect, 1), 0x7fffffff) : g.mmax, false, d.peaks, d.wave)))
             return live_abandon(e, lv, rc);
         inflight = true;
-        if (d.stage_db || d.stage_rgba) {
+        if (d.stage_db || d.stage_rgba || d.stage_peaks || d.stage_wave) {
             if ((rc = live_sync(e, lv))) return rc;
             inflight = false;
-            live_copy_back(lv, d, out_db, out_rgba, e->cfg.rows, &p, max_columns);
+            live_copy_back(e, lv, d, out_db, out_rgba, e->cfg.rows, &p, max_columns);
         }
         live_push_commit(g, lv.c, p);
     }
@@ -454,6 +527,9 @@ void live_free(LiveState& lv) {
     if (lv.h_orgba) (void)hipHostFree(lv.h_orgba);
     if (lv.h_raw) (void)hipHostFree(lv.h_raw);
     (void)hipFree(lv.d_fresh);
+    (void)hipFree(lv.d_pdb); (void)hipFree(lv.d_wring);
+    if (lv.h_opeaks) (void)hipHostFree(lv.h_opeaks);
+    if (lv.h_owave) (void)hipHostFree(lv.h_owave);
     lv = LiveState{};
 }
 }  // namespace
@@ -593,6 +669,41 @@ int emspec_debug_live_stamps(emspec_engine* e, uint64_t* stamps) {
     return EMSPEC_OK;
 }
 #endif
+
+// ---- the overlays of every streaming call above, on both sessions (live_overlay.hip.inc)
+int emspec_set_live_peaks(emspec_engine* e, int32_t k, float min_db, emspec_peak* peaks_out, int64_t capacity) {
+    if (!e) return EMSPEC_ERR_INVALID_ARG;
+    if (!peaks_out) {
+        e->live_peaks = nullptr; e->live_peaks_capacity = 0; e->live_peaks_k = 0;
+        return EMSPEC_OK;
+    }
+    if (k < 1 || k > 32) return fail(e, EMSPEC_ERR_INVALID_ARG, "k must be in 1..32");
+    if (min_db != min_db) return fail(e, EMSPEC_ERR_INVALID_ARG, "min_db must not be NaN");
+    if (capacity < 0) return fail(e, EMSPEC_ERR_INVALID_ARG, "the peaks' capacity must not be negative");
+    const int R = e->cfg.rows;
+    if (R % 4 || R < 4 || R > 4096) return fail(e, EMSPEC_ERR_INVALID_ARG, "peaks need engine rows that are a multiple of 4 in 4..4096");
+    if (reinterpret_cast<uintptr_t>(peaks_out) % 4) return fail(e, EMSPEC_ERR_INVALID_ARG, "peaks_out must be 4-byte aligned");
+    e->live_peaks = peaks_out; e->live_peaks_capacity = capacity; e->live_peaks_k = k; e->live_peaks_min_db = min_db;
+    return EMSPEC_OK;
+}
+
+int emspec_set_live_wave(emspec_engine* e, emspec_wave* wave_out, int64_t capacity) {
+    if (!e) return EMSPEC_ERR_INVALID_ARG;
+    if (!wave_out) {
+        e->live_wave = nullptr; e->live_wave_capacity = 0;
+        return EMSPEC_OK;
+    }
+    if (capacity < 0) return fail(e, EMSPEC_ERR_INVALID_ARG, "the envelope's capacity must not be negative");
+    if (reinterpret_cast<uintptr_t>(wave_out) % 4) return fail(e, EMSPEC_ERR_INVALID_ARG, "wave_out must be 4-byte aligned");
+    if (e->time_reduce > 1) return fail(e, EMSPEC_ERR_STATE, kNoLiveReduce);
+    // the pair of a column is taken when its frame arrives: a stream that already has frames has columns without a pair
+    for (const LiveState* lv : {&e->live, &e->one})
+        for (int s = 0; s < lv->c.streams(); ++s)
+            if (lv->g.form != 0 && lv->c.fed[s] > 0)
+                return fail(e, EMSPEC_ERR_STATE, "the envelope needs the samples of every column still to come: a session has frames fed; call emspec_reset() first");
+    e->live_wave = wave_out; e->live_wave_capacity = capacity;
+    return EMSPEC_OK;
+}
 
 int emspec_reset_stream(emspec_engine* e, int32_t stream) {
     if (!e) return EMSPEC_ERR_INVALID_ARG;

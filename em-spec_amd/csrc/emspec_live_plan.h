@@ -12,6 +12,15 @@
 #include <type_traits>
 #include <vector>
 
+// the one rule below that the overlay kernel and the host share (as in emspec_kernel_plan.h)
+#ifndef EMSPEC_HD
+#ifdef __HIPCC__
+#define EMSPEC_HD __host__ __device__
+#else
+#define EMSPEC_HD
+#endif
+#endif
+
 namespace emspec {
 
 // ---- live multi-stream streaming (emspec_columns / emspec_push_samples_multi; live.hip.inc) ----
@@ -227,6 +236,40 @@ inline void live_push_commit(const LiveGeometry& g, LiveCounters& c, LivePush& p
         if (p.nc[s] > 0) { p.produced[s] += p.nc[s]; c.emitted[s] = c.fed[s] - g.D; }
     }
 }
+
+// ---- overlays of the live calls (emspec_set_live_peaks / emspec_set_live_wave; live_overlay.hip.inc) ----
+// Which slot of the stream's output block the i-th column of a launch goes to (i < frames; flush form: i < flush), or -1 when
+// the launch does not write it: column c = j0 - D + i; columns below 0 are not emitted - or, in the per-frame form (empty_col),
+// emitted as the empty column.  The rule of live_finalize_column (live.hip.inc), shared with the overlay kernel.
+EMSPEC_HD inline int live_out_slot(long long j0, int out_at, int D, int i, bool empty_col) {
+    if (empty_col) return out_at + i;
+    const long long below = j0 - D < 0 ? D - j0 : 0;
+    return i < below ? -1 : out_at + i - (int)below;
+}
+// A call delivers [S][cols][rows]; beside it peaks_out[(s cols + slot) k + i] and wave_out[s cols + slot].
+inline int64_t live_overlay_pair(int64_t cols, int s, int64_t slot) { return (int64_t)s * cols + slot; }
+// the capacity rule: S cols per (per = k for the peaks, 1 for the envelope) pairs must fit, without overflow for any int64 cols
+inline bool live_overlay_fits(int S, int64_t cols, int per, int64_t capacity) {
+    if (cols <= 0 || S <= 0) return true;
+    return capacity >= 0 && cols <= capacity / ((int64_t)S * per);
+}
+// The envelope's pair ring, per stream [wslots] pairs of 8 bytes: frame j's pair - the key-min / key-max of the hop samples
+// [j hop + off, j hop + off + hop), off = n / 2 - hop / 2, all inside frame j - goes to slot j % wslots when frame j arrives and is
+// read when column j is emitted, D frames later.  A launch feeds frames j0 .. j0 + M - 1 (M <= mmax) and emits columns
+// j0 - D .. j0 + M - 1 - D.  Those at or above j0 belong to frames of the same launch: the emitting wave takes them from the
+// samples, not from the ring, so the kernel needs no order between its waves.  The others, [j0 - D, j0), were written by
+// earlier launches, and the launch's own writes [j0, j0 + M) must not land on them: D + M distinct slots, wslots >= D + mmax.
+// That is also enough over time: slot j % wslots is written again by frame j + D + mmax, and the launch that brings frame j + D
+// (and emits column j, at the latest) ends at frame j + D + mmax - 1 or earlier.  A flush emits columns of [fed - D, fed) from
+// the ring alone.  Every slot is written before it is read (column c is only emitted after frame c was fed since the
+// stream's last reset): emspec_reset_stream clears nothing.
+inline int live_wave_slots(const LiveGeometry& g) { return g.D + g.mmax; }
+inline size_t live_wave_ring_bytes(const LiveGeometry& g) { return (size_t)g.S * live_wave_slots(g) * 8; }
+inline int live_wave_offset(const LiveGeometry& g) { return g.n / 2 - g.hop / 2; }
+// the device block that holds the delivered dB while peaks are set, laid out like the launch's output: [S][cols][R] float32,
+// and the page-locked staging blocks of pageable overlay outputs: [S][cols][k] and [S][cols] pairs
+inline size_t live_peaks_bytes(const LiveGeometry& g, int64_t cols, int k) { return (size_t)g.S * cols * k * 8; }
+inline size_t live_wave_bytes(const LiveGeometry& g, int64_t cols) { return (size_t)g.S * cols * 8; }
 
 // ---- PCM session: the staged samples into the device sample rings, no frame ----
 inline void live_drain_fill(const LiveGeometry& g, const LiveCounters& c, LiveStream* d) {

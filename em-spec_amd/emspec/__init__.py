@@ -60,7 +60,9 @@ PEAKS_SYMBOLS = SYMBOLS[-11:-6]
 WAVE_SYMBOLS = SYMBOLS[-14:-11]
 # the multi-band batch's: likewise (tools/multiband_rate.py may load a library built before them); appended behind the slices above
 MULTIBAND_SYMBOLS = ["emspec_multiband_shifts", "emspec_multiband_columns", "emspec_batch_multiband", "emspec_batch_multiband_device"]
-SYMBOLS = SYMBOLS + MULTIBAND_SYMBOLS
+# the live calls' overlays: likewise (tools/live_rate.py times the parent commit's library next to this build)
+LIVE_OVERLAY_SYMBOLS = ["emspec_set_live_peaks", "emspec_set_live_wave"]
+SYMBOLS = SYMBOLS + MULTIBAND_SYMBOLS + LIVE_OVERLAY_SYMBOLS
 
 
 class Config(C.Structure):
@@ -200,6 +202,11 @@ def wave_host(pcm, n, hop, factor=1, out=None, diag=False):
     if rc != 0:
         raise EmspecError(rc, lib.emspec_last_error(None).decode())
     return out
+
+
+# the 8-byte records of the overlays, as numpy structured types (include/emspec.h: emspec_peak, emspec_wave)
+PEAK_DTYPE = np.dtype([("pos", np.float32), ("db", np.float32)])
+WAVE_DTYPE = np.dtype([("lo", np.float32), ("hi", np.float32)])
 
 
 class EmspecError(RuntimeError):
@@ -350,6 +357,9 @@ def load(diag=False):
                                                C.c_int32, C.c_int32, C.POINTER(Out)]
         lib.emspec_batch_multiband_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                                       C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if all(hasattr(lib, sym) for sym in LIVE_OVERLAY_SYMBOLS):
+        lib.emspec_set_live_peaks.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_int64]
+        lib.emspec_set_live_wave.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     _libs[diag] = lib
     return lib
 
@@ -1104,3 +1114,37 @@ class Engine:
 
     def reset_stream(self, stream):
         self._chk(self._lib.emspec_reset_stream(self._h, stream))
+
+    # -- overlays of every streaming call above (include/emspec.h: emspec_set_live_peaks / emspec_set_live_wave) ------------
+    @staticmethod
+    def _overlay_array(out, dtype):
+        """out: a PinnedArray or a C-contiguous writable numpy array of float32 or of 8-byte records -> (array, pairs)."""
+        arr = out.array if isinstance(out, PinnedArray) else out
+        assert isinstance(arr, np.ndarray) and arr.flags.c_contiguous and arr.flags.writeable
+        assert arr.dtype == np.float32 or arr.dtype == dtype, arr.dtype
+        return arr, arr.nbytes // 8
+
+    def set_live_peaks(self, k, min_db, out):
+        """emspec_set_live_peaks: while set, every streaming call also writes the k loudest peaks at or above min_db of each
+        column it delivers to out[(s * cols + slot) * k + i] (cols: 1 for the per-frame calls and flushes, the call's max_columns
+        for the push calls).  out: a float32 array of (pos, db) pairs, an array of dtype PEAK_DTYPE, or a PinnedArray of either
+        (written in place by the kernel); None clears.  The engine keeps a reference while it is set."""
+        if out is None:
+            self._chk(self._lib.emspec_set_live_peaks(self._h, 0, 0.0, None, 0))
+            self._live_peaks = None
+            return
+        arr, pairs = self._overlay_array(out, PEAK_DTYPE)
+        self._chk(self._lib.emspec_set_live_peaks(self._h, int(k), float(min_db), _np_ptr(arr), pairs))
+        self._live_peaks = out
+
+    def set_live_wave(self, out):
+        """emspec_set_live_wave: while set, every streaming call also writes the (lo, hi) envelope pair of the samples under each
+        column it delivers to out[s * cols + slot].  out as for set_live_peaks (dtype WAVE_DTYPE); None clears.  Set it before
+        the sessions' first frames (or after reset())."""
+        if out is None:
+            self._chk(self._lib.emspec_set_live_wave(self._h, None, 0))
+            self._live_wave = None
+            return
+        arr, pairs = self._overlay_array(out, WAVE_DTYPE)
+        self._chk(self._lib.emspec_set_live_wave(self._h, _np_ptr(arr), pairs))
+        self._live_wave = out

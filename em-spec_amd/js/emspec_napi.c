@@ -44,16 +44,20 @@ static napi_value throw_status(napi_env env, emspec_engine* e, int rc) {
     return NULL;
 }
 
-/* rows: the engine's row count, for output-size checks; wave: the array given to setWaveOut, referenced while it is set */
-typedef struct { emspec_engine* e; int32_t rows; napi_ref wave; } handle_t;
+/* rows: the engine's row count, for output-size checks; wave: the array given to setWaveOut, referenced while it is set;
+ * live_peaks / live_wave: likewise the arrays given to setLivePeaks / setLiveWave */
+typedef struct { emspec_engine* e; int32_t rows; napi_ref wave, live_peaks, live_wave; } handle_t;
 
+static void drop_ref(napi_env env, napi_ref* r) {
+    if (*r) { napi_delete_reference(env, *r); *r = NULL; }
+}
 static void drop_wave(napi_env env, handle_t* h) {
-    if (h->wave) { napi_delete_reference(env, h->wave); h->wave = NULL; }
+    drop_ref(env, &h->wave);
 }
 static void finalize_handle(napi_env env, void* data, void* hint) {
     (void)hint;
     handle_t* h = (handle_t*)data;
-    if (h) { if (h->e) emspec_destroy(h->e); drop_wave(env, h); free(h); }
+    if (h) { if (h->e) emspec_destroy(h->e); drop_wave(env, h); drop_ref(env, &h->live_peaks); drop_ref(env, &h->live_wave); free(h); }
 }
 
 static int get_number_prop(napi_env env, napi_value obj, const char* name, double* out) {
@@ -131,6 +135,7 @@ static napi_value Create(napi_env env, napi_callback_info info) {
     h->e = e;
     h->rows = cfg.rows;
     h->wave = NULL;
+    h->live_peaks = h->live_wave = NULL;
     napi_value ext;
     if (napi_create_external(env, h, finalize_handle, NULL, &ext) != napi_ok) {
         finalize_handle(env, h, NULL);
@@ -148,6 +153,8 @@ static napi_value Destroy(napi_env env, napi_callback_info info) {
         handle_t* h = (handle_t*)p;
         if (h->e) { emspec_destroy(h->e); h->e = NULL; }
         drop_wave(env, h);
+        drop_ref(env, &h->live_peaks);
+        drop_ref(env, &h->live_wave);
     }
     return NULL;
 }
@@ -1234,6 +1241,50 @@ static napi_value SetWaveOut(napi_env env, napi_callback_info info) {
     h->wave = ref;
     return NULL;
 }
+/* Overlays of the live calls (include/emspec.h: emspec_set_live_peaks / emspec_set_live_wave).
+ * setLivePeaks(handle, k, minDb, peaks:Float32Array | null): capacity peaks.length / 2 pairs
+ * setLiveWave(handle, wave:Float32Array | null): capacity wave.length / 2 pairs
+ * While set, every live call also fills them; the addon references an array until it is replaced, cleared or the engine is
+ * destroyed.  index.js hands over page-locked arrays, which the kernel writes in place. */
+static napi_value SetLivePeaks(napi_env env, napi_callback_info info) {
+    size_t argc = 4; napi_value argv[4];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 4) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "setLivePeaks(handle, k, minDb, peaks)"); return NULL; }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    int32_t k = 0; double min_db = 0;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[1], &k));
+    NAPI_OK_OR_RETURN(env, napi_get_value_double(env, argv[2], &min_db));
+    void* arr = NULL; size_t len = 0;
+    if (!get_typed(env, argv[3], napi_float32_array, &arr, &len, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "peaks must be a Float32Array or null"); return NULL; }
+    napi_ref ref = NULL;
+    if (arr) NAPI_OK_OR_RETURN(env, napi_create_reference(env, argv[3], 1, &ref));
+    int rc = emspec_set_live_peaks(h->e, k, (float)min_db, (emspec_peak*)arr, arr ? (int64_t)(len / 2) : 0);
+    if (rc != EMSPEC_OK) {
+        if (ref) napi_delete_reference(env, ref);
+        return throw_status(env, h->e, rc);
+    }
+    drop_ref(env, &h->live_peaks);
+    h->live_peaks = ref;
+    return NULL;
+}
+static napi_value SetLiveWave(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "setLiveWave(handle, wave)"); return NULL; }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    void* arr = NULL; size_t len = 0;
+    if (!get_typed(env, argv[1], napi_float32_array, &arr, &len, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "wave must be a Float32Array or null"); return NULL; }
+    napi_ref ref = NULL;
+    if (arr) NAPI_OK_OR_RETURN(env, napi_create_reference(env, argv[1], 1, &ref));
+    int rc = emspec_set_live_wave(h->e, (emspec_wave*)arr, arr ? (int64_t)(len / 2) : 0);
+    if (rc != EMSPEC_OK) {
+        if (ref) napi_delete_reference(env, ref);
+        return throw_status(env, h->e, rc);
+    }
+    drop_ref(env, &h->live_wave);
+    h->live_wave = ref;
+    return NULL;
+}
 static napi_value WaveOf(napi_env env, napi_callback_info info) {
     size_t argc = 7; napi_value argv[7];
     NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -1467,6 +1518,8 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"peaksOf", NULL, PeaksOf, NULL, NULL, NULL, napi_default, NULL},
         {"setWaveOut", NULL, SetWaveOut, NULL, NULL, NULL, napi_default, NULL},
         {"waveOf", NULL, WaveOf, NULL, NULL, NULL, napi_default, NULL},
+        {"setLivePeaks", NULL, SetLivePeaks, NULL, NULL, NULL, napi_default, NULL},
+        {"setLiveWave", NULL, SetLiveWave, NULL, NULL, NULL, napi_default, NULL},
         {"positionHz", NULL, PositionHz, NULL, NULL, NULL, napi_default, NULL},
         {"setRowEdges", NULL, SetRowEdges, NULL, NULL, NULL, napi_default, NULL},
         {"getRowEdges", NULL, GetRowEdges, NULL, NULL, NULL, napi_default, NULL},

@@ -50,6 +50,32 @@ class Engine {
    */
   setWaveOut(wave) { native.setWaveOut(this._h, wave === undefined ? null : wave); }
 
+  /**
+   * Overlays of the live calls (emspec_set_live_peaks / emspec_set_live_wave; DESIGN.md §4.15): while set, every live call of
+   * this engine also fills engine.columnsPeaks - Float32Array of (pos, dB) pairs, [(s * cols + slot) * k + i] - and
+   * engine.columnsWave - (lo, hi) pairs, [s * cols + slot] - for exactly the column slots it writes: cols = 1 for
+   * computeSpectrogramColumn(s) and the flushes, the call's maxColumns for the push calls.  Both are page-locked and sized like
+   * engine.columnsDb, for `columns` columns per stream (default 1: one hop per call; a push that may complete more needs
+   * {columns} at least its maxColumns, or it throws EMSPEC_ERR_INVALID_ARG).  The peaks are peaksOf(the delivered dB, k, minDb),
+   * written also when only RGBA is taken; the envelope is waveOf(the samples fed) column by column, and can only be switched on
+   * before a session's first frame (or after reset()).  null / false clears.
+   */
+  setLivePeaks(opts) {
+    if (!opts) { native.setLivePeaks(this._h, 0, 0, null); this.columnsPeaks = undefined; return; }
+    const k = opts.k === undefined ? 8 : opts.k | 0, minDb = opts.minDb === undefined ? -60 : +opts.minDb;
+    const cols = Math.max(1, opts.columns | 0);
+    const arr = new Float32Array(native.allocPinned(8 * this.streams * cols * Math.max(k, 1)));
+    native.setLivePeaks(this._h, k, minDb, arr);
+    this.columnsPeaks = arr;
+  }
+  setLiveWave(opts) {
+    if (!opts) { native.setLiveWave(this._h, null); this.columnsWave = undefined; return; }
+    const cols = Math.max(1, (opts === true ? 1 : opts.columns) | 0);
+    const arr = new Float32Array(native.allocPinned(8 * this.streams * cols));
+    native.setLiveWave(this._h, arr);
+    this.columnsWave = arr;
+  }
+
   /** Page-locked Float32Array / Uint8Array views for the live calls, (re)made when the shape changes. */
   _liveBlocks(fftSize, wantRgba) {
     const S = this.streams, R = this.rows;

@@ -768,8 +768,7 @@ int emspec_position_hz(emspec_engine* e, float pos, double* hz);
  * rule of the reduced columns it sits under).  For the PCM entries the samples are the decoded, mixed float32 values of the
  * views; for emspec_batch_multires the column grid is the long band's, n = n_low
  * (emspec_batch_multiband: n = n[0]).
- * NOT for the live calls (emspec_columns, emspec_push_samples*): a live host holds the hop it has just pushed, and the pair of
- * column c would have to be kept D columns until c is emitted.  No RMS or other sum: a float sum depends on its order.
+ * The live calls deliver it through emspec_set_live_wave (below).  No RMS or other sum: a float sum depends on its order.
  */
 typedef struct emspec_wave { float lo; float hi; } emspec_wave;   /* 8 bytes */
 
@@ -796,6 +795,45 @@ int emspec_wave_host(const float* pcm, int32_t S, int64_t L, int32_t n, int32_t 
 int emspec_set_wave_out(emspec_engine* e, emspec_wave* wave_out, int64_t capacity /* pairs */);
 /* Every refusal above is EMSPEC_ERR_INVALID_ARG with a message naming the rule - a factor outside 1 .. 65536, a hop outside
  * 1 .. n, an unsupported n, S outside 0 .. 65535, null or misaligned pointers, a negative capacity - and leaves the engine usable. */
+
+/*
+ * ---- Overlays of the streaming calls: the spectral peaks of every column a live call delivers
+ * and the waveform envelope of the samples under it, written by one more kernel behind the call's launch.  Serves: a live
+ * viewer's note / frequency read-out and the waveform it draws beside the scrolling image - 64 bytes of peaks per column
+ * instead of the 4 KB dB column over PCIe, and the envelope of a PCM session's views, whose float streams exist in no host
+ * buffer; [BUILD-DEFINED].
+ *
+ * While a setting is on, every streaming call on either session of the engine - emspec_column, emspec_column_flush,
+ * emspec_push_samples; emspec_columns, emspec_columns_flush, emspec_push_samples_multi; the _multires forms;
+ * emspec_push_samples_pcm and _pcm_multires - also writes the overlay, for exactly the column slots it writes.  A call delivers
+ * its dB as [S][cols][rows] (cols = 1 for the per-frame calls and the flushes, max_columns for the push calls); the same call
+ * writes
+ *     peaks_out[(s * cols + slot) * k + i],  i in 0 .. k-1        and        wave_out[s * cols + slot]
+ * and leaves the other slots untouched; out_columns / out_counts / out_first_columns mean what they mean without overlays.
+ * A push call with an overlay on must fit max_columns like one with an output.  A call with S * cols * k (peaks) or S * cols
+ * (envelope) above the capacity returns EMSPEC_ERR_INVALID_ARG before anything is fed; the session stays as it was.
+ * Both arrays are host memory, 4-byte aligned, valid while set: page-locked (emspec_host_alloc, 8-byte aligned) they are
+ * written in place by the kernel, pageable they are staged and copied after the call's synchronisation, as out_db is.  NULL
+ * clears a setting; with both cleared the calls launch, allocate and write exactly what they did before these entries.
+ *
+ * Peaks: those of emspec_peaks_host(k, min_db) applied to the dB column the call delivers - the post-processed column with
+ * emspec_set_display on, the composed column of a multi-resolution session, the empty column "-1" of the per-frame form - so
+ * byte-equal to emspec_peaks_host on the delivered bytes in both modes; written whether or not out_db is given (a renderer
+ * that takes RGBA only still gets them).  Stateless: set, changed or cleared between any two calls.
+ * EMSPEC_ERR_INVALID_ARG: k outside 1 .. 32, a NaN min_db, a negative capacity, engine rows that break the rule of
+ * emspec_peaks_device (rows % 4 == 0, 4 <= rows <= 4096).
+ *
+ * Envelope: the pair of the definition above at factor 1 on the session's grid - n the session's FFT size (n_low for a
+ * multi-resolution session), column c covers the samples [c hop + off, c hop + off + hop) of its stream, off = n / 2 - hop / 2;
+ * the empty column of the per-frame form gives (+INFINITY, -INFINITY).  For a stream fed [0, L) and then flushed the emitted
+ * pairs are byte-equal to emspec_wave_host(pcm, 1, L, n, hop, 1), in both modes; for a PCM session the samples are the decoded,
+ * mixed float32 values of each view.  The pair of column c is taken when frame c arrives and kept on the device until c is
+ * emitted, so the setting needs the session's whole history: with a non-NULL array it returns EMSPEC_ERR_STATE while either
+ * session has frames fed (emspec_reset first) or a time reduction is set.  emspec_reset_stream restarts that stream's envelope
+ * with its columns.  Clearing is always allowed.
+ */
+int emspec_set_live_peaks(emspec_engine* e, int32_t k, float min_db, emspec_peak* peaks_out, int64_t capacity /* pairs */);
+int emspec_set_live_wave(emspec_engine* e, emspec_wave* wave_out, int64_t capacity /* pairs */);
 
 #ifdef __cplusplus
 }
