@@ -149,6 +149,16 @@ hipError_t launch_multiband_compose(const BandSrc& b, int S, int64_t C, int R, c
 // (ncol: the largest number of columns any stream emits - grid (ncol, S), one workgroup per column)
 hipError_t launch_live_flush(bool exact, const LiveSinks& lv, void* cells, int slots, int rows, int D, const DbMap& m,
                              const ExactDbMap& xm, int S, int ncol, hipStream_t st);
+// ... of a live multi-band session: every band's rows of each column in ONE launch (live_finalize_bands_kernel).  Band k: its ring
+// [S][slots][rows], the first of its rows in the output column, and its conversion (FAST: m, EXACT: xm).  lv.row0 is not read.
+struct LiveBandRings {
+    int bands = 0;
+    void* cells[kMaxBands] = {};
+    int slots[kMaxBands] = {}, rows[kMaxBands] = {}, row0[kMaxBands] = {};
+    DbMap m[kMaxBands] = {};
+    ExactDbMap xm[kMaxBands] = {};
+};
+hipError_t launch_live_finalize_bands(bool exact, const LiveSinks& lv, const LiveBandRings& r, int D, int S, int ncol, hipStream_t st);
 hipError_t launch_live_post(const LiveSinks& lv, const float* raw, int raw_cols, int rows, int D, float sm, float agc, float db_top,
                             const DbMap& dm, float* pstate, int S, hipStream_t st);
 // The overlays of a live launch (live_overlay.hip.inc; emspec_set_live_peaks / emspec_set_live_wave): one kernel behind the

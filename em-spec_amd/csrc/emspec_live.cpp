@@ -24,6 +24,7 @@
 #endif
 
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 
 using namespace emspec;
@@ -52,39 +53,56 @@ void live_forget(LiveState& lv) {
     lv.g = LiveGeometry{};
     lv.c = LiveCounters{};
     lv.pcm = LivePcm{};
+    lv.mb = LiveBandGeometry{};
 }
 
 // first call of a session: every allocation, then the state.  n_high != 0: a multi-resolution session (n = n_low; rows below
 // `split` from n, the rest from n_high).
 // pcm: a PCM session - its staging block holds raw frames (live_open_pcm), not floats.
+// bp != null: a multi-band session (n = bp->n[0], n_high = 0): K rings and K sets of arrival counters, everything else that of
+// the single-resolution session at n[0].
 int live_open(emspec_engine* e, LiveState& lv, int S, int n, int hop, int reassign, int form, int n_high = 0, int split = 0,
-              bool pcm = false) {
-    const LiveGeometry g = live_geometry(S, n, hop, reassign, form, n_high, split);
+              bool pcm = false, const BandPlan* bp = nullptr) {
+    const LiveBandGeometry mb = bp ? live_band_geometry(S, *bp, hop, reassign, form) : LiveBandGeometry{};
+    const LiveGeometry g = bp ? mb.g : live_geometry(S, n, hop, reassign, form, n_high, split);
     const int R = e->cfg.rows;
     const size_t cell = e->exact() ? 8 : 4;
+    // the rings: band 0's, then those of the bands behind it (a multi-resolution session: the short band's)
+    const int K = bp ? mb.bands : n_high ? 2 : 1;
+    size_t ring[kMaxBands] = {g.rings_bytes(R, cell), g.rings_high_bytes(R, cell)};
+    for (int k = 0; bp && k < K; ++k) ring[k] = mb.rings_bytes(k, cell);
+    const size_t done = bp ? mb.done_bytes() : g.done_bytes();
     int rc;
-    if ((rc = grow(e, &lv.d_cells, &lv.cells_bytes, g.rings_bytes(R, cell)))) return rc;
-    if (n_high && (rc = grow(e, &lv.d_cells_high, &lv.cells_high_bytes, g.rings_high_bytes(R, cell)))) return rc;
+    if ((rc = grow(e, &lv.d_cells, &lv.cells_bytes, ring[0]))) return rc;
+    for (int k = 1; k < K; ++k)
+        if ((rc = grow(e, &lv.d_cells_band[k - 1], &lv.cells_band_bytes[k - 1], ring[k]))) return rc;
     if (form == 2 && (rc = grow(e, (void**)&lv.d_sring, &lv.sring_bytes, g.sring_bytes()))) return rc;
-    if ((rc = grow(e, (void**)&lv.d_done, &lv.done_bytes, g.done_bytes()))) return rc;
+    if ((rc = grow(e, (void**)&lv.d_done, &lv.done_bytes, done))) return rc;
     if ((rc = pinned_grow(e, &lv.h_desc, &lv.desc_bytes, g.desc_bytes()))) return rc;
     if (form == 2 && !pcm && (rc = pinned_grow(e, (void**)&lv.h_fresh, &lv.fresh_bytes, g.fresh_bytes()))) return rc;
-    HIPCHK(e, hipMemsetAsync(lv.d_cells, 0, g.rings_bytes(R, cell), e->stream));
-    if (n_high) HIPCHK(e, hipMemsetAsync(lv.d_cells_high, 0, g.rings_high_bytes(R, cell), e->stream));
-    HIPCHK(e, hipMemsetAsync(lv.d_done, 0, g.done_bytes(), e->stream));
+    HIPCHK(e, hipMemsetAsync(lv.d_cells, 0, ring[0], e->stream));
+    for (int k = 1; k < K; ++k) HIPCHK(e, hipMemsetAsync(lv.d_cells_band[k - 1], 0, ring[k], e->stream));
+    HIPCHK(e, hipMemsetAsync(lv.d_done, 0, done, e->stream));
     if (lv.d_pstate) HIPCHK(e, hipMemsetAsync(lv.d_pstate, 0, lv.pstate_bytes, e->stream));
     lv.g = g;
+    lv.mb = mb;
     lv.c.open(S);
     return EMSPEC_OK;
 }
 
+// (bp != null: a multi-band call - its shape and split rows were checked by the entry, n is bp->n[0] and n_high is 0)
 int live_check(emspec_engine* e, const LiveState& lv, int S, int n, int hop, int reassign, int rows, int form, int n_high = 0,
-               int split = 0) {
+               int split = 0, const BandPlan* bp = nullptr) {
     const LiveGeometry& g = lv.g;
     int rc = n_high ? multires_check(e, S, n, n_high, hop, split) : check_shape(e, n, hop);
     if (rc) return rc;
     if (rows != e->cfg.rows) return fail(e, EMSPEC_ERR_INVALID_ARG, "rows does not match the engine configuration");
     if (S < 1 || S > 65535) return fail(e, EMSPEC_ERR_INVALID_ARG, "streams must be in 1..65535");
+    if (g.form != 0 && (bp != nullptr) != (lv.mb.bands != 0))
+        return fail(e, EMSPEC_ERR_STATE, lv.mb.bands ? "the live session is a multi-band one (emspec_columns_multiband / emspec_push_samples_multiband); call emspec_reset() first"
+                                                     : "the live session is not a multi-band one; call emspec_reset() before a multi-band call");
+    if (g.form != 0 && bp && (S != g.S || hop != g.hop || reassign != g.reassign || form != g.form || !lv.mb.same_bands(*bp)))
+        return fail(e, EMSPEC_ERR_STATE, "streams / bands / fft sizes / split rows / hop / reassign / feeding mode changed mid-stream; call emspec_reset() first");
     if (g.form != 0 && (n_high != 0) != (g.n_high != 0))
         return fail(e, EMSPEC_ERR_STATE, g.n_high ? "the live session is a multi-resolution one (emspec_columns_multires / emspec_push_samples_multires); call emspec_reset() first"
                                                   : "the live session is a single-resolution one; call emspec_reset() before a multi-resolution call");
@@ -167,6 +185,10 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
     }
     const DbMap m = db_map(e, g.n);
     const bool exact = e->exact();
+    // a multi-band session: its flush is one launch for all bands, and its bands defer their finalize together or not at all
+    // (emspec_live_band_plan.h: defers) - to one launch of live_finalize_bands_kernel behind the last band's frames
+    const LiveBandGeometry& mb = lv.mb;
+    const bool bands_defer = mb.bands && !flush && mb.defers(mlaunch, kInlineFinalize);
     // One band: its frame launch (or, flush = true, the flush kernel) on rows [p.row0, p.row0 + p.rows) of the output column.
     // A single-resolution session is one band of all rows; a multi-resolution one runs the long band, then the short band,
     // each finalising its own rows of the same column in place (live.hip.inc: live_finalize_column).
@@ -180,7 +202,7 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
         // (inline they are one workgroup's serial round trips to the memory side, ~2 us per column)
         // ... and so does a small transform: its workgroup has n / 16 (EXACT: n / 8) threads, and 1024 rows through 16 threads
         // are 8 serial batches of round trips (emspec_column at N = 256: 32.6 us per call against 25.7 at N = 4096)
-        const bool defer = !flush && (mlaunch > kInlineFinalize || p.n < 2048);
+        const bool defer = mb.bands ? bands_defer : !flush && (mlaunch > kInlineFinalize || p.n < 2048);
         LiveSinks bs = bl;
         bs.defer_finalize = defer ? 1 : 0;
         if (flush) {
@@ -201,11 +223,51 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
             HIPCHK(e, launch_frames(p.n, plan_dev(e, p, g.hop, g.reassign), nullptr, 0, g.S, 0, (int64_t)frames + 1, sk, e->stream));
         }
         // (the columns a launch completes are the long band's frame count for either band)
-        if (defer) HIPCHK(e, launch_live_flush(exact, bs, cells, slots, p.rows, g.D, bm, xm, g.S, mlaunch, e->stream));
+        if (defer && !mb.bands) HIPCHK(e, launch_live_flush(exact, bs, cells, slots, p.rows, g.D, bm, xm, g.S, mlaunch, e->stream));
         return EMSPEC_OK;
     };
     Plan* p;
-    if (!g.n_high) {
+    if (mb.bands) {
+        Plan* pb[kMaxBands];
+        LiveBandRings fin;
+        fin.bands = mb.bands;
+        for (int k = 0; k < mb.bands; ++k) {
+            const LiveBand& b = mb.b[k];
+            if ((rc = get_band_plan(e, b.n, b.lo, b.rows(), &pb[k]))) return rc;
+            fin.cells[k] = k ? lv.d_cells_band[k - 1] : lv.d_cells;
+            fin.slots[k] = b.slots; fin.rows[k] = b.rows(); fin.row0[k] = b.lo;
+            if (!(flush || bands_defer)) continue;   // (the conversions are the bands kernel's alone)
+            fin.m[k] = db_map(e, b.n);
+            if (exact) fin.xm[k] = exact_db_map(e, b.n, exact_plan_dev(e, *pb[k], g.hop, g.reassign));
+        }
+        // band 0's frame launch carries the ingest workgroup; the others follow without one, and not at all when no stream has
+        // a frame
+        for (int k = 0; !flush && k < mb.bands && (k == 0 || mlaunch > 0); ++k) {
+            const LiveBand& b = mb.b[k];
+            LiveSinks bs = ls;
+            bs.row0 = b.lo;
+            bs.frame_shift = b.frame_shift;
+            bs.col_shift = b.shift;
+            bs.lat_extra = b.lat_extra;
+            bs.no_ingest = k ? 1 : 0;
+            bs.done = lv.d_done + (size_t)k * g.S;
+            if ((rc = band(*pb[k], bs, fin.cells[k], b.slots, mb.launch_frames(k, mlaunch, priming)))) return rc;
+        }
+        if (flush || bands_defer) {
+            const int ncol = flush ? 1 : mlaunch;
+#ifdef EMSPEC_DIAG
+            // A/B aid (tools/live_multiband_rate.py): the K-launch form, one live_finalize_kernel per band
+            static const bool per_band = [] { const char* ev = getenv("EMSPEC_LIVE_FINALIZE_PER_BAND"); return ev && ev[0] == '1'; }();
+            for (int k = 0; per_band && k < mb.bands; ++k) {
+                LiveSinks bs = ls;
+                bs.row0 = fin.row0[k];
+                HIPCHK(e, launch_live_flush(exact, bs, fin.cells[k], fin.slots[k], fin.rows[k], g.D, fin.m[k], fin.xm[k], g.S, ncol, e->stream));
+            }
+            if (per_band) fin.bands = 0;   // (the launcher does nothing without bands)
+#endif
+            HIPCHK(e, launch_live_finalize_bands(exact, ls, fin, g.D, g.S, ncol, e->stream));
+        }
+    } else if (!g.n_high) {
         if ((rc = get_plan(e, g.n, &p))) return rc;
         if ((rc = band(*p, ls, lv.d_cells, g.slots, mlaunch))) return rc;
     } else {
@@ -223,7 +285,7 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
             hs.lat_extra = g.D - g.D_high;
             hs.no_ingest = 1;
             hs.done = lv.d_done + g.S;
-            if ((rc = band(*ph, hs, lv.d_cells_high, g.slots_high, mlaunch + (priming ? 2 * g.shift : 0)))) return rc;
+            if ((rc = band(*ph, hs, lv.d_cells_band[0], g.slots_high, mlaunch + (priming ? 2 * g.shift : 0)))) return rc;
         }
     }
     if (post) {
@@ -394,17 +456,19 @@ int live_overlay_check(emspec_engine* e, int S, int64_t cols) {
 const char* const kNoLiveReduce = "the streaming calls return full-rate columns: not available while a time reduction is set (emspec_set_time_reduce(e, 1) turns it off)";
 
 // (n_high != 0: the multi-resolution form - n is n_low, the frames are n_low samples long and the short band reads the newest
-// n_high of them; on a stream's first frame it reads all of it, frames 0 .. 2 shift)
+// n_high of them; on a stream's first frame it reads all of it, frames 0 .. 2 shift.  bp != null: the multi-band form, n = n[0],
+// every shorter band as that short band)
 int columns_impl(emspec_engine* e, LiveState& lv, const float* frames, int32_t streams, int32_t n, int32_t hop, int32_t reassign,
-                 float* out_db, uint8_t* out_rgba, int32_t rows, int64_t* out_columns, int32_t n_high = 0, int32_t split = 0) {
+                 float* out_db, uint8_t* out_rgba, int32_t rows, int64_t* out_columns, int32_t n_high = 0, int32_t split = 0,
+                 const BandPlan* bp = nullptr) {
     if (e && e->time_reduce > 1) return fail(e, EMSPEC_ERR_STATE, kNoLiveReduce);
     if (!e || !frames) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument");
     reassign = reassign ? 1 : 0;
-    int rc = live_check(e, lv, streams, n, hop, reassign, rows, 1, n_high, split);
+    int rc = live_check(e, lv, streams, n, hop, reassign, rows, 1, n_high, split, bp);
     if (rc) return rc;
     if ((rc = live_overlay_check(e, streams, 1))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
-    if (lv.g.form == 0 && (rc = live_open(e, lv, streams, n, hop, reassign, 1, n_high, split))) return rc;
+    if (lv.g.form == 0 && (rc = live_open(e, lv, streams, n, hop, reassign, 1, n_high, split, false, bp))) return rc;
     // the frames: read by the kernel where they are when the caller's block is page-locked, else staged
     const float* src = reinterpret_cast<const float*>(device_view(frames));
     if (!src) {
@@ -445,20 +509,20 @@ int64_t push_columns_impl(const emspec_engine* e, const LiveState& lv, int64_t c
     return live_push_columns(lv.g, lv.c, count, n, hop, reassign);
 }
 
-// (n_high != 0: the multi-resolution form - n is n_low; max_columns then bounds what the block may complete whether or not an
+// (n_high != 0, or bp != null: the multi-resolution / multi-band form - n is n_low / n[0]; max_columns then bounds what the block may complete whether or not an
 // output is given: it is the stride of every block the launch writes)
 // (fmt != null: the PCM form - `block` holds raw interleaved frames, `count` of them per source, source i at block + i * stride
 // BYTES, and streams = sources * fmt->views; as for the multi-resolution form, max_columns always bounds what a block completes)
 int push_impl(emspec_engine* e, LiveState& lv, const void* block, int32_t streams, int64_t count, int64_t stride, int32_t n,
               int32_t hop, int32_t reassign, float* out_db, uint8_t* out_rgba, int32_t rows, int64_t max_columns,
               int64_t* out_counts, int64_t* out_first_columns, int32_t n_high = 0, int32_t split = 0,
-              const emspec_pcm_format* fmt = nullptr) {
+              const emspec_pcm_format* fmt = nullptr, const BandPlan* bp = nullptr) {
     if (e && e->time_reduce > 1) return fail(e, EMSPEC_ERR_STATE, kNoLiveReduce);
     const float* samples = static_cast<const float*>(block);
     const int fb = fmt ? pcm_frame_bytes(*fmt) : 1;   // (the float form's stride counts samples)
     if (!e || (!block && count > 0) || count < 0 || stride / fb < count) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument, negative count or stride < count");
     reassign = reassign ? 1 : 0;
-    int rc = live_check(e, lv, streams, n, hop, reassign, rows, 2, n_high, split);
+    int rc = live_check(e, lv, streams, n, hop, reassign, rows, 2, n_high, split, bp);
     if (rc) return rc;
     if (lv.g.form != 0 && (fmt != nullptr) != (lv.pcm.views != 0))
         return fail(e, EMSPEC_ERR_STATE, lv.pcm.views ? "the live session is a PCM one (emspec_push_samples_pcm); call emspec_reset() before a float call"
@@ -468,13 +532,13 @@ int push_impl(emspec_engine* e, LiveState& lv, const void* block, int32_t stream
     if (max_columns < 0) return fail(e, EMSPEC_ERR_INVALID_ARG, "max_columns must be >= 0");
     const int64_t expect = push_columns_impl(e, lv, count, n, hop, reassign);
     // (an overlay is an output too: its slots are the columns of [S][max_columns])
-    if ((out_db || out_rgba || n_high || fmt || e->live_peaks || e->live_wave) && expect > max_columns)
+    if ((out_db || out_rgba || n_high || bp || fmt || e->live_peaks || e->live_wave) && expect > max_columns)
         return fail(e, EMSPEC_ERR_INVALID_ARG, "output holds fewer columns than this block completes (" + std::to_string(expect) +
                                                    "); size it with emspec_push_columns() / emspec_push_columns_multi()");
     if ((rc = live_overlay_check(e, streams, max_columns))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     if (lv.g.form == 0) {
-        if ((rc = live_open(e, lv, streams, n, hop, reassign, 2, n_high, split, fmt != nullptr))) return rc;
+        if ((rc = live_open(e, lv, streams, n, hop, reassign, 2, n_high, split, fmt != nullptr, bp))) return rc;
         if (fmt && (rc = live_open_pcm(e, lv, *fmt))) { live_forget(lv); return rc; }
     }
     const LiveGeometry& g = lv.g;
@@ -520,7 +584,9 @@ int push_impl(emspec_engine* e, LiveState& lv, const void* block, int32_t stream
 }
 
 void live_free(LiveState& lv) {
-    (void)hipFree(lv.d_cells); (void)hipFree(lv.d_cells_high); (void)hipFree(lv.d_sring); (void)hipFree(lv.d_done); (void)hipFree(lv.d_raw); (void)hipFree(lv.d_pstate);
+    (void)hipFree(lv.d_cells); (void)hipFree(lv.d_sring);
+    for (void* ring : lv.d_cells_band) (void)hipFree(ring);
+    (void)hipFree(lv.d_done); (void)hipFree(lv.d_raw); (void)hipFree(lv.d_pstate);
     if (lv.h_desc) (void)hipHostFree(lv.h_desc);
     if (lv.h_fresh) (void)hipHostFree(lv.h_fresh);
     if (lv.h_odb) (void)hipHostFree(lv.h_odb);
@@ -597,6 +663,41 @@ int emspec_push_samples_multires(emspec_engine* e, const float* samples, int32_t
                      out_counts, out_first_columns, n_high, split_row);
 }
 
+// ---- the live session's multi-band form: 2..4 bands of the row table, band k from n[k], one column per hop with
+// the latency of n[0].  emspec_columns_flush / emspec_reset_stream / emspec_live_streams and the overlays serve it as above.
+// Shapes and split rows: the multi-band batch's rules and words (emspec_band_plan.h), before anything is fed.
+static int multiband_entry_check(emspec_engine* e, int32_t bands, const int32_t* n, const int32_t* split_rows, int32_t hop) {
+    if (!e) return EMSPEC_ERR_INVALID_ARG;
+    if (e->time_reduce > 1) return fail(e, EMSPEC_ERR_STATE, kNoLiveReduce);
+    if (const char* why = band_shape_error(bands, n, hop)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
+    if (const char* why = band_split_error(bands, split_rows, e->cfg.rows)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
+    return EMSPEC_OK;
+}
+
+int emspec_columns_multiband(emspec_engine* e, const float* frames, int32_t streams, int32_t bands, const int32_t* n,
+                             const int32_t* split_rows, int32_t hop, int32_t reassign, float* out_db, uint8_t* out_rgba, int32_t rows,
+                             int64_t* out_columns) {
+    if (int rc = multiband_entry_check(e, bands, n, split_rows, hop)) return rc;
+    const BandPlan bp = band_plan(bands, n, split_rows, hop, e->cfg.rows);
+    return columns_impl(e, e->live, frames, streams, n[0], hop, reassign, out_db, out_rgba, rows, out_columns, 0, 0, &bp);
+}
+
+int64_t emspec_push_columns_multiband(const emspec_engine* e, int64_t count, int32_t bands, const int32_t* n, int32_t hop,
+                                      int32_t reassign) {
+    if (!e || band_shape_error(bands, n, hop)) return -1;
+    return push_columns_impl(e, e->live, count, n[0], hop, reassign);
+}
+
+int emspec_push_samples_multiband(emspec_engine* e, const float* samples, int32_t streams, int64_t count, int64_t stride,
+                                  int32_t bands, const int32_t* n, const int32_t* split_rows, int32_t hop, int32_t reassign,
+                                  float* out_db, uint8_t* out_rgba, int32_t rows, int64_t max_columns, int64_t* out_counts,
+                                  int64_t* out_first_columns) {
+    if (int rc = multiband_entry_check(e, bands, n, split_rows, hop)) return rc;
+    const BandPlan bp = band_plan(bands, n, split_rows, hop, e->cfg.rows);
+    return push_impl(e, e->live, samples, streams, count, stride, n[0], hop, reassign, out_db, out_rgba, rows, max_columns, out_counts,
+                     out_first_columns, 0, 0, nullptr, &bp);
+}
+
 // ---- the live session fed raw interleaved frames (include/emspec.h, PCM front end): sources * views streams
 static int pcm_entry_check(emspec_engine* e, const emspec_pcm_format* fmt, int32_t sources) {
     if (!e) return EMSPEC_ERR_INVALID_ARG;
@@ -621,6 +722,17 @@ int emspec_push_samples_pcm_multires(emspec_engine* e, const void* block, const 
     if (const char* why = multires_shape_error(n_low, n_high, hop)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
     return push_impl(e, e->live, block, sources * fmt->views, count, stride_bytes, n_low, hop, reassign, out_db, out_rgba, rows,
                      max_columns, out_counts, out_first_columns, n_high, split_row, fmt);
+}
+
+int emspec_push_samples_pcm_multiband(emspec_engine* e, const void* block, const emspec_pcm_format* fmt, int32_t sources,
+                                      int64_t count, int64_t stride_bytes, int32_t bands, const int32_t* n, const int32_t* split_rows,
+                                      int32_t hop, int32_t reassign, float* out_db, uint8_t* out_rgba, int32_t rows,
+                                      int64_t max_columns, int64_t* out_counts, int64_t* out_first_columns) {
+    if (int rc = pcm_entry_check(e, fmt, sources)) return rc;
+    if (int rc = multiband_entry_check(e, bands, n, split_rows, hop)) return rc;
+    const BandPlan bp = band_plan(bands, n, split_rows, hop, e->cfg.rows);
+    return push_impl(e, e->live, block, sources * fmt->views, count, stride_bytes, n[0], hop, reassign, out_db, out_rgba, rows,
+                     max_columns, out_counts, out_first_columns, 0, 0, fmt, &bp);
 }
 
 // ---- the renderer's own calls: ONE stream, the same machinery on the engine's second session (e->one).  Until round 5
@@ -713,10 +825,13 @@ int emspec_reset_stream(emspec_engine* e, int32_t stream) {
     HIPCHK(e, hipSetDevice(e->device));
     if (int rc = live_pcm_drain(e, lv)) return rc;
     const int R = e->cfg.rows;
-    const size_t cell = e->exact() ? 8 : 4, per = lv.g.ring_bytes(R, cell), perh = lv.g.ring_high_bytes(R, cell), perp = LiveGeometry::pstate_bytes(R);
-    HIPCHK(e, hipMemsetAsync(reinterpret_cast<char*>(lv.d_cells) + stream * per, 0, per, e->stream));
-    if (lv.g.n_high)   // the short band's ring too
-        HIPCHK(e, hipMemsetAsync(reinterpret_cast<char*>(lv.d_cells_high) + stream * perh, 0, perh, e->stream));
+    const size_t cell = e->exact() ? 8 : 4, perp = LiveGeometry::pstate_bytes(R);
+    // every band's ring: a multi-band session's K, a multi-resolution session's two, else the one
+    const int K = lv.mb.bands ? lv.mb.bands : lv.g.n_high ? 2 : 1;
+    for (int k = 0; k < K; ++k) {
+        const size_t per = lv.mb.bands ? lv.mb.ring_bytes(k, cell) : k ? lv.g.ring_high_bytes(R, cell) : lv.g.ring_bytes(R, cell);
+        HIPCHK(e, hipMemsetAsync(reinterpret_cast<char*>(k ? lv.d_cells_band[k - 1] : lv.d_cells) + stream * per, 0, per, e->stream));
+    }
     if (lv.d_pstate) HIPCHK(e, hipMemsetAsync(reinterpret_cast<char*>(lv.d_pstate) + stream * perp, 0, perp, e->stream));
     lv.c.reset_stream(stream);
     return EMSPEC_OK;

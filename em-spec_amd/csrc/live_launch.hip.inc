@@ -26,6 +26,56 @@ hipError_t launch_live_flush(bool exact, const LiveSinks& lv, void* cells, int s
     return hipGetLastError();
 }
 
+// Finalise every band's rows of a column in one launch (a live multi-band session, DESIGN.md §3.13; emspec_live_band_plan.h): grid
+// (columns, S) as above, and workgroup (i, s) runs one live_finalize_column per band - that band's ring, slots, rows, first row and
+// conversion, all in the kernel arguments - so a column of K bands costs one launch, not K.  It serves the session's flush and
+// its deferred finalize; as for live_finalize_kernel, the kernel boundary behind the bands' frame launches on the one stream
+// orders their scatter before these loads.  Bands own disjoint rows of the output column and rings of their own: nothing is
+// shared between the K passes of a workgroup.
+template <class CELL, class CONV>
+struct LiveBandFin {
+    CELL* cells;             // [S][slots][rows]
+    int slots, rows, row0;   // the band fills rows [row0, row0 + rows) of the output column
+    CONV conv;
+};
+template <class CELL, class CONV>
+struct LiveBandsFin {
+    int bands;
+    LiveBandFin<CELL, CONV> b[kMaxBands];
+};
+template <class CELL, class CONV>
+__global__ __launch_bounds__(256) void live_finalize_bands_kernel(LiveSinks lv, LiveBandsFin<CELL, CONV> f, int D) {
+    const int s = (int)blockIdx.y, i = (int)blockIdx.x;
+    const LiveStream d = lv.uniform ? lv.uni : lv.streams[s];
+    if (i >= (d.flush ? d.flush : d.frames)) return;
+#pragma unroll
+    for (int k = 0; k < kMaxBands; ++k) {
+        if (k >= f.bands) break;
+        lv.row0 = f.b[k].row0;
+        live_finalize_column<CELL>(lv, d, s, i, f.b[k].cells, f.b[k].slots, f.b[k].rows, D, 256, f.b[k].conv);
+    }
+}
+
+hipError_t launch_live_finalize_bands(bool exact, const LiveSinks& lv, const LiveBandRings& r, int D, int S, int ncol, hipStream_t st) {
+    if (S <= 0 || ncol <= 0 || r.bands <= 0) return hipSuccess;
+    if (r.bands > kMaxBands) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)ncol, (unsigned)S);
+    if (exact) {
+        LiveBandsFin<unsigned long long, ex::LiveConvExact> f{};
+        f.bands = r.bands;
+        for (int k = 0; k < r.bands; ++k)
+            f.b[k] = {reinterpret_cast<unsigned long long*>(r.cells[k]), r.slots[k], r.rows[k], r.row0[k], ex::LiveConvExact{r.xm[k]}};
+        hipLaunchKernelGGL((live_finalize_bands_kernel<unsigned long long, ex::LiveConvExact>), grid, dim3(256), 0, st, lv, f, D);
+    } else {
+        LiveBandsFin<float, LiveConvF32> f{};
+        f.bands = r.bands;
+        for (int k = 0; k < r.bands; ++k)
+            f.b[k] = {reinterpret_cast<float*>(r.cells[k]), r.slots[k], r.rows[k], r.row0[k], LiveConvF32{r.m[k]}};
+        hipLaunchKernelGGL((live_finalize_bands_kernel<float, LiveConvF32>), grid, dim3(256), 0, st, lv, f, D);
+    }
+    return hipGetLastError();
+}
+
 // Display post-process of a live launch (DESIGN.md §3.6; post.hip.inc's laws, state per stream): the frame kernels wrote the
 // RAW dB columns to raw[S][raw_cols][rows] (device memory, same slots as the outputs, its own stride); this turns each stream's columns, in
 // time order, into the caller's out_db / out_rgba.  The empty columns of the per-frame form pass through unprocessed, as in

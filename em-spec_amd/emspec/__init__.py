@@ -62,7 +62,10 @@ WAVE_SYMBOLS = SYMBOLS[-14:-11]
 MULTIBAND_SYMBOLS = ["emspec_multiband_shifts", "emspec_multiband_columns", "emspec_batch_multiband", "emspec_batch_multiband_device"]
 # the live calls' overlays: likewise (tools/live_rate.py times the parent commit's library next to this build)
 LIVE_OVERLAY_SYMBOLS = ["emspec_set_live_peaks", "emspec_set_live_wave"]
-SYMBOLS = SYMBOLS + MULTIBAND_SYMBOLS + LIVE_OVERLAY_SYMBOLS
+# the multi-band live session's: likewise (tools/live_multiband_rate.py times the parent commit's library next to this build)
+LIVE_MULTIBAND_SYMBOLS = ["emspec_columns_multiband", "emspec_push_columns_multiband", "emspec_push_samples_multiband",
+                          "emspec_push_samples_pcm_multiband"]
+SYMBOLS = SYMBOLS + MULTIBAND_SYMBOLS + LIVE_OVERLAY_SYMBOLS + LIVE_MULTIBAND_SYMBOLS
 
 
 class Config(C.Structure):
@@ -360,6 +363,17 @@ def load(diag=False):
     if all(hasattr(lib, sym) for sym in LIVE_OVERLAY_SYMBOLS):
         lib.emspec_set_live_peaks.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_int64]
         lib.emspec_set_live_wave.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    if all(hasattr(lib, sym) for sym in LIVE_MULTIBAND_SYMBOLS):
+        lib.emspec_columns_multiband.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        lib.emspec_push_columns_multiband.restype = C.c_int64
+        lib.emspec_push_columns_multiband.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
+        lib.emspec_push_samples_multiband.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                                      C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
+                                                      C.c_void_p, C.c_void_p]
+        lib.emspec_push_samples_pcm_multiband.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
+                                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                                          C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
     _libs[diag] = lib
     return lib
 
@@ -663,8 +677,9 @@ class Engine:
         return wire, offsets
 
     def push_samples_pcm(self, block, fmt, n, hop, reassign=True, n_high=0, split_row=0, want_db=True, want_rgba=False, db=None,
-                         rgba=None, count=None, offset=0, max_columns=None):
-        """Live session from raw frames (emspec_push_samples_pcm; n_high != 0: emspec_push_samples_pcm_multires with n = n_low).
+                         rgba=None, count=None, offset=0, max_columns=None, split_rows=None):
+        """Live session from raw frames (emspec_push_samples_pcm; n_high != 0: emspec_push_samples_pcm_multires with n = n_low;
+        n a sequence of sizes and split_rows given: emspec_push_samples_pcm_multiband).
         block [sources][frames x channels] of fmt.dtype; the window of `count` frames from frame `offset` of every row is fed
         -> (db [sources * views][k][rows], rgba, counts, first_columns) as push_samples_multi."""
         block, sources, width = _pcm_rows(block, fmt)
@@ -673,7 +688,12 @@ class Engine:
             count = width - offset
         assert 0 <= offset and offset + count <= width
         S = sources * fmt.views
-        k = self.push_columns_multires(count, n, n_high, hop, reassign) if n_high else self.push_columns_multi(count, n, hop, reassign)
+        bands = not isinstance(n, (int, np.integer))
+        if bands:
+            K, sizes, splits = self._bands(n, split_rows)
+            k = self.push_columns_multiband(count, n, hop, reassign)
+        else:
+            k = self.push_columns_multires(count, n, n_high, hop, reassign) if n_high else self.push_columns_multi(count, n, hop, reassign)
         if k < 0:   # (the call itself names the rule the shape breaks)
             k = 0
         if db is not None:
@@ -684,7 +704,12 @@ class Engine:
         counts, firsts = np.empty(S, np.int64), np.empty(S, np.int64)
         base = C.c_void_p(block.ctypes.data + fb * offset)
         cap = k if max_columns is None else max_columns
-        if n_high:
+        if bands:
+            rc = self._lib.emspec_push_samples_pcm_multiband(self._h, base, C.byref(fmt), sources, count, width * fb, K, sizes,
+                                                             splits, hop, int(bool(reassign)),
+                                                             _np_ptr(db), _np_ptr(rgba), self.rows, cap, _np_ptr(counts),
+                                                             _np_ptr(firsts))
+        elif n_high:
             rc = self._lib.emspec_push_samples_pcm_multires(self._h, base, C.byref(fmt), sources, count, width * fb, n, n_high, hop,
                                                             split_row, int(bool(reassign)), _np_ptr(db), _np_ptr(rgba), self.rows,
                                                             cap, _np_ptr(counts), _np_ptr(firsts))
@@ -1110,6 +1135,61 @@ class Engine:
                                                          int(bool(reassign)), _np_ptr(db), _np_ptr(rgba), self.rows,
                                                          k if max_columns is None else max_columns, _np_ptr(counts),
                                                          _np_ptr(firsts)))
+        return db, rgba, counts, firsts
+
+    # -- the live session's multi-band form: 2..4 fft sizes n[0] > ... > n[K-1], band k above split_rows[k-1], one column per hop -
+    def _bands(self, n, split_rows=()):
+        """(K, the sizes and the split rows as ctypes int32 arrays), kept per ladder: a live call per hop does not rebuild them."""
+        key = (tuple(n), tuple(split_rows))
+        cache = self.__dict__.setdefault("_band_arrays", {})
+        hit = cache.get(key)
+        if hit is None:
+            if len(cache) >= 64:
+                cache.clear()
+            hit = cache[key] = (len(key[0]), _i32(key[0]), _i32(key[1]))
+        return hit
+
+    def columns_multiband(self, frames, n, split_rows, hop, reassign=True, want_db=True, want_rgba=False, db=None, rgba=None):
+        """Per-frame form (emspec_columns_multiband): frames [S][n[0]] -> (db [S][rows] or None, rgba or None, columns
+        int64 [S] (-1 = the empty column)); as `columns`."""
+        frames = frames if isinstance(frames, np.ndarray) and frames.dtype == np.float32 and frames.flags.c_contiguous \
+            else np.ascontiguousarray(frames, np.float32)
+        K, sizes, splits = self._bands(n, split_rows)
+        S = frames.shape[0]
+        db, rgba = self._live_out(S, None, want_db, want_rgba, db, rgba)
+        cols = np.empty(S, np.int64)
+        self._chk(self._lib.emspec_columns_multiband(self._h, _np_ptr(frames), S, K, sizes, splits, hop,
+                                                     int(bool(reassign)), _np_ptr(db), _np_ptr(rgba), self.rows, _np_ptr(cols)))
+        return db, rgba, cols
+
+    def push_columns_multiband(self, count, n, hop, reassign=True):
+        K, sizes, _ = self._bands(n)
+        return int(self._lib.emspec_push_columns_multiband(self._h, count, K, sizes, hop, int(bool(reassign))))
+
+    def push_samples_multiband(self, samples, n, split_rows, hop, reassign=True, want_db=True, want_rgba=False, db=None, rgba=None,
+                               count=None, offset=0, max_columns=None):
+        """Per-sample-block form (emspec_push_samples_multiband): as `push_samples_multires`."""
+        samples = samples if isinstance(samples, np.ndarray) and samples.dtype == np.float32 and samples.flags.c_contiguous \
+            else np.ascontiguousarray(samples, np.float32)
+        K, sizes, splits = self._bands(n, split_rows)
+        S, width = samples.shape
+        if count is None:
+            count = width - offset
+        assert 0 <= offset and offset + count <= width
+        k = self.push_columns_multiband(count, n, hop, reassign)
+        if k < 0:   # (the call itself names the rule the shape breaks)
+            k = 0
+        if db is not None:
+            k = db.shape[1]
+        elif rgba is not None:
+            k = rgba.shape[1]
+        db, rgba = self._live_out(S, k, want_db, want_rgba, db, rgba)
+        counts, firsts = np.empty(S, np.int64), np.empty(S, np.int64)
+        base = C.c_void_p(samples.ctypes.data + 4 * offset)
+        self._chk(self._lib.emspec_push_samples_multiband(self._h, base, S, count, width, K, sizes, splits, hop,
+                                                          int(bool(reassign)), _np_ptr(db), _np_ptr(rgba), self.rows,
+                                                          k if max_columns is None else max_columns, _np_ptr(counts),
+                                                          _np_ptr(firsts)))
         return db, rgba, counts, firsts
 
     def reset_stream(self, stream):

@@ -691,8 +691,22 @@ static bool get_multires_pair(napi_env env, size_t argc, napi_value* argv, size_
     return napi_get_value_int32(env, argv[at], n_high) == napi_ok && napi_get_value_int32(env, argv[at + 1], split) == napi_ok;
 }
 
+/* Optional trailing pair behind that one: fftSizes:Int32Array(K), splitRows:Int32Array(K-1) make the call the multi-band one
+ * (emspec_columns_multiband / emspec_push_samples_multiband / _pcm_multiband); fftSize is then fftSizes[0] and the pair before it
+ * is ignored.  *K = 0: absent.  The library judges the sizes, the split rows and K itself. */
+static bool get_bands(napi_env env, size_t argc, napi_value* argv, size_t at, int32_t* K, int32_t* n, int32_t* split) {
+    *K = 0;
+    if (argc < at + 2) return true;
+    int32_t nsplit = 0;
+    if (!get_int32_list(env, argv[at], n, K) || !get_int32_list(env, argv[at + 1], split, &nsplit)) return false;
+    return *K < 1 || nsplit == *K - 1;
+}
+#define BANDS_OR_THROW(at) \
+    int32_t K, bn[8], bsplit[8]; \
+    if (!get_bands(env, argc, argv, (at), &K, bn, bsplit)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "fftSizes and splitRows must be Int32Arrays of at most 8 values, splitRows one fewer than fftSizes"); return NULL; }
+
 static napi_value Columns(napi_env env, napi_callback_info info) {
-    size_t argc = 11; napi_value argv[11];
+    size_t argc = 13; napi_value argv[13];
     NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     if (argc < 6) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "columns(handle, frames, S, fftSize, hop, reassign[, outDb, outRgba, outColumns])"); return NULL; }
     handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
@@ -711,11 +725,13 @@ static napi_value Columns(napi_env env, napi_callback_info info) {
     if (argc > 8 && !get_f64_out(env, argv[8], (size_t)S, &ocol)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outColumns must be a Float64Array(S)"); return NULL; }
     int32_t n_high, split;
     if (!get_multires_pair(env, argc, argv, 9, &n_high, &split)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "nHigh and splitRow must be integers"); return NULL; }
+    BANDS_OR_THROW(11)
     const size_t cells = (size_t)S * (size_t)h->rows;
     if ((db && dblen != cells) || (rgba && rgbalen != 4 * cells)) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "outDb must hold S*rows floats, outRgba 4*S*rows bytes (rows = the engine's row count)"); return NULL; }
     int64_t* c64 = ocol ? (int64_t*)malloc((size_t)S * sizeof(int64_t)) : NULL;
     if (ocol && !c64) { napi_throw_error(env, "EMSPEC_ERR_OUT_OF_MEMORY", "malloc"); return NULL; }
-    int rc = n_high > 0 ? emspec_columns_multires(h->e, (const float*)fr, S, n, n_high, hop, split, reassign ? 1 : 0, (float*)db, (uint8_t*)rgba, h->rows, c64)
+    int rc = K > 0 ? emspec_columns_multiband(h->e, (const float*)fr, S, K, bn, bsplit, hop, reassign ? 1 : 0, (float*)db, (uint8_t*)rgba, h->rows, c64)
+           : n_high > 0 ? emspec_columns_multires(h->e, (const float*)fr, S, n, n_high, hop, split, reassign ? 1 : 0, (float*)db, (uint8_t*)rgba, h->rows, c64)
                         : emspec_columns(h->e, (const float*)fr, S, n, hop, reassign ? 1 : 0, (float*)db, (uint8_t*)rgba, h->rows, c64);
     if (rc == EMSPEC_OK && ocol) for (int32_t s = 0; s < S; ++s) ocol[s] = (double)c64[s];
     free(c64);
@@ -744,9 +760,9 @@ static napi_value ColumnsFlush(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
-/* pushColumnsMulti(handle, count, fftSize, hop, reassign) -> the largest per-stream column count a block of `count` samples completes */
+/* pushColumnsMulti(handle, count, fftSize, hop, reassign[, nHigh[, fftSizes]]) -> the largest per-stream column count a block of `count` samples completes */
 static napi_value PushColumnsMulti(napi_env env, napi_callback_info info) {
-    size_t argc = 6; napi_value argv[6];
+    size_t argc = 7; napi_value argv[7];
     NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     if (argc < 5) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "pushColumnsMulti(handle, count, fftSize, hop, reassign[, nHigh])"); return NULL; }
     handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
@@ -758,9 +774,13 @@ static napi_value PushColumnsMulti(napi_env env, napi_callback_info info) {
     NAPI_OK_OR_RETURN(env, napi_get_value_bool(env, argv[4], &reassign));
     int32_t n_high = 0;   /* > 0: the multi-resolution session's count (fftSize = n_low) */
     if (argc > 5) NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[5], &n_high));
-    const int64_t k = n_high > 0 ? emspec_push_columns_multires(h->e, count, n, n_high, hop, reassign ? 1 : 0)
+    int32_t K = 0, bn[8];   /* fftSizes:Int32Array: the multi-band session's count */
+    if (argc > 6 && !get_int32_list(env, argv[6], bn, &K)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "fftSizes must be an Int32Array of at most 8 values"); return NULL; }
+    const int64_t k = K > 0 ? emspec_push_columns_multiband(h->e, count, K, bn, hop, reassign ? 1 : 0)
+                    : n_high > 0 ? emspec_push_columns_multires(h->e, count, n, n_high, hop, reassign ? 1 : 0)
                                  : emspec_push_columns_multi(h->e, count, n, hop, reassign ? 1 : 0);
-    if (k < 0) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "invalid count / fftSize / hop"); return NULL; }
+    /* (a multi-band shape that is not accepted: -1, and the push call that follows names the rule it breaks) */
+    if (k < 0 && K == 0) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "invalid count / fftSize / hop"); return NULL; }
     napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int64(env, k, &r));
     return r;
 }
@@ -768,7 +788,7 @@ static napi_value PushColumnsMulti(napi_env env, napi_callback_info info) {
 /* pushMulti(handle, samples:Float32Array(S*count), S, fftSize, hop, reassign, maxColumns, outDb?:Float32Array(S*maxColumns*rows),
  *           outRgba?:Uint8Array(4*S*maxColumns*rows), outCounts?:Float64Array(S), outFirst?:Float64Array(S)) */
 static napi_value PushMulti(napi_env env, napi_callback_info info) {
-    size_t argc = 13; napi_value argv[13];
+    size_t argc = 15; napi_value argv[15];
     NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     if (argc < 7) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "pushMulti(handle, samples, S, fftSize, hop, reassign, maxColumns[, outDb, outRgba, outCounts, outFirst])"); return NULL; }
     handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
@@ -791,11 +811,14 @@ static napi_value PushMulti(napi_env env, napi_callback_info info) {
     if (argc > 10 && !get_f64_out(env, argv[10], (size_t)S, &ofirst)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outFirst must be a Float64Array(S)"); return NULL; }
     int32_t n_high, split;
     if (!get_multires_pair(env, argc, argv, 11, &n_high, &split)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "nHigh and splitRow must be integers"); return NULL; }
+    BANDS_OR_THROW(13)
     const size_t cells = (size_t)S * (size_t)maxc * (size_t)h->rows;
     if ((db && dblen != cells) || (rgba && rgbalen != 4 * cells)) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "outDb must hold S*maxColumns*rows floats, outRgba 4x that in bytes"); return NULL; }
     int64_t* tmp = (int64_t*)malloc((size_t)S * 2 * sizeof(int64_t));
     if (!tmp) { napi_throw_error(env, "EMSPEC_ERR_OUT_OF_MEMORY", "malloc"); return NULL; }
-    int rc = n_high > 0 ? emspec_push_samples_multires(h->e, (const float*)smp, S, count, count, n, n_high, hop, split, reassign ? 1 : 0,
+    int rc = K > 0 ? emspec_push_samples_multiband(h->e, (const float*)smp, S, count, count, K, bn, bsplit, hop, reassign ? 1 : 0,
+                                                   (float*)db, (uint8_t*)rgba, h->rows, maxc, tmp, tmp + S)
+           : n_high > 0 ? emspec_push_samples_multires(h->e, (const float*)smp, S, count, count, n, n_high, hop, split, reassign ? 1 : 0,
                                                        (float*)db, (uint8_t*)rgba, h->rows, maxc, tmp, tmp + S)
                         : emspec_push_samples_multi(h->e, (const float*)smp, S, count, count, n, hop, reassign ? 1 : 0, (float*)db,
                                                     (uint8_t*)rgba, h->rows, maxc, tmp, tmp + S);
@@ -943,10 +966,11 @@ static napi_value BatchPcmPacked(napi_env env, napi_callback_info info) {
 }
 
 /* pushPcm(handle, block, sampleType, channels, views, mix, sources, fftSize, hop, reassign, maxColumns, outDb?, outRgba?,
- *         outCounts?:Float64Array(sources*views), outFirst?[, nHigh, splitRow]): emspec_push_samples_pcm / _pcm_multires; block holds
+ *         outCounts?:Float64Array(sources*views), outFirst?[, nHigh, splitRow[, fftSizes, splitRows]]): emspec_push_samples_pcm /
+ *         _pcm_multires / _pcm_multiband; block holds
  *         `count` frames of every source, source after source. */
 static napi_value PushPcm(napi_env env, napi_callback_info info) {
-    size_t argc = 17; napi_value argv[17];
+    size_t argc = 19; napi_value argv[19];
     NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     if (argc < 11) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "pushPcm(handle, block, sampleType, channels, views, mix, sources, fftSize, hop, reassign, maxColumns[, outDb, outRgba, outCounts, outFirst, nHigh, splitRow])"); return NULL; }
     handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
@@ -970,12 +994,15 @@ static napi_value PushPcm(napi_env env, napi_callback_info info) {
     if (argc > 14 && !get_f64_out(env, argv[14], S, &ofirst)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outFirst must be a Float64Array(sources * views)"); return NULL; }
     int32_t n_high, split;
     if (!get_multires_pair(env, argc, argv, 15, &n_high, &split)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "nHigh and splitRow must be integers"); return NULL; }
+    BANDS_OR_THROW(17)
     const size_t cells = S * (size_t)maxc * (size_t)h->rows;
     if (fb > 0 && ((db && dblen != cells) || (rgba && rgbalen != 4 * cells))) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "outDb must hold sources*views*maxColumns*rows floats, outRgba 4x that in bytes"); return NULL; }
     int64_t* tmp = (int64_t*)malloc(S * 2 * sizeof(int64_t));
     if (!tmp) { napi_throw_error(env, "EMSPEC_ERR_OUT_OF_MEMORY", "malloc"); return NULL; }
     const int64_t stride = count * (fb > 0 ? fb : 0);
-    int rc = n_high > 0 ? emspec_push_samples_pcm_multires(h->e, blk, &fmt, sources, count, stride, n, n_high, hop, split, reassign ? 1 : 0,
+    int rc = K > 0 ? emspec_push_samples_pcm_multiband(h->e, blk, &fmt, sources, count, stride, K, bn, bsplit, hop, reassign ? 1 : 0,
+                                                       (float*)db, (uint8_t*)rgba, h->rows, maxc, tmp, tmp + S)
+           : n_high > 0 ? emspec_push_samples_pcm_multires(h->e, blk, &fmt, sources, count, stride, n, n_high, hop, split, reassign ? 1 : 0,
                                                            (float*)db, (uint8_t*)rgba, h->rows, maxc, tmp, tmp + S)
                         : emspec_push_samples_pcm(h->e, blk, &fmt, sources, count, stride, n, hop, reassign ? 1 : 0, (float*)db,
                                                   (uint8_t*)rgba, h->rows, maxc, tmp, tmp + S);

@@ -169,6 +169,66 @@ class Engine {
   }
 
   /**
+   * The live calls' multi-band form (emspec_columns_multiband / emspec_push_samples_multiband, DESIGN.md §3.13): the image of
+   * computeColumnsMultiband column by column, one column per hop at the latency of fftSizes[0].  opts as computeColumnsMultiband
+   * takes them ({fftSizes, hop, splitHz | splitRows, reassign = true}) plus wantRgba.  frames: Float32Array(S * fftSizes[0]).
+   * Results, flushColumns() and resetStream() as for computeSpectrogramColumns; a session is one kind until reset().
+   */
+  computeSpectrogramColumnsMultiband(frames, opts) {
+    const m = this._multibandOpts(opts);
+    this._liveBlocks(m.sizes[0], m.wantRgba);
+    native.columns(this._h, frames, this.streams, m.sizes[0], opts.hop, m.reassign, this.columnsDb,
+      m.wantRgba ? this.columnsRgba : undefined, this.columnIndex, 0, 0, m.sizes, m.splits);
+    return this.columnsDb;
+  }
+
+  /** pushSamplesMulti for a multi-band session: same return value, opts as in computeSpectrogramColumnsMultiband. */
+  pushSamplesMultiband(samples, opts) {
+    const m = this._multibandOpts(opts);
+    const S = this.streams, count = samples.length / S;
+    const o = this._pushBlocks(native.pushColumnsMulti(this._h, count, m.sizes[0], opts.hop, m.reassign, 0, m.sizes), m.wantRgba);
+    native.pushMulti(this._h, samples, S, m.sizes[0], opts.hop, m.reassign, o.maxColumns, o.dbAll,
+      m.wantRgba ? o.rgbaAll : undefined, o.counts, o.first, 0, 0, m.sizes, m.splits);
+    return { maxColumns: o.maxColumns, counts: o.counts, first: o.first, db: o.dbAll, rgba: m.wantRgba ? o.rgbaAll : undefined };
+  }
+
+  /** pushSamplesPcm for a multi-band session (emspec_push_samples_pcm_multiband): block and format as there, opts as above. */
+  pushSamplesPcmMultiband(block, format, opts) {
+    const m = this._multibandOpts(opts);
+    const S = this.streams, sources = S / format.views;
+    const count = block.byteLength / (sources * format.frameBytes);
+    const o = this._pushBlocks(native.pushColumnsMulti(this._h, count, m.sizes[0], opts.hop, m.reassign, 0, m.sizes), m.wantRgba);
+    native.pushPcm(this._h, block, format.sampleType, format.channels, format.views, format.mix, sources, m.sizes[0], opts.hop,
+      m.reassign, o.maxColumns, o.dbAll, m.wantRgba ? o.rgbaAll : undefined, o.counts, o.first, 0, 0, m.sizes, m.splits);
+    return { maxColumns: o.maxColumns, counts: o.counts, first: o.first, db: o.dbAll, rgba: m.wantRgba ? o.rgbaAll : undefined };
+  }
+
+  /** the push calls' engine-owned page-locked blocks, grown to hold maxColumns columns per stream */
+  _pushBlocks(maxColumns, wantRgba) {
+    const S = this.streams;
+    let o = this._push;
+    if (!o || o.maxColumns < maxColumns || (wantRgba && !o.rgbaAll)) {
+      const cap = Math.max(maxColumns, 1);
+      o = this._push = { maxColumns: cap, dbAll: new Float32Array(native.allocPinned(4 * S * cap * this.rows)),
+        rgbaAll: wantRgba ? new Uint8Array(native.allocPinned(4 * S * cap * this.rows)) : undefined,
+        counts: new Float64Array(S), first: new Float64Array(S) };
+    }
+    return o;
+  }
+
+  /** (the split rows of opts.splitHz are looked up once per list of frequencies, not per call) */
+  _multibandOpts(opts) {
+    let splits = opts.splitRows;
+    if (splits === undefined) {
+      const key = Array.from(opts.splitHz).join();
+      if (this._mbHz !== key) { this._mbSplits = Array.from(opts.splitHz, (hz) => this.splitRowForHz(hz)); this._mbHz = key; }
+      splits = this._mbSplits;
+    }
+    return { sizes: Int32Array.from(opts.fftSizes), splits: Int32Array.from(splits),
+      reassign: opts.reassign === undefined ? true : !!opts.reassign, wantRgba: !!opts.wantRgba };
+  }
+
+  /**
    * Live session from raw interleaved frames (emspec_push_samples_pcm / _pcm_multires): the capture buffer in, the columns of
    * sources * format.views streams out (stream = source * views + view; sources = engine.streams / format.views).
    * block: `count` frames of every source, source after source, in the typed array of format.type (Int16Array, Int32Array,

@@ -567,8 +567,8 @@ int emspec_batch_multires_device(emspec_engine* e, const float* pcm_dev, int32_t
  *   pipeline over units of whole streams.  Both honour emspec_set_time_reduce and emspec_set_display; the host entry honours
  *   emspec_set_wave_out with the envelope on the n[0] column grid.  The bands' raw dB share the two-band batch's engine workspace.
  * Single-resolution and two-band results on the same engine are not affected by a multi-band call.
- * Not offered: a live multi-band session (the live session stays two-band); a multi-band form of emspec_batch_gather, of the
- * packed entries and of the PCM entries; more than four bands; per-band hops.
+ * Not offered: a multi-band form of emspec_batch_gather, of the packed entries and of the batch PCM entries; more than four
+ * bands; per-band hops.  (The live form: emspec_columns_multiband and emspec_push_samples_multiband, below.)
  */
 int emspec_multiband_shifts(int32_t bands, const int32_t* n, int32_t hop, int32_t* shifts_out /* [bands], may be NULL */);
 int64_t emspec_multiband_columns(int64_t L, int32_t bands, const int32_t* n, int32_t hop);
@@ -606,6 +606,43 @@ int emspec_push_samples_multires(emspec_engine* e, const float* samples, int32_t
                                  int32_t n_low, int32_t n_high, int32_t hop, int32_t split_row, int32_t reassign,
                                  float* out_db, uint8_t* out_rgba, int32_t rows, int64_t max_columns, int64_t* out_counts,
                                  int64_t* out_first_columns);
+
+/*
+ * Multi-band LIVE session: the multi-band image, column by column while the audio arrives - what the
+ * multi-resolution live session is to emspec_batch_multires, for K = `bands` in 2..4.  These calls open the engine's live
+ * multi-stream session as a multi-band session.  For a stream that was fed samples [0, L) and then flushed, the
+ * emspec_multiband_columns(L, ...) emitted columns are those of emspec_batch_multiband on the same samples, engine and row table
+ * (EXACT mode: bit for bit, dB and RGBA; FAST mode: sums in arrival order).  Latency: emspec_latency_columns(n[0], hop, reassign).
+ * Only n[0]'s frame count drives a call: band k runs 2 shift[k] frames ahead on the same samples (a stream's first frame runs its
+ * frames 0 .. 2 shift[k]) and keeps a column ring of its own, indexed by the emitted column.
+ * Per call: one frame launch per band - the first moves the new samples into the device ring, the others are not launched when no
+ * stream has a frame.  When no band's finalize is deferred, each band's last workgroup of a stream writes its own rows of the
+ * output column in place; when any band's would be (a call that completes more than two columns per stream, or a band with
+ * n < 2048), every frame launch only scatters and ONE further kernel finalises all bands' rows: at most K + 1 launches.  A flush
+ * is one launch.  With emspec_set_display on, the post-process runs once over the composed raw column; the overlays
+ * (emspec_set_live_peaks, emspec_set_live_wave) run once, the envelope on the n[0] grid.  One host synchronisation ends the call.
+ * emspec_columns_multiband: as emspec_columns, frames [streams][n[0]].
+ * emspec_push_samples_multiband: as emspec_push_samples_multi; max_columns must hold what the block completes
+ *   (emspec_push_columns_multiband) even when both outputs are NULL - EMSPEC_ERR_INVALID_ARG otherwise, nothing fed.
+ * emspec_push_columns_multiband: as emspec_push_columns_multi (-1 for a shape that is not accepted).
+ * emspec_push_samples_pcm_multiband: the session fed raw interleaved frames, as emspec_push_samples_pcm_multires (PCM front end,
+ *   below).
+ * emspec_columns_flush, emspec_reset_stream, emspec_reset, emspec_live_streams, emspec_set_live_peaks, emspec_set_live_wave and
+ * emspec_set_display act on the session as on a two-band one.  Shapes, split rows and their messages: those of
+ * emspec_batch_multiband (EMSPEC_ERR_INVALID_ARG before anything is fed; the engine stays usable).  K = 2 is accepted with the
+ * band rule's sizes; its columns are those of the two-band live session.  EMSPEC_ERR_STATE until emspec_reset(): a
+ * single-resolution or two-band live call on a multi-band session or the reverse; a change of streams, bands, any size, any split
+ * row, hop, reassign or feeding form mid-session; feeding a flushed stream; any of these calls while a time reduction is set.
+ */
+int emspec_columns_multiband(emspec_engine* e, const float* frames /* [streams][n[0]] */, int32_t streams, int32_t bands,
+                             const int32_t* n, const int32_t* split_rows /* [bands-1] */, int32_t hop, int32_t reassign,
+                             float* out_db, uint8_t* out_rgba, int32_t rows, int64_t* out_columns);
+int64_t emspec_push_columns_multiband(const emspec_engine* e, int64_t count, int32_t bands, const int32_t* n, int32_t hop,
+                                      int32_t reassign);
+int emspec_push_samples_multiband(emspec_engine* e, const float* samples, int32_t streams, int64_t count, int64_t stride,
+                                  int32_t bands, const int32_t* n, const int32_t* split_rows, int32_t hop, int32_t reassign,
+                                  float* out_db, uint8_t* out_rgba, int32_t rows, int64_t max_columns, int64_t* out_counts,
+                                  int64_t* out_first_columns);
 
 /*
  * ---- PCM front end: the buffer an audio source really delivers - interleaved channels of int16,
@@ -681,6 +718,7 @@ int emspec_batch_pcm_packed(emspec_engine* e, const void* src, const emspec_pcm_
  * of format, sources or shape mid-session, feeding a flushed stream.  "The same format" means the same sample type, channels,
  * views and the same BITS of the views * channels weights (-0.0 is not 0.0: the sign of a zero result can differ).
  * sources * views, the session's streams, must be in 1..65535 as for every live session (EMSPEC_ERR_INVALID_ARG).
+ * emspec_push_samples_pcm_multiband: the same for the multi-band live session (emspec_push_samples_multiband).
  */
 int emspec_push_samples_pcm(emspec_engine* e, const void* block, const emspec_pcm_format* fmt, int32_t sources, int64_t count,
                             int64_t stride_bytes, int32_t n, int32_t hop, int32_t reassign, float* out_db, uint8_t* out_rgba,
@@ -689,6 +727,10 @@ int emspec_push_samples_pcm_multires(emspec_engine* e, const void* block, const 
                                      int64_t count, int64_t stride_bytes, int32_t n_low, int32_t n_high, int32_t hop,
                                      int32_t split_row, int32_t reassign, float* out_db, uint8_t* out_rgba, int32_t rows,
                                      int64_t max_columns, int64_t* out_counts, int64_t* out_first_columns);
+int emspec_push_samples_pcm_multiband(emspec_engine* e, const void* block, const emspec_pcm_format* fmt, int32_t sources,
+                                      int64_t count, int64_t stride_bytes, int32_t bands, const int32_t* n,
+                                      const int32_t* split_rows, int32_t hop, int32_t reassign, float* out_db, uint8_t* out_rgba,
+                                      int32_t rows, int64_t max_columns, int64_t* out_counts, int64_t* out_first_columns);
 
 /*
  * ---- Spectral peaks: the k loudest local maxima of every finished column, computed where the dB
