@@ -346,6 +346,23 @@ int main() {
     chunk_case(200 * GiB, 0, 700 * MiB, 1024, 4 * GiB, 7, -1);  // chunk 5 of 7 streams
     chunk_case(4 * (4 * GiB), 0, per, 0, 4 * GiB, 16, -1);
     for (long long mb : {0, 1, 64, 3000, 100000}) chunk_case(200 * GiB, 0, 20 * MiB, 256, 8 * GiB, 64, mb);
+
+    // ---- row counts that are no power of two: the cases of tests/row_grid_cases.py (appended, so that every earlier record keeps
+    // its line).  17, 25, 129, 250 and 255 quads; the records-only rows above the ring gate; every column kernel of either mode ----
+    const int sweep[5] = {68, 100, 516, 1000, 1020};
+    const int fast_shapes[12][2] = {{4096, 256}, {4096, 512}, {4096, 1024}, {4096, 300}, {2048, 128}, {1024, 256}, {1024, 100},
+                                    {8192, 512}, {8192, 1024}, {16384, 512}, {8192, 256}, {512, 64}};
+    for (const auto& s : fast_shapes) {
+        for (int rows : sweep) fast_case(s[0], s[1], rows, 1, 0);
+        fast_case(s[0], s[1], 1000, 0, 0);
+    }
+    for (int rows : {2052, 4092}) { fast_case(4096, 256, rows, 1, 0); fast_case(16384, 512, rows, 1, 0); }
+    const int exact_shapes[6][2] = {{4096, 256}, {4096, 300}, {2048, 128}, {1024, 256}, {8192, 512}, {16384, 512}};
+    for (const auto& s : exact_shapes)
+        for (int rows : sweep) exact_case(s[0], s[1], 1, rows, 0, rows, 0, 0, 0);
+    for (int rows : sweep) exact_case(4096, 256, 1, rows, 0, rows, 2, 0, 0);
+    for (int rows : {2052, 4092}) exact_case(4096, 256, 1, rows, 0, rows, 0, 0, 0);
+    for (int rows : {68, 1020}) exact_case(4096, 256, 1, rows, 0, rows, 2, 1, 0);   // the parked kernel where the switch asks for it
     printf("\n]\n");
     return 0;
 }

@@ -54,3 +54,29 @@ def test_fuzz_slice_live_multi_stream():
     size, 1..8 streams, sub-hop and over-long blocks, page-locked or pageable buffers, one stream restarted mid-session) against
     the oracle's batch columns: EXACT bytes, float32 within 8.7e-4 dB."""
     _run("fuzz_live.py", 60, 508)
+
+
+# ---- the same four tools with the row count drawn from every multiple of 4 (EMSPEC_FUZZ_ROWS=any): 4 * integers(16, 257), and on the
+# tools that visit the records paths one case in eight up to 4096.  New seeds; the slices above keep theirs and their cases.
+ANY_ROWS = {"EMSPEC_FUZZ_ROWS": "any"}
+
+
+@pytest.mark.timeout(900)
+def test_fuzz_slice_float32_shapes_any_rows():
+    _run("fuzz_parity.py", 60, 611, ANY_ROWS)
+
+
+@pytest.mark.timeout(900)
+def test_fuzz_slice_fused_long_walks_any_rows():
+    _run("fuzz_long.py", 15, 612, ANY_ROWS)
+
+
+@pytest.mark.timeout(900)
+def test_fuzz_slice_exact_mode_any_rows():
+    out = _run("fuzz_exact.py", 60, 613, {"EMSPEC_FUZZ_DIAG": "1", **ANY_ROWS})
+    assert "vs the independent float64 method: 0 mismatches" in out, out[-1500:]
+
+
+@pytest.mark.timeout(900)
+def test_fuzz_slice_live_multi_stream_any_rows():
+    _run("fuzz_live.py", 20, 614, ANY_ROWS)

@@ -82,20 +82,22 @@ def test_kernel_plans_match_the_recorded_answers(tmp_path):
         by_hop = {w["case"]["hop"]: w for w in plain if w["case"]["n"] == n and w["case"]["rows"] == 1024 and w["case"]["reassign"]}
         assert any(by_hop[h]["route"] == "records_f32" and by_hop[h]["small_lds"] > LDS and h + 1 in by_hop and
                    by_hop[h + 1]["route"] == "fused_small" and by_hop[h + 1]["lds"] <= LDS for h in by_hop), n
-        # ... and its rows threshold, four rows apart
-        for hop in {w["case"]["hop"] for w in plain if w["case"]["n"] == n} - {1, 256, 512, 1024, n}:
-            by_rows = {w["case"]["rows"]: w for w in plain if w["case"]["n"] == n and w["case"]["hop"] == hop and w["case"]["reassign"]}
-            if len(by_rows) > 2:
-                assert any(by_rows[r]["route"] == "fused_small" and r + 4 in by_rows and by_rows[r + 4]["route"] == "records_f32" and
-                           r + 4 <= 1024 for r in by_rows), (n, hop)
+        # ... and its rows threshold, four rows apart, at the hop whose rows are swept for it (the sweep of tests/row_grid_cases.py
+        # visits other hops at rows on one side only)
+        hop = {4096: 200, 2048: 60, 1024: 40}[n]
+        by_rows = {w["case"]["rows"]: w for w in plain if w["case"]["n"] == n and w["case"]["hop"] == hop and w["case"]["reassign"]}
+        assert len(by_rows) > 2
+        assert any(by_rows[r]["route"] == "fused_small" and r + 4 in by_rows and by_rows[r + 4]["route"] == "records_f32" and
+                   r + 4 <= 1024 for r in by_rows), (n, hop)
     big = {(w["case"]["hop"], w["case"]["rows"]): w["route"] for w in plain if w["case"]["n"] == 16384 and w["case"]["reassign"]}
     assert big[511, 1024] == "records_f32" and big[512, 1024] == "fused_16384" and big[256, 516] == "fused_16384" and big[256, 520] == "records_f32"
     assert any(w["case"]["reassign"] == 0 and w["route"] == "fused_small" and w["case"]["hop"] == 1 for w in plain)
-    # the rows gate: 1024 served, 1028 and 4096 not, 62 and 66 not
+    # the rows gate: 64, 1024 and the multiples of 4 between them served, 1028 and 4096 not, 62 and 66 not
     for w in plain:
         c = w["case"]
         if c["hop"] == 512 and c["reassign"] and c["n"] >= 1024:
-            assert (w["route"] != "records_f32") == (c["rows"] in (64, 1024)), c
+            assert (w["route"] != "records_f32") == (c["rows"] % 4 == 0 and 64 <= c["rows"] <= 1024), c
+    assert {64, 68, 1020, 1024, 1028, 4096, 62, 66} <= {w["case"]["rows"] for w in plain if w["case"]["hop"] == 512 and w["case"]["n"] == 4096}
     # the reach check of the kernels built for one hop
     reach = {(w["case"]["n"], w["case"]["hop"], w["case"]["D"]): w["refused"] for w in kinds["fast_reach"]}
     assert reach[4096, 256, 8] == 0 and reach[4096, 256, 9] == 1 and reach[8192, 512, 8] == 0 and reach[8192, 512, 9] == 1

@@ -2,7 +2,8 @@
 """Randomised parity stress of the EXACT mode: random shapes / configs / signals through the C ABI against the binary64
 bit model (oracle/emspec_exact.c) - every comparison is array_equal (dump power / column / row / q, dB bits, palette
 index), plus the streaming call against the batch bytes and (column,row) against the independent float64 method.
-usage: python tools/fuzz_exact.py [cases] [seed]     (needs an MI355X; prints one line per failure)"""
+usage: python tools/fuzz_exact.py [cases] [seed]     (needs an MI355X; prints one line per failure)
+EMSPEC_FUZZ_ROWS=any in the environment draws the row count from every multiple of 4 (the default draw keeps its cases)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "em-spec_amd"), os.path.join(ROOT, "oracle")]
@@ -13,6 +14,7 @@ from emspec import synth
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 rng = np.random.default_rng(seed)
+ANY_ROWS = os.environ.get("EMSPEC_FUZZ_ROWS") == "any"   # rows: any multiple of 4 instead of the list below (the default draw is untouched)
 fails = 0
 f64_bins = f64_bad = 0
 t0 = time.time()
@@ -20,6 +22,8 @@ for ci in range(cases):
     n = int(rng.choice([256, 512, 1024, 2048, 4096, 4096, 4096, 8192, 16384]))
     hop = int(rng.choice([n // 16, n // 16, n // 8, n // 4, n // 2, n, max(1, n // 32), int(rng.integers(1, n + 1))]))
     rows = int(rng.choice([64, 68, 100, 128, 256, 512, 1000, 1024, 1024, 2048, 4096]))
+    if ANY_ROWS:   # 64 .. 1024, what the one-kernel paths take; one case in eight above their gate, on the records path
+        rows = 4 * int(rng.integers(16, 257)) if rng.integers(0, 8) else 4 * int(rng.integers(257, 1025))
     reassign = bool(rng.integers(0, 2))
     S = int(rng.integers(1, 4))
     D = -(-n // (2 * hop)) if reassign else 0

@@ -4,7 +4,8 @@ emspec_columns_flush / emspec_reset_stream) through the C ABI against the oracle
 shape, rows, stream count, feeding form, block sizes (sub-hop blocks, blocks longer than the staging block), page-locked or
 pageable buffers, and a mid-session restart of one stream.  EXACT mode: dB bits and RGBA array_equal; float32 mode: dB within
 8.7e-4, RGBA differing on < 1e-3 of the cells.
-usage: python tools/fuzz_live.py [cases] [seed]     (needs an MI355X; prints one line per failure)"""
+usage: python tools/fuzz_live.py [cases] [seed]     (needs an MI355X; prints one line per failure)
+EMSPEC_FUZZ_ROWS=any in the environment draws the row count from every multiple of 4 (the default draw keeps its cases)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "em-spec_amd"), os.path.join(ROOT, "oracle")]
@@ -15,6 +16,7 @@ from emspec import synth
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 rng = np.random.default_rng(seed)
+ANY_ROWS = os.environ.get("EMSPEC_FUZZ_ROWS") == "any"   # rows: any multiple of 4 instead of the list below (the default draw is untouched)
 fails = 0
 t0 = time.time()
 
@@ -38,6 +40,8 @@ for ci in range(cases):
     n = int(rng.choice([256, 512, 1024, 2048, 4096, 4096, 8192, 16384]))
     hop = int(rng.choice([n // 16, n // 8, n // 4, n // 2, n, int(rng.integers(max(1, n // 32), n + 1))]))
     rows = int(rng.choice([64, 128, 256, 512, 1000, 1024, 1024, 2048]))
+    if ANY_ROWS:   # 64 .. 1024; one case in eight above it
+        rows = 4 * int(rng.integers(16, 257)) if rng.integers(0, 8) else 4 * int(rng.integers(257, 1025))
     reassign = bool(rng.integers(0, 4))
     S = int(rng.integers(1, 9)) if n < 16384 else int(rng.integers(1, 4))
     D = -(-n // (2 * hop)) if reassign else 0

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Long-run parity stress of the fused (LDS ring) kernels: many segments per stream, random segment
 lengths (EMSPEC_SEGLEN), random rows / gain / floor, hundreds to thousands of frames, every fused shape.
-usage: python tools/fuzz_long.py [cases] [seed]     (needs an MI355X; prints one line per failure)"""
+usage: python tools/fuzz_long.py [cases] [seed]     (needs an MI355X; prints one line per failure)
+EMSPEC_FUZZ_ROWS=any in the environment draws the row count from every multiple of 4 (the default draw keeps its cases)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "em-spec_amd"), os.path.join(ROOT, "oracle")]
@@ -12,6 +13,7 @@ from emspec import synth
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 rng = np.random.default_rng(seed)
+ANY_ROWS = os.environ.get("EMSPEC_FUZZ_ROWS") == "any"   # rows: any multiple of 4 instead of the list below (the default draw is untouched)
 SHAPES = [(4096, 256), (4096, 512), (4096, 1024), (4096, 300), (4096, 2048), (8192, 512), (8192, 1024),
           (2048, 128), (2048, 256), (2048, 200), (2048, 1000), (1024, 128), (1024, 256), (1024, 100), (1024, 700),
           (16384, 512), (16384, 512), (16384, 1024), (16384, 700), (16384, 4096)]
@@ -20,6 +22,8 @@ for ci in range(cases):
     n, hop = SHAPES[int(rng.integers(0, len(SHAPES)))]
     reassign = bool(rng.integers(0, 4))            # mostly on
     rows = int(rng.choice([64, 256, 512, 1024, 1024]))
+    if ANY_ROWS:   # (64 .. 1024: every shape of the list stays on its fused kernel)
+        rows = 4 * int(rng.integers(16, 257))
     S = int(rng.integers(1, 4))
     frames = int(rng.integers(200, 2500))
     if n == 16384:
