@@ -70,6 +70,13 @@ struct LiveState {
     void* d_wring = nullptr; size_t wring_bytes = 0;
     void* h_opeaks = nullptr; size_t opeaks_bytes = 0;
     void* h_owave = nullptr; size_t owave_bytes = 0;
+    // live history (emspec_set_live_history; live_history.hip.inc, emspec_history_plan.h), allocated by the first call of the
+    // session while a history is set: the ring [S][W][rows] float32 and, for the view kernel, the columns each stream has
+    // emitted [S] (written by the store kernel; the host's own count is c.emitted).  view_done: recorded behind a device view
+    // on the caller's stream, waited for by the engine's stream, so that later launches do not overwrite what a view still reads
+    float* d_hring = nullptr; size_t hring_bytes = 0;
+    long long* d_hends = nullptr; size_t hends_bytes = 0;
+    hipEvent_t view_done = nullptr;
     LiveStream* desc() const { return reinterpret_cast<LiveStream*>(h_desc); }
 };
 
@@ -148,6 +155,12 @@ int multires_check(emspec_engine* e, int32_t S, int32_t n_low, int32_t n_high, i
 void live_destroy(emspec_engine* e);   // emspec_live.cpp: called by emspec_destroy
 void live_reset(emspec_engine* e);     // drops the live session's stream state (emspec_reset); buffers are kept
 bool live_pending(const emspec_engine* e);   // some stream of either session has fed frames whose columns were not emitted yet
+// emspec_history.cpp: the live history's buffers.  history_ready: the session's ring while a history is set (nothing otherwise) -
+// called by every streaming call once the session's streams are known and before anything is fed; history_free: one session's
+// ring; history_destroy: everything (called by live_destroy)
+int history_ready(emspec_engine* e, LiveState& lv);
+void history_free(LiveState& lv);
+void history_destroy(emspec_engine* e);
 }  // namespace emspec
 
 struct emspec_engine {
@@ -196,6 +209,10 @@ struct emspec_engine {
     // arrays (null: off) and their capacities in pairs
     emspec_peak* live_peaks = nullptr; int64_t live_peaks_capacity = 0; int live_peaks_k = 0; float live_peaks_min_db = 0.0f;
     emspec_wave* live_wave = nullptr; int64_t live_wave_capacity = 0;
+    // live history (emspec_set_live_history; emspec_history.cpp): W columns per stream of both sessions below (0: off), and the
+    // page-locked staging blocks of a host view's pageable outputs (dB, index, RGBA)
+    int64_t history_W = 0;
+    void* h_view[3] = {}; size_t view_bytes[3] = {};
     // streaming (emspec_live.cpp): the live multi-stream session, and the single-stream calls' own (emspec_column,
     // emspec_push_samples: the same machinery with one stream); independent of each other
     emspec::LiveState live, one;

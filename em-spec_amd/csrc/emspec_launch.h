@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "emspec_band_plan.h"
 #include "emspec_device.h"
+#include "emspec_history_plan.h"
 #include "emspec_live_plan.h"
 #include "emspec_wire_plan.h"
 
@@ -178,6 +179,35 @@ struct LiveOverlay {
     int D = 0;   // latency of the emitted column
 };
 hipError_t launch_live_overlay(const LiveSinks& lv, const LiveOverlay& ov, int S, int units, hipStream_t st);
+// The live history (live_history.hip.inc; emspec_set_live_history; geometry: emspec_history_plan.h).  The store: one kernel
+// behind the launch's last kernel, on the same descriptors, lv.out_db / lv.out_cols / units as for the overlay.
+struct LiveHistory {
+    const float* db = nullptr;   // the delivered dB on the device, [S][lv.out_cols][rows] (as LiveOverlay::db)
+    float* ring = nullptr;       // [S][W][rows]: column c of stream s in slot c mod W
+    long long* ends = nullptr;   // [S]: columns emitted so far, kept for the view kernel
+    int W = 0, rows = 0;
+    int D = 0;                   // latency of the emitted column
+    int fill_out = 0;            // != 0: this kernel writes lv.out_db (no overlay kernel does)
+};
+hipError_t launch_live_history_store(const LiveSinks& lv, const LiveHistory& h, int S, int units, hipStream_t st);
+// The view: groups g in [0, groups) of f columns from column `first` on, of streams [stream0, stream0 + streams) ->
+// [streams][groups][rows] dB, palette index of (dB + shift) under `map` (its scale is not read), RGBA = lut[index]; any null.
+struct HistoryView {
+    const float* ring = nullptr;
+    const long long* ends = nullptr;
+    int W = 0, rows = 0, stream0 = 0;
+    long long first = 0;
+    int slot_first = 0;          // first mod W
+    int f = 1, groups = 0;
+    DbMap map{};
+    float shift = 0.0f;
+    const uint32_t* lut = nullptr;
+    float* db = nullptr;
+    uint8_t* index = nullptr;
+    uint32_t* rgba = nullptr;
+};
+int history_view_split(int streams, int64_t groups, int rows, int f);   // waves a group's columns are cut over (1: no split)
+hipError_t launch_history_view(const HistoryView& v, int streams, hipStream_t st);
 // the gather's wire image (pack.hip.inc; its sizes and the pack workspace `scratch` of wire_scratch_bytes: emspec_wire_plan.h).
 // wire_total_ptr: where in the workspace the pack leaves the image's size
 uint64_t* wire_total_ptr(void* scratch, int64_t columns);

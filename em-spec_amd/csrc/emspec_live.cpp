@@ -137,6 +137,8 @@ int live_post_buffers(emspec_engine* e, LiveState& lv) {
 // dst_peaks / dst_wave: the overlays' device-visible destinations ([S][out_cols][k] and [S][out_cols] pairs; null: off) - the
 // overlay kernel goes behind the launch's last kernel.  While peaks are wanted the delivered dB goes to a device block laid out
 // like the destination (d_raw, or d_pdb behind the post kernel) and the overlay kernel writes dst_db from its copy of it.
+// While a history is set (emspec_set_live_history) the delivered dB takes the same way, and the store kernel (live_history.hip.inc)
+// goes behind the launch too: it copies every delivered column into the session's ring and, without peaks, writes dst_db.
 int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fresh_stride, int mlaunch, bool flush, float* dst_db,
                 uint8_t* dst_rgba, int out_cols, int raw_cols, bool empty_col, emspec_peak* dst_peaks = nullptr,
                 emspec_wave* dst_wave = nullptr) {
@@ -147,7 +149,9 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
     if (post && (rc = live_post_buffers(e, lv))) return rc;
     // (a launch without a frame - one that only moves samples into the ring - completes no column: no overlay)
     const bool overlay = (dst_peaks || dst_wave) && (flush || mlaunch > 0), peaks = overlay && dst_peaks;
-    if (peaks) {
+    const bool hist = e->history_W > 0 && (flush || mlaunch > 0);
+    const bool devdb = peaks || hist;   // the delivered dB goes to a device block first
+    if (devdb) {
         const size_t want = g.out_bytes(R, std::max(out_cols, 1));
         if (post ? (rc = grow(e, (void**)&lv.d_pdb, &lv.pdb_bytes, want)) : (rc = grow(e, (void**)&lv.d_raw, &lv.raw_bytes, want))) return rc;
     }
@@ -174,13 +178,13 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
     // (a call without outputs - a priming block - may complete more columns than its max_columns: out_cols bounds the raw
     // block's stride only where it is an output's stride)
     if (post) {
-        raw_cols = std::max(1, (dst_db || dst_rgba || overlay) ? std::min(raw_cols, out_cols) : raw_cols);
+        raw_cols = std::max(1, (dst_db || dst_rgba || overlay || hist) ? std::min(raw_cols, out_cols) : raw_cols);
         if (g.out_bytes(R, raw_cols) > lv.raw_bytes && (rc = grow(e, (void**)&lv.d_raw, &lv.raw_bytes, g.out_bytes(R, raw_cols)))) return rc;
         ls.out_db = lv.d_raw;
         ls.out_rgba = nullptr;
         ls.out_cols = raw_cols;
     } else {
-        ls.out_db = peaks ? lv.d_raw : dst_db;
+        ls.out_db = devdb ? lv.d_raw : dst_db;
         ls.out_rgba = reinterpret_cast<uint32_t*>(dst_rgba);
     }
     const DbMap m = db_map(e, g.n);
@@ -289,7 +293,7 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
         }
     }
     if (post) {
-        ls.out_db = peaks ? lv.d_pdb : dst_db;
+        ls.out_db = devdb ? lv.d_pdb : dst_db;
         ls.out_rgba = reinterpret_cast<uint32_t*>(dst_rgba);
         ls.out_cols = out_cols;
         HIPCHK(e, launch_live_post(ls, lv.d_raw, raw_cols, R, g.D, e->smoothing, e->agc, e->cfg.db_top, m, lv.d_pstate, g.S, e->stream));
@@ -314,6 +318,19 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
         ls.out_db = dst_db;
         ls.out_cols = out_cols;
         HIPCHK(e, launch_live_overlay(ls, ov, g.S, flush ? 1 : mlaunch, e->stream));
+    }
+    if (hist) {
+        LiveHistory h;
+        h.db = post ? lv.d_pdb : lv.d_raw;
+        h.ring = lv.d_hring;
+        h.ends = lv.d_hends;
+        h.W = (int)e->history_W;
+        h.rows = R;
+        h.D = g.D;
+        h.fill_out = peaks ? 0 : 1;   // (with peaks the overlay kernel has written dst_db)
+        ls.out_db = dst_db;
+        ls.out_cols = out_cols;
+        HIPCHK(e, launch_live_history_store(ls, h, g.S, flush ? 1 : mlaunch, e->stream));
     }
     return EMSPEC_OK;
 }
@@ -468,7 +485,9 @@ int columns_impl(emspec_engine* e, LiveState& lv, const float* frames, int32_t s
     if (rc) return rc;
     if ((rc = live_overlay_check(e, streams, 1))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
-    if (lv.g.form == 0 && (rc = live_open(e, lv, streams, n, hop, reassign, 1, n_high, split, false, bp))) return rc;
+    const bool opened = lv.g.form == 0;
+    if (opened && (rc = live_open(e, lv, streams, n, hop, reassign, 1, n_high, split, false, bp))) return rc;
+    if ((rc = history_ready(e, lv))) { if (opened) live_forget(lv); return rc; }
     // the frames: read by the kernel where they are when the caller's block is page-locked, else staged
     const float* src = reinterpret_cast<const float*>(device_view(frames));
     if (!src) {
@@ -494,6 +513,7 @@ int flush_impl(emspec_engine* e, LiveState& lv, float* out_db, uint8_t* out_rgba
     int rc;
     if ((rc = live_overlay_check(e, lv.g.S, 1))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
+    if ((rc = history_ready(e, lv))) return rc;
     LiveDest d;   // (as emspec_columns; the staging blocks are sized for a push's mmax columns at once)
     if ((rc = live_dest(e, lv, out_db, out_rgba, lv.g.mmax, d))) return rc;
     live_flush_fill(lv.g, lv.c, lv.desc());
@@ -531,24 +551,27 @@ int push_impl(emspec_engine* e, LiveState& lv, const void* block, int32_t stream
         return fail(e, EMSPEC_ERR_STATE, "the PCM format changed mid-stream; call emspec_reset() first");
     if (max_columns < 0) return fail(e, EMSPEC_ERR_INVALID_ARG, "max_columns must be >= 0");
     const int64_t expect = push_columns_impl(e, lv, count, n, hop, reassign);
-    // (an overlay is an output too: its slots are the columns of [S][max_columns])
-    if ((out_db || out_rgba || n_high || bp || fmt || e->live_peaks || e->live_wave) && expect > max_columns)
+    // (an overlay is an output too: its slots are the columns of [S][max_columns]; so is the history, whose columns pass
+    // through a device block of that layout)
+    if ((out_db || out_rgba || n_high || bp || fmt || e->live_peaks || e->live_wave || e->history_W > 0) && expect > max_columns)
         return fail(e, EMSPEC_ERR_INVALID_ARG, "output holds fewer columns than this block completes (" + std::to_string(expect) +
                                                    "); size it with emspec_push_columns() / emspec_push_columns_multi()");
     if ((rc = live_overlay_check(e, streams, max_columns))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
-    if (lv.g.form == 0) {
+    const bool opened = lv.g.form == 0;
+    if (opened) {
         if ((rc = live_open(e, lv, streams, n, hop, reassign, 2, n_high, split, fmt != nullptr, bp))) return rc;
         if (fmt && (rc = live_open_pcm(e, lv, *fmt))) { live_forget(lv); return rc; }
     }
+    if ((rc = history_ready(e, lv))) { if (opened) live_forget(lv); return rc; }
     const LiveGeometry& g = lv.g;
     // Unlike the one-column calls, a push decides for both outputs together: page-locked outputs are written in place
     // ([S][max_columns][rows], every round at the columns produced so far) only when BOTH are page-locked and max_columns fits
     // the launch's int; otherwise both go through a staging block of mmax columns per launch.  The overlays' arrays count as
-    // outputs here; and while peaks are set the delivered dB also lives in a device block with the launch's layout, so a block
-    // of more than mmax columns is staged.
+    // outputs here; and while peaks or a history are set the delivered dB also lives in a device block with the launch's
+    // layout, so a block of more than mmax columns is staged.
     LiveDest d;
-    if ((rc = live_dest(e, lv, out_db, out_rgba, g.mmax, d, true, max_columns <= (e->live_peaks ? g.mmax : 0x7fffffff)))) return rc;
+    if ((rc = live_dest(e, lv, out_db, out_rgba, g.mmax, d, true, max_columns <= (e->live_peaks || e->history_W > 0 ? g.mmax : 0x7fffffff)))) return rc;
     LivePush p(g.S);
     bool inflight = false;
     while (p.used < count) {
@@ -596,12 +619,13 @@ void live_free(LiveState& lv) {
     (void)hipFree(lv.d_pdb); (void)hipFree(lv.d_wring);
     if (lv.h_opeaks) (void)hipHostFree(lv.h_opeaks);
     if (lv.h_owave) (void)hipHostFree(lv.h_owave);
+    history_free(lv);
     lv = LiveState{};
 }
 }  // namespace
 
 namespace emspec {
-void live_destroy(emspec_engine* e) { live_free(e->live); live_free(e->one); }
+void live_destroy(emspec_engine* e) { live_free(e->live); live_free(e->one); history_destroy(e); }
 void live_reset(emspec_engine* e) { live_forget(e->live); live_forget(e->one); }
 bool live_pending(const emspec_engine* e) {
     return e->live.c.any_pending() || e->one.c.any_pending();

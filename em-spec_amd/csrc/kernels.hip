@@ -615,3 +615,4 @@ hipError_t launch_occupy(int groups, int usec, unsigned* sink, hipStream_t st) {
 #include "exact_fused_lr.hip.inc"
 #include "live_launch.hip.inc"
 #include "live_overlay.hip.inc"
+#include "live_history.hip.inc"

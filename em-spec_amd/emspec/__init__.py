@@ -65,7 +65,11 @@ LIVE_OVERLAY_SYMBOLS = ["emspec_set_live_peaks", "emspec_set_live_wave"]
 # the multi-band live session's: likewise (tools/live_multiband_rate.py times the parent commit's library next to this build)
 LIVE_MULTIBAND_SYMBOLS = ["emspec_columns_multiband", "emspec_push_columns_multiband", "emspec_push_samples_multiband",
                           "emspec_push_samples_pcm_multiband"]
-SYMBOLS = SYMBOLS + MULTIBAND_SYMBOLS + LIVE_OVERLAY_SYMBOLS + LIVE_MULTIBAND_SYMBOLS
+# the live history's: likewise (tools/history_rate.py times the parent commit's library next to this build)
+HISTORY_SYMBOLS = ["emspec_set_live_history", "emspec_live_history", "emspec_history_view_device", "emspec_history_view"]
+SYMBOLS = SYMBOLS + MULTIBAND_SYMBOLS + LIVE_OVERLAY_SYMBOLS + LIVE_MULTIBAND_SYMBOLS + HISTORY_SYMBOLS
+SESSION_MULTI, SESSION_ONE = 0, 1
+_SESSIONS = {"multi": SESSION_MULTI, "one": SESSION_ONE, SESSION_MULTI: SESSION_MULTI, SESSION_ONE: SESSION_ONE}
 
 
 class Config(C.Structure):
@@ -76,6 +80,12 @@ class Config(C.Structure):
 
 class Out(C.Structure):
     _fields_ = [("db", C.c_void_p), ("rgba", C.c_void_p), ("index", C.c_void_p)]
+
+
+class ViewMap(C.Structure):
+    """emspec_view_map: the colour law of a history view (db_top, db_range, gate_db as in the configuration) and the dB shift
+    applied in front of it."""
+    _fields_ = [("db_top", C.c_float), ("db_range", C.c_float), ("gate_db", C.c_float), ("shift_db", C.c_float)]
 
 
 class PcmFormat(C.Structure):
@@ -374,6 +384,14 @@ def load(diag=False):
         lib.emspec_push_samples_pcm_multiband.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
                                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                                           C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
+    if all(hasattr(lib, sym) for sym in HISTORY_SYMBOLS):
+        lib.emspec_set_live_history.argtypes = [C.c_void_p, C.c_int64]
+        lib.emspec_live_history.restype = C.c_int64
+        lib.emspec_live_history.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        lib.emspec_history_view_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.emspec_history_view.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _libs[diag] = lib
     return lib
 
@@ -1228,3 +1246,66 @@ class Engine:
         arr, pairs = self._overlay_array(out, WAVE_DTYPE)
         self._chk(self._lib.emspec_set_live_wave(self._h, _np_ptr(arr), pairs))
         self._live_wave = out
+
+    # -- live history (include/emspec.h: emspec_set_live_history / emspec_history_view) ----------------------------------------
+    def set_live_history(self, columns):
+        """emspec_set_live_history: keep the last `columns` delivered dB columns of every stream of both sessions on the device
+        (0 clears).  Set it before the sessions' first frames (or after reset())."""
+        self._chk(self._lib.emspec_set_live_history(self._h, int(columns)))
+
+    def live_history(self, stream=0, session="multi"):
+        """emspec_live_history: (end, first) - the columns the stream has emitted and the first one its ring holds - or None
+        without a history, for a session that has not started or a stream it does not have."""
+        first = C.c_int64(-1)
+        end = int(self._lib.emspec_live_history(self._h, _SESSIONS[session], int(stream), C.byref(first)))
+        return None if end < 0 else (end, int(first.value))
+
+    @staticmethod
+    def _view_map(map):
+        """None, a ViewMap, a (db_top, db_range, gate_db, shift_db) tuple or a dict of those names -> ViewMap or None."""
+        if map is None or isinstance(map, ViewMap):
+            return map
+        if isinstance(map, dict):
+            return ViewMap(float(map["db_top"]), float(map["db_range"]), float(map["gate_db"]), float(map.get("shift_db", 0.0)))
+        return ViewMap(*(float(x) for x in map))
+
+    def history_view_device(self, first_column, factor, groups, stream0=0, streams=None, map=None, db=None, index=None, rgba=None,
+                            session="multi", stream=None):
+        """emspec_history_view_device: db [streams][groups][rows] float32 / index uint8 / rgba [..][4] uint8 contiguous CUDA
+        tensors or None (not all).  Enqueues on `stream` (a torch.cuda.Stream; default: the current torch stream); does not
+        synchronise."""
+        import torch
+        sess = _SESSIONS[session]
+        if streams is None:
+            streams = (self.live_streams if sess == SESSION_MULTI else 1) - stream0
+        for t in (db, index, rgba):
+            assert t is None or (t.is_cuda and t.is_contiguous())
+        st = stream if stream is not None else torch.cuda.current_stream()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        m = self._view_map(map)
+        self._chk(self._lib.emspec_history_view_device(self._h, sess, int(stream0), int(streams), int(first_column), int(factor),
+                                                       int(groups), C.byref(m) if m is not None else None, ptr(db), ptr(index),
+                                                       ptr(rgba), C.c_void_p(st.cuda_stream)))
+
+    def history_view(self, first_column, factor, groups, stream0=0, streams=None, map=None, want=("db",), db=None, index=None,
+                     rgba=None, session="multi"):
+        """emspec_history_view: groups of `factor` stored columns from first_column on, of streams [stream0, stream0 + streams)
+        (default: all from stream0 on) -> {"db": [streams][groups][rows] float32, "index": uint8, "rgba": [..][4] uint8}, each
+        present when named in `want` or preallocated (numpy arrays or PinnedArray.array, written in place)."""
+        sess = _SESSIONS[session]
+        if streams is None:
+            streams = (self.live_streams if sess == SESSION_MULTI else 1) - stream0
+        shape = (max(int(streams), 0), max(int(groups), 0), self.rows)
+        if db is None and "db" in want:
+            db = np.empty(shape, np.float32)
+        if index is None and "index" in want:
+            index = np.empty(shape, np.uint8)
+        if rgba is None and "rgba" in want:
+            rgba = np.empty(shape + (4,), np.uint8)
+        for a, dt, sh in ((db, np.float32, shape), (index, np.uint8, shape), (rgba, np.uint8, shape + (4,))):
+            assert a is None or (a.dtype == dt and a.flags.c_contiguous and a.shape == sh), (a.dtype, a.shape, sh)
+        m = self._view_map(map)
+        self._chk(self._lib.emspec_history_view(self._h, sess, int(stream0), int(streams), int(first_column), int(factor),
+                                                int(groups), C.byref(m) if m is not None else None, _np_ptr(db), _np_ptr(index),
+                                                _np_ptr(rgba)))
+        return {"db": db, "index": index, "rgba": rgba}

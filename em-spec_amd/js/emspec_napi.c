@@ -1312,6 +1312,78 @@ static napi_value SetLiveWave(napi_env env, napi_callback_info info) {
     h->live_wave = ref;
     return NULL;
 }
+/* Live history (include/emspec.h: emspec_set_live_history / emspec_live_history / emspec_history_view).
+ * setLiveHistory(handle, columns): W columns per stream, 0 clears
+ * liveHistory(handle, session, stream) -> [end, first] or null (no history, or the session has no such stream)
+ * historyView(handle, session, stream0, streams, firstColumn, factor, groups, map:Float32Array(4) | null,
+ *             outDb:Float32Array | null, outIndex:Uint8Array | null, outRgba:Uint8Array | null): the arrays hold exactly
+ *             streams * groups * rows cells (RGBA: x 4); map = [dbTop, dbRange, gateDb, shiftDb] */
+static napi_value SetLiveHistory(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "setLiveHistory(handle, columns)"); return NULL; }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    int64_t w = 0;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[1], &w));
+    int rc = emspec_set_live_history(h->e, w);
+    if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
+    return NULL;
+}
+static napi_value LiveHistory(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 3) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "liveHistory(handle, session, stream)"); return NULL; }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    int32_t session = 0, stream = 0;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[1], &session));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[2], &stream));
+    int64_t first = -1;
+    const int64_t end = emspec_live_history(h->e, session, stream, &first);
+    napi_value r;
+    if (end < 0) { NAPI_OK_OR_RETURN(env, napi_get_null(env, &r)); return r; }
+    napi_value a, b;
+    NAPI_OK_OR_RETURN(env, napi_create_array_with_length(env, 2, &r));
+    NAPI_OK_OR_RETURN(env, napi_create_int64(env, end, &a));
+    NAPI_OK_OR_RETURN(env, napi_create_int64(env, first, &b));
+    NAPI_OK_OR_RETURN(env, napi_set_element(env, r, 0, a));
+    NAPI_OK_OR_RETURN(env, napi_set_element(env, r, 1, b));
+    return r;
+}
+static napi_value HistoryView(napi_env env, napi_callback_info info) {
+    size_t argc = 11; napi_value argv[11];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 11) {
+        napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "historyView(handle, session, stream0, streams, firstColumn, factor, groups, map, outDb, outIndex, outRgba)");
+        return NULL;
+    }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    int32_t session = 0, stream0 = 0, streams = 0, factor = 0; int64_t first = 0, groups = 0;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[1], &session));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[2], &stream0));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[3], &streams));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[4], &first));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[5], &factor));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[6], &groups));
+    void *mp = NULL, *db = NULL, *idx = NULL, *rgba = NULL; size_t mlen = 0, dlen = 0, ilen = 0, rlen = 0;
+    if (!get_typed(env, argv[7], napi_float32_array, &mp, &mlen, 1) || (mp && mlen != 4)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "map must be a Float32Array(4) or null"); return NULL; }
+    if (!get_typed(env, argv[8], napi_float32_array, &db, &dlen, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outDb must be a Float32Array or null"); return NULL; }
+    if (!get_typed(env, argv[9], napi_uint8_array, &idx, &ilen, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outIndex must be a Uint8Array or null"); return NULL; }
+    if (!get_typed(env, argv[10], napi_uint8_array, &rgba, &rlen, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outRgba must be a Uint8Array or null"); return NULL; }
+    /* (streams or groups below 1: the library rejects the call with its message before it touches an output) */
+    if (streams >= 1 && groups >= 1) {
+        const size_t cells = (size_t)streams * (size_t)groups * (size_t)h->rows;
+        if ((db && dlen != cells) || (idx && ilen != cells) || (rgba && rlen != 4 * cells)) {
+            napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "every output must hold exactly streams*groups*rows cells (RGBA: x 4)");
+            return NULL;
+        }
+    }
+    emspec_view_map m;
+    if (mp) { const float* f = (const float*)mp; m.db_top = f[0]; m.db_range = f[1]; m.gate_db = f[2]; m.shift_db = f[3]; }
+    int rc = emspec_history_view(h->e, session, stream0, streams, first, factor, groups, mp ? &m : NULL, (float*)db, (uint8_t*)idx, (uint8_t*)rgba);
+    if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
+    return NULL;
+}
+
 static napi_value WaveOf(napi_env env, napi_callback_info info) {
     size_t argc = 7; napi_value argv[7];
     NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -1547,6 +1619,9 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"waveOf", NULL, WaveOf, NULL, NULL, NULL, napi_default, NULL},
         {"setLivePeaks", NULL, SetLivePeaks, NULL, NULL, NULL, napi_default, NULL},
         {"setLiveWave", NULL, SetLiveWave, NULL, NULL, NULL, napi_default, NULL},
+        {"setLiveHistory", NULL, SetLiveHistory, NULL, NULL, NULL, napi_default, NULL},
+        {"liveHistory", NULL, LiveHistory, NULL, NULL, NULL, napi_default, NULL},
+        {"historyView", NULL, HistoryView, NULL, NULL, NULL, napi_default, NULL},
         {"positionHz", NULL, PositionHz, NULL, NULL, NULL, napi_default, NULL},
         {"setRowEdges", NULL, SetRowEdges, NULL, NULL, NULL, napi_default, NULL},
         {"getRowEdges", NULL, GetRowEdges, NULL, NULL, NULL, napi_default, NULL},

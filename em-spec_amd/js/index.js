@@ -76,6 +76,39 @@ class Engine {
     this.columnsWave = arr;
   }
 
+  /**
+   * Live history (emspec_set_live_history / emspec_live_history / emspec_history_view, DESIGN.md §3.14): the engine keeps the
+   * last `columns` dB columns every live call delivers, per stream, on the device; historyView reads them back reduced in time
+   * and coloured - what a renderer needs when the scroll speed, the window, the dB range, the gain, the gate or the colour map
+   * changes, or the user scrolls back.  Set it before a session's first frame (or after reset()); 0 clears.
+   * liveHistory(stream) -> {end, first}: the columns the stream has emitted and the first one still held, or null.
+   * historyView({stream0 = 0, streams = all from stream0, firstColumn, factor = 1, groups, map, want = ['db']}) ->
+   *   {db: Float32Array(streams * groups * rows), index: Uint8Array, rgba: Uint8Array(x 4)} (those named in `want`): group g
+   *   is the peak hold of columns firstColumn + g * factor ... of each stream; map = {dbTop, dbRange, gateDb, shiftDb} is the
+   *   colour law of index / rgba (default: the engine's configuration, no shift).  A single-stream engine views the session of
+   *   computeSpectrogramColumn / pushSamples.
+   */
+  setLiveHistory(columns) { native.setLiveHistory(this._h, columns); }
+  _historySession() { return this.streams > 1 ? 0 : 1; }
+  liveHistory(stream = 0) {
+    const r = native.liveHistory(this._h, this._historySession(), stream);
+    return r ? { end: r[0], first: r[1] } : null;
+  }
+  historyView(opts) {
+    const stream0 = opts.stream0 | 0, streams = opts.streams === undefined ? this.streams - stream0 : opts.streams | 0;
+    const groups = +opts.groups, factor = opts.factor === undefined ? 1 : opts.factor | 0;
+    const want = opts.want || ['db'];
+    const cells = Math.max(0, streams) * Math.max(0, groups) * this.rows;
+    const out = {};
+    if (want.includes('db')) out.db = new Float32Array(cells);
+    if (want.includes('index')) out.index = new Uint8Array(cells);
+    if (want.includes('rgba')) out.rgba = new Uint8Array(4 * cells);
+    const m = opts.map ? Float32Array.of(opts.map.dbTop, opts.map.dbRange, opts.map.gateDb, opts.map.shiftDb || 0) : null;
+    native.historyView(this._h, this._historySession(), stream0, streams, +opts.firstColumn, factor, groups, m,
+      out.db || null, out.index || null, out.rgba || null);
+    return out;
+  }
+
   /** Page-locked Float32Array / Uint8Array views for the live calls, (re)made when the shape changes. */
   _liveBlocks(fftSize, wantRgba) {
     const S = this.streams, R = this.rows;

@@ -877,6 +877,75 @@ int emspec_set_wave_out(emspec_engine* e, emspec_wave* wave_out, int64_t capacit
 int emspec_set_live_peaks(emspec_engine* e, int32_t k, float min_db, emspec_peak* peaks_out, int64_t capacity /* pairs */);
 int emspec_set_live_wave(emspec_engine* e, emspec_wave* wave_out, int64_t capacity /* pairs */);
 
+/*
+ * ---- Live history: a ring on the device of the dB columns the streaming calls deliver, W per stream,
+ * and views that read it back reduced in time and coloured by a law of the caller's.  Serves the events that make a live
+ * renderer redraw its whole visible image - a change of "Scroll Speed" (columns per pixel), a window resize, pause and scroll
+ * back, a change of "dB Range", "Gain", "Noise Gate" or "Color Map" - without the host keeping every 4 KB column of every stream
+ * and taking maxima and colours on its own cores; [BUILD-DEFINED].  Off unless set; with it cleared the streaming calls launch,
+ * allocate and write exactly what they did before these entries.  The streaming calls keep refusing emspec_set_time_reduce
+ * factors above 1 (above): a view's factor is given per view.
+ *
+ * Columns are numbered per stream: column c is the c-th finished column the stream's session has emitted since the stream was
+ * (re)started - the batch's column index, the number out_columns / out_first_columns speak of.  The empty column "-1" the
+ * per-frame form delivers before the latency has passed is not a column and is not stored.
+ * Stored is the dB column the call delivers, byte for byte - the post-processed column with emspec_set_display on, the composed
+ * column of a multi-resolution or multi-band session, the decoded views' columns of a PCM session - whether or not the caller
+ * asked for out_db; flush columns too.  Column c lives in slot c mod W (W need not be a power of two); after any call the ring
+ * of a stream holds the columns [max(0, end - W), end), end = the number emitted so far; a launch that emits more than W columns
+ * of a stream stores its last W.
+ * While a history is set the delivered dB passes through a device block, as with emspec_set_live_peaks: a push call must fit
+ * max_columns like one with an output (EMSPEC_ERR_INVALID_ARG before anything is fed), and page-locked outputs of more than
+ * one launch's columns are staged.
+ *
+ * emspec_set_live_history(e, W): W columns per stream for both sessions of the engine; 0 clears and frees the rings (always
+ *   allowed).  EMSPEC_ERR_INVALID_ARG: W outside 0 .. 2^20, engine rows not a multiple of 4.  EMSPEC_ERR_STATE: W > 0 while
+ *   either session has frames fed (emspec_reset first).  A ring (streams x W x rows x 4 bytes) is allocated by the first
+ *   streaming call of a session, when its streams are known: EMSPEC_ERR_OUT_OF_MEMORY on that call, before anything is fed;
+ *   the session stays as it was.  emspec_reset empties every ring; emspec_reset_stream empties that stream's ring and restarts
+ *   its numbering, the other streams keep theirs.
+ * emspec_live_history(e, session, stream, &first): the number of columns stream `stream` of the session has emitted (`end`),
+ *   and in *first (may be NULL) the first column held; -1 for a NULL engine, an unknown session or stream (a session that has
+ *   not started has no streams), or no history.  session: EMSPEC_SESSION_MULTI (emspec_columns*, emspec_push_samples_multi /
+ *   _multires / _multiband / _pcm*) or EMSPEC_SESSION_ONE (emspec_column, emspec_push_samples, emspec_column_flush).
+ *
+ * A view of streams [stream0, stream0 + streams): for g in [0, groups), with a = first_column and f = factor, group g covers the
+ * columns a + g f .. min(a + (g + 1) f, end) - 1 of each stream (the last group may be short) and
+ *     db   [s][g][r] = the peak hold of emspec_set_time_reduce over the group's stored bytes, in column order, same comparison
+ *     index[s][g][r] = the palette index of db[s][g][r] + map->shift_db under the law of map (db_top, db_range, gate_db as in
+ *                      emspec_config; map == NULL: the engine's configuration, shift 0)
+ *     rgba [s][g][r] = LUT[index[s][g][r]], the colour map the engine holds when the view runs (emspec_set_colormap)
+ * Layouts [streams][groups][rows] (+[4]); any output may be NULL, not all.  The dB output is NOT shifted.  The index is the
+ * law applied to the stored dB - that is what lets a view re-colour after the fact: in EXACT mode without the display
+ * post-process it is the law on the dB bytes, not the cell-derived index of the live RGBA, and may differ from it by one step
+ * on a borderline cell.  db_range must be > 0 and no field NaN.
+ * Required: first_column >= the first held column and first_column + (groups - 1) factor < end, for every addressed stream -
+ * else EMSPEC_ERR_INVALID_ARG with a message naming the stream and its held range, nothing written.  Also
+ * EMSPEC_ERR_INVALID_ARG: factor outside 1 .. 65536, groups < 1, streams < 1, a stream range outside the session, all outputs
+ * NULL, a misaligned output.  EMSPEC_ERR_STATE: no history set, or a session that does not exist.  Every refusal leaves the
+ * engine usable.
+ * emspec_history_view_device: outputs are device memory (db_dev and rgba_dev 16-byte, index_dev 4-byte aligned); enqueues on
+ *   hip_stream (NULL: the default stream, as for emspec_batch_device) behind the session's launches - every streaming call
+ *   has synchronised before it returned - and does not synchronise; later streaming calls are ordered behind the view.  emspec_history_view: outputs are host arrays, page-locked (written in place) or pageable (staged through
+ *   page-locked blocks), as out_db of the live calls; synchronises.
+ */
+#define EMSPEC_SESSION_MULTI 0   /* emspec_columns*, emspec_push_samples_multi / _multires / _multiband / _pcm* */
+#define EMSPEC_SESSION_ONE   1   /* emspec_column, emspec_push_samples, emspec_column_flush */
+
+typedef struct emspec_view_map {   /* the colour law of a view; NULL = the engine's configuration, shift 0 */
+    float db_top, db_range, gate_db;   /* as in emspec_config */
+    float shift_db;                    /* added to the dB before the law ("Gain" after the fact); the dB output is NOT shifted */
+} emspec_view_map;
+
+int     emspec_set_live_history(emspec_engine* e, int64_t columns /* W per stream; 0 clears */);
+int64_t emspec_live_history(const emspec_engine* e, int32_t session, int32_t stream, int64_t* first_column /* may be NULL */);
+int     emspec_history_view_device(emspec_engine* e, int32_t session, int32_t stream0, int32_t streams, int64_t first_column,
+                                   int32_t factor, int64_t groups, const emspec_view_map* map,
+                                   float* db_dev, uint8_t* index_dev, uint8_t* rgba_dev, void* hip_stream);
+int     emspec_history_view(emspec_engine* e, int32_t session, int32_t stream0, int32_t streams, int64_t first_column,
+                            int32_t factor, int64_t groups, const emspec_view_map* map,
+                            float* out_db, uint8_t* out_index, uint8_t* out_rgba);
+
 #ifdef __cplusplus
 }
 #endif
