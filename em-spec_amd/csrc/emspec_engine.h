@@ -77,6 +77,11 @@ struct LiveState {
     float* d_hring = nullptr; size_t hring_bytes = 0;
     long long* d_hends = nullptr; size_t hends_bytes = 0;
     hipEvent_t view_done = nullptr;
+    // live audio history (emspec_set_live_audio; live_audio.hip.inc, emspec_audio_plan.h), allocated by the first call of the
+    // session while an audio history is set: the ring [S][audio_stride(W)] samples.  What a stream holds follows from the
+    // counters above (audio_end).  audio_done: as view_done, behind a device view or re-analysis on the caller's stream
+    uint32_t* d_aring = nullptr; size_t aring_bytes = 0;
+    hipEvent_t audio_done = nullptr;
     LiveStream* desc() const { return reinterpret_cast<LiveStream*>(h_desc); }
 };
 
@@ -161,6 +166,12 @@ bool live_pending(const emspec_engine* e);   // some stream of either session ha
 int history_ready(emspec_engine* e, LiveState& lv);
 void history_free(LiveState& lv);
 void history_destroy(emspec_engine* e);
+// emspec_audio.cpp: the live audio history's buffers, as their history twins.  audio_store: the store kernel of one launch of
+// the session, behind its other kernels (nothing while no audio history is set, and for a flush)
+int audio_ready(emspec_engine* e, LiveState& lv);
+void audio_free(LiveState& lv);
+void audio_destroy(emspec_engine* e);
+int audio_store(emspec_engine* e, LiveState& lv, const LiveSinks& ls, bool flush);
 }  // namespace emspec
 
 struct emspec_engine {
@@ -213,6 +224,13 @@ struct emspec_engine {
     // page-locked staging blocks of a host view's pageable outputs (dB, index, RGBA)
     int64_t history_W = 0;
     void* h_view[3] = {}; size_t view_bytes[3] = {};
+    // live audio history (emspec_set_live_audio; emspec_audio.cpp): W samples per stream of both sessions below (0: off), the
+    // page-locked staging block of a host view's pageable output, and the device blocks of a re-analysis (emspec_audio_batch*):
+    // the viewed samples [streams][count] and the host form's dB / RGBA / index columns
+    int64_t audio_W = 0;
+    void* h_aview = nullptr; size_t aview_bytes = 0;
+    float* d_apcm = nullptr; size_t apcm_bytes = 0;
+    void* d_aout[3] = {}; size_t aout_bytes[3] = {};
     // streaming (emspec_live.cpp): the live multi-stream session, and the single-stream calls' own (emspec_column,
     // emspec_push_samples: the same machinery with one stream); independent of each other
     emspec::LiveState live, one;

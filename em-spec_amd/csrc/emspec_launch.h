@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "emspec_audio_plan.h"
 #include "emspec_band_plan.h"
 #include "emspec_device.h"
 #include "emspec_history_plan.h"
@@ -208,6 +209,26 @@ struct HistoryView {
 };
 int history_view_split(int streams, int64_t groups, int rows, int f);   // waves a group's columns are cut over (1: no split)
 hipError_t launch_history_view(const HistoryView& v, int streams, hipStream_t st);
+// The live audio history (live_audio.hip.inc; emspec_set_live_audio; geometry: emspec_audio_plan.h).  The store: one kernel
+// behind the launch's other kernels, on the same descriptors (lv.fresh / lv.fresh_stride / lv.streams); `most`: the most
+// samples any stream brings in the launch.
+struct LiveAudio {
+    uint32_t* ring = nullptr;    // [S][stride] samples as words: sample a of stream s in slot a mod W
+    long long W = 0, stride = 0; // stride = audio_stride(W)
+    int form = 0, n = 0, hop = 0;   // the session's feeding form (1 per-frame, 2 block), frame length and hop
+};
+hipError_t launch_live_audio_store(const LiveSinks& lv, const LiveAudio& a, int S, int64_t most, hipStream_t st);
+// The view: samples [first, first + n0 + n1) of streams [stream0, stream0 + streams) -> out [streams][out_stride] words;
+// slot0 = first mod W, n0 / n1 the range's runs before and behind the wrap (audio_runs).
+struct AudioView {
+    const uint32_t* ring = nullptr;
+    long long W = 0, stride = 0;
+    int stream0 = 0;
+    long long slot0 = 0, n0 = 0, n1 = 0;
+    uint32_t* out = nullptr;
+    long long out_stride = 0;
+};
+hipError_t launch_audio_view(const AudioView& v, int streams, hipStream_t st);
 // the gather's wire image (pack.hip.inc; its sizes and the pack workspace `scratch` of wire_scratch_bytes: emspec_wire_plan.h).
 // wire_total_ptr: where in the workspace the pack leaves the image's size
 uint64_t* wire_total_ptr(void* scratch, int64_t columns);

@@ -139,6 +139,7 @@ int live_post_buffers(emspec_engine* e, LiveState& lv) {
 // like the destination (d_raw, or d_pdb behind the post kernel) and the overlay kernel writes dst_db from its copy of it.
 // While a history is set (emspec_set_live_history) the delivered dB takes the same way, and the store kernel (live_history.hip.inc)
 // goes behind the launch too: it copies every delivered column into the session's ring and, without peaks, writes dst_db.
+// While an audio history is set (emspec_set_live_audio) the audio store kernel (live_audio.hip.inc) goes last.
 int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fresh_stride, int mlaunch, bool flush, float* dst_db,
                 uint8_t* dst_rgba, int out_cols, int raw_cols, bool empty_col, emspec_peak* dst_peaks = nullptr,
                 emspec_wave* dst_wave = nullptr) {
@@ -332,6 +333,9 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
         ls.out_cols = out_cols;
         HIPCHK(e, launch_live_history_store(ls, h, g.S, flush ? 1 : mlaunch, e->stream));
     }
+    // while an audio history is set (emspec_set_live_audio): the samples this launch moved to the device, into the session's
+    // sample ring - also for a launch without a frame; a flush brings none
+    if (e->audio_W > 0 && (rc = audio_store(e, lv, ls, flush))) return rc;
     return EMSPEC_OK;
 }
 
@@ -488,6 +492,7 @@ int columns_impl(emspec_engine* e, LiveState& lv, const float* frames, int32_t s
     const bool opened = lv.g.form == 0;
     if (opened && (rc = live_open(e, lv, streams, n, hop, reassign, 1, n_high, split, false, bp))) return rc;
     if ((rc = history_ready(e, lv))) { if (opened) live_forget(lv); return rc; }
+    if ((rc = audio_ready(e, lv))) { if (opened) live_forget(lv); return rc; }
     // the frames: read by the kernel where they are when the caller's block is page-locked, else staged
     const float* src = reinterpret_cast<const float*>(device_view(frames));
     if (!src) {
@@ -564,6 +569,7 @@ int push_impl(emspec_engine* e, LiveState& lv, const void* block, int32_t stream
         if (fmt && (rc = live_open_pcm(e, lv, *fmt))) { live_forget(lv); return rc; }
     }
     if ((rc = history_ready(e, lv))) { if (opened) live_forget(lv); return rc; }
+    if ((rc = audio_ready(e, lv))) { if (opened) live_forget(lv); return rc; }
     const LiveGeometry& g = lv.g;
     // Unlike the one-column calls, a push decides for both outputs together: page-locked outputs are written in place
     // ([S][max_columns][rows], every round at the columns produced so far) only when BOTH are page-locked and max_columns fits
@@ -620,12 +626,13 @@ void live_free(LiveState& lv) {
     if (lv.h_opeaks) (void)hipHostFree(lv.h_opeaks);
     if (lv.h_owave) (void)hipHostFree(lv.h_owave);
     history_free(lv);
+    audio_free(lv);
     lv = LiveState{};
 }
 }  // namespace
 
 namespace emspec {
-void live_destroy(emspec_engine* e) { live_free(e->live); live_free(e->one); history_destroy(e); }
+void live_destroy(emspec_engine* e) { live_free(e->live); live_free(e->one); history_destroy(e); audio_destroy(e); }
 void live_reset(emspec_engine* e) { live_forget(e->live); live_forget(e->one); }
 bool live_pending(const emspec_engine* e) {
     return e->live.c.any_pending() || e->one.c.any_pending();

@@ -67,7 +67,10 @@ LIVE_MULTIBAND_SYMBOLS = ["emspec_columns_multiband", "emspec_push_columns_multi
                           "emspec_push_samples_pcm_multiband"]
 # the live history's: likewise (tools/history_rate.py times the parent commit's library next to this build)
 HISTORY_SYMBOLS = ["emspec_set_live_history", "emspec_live_history", "emspec_history_view_device", "emspec_history_view"]
-SYMBOLS = SYMBOLS + MULTIBAND_SYMBOLS + LIVE_OVERLAY_SYMBOLS + LIVE_MULTIBAND_SYMBOLS + HISTORY_SYMBOLS
+# the live audio history's: likewise (tools/live_audio_rate.py times the parent commit's library next to this build)
+AUDIO_SYMBOLS = ["emspec_set_live_audio", "emspec_live_audio", "emspec_audio_view_device", "emspec_audio_view",
+                 "emspec_audio_batch_device", "emspec_audio_batch"]
+SYMBOLS = SYMBOLS + MULTIBAND_SYMBOLS + LIVE_OVERLAY_SYMBOLS + LIVE_MULTIBAND_SYMBOLS + HISTORY_SYMBOLS + AUDIO_SYMBOLS
 SESSION_MULTI, SESSION_ONE = 0, 1
 _SESSIONS = {"multi": SESSION_MULTI, "one": SESSION_ONE, SESSION_MULTI: SESSION_MULTI, SESSION_ONE: SESSION_ONE}
 
@@ -392,6 +395,17 @@ def load(diag=False):
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.emspec_history_view.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if all(hasattr(lib, sym) for sym in AUDIO_SYMBOLS):
+        lib.emspec_set_live_audio.argtypes = [C.c_void_p, C.c_int64]
+        lib.emspec_live_audio.restype = C.c_int64
+        lib.emspec_live_audio.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        lib.emspec_audio_view_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
+                                                 C.c_int64, C.c_void_p]
+        lib.emspec_audio_view.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
+        lib.emspec_audio_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                                                  C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.emspec_audio_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                           C.c_int32, C.POINTER(Out)]
     _libs[diag] = lib
     return lib
 
@@ -1309,3 +1323,77 @@ class Engine:
                                                 int(groups), C.byref(m) if m is not None else None, _np_ptr(db), _np_ptr(index),
                                                 _np_ptr(rgba)))
         return {"db": db, "index": index, "rgba": rgba}
+
+    # -- live audio history (include/emspec.h: emspec_set_live_audio / emspec_audio_view / emspec_audio_batch) ------------------
+    def _audio_streams(self, sess, stream0, streams):
+        return (self.live_streams if sess == SESSION_MULTI else 1) - stream0 if streams is None else int(streams)
+
+    def set_live_audio(self, samples):
+        """emspec_set_live_audio: keep the last `samples` samples every streaming call was fed, per stream of both sessions, on
+        the device (0 clears).  Set it before the sessions' first samples (or after reset())."""
+        self._chk(self._lib.emspec_set_live_audio(self._h, int(samples)))
+
+    def live_audio(self, stream=0, session="multi"):
+        """emspec_live_audio: (end, first) - the samples of the stream that were stored and the first one its ring holds - or
+        None without an audio history, for a session that has not started or a stream it does not have."""
+        first = C.c_int64(-1)
+        end = int(self._lib.emspec_live_audio(self._h, _SESSIONS[session], int(stream), C.byref(first)))
+        return None if end < 0 else (end, int(first.value))
+
+    def audio_view_device(self, first_sample, count, pcm, stream0=0, streams=None, stride=None, session="multi", stream=None):
+        """emspec_audio_view_device: samples [first_sample, first_sample + count) of streams [stream0, stream0 + streams) into
+        the float32 CUDA tensor `pcm` (any 4-byte alignment - a slice will do), rows `stride` samples apart (default: count).
+        Enqueues on `stream` (a torch.cuda.Stream; default: the current torch stream); does not synchronise."""
+        import torch
+        sess = _SESSIONS[session]
+        assert pcm is None or (pcm.is_cuda and pcm.dtype == torch.float32)
+        st = stream if stream is not None else torch.cuda.current_stream()
+        self._chk(self._lib.emspec_audio_view_device(self._h, sess, int(stream0), self._audio_streams(sess, stream0, streams),
+                                                     int(first_sample), int(count), C.c_void_p(pcm.data_ptr()) if pcm is not None else None,
+                                                     int(count if stride is None else stride), C.c_void_p(st.cuda_stream)))
+
+    def audio_view(self, first_sample, count, stream0=0, streams=None, pcm=None, stride=None, session="multi"):
+        """emspec_audio_view: samples [first_sample, first_sample + count) of streams [stream0, stream0 + streams) (default: all
+        from stream0 on) -> float32 [streams][stride] (default stride: count; a numpy array or PinnedArray.array given as `pcm`
+        is written in place), bit for bit what the session was fed."""
+        sess = _SESSIONS[session]
+        streams = self._audio_streams(sess, stream0, streams)
+        stride = int(count if stride is None else stride)
+        if pcm is None:
+            pcm = np.zeros((max(streams, 0), max(stride, 0)), np.float32)
+        assert pcm.dtype == np.float32 and pcm.flags.c_contiguous
+        self._chk(self._lib.emspec_audio_view(self._h, sess, int(stream0), streams, int(first_sample), int(count), _np_ptr(pcm), stride))
+        return pcm
+
+    def audio_batch_device(self, first_sample, count, n, hop, reassign=True, stream0=0, streams=None, db=None, rgba=None, index=None,
+                           session="multi", stream=None):
+        """emspec_audio_batch_device: batch_device over the held samples [first_sample, first_sample + count) of the streams -
+        at any n, hop and reassign, not only the session's.  db / rgba / index: contiguous CUDA tensors [streams][columns][rows]
+        (+[4]) or None, as for batch_device.  Enqueues on `stream` (default: the current torch stream); does not synchronise."""
+        import torch
+        sess = _SESSIONS[session]
+        for t in (db, rgba, index):
+            assert t is None or (t.is_cuda and t.is_contiguous())
+        st = stream if stream is not None else torch.cuda.current_stream()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._chk(self._lib.emspec_audio_batch_device(self._h, sess, int(stream0), self._audio_streams(sess, stream0, streams),
+                                                      int(first_sample), int(count), int(n), int(hop), 1 if reassign else 0, ptr(db),
+                                                      ptr(rgba), ptr(index), C.c_void_p(st.cuda_stream)))
+
+    def audio_batch(self, first_sample, count, n, hop, reassign=True, stream0=0, streams=None, want=("db",), session="multi"):
+        """emspec_audio_batch: the same with host outputs -> {"db": [streams][columns][rows] float32, "rgba": [..][4] uint8,
+        "index": uint8}, each present when named in `want`; columns = num_columns(count, n, hop), reduced by the engine's time
+        reduction."""
+        sess = _SESSIONS[session]
+        streams = self._audio_streams(sess, stream0, streams)
+        cols = max(num_columns(int(count), int(n), int(hop)), 0)
+        f = int(self._lib.emspec_time_reduce(self._h))
+        cols = (cols + f - 1) // f if f > 1 else cols
+        shape = (max(streams, 0), cols, self.rows)
+        db = np.empty(shape, np.float32) if "db" in want else None
+        rgba = np.empty(shape + (4,), np.uint8) if "rgba" in want else None
+        index = np.empty(shape, np.uint8) if "index" in want else None
+        out = Out(_np_ptr(db), _np_ptr(rgba), _np_ptr(index))
+        self._chk(self._lib.emspec_audio_batch(self._h, sess, int(stream0), streams, int(first_sample), int(count), int(n), int(hop),
+                                               1 if reassign else 0, C.byref(out)))
+        return {"db": db, "rgba": rgba, "index": index}

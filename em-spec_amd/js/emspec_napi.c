@@ -1384,6 +1384,104 @@ static napi_value HistoryView(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* Live audio history (include/emspec.h: emspec_set_live_audio / emspec_live_audio / emspec_audio_view / emspec_audio_batch).
+ * setLiveAudio(handle, samples): W samples per stream, 0 clears
+ * liveAudio(handle, session, stream) -> [end, first] or null (no audio history, or the session has no such stream)
+ * audioView(handle, session, stream0, streams, firstSample, count, out:Float32Array(streams * count))
+ * audioBatch(handle, session, stream0, streams, firstSample, count, fftSize, hop, reassign, outDb, outRgba, outIndex) -> columns:
+ *            each output a typed array of exactly streams * columns * rows cells (RGBA: x 4) or null */
+static napi_value SetLiveAudio(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "setLiveAudio(handle, samples)"); return NULL; }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    int64_t w = 0;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[1], &w));
+    int rc = emspec_set_live_audio(h->e, w);
+    if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
+    return NULL;
+}
+static napi_value LiveAudio(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 3) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "liveAudio(handle, session, stream)"); return NULL; }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    int32_t session = 0, stream = 0;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[1], &session));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[2], &stream));
+    int64_t first = -1;
+    const int64_t end = emspec_live_audio(h->e, session, stream, &first);
+    napi_value r;
+    if (end < 0) { NAPI_OK_OR_RETURN(env, napi_get_null(env, &r)); return r; }
+    napi_value a, b;
+    NAPI_OK_OR_RETURN(env, napi_create_array_with_length(env, 2, &r));
+    NAPI_OK_OR_RETURN(env, napi_create_int64(env, end, &a));
+    NAPI_OK_OR_RETURN(env, napi_create_int64(env, first, &b));
+    NAPI_OK_OR_RETURN(env, napi_set_element(env, r, 0, a));
+    NAPI_OK_OR_RETURN(env, napi_set_element(env, r, 1, b));
+    return r;
+}
+static napi_value AudioView(napi_env env, napi_callback_info info) {
+    size_t argc = 7; napi_value argv[7];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 7) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "audioView(handle, session, stream0, streams, firstSample, count, out)"); return NULL; }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    int32_t session = 0, stream0 = 0, streams = 0; int64_t first = 0, count = 0;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[1], &session));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[2], &stream0));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[3], &streams));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[4], &first));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[5], &count));
+    void* out = NULL; size_t olen = 0;
+    if (!get_typed(env, argv[6], napi_float32_array, &out, &olen, 0)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "out must be a Float32Array"); return NULL; }
+    /* (streams or count below 1: the library rejects the call with its message before it touches the output) */
+    if (streams >= 1 && count >= 1 && olen != (size_t)streams * (size_t)count) {
+        napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "out must hold exactly streams*count samples");
+        return NULL;
+    }
+    int rc = emspec_audio_view(h->e, session, stream0, streams, first, count, (float*)out, count);
+    if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
+    return NULL;
+}
+static napi_value AudioBatch(napi_env env, napi_callback_info info) {
+    size_t argc = 12; napi_value argv[12];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 12) {
+        napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "audioBatch(handle, session, stream0, streams, firstSample, count, fftSize, hop, reassign, outDb, outRgba, outIndex)");
+        return NULL;
+    }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    int32_t session = 0, stream0 = 0, streams = 0, n = 0, hop = 0; int64_t first = 0, count = 0; bool reassign = true;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[1], &session));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[2], &stream0));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[3], &streams));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[4], &first));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[5], &count));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[6], &n));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[7], &hop));
+    NAPI_OK_OR_RETURN(env, napi_coerce_to_bool(env, argv[8], &argv[8]));
+    NAPI_OK_OR_RETURN(env, napi_get_value_bool(env, argv[8], &reassign));
+    void *db = NULL, *rgba = NULL, *idx = NULL; size_t dlen = 0, rlen = 0, ilen = 0;
+    if (!get_typed(env, argv[9], napi_float32_array, &db, &dlen, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outDb must be a Float32Array or null"); return NULL; }
+    if (!get_typed(env, argv[10], napi_uint8_array, &rgba, &rlen, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outRgba must be a Uint8Array or null"); return NULL; }
+    if (!get_typed(env, argv[11], napi_uint8_array, &idx, &ilen, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "outIndex must be a Uint8Array or null"); return NULL; }
+    const int64_t C = out_columns(h, emspec_num_columns(count, n, hop));
+    /* (a range or a shape that yields no column: the library rejects the call with its message before it touches an output) */
+    if (streams >= 1 && C >= 1) {
+        const size_t cells = (size_t)streams * (size_t)C * (size_t)h->rows;
+        if ((db && dlen != cells) || (idx && ilen != cells) || (rgba && rlen != 4 * cells)) {
+            napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "every output must hold exactly streams*columns*rows cells (RGBA: x 4)");
+            return NULL;
+        }
+    }
+    emspec_out out; memset(&out, 0, sizeof(out));
+    out.db = (float*)db; out.rgba = (uint8_t*)rgba; out.index = (uint8_t*)idx;
+    int rc = emspec_audio_batch(h->e, session, stream0, streams, first, count, n, hop, reassign ? 1 : 0, &out);
+    if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
+    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int64(env, C, &r));
+    return r;
+}
+
 static napi_value WaveOf(napi_env env, napi_callback_info info) {
     size_t argc = 7; napi_value argv[7];
     NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -1622,6 +1720,10 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"setLiveHistory", NULL, SetLiveHistory, NULL, NULL, NULL, napi_default, NULL},
         {"liveHistory", NULL, LiveHistory, NULL, NULL, NULL, napi_default, NULL},
         {"historyView", NULL, HistoryView, NULL, NULL, NULL, napi_default, NULL},
+        {"setLiveAudio", NULL, SetLiveAudio, NULL, NULL, NULL, napi_default, NULL},
+        {"liveAudio", NULL, LiveAudio, NULL, NULL, NULL, napi_default, NULL},
+        {"audioView", NULL, AudioView, NULL, NULL, NULL, napi_default, NULL},
+        {"audioBatch", NULL, AudioBatch, NULL, NULL, NULL, napi_default, NULL},
         {"positionHz", NULL, PositionHz, NULL, NULL, NULL, napi_default, NULL},
         {"setRowEdges", NULL, SetRowEdges, NULL, NULL, NULL, napi_default, NULL},
         {"getRowEdges", NULL, GetRowEdges, NULL, NULL, NULL, napi_default, NULL},

@@ -109,6 +109,46 @@ class Engine {
     return out;
   }
 
+  /**
+   * Live audio history (emspec_set_live_audio / emspec_live_audio / emspec_audio_view / emspec_audio_batch, DESIGN.md §3.15):
+   * the engine keeps the last `samples` samples every live call was fed, per stream, on the device - what a renderer needs when
+   * FFT Size, Smoothing or Enhanced / Natural changes and the scroll-back image has to be computed again (Frequency Scale and
+   * Low-End Boost: INTEGRATION.md).  Set it before a session's first samples (or after reset()); 0 clears.
+   * liveAudio(stream) -> {end, first}: the samples of the stream that were stored and the first one still held, or null.
+   * audioView({stream0 = 0, streams = all from stream0, firstSample, count}) -> Float32Array(streams * count), bit for bit.
+   * reanalyse({stream0, streams, firstSample, count, fftSize, hop, reassign = true, want = ['db']}) ->
+   *   {columns, db: Float32Array(streams * columns * rows), rgba: Uint8Array(x 4), index: Uint8Array} (those named in `want`):
+   *   computeColumns of the held samples, at any fftSize / hop / reassign; honours setTimeReduce and the display settings.
+   * A single-stream engine addresses the session of computeSpectrogramColumn / pushSamples.
+   */
+  setLiveAudio(samples) { native.setLiveAudio(this._h, samples); }
+  liveAudio(stream = 0) {
+    const r = native.liveAudio(this._h, this._historySession(), stream);
+    return r ? { end: r[0], first: r[1] } : null;
+  }
+  audioView(opts) {
+    const stream0 = opts.stream0 | 0, streams = opts.streams === undefined ? this.streams - stream0 : opts.streams | 0;
+    const count = +opts.count;
+    const out = new Float32Array(Math.max(0, streams) * Math.max(0, count));
+    native.audioView(this._h, this._historySession(), stream0, streams, +opts.firstSample, count, out);
+    return out;
+  }
+  reanalyse(opts) {
+    const stream0 = opts.stream0 | 0, streams = opts.streams === undefined ? this.streams - stream0 : opts.streams | 0;
+    const count = +opts.count, want = opts.want || ['db'];
+    const full = Math.max(0, native.numColumns(count, opts.fftSize | 0, opts.hop | 0));
+    const columns = Math.max(0, native.reducedColumns(full, this.timeReduce));
+    const cells = Math.max(0, streams) * columns * this.rows;
+    const out = { columns };
+    if (want.includes('db')) out.db = new Float32Array(cells);
+    if (want.includes('rgba')) out.rgba = new Uint8Array(4 * cells);
+    if (want.includes('index')) out.index = new Uint8Array(cells);
+    native.audioBatch(this._h, opts.session === undefined ? this._historySession() : opts.session | 0, stream0, streams, +opts.firstSample,
+      count, opts.fftSize | 0, opts.hop | 0, opts.reassign === undefined ? true : !!opts.reassign, out.db || null, out.rgba || null,
+      out.index || null);
+    return out;
+  }
+
   /** Page-locked Float32Array / Uint8Array views for the live calls, (re)made when the shape changes. */
   _liveBlocks(fftSize, wantRgba) {
     const S = this.streams, R = this.rows;

@@ -946,6 +946,68 @@ int     emspec_history_view(emspec_engine* e, int32_t session, int32_t stream0, 
                             int32_t factor, int64_t groups, const emspec_view_map* map,
                             float* out_db, uint8_t* out_index, uint8_t* out_rgba);
 
+/*
+ * ---- Live audio history: a ring on the device of the samples the streaming calls were fed, W per
+ * stream, views that read a range back bit for bit, and a re-analysis that runs the batch kernels over a held range.  Serves the
+ * settings the live history above cannot follow because they change the analysis itself - "FFT Size", "Smoothing", the Enhanced
+ * / Natural switch (reassign), and, through emspec_reset, "Frequency Scale" and "Low-End Boost"  - without the
+ * host keeping every sample of every stream and pushing them over the bus again; [BUILD-DEFINED].  Off unless set; with it
+ * cleared every streaming call launches, allocates and writes exactly what it did before these entries.
+ *
+ * Samples are numbered per stream: sample a is the a-th sample the stream's session has received since the stream was
+ * (re)started.  Block forms (emspec_push_samples, _multi, _multires, _multiband, _pcm*): the stream's samples in the order
+ * pushed; a PCM session stores the decoded views' float samples, one ring per view stream.  Per-frame forms (emspec_column,
+ * emspec_columns, _multires, _multiband): frame j of a stream is taken to be samples [j hop, j hop + n), and each frame stores
+ * the samples the ring does not yet have - frame 0 whole, then each frame's last `hop`; the library does not check that frames
+ * overlap consistently, as it never has.
+ * Stored is what a launch has moved to the device.  A block that completes no frame only joins the host staging block (see
+ * emspec_push_samples_multi) and is stored by the launch that ingests it: `end` may trail the samples pushed by less than one
+ * frame before the first frame, and by less than `hop` after.  Flush calls store nothing.  Sample a lives in slot a mod W (any
+ * W in 1 .. 2^28; the per-stream stride of the allocation may be padded); after any call the ring of a stream holds
+ * [max(0, end - W), end); a launch that ingests more than W samples of a stream stores its last W.
+ *
+ * emspec_set_live_audio(e, W): W samples per stream for both sessions of the engine; 0 clears and frees (always allowed).
+ *   EMSPEC_ERR_INVALID_ARG: W outside 0 .. 2^28.  EMSPEC_ERR_STATE: W > 0 while either session has samples fed (emspec_reset
+ *   first).  The rings (streams x W x 4 bytes) are allocated by the first streaming call of a session, when its streams are
+ *   known: EMSPEC_ERR_OUT_OF_MEMORY on that call, before anything is fed; the session stays as it was.  emspec_reset empties
+ *   every ring; emspec_reset_stream empties that stream's ring and restarts its numbering, the other streams keep theirs.
+ * emspec_live_audio(e, session, stream, &first): the number of samples of the stream that were stored (`end`), and in *first
+ *   (may be NULL) the first sample held; -1 for a NULL engine, an unknown session or stream (a session that has not started
+ *   has no streams), or no audio history.  session: as for emspec_live_history.
+ *
+ * A view of streams [stream0, stream0 + streams): pcm[sv][i] = sample first_sample + i of stream stream0 + sv, bit for bit
+ * (NaN payloads and -0 are kept), i < count; layout [streams][stride] float32, stride >= count.
+ * Required: first_sample >= the first held sample and first_sample + count <= end, for every addressed stream - else
+ * EMSPEC_ERR_INVALID_ARG with a message naming the stream and its held range, nothing written.  Also EMSPEC_ERR_INVALID_ARG:
+ * count < 1, streams < 1, a stream range outside the session, a NULL output or one that is not 4-byte aligned, stride < count.
+ * EMSPEC_ERR_STATE: no audio history set, or a session that does not exist.  Every refusal leaves the engine usable.
+ * emspec_audio_view_device: pcm_dev is device memory at any 4-byte alignment, any stride; enqueues on hip_stream (NULL: the
+ *   default stream) behind the session's launches - every streaming call has synchronised before it returned - and does not
+ *   synchronise; later streaming calls are ordered behind the view.  emspec_audio_view: pcm is a host array, page-locked
+ *   (written in place) or pageable (staged through a page-locked block), as emspec_history_view's outputs; synchronises.
+ *
+ * emspec_audio_batch_device: emspec_audio_view_device of the range into an engine workspace [streams][count], followed by
+ *   emspec_batch_device(e, that, streams, count, n, hop, reassign, db_dev, rgba_dev, index_dev, hip_stream) on the same stream:
+ *   everything emspec_batch_device honours applies - emspec_set_time_reduce, emspec_set_display, the engine's current row
+ *   edges, colour law and colour map, its output layouts and its refusals; count < n is EMSPEC_ERR_INVALID_ARG.  n, hop and
+ *   reassign need not be the session's.  The live sessions are not disturbed: the call shares none of their buffers and
+ *   changes none of their counters.  The workspace is the engine's: a second re-analysis must be ordered behind the first.
+ * emspec_audio_batch: the same with host outputs in an emspec_out ([streams][columns][rows] of emspec_num_columns(count, n,
+ *   hop) columns, reduced by emspec_set_time_reduce): device blocks grown in the engine, plain copies out, synchronises.  No
+ *   pipeline: the picture is one window's worth.
+ */
+int     emspec_set_live_audio(emspec_engine* e, int64_t samples /* W per stream; 0 clears */);
+int64_t emspec_live_audio(const emspec_engine* e, int32_t session, int32_t stream, int64_t* first_sample /* may be NULL */);
+int     emspec_audio_view_device(emspec_engine* e, int32_t session, int32_t stream0, int32_t streams, int64_t first_sample,
+                                 int64_t count, float* pcm_dev, int64_t stride, void* hip_stream);
+int     emspec_audio_view(emspec_engine* e, int32_t session, int32_t stream0, int32_t streams, int64_t first_sample,
+                          int64_t count, float* pcm, int64_t stride);
+int     emspec_audio_batch_device(emspec_engine* e, int32_t session, int32_t stream0, int32_t streams, int64_t first_sample,
+                                  int64_t count, int32_t n, int32_t hop, int32_t reassign,
+                                  float* db_dev, uint8_t* rgba_dev, uint8_t* index_dev, void* hip_stream);
+int     emspec_audio_batch(emspec_engine* e, int32_t session, int32_t stream0, int32_t streams, int64_t first_sample,
+                           int64_t count, int32_t n, int32_t hop, int32_t reassign, const emspec_out* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,8 @@ S streams x one hop per call, N = 4096 / hop 256 (BASELINE configs[2] in its liv
 median / p90 microseconds per call and columns/s.  usage: live_rate.py [S] [calls] [filter,filter,...] [overlay,overlay,...]
 (filters: every token must appear in the variant's label, e.g. FAST,samples,pinned,out=db; an empty string: no filter)
 overlays: which overlay settings each variant runs with, in turn - none (the default), peaks (emspec_set_live_peaks, k = 8,
-min_db = -60), wave (emspec_set_live_wave), both.  Their arrays are page-locked or pageable as the other buffers are.
+min_db = -60), wave (emspec_set_live_wave), both, audio (emspec_set_live_audio, W = 2^19 samples per stream).  Their arrays are
+page-locked or pageable as the other buffers are.
 EMSPEC_LIB=path times another build of the library (the parent commit's, which has no overlays: `none` only) in the same
 session, as tools/ab_kernel.py does; EMSPEC_MULTIRES=1 times the 16384 / 4096 multi-resolution session (split row 512) instead."""
 import os
@@ -63,6 +64,8 @@ def main():
                             e.set_live_peaks(8, -60.0, buf((S * 8 * 2,), np.float32))
                         if overlay in ("wave", "both"):
                             e.set_live_wave(buf((S * 2,), np.float32))
+                        if overlay == "audio":
+                            e.set_live_audio(1 << 19)
                         if form == "frames":
                             fin = buf((S, n), np.float32)
                             db = buf((S, R), np.float32) if "db" in outs else None
