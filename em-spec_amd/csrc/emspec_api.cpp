@@ -107,8 +107,12 @@ int get_band_plan(emspec_engine* e, int n, int row0, int rows, Plan** out) {
     return EMSPEC_OK;
 }
 
+// log_rows: the configured log axis, wide enough in every row for the float32 log2 hint (a narrower one is searched)
+static bool plan_log_rows(const emspec_engine* e, const Plan& p) {
+    return e->custom_edges_hz.empty() && hint_rows_ok(p.h_ebin64.front(), p.h_ebin64.back(), p.rows);
+}
 static PlanScalars scalars_of(const emspec_engine* e, const Plan& p, int hop, int reassign) {
-    return plan_scalars(e->cfg, p.rows, e->custom_edges_hz.empty(), p.n, hop, reassign);
+    return plan_scalars(e->cfg, p.rows, plan_log_rows(e, p), p.n, hop, reassign);
 }
 PlanDev plan_dev(const emspec_engine* e, const Plan& p, int hop, int reassign) {
     const PlanScalars c = scalars_of(e, p, hop, reassign);
@@ -592,8 +596,8 @@ int emspec_debug_occupy(emspec_engine* e, int32_t groups, int32_t usec, void* hi
     return EMSPEC_OK;
 }
 
-// Diagnostic (tests only): evaluate the fused kernels' hinted row lookup and the generic
-// binary search on `count` host values of k-hat for fft size n.
+// Diagnostic (tests only): evaluate the fused kernels' row lookup as the plan of fft size n would run it (hinted, or searched
+// where hint_rows_ok refuses the axis) and the generic binary search on `count` host values of k-hat.
 int emspec_debug_row_lookup(emspec_engine* e, int32_t n, const float* kh, int64_t count, int32_t* out_hint,
                             int32_t* out_exact) {
     if (!e || !kh || !out_hint || !out_exact || count < 0) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument");
@@ -607,7 +611,7 @@ int emspec_debug_row_lookup(emspec_engine* e, int32_t n, const float* kh, int64_
     if (r == hipSuccess) r = hipMalloc(&d_a, count * 4 + 4);
     if (r == hipSuccess) r = hipMalloc(&d_b, count * 4 + 4);
     if (r == hipSuccess) r = hipMemcpyAsync(d_kh, kh, count * 4, hipMemcpyHostToDevice, e->stream);
-    if (r == hipSuccess) r = launch_row_lookup_probe(p->d_ebin, e->cfg.rows, d_kh, count, d_a, d_b, e->stream);
+    if (r == hipSuccess) r = launch_row_lookup_probe(p->d_ebin, e->cfg.rows, plan_log_rows(e, *p) ? 1 : 0, d_kh, count, d_a, d_b, e->stream);
     if (r == hipSuccess) r = hipMemcpyAsync(out_hint, d_a, count * 4, hipMemcpyDeviceToHost, e->stream);
     if (r == hipSuccess) r = hipMemcpyAsync(out_exact, d_b, count * 4, hipMemcpyDeviceToHost, e->stream);
     if (r == hipSuccess) r = hipStreamSynchronize(e->stream);

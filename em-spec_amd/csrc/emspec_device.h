@@ -19,7 +19,7 @@ struct PlanDev {
     const float2* tw;    // twiddle table, N/2 entries: (cos, -sin)(2*pi*q/N); tw[N/4] == (0,-1) exactly
     const float* ebin;   // row edges in DFT-bin units, rows+1 entries, strictly increasing
     int rows;            // R
-    int log_rows;        // 1: edges are log-spaced (hinted lookup is valid); 0: arbitrary monotone table (binary search)
+    int log_rows;        // 1: edges are log-spaced and wide enough for the hint (hint_rows_ok); 0: any monotone table (binary search)
     int D;               // max |column shift| = ceil(N/(2*hop)) (0 when reassign is off)
     int reassign;        // 0/1
     int hop;
@@ -202,10 +202,12 @@ __device__ __forceinline__ int row_lookup(const float* eb, int R, int wtop, floa
 }
 
 // Row lookup with a log2 hint and an exact +-1 correction against the table: same result as
-// the binary search.  The hint is off by at most one row (v_log_f32 error and the float32
-// rounding of the edges are both << a row, which is >= 0.67 % wide); the two exact compares
-// against the table decide.  Verified around every edge by tests/test_gpu_parity.py
-// (emspec_debug_row_lookup).  Garbage / NaN inputs map to row -1 through the range test.
+// the binary search.  The hint is off by less than one row on every axis the host hands over
+// with log_rows = 1 (emspec_tables.h: hint_rows_ok bounds the v_log_f32 and float32 rounding
+// errors below a quarter of a row; a narrower axis comes with log_rows = 0 and is searched);
+// the two exact compares against the table decide.  Verified around every edge by
+// tests/test_gpu_parity.py and tests/test_gpu_axes.py (emspec_debug_row_lookup).  Garbage /
+// NaN inputs map to row -1 through the range test.
 struct HintLookup {
     const float* eb; int R; float e0, eR, l2e0, rscale; int wtop;   // wtop > 0: table is not log-spaced, search it
     __device__ __forceinline__ void init(const float* table, const float* gtable, int rows, int log_rows = 1) {

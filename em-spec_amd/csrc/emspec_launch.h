@@ -264,7 +264,7 @@ Route fused_route(int n, int hop, int rows, int reassign);
 bool fused_supported(int n, int hop, int rows, int reassign);
 int device_cus();           // compute units of the current device
 #ifdef EMSPEC_DIAG          // diagnostic build only (libemspec_diag.so, include/emspec_debug.h)
-hipError_t launch_row_lookup_probe(const float* ebin, int rows, const float* kh, int64_t count, int32_t* out_hint,
+hipError_t launch_row_lookup_probe(const float* ebin, int rows, int log_rows, const float* kh, int64_t count, int32_t* out_hint,
                                    int32_t* out_exact, hipStream_t st);
 hipError_t launch_occupy(int groups, int usec, unsigned* sink, hipStream_t st);
 hipError_t launch_recip_probe(const float* d, int64_t count, float* out_short, float* out_ieee, hipStream_t st);

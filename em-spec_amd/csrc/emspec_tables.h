@@ -115,9 +115,15 @@ inline double edge_hz(const Axis& a, int r) {
                        : (double)a.fmin_hz * spec_pow((double)a.fmax_hz / (double)a.fmin_hz, (double)r / (double)a.rows);
 }
 // Row edges in DFT-bin units (DESIGN.md §3 "Tables"): binary64, and the float32 table is that one rounded once per entry.
+// The axis ends at Nyquist by construction: e[R] = min(e[R], n / 2).  fmax <= sample_rate / 2 is enforced by emspec_create, but
+// fmin * (fmax / fmin) * n / fs rounds twice and can come out an ulp above n / 2 (8 kHz from 30 Hz to 4 kHz: + 4.5e-13 at
+// n = 4096); the Nyquist bin, whose k-hat is exactly n / 2, would then belong to row R - 1 in binary64 and to no row in float32.
+// With the clamp k-hat = n / 2 >= e[R] in both precisions, so no route of either mode accumulates that bin.  (Custom edges satisfy
+// it already: hz <= 0.5f * fs is checked, hz * n is exact in double and the division is monotone.)
 inline std::vector<double> edges_bin64(const Axis& a, int n) {
     std::vector<double> e((size_t)a.rows + 1);
     for (int r = 0; r <= a.rows; ++r) e[r] = edge_hz(a, r) * (double)n / (double)a.sample_rate;
+    e[a.rows] = std::min(e[a.rows], (double)n * 0.5);
     return e;
 }
 inline std::vector<float> edges_bin32(const std::vector<double>& e64) { return std::vector<float>(e64.begin(), e64.end()); }
@@ -135,6 +141,31 @@ inline const char* edges_error(const std::vector<double>& e) { return strictly_i
 inline bool low_share_ok(const Axis& a, int row) {
     const double share = edge_hz(a, row) / ((double)a.sample_rate * 0.5);
     return share <= 0.06;
+}
+
+// May the FAST kernels' log2 row hint (emspec_device.h: HintLookup) serve a log axis from e0 to eR bins in `rows` rows?  The hint
+// h = (v_log_f32(k) - l2e0) * rscale, l2e0 = log2f(e0), rscale = rows / (log2f(eR) - l2e0), is corrected by one row either way
+// against the table, so it must lie within one row of k's position.  With u = 2^-23 (one float32 ulp is at most u |x|),
+// L = max(1, |log2 e0|, |log2 eR|) the largest |log2| of a k on the axis, W = log2(eR / e0) <= 2 L and rho = rows / W rows per
+// unit of log2, its error in rows is at most
+//     rho * (u L      v_log_f32: 1 ulp, the ISA documentation's figure
+//          + u L      l2e0: log2f is within 1 ulp
+//          + u L      the difference, rounded once: u W / 2
+//          + 2 u L    rscale's denominator: two logarithms and a rounding, relative to W, on a hint of at most `rows` rows
+//          + 2 u)     e0 and eR are the float32 table's ends, and an edge sits half an ulp from its log-spaced place: 1.44 u / 2 each
+//     + 2 u rows      the quotient rscale and the product, rounded once each: u / 2 of at most `rows`, doubled
+//   <= u (8 rho L + 2 rows),
+// which must stay below 1 / 4: a safety factor of 4, since the instruction's figure is documented, not measured here.  k off the
+// axis by d in log2 adds d u to the error and d rho to the distance, so the clamped hint still ends on the first or last row.
+// The default axis has 8 rho L + 2 rows = 1.3e4 at 1024 rows, one octave in 4096 rows 4.3e5; the bound, 2^21, is reached near
+// 20,000 rows per unit of log2 (a row 5e-5 wide, 290 float32 ulp at 8192 bins).  Narrower axes are searched (PlanDev::log_rows
+// = 0, the generic per-bin core): the same rows, slower.  spec_log2: the same answer on every host.
+inline bool hint_rows_ok(double e0, double eR, int rows) {
+    if (!(e0 > 0.0) || !(eR > e0) || rows < 1) return false;
+    const double l0 = spec_log2(e0), lR = spec_log2(eR);
+    const double L = std::max(1.0, std::max(std::fabs(l0), std::fabs(lR)));
+    const double rho = (double)rows / (lR - l0);
+    return 8.0 * rho * L + 2.0 * (double)rows <= 2097152.0;   // 2^23 / 4
 }
 
 // Twiddles tw[q] = (cos, -sin)(2 pi q / n), q < n / 2, interleaved.  The first quarter is the caller's; this writes the second by

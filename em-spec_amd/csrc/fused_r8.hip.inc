@@ -23,8 +23,9 @@
 //    owns bins 4g..4g+3): a log-frequency row is up to ~12 bins wide, and lanes that share a cell in the same accumulate
 //    instruction serialise it (one LDS round each).
 //  - The Nyquist bin k = N/2 is not visited: Y[N/2+1] = conj Y[N/2-1] makes its k-shift exactly 0 in this arithmetic, so
-//    k-hat = N/2 >= ebin[R] (fmax <= fs/2 is enforced by emspec_create) and it can never reach the histogram.  Skipping it
-//    keeps the 8 waves of a frame at equal work.  (frames_kernel still reports it in the parity dump.)
+//    k-hat = N/2 >= ebin[R] (emspec_tables.h: edges_bin64 ends the axis at min(e[R], N/2), in binary64 and so in float32; that
+//    fmax <= fs/2 is enforced by emspec_create is not enough, the unclamped binary64 edge can round an ulp above N/2) and it
+//    can never reach the histogram.  Skipping it keeps the 8 waves of a frame at equal work.  (frames_kernel still reports it in the parity dump.)
 //  - The thread index is laundered once per iteration (asm volatile("" : "+v"(tt))): every LDS address is then recomputed
 //    (1-3 VALU each) instead of being hoisted out of the frame loop, which would pin ~50 VGPRs.
 //  - FAST (template parameter of every kernel here): reassignment ON and a log-spaced edge table are known at compile time

@@ -12,8 +12,8 @@
 extern "C" {
 #endif
 
-/* Evaluate the hinted row lookup (fused/generic kernels) and the binary search on `count`
- * host values of k-hat for fft size n: out_hint[i], out_exact[i] = row or -1. */
+/* Evaluate the row lookup of the fused/generic kernels as the plan of fft size n runs it (the log2 hint, or the search
+ * on an axis too narrow for it) and the binary search on `count` host values of k-hat: out_hint[i], out_exact[i] = row or -1. */
 int emspec_debug_row_lookup(emspec_engine* e, int32_t n, const float* kh, int64_t count,
                             int32_t* out_hint, int32_t* out_exact);
 

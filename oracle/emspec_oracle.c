@@ -118,15 +118,19 @@ double eo_spec_pow(double ratio, double x) {
 }
 
 static void make_edges64(const eo_cfg* c, double* e) {
-    /* row edges expressed in DFT-bin units (Hz * N / fs): custom table, or log-spaced */
+    /* row edges expressed in DFT-bin units (Hz * N / fs): custom table, or log-spaced.  The axis ends at Nyquist by
+     * construction, e[R] = min(e[R], n / 2): the two roundings of fmin * ratio * n / fs can leave the top edge an ulp
+     * above n / 2, and the Nyquist bin (k-hat exactly n / 2) belongs to no row in either precision */
+    const double nyq = (double)c->n * 0.5;
     if (g_custom_edges && g_custom_count == c->rows + 1) {
         for (int r = 0; r <= c->rows; ++r) e[r] = (double)g_custom_edges[r] * (double)c->n / (double)c->sample_rate;
-        return;
+    } else {
+        double ratio = (double)c->fmax_hz / (double)c->fmin_hz;
+        for (int r = 0; r <= c->rows; ++r)
+            e[r] = (double)c->fmin_hz * eo_spec_pow(ratio, (double)r / (double)c->rows) *
+                   (double)c->n / (double)c->sample_rate;
     }
-    double ratio = (double)c->fmax_hz / (double)c->fmin_hz;
-    for (int r = 0; r <= c->rows; ++r)
-        e[r] = (double)c->fmin_hz * eo_spec_pow(ratio, (double)r / (double)c->rows) *
-               (double)c->n / (double)c->sample_rate;
+    if (e[c->rows] > nyq) e[c->rows] = nyq;
 }
 /* float64 row edges in DFT-bin units (rows+1): what eo_frames_f64 and the exact mode (emspec_exact.c) compare against */
 int eo_edges64(const eo_cfg* c, double* e) {

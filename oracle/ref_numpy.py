@@ -20,7 +20,9 @@ def windows(n):
 
 def edges_bins(n, rows, fs, fmin, fmax):
     r = np.arange(rows + 1, dtype=np.float64)
-    return fmin * (fmax / fmin) ** (r / rows) * n / fs
+    e = fmin * (fmax / fmin) ** (r / rows) * n / fs
+    e[-1] = min(e[-1], n / 2.0)      # the axis ends at Nyquist by construction
+    return e
 
 
 def reassign_frames(pcm, n, hop, frame0, nframes, rows=1024, fs=48000.0, fmin=20.0, fmax=24000.0,

@@ -122,15 +122,21 @@ void exact_frames_case(int n, int rows, int S, long long nframes, int plain) {
 // axis: 0 the configured log axis (20 Hz .. 24 kHz at 48 kHz), 1 linear edges, 2 warped edges (low_end_boost 0.5), of axis_rows
 // rows; the plan serves rows [row0, row0 + rows) of it (a band plan when row0 > 0 or rows < axis_rows).  parked / records:
 // EMSPEC_EXACT_PARKED / EMSPEC_EXACT_RECORDS.
-void exact_case(int n, int hop, int reassign, int rows, int row0, int axis_rows, int axis, int parked, int records) {
+// A case may carry a log axis of its own, log_axis = {sample_rate, fmin, fmax} (tests/axis_cases.py): its record names the three
+// beside the other fields of the case, with "axis": 0.
+void exact_case(int n, int hop, int reassign, int rows, int row0, int axis_rows, int axis, int parked, int records,
+                const float* log_axis = nullptr) {
     std::vector<float> hz(axis_rows + 1);
     if (axis == 1) for (int r = 0; r <= axis_rows; ++r) hz[r] = 20.0f + (24000.0f - 20.0f) * (float)r / (float)axis_rows;
     if (axis == 2) warped_edges_hz(axis_rows, 20.0f, 24000.0f, 0.5f, 1.0f, hz.data());
-    const Axis ax{axis_rows, 48000.0f, 20.0f, 24000.0f, axis ? hz.data() : nullptr};
+    const Axis ax = log_axis ? Axis{axis_rows, log_axis[0], log_axis[1], log_axis[2], nullptr}
+                             : Axis{axis_rows, 48000.0f, 20.0f, 24000.0f, axis ? hz.data() : nullptr};
     const int D = latency(n, hop, reassign);
     open_record("exact");
-    printf("\"case\": {\"n\": %d, \"hop\": %d, \"reassign\": %d, \"rows\": %d, \"row0\": %d, \"axis_rows\": %d, \"axis\": %d, \"parked\": %d, \"records\": %d}, ",
+    printf("\"case\": {\"n\": %d, \"hop\": %d, \"reassign\": %d, \"rows\": %d, \"row0\": %d, \"axis_rows\": %d, \"axis\": %d, \"parked\": %d, \"records\": %d",
            n, hop, reassign, rows, row0, axis_rows, axis, parked, records);
+    if (log_axis) printf(", \"sample_rate\": %g, \"fmin\": %g, \"fmax\": %g", log_axis[0], log_axis[1], log_axis[2]);
+    printf("}, ");
     static const char* const names[3] = {"exact_lr", "exact_parked", "exact_records"};
     int step, rl, slots = 0, uses = -1, lr_refused = 0;
     size_t lds = 0;
@@ -363,6 +369,18 @@ int main() {
     for (int rows : sweep) exact_case(4096, 256, 1, rows, 0, rows, 2, 0, 0);
     for (int rows : {2052, 4092}) exact_case(4096, 256, 1, rows, 0, rows, 0, 0, 0);
     for (int rows : {68, 1020}) exact_case(4096, 256, 1, rows, 0, rows, 2, 1, 0);   // the parked kernel where the switch asks for it
+
+    // ---- other sample rates and log axes: the cases of tests/axis_cases.py (appended).  The FAST route does not look at the axis:
+    // only the shapes that have no record at 1024 rows yet.  The EXACT route does, through the low-share rule ----
+    fast_case(4096, 300, 1024, 1, 0);
+    const float axes[6][3] = {{44100.0f, 20.0f, 22050.0f}, {8000.0f, 30.0f, 4000.0f}, {32000.0f, 55.0f, 16000.0f},
+                              {96000.0f, 20.0f, 20000.0f}, {192000.0f, 10.0f, 96000.0f}, {48000.0f, 2000.0f, 4000.0f}};
+    const int axis_shapes[5][2] = {{4096, 256}, {2048, 128}, {1024, 256}, {8192, 512}, {16384, 512}};
+    for (const auto& a : axes) {
+        for (const auto& s : axis_shapes)
+            for (int rows : {1024, 68}) exact_case(s[0], s[1], 1, rows, 0, rows, 0, 0, 0, a);
+        exact_case(4096, 256, 1, 4092, 0, 4092, 0, 0, 0, a);
+    }
     printf("\n]\n");
     return 0;
 }

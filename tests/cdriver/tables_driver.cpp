@@ -7,6 +7,7 @@
 // float32 arguments are given as the hex of their bits (f:), so nothing depends on how a decimal string is parsed.
 //   twiddles N
 //   edges N rows f:sample_rate f:fmin f:fmax [file of rows + 1 raw float32 Hz edges]
+//   hint N rows f:sample_rate f:fmin f:fmax     hint_rows_ok of the log axis' table, its ends, and whether the float32 edges serve
 //   pow d:ratio R                       spec_pow(ratio, r / R), r = 0 .. R
 //   palette | colormap f:brightness | warped rows f:fmin f:fmax f:boost f:scale
 //   scalars N hop reassign rows f:sample_rate f:fmin f:fmax f:gain f:db_top f:db_range f:gate_db f:power_floor
@@ -73,6 +74,15 @@ int main(int argc, char** argv) {
         line("low_share_ok", low);
         const char *w32 = edges_error(e32), *w64 = edges_error(e64);
         printf("error32 %s\nerror64 %s\n", w32 ? w32 : "-", w64 ? w64 : "-");
+    } else if (cmd == "hint" && argc == 7) {
+        const int n = atoi(argv[2]);
+        emspec_config c{};
+        c.rows = atoi(argv[3]), c.sample_rate = f32_arg(argv[4]), c.fmin_hz = f32_arg(argv[5]), c.fmax_hz = f32_arg(argv[6]);
+        const std::vector<double> e64 = edges_bin64(axis_of(c, {}), n);
+        line("ok", hint_rows_ok(e64.front(), e64.back(), c.rows) ? 1 : 0);
+        line("e0", e64.front()), line("eR", e64.back());
+        const char* w32 = edges_error(edges_bin32(e64));
+        printf("error32 %s\n", w32 ? w32 : "-");
     } else if (cmd == "pow" && argc == 4) {
         const double ratio = f64_arg(argv[2]);
         const int R = atoi(argv[3]);

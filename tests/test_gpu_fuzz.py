@@ -80,3 +80,25 @@ def test_fuzz_slice_exact_mode_any_rows():
 @pytest.mark.timeout(900)
 def test_fuzz_slice_live_multi_stream_any_rows():
     _run("fuzz_live.py", 20, 614, ANY_ROWS)
+
+
+# ---- the batch, EXACT and live tools with the sample rate and the axis drawn too (EMSPEC_FUZZ_RATES=any: 8 .. 96 kHz, fmax at and
+# below the Nyquist frequency, fmin 30 and 55 Hz among the others where the binary64 top edge would round above N / 2 unclamped).
+# New seeds; every slice above keeps its seed and its cases.
+ANY_RATES = {"EMSPEC_FUZZ_RATES": "any"}
+
+
+@pytest.mark.timeout(900)
+def test_fuzz_slice_float32_shapes_any_rates():
+    _run("fuzz_parity.py", 40, 711, ANY_RATES)
+
+
+@pytest.mark.timeout(900)
+def test_fuzz_slice_exact_mode_any_rates():
+    out = _run("fuzz_exact.py", 40, 713, {"EMSPEC_FUZZ_DIAG": "1", **ANY_RATES})
+    assert "vs the independent float64 method: 0 mismatches" in out, out[-1500:]
+
+
+@pytest.mark.timeout(900)
+def test_fuzz_slice_live_multi_stream_any_rates():
+    _run("fuzz_live.py", 15, 714, ANY_RATES)

@@ -18,14 +18,16 @@ import subprocess
 import numpy as np
 import pytest
 
+import axis_cases as A
 import oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 SIZES = (256, 512, 1024, 2048, 4096, 8192, 16384)
 ROWS = (64, 1024, 4096)
-# (sample_rate, fmin, fmax): the default axis, and a narrower one at another rate
-AXES = ((48000.0, 20.0, 24000.0), (44100.0, 30.0, 20000.0))
+# (sample_rate, fmin, fmax): the default axis, a narrower one at another rate, and one whose unclamped binary64 top edge rounds
+# above N / 2 (tests/axis_cases.py: tel)
+AXES = ((48000.0, 20.0, 24000.0), (44100.0, 30.0, 20000.0), (8000.0, 30.0, 4000.0))
 WARPED = (1024, 20.0, 24000.0, 2.0, 1.6)   # the custom axis of the GPU tests (test_gpu_exact.py, test_gpu_sizes.py)
 
 
@@ -100,7 +102,8 @@ def _edge_cases(warped):
 
 def test_edges_are_the_bit_models(driver, warped, tmp_path):
     """float32 edges: oracle.tables; binary64 edges: oracle.edges64; the Hz value of every edge and the 6 % axis test of the EXACT
-    mode's no-parking kernel restated here.  49 cases: every N, three row counts on two log axes, and the custom axis."""
+    mode's no-parking kernel restated here.  70 cases: every N, three row counts on three log axes, and the custom axis.  The
+    top edge is min(e[R], N / 2): the Hz value of the last edge is fmax itself, its bin value never exceeds N / 2."""
     path = tmp_path / "warped.f32"
     warped.tofile(path)
     count = 0
@@ -123,8 +126,13 @@ def test_edges_are_the_bit_models(driver, warped, tmp_path):
             hz = custom.astype(np.float64)
         assert same_bits(as_f64(out["hz"]), hz), case
         assert out["low_share_ok"].split() == ["1" if h / (float(F(sr)) * 0.5) <= 0.06 else "0" for h in hz], case
+        raw = hz * float(n) / float(F(sr))
+        assert same_bits(want64[:-1], raw[:-1]) and want64[-1] == min(raw[-1], n / 2), case
+        if custom is None and hi == sr / 2:
+            assert want64[-1] == n / 2 and want32[-1] == F(n / 2), case
         count += 1
-    assert count == 49
+    assert count == 70
+    assert A.raw_top_edge("tel", 4096) > 2048.0      # the clamp decides on that axis
 
 
 def _spec_pow(ratio, x):
@@ -213,3 +221,72 @@ def test_collapsed_edges_are_reported_not_crashed_on(driver, tmp_path):
     assert "not strictly increasing in float32" in out["error32"]
     want64 = "-" if np.all(np.diff(as_f64(out["e64"])) > 0) else "row edges are not strictly increasing"
     assert out["error64"] == want64
+
+
+# ---- the row hint of the FAST kernels: hint_rows_ok (emspec_tables.h) ----------------------------------------------------------
+
+def _hint(driver, n, rows, axis):
+    out = driver("hint", n, rows, *map(f32, axis))
+    return int(out["ok"]), float(as_f64(out["e0"])[0]), float(as_f64(out["eR"])[0]), out["error32"]
+
+
+@pytest.fixture(scope="module")
+def narrowest(driver):
+    """n -> the largest float32 fmin for which 4096 rows up to 24 kHz at 48 kHz keep the hint, by bisection on the predicate."""
+    found = {}
+    for n in A.PROBE_SIZES:
+        lo, hi = F(1000.0), F(23990.0)
+        assert _hint(driver, n, A.NARROW_ROWS, (48000.0, lo, 24000.0))[0] == 1 and _hint(driver, n, A.NARROW_ROWS, (48000.0, hi, 24000.0))[0] == 0
+        while np.nextafter(lo, F(np.inf)) < hi:
+            mid = F(0.5 * (float(lo) + float(hi)))
+            if _hint(driver, n, A.NARROW_ROWS, (48000.0, mid, 24000.0))[0]:
+                lo = mid
+            else:
+                hi = mid
+        found[n] = (float(lo), float(hi))
+    return found
+
+
+def test_hint_predicate_on_both_sides_of_its_bound(driver, narrowest):
+    """The predicate is its formula (restated in axis_cases.hint_value with libm's log2) away from the bound, and monotone up to
+    it: the last hinted float32 fmin and its neighbour lie within 1e-6 of the bound on either side."""
+    for n, (last, first_not) in narrowest.items():
+        for fmin, want in ((last, 1), (first_not, 0)):
+            ok, e0, eR, err = _hint(driver, n, A.NARROW_ROWS, (48000.0, fmin, 24000.0))
+            v = A.hint_value(e0, eR, A.NARROW_ROWS) / A.HINT_BOUND
+            assert ok == want and err == "-" and abs(v - 1.0) < 1e-6 and (v <= 1.0) == bool(want), (n, fmin, v)
+        # the axes the GPU probe uses: within 1 % of the bound on the hinted side, and past it
+        ok, e0, eR, err = _hint(driver, n, A.NARROW_ROWS, A.NARROW_HINTED[n])
+        assert ok == 1 and err == "-" and 0.99 < A.hint_value(e0, eR, A.NARROW_ROWS) / A.HINT_BOUND < 1.0, n
+        for axis, rows in A.NARROW_SEARCHED:
+            ok, e0, eR, err = _hint(driver, n, rows, axis)
+            assert ok == 0 and err == "-" and A.hint_value(e0, eR, rows) > 1.1 * A.HINT_BOUND, (n, axis)   # emspec_create takes it: searched
+
+
+def test_ordinary_axes_stay_hinted(driver):
+    """The default axis, the six axes of tests/axis_cases.py and one octave below Nyquist, at 64 .. 4096 rows and every N: the
+    plan's log_rows is 1 as before, with a margin of at least 4 below the bound."""
+    axes = [(48000.0, 20.0, 24000.0), (48000.0, 12000.0, 24000.0), *A.AXES.values()]
+    for axis in axes:
+        for n in (256, 1024, 4096, 16384):
+            for rows in (64, 68, 1024, 4092, 4096):
+                ok, e0, eR, err = _hint(driver, n, rows, axis)
+                assert ok == 1 and err == "-" and A.hint_value(e0, eR, rows) < 0.25 * A.HINT_BOUND, (axis, n, rows)
+
+
+def test_hint_model_equals_bisection_on_the_narrowest_hinted_axis(driver, narrowest):
+    """A numpy float32 model of HintLookup::row_signed_log with the logarithm moved by up to +-4 float32 ulp (the bound budgets
+    1 for v_log_f32), on the narrowest hinted axis of each n: every edge, its neighbours at 1 and 2 ulp and the row midpoints
+    land in bisection's row.  The same model on the axes past the bound does give wrong rows: the probe can fail."""
+    for n, (fmin, _) in narrowest.items():
+        eb = as_f32(driver("edges", n, A.NARROW_ROWS, f32(48000.0), f32(fmin), f32(24000.0))["e32"])
+        kh = A.probe_values(eb)
+        want = A.bisect_rows(eb, kh)
+        assert want.min() == -1 and want.max() == A.NARROW_ROWS
+        for ulps in range(-4, 5):
+            got = A.lookup_model(eb, kh, ulps)
+            assert np.array_equal(got, want), (n, fmin, ulps, int(np.sum(got != want)))
+    axis, rows = A.NARROW_SEARCHED[0]
+    eb = as_f32(driver("edges", 16384, rows, *map(f32, axis))["e32"])
+    kh = A.probe_values(eb)
+    assert any(not np.array_equal(A.lookup_model(eb, kh, u), A.bisect_rows(eb, kh)) for u in (-1, 0, 1))

@@ -5,7 +5,10 @@ shape, rows, stream count, feeding form, block sizes (sub-hop blocks, blocks lon
 pageable buffers, and a mid-session restart of one stream.  EXACT mode: dB bits and RGBA array_equal; float32 mode: dB within
 8.7e-4, RGBA differing on < 1e-3 of the cells.
 usage: python tools/fuzz_live.py [cases] [seed]     (needs an MI355X; prints one line per failure)
-EMSPEC_FUZZ_ROWS=any in the environment draws the row count from every multiple of 4 (the default draw keeps its cases)."""
+EMSPEC_FUZZ_ROWS=any in the environment draws the row count from every multiple of 4 (the default draw keeps its cases).
+EMSPEC_FUZZ_RATES=any draws the sample rate from 8, 32, 44.1, 48 and 96 kHz and the axis with it: fmax from the Nyquist frequency
+(twice as likely), 3/8 and 1/6 of the rate, fmin from 20, 35, 80 Hz and, when fmax is the Nyquist frequency, 30 and 55 Hz too (axes whose binary64
+top edge would round above N / 2 without the clamp of emspec_tables.h).  Drawn after everything else: the default draw keeps its cases."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "em-spec_amd"), os.path.join(ROOT, "oracle")]
@@ -17,6 +20,7 @@ cases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 rng = np.random.default_rng(seed)
 ANY_ROWS = os.environ.get("EMSPEC_FUZZ_ROWS") == "any"   # rows: any multiple of 4 instead of the list below (the default draw is untouched)
+ANY_RATES = os.environ.get("EMSPEC_FUZZ_RATES") == "any"   # sample_rate / fmin / fmax from the lists of the docstring
 fails = 0
 t0 = time.time()
 
@@ -55,9 +59,13 @@ for ci in range(cases):
     cut = int(rng.integers(1, frames - D - 2)) if who >= 0 else 0                                   # ... when frame `cut` is due
     kw = dict(rows=rows, fmin_hz=float(rng.choice([20.0, 35.0])), fmax_hz=float(rng.choice([24000.0, 16000.0])),
               gain=float(rng.choice([1.0, 3.5])), db_range=float(rng.choice([80.0, 58.0])), gate_db=float(rng.choice([-80.0, -65.0])))
+    if ANY_RATES:   # another sample rate and an axis that fits it (after every other draw of the configuration)
+        sr = float(rng.choice([8000.0, 32000.0, 44100.0, 48000.0, 96000.0]))
+        top = float(rng.choice([sr / 2, sr / 2, 0.375 * sr, sr / 6]))
+        kw.update(sample_rate=sr, fmax_hz=top, fmin_hz=float(rng.choice([20.0, 35.0, 80.0] + ([30.0, 55.0] if top == sr / 2 else []))))
     pcm = synth.streams(S, L, first=int(rng.integers(0, 1000)))
     fresh = synth.streams(1, L, first=int(rng.integers(1000, 2000)))[0]
-    desc = f"case {ci}: exact={exact} n={n} hop={hop} rows={rows} re={reassign} S={S} frames={frames} form={form} pinned={pinned} who={who} cut={cut}"
+    desc = f"case {ci}: exact={exact} n={n} hop={hop} rows={rows} re={reassign} S={S} frames={frames} form={form} pinned={pinned} who={who} cut={cut}" + (f" {kw}" if ANY_RATES else "")
     try:
         cfg = O.make_cfg(n, hop, reassign, **kw)
         odb, orgba = oracle(cfg, pcm, exact)
