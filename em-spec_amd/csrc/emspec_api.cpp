@@ -243,6 +243,7 @@ void emspec_destroy(emspec_engine* e) {
     if (e->stream_out) (void)hipStreamSynchronize(e->stream_out);
     comm_destroy(e);
     live_destroy(e);
+    stereo_destroy(e);
     drop_plans(e);
     (void)hipFree(e->d_xlow);
     if (e->xlow_event) (void)hipEventDestroy(e->xlow_event);

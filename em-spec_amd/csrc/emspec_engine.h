@@ -124,6 +124,9 @@ bool host_pinned(const void* p);   // p is null or page-locked host memory the d
 struct PackedOut { uint8_t* wire; int64_t capacity; int64_t* offsets; };
 // emspec_batch_peaks: instead of columns, the k loudest peaks at or above min_db of every column, [S][columns][k] (f = 1 only)
 struct PeaksOut { emspec_peak* peaks; int k; float min_db; };
+// emspec_batch_pcm_stereo: instead of columns, the stereo image of each source's channels a and b (views of its format) under
+// `law`, [S][columns][rows] per output (any null; f = 1 only)
+struct StereoHostOut { int a, b; StereoLaw law; float* level; uint8_t* index; uint8_t* pan; uint8_t* rgba; };
 using HostRun = std::function<int(const float* pcm, int sc, int64_t samples, float* db, uint8_t* rgba, uint8_t* index, hipStream_t st)>;
 struct HostJob {
     const void* src = nullptr;   // float32 [S][L] - or, with `dec`, raw interleaved frames: S SOURCES of L frames
@@ -134,11 +137,12 @@ struct HostJob {
     // columns on either side when the batch has too few streams
     bool whole_streams = false;
     int halo_D = 0, min_streams = 1;
-    // what is delivered: exactly one of out / pk / pko (and beside it, while emspec_set_wave_out is set, the envelope of the
+    // what is delivered: exactly one of out / pk / pko / stereo (and beside it, while emspec_set_wave_out is set, the envelope of the
     // streams' samples: emspec_engine::wave_out)
     const emspec_out* out = nullptr;
     const PackedOut* pk = nullptr;
     const PeaksOut* pko = nullptr;
+    const StereoHostOut* stereo = nullptr;   // (needs dec: a pair is the views of one source)
     // (emspec_batch_pcm, emspec_batch_pcm_packed): the copy-in stage moves the raw bytes, the decode kernel (pcm.hip.inc) fills
     // the unit's float streams in front of `run`, which then sees sc * dec->views streams, and the outputs are those of
     // S * dec->views streams
@@ -166,6 +170,14 @@ bool live_pending(const emspec_engine* e);   // some stream of either session ha
 int history_ready(emspec_engine* e, LiveState& lv);
 void history_free(LiveState& lv);
 void history_destroy(emspec_engine* e);
+// ... what its views share with the stereo views (emspec_stereo.cpp): the session of an EMSPEC_SESSION_* (null: neither), and
+// the address the device uses for page-locked host memory aligned to `align` bytes (null: pageable, misaligned or null)
+LiveState* history_session(emspec_engine* e, int32_t session);
+void* pinned_view(const void* p, size_t align);
+// emspec_stereo.cpp: the engine's stereo palette on the device (built at the first use: the default colour map's brightness),
+// and its buffers' end (called by emspec_destroy)
+int stereo_palette_ready(emspec_engine* e);
+void stereo_destroy(emspec_engine* e);
 // emspec_audio.cpp: the live audio history's buffers, as their history twins.  audio_store: the store kernel of one launch of
 // the session, behind its other kernels (nothing while no audio history is set, and for a flush)
 int audio_ready(emspec_engine* e, LiveState& lv);
@@ -224,6 +236,10 @@ struct emspec_engine {
     // page-locked staging blocks of a host view's pageable outputs (dB, index, RGBA)
     int64_t history_W = 0;
     void* h_view[3] = {}; size_t view_bytes[3] = {};
+    // stereo image (emspec_stereo.cpp): the palette [33][256][4] on the device (null until first used or set),
+    // and the page-locked staging blocks of a host stereo view's pageable outputs (level, index, pan, RGBA)
+    uint8_t* d_stereo_pal = nullptr;
+    void* h_sview[4] = {}; size_t sview_bytes[4] = {};
     // live audio history (emspec_set_live_audio; emspec_audio.cpp): W samples per stream of both sessions below (0: off), the
     // page-locked staging block of a host view's pageable output, and the device blocks of a re-analysis (emspec_audio_batch*):
     // the viewed samples [streams][count] and the host form's dB / RGBA / index columns

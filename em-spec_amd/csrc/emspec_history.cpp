@@ -10,8 +10,8 @@
 
 using namespace emspec;
 
-namespace {
-LiveState* session_of(emspec_engine* e, int32_t session) {
+namespace emspec {
+LiveState* history_session(emspec_engine* e, int32_t session) {
     return session == EMSPEC_SESSION_MULTI ? &e->live : session == EMSPEC_SESSION_ONE ? &e->one : nullptr;
 }
 
@@ -22,6 +22,10 @@ void* pinned_view(const void* p, size_t align) {
     if (hipHostGetDevicePointer(&d, const_cast<void*>(p), 0) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     return d;
 }
+}  // namespace emspec
+
+namespace {
+LiveState* session_of(emspec_engine* e, int32_t session) { return history_session(e, session); }
 
 // Every check of a view, then its launch on `st`: db / index / rgba are device-visible.
 int view_launch(emspec_engine* e, int32_t session, int32_t stream0, int32_t streams, int64_t first, int32_t factor, int64_t groups,

@@ -1,7 +1,8 @@
-// emspec_host.cpp — the host-buffer path (include/emspec.h: emspec_batch, _packed, _multires, _pcm, _peaks): S streams in host
-// memory -> columns in host memory, or one packed wire image per stream, through staging sets on the device.  One driver,
-// host_batch, serves every entry: each hands it a HostJob (emspec_engine.h).  It is three parts around one Pipe: plan_pipe (the
-// plan, emspec_pipe_plan.h, and the workspaces), the background delivery (deliver_start / _finish) and the unit loop (run_units).
+// emspec_host.cpp — the host-buffer path (include/emspec.h: emspec_batch, _packed, _multires, _pcm, _peaks, _pcm_stereo): S streams
+// in host memory -> columns in host memory, or one packed wire image per stream, peak lists or the stereo image of each source,
+// through staging sets on the device.  One driver, host_batch, serves every entry: each hands it a HostJob (emspec_engine.h).  It
+// is three parts around one Pipe: plan_pipe (the plan, emspec_pipe_plan.h, and the workspaces), the background delivery
+// (deliver_start / _finish) and the unit loop (run_units).
 #include "emspec_engine.h"
 #include "emspec_pipe_plan.h"
 
@@ -60,9 +61,16 @@ int plan_pipe(Pipe& p) {
     p.outs[kIdx] = OutRow{(char*)o.index, o.index || j.pk ? (size_t)1 : 0};
     p.outs[kPeaks] = OutRow{j.pko ? (char*)j.pko->peaks : nullptr, j.pko ? j.pko->k * sizeof(emspec_peak) : 0};
     p.outs[kWave] = OutRow{(char*)e->wave_out, e->wave_out ? sizeof(emspec_wave) : 0};   // (beside any of them: emspec_set_wave_out)
+    if (const StereoHostOut* so = j.stereo) {   // (the dB columns are staged for the compose kernel and stay on the device)
+        p.outs[kSLevel] = OutRow{(char*)so->level, so->level ? (size_t)4 : 0};
+        p.outs[kSIdx] = OutRow{(char*)so->index, so->index ? (size_t)1 : 0};
+        p.outs[kSPan] = OutRow{(char*)so->pan, so->pan ? (size_t)1 : 0};
+        p.outs[kSRgba] = OutRow{(char*)so->rgba, so->rgba ? (size_t)4 : 0};
+    }
     const size_t wire_s = j.pk ? (size_t)wire_bound_bytes(p.Cr, p.R) : 0, in_s = (size_t)j.L * p.fb;
     const size_t per_stream = per_stream_bytes(p.outs, in_s, j.dec ? (size_t)j.L * 4 * p.V : 0, p.V, p.C, p.Cr, p.R, wire_s, p.f);
-    int units = pipe_units(e->exact(), j.n, (int64_t)j.S * p.V * p.C, (size_t)j.S * in_s, bytes_out_estimate(p.outs, j.pk != nullptr, (size_t)j.S * p.V, p.C, p.Cr, p.R));
+    const size_t bytes_out = j.stereo ? stereo_bytes_out(p.outs, (size_t)j.S, p.C, p.R) : bytes_out_estimate(p.outs, j.pk != nullptr, (size_t)j.S * p.V, p.C, p.Cr, p.R);
+    int units = pipe_units(e->exact(), j.n, (int64_t)j.S * p.V * p.C, (size_t)j.S * in_s, bytes_out);
 #ifdef EMSPEC_DIAG
     if (const char* ev = getenv("EMSPEC_PIPE_CHUNKS")) { const int v = atoi(ev); if (v >= 1) units = v; }   // A/B aid
 #endif
@@ -95,7 +103,7 @@ template <class F>
 void for_pieces(const Pipe& p, int u, F&& fn) {
     for (int k = 0; k < spans_of(p.items[u], p.C, p.V); ++k) {
         const Span sp = span_of(p.items[u], p.C, p.R, p.V, k, p.f);
-        for (int w = 0; w < kOutRows; ++w) {
+        for (int w = 0; w < kSLevel; ++w) {
             const OutRow& o = p.outs[w];
             const size_t cols = sp.cells / p.R, off = p.g.out_off(w);
             if (o.host && w == kWave) {
@@ -105,6 +113,10 @@ void for_pieces(const Pipe& p, int u, F&& fn) {
             if (o.host && w == kPeaks) fn(o.host + sp.to / p.R * o.unit, off + k * cols * o.unit, cols * o.unit);
         }
     }
+    // the stereo image: one span of pair cells per unit
+    const Span ss = stereo_span_of(p.items[u], p.C, p.R);
+    for (int w = kSLevel; w <= kSRgba; ++w)
+        if (const OutRow& o = p.outs[w]; o.host) fn(o.host + ss.to * o.unit, p.g.out_off(w) + ss.from * o.unit, ss.cells * o.unit);
 }
 // the only D2H copies of columns: unit u's kept columns into the caller's arrays, on `st` behind the unit's kernels
 hipError_t copy_out(const Pipe& p, int u, hipStream_t st, bool computed = false) {   // (computed: the host has waited for the kernels)
@@ -261,6 +273,14 @@ void run_units(Pipe& p) {
         if (q.wave && herr == hipSuccess) {
             const WaveRun wr = wave_run_of(it, j.n, j.hop, f);
             herr = launch_wave(q.pcm, it.sc * V, it.samples, wr.first, wr.cols, j.hop, f, q.wave, wr.pairs, e->stream);
+        }
+        // 3e. stereo image: the unit's sc sources are sc pairs of V streams, composed over all the unit's columns (stereo.hip.inc)
+        if (j.stereo && herr == hipSuccess) {
+            StereoCompose sc;
+            sc.db = q.db, sc.views = V, sc.a = j.stereo->a, sc.b = j.stereo->b, sc.cells = (long long)it.cols * R;
+            sc.law = j.stereo->law, sc.pal = reinterpret_cast<const uint32_t*>(e->d_stereo_pal);
+            sc.out = StereoOut{q.slevel, q.sidx, q.span, reinterpret_cast<uint32_t*>(q.srgba)};
+            herr = launch_stereo_compose(sc, it.sc, e->stream);
         }
         if (herr != hipSuccess) break;
         // 4. packed: each stream's image, its header to the host behind it

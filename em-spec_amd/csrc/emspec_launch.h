@@ -7,6 +7,7 @@
 #include "emspec_device.h"
 #include "emspec_history_plan.h"
 #include "emspec_live_plan.h"
+#include "emspec_stereo_plan.h"
 #include "emspec_wire_plan.h"
 
 namespace emspec {
@@ -209,6 +210,38 @@ struct HistoryView {
 };
 int history_view_split(int streams, int64_t groups, int rows, int f);   // waves a group's columns are cut over (1: no split)
 hipError_t launch_history_view(const HistoryView& v, int streams, hipStream_t st);
+// The stereo image (stereo.hip.inc; the law: emspec_stereo_plan.h).  Outputs [pairs][cells] (rgba + [4]), any of them null.
+struct StereoOut {
+    float* level = nullptr;
+    uint8_t* index = nullptr;
+    uint8_t* pan = nullptr;
+    uint32_t* rgba = nullptr;
+};
+// The compose kernel: db [pairs * views][cells], pair p's channels in streams p views + a and p views + b; pal [33][256] RGBA.
+struct StereoCompose {
+    const float* db = nullptr;
+    int views = 2, a = 0, b = 1;
+    long long cells = 0;
+    StereoLaw law{};
+    const uint32_t* pal = nullptr;
+    StereoOut out;
+};
+hipError_t launch_stereo_compose(const StereoCompose& s, int pairs, hipStream_t st);
+// The stereo history view: HistoryView's groups of the rings of streams stream0 + p views + a / + b, pair p in [0, pairs) ->
+// [pairs][groups][rows].
+struct StereoView {
+    const float* ring = nullptr;
+    const long long* ends = nullptr;
+    int W = 0, rows = 0, stream0 = 0;
+    long long first = 0;
+    int slot_first = 0;
+    int f = 1, groups = 0;
+    int views = 2, a = 0, b = 1;
+    StereoLaw law{};
+    const uint32_t* pal = nullptr;
+    StereoOut out;
+};
+hipError_t launch_stereo_view(const StereoView& v, int pairs, hipStream_t st);
 // The live audio history (live_audio.hip.inc; emspec_set_live_audio; geometry: emspec_audio_plan.h).  The store: one kernel
 // behind the launch's other kernels, on the same descriptors (lv.fresh / lv.fresh_stride / lv.streams); `most`: the most
 // samples any stream brings in the launch.

@@ -57,67 +57,83 @@ inline std::vector<PipeItem> pipe_items(int S, int64_t L, int64_t C, int n, int 
 // What a call delivers: one row per array, in the order of a set's layout.  `host`: the caller's array (null: not copied out -
 // the packed entries stage the index for the wire images only); `unit`: bytes per cell - peaks: per column, k pairs - or 0
 // without that array.  Where the unit's copy lies in a staging set: Stage::out_off.  kWave: the waveform envelope of the samples
-// (emspec_set_wave_out), one pair per DELIVERED column.
-enum { kDb, kRgba, kIdx, kPeaks, kWave, kOutRows };
+// (emspec_set_wave_out), one pair per DELIVERED column.  kSLevel .. kSRgba: the stereo image (emspec_batch_pcm_stereo; DESIGN.md
+// §3.16), one cell per PAIR cell - a pair is the V streams of one source, so a unit's sc sources give sc pairs.
+enum { kDb, kRgba, kIdx, kPeaks, kWave, kSLevel, kSIdx, kSPan, kSRgba, kOutRows };
 struct OutRow { char* host; size_t unit; };
+inline bool stereo_rows(const OutRow* o) { return o[kSLevel].unit || o[kSIdx].unit || o[kSPan].unit || o[kSRgba].unit; }
 // The bytes `streams` streams leave the device with (pipe_units): the rows' - or the wire images', about a fifth of the index
 // (the envelope's 8 bytes per delivered column are not counted: a batch is cut the same way with and without it)
 inline size_t bytes_out_estimate(const OutRow* o, bool packed, size_t streams, int64_t C, int64_t Cr, int R) {
     const size_t cell = o[kDb].unit + o[kRgba].unit + o[kIdx].unit;
     return packed ? streams * Cr * R / 5 : streams * Cr * R * cell + streams * C * o[kPeaks].unit;
 }
+// ... of a stereo job instead: its pairs' cells (no other row is set beside them but the envelope's)
+inline size_t stereo_bytes_out(const OutRow* o, size_t pairs, int64_t C, int R) {
+    return pairs * C * R * (o[kSLevel].unit + o[kSIdx].unit + o[kSPan].unit + o[kSRgba].unit);
+}
 
 // (db / rgba / idx: what the unit's kernels write; odb / orgba / oidx: what is delivered - the same arrays, or with a time
 // reduction the reduced columns beside them; peaks: the unit's peak lists, emspec_batch_peaks)
-struct Set { float* pcm; float* db; uint8_t* rgba; uint8_t* idx; uint8_t* wire; char* raw; float* odb; uint8_t* orgba; uint8_t* oidx; emspec_peak* peaks; emspec_wave* wave; };
+// slevel / sidx / span / srgba: the stereo image of the unit's pairs, composed from db
+struct Set { float* pcm; float* db; uint8_t* rgba; uint8_t* idx; uint8_t* wire; char* raw; float* odb; uint8_t* orgba; uint8_t* oidx; emspec_peak* peaks; emspec_wave* wave;
+             float* slevel; uint8_t* sidx; uint8_t* span; uint8_t* srgba; };
 // The staging set: every array at the size the largest unit needs, in the order of off()'s list.
 struct Stage {
     size_t in = 0, db = 0, rgba = 0, idx = 0, wire = 0;   // (wire: one slot of that many bytes per stream of the unit)
     size_t raw = 0;                                       // PCM entries: the unit's raw frames, which the decode kernel turns into `in`
     size_t rdb = 0, rrgba = 0, ridx = 0;                  // time reduction: the reduced columns (db / idx then hold the full-rate ones)
     size_t peaks = 0;                                     // emspec_batch_peaks: k (pos, dB) pairs per kept column of the unit
-    size_t wave = 0;                                      // emspec_set_wave_out: a pair per delivered column of the unit; the LAST array,
-                                                          // so that a job without an envelope keeps every offset and size
+    size_t wave = 0;                                      // emspec_set_wave_out: a pair per delivered column of the unit; behind every
+                                                          // array above, so that a job without an envelope keeps every offset and size
+    size_t stereo[4] = {};                                // emspec_batch_pcm_stereo: level, index, pan, RGBA per pair cell of the unit;
+                                                          // behind the envelope's and empty for every other job, for the same reason
     bool reduced = false; int chunk = 1;                  // (chunk: streams in the largest unit)
     size_t off(int a) const {   // byte offset in a set of its a-th array
-        const size_t s[11] = {in, db, rgba, idx, wire * chunk, raw, rdb, rrgba, ridx, peaks, wave};
+        const size_t s[15] = {in, db, rgba, idx, wire * chunk, raw, rdb, rrgba, ridx, peaks, wave, stereo[0], stereo[1], stereo[2], stereo[3]};
         return std::accumulate(s, s + a, (size_t)0);
     }
-    size_t bytes() const { return off(11); }
+    size_t bytes() const { return off(15); }
     // ... of row w's delivered copy: the reduced array, or without a reduction what the kernels wrote
-    size_t out_off(int w) const { return off(w == kWave ? 10 : w == kPeaks ? 9 : reduced ? 6 + w : 1 + w); }
+    size_t out_off(int w) const { return off(w >= kSLevel ? 11 + (w - kSLevel) : w == kWave ? 10 : w == kPeaks ? 9 : reduced ? 6 + w : 1 + w); }
     Set at(char* stage, int b) const {
         char* base = stage + (size_t)b * bytes();
         auto p = [&](size_t have, size_t o) { return have ? base + o : nullptr; };
         return Set{(float*)base, (float*)p(db, off(1)), (uint8_t*)p(rgba, off(2)), (uint8_t*)p(idx, off(3)), (uint8_t*)p(wire, off(4)), p(raw, off(5)),
                    (float*)p(reduced ? rdb : db, out_off(kDb)), (uint8_t*)p(reduced ? rrgba : rgba, out_off(kRgba)),
                    (uint8_t*)p(reduced ? ridx : idx, out_off(kIdx)), (emspec_peak*)p(peaks, out_off(kPeaks)),
-                   (emspec_wave*)p(wave, out_off(kWave))};
+                   (emspec_wave*)p(wave, out_off(kWave)), (float*)p(stereo[0], out_off(kSLevel)), (uint8_t*)p(stereo[1], out_off(kSIdx)),
+                   (uint8_t*)p(stereo[2], out_off(kSPan)), (uint8_t*)p(stereo[3], out_off(kSRgba))};
     }
 };
 
 // The arrays of a set behind its input, for `cells` full-rate cells, `rcells` reduced ones, the peak lists of `cols` columns and
 // the envelope pairs of `rcols` delivered columns.
-// Full rate: the rows' own arrays, but the dB also for the peaks kernel, and with f > 1 the index in place of RGBA.
-inline Stage stage_arrays(const OutRow* o, int f, size_t cells, size_t rcells, size_t cols, size_t rcols, size_t wire_s) {
+// Full rate: the rows' own arrays, but the dB also for the peaks kernel and the stereo image (of `pcells` pair cells), and with
+// f > 1 the index in place of RGBA.
+inline Stage stage_arrays(const OutRow* o, int f, size_t cells, size_t rcells, size_t cols, size_t rcols, size_t wire_s, size_t pcells = 0) {
     Stage g;
     g.reduced = f > 1;
-    g.db = o[kDb].unit || o[kPeaks].unit ? al(cells * 4) : 0;
+    g.db = o[kDb].unit || o[kPeaks].unit || stereo_rows(o) ? al(cells * 4) : 0;
     g.rgba = o[kRgba].unit && !g.reduced ? al(cells * 4) : 0;
     g.idx = o[kIdx].unit || (o[kRgba].unit && g.reduced) ? al(cells) : 0;
     g.wire = al(wire_s);
     if (g.reduced) { g.rdb = al(rcells * o[kDb].unit); g.rrgba = al(rcells * o[kRgba].unit); g.ridx = al(rcells * o[kIdx].unit); }
     g.peaks = al(cols * o[kPeaks].unit);
     g.wave = al(rcols * o[kWave].unit);
+    for (int w = 0; w < 4; ++w) g.stereo[w] = al(pcells * o[kSLevel + w].unit);
     return g;
 }
-// Staging bytes per stream (pipe_items' 1 GiB cap): the input (`dec_s`: a PCM source's decoded floats) and each view's arrays
+// Staging bytes per stream (pipe_items' 1 GiB cap): the input (`dec_s`: a PCM source's decoded floats), each view's arrays and
+// the source's stereo image
 inline size_t per_stream_bytes(const OutRow* o, size_t in_s, size_t dec_s, int V, int64_t C, int64_t Cr, int R, size_t wire_s, int f) {
-    return al(in_s) + (dec_s ? al(dec_s) : 0) + V * stage_arrays(o, f, (size_t)C * R, (size_t)Cr * R, (size_t)C, (size_t)Cr, wire_s).bytes();
+    size_t pair = 0;
+    for (int w = kSLevel; w <= kSRgba; ++w) pair += al((size_t)C * R * o[w].unit);
+    return al(in_s) + (dec_s ? al(dec_s) : 0) + V * stage_arrays(o, f, (size_t)C * R, (size_t)Cr * R, (size_t)C, (size_t)Cr, wire_s).bytes() + pair;
 }
 // The set of a batch (V streams per unit of PipeItem::sc, frame_bytes of raw input each: 1 and 0 for the float entries)
 inline Stage stage_layout(const std::vector<PipeItem>& items, int R, const OutRow* o, size_t wire_s, int V, int frame_bytes, int f) {
-    size_t in = 0, raw = 0, cells = 0, rcells = 0, cols = 0, rcols = 0; int chunk = 1;
+    size_t in = 0, raw = 0, cells = 0, rcells = 0, cols = 0, rcols = 0, pcells = 0; int chunk = 1;
     for (const PipeItem& it : items) {
         in = std::max(in, al((size_t)it.samples * 4 * it.sc * V));
         raw = std::max(raw, frame_bytes ? al((size_t)it.samples * frame_bytes * it.sc) : 0);
@@ -126,8 +142,9 @@ inline Stage stage_layout(const std::vector<PipeItem>& items, int R, const OutRo
         cols = std::max(cols, (size_t)it.cn * it.sc * V);
         rcols = std::max(rcols, (size_t)((it.cn + f - 1) / f) * it.sc * V);
         chunk = std::max(chunk, it.sc * V);
+        pcells = std::max(pcells, (size_t)it.cols * R * it.sc);
     }
-    Stage g = stage_arrays(o, f, cells, rcells, cols, rcols, wire_s);
+    Stage g = stage_arrays(o, f, cells, rcells, cols, rcols, wire_s, pcells);
     g.in = in; g.raw = raw; g.chunk = chunk;
     return g;
 }
@@ -146,6 +163,11 @@ inline Span span_of(const PipeItem& it, int64_t C, int R, int V, int k, int f) {
     if (it.cn == C) return Span{0, (size_t)it.s0 * V * Cr * R, crn * R * it.sc * V};
     return Span{(size_t)k * crn * R, (((size_t)it.s0 * V + k) * Cr + (size_t)(it.c0 / f)) * R, crn * R};
 }
+
+// The stereo image of a unit: its sc sources are sc pairs of V streams, composed over ALL the unit's columns (a run's halo
+// columns included: the compose kernel takes streams one whole array apart) - one span per unit, that of a job of single-view
+// streams, in pair cells
+inline Span stereo_span_of(const PipeItem& it, int64_t C, int R) { return span_of(it, C, R, 1, 0, 1); }
 
 // The waveform envelope of a unit (wave.hip.inc), in pairs = delivered columns.  Its kernel reads the unit's
 // staged samples: the first window starts WaveRun::first samples into each of the unit's streams (off = n / 2 - hop / 2 past

@@ -616,4 +616,5 @@ hipError_t launch_occupy(int groups, int usec, unsigned* sink, hipStream_t st) {
 #include "live_launch.hip.inc"
 #include "live_overlay.hip.inc"
 #include "live_history.hip.inc"
+#include "stereo.hip.inc"
 #include "live_audio.hip.inc"

@@ -70,7 +70,12 @@ HISTORY_SYMBOLS = ["emspec_set_live_history", "emspec_live_history", "emspec_his
 # the live audio history's: likewise (tools/live_audio_rate.py times the parent commit's library next to this build)
 AUDIO_SYMBOLS = ["emspec_set_live_audio", "emspec_live_audio", "emspec_audio_view_device", "emspec_audio_view",
                  "emspec_audio_batch_device", "emspec_audio_batch"]
-SYMBOLS = SYMBOLS + MULTIBAND_SYMBOLS + LIVE_OVERLAY_SYMBOLS + LIVE_MULTIBAND_SYMBOLS + HISTORY_SYMBOLS + AUDIO_SYMBOLS
+# the stereo image's: likewise (tools/stereo_rate.py times the parent commit's library next to this build)
+STEREO_SYMBOLS = ["emspec_stereo_default_map", "emspec_make_stereo_colormap", "emspec_set_stereo_colormap", "emspec_stereo_device",
+                  "emspec_stereo_host", "emspec_batch_stereo_device", "emspec_batch_pcm_stereo", "emspec_history_view_stereo_device",
+                  "emspec_history_view_stereo"]
+SYMBOLS = SYMBOLS + MULTIBAND_SYMBOLS + LIVE_OVERLAY_SYMBOLS + LIVE_MULTIBAND_SYMBOLS + HISTORY_SYMBOLS + AUDIO_SYMBOLS + STEREO_SYMBOLS
+STEREO_PAN_CENTRE, STEREO_PAN_LEVELS = 16, 33
 SESSION_MULTI, SESSION_ONE = 0, 1
 _SESSIONS = {"multi": SESSION_MULTI, "one": SESSION_ONE, SESSION_MULTI: SESSION_MULTI, SESSION_ONE: SESSION_ONE}
 
@@ -89,6 +94,24 @@ class ViewMap(C.Structure):
     """emspec_view_map: the colour law of a history view (db_top, db_range, gate_db as in the configuration) and the dB shift
     applied in front of it."""
     _fields_ = [("db_top", C.c_float), ("db_range", C.c_float), ("gate_db", C.c_float), ("shift_db", C.c_float)]
+
+
+class StereoMap(C.Structure):
+    """emspec_stereo_map: the colour law of a stereo image - db_top, db_range, gate_db and shift_db as in ViewMap, applied to the
+    level (the louder channel's dB), and pan_range_db, the dB difference that reads as fully to one side."""
+    _fields_ = [("db_top", C.c_float), ("db_range", C.c_float), ("gate_db", C.c_float), ("shift_db", C.c_float),
+                ("pan_range_db", C.c_float)]
+
+
+def _stereo_map(map):
+    """None, a StereoMap, a (db_top, db_range, gate_db, shift_db, pan_range_db) tuple or a dict of those names -> StereoMap or
+    None."""
+    if map is None or isinstance(map, StereoMap):
+        return map
+    if isinstance(map, dict):
+        return StereoMap(float(map["db_top"]), float(map["db_range"]), float(map["gate_db"]), float(map.get("shift_db", 0.0)),
+                         float(map.get("pan_range_db", 12.0)))
+    return StereoMap(*(float(x) for x in map))
 
 
 class PcmFormat(C.Structure):
@@ -215,6 +238,41 @@ def wave_host(pcm, n, hop, factor=1, out=None, diag=False):
         out = np.empty((S, Cr, 2), np.float32)
     assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == S * Cr * 2
     rc = lib.emspec_wave_host(_np_ptr(pcm), S, L, n, hop, int(factor), _np_ptr(out))
+    if rc != 0:
+        raise EmspecError(rc, lib.emspec_last_error(None).decode())
+    return out
+
+
+def make_stereo_colormap(brightness=0.5, diag=False):
+    """The stereo palette built from make_colormap(brightness): uint8 [33][256][4] for Engine.set_stereo_colormap - row 16 the
+    colour map itself, rows towards 0 tinted warm (channel A louder), towards 32 cold (channel B louder)."""
+    out = np.empty((STEREO_PAN_LEVELS, 256, 4), np.uint8)
+    if load(diag).emspec_make_stereo_colormap(brightness, _np_ptr(out)) != OK:
+        raise EmspecError(ERR_INVALID_ARG, "invalid brightness")
+    return out
+
+
+def stereo_host(db, views, a, b, map, palette=None, want=("level", "index", "pan"), diag=False):
+    """The stereo image of db [pairs * views, ...] float32 on the host's own cores (emspec_stereo_host: plain C++, no device, no
+    engine; the definition: include/emspec.h): pair p's channels are streams p views + a and p views + b ->
+    {"level": float32 [pairs, ...], "index": uint8, "pan": uint8, "rgba": uint8 [pairs, ..., 4]}, each present when named in
+    `want` ("rgba" needs a palette [33][256][4])."""
+    db = np.ascontiguousarray(db, np.float32)
+    streams = db.shape[0] if db.ndim else 0
+    cells = db.size // streams if streams else 0
+    pairs = streams // views if views > 0 and streams % views == 0 else -1
+    shape = (max(pairs, 0),) + db.shape[1:]
+    out = {"level": np.empty(shape, np.float32) if "level" in want else None,
+           "index": np.empty(shape, np.uint8) if "index" in want else None,
+           "pan": np.empty(shape, np.uint8) if "pan" in want else None,
+           "rgba": np.empty(shape + (4,), np.uint8) if "rgba" in want else None}
+    if palette is not None:
+        palette = np.ascontiguousarray(palette, np.uint8)
+        assert palette.shape == (STEREO_PAN_LEVELS, 256, 4)
+    m = _stereo_map(map)
+    lib = load(diag=diag)
+    rc = lib.emspec_stereo_host(_np_ptr(db), pairs, int(views), int(a), int(b), cells, C.byref(m) if m is not None else None,
+                                _np_ptr(palette), _np_ptr(out["level"]), _np_ptr(out["index"]), _np_ptr(out["pan"]), _np_ptr(out["rgba"]))
     if rc != 0:
         raise EmspecError(rc, lib.emspec_last_error(None).decode())
     return out
@@ -406,6 +464,23 @@ def load(diag=False):
                                                   C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.emspec_audio_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                            C.c_int32, C.POINTER(Out)]
+    if all(hasattr(lib, sym) for sym in STEREO_SYMBOLS):
+        outs = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.emspec_stereo_default_map.argtypes = [C.c_void_p, C.c_void_p]
+        lib.emspec_make_stereo_colormap.argtypes = [C.c_float, C.c_void_p]
+        lib.emspec_set_stereo_colormap.argtypes = [C.c_void_p, C.c_void_p]
+        lib.emspec_stereo_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                             C.c_void_p] + outs + [C.c_void_p]
+        lib.emspec_stereo_host.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p,
+                                           C.c_void_p] + outs
+        lib.emspec_batch_stereo_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                                   C.c_int32, C.c_int32, C.c_int32, C.c_void_p] + outs + [C.c_void_p]
+        lib.emspec_batch_pcm_stereo.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                                C.c_int32, C.c_int32, C.c_int32, C.c_void_p] + outs
+        lib.emspec_history_view_stereo_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                          C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p] + outs + [C.c_void_p]
+        lib.emspec_history_view_stereo.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                   C.c_int64, C.c_int32, C.c_int64, C.c_void_p] + outs
     _libs[diag] = lib
     return lib
 
@@ -1323,6 +1398,127 @@ class Engine:
                                                 int(groups), C.byref(m) if m is not None else None, _np_ptr(db), _np_ptr(index),
                                                 _np_ptr(rgba)))
         return {"db": db, "index": index, "rgba": rgba}
+
+    # -- stereo image (include/emspec.h: emspec_stereo_*) -----------------------------------------------------
+    STEREO_OUTPUTS = ("level", "index", "pan", "rgba")
+
+    def stereo_default_map(self):
+        """emspec_stereo_default_map: the engine's configuration, shift 0, pan_range_db = 12, as a StereoMap."""
+        m = StereoMap()
+        self._chk(self._lib.emspec_stereo_default_map(self._h, C.byref(m)))
+        return m
+
+    def set_stereo_colormap(self, palette):
+        """emspec_set_stereo_colormap: uint8 [33][256][4] (make_stereo_colormap builds the engine's own law)."""
+        palette = np.ascontiguousarray(palette, np.uint8)
+        assert palette.shape == (STEREO_PAN_LEVELS, 256, 4)
+        self._chk(self._lib.emspec_set_stereo_colormap(self._h, _np_ptr(palette)))
+
+    @staticmethod
+    def _stereo_tensors(shape, device, want, given):
+        """The four outputs as CUDA tensors: those given, those named in `want` allocated, the others None."""
+        import torch
+        out = {}
+        for name in Engine.STEREO_OUTPUTS:
+            t = given.get(name)
+            if t is None and name in want:
+                t = torch.empty(shape + ((4,) if name == "rgba" else ()), dtype=torch.float32 if name == "level" else torch.uint8,
+                                device=device)
+            assert t is None or (t.is_cuda and t.is_contiguous())
+            out[name] = t
+        return out
+
+    @staticmethod
+    def _stereo_arrays(shape, want, given):
+        """The four outputs as numpy arrays: those given (numpy arrays or PinnedArray.array, written in place), those named in
+        `want` allocated, the others None."""
+        out = {}
+        for name in Engine.STEREO_OUTPUTS:
+            a = given.get(name)
+            sh, dt = shape + ((4,) if name == "rgba" else ()), np.float32 if name == "level" else np.uint8
+            if a is None and name in want:
+                a = np.empty(sh, dt)
+            assert a is None or (a.dtype == dt and a.flags.c_contiguous and a.shape == sh), (name, a.dtype, a.shape, sh)
+            out[name] = a
+        return out
+
+    def stereo_device(self, db_t, views=2, a=0, b=1, map=None, want=("index", "pan"), stream=None, **given):
+        """emspec_stereo_device: db_t a contiguous float32 CUDA tensor [pairs * views, ...] -> {"level", "index", "pan", "rgba"}
+        CUDA tensors [pairs, ...] (rgba + [4]): those named in `want` or passed as keywords.  Enqueues; does not synchronise."""
+        import torch
+        assert db_t.is_cuda and db_t.dtype == torch.float32 and db_t.is_contiguous() and db_t.dim() >= 1
+        streams = db_t.shape[0]
+        cells = db_t.numel() // streams if streams else 0
+        assert views > 0 and streams % views == 0
+        out = self._stereo_tensors((streams // views,) + tuple(db_t.shape[1:]), db_t.device, want, given)
+        st = stream if stream is not None else torch.cuda.current_stream(db_t.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        m = _stereo_map(map)
+        self._chk(self._lib.emspec_stereo_device(self._h, ptr(db_t), streams // views, int(views), int(a), int(b), cells,
+                                                 C.byref(m) if m is not None else None, ptr(out["level"]), ptr(out["index"]),
+                                                 ptr(out["pan"]), ptr(out["rgba"]), C.c_void_p(st.cuda_stream)))
+        return out
+
+    def batch_stereo_device(self, pcm_t, n, hop, reassign=True, views=2, a=0, b=1, map=None, want=("index", "pan"), stream=None,
+                            **given):
+        """emspec_batch_stereo_device: pcm_t a contiguous float32 CUDA tensor [S, L], S % views == 0 -> the stereo image of the
+        dB batch_device would deliver, CUDA tensors [S / views, columns, rows].  Enqueues; does not synchronise."""
+        import torch
+        assert pcm_t.is_cuda and pcm_t.dtype == torch.float32 and pcm_t.is_contiguous() and pcm_t.dim() == 2
+        S, L = pcm_t.shape
+        out = self._stereo_tensors((S // max(int(views), 1), num_columns(L, n, hop), self.rows), pcm_t.device, want, given)
+        st = stream if stream is not None else torch.cuda.current_stream(pcm_t.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        m = _stereo_map(map)
+        self._chk(self._lib.emspec_batch_stereo_device(self._h, ptr(pcm_t), S, L, n, hop, int(bool(reassign)), int(views), int(a),
+                                                       int(b), C.byref(m) if m is not None else None, ptr(out["level"]),
+                                                       ptr(out["index"]), ptr(out["pan"]), ptr(out["rgba"]), C.c_void_p(st.cuda_stream)))
+        return out
+
+    def batch_pcm_stereo(self, src, fmt, n, hop, reassign=True, a=0, b=1, map=None, want=("index", "pan"), **given):
+        """emspec_batch_pcm_stereo: raw frames as batch_pcm takes them -> the stereo image of each source's views a and b, numpy
+        arrays [sources, columns, rows] (rgba + [4]); only the requested outputs cross PCIe on the way out."""
+        src, sources, frames = _pcm_rows(src, fmt)
+        out = self._stereo_arrays((sources, max(num_columns(frames, n, hop), 0), self.rows), want, given)
+        m = _stereo_map(map)
+        self._chk(self._lib.emspec_batch_pcm_stereo(self._h, _np_ptr(src), C.byref(fmt), sources, frames, n, hop, int(bool(reassign)),
+                                                    int(a), int(b), C.byref(m) if m is not None else None, _np_ptr(out["level"]),
+                                                    _np_ptr(out["index"]), _np_ptr(out["pan"]), _np_ptr(out["rgba"])))
+        return out
+
+    def _stereo_pairs(self, sess, stream0, pairs, views):
+        return ((self.live_streams if sess == SESSION_MULTI else 1) - stream0) // max(int(views), 1) if pairs is None else int(pairs)
+
+    def history_view_stereo_device(self, first_column, factor, groups, views=2, a=0, b=1, stream0=0, pairs=None, map=None,
+                                   want=("index", "pan"), session="multi", stream=None, **given):
+        """emspec_history_view_stereo_device: the stereo image of the history's groups, CUDA tensors [pairs][groups][rows].
+        Enqueues on `stream` (default: the current torch stream); does not synchronise."""
+        import torch
+        sess = _SESSIONS[session]
+        pairs = self._stereo_pairs(sess, stream0, pairs, views)
+        out = self._stereo_tensors((max(pairs, 0), max(int(groups), 0), self.rows), "cuda", want, given)
+        st = stream if stream is not None else torch.cuda.current_stream()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        m = _stereo_map(map)
+        self._chk(self._lib.emspec_history_view_stereo_device(self._h, sess, int(stream0), pairs, int(views), int(a), int(b),
+                                                              int(first_column), int(factor), int(groups),
+                                                              C.byref(m) if m is not None else None, ptr(out["level"]), ptr(out["index"]),
+                                                              ptr(out["pan"]), ptr(out["rgba"]), C.c_void_p(st.cuda_stream)))
+        return out
+
+    def history_view_stereo(self, first_column, factor, groups, views=2, a=0, b=1, stream0=0, pairs=None, map=None,
+                            want=("index", "pan"), session="multi", **given):
+        """emspec_history_view_stereo: for each pair (streams stream0 + p views + a / + b) the peak hold of each channel's groups
+        of `factor` stored columns, then the stereo law -> numpy arrays [pairs][groups][rows] (rgba + [4])."""
+        sess = _SESSIONS[session]
+        pairs = self._stereo_pairs(sess, stream0, pairs, views)
+        out = self._stereo_arrays((max(pairs, 0), max(int(groups), 0), self.rows), want, given)
+        m = _stereo_map(map)
+        self._chk(self._lib.emspec_history_view_stereo(self._h, sess, int(stream0), pairs, int(views), int(a), int(b),
+                                                       int(first_column), int(factor), int(groups),
+                                                       C.byref(m) if m is not None else None, _np_ptr(out["level"]),
+                                                       _np_ptr(out["index"]), _np_ptr(out["pan"]), _np_ptr(out["rgba"])))
+        return out
 
     # -- live audio history (include/emspec.h: emspec_set_live_audio / emspec_audio_view / emspec_audio_batch) ------------------
     def _audio_streams(self, sess, stream0, streams):

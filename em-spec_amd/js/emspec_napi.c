@@ -1384,6 +1384,127 @@ static napi_value HistoryView(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* Stereo image (include/emspec.h: emspec_make_stereo_colormap / emspec_set_stereo_colormap / emspec_batch_pcm_stereo /
+ * emspec_history_view_stereo).  map = Float32Array(5) [dbTop, dbRange, gateDb, shiftDb, panRangeDb] or null (the engine's
+ * configuration, shift 0, 12 dB to a side); outputs: level Float32Array, index / pan Uint8Array, rgba Uint8Array (x 4), each of
+ * exactly pairs * columns (groups) * rows cells or null.
+ * stereoColormap(brightness) -> Uint8Array(33 * 1024)
+ * setStereoColormap(handle, palette:Uint8Array(33 * 1024))
+ * batchPcmStereo(handle, src, sampleType, channels, views, mix, sources, fftSize, hop, reassign, a, b, map, outLevel, outIndex,
+ *                outPan, outRgba) -> columns
+ * historyViewStereo(handle, session, stream0, pairs, views, a, b, firstColumn, factor, groups, map, outLevel, outIndex, outPan,
+ *                   outRgba) */
+static int get_stereo_map(napi_env env, napi_value v, emspec_stereo_map* m, int* have) {
+    void* mp = NULL; size_t mlen = 0;
+    if (!get_typed(env, v, napi_float32_array, &mp, &mlen, 1) || (mp && mlen != 5)) {
+        napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "map must be a Float32Array(5) or null");
+        return 0;
+    }
+    *have = mp != NULL;
+    if (mp) { const float* f = (const float*)mp; m->db_top = f[0]; m->db_range = f[1]; m->gate_db = f[2]; m->shift_db = f[3]; m->pan_range_db = f[4]; }
+    return 1;
+}
+/* the four outputs from argv[0 .. 3]; *cells: what the first one given holds (0: none) */
+static int get_stereo_outs(napi_env env, const napi_value* argv, void** out, size_t* len) {
+    static const napi_typedarray_type ty[4] = {napi_float32_array, napi_uint8_array, napi_uint8_array, napi_uint8_array};
+    static const char* const what[4] = {"outLevel must be a Float32Array or null", "outIndex must be a Uint8Array or null",
+                                        "outPan must be a Uint8Array or null", "outRgba must be a Uint8Array or null"};
+    for (int i = 0; i < 4; ++i) {
+        out[i] = NULL; len[i] = 0;
+        if (!get_typed(env, argv[i], ty[i], &out[i], &len[i], 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", what[i]); return 0; }
+    }
+    return 1;
+}
+static int stereo_outs_hold(napi_env env, void* const* out, const size_t* len, size_t cells) {
+    for (int i = 0; i < 4; ++i)
+        if (out[i] && len[i] != (i == 3 ? 4 * cells : cells)) {
+            napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "every output must hold exactly pairs*columns*rows cells (RGBA: x 4)");
+            return 0;
+        }
+    return 1;
+}
+static napi_value StereoColormap(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    double b = 0.5;
+    if (argc > 0) NAPI_OK_OR_RETURN(env, napi_get_value_double(env, argv[0], &b));
+    napi_value ab, out; void* data;
+    const size_t bytes = (size_t)EMSPEC_STEREO_PAN_LEVELS * 1024;
+    NAPI_OK_OR_RETURN(env, napi_create_arraybuffer(env, bytes, &data, &ab));
+    if (emspec_make_stereo_colormap((float)b, (uint8_t*)data) != EMSPEC_OK) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "brightness must be >= 0"); return NULL; }
+    NAPI_OK_OR_RETURN(env, napi_create_typedarray(env, napi_uint8_array, bytes, ab, 0, &out));
+    return out;
+}
+static napi_value SetStereoColormap(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    void* pal; size_t len;
+    if (argc < 2 || !get_typed(env, argv[1], napi_uint8_array, &pal, &len, 0) || len != (size_t)EMSPEC_STEREO_PAN_LEVELS * 1024) {
+        napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "the stereo palette must be a Uint8Array(33 * 1024) of RGBA");
+        return NULL;
+    }
+    int rc = emspec_set_stereo_colormap(h->e, (const uint8_t*)pal);
+    if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
+    return NULL;
+}
+static napi_value BatchPcmStereo(napi_env env, napi_callback_info info) {
+    size_t argc = 17; napi_value argv[17];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 17) {
+        napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "batchPcmStereo(handle, src, sampleType, channels, views, mix, sources, fftSize, hop, reassign, a, b, map, outLevel, outIndex, outPan, outRgba)");
+        return NULL;
+    }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    emspec_pcm_format fmt; void* src; size_t bytes;
+    if (!get_pcm_format(env, argv + 2, &fmt) || !get_pcm_source(env, argv[1], &fmt, &src, &bytes)) return NULL;
+    int32_t sources, n, hop, a, b; int64_t frames; bool reassign;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[6], &sources));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[7], &n));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[8], &hop));
+    NAPI_OK_OR_RETURN(env, napi_coerce_to_bool(env, argv[9], &argv[9]));
+    NAPI_OK_OR_RETURN(env, napi_get_value_bool(env, argv[9], &reassign));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[10], &a));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[11], &b));
+    if (!pcm_frames(env, &fmt, sources, bytes, &frames)) return NULL;
+    emspec_stereo_map m; int have = 0;
+    if (!get_stereo_map(env, argv[12], &m, &have)) return NULL;
+    void* out[4]; size_t len[4];
+    if (!get_stereo_outs(env, argv + 13, out, len)) return NULL;
+    const int64_t C = frames > 0 ? emspec_num_columns(frames, n, hop) : 0;
+    /* (C <= 0: an invalid format or shape - the library rejects it with its message before it touches any output) */
+    if (C > 0 && !stereo_outs_hold(env, out, len, (size_t)sources * (size_t)C * (size_t)h->rows)) return NULL;
+    int rc = emspec_batch_pcm_stereo(h->e, src, &fmt, sources, frames, n, hop, reassign ? 1 : 0, a, b, have ? &m : NULL, (float*)out[0],
+                                     (uint8_t*)out[1], (uint8_t*)out[2], (uint8_t*)out[3]);
+    if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
+    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int64(env, C, &r));
+    return r;
+}
+static napi_value HistoryViewStereo(napi_env env, napi_callback_info info) {
+    size_t argc = 15; napi_value argv[15];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 15) {
+        napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "historyViewStereo(handle, session, stream0, pairs, views, a, b, firstColumn, factor, groups, map, outLevel, outIndex, outPan, outRgba)");
+        return NULL;
+    }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    int32_t v32[6] = {0}, factor = 0; int64_t first = 0, groups = 0;   /* session, stream0, pairs, views, a, b */
+    for (int i = 0; i < 6; ++i) NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[1 + i], &v32[i]));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[7], &first));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[8], &factor));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[9], &groups));
+    emspec_stereo_map m; int have = 0;
+    if (!get_stereo_map(env, argv[10], &m, &have)) return NULL;
+    void* out[4]; size_t len[4];
+    if (!get_stereo_outs(env, argv + 11, out, len)) return NULL;
+    /* (pairs or groups below 1: the library rejects the call with its message before it touches an output) */
+    if (v32[2] >= 1 && groups >= 1 && !stereo_outs_hold(env, out, len, (size_t)v32[2] * (size_t)groups * (size_t)h->rows)) return NULL;
+    int rc = emspec_history_view_stereo(h->e, v32[0], v32[1], v32[2], v32[3], v32[4], v32[5], first, factor, groups, have ? &m : NULL,
+                                        (float*)out[0], (uint8_t*)out[1], (uint8_t*)out[2], (uint8_t*)out[3]);
+    if (rc != EMSPEC_OK) return throw_status(env, h->e, rc);
+    return NULL;
+}
+
 /* Live audio history (include/emspec.h: emspec_set_live_audio / emspec_live_audio / emspec_audio_view / emspec_audio_batch).
  * setLiveAudio(handle, samples): W samples per stream, 0 clears
  * liveAudio(handle, session, stream) -> [end, first] or null (no audio history, or the session has no such stream)
@@ -1720,6 +1841,10 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"setLiveHistory", NULL, SetLiveHistory, NULL, NULL, NULL, napi_default, NULL},
         {"liveHistory", NULL, LiveHistory, NULL, NULL, NULL, napi_default, NULL},
         {"historyView", NULL, HistoryView, NULL, NULL, NULL, napi_default, NULL},
+        {"stereoColormap", NULL, StereoColormap, NULL, NULL, NULL, napi_default, NULL},
+        {"setStereoColormap", NULL, SetStereoColormap, NULL, NULL, NULL, napi_default, NULL},
+        {"batchPcmStereo", NULL, BatchPcmStereo, NULL, NULL, NULL, napi_default, NULL},
+        {"historyViewStereo", NULL, HistoryViewStereo, NULL, NULL, NULL, napi_default, NULL},
         {"setLiveAudio", NULL, SetLiveAudio, NULL, NULL, NULL, napi_default, NULL},
         {"liveAudio", NULL, LiveAudio, NULL, NULL, NULL, napi_default, NULL},
         {"audioView", NULL, AudioView, NULL, NULL, NULL, napi_default, NULL},

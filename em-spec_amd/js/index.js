@@ -110,6 +110,50 @@ class Engine {
   }
 
   /**
+   * Stereo image (emspec_set_stereo_colormap / emspec_batch_pcm_stereo / emspec_history_view_stereo, DESIGN.md §3.16): level and
+   * balance of a channel pair in ONE picture, composed on the device - brightness from the louder channel's dB, hue from the
+   * difference of the two.  A pair is two views of one source: a, b index format.views (['left', 'right']: a = 0, b = 1;
+   * ['left', 'right', 'mid', 'side'] with a = 2, b = 3 is a width display).  map = {dbTop, dbRange, gateDb, shiftDb,
+   * panRangeDb = 12} (default: the engine's configuration); want: any of 'level' (Float32Array, dB of the louder channel),
+   * 'index', 'pan' (Uint8Array; pan 0 = all a .. 16 = centre .. 32 = all b), 'rgba' (Uint8Array x 4 = palette[pan][index]).
+   * setStereoColormap(palette): Uint8Array(33 * 1024), e.g. makeStereoColormap(brightness); a new engine holds that of 0.5.
+   * computeStereo(src, sources, frames, format, fftSize, hop, reassign, {a = 0, b = 1, map, want = ['index', 'pan']}) ->
+   *   {columns, level, index, pan, rgba}: arrays of sources * columns * rows cells.  Only what is asked for crosses PCIe on the
+   *   way out.  Throws EMSPEC_ERR_STATE while timeReduce > 1.
+   * historyViewStereo({stream0 = 0, views = 2, pairs = all from stream0, a = 0, b = 1, firstColumn, factor = 1, groups, map,
+   *   want = ['index', 'pan']}) -> the same of the live history's groups (see historyView), pairs * groups * rows cells: what a
+   *   live stereo view redraws from.
+   */
+  setStereoColormap(palette) { native.setStereoColormap(this._h, palette); }
+  _stereoOut(want, cells) {
+    const out = {};
+    if (want.includes('level')) out.level = new Float32Array(cells);
+    if (want.includes('index')) out.index = new Uint8Array(cells);
+    if (want.includes('pan')) out.pan = new Uint8Array(cells);
+    if (want.includes('rgba')) out.rgba = new Uint8Array(4 * cells);
+    return out;
+  }
+  computeStereo(src, sources, frames, format, fftSize, hop, reassign = true, opts = {}) {
+    if (src.byteLength !== sources * frames * format.frameBytes) throw Object.assign(new Error('src must hold sources * frames frames'), { code: 'EMSPEC_ERR_INVALID_ARG' });
+    const C = Math.max(0, native.numColumns(frames, fftSize, hop));
+    const out = this._stereoOut(opts.want || ['index', 'pan'], Math.max(0, sources) * C * this.rows);
+    out.columns = native.batchPcmStereo(this._h, src, format.sampleType, format.channels, format.views, format.mix, sources, fftSize, hop,
+      !!reassign, opts.a === undefined ? 0 : opts.a | 0, opts.b === undefined ? 1 : opts.b | 0, stereoMap(opts.map),
+      out.level || null, out.index || null, out.pan || null, out.rgba || null);
+    return out;
+  }
+  historyViewStereo(opts) {
+    const stream0 = opts.stream0 | 0, views = opts.views === undefined ? 2 : opts.views | 0;
+    const pairs = opts.pairs === undefined ? Math.floor((this.streams - stream0) / Math.max(views, 1)) : opts.pairs | 0;
+    const groups = +opts.groups, factor = opts.factor === undefined ? 1 : opts.factor | 0;
+    const out = this._stereoOut(opts.want || ['index', 'pan'], Math.max(0, pairs) * Math.max(0, groups) * this.rows);
+    native.historyViewStereo(this._h, this._historySession(), stream0, pairs, views, opts.a === undefined ? 0 : opts.a | 0,
+      opts.b === undefined ? 1 : opts.b | 0, +opts.firstColumn, factor, groups, stereoMap(opts.map),
+      out.level || null, out.index || null, out.pan || null, out.rgba || null);
+    return out;
+  }
+
+  /**
    * Live audio history (emspec_set_live_audio / emspec_live_audio / emspec_audio_view / emspec_audio_batch, DESIGN.md §3.15):
    * the engine keeps the last `samples` samples every live call was fed, per stream, on the device - what a renderer needs when
    * FFT Size, Smoothing or Enhanced / Natural changes and the scroll-back image has to be computed again (Frequency Scale and
@@ -544,6 +588,14 @@ function makeColormap(brightness = 0.5, stops = undefined) {
   return lut;
 }
 
+/** The stereo palette built from makeColormap(brightness) (emspec_make_stereo_colormap): Uint8Array(33 * 1024), [pan][index][4] -
+ *  row 16 the colour map itself, rows towards 0 tinted warm (channel a louder), towards 32 cold (channel b louder). */
+function makeStereoColormap(brightness = 0.5) { return native.stereoColormap(brightness); }
+function stereoMap(map) {
+  if (!map) return null;
+  return Float32Array.of(map.dbTop, map.dbRange, map.gateDb, map.shiftDb || 0, map.panRangeDb === undefined ? 12 : map.panRangeDb);
+}
+
 /** Gradient stop tables for makeColormap().  'reference' is the ramp measured from the reference's
  *  settings screenshot (SURVEY.md §4); the others are plain conveniences, not claims about the
  *  reference's other (undocumented) maps. */
@@ -643,6 +695,7 @@ module.exports = {
   allocPinned: native.allocPinned,
   warpedEdges,
   makeColormap,
+  makeStereoColormap,
   colormapStops,
   commUniqueId: native.commUniqueId,
   numColumns: native.numColumns,

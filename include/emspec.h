@@ -1008,6 +1008,89 @@ int     emspec_audio_batch_device(emspec_engine* e, int32_t session, int32_t str
 int     emspec_audio_batch(emspec_engine* e, int32_t session, int32_t stream0, int32_t streams, int64_t first_sample,
                            int64_t count, int32_t n, int32_t hop, int32_t reassign, const emspec_out* out);
 
+/*
+ * ---- Stereo image: level and balance of a channel pair in ONE picture - brightness from the louder
+ * channel's dB, hue from the difference of the two - composed on the device from dB that is already there (a batch's
+ * workspace, the live history ring), so that a renderer need not pull both channels' dB over the bus and compare them on its
+ * own cores; [BUILD-DEFINED].  Nothing existing changes: every entry below is new.
+ *
+ * Streams.  A pair is two streams of one [S][C][R] array, chosen by (views, a, b): pair p uses streams p views + a (channel A)
+ * and p views + b (channel B); views >= 2, 0 <= a, b < views, a != b.  This is the PCM front end's stream numbering: views = 2,
+ * a = 0, b = 1 for left / right; views = 4 (L R M S) with (0, 1) for left / right and (2, 3) for mid / side as a width display.
+ *
+ * The law, per cell, on the two dB values x_a, x_b; all arithmetic binary32, one rounding per operation, no fused multiply-add.
+ * Scalars (computed on the host): lo = db_top - db_range (binary32), inv = (float)(1.0 / (double)db_range),
+ * inv_pan = (float)(1.0 / (double)pan_range_db).
+ *     level:   m = (x_b > x_a || x_a != x_a) ? x_b : x_a          the cell's own bits; a NaN only when both are
+ *     shifted: s = m + shift_db;  gated = s < gate_db
+ *     index:   0 if s is NaN, else the palette index of s under (lo, inv, gate_db) - the law of emspec_history_view
+ *     balance: d = x_b - x_a;  u = d * inv_pan;  if (u > 1) u = 1;  if (u < -1) u = -1;
+ *              pan = 16 + (int)rintf(u * 16.0f)  (round half to even);  pan = 16 if gated or d is NaN
+ *     rgba:    PAL[pan][index]                                    the engine's stereo palette, [33][256][4]
+ * Outputs: level (float32, NOT shifted), index, pan (bytes) and rgba; any may be NULL, not all.  The balance needs no power
+ * sum: a difference of dB values is the log of the energy ratio.
+ *
+ * Palette.  emspec_make_stereo_colormap(brightness, out[33][256][4]) builds it in integers from base =
+ * emspec_make_colormap(brightness): for row pan, t = pan - 16, w = |t|, K = t < 0 ? (255, 96, 32) : (32, 160, 255); for entry i,
+ * v = max(r, g, b) of base[i], per colour channel tint = (K_c v + 127) / 255 and out = (base_c (16 - w) + tint w + 8) / 16
+ * (truncating divisions); alpha is base's; row 16 is base itself.  emspec_set_stereo_colormap(e, rgba33x256x4) uploads any
+ * palette; a new engine holds the built one at the brightness of its default colour map (0.5).
+ *
+ * emspec_stereo_default_map(e, &map): the engine's db_top, db_range and gate_db, shift 0, pan_range_db = 12.
+ * emspec_stereo_device: the law on any device dB array [pairs views][cells]; outputs [pairs][cells] (rgba + [4]).
+ *   cells % 4 == 0; db_dev, level_dev, rgba_dev 16-byte and index_dev, pan_dev 4-byte aligned; pairs in 0 .. 65535, 0 a no-op.
+ *   Enqueues on hip_stream (NULL: the default stream); does not synchronise.
+ * emspec_stereo_host: the same definition in plain C++ on host arrays: no engine, no device.  `palette` ([33][256][4]) is
+ *   needed only with rgba.  The message of a refusal: emspec_last_error(NULL).
+ * emspec_batch_stereo_device: the law on exactly the dB emspec_batch_device(e, pcm_dev, S, L, n, hop, reassign, ..) would deliver
+ *   (the display post-process included), without that dB leaving the engine.  S % views == 0; outputs [S / views][C][R].
+ *   Chunks of whole pairs run through the engine workspace emspec_batch_peaks_device uses.
+ * emspec_batch_pcm_stereo: the host entry, from raw interleaved frames as emspec_batch_pcm takes them; views = fmt->views, a pair
+ *   is the views of one source.  Outputs [sources][C][R] host arrays, page-locked or pageable.  Only the requested outputs
+ *   cross the bus on the way out: 1 + 1 bytes (index, pan) or 4 (RGBA) per pair cell instead of 8 of dB.  emspec_set_wave_out is
+ *   honoured as by emspec_batch_pcm (the envelope of all sources x views streams).
+ * emspec_history_view_stereo_device / emspec_history_view_stereo: the live form.  Reads the live history ring: for each pair, the
+ *   peak hold of each channel's group - exactly emspec_history_view's dB of that stream - then the law.  Streams
+ *   stream0 .. stream0 + pairs views - 1 of the session; outputs [pairs][groups][rows].  Every rule of emspec_history_view
+ *   applies to BOTH streams of every pair: held range, factor, groups, alignment (level as its dB, pan as its index), the
+ *   ordering behind the session's launches.  A renderer calls it per redraw, like a mono view.
+ *
+ * Refusals.  The batch entries return EMSPEC_ERR_STATE while a time reduction is set (emspec_set_time_reduce(e, 1) turns it off).
+ * Every other refusal is EMSPEC_ERR_INVALID_ARG with a message naming the rule: views / a / b, pan_range_db or db_range not > 0,
+ * a NaN field, cells % 4, S % views, all outputs NULL, misalignment - and, for the views, those of emspec_history_view.  The
+ * engine stays usable.
+ */
+#define EMSPEC_STEREO_PAN_CENTRE 16
+#define EMSPEC_STEREO_PAN_LEVELS 33          /* balance byte 0 (all A / left) .. 32 (all B / right) */
+typedef struct emspec_stereo_map {
+    float db_top, db_range, gate_db, shift_db;   /* as emspec_view_map, applied to the level */
+    float pan_range_db;                          /* |dB_b - dB_a| that reads as fully to one side; > 0 */
+} emspec_stereo_map;                             /* 20 bytes */
+
+int     emspec_stereo_default_map(const emspec_engine* e, emspec_stereo_map* map);
+int     emspec_make_stereo_colormap(float brightness, uint8_t* rgba33x256x4);
+int     emspec_set_stereo_colormap(emspec_engine* e, const uint8_t* rgba33x256x4);
+int     emspec_stereo_device(emspec_engine* e, const float* db_dev, int32_t pairs, int32_t views, int32_t a, int32_t b,
+                             int64_t cells, const emspec_stereo_map* map,
+                             float* level_dev, uint8_t* index_dev, uint8_t* pan_dev, uint8_t* rgba_dev, void* hip_stream);
+int     emspec_stereo_host(const float* db, int64_t pairs, int32_t views, int32_t a, int32_t b, int64_t cells,
+                           const emspec_stereo_map* map, const uint8_t* palette,
+                           float* level, uint8_t* index, uint8_t* pan, uint8_t* rgba);
+int     emspec_batch_stereo_device(emspec_engine* e, const float* pcm_dev, int32_t S, int64_t L, int32_t n, int32_t hop,
+                                   int32_t reassign, int32_t views, int32_t a, int32_t b, const emspec_stereo_map* map,
+                                   float* level_dev, uint8_t* index_dev, uint8_t* pan_dev, uint8_t* rgba_dev, void* hip_stream);
+int     emspec_batch_pcm_stereo(emspec_engine* e, const void* src, const emspec_pcm_format* fmt, int32_t sources, int64_t frames,
+                                int32_t n, int32_t hop, int32_t reassign, int32_t a, int32_t b, const emspec_stereo_map* map,
+                                float* out_level, uint8_t* out_index, uint8_t* out_pan, uint8_t* out_rgba);
+int     emspec_history_view_stereo_device(emspec_engine* e, int32_t session, int32_t stream0, int32_t pairs, int32_t views,
+                                          int32_t a, int32_t b, int64_t first_column, int32_t factor, int64_t groups,
+                                          const emspec_stereo_map* map,
+                                          float* level_dev, uint8_t* index_dev, uint8_t* pan_dev, uint8_t* rgba_dev, void* hip_stream);
+int     emspec_history_view_stereo(emspec_engine* e, int32_t session, int32_t stream0, int32_t pairs, int32_t views,
+                                   int32_t a, int32_t b, int64_t first_column, int32_t factor, int64_t groups,
+                                   const emspec_stereo_map* map,
+                                   float* out_level, uint8_t* out_index, uint8_t* out_pan, uint8_t* out_rgba);
+
 #ifdef __cplusplus
 }
 #endif
