@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "emspec_row_hint.h"
 #include "emspec_seg_plan.h"
 
 namespace emspec {
@@ -201,19 +202,22 @@ __device__ __forceinline__ int row_lookup(const float* eb, int R, int wtop, floa
     return lo;
 }
 
-// Row lookup with a log2 hint and an exact +-1 correction against the table: same result as
-// the binary search.  The hint is off by less than one row on every axis the host hands over
-// with log_rows = 1 (emspec_tables.h: hint_rows_ok bounds the v_log_f32 and float32 rounding
-// errors below a quarter of a row; a narrower axis comes with log_rows = 0 and is searched);
-// the two exact compares against the table decide.  Verified around every edge by
-// tests/test_gpu_parity.py and tests/test_gpu_axes.py (emspec_debug_row_lookup).  Garbage /
-// NaN inputs map to row -1 through the range test.
+// Row lookup with a log2 hint and one exact compare against the table: same result as the binary search.  The hint
+// f = fma(v_log_f32(kh), rscale, c0) is kh's position on the axis in rows plus one half, off by less than half a row on every
+// axis the host hands over with log_rows = 1 (emspec_tables.h: hint_rows_ok bounds the v_log_f32 and float32 rounding errors
+// below a quarter of a row; a narrower axis comes with log_rows = 0 and is searched), so its integer part is one of the two
+// edges around kh and the compare against that edge decides: ONE table read per bin (the two-edge form, eb[r0] and eb[r0 + 1]
+// with a correction either way, cost twice the LDS-array cycles: profiles/lds_conflict_model.txt).  The decision itself is
+// emspec_row_hint.h: row_from_hint, which tests/test_row_lookup_cpu.py runs on the CPU; verified on the device around every
+// edge by tests/test_gpu_parity.py and tests/test_gpu_axes.py (emspec_debug_row_lookup).  Garbage inputs map to row -1 / R:
+// a NaN k-hat yields -1 (the two-edge form read it as row 0); callers gate on a finite power first, so no used result changed.
 struct HintLookup {
-    const float* eb; int R; float e0, eR, l2e0, rscale; int wtop;   // wtop > 0: table is not log-spaced, search it
+    const float* eb; int R; float e0, eR, l2e0, rscale, c0; int wtop;   // wtop > 0: table is not log-spaced, search it
     __device__ __forceinline__ void init(const float* table, const float* gtable, int rows, int log_rows = 1) {
         eb = table; R = rows; e0 = gtable[0]; eR = gtable[rows];
         l2e0 = log2f(e0);
         rscale = (float)rows / (log2f(eR) - l2e0);
+        c0 = row_hint_offset(l2e0, rscale);
         wtop = 0;
         if (!log_rows) { wtop = 1; while (wtop * 2 < rows) wtop *= 2; }
     }
@@ -228,16 +232,10 @@ struct HintLookup {
             }
             return lo;
         }
-        int r0 = (int)((__log2f(kh) - l2e0) * rscale);
-        r0 = max(0, min(r0, R - 1));
-        const float lo = eb[r0], hi = eb[r0 + 1];
-        r0 += (kh >= hi) ? 1 : 0;
-        r0 -= (kh < lo) ? 1 : 0;
-        return r0;
+        return row_signed_log(kh);
     }
-    // Row, or -1 / R when kh lies below / at-or-above the table: the +-1 correction of the clamped hint walks
-    // off the table exactly when kh is out of range, so `(unsigned)row < R` replaces the two range compares.
-    // (NaN compares false and would read as in range: callers gate on a finite power first.)
+    // Row, or -1 / R when kh lies below / at-or-above the table: the nearest edge of an out-of-range kh is the table's first
+    // or last, and the compare against it says so, so `(unsigned)row < R` replaces the two range compares.
     __device__ __forceinline__ int row_signed(float kh) const {
         if (wtop) return in_range(kh) ? row_unchecked(kh) : -1;
         return row_unchecked(kh);
@@ -245,12 +243,7 @@ struct HintLookup {
     // row_signed for a table the caller KNOWS is log-spaced (wtop == 0): no branch, so the lookups of a thread's
     // consecutive bins stay in one basic block and their table reads are issued together
     __device__ __forceinline__ int row_signed_log(float kh) const {
-        int r0 = (int)((__log2f(kh) - l2e0) * rscale);
-        r0 = max(0, min(r0, R - 1));
-        const float lo = eb[r0], hi = eb[r0 + 1];
-        r0 += (kh >= hi) ? 1 : 0;
-        r0 -= (kh < lo) ? 1 : 0;
-        return r0;
+        return row_from_hint(row_hint(__log2f(kh), rscale, c0), kh, eb, R);
     }
     __device__ __forceinline__ int operator()(float kh) const { return in_range(kh) ? row_unchecked(kh) : -1; }
 };

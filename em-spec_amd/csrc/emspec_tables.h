@@ -144,19 +144,25 @@ inline bool low_share_ok(const Axis& a, int row) {
 }
 
 // May the FAST kernels' log2 row hint (emspec_device.h: HintLookup) serve a log axis from e0 to eR bins in `rows` rows?  The hint
-// h = (v_log_f32(k) - l2e0) * rscale, l2e0 = log2f(e0), rscale = rows / (log2f(eR) - l2e0), is corrected by one row either way
-// against the table, so it must lie within one row of k's position.  With u = 2^-23 (one float32 ulp is at most u |x|),
+// f = fma(v_log_f32(k), rscale, c0), l2e0 = log2f(e0), rscale = rows / (log2f(eR) - l2e0), c0 = fma(-l2e0, rscale, 1/2)
+// (emspec_row_hint.h), is k's position on the axis in rows plus one half; its integer part names the NEAREST edge, and one
+// compare against that edge decides the row.  That is right while the position's error stays below HALF a row (the integer
+// part is then one of the two edges around k).  With u = 2^-23 (one float32 ulp is at most u |x|),
 // L = max(1, |log2 e0|, |log2 eR|) the largest |log2| of a k on the axis, W = log2(eR / e0) <= 2 L and rho = rows / W rows per
-// unit of log2, its error in rows is at most
+// unit of log2, the error in rows is at most
 //     rho * (u L      v_log_f32: 1 ulp, the ISA documentation's figure
 //          + u L      l2e0: log2f is within 1 ulp
-//          + u L      the difference, rounded once: u W / 2
-//          + 2 u L    rscale's denominator: two logarithms and a rounding, relative to W, on a hint of at most `rows` rows
+//          + u L      c0, rounded once: u (rho L + 1/2) / 2 - half of this line; the other half is spare
+//          + 2 u L    rscale's denominator: two logarithms and a rounding, relative to W, on a hint of at most `rows` rows (the
+//                     SAME rscale multiplies the logarithm and l2e0, so its error scales their difference, as it did the product's)
 //          + 2 u)     e0 and eR are the float32 table's ends, and an edge sits half an ulp from its log-spaced place: 1.44 u / 2 each
-//     + 2 u rows      the quotient rscale and the product, rounded once each: u / 2 of at most `rows`, doubled
+//     + 2 u rows      the quotient rscale and the fma's one rounding of a value of at most `rows` + 1: u / 2 each, doubled
 //   <= u (8 rho L + 2 rows),
-// which must stay below 1 / 4: a safety factor of 4, since the instruction's figure is documented, not measured here.  k off the
-// axis by d in log2 adds d u to the error and d rho to the distance, so the clamped hint still ends on the first or last row.
+// which must stay below 1 / 4: a safety factor of 2 against the half row, since the instruction's figure is documented, not
+// measured here.  (The earlier two-edge form, h = (log - l2e0) * rscale corrected by one row either way against eb[r0] and
+// eb[r0 + 1], needed only "within one row" and had the same terms: the difference's rounding where c0's stands now, and two
+// roundings of at most `rows`.  The bound, and so the set of hinted axes, did not change.)  k off the
+// axis by d in log2 adds d u to the error and d rho to the distance, so the clamped hint still ends on the first or last edge.
 // The default axis has 8 rho L + 2 rows = 1.3e4 at 1024 rows, one octave in 4096 rows 4.3e5; the bound, 2^21, is reached near
 // 20,000 rows per unit of log2 (a row 5e-5 wide, 290 float32 ulp at 8192 bins).  Narrower axes are searched (PlanDev::log_rows
 // = 0, the generic per-bin core): the same rows, slower.  spec_log2: the same answer on every host.
