@@ -478,6 +478,8 @@ int emspec_batch_gather(emspec_engine* e, const float* pcm, int32_t S, int64_t L
     if (!e || !pcm) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument");
     if (e->wave_out)
         return fail(e, EMSPEC_ERR_STATE, "the gather delivers no waveform envelope: not available while emspec_set_wave_out is set (NULL clears it)");
+    if (e->level_out || e->cross_out)
+        return fail(e, EMSPEC_ERR_STATE, "the gather delivers no level or cross records: not available while emspec_set_level_out or emspec_set_cross_out is set (NULL clears them)");
     emspec_comm_state* c = e->comm;
     if (!has_comm(c)) return fail(e, EMSPEC_ERR_STATE, "no communicator: call emspec_comm_init first");
     if (root < 0 || root >= c->world) return fail(e, EMSPEC_ERR_INVALID_ARG, "root out of range");

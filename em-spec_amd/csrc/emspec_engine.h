@@ -138,7 +138,8 @@ struct HostJob {
     bool whole_streams = false;
     int halo_D = 0, min_streams = 1;
     // what is delivered: exactly one of out / pk / pko / stereo (and beside it, while emspec_set_wave_out is set, the envelope of the
-    // streams' samples: emspec_engine::wave_out)
+    // streams' samples: emspec_engine::wave_out; while emspec_set_level_out / emspec_set_cross_out are set, their level and cross
+    // records: emspec_engine::level_out, cross_out)
     const emspec_out* out = nullptr;
     const PackedOut* pk = nullptr;
     const PeaksOut* pko = nullptr;
@@ -228,6 +229,10 @@ struct emspec_engine {
     char* d_full = nullptr; size_t full_bytes = 0;
     // waveform envelope (emspec_set_wave_out): the caller's pair array the host pipeline also fills, or null
     emspec_wave* wave_out = nullptr; int64_t wave_capacity = 0;
+    // level meters (emspec_set_level_out / emspec_set_cross_out): the caller's record arrays the host pipeline
+    // also fills, or null; cross_a / cross_b: the views of each PCM source whose products the cross records sum
+    emspec_level* level_out = nullptr; int64_t level_capacity = 0;
+    emspec_cross* cross_out = nullptr; int64_t cross_capacity = 0; int cross_a = 0, cross_b = 0;
     // overlays of the streaming calls (emspec_set_live_peaks / emspec_set_live_wave), for both sessions below: the caller's
     // arrays (null: off) and their capacities in pairs
     emspec_peak* live_peaks = nullptr; int64_t live_peaks_capacity = 0; int live_peaks_k = 0; float live_peaks_min_db = 0.0f;

@@ -50,6 +50,14 @@ int plan_pipe(Pipe& p) {
     p.V = j.dec ? j.dec->views : 1; p.fb = j.dec ? pcm_frame_bytes(*j.dec) : (int)sizeof(float);
     if (e->wave_out && (int64_t)j.S * p.V * p.Cr > e->wave_capacity)
         return fail(e, EMSPEC_ERR_INVALID_ARG, "the envelope set with emspec_set_wave_out is too small: it needs streams x delivered columns pairs");
+    if (e->level_out && (int64_t)j.S * p.V * p.Cr > e->level_capacity)
+        return fail(e, EMSPEC_ERR_INVALID_ARG, "the array set with emspec_set_level_out is too small: it needs streams x delivered columns records");
+    if (e->cross_out && !j.dec)
+        return fail(e, EMSPEC_ERR_STATE, "cross records are of a PCM source's views: not available on float streams while emspec_set_cross_out is set (NULL clears it)");
+    if (e->cross_out && (e->cross_a >= p.V || e->cross_b >= p.V))
+        return fail(e, EMSPEC_ERR_INVALID_ARG, "the channels a and b set with emspec_set_cross_out must be in 0 .. views - 1 of the call's format");
+    if (e->cross_out && (int64_t)j.S * p.Cr > e->cross_capacity)
+        return fail(e, EMSPEC_ERR_INVALID_ARG, "the array set with emspec_set_cross_out is too small: it needs sources x delivered columns records");
     if (!e->stream_in) HIPCHK(e, hipStreamCreateWithFlags(&e->stream_in, hipStreamNonBlocking));
     if (!e->stream_out) HIPCHK(e, hipStreamCreateWithFlags(&e->stream_out, hipStreamNonBlocking));
     for (hipEvent_t& ev : e->pipe_ev) if (!ev) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -61,6 +69,8 @@ int plan_pipe(Pipe& p) {
     p.outs[kIdx] = OutRow{(char*)o.index, o.index || j.pk ? (size_t)1 : 0};
     p.outs[kPeaks] = OutRow{j.pko ? (char*)j.pko->peaks : nullptr, j.pko ? j.pko->k * sizeof(emspec_peak) : 0};
     p.outs[kWave] = OutRow{(char*)e->wave_out, e->wave_out ? sizeof(emspec_wave) : 0};   // (beside any of them: emspec_set_wave_out)
+    p.outs[kLevel] = OutRow{(char*)e->level_out, e->level_out ? sizeof(emspec_level) : 0};   // (likewise: emspec_set_level_out, _cross_out)
+    p.outs[kCross] = OutRow{(char*)e->cross_out, e->cross_out ? sizeof(emspec_cross) : 0};
     if (const StereoHostOut* so = j.stereo) {   // (the dB columns are staged for the compose kernel and stay on the device)
         p.outs[kSLevel] = OutRow{(char*)so->level, so->level ? (size_t)4 : 0};
         p.outs[kSIdx] = OutRow{(char*)so->index, so->index ? (size_t)1 : 0};
@@ -98,7 +108,7 @@ int plan_pipe(Pipe& p) {
 
 // What unit u delivers: fn(where in the caller's array, byte offset in the unit's set, bytes) for every span of every row that
 // is copied out.  (The peak lists count in columns, and a set holds those of the unit's kept columns only, span after span; so
-// do the envelope's pairs, in delivered columns: wave_span_of.)
+// do the envelope's pairs and the level meters' records, in delivered columns: wave_span_of, cross_span_of.)
 template <class F>
 void for_pieces(const Pipe& p, int u, F&& fn) {
     for (int k = 0; k < spans_of(p.items[u], p.C, p.V); ++k) {
@@ -112,6 +122,14 @@ void for_pieces(const Pipe& p, int u, F&& fn) {
             } else if (o.host && w != kPeaks) fn(o.host + sp.to * o.unit, off + sp.from * o.unit, sp.cells * o.unit);
             if (o.host && w == kPeaks) fn(o.host + sp.to / p.R * o.unit, off + k * cols * o.unit, cols * o.unit);
         }
+        if (const OutRow& o = p.outs[kLevel]; o.host) {   // the level records: the envelope's spans
+            const Span ws = wave_span_of(p.items[u], p.C, p.V, k, p.f);
+            fn(o.host + ws.to * o.unit, p.g.out_off(kLevel) + ws.from * o.unit, ws.cells * o.unit);
+        }
+    }
+    if (const OutRow& o = p.outs[kCross]; o.host) {   // the cross records: one span of sources' delivered columns per unit
+        const Span cs = cross_span_of(p.items[u], p.C, p.f);
+        fn(o.host + cs.to * o.unit, p.g.out_off(kCross) + cs.from * o.unit, cs.cells * o.unit);
     }
     // the stereo image: one span of pair cells per unit
     const Span ss = stereo_span_of(p.items[u], p.C, p.R);
@@ -273,6 +291,13 @@ void run_units(Pipe& p) {
         if (q.wave && herr == hipSuccess) {
             const WaveRun wr = wave_run_of(it, j.n, j.hop, f);
             herr = launch_wave(q.pcm, it.sc * V, it.samples, wr.first, wr.cols, j.hop, f, q.wave, wr.pairs, e->stream);
+        }
+        // 3d'. level meters: the same windows, one level record per stream and one cross record per source (level.hip.inc)
+        if ((q.level || q.cross) && herr == hipSuccess) {
+            const WaveRun wr = wave_run_of(it, j.n, j.hop, f);
+            if (q.level) herr = launch_level(q.pcm, it.sc * V, it.samples, wr.first, wr.cols, j.hop, f, q.level, wr.pairs, e->stream);
+            if (q.cross && herr == hipSuccess)
+                herr = launch_cross(q.pcm, it.sc, V, e->cross_a, e->cross_b, it.samples, wr.first, wr.cols, j.hop, f, q.cross, wr.pairs, e->stream);
         }
         // 3e. stereo image: the unit's sc sources are sc pairs of V streams, composed over all the unit's columns (stereo.hip.inc)
         if (j.stereo && herr == hipSuccess) {

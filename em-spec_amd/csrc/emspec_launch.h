@@ -283,6 +283,15 @@ hipError_t launch_peaks(const float* db, int64_t columns, int R, int k, float mi
 // pairs apart, 8-byte aligned.  The caller guarantees first + cols * hop <= the samples a stream holds.
 hipError_t launch_wave(const float* pcm, int S, int64_t stride, int64_t first, int64_t cols, int hop, int f, void* out, int64_t out_stride,
                        hipStream_t st);
+// level meters (level.hip.inc): the envelope's windows - S streams `stride` samples apart, groups of f columns of `hop` samples
+// from `first` on, `cols` columns - give one 24-byte level record each (sum of squares in two limbs, peak, odd count; the
+// samples in units of 2^-24) into out [S] x ceil(cols / f), out_stride records apart, 8-byte aligned; launch_cross: per pair p
+// of streams p views + a and p views + b one 16-byte cross record (sum of products in two limbs) into out [pairs] x ceil(cols / f).
+// The caller guarantees first + cols * hop <= the samples a stream holds and f * hop <= 2^30.
+hipError_t launch_level(const float* pcm, int S, int64_t stride, int64_t first, int64_t cols, int hop, int f, void* out, int64_t out_stride,
+                        hipStream_t st);
+hipError_t launch_cross(const float* pcm, int pairs, int views, int a, int b, int64_t stride, int64_t first, int64_t cols, int hop, int f,
+                        void* out, int64_t out_stride, hipStream_t st);
 // PCM front end (pcm.hip.inc): `frames` interleaved frames of `sources` sources (source i at src + i * src_stride_bytes, device
 // memory or page-locked host memory, any byte offset that is a multiple of the sample size) -> float32 streams, stream
 // i * views + v at out + (i * views + v) * out_stride.  sample_type: kPcmS16 .. kPcmF32 (the values of include/emspec.h's

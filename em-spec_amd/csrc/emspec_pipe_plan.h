@@ -58,12 +58,15 @@ inline std::vector<PipeItem> pipe_items(int S, int64_t L, int64_t C, int n, int 
 // the packed entries stage the index for the wire images only); `unit`: bytes per cell - peaks: per column, k pairs - or 0
 // without that array.  Where the unit's copy lies in a staging set: Stage::out_off.  kWave: the waveform envelope of the samples
 // (emspec_set_wave_out), one pair per DELIVERED column.  kSLevel .. kSRgba: the stereo image (emspec_batch_pcm_stereo; DESIGN.md
-// §3.16), one cell per PAIR cell - a pair is the V streams of one source, so a unit's sc sources give sc pairs.
-enum { kDb, kRgba, kIdx, kPeaks, kWave, kSLevel, kSIdx, kSPan, kSRgba, kOutRows };
+// §3.16), one cell per PAIR cell - a pair is the V streams of one source, so a unit's sc sources give sc pairs.  kLevel: the
+// level records of the samples (emspec_set_level_out), one per stream and DELIVERED column, as the envelope's
+// pairs; kCross: the cross records of two views of each source (emspec_set_cross_out), one per SOURCE and delivered column.
+enum { kDb, kRgba, kIdx, kPeaks, kWave, kSLevel, kSIdx, kSPan, kSRgba, kLevel, kCross, kOutRows };
 struct OutRow { char* host; size_t unit; };
 inline bool stereo_rows(const OutRow* o) { return o[kSLevel].unit || o[kSIdx].unit || o[kSPan].unit || o[kSRgba].unit; }
 // The bytes `streams` streams leave the device with (pipe_units): the rows' - or the wire images', about a fifth of the index
-// (the envelope's 8 bytes per delivered column are not counted: a batch is cut the same way with and without it)
+// (the envelope's 8 bytes per delivered column are not counted, nor the level meters' 24 and 16: a batch is cut the same way
+// with and without them)
 inline size_t bytes_out_estimate(const OutRow* o, bool packed, size_t streams, int64_t C, int64_t Cr, int R) {
     const size_t cell = o[kDb].unit + o[kRgba].unit + o[kIdx].unit;
     return packed ? streams * Cr * R / 5 : streams * Cr * R * cell + streams * C * o[kPeaks].unit;
@@ -76,8 +79,9 @@ inline size_t stereo_bytes_out(const OutRow* o, size_t pairs, int64_t C, int R) 
 // (db / rgba / idx: what the unit's kernels write; odb / orgba / oidx: what is delivered - the same arrays, or with a time
 // reduction the reduced columns beside them; peaks: the unit's peak lists, emspec_batch_peaks)
 // slevel / sidx / span / srgba: the stereo image of the unit's pairs, composed from db
+// level / cross: the level and cross records of the unit's delivered columns
 struct Set { float* pcm; float* db; uint8_t* rgba; uint8_t* idx; uint8_t* wire; char* raw; float* odb; uint8_t* orgba; uint8_t* oidx; emspec_peak* peaks; emspec_wave* wave;
-             float* slevel; uint8_t* sidx; uint8_t* span; uint8_t* srgba; };
+             float* slevel; uint8_t* sidx; uint8_t* span; uint8_t* srgba; emspec_level* level; emspec_cross* cross; };
 // The staging set: every array at the size the largest unit needs, in the order of off()'s list.
 struct Stage {
     size_t in = 0, db = 0, rgba = 0, idx = 0, wire = 0;   // (wire: one slot of that many bytes per stream of the unit)
@@ -88,13 +92,17 @@ struct Stage {
                                                           // array above, so that a job without an envelope keeps every offset and size
     size_t stereo[4] = {};                                // emspec_batch_pcm_stereo: level, index, pan, RGBA per pair cell of the unit;
                                                           // behind the envelope's and empty for every other job, for the same reason
+    size_t level = 0, cross = 0;                          // emspec_set_level_out / _cross_out: a record per stream (per source) and
+                                                          // delivered column of the unit; last and empty while cleared, likewise
     bool reduced = false; int chunk = 1;                  // (chunk: streams in the largest unit)
     size_t off(int a) const {   // byte offset in a set of its a-th array
-        const size_t s[15] = {in, db, rgba, idx, wire * chunk, raw, rdb, rrgba, ridx, peaks, wave, stereo[0], stereo[1], stereo[2], stereo[3]};
+        const size_t s[17] = {in, db, rgba, idx, wire * chunk, raw, rdb, rrgba, ridx, peaks, wave, stereo[0], stereo[1], stereo[2], stereo[3],
+                              level, cross};
         return std::accumulate(s, s + a, (size_t)0);
     }
-    size_t bytes() const { return off(15); }
-    // ... of row w's delivered copy: the reduced array, or without a reduction what the kernels wrote
+    size_t bytes() const { return off(17); }
+    // ... of row w's delivered copy: the reduced array, or without a reduction what the kernels wrote (kLevel, kCross: arrays
+    // 15 and 16, behind the stereo rows)
     size_t out_off(int w) const { return off(w >= kSLevel ? 11 + (w - kSLevel) : w == kWave ? 10 : w == kPeaks ? 9 : reduced ? 6 + w : 1 + w); }
     Set at(char* stage, int b) const {
         char* base = stage + (size_t)b * bytes();
@@ -103,15 +111,17 @@ struct Stage {
                    (float*)p(reduced ? rdb : db, out_off(kDb)), (uint8_t*)p(reduced ? rrgba : rgba, out_off(kRgba)),
                    (uint8_t*)p(reduced ? ridx : idx, out_off(kIdx)), (emspec_peak*)p(peaks, out_off(kPeaks)),
                    (emspec_wave*)p(wave, out_off(kWave)), (float*)p(stereo[0], out_off(kSLevel)), (uint8_t*)p(stereo[1], out_off(kSIdx)),
-                   (uint8_t*)p(stereo[2], out_off(kSPan)), (uint8_t*)p(stereo[3], out_off(kSRgba))};
+                   (uint8_t*)p(stereo[2], out_off(kSPan)), (uint8_t*)p(stereo[3], out_off(kSRgba)),
+                   (emspec_level*)p(level, out_off(kLevel)), (emspec_cross*)p(cross, out_off(kCross))};
     }
 };
 
 // The arrays of a set behind its input, for `cells` full-rate cells, `rcells` reduced ones, the peak lists of `cols` columns and
-// the envelope pairs of `rcols` delivered columns.
+// the envelope pairs (and level records) of `rcols` delivered columns and the cross records of `prcols` sources' delivered columns.
 // Full rate: the rows' own arrays, but the dB also for the peaks kernel and the stereo image (of `pcells` pair cells), and with
 // f > 1 the index in place of RGBA.
-inline Stage stage_arrays(const OutRow* o, int f, size_t cells, size_t rcells, size_t cols, size_t rcols, size_t wire_s, size_t pcells = 0) {
+inline Stage stage_arrays(const OutRow* o, int f, size_t cells, size_t rcells, size_t cols, size_t rcols, size_t wire_s, size_t pcells = 0,
+                          size_t prcols = 0) {
     Stage g;
     g.reduced = f > 1;
     g.db = o[kDb].unit || o[kPeaks].unit || stereo_rows(o) ? al(cells * 4) : 0;
@@ -122,18 +132,21 @@ inline Stage stage_arrays(const OutRow* o, int f, size_t cells, size_t rcells, s
     g.peaks = al(cols * o[kPeaks].unit);
     g.wave = al(rcols * o[kWave].unit);
     for (int w = 0; w < 4; ++w) g.stereo[w] = al(pcells * o[kSLevel + w].unit);
+    g.level = al(rcols * o[kLevel].unit);
+    g.cross = al(prcols * o[kCross].unit);
     return g;
 }
 // Staging bytes per stream (pipe_items' 1 GiB cap): the input (`dec_s`: a PCM source's decoded floats), each view's arrays and
-// the source's stereo image
+// the source's stereo image and cross records
 inline size_t per_stream_bytes(const OutRow* o, size_t in_s, size_t dec_s, int V, int64_t C, int64_t Cr, int R, size_t wire_s, int f) {
     size_t pair = 0;
     for (int w = kSLevel; w <= kSRgba; ++w) pair += al((size_t)C * R * o[w].unit);
+    pair += al((size_t)Cr * o[kCross].unit);
     return al(in_s) + (dec_s ? al(dec_s) : 0) + V * stage_arrays(o, f, (size_t)C * R, (size_t)Cr * R, (size_t)C, (size_t)Cr, wire_s).bytes() + pair;
 }
 // The set of a batch (V streams per unit of PipeItem::sc, frame_bytes of raw input each: 1 and 0 for the float entries)
 inline Stage stage_layout(const std::vector<PipeItem>& items, int R, const OutRow* o, size_t wire_s, int V, int frame_bytes, int f) {
-    size_t in = 0, raw = 0, cells = 0, rcells = 0, cols = 0, rcols = 0, pcells = 0; int chunk = 1;
+    size_t in = 0, raw = 0, cells = 0, rcells = 0, cols = 0, rcols = 0, pcells = 0, prcols = 0; int chunk = 1;
     for (const PipeItem& it : items) {
         in = std::max(in, al((size_t)it.samples * 4 * it.sc * V));
         raw = std::max(raw, frame_bytes ? al((size_t)it.samples * frame_bytes * it.sc) : 0);
@@ -143,8 +156,9 @@ inline Stage stage_layout(const std::vector<PipeItem>& items, int R, const OutRo
         rcols = std::max(rcols, (size_t)((it.cn + f - 1) / f) * it.sc * V);
         chunk = std::max(chunk, it.sc * V);
         pcells = std::max(pcells, (size_t)it.cols * R * it.sc);
+        prcols = std::max(prcols, (size_t)((it.cn + f - 1) / f) * it.sc);
     }
-    Stage g = stage_arrays(o, f, cells, rcells, cols, rcols, wire_s, pcells);
+    Stage g = stage_arrays(o, f, cells, rcells, cols, rcols, wire_s, pcells, prcols);
     g.in = in; g.raw = raw; g.chunk = chunk;
     return g;
 }
@@ -183,4 +197,9 @@ inline Span wave_span_of(const PipeItem& it, int64_t C, int V, int k, int f) {
     if (it.cn == C) return Span{0, (size_t)it.s0 * V * Cr, crn * it.sc * V};
     return Span{(size_t)k * crn, ((size_t)it.s0 * V + k) * Cr + (size_t)(it.c0 / f), crn};
 }
+
+// The level records of a unit (level.hip.inc) lie and travel exactly as the envelope's pairs: wave_run_of,
+// wave_span_of.  The cross records are one per SOURCE and delivered column: the unit's sc sources as sc streams of one view -
+// a run of columns is one source (sc = 1), so a pair never straddles a unit.
+inline Span cross_span_of(const PipeItem& it, int64_t C, int f) { return wave_span_of(it, C, 1, 0, f); }
 }  // namespace emspec

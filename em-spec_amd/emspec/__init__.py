@@ -74,7 +74,11 @@ AUDIO_SYMBOLS = ["emspec_set_live_audio", "emspec_live_audio", "emspec_audio_vie
 STEREO_SYMBOLS = ["emspec_stereo_default_map", "emspec_make_stereo_colormap", "emspec_set_stereo_colormap", "emspec_stereo_device",
                   "emspec_stereo_host", "emspec_batch_stereo_device", "emspec_batch_pcm_stereo", "emspec_history_view_stereo_device",
                   "emspec_history_view_stereo"]
-SYMBOLS = SYMBOLS + MULTIBAND_SYMBOLS + LIVE_OVERLAY_SYMBOLS + LIVE_MULTIBAND_SYMBOLS + HISTORY_SYMBOLS + AUDIO_SYMBOLS + STEREO_SYMBOLS
+# the level meters': likewise (tools/level_rate.py times the parent commit's library next to this build)
+LEVEL_SYMBOLS = ["emspec_level_device", "emspec_level_host", "emspec_cross_device", "emspec_cross_host", "emspec_set_level_out",
+                 "emspec_set_cross_out", "emspec_level_window", "emspec_level_values", "emspec_cross_correlation"]
+SYMBOLS = (SYMBOLS + MULTIBAND_SYMBOLS + LIVE_OVERLAY_SYMBOLS + LIVE_MULTIBAND_SYMBOLS + HISTORY_SYMBOLS + AUDIO_SYMBOLS + STEREO_SYMBOLS
+           + LEVEL_SYMBOLS)
 STEREO_PAN_CENTRE, STEREO_PAN_LEVELS = 16, 33
 SESSION_MULTI, SESSION_ONE = 0, 1
 _SESSIONS = {"multi": SESSION_MULTI, "one": SESSION_ONE, SESSION_MULTI: SESSION_MULTI, SESSION_ONE: SESSION_ONE}
@@ -94,6 +98,17 @@ class ViewMap(C.Structure):
     """emspec_view_map: the colour law of a history view (db_top, db_range, gate_db as in the configuration) and the dB shift
     applied in front of it."""
     _fields_ = [("db_top", C.c_float), ("db_range", C.c_float), ("gate_db", C.c_float), ("shift_db", C.c_float)]
+
+
+class Level(C.Structure):
+    """emspec_level: the sum of k^2 of a window's samples in two limbs (sq_hi 2^32 + sq_lo), the peak |k| and the count of NaN and
+    saturated samples; k = the sample in units of 2^-24."""
+    _fields_ = [("sq_lo", C.c_uint64), ("sq_hi", C.c_uint64), ("peak", C.c_uint32), ("odd", C.c_uint32)]
+
+
+class Cross(C.Structure):
+    """emspec_cross: the sum of k_A k_B of a pair of streams over a window in two limbs (hi 2^32 + lo)."""
+    _fields_ = [("lo", C.c_uint64), ("hi", C.c_int64)]
 
 
 class StereoMap(C.Structure):
@@ -243,6 +258,73 @@ def wave_host(pcm, n, hop, factor=1, out=None, diag=False):
     return out
 
 
+def _level_shape(lib, S, L, n, hop, factor):
+    return S, max(int(lib.emspec_reduced_columns(max(int(lib.emspec_num_columns(L, n, hop)), 0), factor)), 0)
+
+
+def level_host(pcm, n, hop, factor=1, out=None, diag=False):
+    """The level records of pcm [S, L] (or [L]) float32 on the host's own cores (emspec_level_host: plain C++, no device, no
+    engine; the definition: include/emspec.h) -> LEVEL_DTYPE [S, Cr]: per delivered column the exact sum of
+    squares (two limbs), the peak and the odd count of the samples under it, the samples in units of 2^-24."""
+    pcm = np.ascontiguousarray(pcm, np.float32)
+    if pcm.ndim == 1:
+        pcm = pcm[None]
+    S, L = pcm.shape
+    lib = load(diag=diag)
+    if out is None:
+        out = np.zeros(_level_shape(lib, S, L, n, hop, factor), LEVEL_DTYPE)
+    assert out.dtype == LEVEL_DTYPE and out.flags.c_contiguous
+    rc = lib.emspec_level_host(_np_ptr(pcm), S, L, n, hop, int(factor), _np_ptr(out))
+    if rc != 0:
+        raise EmspecError(rc, lib.emspec_last_error(None).decode())
+    return out
+
+
+def cross_host(pcm, views, a, b, n, hop, factor=1, out=None, diag=False):
+    """The cross records of pcm [pairs * views, L] float32 on the host's own cores (emspec_cross_host): pair p's streams are
+    p views + a and p views + b -> CROSS_DTYPE [pairs, Cr], the exact sum of the products in two limbs."""
+    pcm = np.ascontiguousarray(pcm, np.float32)
+    streams, L = pcm.shape
+    pairs = streams // views if views > 0 and streams % views == 0 else -1
+    lib = load(diag=diag)
+    if out is None:
+        out = np.zeros(_level_shape(lib, max(pairs, 0), L, n, hop, factor), CROSS_DTYPE)
+    assert out.dtype == CROSS_DTYPE and out.flags.c_contiguous
+    rc = lib.emspec_cross_host(_np_ptr(pcm), pairs, int(views), int(a), int(b), L, n, hop, int(factor), _np_ptr(out))
+    if rc != 0:
+        raise EmspecError(rc, lib.emspec_last_error(None).decode())
+    return out
+
+
+def _record(rec, ctype):
+    """one record - a numpy structured scalar, a 0-d array or the ctypes structure - as the ctypes structure"""
+    return rec if isinstance(rec, ctype) else ctype.from_buffer_copy(np.asarray(rec).tobytes())
+
+
+def level_window(L, n, hop, factor, g, diag=False):
+    """emspec_level_window: the samples in window g (0 where there is none)."""
+    return int(load(diag).emspec_level_window(L, n, hop, int(factor), g))
+
+
+def level_values(level, samples, diag=False):
+    """emspec_level_values: (rms_db, peak_db) of one level record over `samples` samples, dB re full scale (|x| = 1); -inf for
+    silence."""
+    rms, peak = C.c_double(0.0), C.c_double(0.0)
+    lv = _record(level, Level)
+    if load(diag).emspec_level_values(C.byref(lv), int(samples), C.byref(rms), C.byref(peak)) != OK:
+        raise EmspecError(ERR_INVALID_ARG, "level_values needs a record and samples >= 1")
+    return rms.value, peak.value
+
+
+def cross_correlation(level_a, level_b, cross, diag=False):
+    """emspec_cross_correlation: rho of a pair's cross record and its two channels' level records, in [-1, 1]; 0 for silence."""
+    rho = C.c_double(0.0)
+    la, lb, cr = _record(level_a, Level), _record(level_b, Level), _record(cross, Cross)
+    if load(diag).emspec_cross_correlation(C.byref(la), C.byref(lb), C.byref(cr), C.byref(rho)) != OK:
+        raise EmspecError(ERR_INVALID_ARG, "cross_correlation needs three records")
+    return rho.value
+
+
 def make_stereo_colormap(brightness=0.5, diag=False):
     """The stereo palette built from make_colormap(brightness): uint8 [33][256][4] for Engine.set_stereo_colormap - row 16 the
     colour map itself, rows towards 0 tinted warm (channel A louder), towards 32 cold (channel B louder)."""
@@ -281,6 +363,9 @@ def stereo_host(db, views, a, b, map, palette=None, want=("level", "index", "pan
 # the 8-byte records of the overlays, as numpy structured types (include/emspec.h: emspec_peak, emspec_wave)
 PEAK_DTYPE = np.dtype([("pos", np.float32), ("db", np.float32)])
 WAVE_DTYPE = np.dtype([("lo", np.float32), ("hi", np.float32)])
+# ... and the level meters' records (emspec_level: 24 bytes, emspec_cross: 16)
+LEVEL_DTYPE = np.dtype([("sq_lo", np.uint64), ("sq_hi", np.uint64), ("peak", np.uint32), ("odd", np.uint32)])
+CROSS_DTYPE = np.dtype([("lo", np.uint64), ("hi", np.int64)])
 
 
 class EmspecError(RuntimeError):
@@ -481,6 +566,20 @@ def load(diag=False):
                                                           C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p] + outs + [C.c_void_p]
         lib.emspec_history_view_stereo.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                    C.c_int64, C.c_int32, C.c_int64, C.c_void_p] + outs
+    if all(hasattr(lib, sym) for sym in LEVEL_SYMBOLS):
+        lib.emspec_level_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                            C.c_void_p]
+        lib.emspec_level_host.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+        lib.emspec_cross_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
+                                            C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        lib.emspec_cross_host.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_void_p]
+        lib.emspec_set_level_out.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        lib.emspec_set_cross_out.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
+        lib.emspec_level_window.restype = C.c_int64
+        lib.emspec_level_window.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64]
+        lib.emspec_level_values.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.emspec_cross_correlation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _libs[diag] = lib
     return lib
 
@@ -922,6 +1021,63 @@ class Engine:
         assert isinstance(wave, np.ndarray) and wave.dtype == np.float32 and wave.flags.c_contiguous and wave.flags.writeable
         self._chk(self._lib.emspec_set_wave_out(self._h, _np_ptr(wave), wave.size // 2))
         self._wave_out = wave
+
+    # -- level meters: exact sums of squares / products of the samples under each delivered column ----------
+    def level_device(self, pcm_t, n, hop, factor=1, out=None, stream=None):
+        """emspec_level_device: pcm_t a contiguous float32 CUDA tensor [S, L] (4-byte aligned) -> uint8 CUDA tensor
+        [S, Cr, 24] of emspec_level records (8-byte aligned; .cpu().numpy().view(LEVEL_DTYPE)[..., 0] names the fields).
+        `factor` is the call's own.  Enqueues; does not synchronise."""
+        import torch
+        assert pcm_t.is_cuda and pcm_t.dtype == torch.float32 and pcm_t.is_contiguous() and pcm_t.dim() == 2
+        S, L = pcm_t.shape
+        Cr = max(reduced_columns(max(num_columns(L, n, hop), 0), factor), 0)
+        if out is None:
+            out = torch.empty((S, Cr, 24), dtype=torch.uint8, device=pcm_t.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == S * Cr * 24
+        st = stream if stream is not None else torch.cuda.current_stream(pcm_t.device)
+        self._chk(self._lib.emspec_level_device(self._h, C.c_void_p(pcm_t.data_ptr()), S, L, n, hop, int(factor),
+                                                C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream)))
+        return out
+
+    def cross_device(self, pcm_t, views, a, b, n, hop, factor=1, out=None, stream=None):
+        """emspec_cross_device: pcm_t [pairs * views, L] as for level_device; pair p's streams are p views + a and p views + b
+        -> uint8 CUDA tensor [pairs, Cr, 16] of emspec_cross records (view as CROSS_DTYPE).  Enqueues; does not synchronise."""
+        import torch
+        assert pcm_t.is_cuda and pcm_t.dtype == torch.float32 and pcm_t.is_contiguous() and pcm_t.dim() == 2
+        streams, L = pcm_t.shape
+        pairs = streams // views if views > 0 and streams % views == 0 else -1
+        Cr = max(reduced_columns(max(num_columns(L, n, hop), 0), factor), 0)
+        if out is None:
+            out = torch.empty((max(pairs, 0), Cr, 16), dtype=torch.uint8, device=pcm_t.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == max(pairs, 0) * Cr * 16
+        st = stream if stream is not None else torch.cuda.current_stream(pcm_t.device)
+        self._chk(self._lib.emspec_cross_device(self._h, C.c_void_p(pcm_t.data_ptr()), pairs, int(views), int(a), int(b), L, n, hop,
+                                                int(factor), C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream)))
+        return out
+
+    def set_level_out(self, level):
+        """emspec_set_level_out: while set, every call that honours set_wave_out also writes the level records of its streams to
+        `level`, a C-contiguous numpy array of LEVEL_DTYPE with streams x delivered columns records or more; None clears it.
+        The engine keeps a reference to the array while it is set."""
+        if level is None:
+            self._chk(self._lib.emspec_set_level_out(self._h, None, 0))
+            self._level_out = None
+            return
+        assert isinstance(level, np.ndarray) and level.dtype == LEVEL_DTYPE and level.flags.c_contiguous and level.flags.writeable
+        self._chk(self._lib.emspec_set_level_out(self._h, _np_ptr(level), level.size))
+        self._level_out = level
+
+    def set_cross_out(self, a, b, cross):
+        """emspec_set_cross_out: while set, batch_pcm(), batch_pcm_packed() and batch_pcm_stereo() also write the cross records
+        of views a and b of each source to `cross`, a C-contiguous numpy array of CROSS_DTYPE with sources x delivered columns
+        records or more; None clears it.  The float-stream host calls raise ERR_STATE while it is set."""
+        if cross is None:
+            self._chk(self._lib.emspec_set_cross_out(self._h, 0, 0, None, 0))
+            self._cross_out = None
+            return
+        assert isinstance(cross, np.ndarray) and cross.dtype == CROSS_DTYPE and cross.flags.c_contiguous and cross.flags.writeable
+        self._chk(self._lib.emspec_set_cross_out(self._h, int(a), int(b), _np_ptr(cross), cross.size))
+        self._cross_out = cross
 
     # -- multi-resolution batch (DESIGN.md §3.8): n_low below split_row, n_high from it up, one column grid --------
     def split_row_for_hz(self, hz):

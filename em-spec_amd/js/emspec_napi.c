@@ -45,14 +45,17 @@ static napi_value throw_status(napi_env env, emspec_engine* e, int rc) {
 }
 
 /* rows: the engine's row count, for output-size checks; wave: the array given to setWaveOut, referenced while it is set;
- * live_peaks / live_wave: likewise the arrays given to setLivePeaks / setLiveWave */
-typedef struct { emspec_engine* e; int32_t rows; napi_ref wave, live_peaks, live_wave; } handle_t;
+ * level / cross: likewise the arrays given to setLevelOut / setCrossOut; live_peaks / live_wave: those given to setLivePeaks /
+ * setLiveWave */
+typedef struct { emspec_engine* e; int32_t rows; napi_ref wave, level, cross, live_peaks, live_wave; } handle_t;
 
 static void drop_ref(napi_env env, napi_ref* r) {
     if (*r) { napi_delete_reference(env, *r); *r = NULL; }
 }
-static void drop_wave(napi_env env, handle_t* h) {
+static void drop_wave(napi_env env, handle_t* h) {   /* ... and the level meters' arrays: what the batch calls also fill */
     drop_ref(env, &h->wave);
+    drop_ref(env, &h->level);
+    drop_ref(env, &h->cross);
 }
 static void finalize_handle(napi_env env, void* data, void* hint) {
     (void)hint;
@@ -134,7 +137,7 @@ static napi_value Create(napi_env env, napi_callback_info info) {
     if (!h) { emspec_destroy(e); napi_throw_error(env, "EMSPEC_ERR_OUT_OF_MEMORY", "malloc"); return NULL; }
     h->e = e;
     h->rows = cfg.rows;
-    h->wave = NULL;
+    h->wave = h->level = h->cross = NULL;
     h->live_peaks = h->live_wave = NULL;
     napi_value ext;
     if (napi_create_external(env, h, finalize_handle, NULL, &ext) != napi_ok) {
@@ -1268,6 +1271,153 @@ static napi_value SetWaveOut(napi_env env, napi_callback_info info) {
     h->wave = ref;
     return NULL;
 }
+/* Level meters (include/emspec.h).  Records travel as bytes: index.js lays BigUint64Array / BigInt64Array
+ * views over them.
+ * setLevelOut(handle, level:Uint8Array | null): emspec_set_level_out with capacity level.length / 24 records
+ * setCrossOut(handle, a, b, cross:Uint8Array | null): emspec_set_cross_out with capacity cross.length / 16 records
+ *   While set, the batch calls that run the host pipeline also fill them; the addon references an array until it is replaced,
+ *   cleared or the engine is destroyed.
+ * levelsOf(pcm:Float32Array(S*L), S, L, fftSize, hop, factor, out:Uint8Array(S*Cr*24)): emspec_level_host
+ * crossOf(pcm, pairs, views, a, b, L, fftSize, hop, factor, out:Uint8Array(pairs*Cr*16)): emspec_cross_host
+ * levelWindow(L, fftSize, hop, factor, g) -> samples;  levelValues(level:Uint8Array(24), samples) -> [rmsDb, peakDb];
+ * crossCorrelation(a:Uint8Array(24), b:Uint8Array(24), ab:Uint8Array(16)) -> rho */
+static napi_value SetLevelOut(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "setLevelOut(handle, level)"); return NULL; }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    void* arr = NULL; size_t len = 0;
+    if (!get_typed(env, argv[1], napi_uint8_array, &arr, &len, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "level must be a Uint8Array or null"); return NULL; }
+    napi_ref ref = NULL;
+    if (arr) NAPI_OK_OR_RETURN(env, napi_create_reference(env, argv[1], 1, &ref));
+    int rc = emspec_set_level_out(h->e, (emspec_level*)arr, arr ? (int64_t)(len / sizeof(emspec_level)) : 0);
+    if (rc != EMSPEC_OK) {
+        if (ref) napi_delete_reference(env, ref);
+        return throw_status(env, h->e, rc);
+    }
+    drop_ref(env, &h->level);
+    h->level = ref;
+    return NULL;
+}
+static napi_value SetCrossOut(napi_env env, napi_callback_info info) {
+    size_t argc = 4; napi_value argv[4];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 4) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "setCrossOut(handle, a, b, cross)"); return NULL; }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    int32_t a = 0, b = 0;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[1], &a));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[2], &b));
+    void* arr = NULL; size_t len = 0;
+    if (!get_typed(env, argv[3], napi_uint8_array, &arr, &len, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "cross must be a Uint8Array or null"); return NULL; }
+    napi_ref ref = NULL;
+    if (arr) NAPI_OK_OR_RETURN(env, napi_create_reference(env, argv[3], 1, &ref));
+    int rc = emspec_set_cross_out(h->e, a, b, (emspec_cross*)arr, arr ? (int64_t)(len / sizeof(emspec_cross)) : 0);
+    if (rc != EMSPEC_OK) {
+        if (ref) napi_delete_reference(env, ref);
+        return throw_status(env, h->e, rc);
+    }
+    drop_ref(env, &h->cross);
+    h->cross = ref;
+    return NULL;
+}
+/* the shared tail of levelsOf / crossOf: argv[at ..] = L, fftSize, hop, factor, out; rows records of `size` bytes per delivered column */
+static int level_shape(napi_env env, napi_value* argv, int at, int64_t rows, size_t size, int64_t* L, int32_t* n, int32_t* hop, int32_t* factor,
+                       void** out) {
+    size_t olen = 0;
+    if (napi_get_value_int64(env, argv[at], L) != napi_ok || napi_get_value_int32(env, argv[at + 1], n) != napi_ok ||
+        napi_get_value_int32(env, argv[at + 2], hop) != napi_ok || napi_get_value_int32(env, argv[at + 3], factor) != napi_ok) {
+        napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "L, fftSize, hop and factor must be numbers");
+        return 0;
+    }
+    if (!get_typed(env, argv[at + 4], napi_uint8_array, out, &olen, 0)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "out must be a Uint8Array"); return 0; }
+    /* (a shape the library rejects: it does so with its message before it touches the output) */
+    const int64_t C = emspec_num_columns(*L, *n, *hop), Cr = C >= 0 ? emspec_reduced_columns(C, *factor) : -1;
+    if (Cr >= 0 && rows >= 0 && olen != (size_t)rows * (size_t)Cr * size) {
+        napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "out must hold exactly rows*reducedColumns records");
+        return 0;
+    }
+    return 1;
+}
+static napi_value LevelsOf(napi_env env, napi_callback_info info) {
+    size_t argc = 7; napi_value argv[7];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 7) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "levelsOf(pcm, S, L, fftSize, hop, factor, out)"); return NULL; }
+    void *pcm = NULL, *out = NULL; size_t plen = 0;
+    if (!get_typed(env, argv[0], napi_float32_array, &pcm, &plen, 0)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "pcm must be a Float32Array"); return NULL; }
+    int32_t S = 0, n = 0, hop = 0, factor = 0; int64_t L = 0;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[1], &S));
+    if (!level_shape(env, argv, 2, S, sizeof(emspec_level), &L, &n, &hop, &factor, &out)) return NULL;
+    if (S < 0 || L < 0 || (size_t)S * (size_t)L != plen) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "pcm.length must equal S*L"); return NULL; }
+    int rc = emspec_level_host((const float*)pcm, S, L, n, hop, factor, (emspec_level*)out);
+    if (rc != EMSPEC_OK) return throw_status(env, NULL, rc);
+    return NULL;
+}
+static napi_value CrossOf(napi_env env, napi_callback_info info) {
+    size_t argc = 10; napi_value argv[10];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 10) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "crossOf(pcm, pairs, views, a, b, L, fftSize, hop, factor, out)"); return NULL; }
+    void *pcm = NULL, *out = NULL; size_t plen = 0;
+    if (!get_typed(env, argv[0], napi_float32_array, &pcm, &plen, 0)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "pcm must be a Float32Array"); return NULL; }
+    int32_t pairs = 0, views = 0, a = 0, b = 0, n = 0, hop = 0, factor = 0; int64_t L = 0;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[1], &pairs));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[2], &views));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[3], &a));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[4], &b));
+    if (!level_shape(env, argv, 5, pairs, sizeof(emspec_cross), &L, &n, &hop, &factor, &out)) return NULL;
+    if (pairs < 0 || views < 0 || L < 0 || (size_t)pairs * (size_t)views * (size_t)L != plen) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "pcm.length must equal pairs*views*L"); return NULL; }
+    int rc = emspec_cross_host((const float*)pcm, pairs, views, a, b, L, n, hop, factor, (emspec_cross*)out);
+    if (rc != EMSPEC_OK) return throw_status(env, NULL, rc);
+    return NULL;
+}
+static napi_value LevelWindow(napi_env env, napi_callback_info info) {
+    size_t argc = 5; napi_value argv[5];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 5) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "levelWindow(L, fftSize, hop, factor, g)"); return NULL; }
+    int64_t L = 0, g = 0; int32_t n = 0, hop = 0, factor = 0;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[0], &L));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[1], &n));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[2], &hop));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[3], &factor));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[4], &g));
+    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_int64(env, emspec_level_window(L, n, hop, factor, g), &r));
+    return r;
+}
+/* one record of `size` bytes out of a Uint8Array (copied: a view may lie at any byte offset) */
+static int get_record(napi_env env, napi_value v, void* rec, size_t size) {
+    void* p = NULL; size_t len = 0;
+    if (!get_typed(env, v, napi_uint8_array, &p, &len, 0) || len != size) {
+        napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "a record must be a Uint8Array of its size (24 or 16 bytes)");
+        return 0;
+    }
+    memcpy(rec, p, size);
+    return 1;
+}
+static napi_value LevelValues(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "levelValues(level, samples)"); return NULL; }
+    emspec_level lv; int64_t samples = 0; double rms = 0.0, peak = 0.0;
+    if (!get_record(env, argv[0], &lv, sizeof lv)) return NULL;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int64(env, argv[1], &samples));
+    if (emspec_level_values(&lv, samples, &rms, &peak) != EMSPEC_OK) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "levelValues needs samples >= 1"); return NULL; }
+    napi_value r, a, b;
+    NAPI_OK_OR_RETURN(env, napi_create_array_with_length(env, 2, &r));
+    NAPI_OK_OR_RETURN(env, napi_create_double(env, rms, &a));
+    NAPI_OK_OR_RETURN(env, napi_create_double(env, peak, &b));
+    NAPI_OK_OR_RETURN(env, napi_set_element(env, r, 0, a));
+    NAPI_OK_OR_RETURN(env, napi_set_element(env, r, 1, b));
+    return r;
+}
+static napi_value CrossCorrelation(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 3) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "crossCorrelation(levelA, levelB, cross)"); return NULL; }
+    emspec_level a, b; emspec_cross ab; double rho = 0.0;
+    if (!get_record(env, argv[0], &a, sizeof a) || !get_record(env, argv[1], &b, sizeof b) || !get_record(env, argv[2], &ab, sizeof ab)) return NULL;
+    if (emspec_cross_correlation(&a, &b, &ab, &rho) != EMSPEC_OK) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "crossCorrelation"); return NULL; }
+    napi_value r; NAPI_OK_OR_RETURN(env, napi_create_double(env, rho, &r));
+    return r;
+}
 /* Overlays of the live calls (include/emspec.h: emspec_set_live_peaks / emspec_set_live_wave).
  * setLivePeaks(handle, k, minDb, peaks:Float32Array | null): capacity peaks.length / 2 pairs
  * setLiveWave(handle, wave:Float32Array | null): capacity wave.length / 2 pairs
@@ -1836,6 +1986,13 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"peaksOf", NULL, PeaksOf, NULL, NULL, NULL, napi_default, NULL},
         {"setWaveOut", NULL, SetWaveOut, NULL, NULL, NULL, napi_default, NULL},
         {"waveOf", NULL, WaveOf, NULL, NULL, NULL, napi_default, NULL},
+        {"setLevelOut", NULL, SetLevelOut, NULL, NULL, NULL, napi_default, NULL},
+        {"setCrossOut", NULL, SetCrossOut, NULL, NULL, NULL, napi_default, NULL},
+        {"levelsOf", NULL, LevelsOf, NULL, NULL, NULL, napi_default, NULL},
+        {"crossOf", NULL, CrossOf, NULL, NULL, NULL, napi_default, NULL},
+        {"levelWindow", NULL, LevelWindow, NULL, NULL, NULL, napi_default, NULL},
+        {"levelValues", NULL, LevelValues, NULL, NULL, NULL, napi_default, NULL},
+        {"crossCorrelation", NULL, CrossCorrelation, NULL, NULL, NULL, napi_default, NULL},
         {"setLivePeaks", NULL, SetLivePeaks, NULL, NULL, NULL, napi_default, NULL},
         {"setLiveWave", NULL, SetLiveWave, NULL, NULL, NULL, napi_default, NULL},
         {"setLiveHistory", NULL, SetLiveHistory, NULL, NULL, NULL, napi_default, NULL},

@@ -51,6 +51,16 @@ class Engine {
   setWaveOut(wave) { native.setWaveOut(this._h, wave === undefined ? null : wave); }
 
   /**
+   * Level meters (emspec_set_level_out, emspec_set_cross_out; DESIGN.md §3.17): while set, every call that honours setWaveOut
+   * also writes the level records of its streams to `level` (levelRecords(streams x delivered columns) or more), and the PCM
+   * calls the cross records of views a and b of each source to `cross` (crossRecords(sources x delivered columns) or more).
+   * The records are exact integer sums, the same bytes whatever the mode; levelValues / crossCorrelation read them.  null
+   * clears.  While setCrossOut is set, the calls on float streams throw EMSPEC_ERR_STATE.
+   */
+  setLevelOut(level) { native.setLevelOut(this._h, level ? level.bytes : null); }
+  setCrossOut(a, b, cross) { native.setCrossOut(this._h, a | 0, b | 0, cross ? cross.bytes : null); }
+
+  /**
    * Overlays of the live calls (emspec_set_live_peaks / emspec_set_live_wave; DESIGN.md §4.15): while set, every live call of
    * this engine also fills engine.columnsPeaks - Float32Array of (pos, dB) pairs, [(s * cols + slot) * k + i] - and
    * engine.columnsWave - (lo, hi) pairs, [s * cols + slot] - for exactly the column slots it writes: cols = 1 for
@@ -671,6 +681,51 @@ function waveOf(pcm, S, L, fftSize, hop, factor = 1) {
   return out;
 }
 
+/**
+ * Level and cross records (emspec_level: 24 bytes, emspec_cross: 16) as views over one buffer.
+ * levelRecords(count): { count, bytes, limbs: BigUint64Array - sq_lo at [3 i], sq_hi at [3 i + 1] -, words: Uint32Array - peak at
+ * [6 i + 4], odd at [6 i + 5] };  crossRecords(count): { count, bytes, lo: BigUint64Array - at [2 i] -, hi: BigInt64Array - at
+ * [2 i + 1] }.  The sum of squares of record i is limbs[3 i + 1] * 2n ** 32n + limbs[3 i], the sum of products hi * 2n ** 32n + lo.
+ */
+function levelRecords(count) {
+  const buf = new ArrayBuffer(Math.max(0, count) * 24);
+  return { count, bytes: new Uint8Array(buf), limbs: new BigUint64Array(buf), words: new Uint32Array(buf) };
+}
+function crossRecords(count) {
+  const buf = new ArrayBuffer(Math.max(0, count) * 16);
+  return { count, bytes: new Uint8Array(buf), lo: new BigUint64Array(buf), hi: new BigInt64Array(buf) };
+}
+function reducedColumnsOf(L, fftSize, hop, factor) {
+  const C = L >= fftSize && hop >= 1 ? Math.floor((L - fftSize) / hop) + 1 : 0;
+  return Math.ceil(C / Math.min(65536, Math.max(1, factor | 0)));
+}
+/**
+ * The level records of pcm (Float32Array, S streams of L samples) on the host's own cores (emspec_level_host: no device, no
+ * engine): levelRecords of S x ceil(columns / factor) - per delivered column the exact sum of squares, the peak and the count of
+ * NaN / saturated samples under it, the samples in units of 2^-24.
+ */
+function levelsOf(pcm, S, L, fftSize, hop, factor = 1) {
+  const out = levelRecords(Math.max(0, S) * reducedColumnsOf(L, fftSize, hop, factor));
+  native.levelsOf(pcm, S, L, fftSize, hop, factor | 0, out.bytes);
+  return out;
+}
+/** The cross records of pairs of streams (emspec_cross_host): pair p is streams p views + a and p views + b of pcm. */
+function crossOf(pcm, pairs, views, a, b, L, fftSize, hop, factor = 1) {
+  const out = crossRecords(Math.max(0, pairs) * reducedColumnsOf(L, fftSize, hop, factor));
+  native.crossOf(pcm, pairs, views | 0, a | 0, b | 0, L, fftSize, hop, factor | 0, out.bytes);
+  return out;
+}
+/** {rmsDb, peakDb} of level record i over `samples` samples (levelWindow), dB re full scale; -Infinity for silence. */
+function levelValues(level, i, samples) {
+  const [rmsDb, peakDb] = native.levelValues(level.bytes.subarray(24 * i, 24 * i + 24), samples);
+  return { rmsDb, peakDb };
+}
+/** rho in [-1, 1] of cross record k and its two channels' level records i and j; 0 for silence. */
+function crossCorrelation(levelA, i, levelB, j, cross, k) {
+  return native.crossCorrelation(levelA.bytes.subarray(24 * i, 24 * i + 24), levelB.bytes.subarray(24 * j, 24 * j + 24),
+    cross.bytes.subarray(16 * k, 16 * k + 16));
+}
+
 function peaksOf(db, columns, rows, k = 8, minDb = -60) {
   const out = new Float32Array(Math.max(0, columns) * Math.min(32, Math.max(1, k | 0)) * 2);
   native.peaksOf(db, columns, rows, k | 0, +minDb, out);
@@ -709,6 +764,14 @@ module.exports = {
    *  - a live call's, computeColumnsMultires's - -> Float32Array [columns][k][2]. */
   peaksOf,
   waveOf,
+  levelRecords,
+  crossRecords,
+  levelsOf,
+  crossOf,
+  /** The samples in window g of a stream of L samples (emspec_level_window); 0 where there is none. */
+  levelWindow: native.levelWindow,
+  levelValues,
+  crossCorrelation,
   /** hz -> {name, octave, cents}: 12-tone equal temperament around A4 = 440 Hz, the nearest semitone, cents in [-50, 50). */
   noteOf,
   latencyColumns: native.latencyColumns,

@@ -810,7 +810,8 @@ int emspec_position_hz(emspec_engine* e, float pos, double* hz);
  * rule of the reduced columns it sits under).  For the PCM entries the samples are the decoded, mixed float32 values of the
  * views; for emspec_batch_multires the column grid is the long band's, n = n_low
  * (emspec_batch_multiband: n = n[0]).
- * The live calls deliver it through emspec_set_live_wave (below).  No RMS or other sum: a float sum depends on its order.
+ * The live calls deliver it through emspec_set_live_wave (below).  Sums - RMS, correlation - are the level meters' (next section):
+ * a float sum depends on its order, so they are summed as integers.
  */
 typedef struct emspec_wave { float lo; float hi; } emspec_wave;   /* 8 bytes */
 
@@ -837,6 +838,76 @@ int emspec_wave_host(const float* pcm, int32_t S, int64_t L, int32_t n, int32_t 
 int emspec_set_wave_out(emspec_engine* e, emspec_wave* wave_out, int64_t capacity /* pairs */);
 /* Every refusal above is EMSPEC_ERR_INVALID_ARG with a message naming the rule - a factor outside 1 .. 65536, a hop outside
  * 1 .. n, an unsupported n, S outside 0 .. 65535, null or misaligned pointers, a negative capacity - and leaves the engine usable. */
+
+/*
+ * ---- Level meters: exact RMS, peak and pair correlation of the samples under each delivered column.
+ * Serves: the level meter a viewer draws beside the waveform lane and the correlation meter beside a stereo image, also zoomed
+ * out and for the views of a PCM source, whose float streams exist in no host buffer; [BUILD-DEFINED].
+ *
+ * DEFINITION.  The windows are the envelope's: L, n, hop, factor f, C, Cr and off as above, record g covers W(g).
+ *   Quantiser.  A sample x with bits u gives an integer k in units of 2^-24.  A NaN gives k = 0 and counts in `odd`.  Otherwise
+ *   k = x 2^24 rounded to nearest, ties to even, saturated to +-(2^31 - 1); a saturated sample - |x| >= 128, or an infinity -
+ *   also counts in `odd`.  The product x 2^24 is exact in binary32, and every |x| <= 2^-25 gives 0, so k does not depend on
+ *   how denormals are handled and can be evaluated from the bits in integers.  s16 and s24 PCM are represented exactly; the
+ *   floor is -144 dBFS, the ceiling +42 dBFS.
+ *   Level record.  Over the samples of W(g), with q = k^2 (below 2^62):
+ *       sq_lo = sum of (q & 0xffffffff),  sq_hi = sum of (q >> 32),  peak = max |k|,  odd = the count above
+ *   so that the sum of k^2 is sq_hi 2^32 + sq_lo.  A window has at most 2^30 samples: no limb overflows.
+ *   Cross record of a pair of streams (A, B).  With p = k_A k_B (int64):
+ *       lo = sum of ((uint64)p & 0xffffffff),  hi = sum of (p >> 32, arithmetic shift)
+ *   so that the sum of k_A k_B is hi 2^32 + lo.
+ * LAWS.  The limbs are deliberately not normalised.  Every field is a sum or a maximum of integers: a record does not depend on
+ * the order of evaluation, on how the work is split, or on the engine's mode - device, host, FAST and EXACT give the same bytes.
+ * The record at factor f is the field-wise sum (peak: maximum) of the f = 1 records of its group.  For the PCM entries the
+ * samples are the decoded, mixed float32 values of the views.
+ */
+typedef struct emspec_level { uint64_t sq_lo; uint64_t sq_hi; uint32_t peak; uint32_t odd; } emspec_level;   /* 24 bytes */
+typedef struct emspec_cross { uint64_t lo; int64_t hi; } emspec_cross;                                         /* 16 bytes */
+
+/*
+ * The level records of S device-resident streams, pcm_dev [S][L] (4-byte aligned), into level_dev [S][Cr] (8-byte aligned).
+ * Arguments and refusals as for emspec_wave_device; `factor` is the call's own.  One pass over the samples.  Enqueued on
+ * hip_stream (NULL = the default stream); does not synchronise.
+ */
+int emspec_level_device(emspec_engine* e, const float* pcm_dev, int32_t S, int64_t L, int32_t n, int32_t hop, int32_t factor,
+                        emspec_level* level_dev, void* hip_stream);
+/* The same definition in plain C++ on host arrays: no engine, no device.  The message of a refusal: emspec_last_error(NULL). */
+int emspec_level_host(const float* pcm, int32_t S, int64_t L, int32_t n, int32_t hop, int32_t factor, emspec_level* level_out);
+/*
+ * The cross records of `pairs` pairs of device-resident streams: pair p is streams p views + a and p views + b of
+ * pcm_dev [pairs views][L] - the addressing of emspec_stereo_device, but a == b is allowed (the cross limbs then are the level's
+ * sums) - into cross_dev [pairs][Cr] (8-byte aligned).  views in 1 .. 64, a and b in 0 .. views - 1, pairs views <= 65535;
+ * otherwise as emspec_level_device.
+ */
+int emspec_cross_device(emspec_engine* e, const float* pcm_dev, int32_t pairs, int32_t views, int32_t a, int32_t b, int64_t L, int32_t n,
+                        int32_t hop, int32_t factor, emspec_cross* cross_dev, void* hip_stream);
+int emspec_cross_host(const float* pcm, int32_t pairs, int32_t views, int32_t a, int32_t b, int64_t L, int32_t n, int32_t hop,
+                      int32_t factor, emspec_cross* cross_out);
+/*
+ * While set, every entry that honours emspec_set_wave_out also writes the level records of its streams to
+ * level_out[streams][Cr], in the same pass, from each unit's staged samples; f, streams, capacity (in records), validity and
+ * the contents after an error return follow emspec_set_wave_out's rules.  level_out is 8-byte aligned host memory.  NULL clears
+ * it.  emspec_batch_gather returns EMSPEC_ERR_STATE while it is set.
+ */
+int emspec_set_level_out(emspec_engine* e, emspec_level* level_out, int64_t capacity /* records */);
+/*
+ * While set, the PCM host entries - emspec_batch_pcm, _pcm_packed, _pcm_stereo - also write the cross records of views a and b
+ * of each source to cross_out[sources][Cr] (8-byte aligned host memory; capacity in records).  a or b outside the call's views
+ * gives EMSPEC_ERR_INVALID_ARG before anything runs, as does sources x Cr > capacity.  While it is set, the host entries on
+ * float streams and emspec_batch_gather return EMSPEC_ERR_STATE.  NULL clears it.
+ */
+int emspec_set_cross_out(emspec_engine* e, int32_t a, int32_t b, emspec_cross* cross_out, int64_t capacity /* records */);
+/*
+ * Pure helpers, binary64, no engine.  emspec_level_window: the samples in W(g) (0 where there is no such window).
+ * emspec_level_values: rms_db = 10 log10((ldexp((double)sq_hi, 32) + (double)sq_lo) / samples) - 20 log10(2^24), -INFINITY for a
+ * zero sum; peak_db likewise from `peak`; either pointer may be null.  emspec_cross_correlation: rho = sum ab / sqrt(sum a^2
+ * sum b^2), clamped to [-1, 1]; 0 for a zero denominator.  They return EMSPEC_ERR_INVALID_ARG for a null record or samples < 1.
+ */
+int64_t emspec_level_window(int64_t L, int32_t n, int32_t hop, int32_t factor, int64_t g);
+int emspec_level_values(const emspec_level* level, int64_t samples, double* rms_db, double* peak_db);
+int emspec_cross_correlation(const emspec_level* a, const emspec_level* b, const emspec_cross* ab, double* rho);
+/* Every refusal above is EMSPEC_ERR_INVALID_ARG with a message naming the rule - those of the envelope's entries, an output that
+ * is not 8-byte aligned, views outside 1 .. 64, a or b outside 0 .. views - 1, pairs views > 65535 - and leaves the engine usable. */
 
 /*
  * ---- Overlays of the streaming calls: the spectral peaks of every column a live call delivers
