@@ -48,16 +48,17 @@ int plan_pipe(Pipe& p) {
     p.C = emspec_num_columns(j.L, j.n, j.hop); p.Cr = reduced_columns(p.C, p.f);
     // dec: the S rows are SOURCES of interleaved frames (emspec_batch_pcm): fb bytes per frame in, V streams each out
     p.V = j.dec ? j.dec->views : 1; p.fb = j.dec ? pcm_frame_bytes(*j.dec) : (int)sizeof(float);
-    if (e->wave_out && (int64_t)j.S * p.V * p.Cr > e->wave_capacity)
-        return fail(e, EMSPEC_ERR_INVALID_ARG, "the envelope set with emspec_set_wave_out is too small: it needs streams x delivered columns pairs");
-    if (e->level_out && (int64_t)j.S * p.V * p.Cr > e->level_capacity)
-        return fail(e, EMSPEC_ERR_INVALID_ARG, "the array set with emspec_set_level_out is too small: it needs streams x delivered columns records");
+    // the array of a setting that is on holds an item per stream (cross: per source) and delivered column
+    auto room = [&](const void* set, int64_t rows, int64_t capacity, const char* too_small) {
+        return set && rows * p.Cr > capacity ? fail(e, EMSPEC_ERR_INVALID_ARG, too_small) : (int)EMSPEC_OK;
+    };
+    if (int rc = room(e->wave_out, (int64_t)j.S * p.V, e->wave_capacity, "the envelope set with emspec_set_wave_out is too small: it needs streams x delivered columns pairs")) return rc;
+    if (int rc = room(e->level_out, (int64_t)j.S * p.V, e->level_capacity, "the array set with emspec_set_level_out is too small: it needs streams x delivered columns records")) return rc;
     if (e->cross_out && !j.dec)
         return fail(e, EMSPEC_ERR_STATE, "cross records are of a PCM source's views: not available on float streams while emspec_set_cross_out is set (NULL clears it)");
     if (e->cross_out && (e->cross_a >= p.V || e->cross_b >= p.V))
         return fail(e, EMSPEC_ERR_INVALID_ARG, "the channels a and b set with emspec_set_cross_out must be in 0 .. views - 1 of the call's format");
-    if (e->cross_out && (int64_t)j.S * p.Cr > e->cross_capacity)
-        return fail(e, EMSPEC_ERR_INVALID_ARG, "the array set with emspec_set_cross_out is too small: it needs sources x delivered columns records");
+    if (int rc = room(e->cross_out, (int64_t)j.S, e->cross_capacity, "the array set with emspec_set_cross_out is too small: it needs sources x delivered columns records")) return rc;
     if (!e->stream_in) HIPCHK(e, hipStreamCreateWithFlags(&e->stream_in, hipStreamNonBlocking));
     if (!e->stream_out) HIPCHK(e, hipStreamCreateWithFlags(&e->stream_out, hipStreamNonBlocking));
     for (hipEvent_t& ev : e->pipe_ev) if (!ev) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -112,22 +113,18 @@ int plan_pipe(Pipe& p) {
 template <class F>
 void for_pieces(const Pipe& p, int u, F&& fn) {
     for (int k = 0; k < spans_of(p.items[u], p.C, p.V); ++k) {
-        const Span sp = span_of(p.items[u], p.C, p.R, p.V, k, p.f);
-        for (int w = 0; w < kSLevel; ++w) {
+        const Span sp = span_of(p.items[u], p.C, p.R, p.V, k, p.f), ws = wave_span_of(p.items[u], p.C, p.V, k, p.f);
+        static_assert(kWave == 4 && kWave + 1 == kSLevel && kSRgba + 1 == kLevel && kCross + 1 == kOutRows, "a new row is served by no loop of for_pieces");
+        for (int w : {kDb, kRgba, kIdx, kPeaks, kWave, kLevel}) {   // every row in front of the stereo rows, and the level records
             const OutRow& o = p.outs[w];
             const size_t cols = sp.cells / p.R, off = p.g.out_off(w);
-            if (o.host && w == kWave) {
-                const Span ws = wave_span_of(p.items[u], p.C, p.V, k, p.f);
-                fn(o.host + ws.to * o.unit, off + ws.from * o.unit, ws.cells * o.unit);
-            } else if (o.host && w != kPeaks) fn(o.host + sp.to * o.unit, off + sp.from * o.unit, sp.cells * o.unit);
-            if (o.host && w == kPeaks) fn(o.host + sp.to / p.R * o.unit, off + k * cols * o.unit, cols * o.unit);
-        }
-        if (const OutRow& o = p.outs[kLevel]; o.host) {   // the level records: the envelope's spans
-            const Span ws = wave_span_of(p.items[u], p.C, p.V, k, p.f);
-            fn(o.host + ws.to * o.unit, p.g.out_off(kLevel) + ws.from * o.unit, ws.cells * o.unit);
+            if (!o.host) continue;
+            if (w == kWave || w == kLevel) fn(o.host + ws.to * o.unit, off + ws.from * o.unit, ws.cells * o.unit);   // the envelope's pairs, the level records
+            else if (w == kPeaks) fn(o.host + sp.to / p.R * o.unit, off + k * cols * o.unit, cols * o.unit);
+            else fn(o.host + sp.to * o.unit, off + sp.from * o.unit, sp.cells * o.unit);
         }
     }
-    if (const OutRow& o = p.outs[kCross]; o.host) {   // the cross records: one span of sources' delivered columns per unit
+    if (const OutRow& o = p.outs[kCross]; o.host) {   // beside them the cross records: one span of sources' delivered columns per unit
         const Span cs = cross_span_of(p.items[u], p.C, p.f);
         fn(o.host + cs.to * o.unit, p.g.out_off(kCross) + cs.from * o.unit, cs.cells * o.unit);
     }
@@ -287,15 +284,13 @@ void run_units(Pipe& p) {
             const Span sp = span_of(it, p.C, R, V, k, 1);
             herr = launch_peaks(q.db + sp.from, (int64_t)(sp.cells / R), R, j.pko->k, j.pko->min_db, q.peaks + (size_t)k * (sp.cells / R) * j.pko->k, e->stream);
         }
-        // 3d. envelope: the samples under the unit's kept columns, in groups of f (wave.hip.inc), into the set's pairs
-        if (q.wave && herr == hipSuccess) {
+        // 3d. envelope and level meters: the samples under the unit's kept columns, in groups of f (window.hip.inc) - a pair and
+        // a level record per stream, a cross record per source - into the set's arrays
+        if ((q.wave || q.level || q.cross) && herr == hipSuccess) {
             const WaveRun wr = wave_run_of(it, j.n, j.hop, f);
-            herr = launch_wave(q.pcm, it.sc * V, it.samples, wr.first, wr.cols, j.hop, f, q.wave, wr.pairs, e->stream);
-        }
-        // 3d'. level meters: the same windows, one level record per stream and one cross record per source (level.hip.inc)
-        if ((q.level || q.cross) && herr == hipSuccess) {
-            const WaveRun wr = wave_run_of(it, j.n, j.hop, f);
-            if (q.level) herr = launch_level(q.pcm, it.sc * V, it.samples, wr.first, wr.cols, j.hop, f, q.level, wr.pairs, e->stream);
+            if (q.wave) herr = launch_wave(q.pcm, it.sc * V, it.samples, wr.first, wr.cols, j.hop, f, q.wave, wr.pairs, e->stream);
+            if (q.level && herr == hipSuccess)
+                herr = launch_level(q.pcm, it.sc * V, it.samples, wr.first, wr.cols, j.hop, f, q.level, wr.pairs, e->stream);
             if (q.cross && herr == hipSuccess)
                 herr = launch_cross(q.pcm, it.sc, V, e->cross_a, e->cross_b, it.samples, wr.first, wr.cols, j.hop, f, q.cross, wr.pairs, e->stream);
         }

@@ -277,13 +277,13 @@ hipError_t launch_reduce_columns(const float* db_in, const uint8_t* idx_in, int 
 // (position in row units, dB) pairs into peaks [columns][k] (8 bytes each; unused slots (-1, -inf)).  R % 4 == 0, 4 <= R <= 4096,
 // 1 <= k <= 32, min_db not NaN, db 16-byte and peaks 8-byte aligned; any number of columns (the grid strides, 64-bit offsets).
 hipError_t launch_peaks(const float* db, int64_t columns, int R, int k, float min_db, void* peaks, hipStream_t st);
-// waveform envelope (wave.hip.inc): per stream (S of them, `stride` samples apart, 4-byte aligned) and group of f columns of `hop`
+// waveform envelope (window.hip.inc): per stream (S of them, `stride` samples apart, 4-byte aligned) and group of f columns of `hop`
 // samples, from `first` samples into the stream on, `cols` columns in all, the pair (lo, hi) of the group's samples in the total
 // order of the floats (-0.0 < +0.0, NaN skipped, none: (+inf, -inf)) into out [S] x ceil(cols / f) pairs of 8 bytes, out_stride
 // pairs apart, 8-byte aligned.  The caller guarantees first + cols * hop <= the samples a stream holds.
 hipError_t launch_wave(const float* pcm, int S, int64_t stride, int64_t first, int64_t cols, int hop, int f, void* out, int64_t out_stride,
                        hipStream_t st);
-// level meters (level.hip.inc): the envelope's windows - S streams `stride` samples apart, groups of f columns of `hop` samples
+// level meters (window.hip.inc): the envelope's windows - S streams `stride` samples apart, groups of f columns of `hop` samples
 // from `first` on, `cols` columns - give one 24-byte level record each (sum of squares in two limbs, peak, odd count; the
 // samples in units of 2^-24) into out [S] x ceil(cols / f), out_stride records apart, 8-byte aligned; launch_cross: per pair p
 // of streams p views + a and p views + b one 16-byte cross record (sum of products in two limbs) into out [pairs] x ceil(cols / f).

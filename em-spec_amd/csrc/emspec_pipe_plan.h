@@ -183,7 +183,7 @@ inline Span span_of(const PipeItem& it, int64_t C, int R, int V, int k, int f) {
 // streams, in pair cells
 inline Span stereo_span_of(const PipeItem& it, int64_t C, int R) { return span_of(it, C, R, 1, 0, 1); }
 
-// The waveform envelope of a unit (wave.hip.inc), in pairs = delivered columns.  Its kernel reads the unit's
+// The waveform envelope of a unit (window.hip.inc), in pairs = delivered columns.  Its kernel reads the unit's
 // staged samples: the first window starts WaveRun::first samples into each of the unit's streams (off = n / 2 - hop / 2 past
 // the first sample of the unit's first kept column), `cols` = the kept columns in groups of f - a run starts on a multiple of
 // f, so its groups are the stream's - and writes ceil(cn / f) pairs per stream, stream after stream, into the set's array.
@@ -198,7 +198,7 @@ inline Span wave_span_of(const PipeItem& it, int64_t C, int V, int k, int f) {
     return Span{(size_t)k * crn, ((size_t)it.s0 * V + k) * Cr + (size_t)(it.c0 / f), crn};
 }
 
-// The level records of a unit (level.hip.inc) lie and travel exactly as the envelope's pairs: wave_run_of,
+// The level records of a unit (window.hip.inc) lie and travel exactly as the envelope's pairs: wave_run_of,
 // wave_span_of.  The cross records are one per SOURCE and delivered column: the unit's sc sources as sc streams of one view -
 // a run of columns is one source (sc = 1), so a pair never straddles a unit.
 inline Span cross_span_of(const PipeItem& it, int64_t C, int f) { return wave_span_of(it, C, 1, 0, f); }

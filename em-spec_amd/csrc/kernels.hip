@@ -608,8 +608,7 @@ hipError_t launch_occupy(int groups, int usec, unsigned* sink, hipStream_t st) {
 #include "pack.hip.inc"
 #include "reduce.hip.inc"
 #include "peaks.hip.inc"
-#include "wave.hip.inc"
-#include "level.hip.inc"
+#include "window.hip.inc"
 #include "pcm.hip.inc"
 #include "exact.hip.inc"
 #include "exact_fused.hip.inc"

@@ -4,7 +4,7 @@
 // display post-process is on), enqueued only while a setting is on.  It reads the launch's own LiveSinks descriptors, so it
 // knows j0, frames, flush, out_at, empty_col and uniform without another host round trip, and it writes exactly the column
 // slots the launch writes (emspec_live_plan.h: live_out_slot).  Included by kernels.hip behind live_launch.hip.inc (needs
-// peaks.hip.inc and wave.hip.inc).
+// peaks.hip.inc and window.hip.inc).
 namespace emspec {
 
 // ---- the peaks of one column, by one wave: peaks_kernel's body (peaks.hip.inc) as two functions.  A COPY: with the body
@@ -90,8 +90,8 @@ __device__ __forceinline__ void peaks_select_column(const float* x, int R, int Q
     }
 }
 
-// The envelope pair of frame j of stream s: key-min / key-max (wave.hip.inc) over the hop samples [j hop + off, j hop + off + hop)
-// of the stream, read by the rule of LiveBlock::sample - absolute sample a is fresh[a - newbase] when a >= newbase, else
+// The envelope pair of frame j of stream s: key-min / key-max (emspec_window_plan.h: wave_take, wave_bits) over the hop samples
+// [j hop + off, j hop + off + hop) of the stream, read by the rule of LiveBlock::sample - absolute sample a is fresh[a - newbase] when a >= newbase, else
 // sring[a & mask] - by the 64 lanes of one wave; every lane returns the pair.  The caller guarantees that frame j is one of the
 // launch's frames (its samples are then in the staging block or, after the launch's ingest, still in the ring).
 __device__ __forceinline__ uint2 live_wave_pair(const LiveSinks& lv, const LiveStream& d, int s, long long j, int hop, int off, int lane) {

@@ -1,20 +1,30 @@
-// level_plan_driver.cpp — pins the level meters' plan header (em-spec_amd/csrc/emspec_level_plan.h) and their rows of the host
-// pipeline's plan (emspec_pipe_plan.h: kLevel, kCross, cross_span_of) without a GPU:
+// window_plan_driver.cpp — pins the window walk's plan header (em-spec_amd/csrc/emspec_window_plan.h) and the level meters' rows of
+// the host pipeline's plan (emspec_pipe_plan.h: kLevel, kCross, cross_span_of) without a GPU:
 //   1. the quantiser against an integer evaluation from the bits written here, on the edges and on random bits;
 //   2. the limb bounds: 2^30 saturated samples leave every limb of a level and of a cross record (both signs) inside 64 bits,
 //      and the limbs still compose to the exact sum;
 //   3. the combine: the record of a random signal is that of any split into pieces, combined in any grouping;
 //   4. the pipeline table: with the rows cleared a set has the layout it had, with them set the new arrays lie behind the
-//      stereo rows, and the pieces of all units cover the caller's [S V][Cr] level and [S][Cr] cross records exactly once.
-//   g++ -std=c++17 -O1 -fsanitize=address,undefined -I em-spec_amd/csrc tests/cdriver/level_plan_driver.cpp -o level_plan_driver
-// Prints "ok <quantised> <splits> <plans>" and returns 0, or prints the first violation and returns 1 (tests/test_level_cpu.py).
-#include "emspec_level_plan.h"
+//      stereo rows, and the pieces of all units cover the caller's [S V][Cr] level and [S][Cr] cross records exactly once;
+//   5. the scan the kernels run (window_scan) for the three reducers: the lanes of every team size, combined, against the plain
+//      loop of one sample at a time, on heap blocks that end with the window (and start with it where the alignment allows), so
+//      that the sanitizer sees a read outside [a, b), and a filler in front that every reducer shows;
+//   6. the split: the pieces tile each window, those past a short last window's end are empty, and the pieces' results merged
+//      in either order are the window's;
+//   7. the team rule on its edges.
+//   g++ -std=c++17 -O1 -fsanitize=address,undefined -I em-spec_amd/csrc tests/cdriver/window_plan_driver.cpp -o window_plan_driver
+// Prints "ok <quantised> <splits> <plans> <scans> <pieces>" and returns 0, or prints the first violation and returns 1
+// (tests/test_level_cpu.py).
+#include "emspec_window_plan.h"
 #include "emspec_pipe_plan.h"
 
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <random>
+#include <vector>
+#include <algorithm>
 
 using namespace emspec;
 
@@ -52,7 +62,16 @@ int64_t k_of_bits(uint32_t u, uint32_t& odd) {
 }
 uint32_t bits_of(float x) { uint32_t u; std::memcpy(&u, &x, 4); return u; }
 
-long long quantised = 0, splits = 0, plans = 0;
+// The definition on host arrays, one window of x[0 .. count): one sample at a time
+template <class Red> typename Red::Acc plain(const uint32_t* xa, const uint32_t* xb, int64_t count) {
+    typename Red::Acc r = Red::start();
+    for (int64_t i = 0; i < count; ++i) Red::take(r, xa[i], Red::kStreams == 2 ? xb[i] : 0);
+    return r;
+}
+emspec_level level_of(const uint32_t* x, int64_t count) { return plain<LevelRed>(x, x, count); }
+emspec_cross cross_of(const uint32_t* xa, const uint32_t* xb, int64_t count) { return plain<CrossRed>(xa, xb, count); }
+
+long long quantised = 0, splits = 0, plans = 0, scans = 0, pieces = 0;
 
 bool check_quantiser() {
     auto one = [](uint32_t u) {
@@ -204,11 +223,119 @@ bool check_plan(int S, int V, int64_t L, int n, int hop, int f, int target, bool
     return true;
 }
 
+// ---- 5. the scan.  A heap block of `pad` + count samples, 16-byte aligned: the window starts pad samples in (its start alignment)
+// and ends with the block, so the sanitizer sees every read behind it and, without a pad, in front of it.  A read of the pad
+// itself stays inside the block; the filler shows it.  Two kinds of window: every kind of sample (+0.0, -0.0, the infinities,
+// NaN of both signs, denormals, |x| >= 128, ordinary values) in front of a saturated filler, which a level or a cross record
+// that took one shows in its odd count or its sum; and `plain`, ordinary values below 1 only, in front of a filler of both
+// infinities, which lies outside the window's range, so that the envelope shows it too.
+struct Block {
+    uint32_t* base = nullptr; const uint32_t* x = nullptr;
+    Block(int pad, int64_t count, std::mt19937& rng, bool plain = false) {
+        void* p = nullptr;
+        if (posix_memalign(&p, 16, (size_t)(pad + count) * 4 + (pad + count == 0))) abort();
+        base = static_cast<uint32_t*>(p);
+        for (int i = 0; i < pad; ++i) base[i] = !plain ? 0x7f7fffffu : i % 2 ? 0xff800000u : 0x7f800000u;
+        static const uint32_t special[] = {0u, 0x80000000u, 0x7f800000u, 0xff800000u, 0x7fc00000u, 0xffc00001u, 0x00000001u, 0x807fffffu,
+                                           0x43000000u, 0xc3000001u, 0x7f7fffffu, 0x3f800000u, 0xbf800000u};
+        for (int64_t i = 0; i < count; ++i) {
+            const uint32_t v = rng();
+            base[pad + i] = v % 4 == 0 && !plain ? special[(v >> 8) % (sizeof special / 4)]
+                                                 : bits_of(std::ldexp((float)((int)((v >> 4) % 2000001) - 1000000) / 1000000.0f, v % 4 == 1 ? -20 : 0));
+        }
+        x = base + pad;
+    }
+    ~Block() { free(base); }
+    Block(const Block&) = delete;
+};
+
+template <class Red> bool check_scan(const char* name) {
+    std::mt19937 rng(11);
+    std::vector<int64_t> lengths;
+    for (int64_t n = 0; n <= 70; ++n) lengths.push_back(n);
+    for (int64_t n : {255, 256, 257, 1027, 16384}) lengths.push_back(n);
+    for (int64_t n : lengths)
+        for (int pa = 0; pa < 4; ++pa)
+            for (int pb = 0; pb < (Red::kStreams == 2 ? 8 : 2); ++pb) {   // (B's start alignment, and both kinds of window)
+                const Block A(pa, n, rng, pb & 1), B(pb >> 1, Red::kStreams == 2 ? n : 0, rng, pb & 1);
+                const typename Red::Acc want = plain<Red>(A.x, B.x, n);
+                for (int T : {1, 2, 4, 8, 16, 32, 64, 256}) {
+                    typename Red::Acc got = Red::start();
+                    for (int l = 0; l < T; ++l) {
+                        typename Red::Acc r = Red::start();
+                        window_scan<Red>(A.x, B.x, 0, n, l, T, r);
+                        Red::combine(got, r);
+                    }
+                    CHECK(std::memcmp(&got, &want, sizeof want) == 0, "%s: the scan of %lld samples by %d lanes differs (alignments %d, %d)", name, (long long)n, T, pa, pb >> 1);
+                    ++scans;
+                }
+            }
+    return true;
+}
+
+// ---- 6. the split: a launch of `cols` columns of hop samples in groups of f, from `first` on
+template <class Red> bool check_pieces(const char* name, const uint32_t* xa, const uint32_t* xb, int64_t first, int64_t cols, int64_t hop, int64_t f, int64_t want_ppw) {
+    const int64_t longest = window_longest(f, cols, hop), ppw = window_pieces(longest), Cr = (cols + f - 1) / f;
+    CHECK(longest > kWindowSplit && ppw == want_ppw, "%s: %lld pieces per window of %lld samples", name, (long long)ppw, (long long)longest);
+    for (int64_t g = 0; g < Cr; ++g) {
+        const WindowSpan w = window_of(g, f, cols, hop, first);
+        CHECK(w.a == first + g * f * hop && w.b == first + std::min((g + 1) * f, cols) * hop, "%s: window %lld", name, (long long)g);
+        std::vector<typename Red::Acc> part;
+        int64_t at = w.a;
+        for (int64_t p = 0; p < ppw; ++p) {
+            const WindowSpan ps = window_piece(w, p);
+            CHECK(ps.a <= ps.b && ps.b - ps.a <= kWindowPiece && ps.b <= w.b, "%s: piece %lld of window %lld", name, (long long)p, (long long)g);
+            if (at < w.b) CHECK(ps.a == at && (ps.b == w.b || ps.b - ps.a == kWindowPiece), "%s: the pieces of window %lld do not tile it", name, (long long)g);
+            else CHECK(ps.a == ps.b, "%s: a piece past the end of window %lld is not empty", name, (long long)g);
+            at = ps.b > at ? ps.b : at;
+            typename Red::Acc r = Red::start();
+            window_scan<Red>(xa, xb, ps.a, ps.b, 0, 1, r);
+            part.push_back(r);
+            ++pieces;
+        }
+        CHECK(at == w.b, "%s: the pieces of window %lld end at %lld, not %lld", name, (long long)g, (long long)at, (long long)w.b);
+        typename Red::Acc fwd = Red::start(), bwd = Red::start();
+        for (size_t i = 0; i < part.size(); ++i) { Red::combine(fwd, part[i]); Red::combine(bwd, part[part.size() - 1 - i]); }
+        const typename Red::Acc want = plain<Red>(xa + w.a, xb + w.a, w.b - w.a);
+        CHECK(std::memcmp(&fwd, &want, sizeof want) == 0 && std::memcmp(&bwd, &want, sizeof want) == 0, "%s: the merged pieces of window %lld differ from one pass", name, (long long)g);
+    }
+    return true;
+}
+bool check_split() {
+    std::mt19937 rng(13);
+    // windows of 76,800 samples, two pieces each, in front of a last one of 2,560; of 65,537 in front of 65,535 (its second piece
+    // is empty); of 65,536 (one piece) in front of one sample
+    const int64_t geoms[3][5] = {{3, 610, 256, 300, 2}, {1, 65537 + 65535, 1, 65537, 2}, {2, 2 * 65536 + 1, 1, 65536, 1}};
+    for (auto& g : geoms) {
+        const Block A(0, g[0] + g[1] * g[2], rng), B(1, g[0] + g[1] * g[2], rng);
+        if (!check_pieces<EnvelopeRed>("envelope", A.x, A.x, g[0], g[1], g[2], g[3], g[4]) || !check_pieces<LevelRed>("level", A.x, A.x, g[0], g[1], g[2], g[3], g[4]) ||
+            !check_pieces<CrossRed>("cross", A.x, B.x, g[0], g[1], g[2], g[3], g[4]))
+            return false;
+    }
+    const WindowSpan last = window_of(2, 300, 610, 256, 0);
+    CHECK(last.b - last.a == 2560 && window_longest(300, 610, 256) == 76800, "the short last window");
+    return true;
+}
+
+// ---- 7. the team rule: the largest power of two up to 64 that leaves a lane 16 samples or more (T 32 <= longest doubles T)
+bool check_team() {
+    const int64_t edges[9][2] = {{1, 1}, {31, 1}, {32, 2}, {63, 2}, {64, 4}, {2047, 64}, {2048, 64}, {16384, 64}, {16385, 64}};
+    for (auto& e : edges) CHECK(window_team(e[0]) == e[1], "window_team(%lld) = %d", (long long)e[0], window_team(e[0]));
+    for (int64_t n = 1; n <= 20000; ++n) {
+        int T = 1;
+        while (T < 64 && T * 32 <= n) T *= 2;
+        CHECK(window_team(n) == T, "window_team(%lld)", (long long)n);
+    }
+    CHECK(kWindowBlock == 256 && kWindowSplit == 16384 && kWindowPiece == 65536, "the split constants");
+    return true;
+}
+
 }  // namespace
 
 int main() {
     static_assert(sizeof(emspec_level) == 24 && alignof(emspec_level) == 8 && sizeof(emspec_cross) == 16 && alignof(emspec_cross) == 8, "record sizes");
     if (!check_quantiser() || !check_limbs() || !check_combine()) return 1;
+    if (!check_scan<EnvelopeRed>("envelope") || !check_scan<LevelRed>("level") || !check_scan<CrossRed>("cross") || !check_split() || !check_team()) return 1;
     const int shapes[4][2] = {{256, 1}, {1024, 255}, {4096, 256}, {16384, 512}};
     for (auto& sh : shapes)
         for (int S : {1, 3, 8})
@@ -220,6 +347,6 @@ int main() {
                                 if (extra > 4000000 && S * V > 8) continue;   // (keeps the hit maps small)
                                 if (!check_plan(S, V, sh[0] + extra, sh[0], sh[1], f, target, whole)) return 1;
                             }
-    printf("ok %lld %lld %lld\n", quantised, splits, plans);
+    printf("ok %lld %lld %lld %lld %lld\n", quantised, splits, plans, scans, pieces);
     return 0;
 }

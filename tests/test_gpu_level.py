@@ -12,14 +12,12 @@ import emspec
 import level_ref as LR
 import pcm_ref as PR
 from emspec import synth
+from window_cases import DEVICE_CASES, IDS, PATHS, PRECEDENCE, SPLIT_CASES, _team
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 U = np.uint32
-IDS = dict(ids=lambda c: "n%d-hop%d-L%d-f%d" % c)
-# beside the envelope's cases: windows of 76,800 samples (two pieces each) in front of a last one of 2,560, shorter than the split
-SPLIT_CASES = [(1024, 256, 1024 + 256 * 609 + 3, 300), (1024, 256, 1024 + 256 * 609 + 3, 65536)]
 
 
 @pytest.fixture(scope="module")
@@ -71,23 +69,10 @@ def _dev_cross(e, x, views, a, b, n, hop, f):
     return _records(e, lambda out: e.cross_device(src, views, a, b, n, hop, f, out=out), x.shape[0] // views, Cr, emspec.CROSS_DTYPE)
 
 
-# ---- 1. the device entry on the shared cases: every team size from one lane (hop 1) to 64 (hop = n = 4096), and the split
-def _team(n, hop, L, f):
-    longest = min(f, LR.num_columns(L, n, hop)) * hop
-    if longest > 16384:
-        return "split"
-    T = 1
-    while T < 64 and T * 32 <= longest:
-        T *= 2
-    return T
-
-
-# (the envelope's cases have no team of 2 or 4 lanes: windows of 32 and 64 samples)
-DEVICE_CASES = LR.CASES + [(256, 32, 4099, 1), (256, 32, 4099, 2), (512, 512, 5001, 2)]
-
-
+# ---- 1. the device entry on the cases shared with the envelope's suite (tests/window_cases.py): every team size from one lane
+# (hop 1) to 64 (hop = n = 4096), and the split
 def test_cases_cover_every_path():
-    assert {_team(*c) for c in DEVICE_CASES} == {1, 2, 4, 8, 16, 32, 64, "split"}
+    assert {_team(*c) for c in DEVICE_CASES} == PATHS == {1, 2, 4, 8, 16, 32, 64, "split"}
     assert _team(256, 1, 300, 1) == 1 and _team(4096, 4096, 5 * 4096 + 1, 1) == 64
 
 
@@ -323,3 +308,20 @@ def test_refusals_through_the_engine(exact):
     assert bool(torch.all(o == 0xA5))
     got = exact.level_device(t, n, hop, 1).cpu().numpy().view(emspec.LEVEL_DTYPE)[..., 0]
     assert LR.same(got, LR.levels(x, n, hop, 1))
+
+
+def test_device_entries_report_the_first_broken_rule(exact):
+    """With more than one rule broken the three device entries report the same one as the host forms (tests/test_level_cpu.py):
+    the pair's rules (cross), then streams, length, FFT size, hop, factor.  Refused before anything is read or written."""
+    lib, h = exact._lib, exact._h
+    t = torch.zeros(4 * 1000, dtype=torch.float32, device="cuda")
+    o = torch.full((4 * 8 * 24,), 0xA5, dtype=torch.uint8, device="cuda")
+    p, q, st = C.c_void_p(t.data_ptr()), C.c_void_p(o.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for (S, L, n, hop, f), word in PRECEDENCE:
+        for call in (lambda: lib.emspec_wave_device(h, p, S, L, n, hop, f, q, st), lambda: lib.emspec_level_device(h, p, S, L, n, hop, f, q, st),
+                     lambda: lib.emspec_cross_device(h, p, S, 1, 0, 0, L, n, hop, f, q, st)):
+            msg = (call(), lib.emspec_last_error(h).decode())
+            assert msg[0] == emspec.ERR_INVALID_ARG and word in msg[1], ((S, L, n, hop, f), msg)
+    assert lib.emspec_cross_device(h, p, -1, 0, 0, 0, -1, 300, 0, 0, q, st) == emspec.ERR_INVALID_ARG and "views" in lib.emspec_last_error(h).decode()
+    torch.cuda.synchronize()
+    assert bool(torch.all(o == 0xA5))

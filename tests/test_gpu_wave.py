@@ -16,6 +16,7 @@ import emspec
 import pcm_ref as PR
 import wave_ref as W
 from emspec import synth
+from window_cases import DEVICE_CASES, IDS, PATHS, SPLIT_CASES, _team
 
 pytestmark = pytest.mark.gpu
 
@@ -58,12 +59,28 @@ def _dev_wave(e, x, n, hop, f):
     return got[2:-2].reshape(S, Cr, 2)
 
 
-# ---- 1. the device entry on the shared cases
-@pytest.mark.parametrize("case", W.CASES, ids=lambda c: "n%d-hop%d-L%d-f%d" % c)
+# ---- 1. the device entry on the cases shared with the level meters' suite (tests/window_cases.py): every team size and the split
+def test_cases_cover_every_path():
+    assert {_team(*c) for c in DEVICE_CASES} == PATHS == {1, 2, 4, 8, 16, 32, 64, "split"}
+    assert _team(256, 1, 300, 1) == 1 and _team(4096, 4096, 5 * 4096 + 1, 1) == 64
+
+
+@pytest.mark.parametrize("case", DEVICE_CASES, **IDS)
 def test_wave_device_is_the_reference(fast, case):
     n, hop, L, f = case
     x = W.case_signal(case)
     assert W.same(_dev_wave(fast, x, n, hop, f), W.envelope(x, n, hop, f))
+
+
+@pytest.mark.parametrize("case", SPLIT_CASES, **IDS)
+def test_split_path(fast, case):
+    """factor 300: three windows, two pieces each, the last one shorter than the split, so that its second piece lies past its
+    end; factor 65536: one window of three pieces"""
+    n, hop, L, f = case
+    x = W.case_signal(case, seed=2)
+    want = W.envelope(x, n, hop, f)
+    assert _team(*case) == "split" and (f == 65536 or (want.shape[1] == 3 and 2560 < 16384 < 65536 < 300 * 256))
+    assert W.same(_dev_wave(fast, x, n, hop, f), want)
 
 
 def test_wave_device_is_the_same_on_an_exact_engine(exact):

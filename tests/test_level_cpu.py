@@ -1,7 +1,7 @@
 """CPU: the level meters (include/emspec.h: emspec_level_host, emspec_cross_host and the pure helpers) without
 a device - the host forms against tests/level_ref.py byte for byte on the envelope's cases and on the worst-case signals, the
 quantiser's edges, the factor law, known answers through the helpers, the refusals, the plan header through its stand-alone
-driver (tests/cdriver/level_plan_driver.cpp), and the Node binding's levelsOf / crossOf."""
+driver (tests/cdriver/window_plan_driver.cpp), and the Node binding's levelsOf / crossOf."""
 import ctypes as C
 import math
 import os
@@ -14,6 +14,7 @@ import pytest
 import emspec
 import level_ref as LR
 import worst_signals as WS
+from window_cases import PRECEDENCE
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
@@ -216,18 +217,38 @@ def test_refusals():
         emspec.cross_host(x, 2, 0, 2, 256, 100)
 
 
+def test_host_forms_report_the_first_broken_rule():
+    lib = emspec.load()
+    x = np.zeros((4, 1000), F)
+    out = np.full((4, 8, 3), 7, np.uint64)
+    p, o = x.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)
+    for (S, L, n, hop, f), word in PRECEDENCE:
+        for call in (lambda: lib.emspec_wave_host(p, S, L, n, hop, f, o), lambda: lib.emspec_level_host(p, S, L, n, hop, f, o),
+                     lambda: lib.emspec_cross_host(p, S, 1, 0, 0, L, n, hop, f, o)):
+            msg = (call(), lib.emspec_last_error(None).decode())
+            assert msg[0] == emspec.ERR_INVALID_ARG and word in msg[1], ((S, L, n, hop, f), msg)
+    # the choice of streams comes first
+    assert lib.emspec_cross_host(p, -1, 0, 0, 0, -1, 300, 0, 0, o) == emspec.ERR_INVALID_ARG and "views" in lib.emspec_last_error(None).decode()
+    assert lib.emspec_cross_host(p, 1024, 64, 0, 1, -1, 300, 0, 0, o) == emspec.ERR_INVALID_ARG and "pairs x views" in lib.emspec_last_error(None).decode()
+    assert np.all(out == 7)
+
+
 def test_level_plan_driver(tmp_path):
     """The stand-alone driver over the plan headers, built with the host compiler under ASan and UBSan (a program of its own:
     nothing is preloaded): the quantiser against the integer form, limb bounds at 2^30 saturated samples, combine associativity on
-    random splits, and the pipeline table's offsets and coverage with the new rows set and cleared."""
-    exe = str(tmp_path / "level_plan_driver")
+    random splits, the pipeline table's offsets and coverage with the new rows set and cleared - and the kernels' own scan for the
+    envelope, level and cross reducers: every lane of every team size against the plain loop on heap blocks that end with the
+    window, the pieces of long windows, the team rule."""
+    exe = str(tmp_path / "window_plan_driver")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-I", os.path.join(ROOT, "em-spec_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "cdriver", "level_plan_driver.cpp"), "-o", exe])
+                           os.path.join(ROOT, "tests", "cdriver", "window_plan_driver.cpp"), "-o", exe])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and not r.stderr and r.stdout.startswith("ok "), (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
-    quantised, splits, plans = (int(v) for v in r.stdout.split()[1:4])
+    quantised, splits, plans, scans, pieces = (int(v) for v in r.stdout.split()[1:6])
     assert quantised >= 2000000 and splits == 300 and plans >= 1000
+    # 76 lengths x 4 alignments of A (x 4 of B for the cross reducer) x 2 kinds of window x 8 team sizes; 13 pieces per reducer
+    assert scans == 76 * 4 * 2 * 8 * (1 + 1 + 4) and pieces == 3 * 13
 
 
 def test_node_levels_of_is_the_reference(refs):
