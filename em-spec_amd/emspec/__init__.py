@@ -1242,6 +1242,27 @@ class Engine:
                                                nframes, _np_ptr(pw), _np_ptr(col), _np_ptr(row)))
         return pw, col, row
 
+    def parity_dump_device(self, pcm_t, n, hop, reassign=True, frame0=0, nframes=None, power=None, col=None, row=None, stream=None):
+        """emspec_parity_dump_device: pcm_t a contiguous float32 CUDA tensor [S, L] -> (power float32, col int32, row int32)
+        CUDA tensors [S, nframes, n/2+1] (those given are written in place).  FAST-mode engines only.  Enqueues on `stream`
+        (default: the current torch stream); does not synchronise."""
+        import torch
+        assert pcm_t.is_cuda and pcm_t.dtype == torch.float32 and pcm_t.is_contiguous() and pcm_t.dim() == 2
+        S, L = pcm_t.shape
+        if nframes is None:
+            nframes = num_columns(L, n, hop) - frame0
+        shape = (S, max(int(nframes), 0), n // 2 + 1)
+        power = torch.empty(shape, dtype=torch.float32, device=pcm_t.device) if power is None else power
+        col = torch.empty(shape, dtype=torch.int32, device=pcm_t.device) if col is None else col
+        row = torch.empty(shape, dtype=torch.int32, device=pcm_t.device) if row is None else row
+        for t, dt in ((power, torch.float32), (col, torch.int32), (row, torch.int32)):
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape
+        st = stream if stream is not None else torch.cuda.current_stream(pcm_t.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        self._chk(self._lib.emspec_parity_dump_device(self._h, ptr(pcm_t), S, L, n, hop, int(bool(reassign)), frame0, nframes,
+                                                      ptr(power), ptr(col), ptr(row), C.c_void_p(st.cuda_stream)))
+        return power, col, row
+
     def parity_dump_exact(self, pcm, n, hop, reassign=True, frame0=0, nframes=None):
         """EXACT-mode engine: (power float64, col, row, q int64), each [S][nframes][n/2+1]."""
         pcm = np.ascontiguousarray(pcm, np.float32)

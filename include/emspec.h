@@ -315,6 +315,21 @@ void emspec_host_free(void* p);
  * without synchronising.  Output pointers may be NULL.  Calls on one engine
  * share its device workspaces: enqueue them on one stream, or order them
  * yourself (events) when using several.
+ *
+ * Streams and ordering (every entry with a hip_stream argument; tests/test_gpu_stream_order.py holds each to it under forced
+ * delays).  All of an entry's work is enqueued on hip_stream, and the entry returns without synchronising, except where its own
+ * text says otherwise (emspec_wire_pack when the size is asked for, emspec_wire_unpack's header check, emspec_gather_columns).
+ *   The library orders by itself: the EXACT kernels' low-row scratch - a launch on another stream than the previous one waits
+ *     for it, and a call that has to regrow the scratch blocks the host until the launch on the old buffer has finished; and
+ *     the streaming calls behind the views and re-analyses of the live rings (emspec_history_view_device,
+ *     emspec_history_view_stereo_device, emspec_audio_view_device, emspec_audio_batch_device): a push, emspec_reset_stream,
+ *     emspec_set_live_history(0) and emspec_set_live_audio(0) that follow one of them take effect behind it.
+ *   The caller orders: everything else that shares the engine's workspaces - two device entries on two streams need an event
+ *     between them (record on the first stream behind call 1, make the second stream wait for it in front of call 2).  A call
+ *     that has to build a shape's tables or grow a workspace may block the host while it does.
+ *   The caller's duty: the setters that rewrite device tables - emspec_set_colormap, emspec_set_stereo_colormap,
+ *     emspec_set_row_edges_hz - run on the engine's own stream; do not call them while a device entry is pending on another
+ *     stream.
  */
 int emspec_batch_device(emspec_engine* e, const float* pcm_dev, int32_t S,
                         int64_t L, int32_t n, int32_t hop, int32_t reassign,
