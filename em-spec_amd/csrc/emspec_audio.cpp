@@ -16,7 +16,7 @@ LiveState* session_of(emspec_engine* e, int32_t session) {
     return session == EMSPEC_SESSION_MULTI ? &e->live : session == EMSPEC_SESSION_ONE ? &e->one : nullptr;
 }
 // the samples stream s of the session has in its ring's numbering: from the session's own counters
-int64_t stream_end(const LiveState& lv, int s) { return audio_end(lv.g.form, lv.c.fed[s], lv.c.newbase[s], lv.g.n, lv.g.hop); }
+int64_t stream_end(const LiveState& lv, int s) { return audio_end(lv.ss.g.form, lv.c.fed[s], lv.c.newbase[s], lv.ss.g.n, lv.ss.g.hop); }
 
 // Every check of a view: nothing is launched or written when it fails.
 // (with_out = false: the re-analysis, whose output is the engine's own workspace)
@@ -26,10 +26,10 @@ int view_check(emspec_engine* e, int32_t session, int32_t stream0, int32_t strea
     if (e->audio_W <= 0) return fail(e, EMSPEC_ERR_STATE, "no live audio history is set (emspec_set_live_audio)");
     if (!lvp) return fail(e, EMSPEC_ERR_STATE, "session must be EMSPEC_SESSION_MULTI or EMSPEC_SESSION_ONE");
     const LiveState& lv = *lvp;
-    if (lv.g.form == 0 || !lv.d_aring) return fail(e, EMSPEC_ERR_STATE, "the session has not started: it has no audio history");
+    if (lv.ss.g.form == 0 || !lv.d_aring) return fail(e, EMSPEC_ERR_STATE, "the session has not started: it has no audio history");
     if (count < 1) return fail(e, EMSPEC_ERR_INVALID_ARG, "an audio view needs at least one sample");
-    if (streams < 1 || stream0 < 0 || stream0 > lv.g.S - streams)
-        return fail(e, EMSPEC_ERR_INVALID_ARG, "the view's streams must lie inside the session's 0.." + std::to_string(lv.g.S - 1));
+    if (streams < 1 || stream0 < 0 || stream0 > lv.ss.g.S - streams)
+        return fail(e, EMSPEC_ERR_INVALID_ARG, "the view's streams must lie inside the session's 0.." + std::to_string(lv.ss.g.S - 1));
     if (with_out && !out) return fail(e, EMSPEC_ERR_INVALID_ARG, "an audio view needs an output");
     if (with_out && reinterpret_cast<uintptr_t>(out) % 4) return fail(e, EMSPEC_ERR_INVALID_ARG, "an audio view's output must be 4-byte aligned");
     if (stride < count) return fail(e, EMSPEC_ERR_INVALID_ARG, "an audio view's stride must be at least its count");
@@ -81,7 +81,7 @@ namespace emspec {
 int audio_ready(emspec_engine* e, LiveState& lv) {
     if (e->audio_W <= 0) return EMSPEC_OK;
     int rc;
-    if ((rc = grow(e, (void**)&lv.d_aring, &lv.aring_bytes, audio_ring_bytes(lv.g.S, e->audio_W)))) return rc;
+    if ((rc = grow(e, (void**)&lv.d_aring, &lv.aring_bytes, audio_ring_bytes(lv.ss.g.S, e->audio_W)))) return rc;
     if (!lv.audio_done) HIPCHK(e, hipEventCreateWithFlags(&lv.audio_done, hipEventDisableTiming));
     return EMSPEC_OK;
 }
@@ -103,7 +103,7 @@ void audio_destroy(emspec_engine* e) {
 }
 int audio_store(emspec_engine* e, LiveState& lv, const LiveSinks& ls, bool flush) {
     if (e->audio_W <= 0 || flush || !lv.d_aring || !ls.fresh) return EMSPEC_OK;
-    const LiveGeometry& g = lv.g;
+    const LiveGeometry& g = lv.ss.g;
     int64_t most = 0;
     for (int s = 0; s < g.S; ++s) {
         const LiveStream& d = lv.desc()[s];
@@ -136,7 +136,7 @@ int emspec_set_live_audio(emspec_engine* e, int64_t samples) {
     // a ring holds the samples since each stream's start: a stream that already has samples has some that were not stored
     for (const LiveState* lv : {&e->live, &e->one})
         for (int s = 0; s < lv->c.streams(); ++s)
-            if (lv->g.form != 0 && (lv->c.fed[s] > 0 || lv->c.seen[s] > 0))
+            if (lv->ss.g.form != 0 && (lv->c.fed[s] > 0 || lv->c.seen[s] > 0))
                 return fail(e, EMSPEC_ERR_STATE, "the audio history needs every sample of a stream since its start: a session has samples fed; call emspec_reset() first");
     if (samples != e->audio_W) {   // (a ring of another W: the next call of each session allocates its own)
         HIPCHK(e, hipSetDevice(e->device));
@@ -151,7 +151,7 @@ int emspec_set_live_audio(emspec_engine* e, int64_t samples) {
 int64_t emspec_live_audio(const emspec_engine* e, int32_t session, int32_t stream, int64_t* first_sample) {
     if (!e || e->audio_W <= 0) return -1;
     const LiveState* lv = session_of(const_cast<emspec_engine*>(e), session);
-    if (!lv || lv->g.form == 0 || stream < 0 || stream >= lv->g.S) return -1;
+    if (!lv || lv->ss.g.form == 0 || stream < 0 || stream >= lv->ss.g.S) return -1;
     const int64_t end = stream_end(*lv, stream);
     if (first_sample) *first_sample = audio_first(end, e->audio_W);
     return end;

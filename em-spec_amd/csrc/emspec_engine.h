@@ -6,7 +6,7 @@
 #include "../../include/emspec.h"
 #pragma GCC visibility pop
 #include "emspec_launch.h"
-#include "emspec_live_band_plan.h"
+#include "emspec_live_plan.h"
 #include "emspec_tables.h"
 
 #include <functional>
@@ -39,16 +39,11 @@ struct LivePcm {   // PCM session (emspec_push_samples_pcm; form 2 only): S = so
     emspec_pcm_format fmt{};
 };
 struct LiveState {
-    LiveGeometry g;
+    LiveSession ss;   // the geometry: ss.g at the first band's fft size, and the bands (ss.kind == kLiveNone: no session)
     LiveCounters c;
     LivePcm pcm;
-    // multi-band session (emspec_columns_multiband / emspec_push_samples_multiband; mb.bands == 0: none): g is then mb.g, the
-    // single-resolution geometry at n[0], and the bands' rings are mb's
-    LiveBandGeometry mb;
-    void* d_cells = nullptr; size_t cells_bytes = 0;    // [S][slots][rows] float32 (FAST) / u64 (EXACT): band 0's
-    // the column rings of the bands behind the first, band k's at [k - 1]: [S][slots_k][rows_k] (a multi-resolution session: the
-    // short band's [S][slots_high][R - split] at [0])
-    void* d_cells_band[kMaxBands - 1] = {}; size_t cells_band_bytes[kMaxBands - 1] = {};
+    // the bands' column rings, band k's [S][slots_k][rows_k] float32 (FAST) / u64 (EXACT)
+    void* d_cells[kMaxBands] = {}; size_t cells_bytes[kMaxBands] = {};
     float* d_sring = nullptr; size_t sring_bytes = 0;   // [S][ring_mask + 1]
     unsigned* d_done = nullptr; size_t done_bytes = 0;  // [S] arrival counters ([bands][S] with several bands: one set per band)
     float* d_raw = nullptr; size_t raw_bytes = 0;       // display post-process: raw dB [S][mmax][rows]

@@ -34,11 +34,11 @@ int view_launch(emspec_engine* e, int32_t session, int32_t stream0, int32_t stre
     if (e->history_W <= 0) return fail(e, EMSPEC_ERR_STATE, "no live history is set (emspec_set_live_history)");
     if (!lvp) return fail(e, EMSPEC_ERR_STATE, "session must be EMSPEC_SESSION_MULTI or EMSPEC_SESSION_ONE");
     LiveState& lv = *lvp;
-    if (lv.g.form == 0 || !lv.d_hring) return fail(e, EMSPEC_ERR_STATE, "the session has not started: it has no history");
+    if (lv.ss.g.form == 0 || !lv.d_hring) return fail(e, EMSPEC_ERR_STATE, "the session has not started: it has no history");
     if (factor < 1 || factor > kHistoryMaxFactor) return fail(e, EMSPEC_ERR_INVALID_ARG, "a view's factor must be in 1..65536");
     if (groups < 1) return fail(e, EMSPEC_ERR_INVALID_ARG, "a view needs at least one group");
-    if (streams < 1 || stream0 < 0 || stream0 > lv.g.S - streams)
-        return fail(e, EMSPEC_ERR_INVALID_ARG, "the view's streams must lie inside the session's 0.." + std::to_string(lv.g.S - 1));
+    if (streams < 1 || stream0 < 0 || stream0 > lv.ss.g.S - streams)
+        return fail(e, EMSPEC_ERR_INVALID_ARG, "the view's streams must lie inside the session's 0.." + std::to_string(lv.ss.g.S - 1));
     if (!db && !index && !rgba) return fail(e, EMSPEC_ERR_INVALID_ARG, "a view needs at least one output");
     if (map && !(map->db_range > 0.0f && map->db_top == map->db_top && map->gate_db == map->gate_db && map->shift_db == map->shift_db))
         return fail(e, EMSPEC_ERR_INVALID_ARG, "a view's map needs db_range > 0 and no NaN field");
@@ -81,9 +81,9 @@ namespace emspec {
 int history_ready(emspec_engine* e, LiveState& lv) {
     if (e->history_W <= 0) return EMSPEC_OK;
     int rc;
-    const bool fresh = lv.hends_bytes < (size_t)lv.g.S * 8;
-    if ((rc = grow(e, (void**)&lv.d_hring, &lv.hring_bytes, history_ring_bytes(lv.g.S, e->history_W, e->cfg.rows)))) return rc;
-    if ((rc = grow(e, (void**)&lv.d_hends, &lv.hends_bytes, (size_t)lv.g.S * 8))) return rc;
+    const bool fresh = lv.hends_bytes < (size_t)lv.ss.g.S * 8;
+    if ((rc = grow(e, (void**)&lv.d_hring, &lv.hring_bytes, history_ring_bytes(lv.ss.g.S, e->history_W, e->cfg.rows)))) return rc;
+    if ((rc = grow(e, (void**)&lv.d_hends, &lv.hends_bytes, (size_t)lv.ss.g.S * 8))) return rc;
     if (fresh) HIPCHK(e, hipMemsetAsync(lv.d_hends, 0, lv.hends_bytes, e->stream));
     if (!lv.view_done) HIPCHK(e, hipEventCreateWithFlags(&lv.view_done, hipEventDisableTiming));
     return EMSPEC_OK;
@@ -120,7 +120,7 @@ int emspec_set_live_history(emspec_engine* e, int64_t columns) {
     // a ring holds the columns since each stream's start: a stream that already has frames has columns that were not stored
     for (const LiveState* lv : {&e->live, &e->one})
         for (int s = 0; s < lv->c.streams(); ++s)
-            if (lv->g.form != 0 && lv->c.fed[s] > 0)
+            if (lv->ss.g.form != 0 && lv->c.fed[s] > 0)
                 return fail(e, EMSPEC_ERR_STATE, "the history needs every column of a stream since its start: a session has frames fed; call emspec_reset() first");
     if (columns != e->history_W) {   // (a ring of another W: the next call of each session allocates its own)
         HIPCHK(e, hipSetDevice(e->device));
@@ -135,7 +135,7 @@ int emspec_set_live_history(emspec_engine* e, int64_t columns) {
 int64_t emspec_live_history(const emspec_engine* e, int32_t session, int32_t stream, int64_t* first_column) {
     if (!e || e->history_W <= 0) return -1;
     const LiveState* lv = session_of(const_cast<emspec_engine*>(e), session);
-    if (!lv || lv->g.form == 0 || stream < 0 || stream >= lv->g.S) return -1;
+    if (!lv || lv->ss.g.form == 0 || stream < 0 || stream >= lv->ss.g.S) return -1;
     const int64_t end = lv->c.emitted[stream];
     if (first_column) *first_column = history_first(end, e->history_W);
     return end;

@@ -14,8 +14,9 @@
 // No reference file:line exists (the reference source is private, README.md:73); SURVEY.md §8(f) row 4 is the streaming glue.
 // Device side: live.hip.inc / live_launch.hip.inc.
 // This file holds the HIP side only: allocations, copies, launches, synchronisations, the ABI's checks and messages.  What a
-// session's buffers measure and which column a call's output slot holds - the geometry, the per-stream counters, the
-// descriptors of every launch - is emspec_live_plan.h, plain integer code that tests/test_live_plan_cpu.py runs on the CPU.
+// session's buffers measure, which call fits the open session, which kernels a launch runs and which column a call's output slot
+// holds - the geometry (a list of bands for every kind of session), the per-stream counters, the descriptors and the steps of
+// every launch - is emspec_live_plan.h, plain integer code that tests/test_live_plan_cpu.py runs on the CPU.
 #include "emspec_engine.h"
 #ifdef EMSPEC_DIAG
 #pragma GCC visibility push(default)
@@ -50,66 +51,41 @@ void* device_view(const void* p) {
 
 // drops the session; the buffers and their capacities stay
 void live_forget(LiveState& lv) {
-    lv.g = LiveGeometry{};
+    lv.ss = LiveSession{};
     lv.c = LiveCounters{};
     lv.pcm = LivePcm{};
-    lv.mb = LiveBandGeometry{};
 }
 
-// first call of a session: every allocation, then the state.  n_high != 0: a multi-resolution session (n = n_low; rows below
-// `split` from n, the rest from n_high).
+// first call of a session: every allocation, then the state.  One column ring and one set of arrival counters per band.
 // pcm: a PCM session - its staging block holds raw frames (live_open_pcm), not floats.
-// bp != null: a multi-band session (n = bp->n[0], n_high = 0): K rings and K sets of arrival counters, everything else that of
-// the single-resolution session at n[0].
-int live_open(emspec_engine* e, LiveState& lv, int S, int n, int hop, int reassign, int form, int n_high = 0, int split = 0,
-              bool pcm = false, const BandPlan* bp = nullptr) {
-    const LiveBandGeometry mb = bp ? live_band_geometry(S, *bp, hop, reassign, form) : LiveBandGeometry{};
-    const LiveGeometry g = bp ? mb.g : live_geometry(S, n, hop, reassign, form, n_high, split);
-    const int R = e->cfg.rows;
+int live_open(emspec_engine* e, LiveState& lv, const LiveAsk& ask, bool pcm = false) {
+    const LiveSession ss = live_session(ask);
+    const LiveGeometry& g = ss.g;
     const size_t cell = e->exact() ? 8 : 4;
-    // the rings: band 0's, then those of the bands behind it (a multi-resolution session: the short band's)
-    const int K = bp ? mb.bands : n_high ? 2 : 1;
-    size_t ring[kMaxBands] = {g.rings_bytes(R, cell), g.rings_high_bytes(R, cell)};
-    for (int k = 0; bp && k < K; ++k) ring[k] = mb.rings_bytes(k, cell);
-    const size_t done = bp ? mb.done_bytes() : g.done_bytes();
     int rc;
-    if ((rc = grow(e, &lv.d_cells, &lv.cells_bytes, ring[0]))) return rc;
-    for (int k = 1; k < K; ++k)
-        if ((rc = grow(e, &lv.d_cells_band[k - 1], &lv.cells_band_bytes[k - 1], ring[k]))) return rc;
-    if (form == 2 && (rc = grow(e, (void**)&lv.d_sring, &lv.sring_bytes, g.sring_bytes()))) return rc;
-    if ((rc = grow(e, (void**)&lv.d_done, &lv.done_bytes, done))) return rc;
+    for (int k = 0; k < ss.bands; ++k)
+        if ((rc = grow(e, &lv.d_cells[k], &lv.cells_bytes[k], ss.rings_bytes(k, cell)))) return rc;
+    if (g.form == 2 && (rc = grow(e, (void**)&lv.d_sring, &lv.sring_bytes, g.sring_bytes()))) return rc;
+    if ((rc = grow(e, (void**)&lv.d_done, &lv.done_bytes, ss.done_bytes()))) return rc;
     if ((rc = pinned_grow(e, &lv.h_desc, &lv.desc_bytes, g.desc_bytes()))) return rc;
-    if (form == 2 && !pcm && (rc = pinned_grow(e, (void**)&lv.h_fresh, &lv.fresh_bytes, g.fresh_bytes()))) return rc;
-    HIPCHK(e, hipMemsetAsync(lv.d_cells, 0, ring[0], e->stream));
-    for (int k = 1; k < K; ++k) HIPCHK(e, hipMemsetAsync(lv.d_cells_band[k - 1], 0, ring[k], e->stream));
-    HIPCHK(e, hipMemsetAsync(lv.d_done, 0, done, e->stream));
+    if (g.form == 2 && !pcm && (rc = pinned_grow(e, (void**)&lv.h_fresh, &lv.fresh_bytes, g.fresh_bytes()))) return rc;
+    for (int k = 0; k < ss.bands; ++k) HIPCHK(e, hipMemsetAsync(lv.d_cells[k], 0, ss.rings_bytes(k, cell), e->stream));
+    HIPCHK(e, hipMemsetAsync(lv.d_done, 0, ss.done_bytes(), e->stream));
     if (lv.d_pstate) HIPCHK(e, hipMemsetAsync(lv.d_pstate, 0, lv.pstate_bytes, e->stream));
-    lv.g = g;
-    lv.mb = mb;
-    lv.c.open(S);
+    lv.ss = ss;
+    lv.c.open(g.S);
     return EMSPEC_OK;
 }
 
-// (bp != null: a multi-band call - its shape and split rows were checked by the entry, n is bp->n[0] and n_high is 0)
-int live_check(emspec_engine* e, const LiveState& lv, int S, int n, int hop, int reassign, int rows, int form, int n_high = 0,
-               int split = 0, const BandPlan* bp = nullptr) {
-    const LiveGeometry& g = lv.g;
-    int rc = n_high ? multires_check(e, S, n, n_high, hop, split) : check_shape(e, n, hop);
+// (a multi-band call's shape and split rows were checked by its entry)
+int live_check(emspec_engine* e, const LiveState& lv, const LiveAsk& ask, int rows) {
+    const LiveGeometry& g = lv.ss.g;
+    const BandPlan& p = ask.p;
+    int rc = ask.kind == kLiveTwoBand ? multires_check(e, ask.S, p.n[0], p.n[1], ask.hop, p.hi[0]) : check_shape(e, p.n[0], ask.hop);
     if (rc) return rc;
     if (rows != e->cfg.rows) return fail(e, EMSPEC_ERR_INVALID_ARG, "rows does not match the engine configuration");
-    if (S < 1 || S > 65535) return fail(e, EMSPEC_ERR_INVALID_ARG, "streams must be in 1..65535");
-    if (g.form != 0 && (bp != nullptr) != (lv.mb.bands != 0))
-        return fail(e, EMSPEC_ERR_STATE, lv.mb.bands ? "the live session is a multi-band one (emspec_columns_multiband / emspec_push_samples_multiband); call emspec_reset() first"
-                                                     : "the live session is not a multi-band one; call emspec_reset() before a multi-band call");
-    if (g.form != 0 && bp && (S != g.S || hop != g.hop || reassign != g.reassign || form != g.form || !lv.mb.same_bands(*bp)))
-        return fail(e, EMSPEC_ERR_STATE, "streams / bands / fft sizes / split rows / hop / reassign / feeding mode changed mid-stream; call emspec_reset() first");
-    if (g.form != 0 && (n_high != 0) != (g.n_high != 0))
-        return fail(e, EMSPEC_ERR_STATE, g.n_high ? "the live session is a multi-resolution one (emspec_columns_multires / emspec_push_samples_multires); call emspec_reset() first"
-                                                  : "the live session is a single-resolution one; call emspec_reset() before a multi-resolution call");
-    if (g.form != 0 && (S != g.S || n != g.n || hop != g.hop || reassign != g.reassign || form != g.form || n_high != g.n_high ||
-                        split != g.split))
-        return fail(e, EMSPEC_ERR_STATE, n_high ? "streams / fft sizes / hop / split row / reassign / feeding mode changed mid-stream; call emspec_reset() first"
-                                                : "streams / fft size / hop / reassign / feeding mode changed mid-stream; call emspec_reset() first");
+    if (ask.S < 1 || ask.S > 65535) return fail(e, EMSPEC_ERR_INVALID_ARG, "streams must be in 1..65535");
+    if (const char* why = live_mismatch(lv.ss, ask)) return fail(e, EMSPEC_ERR_STATE, why);
     // Feeding a flushed stream again would emit its last columns a second time, holding only the new frames' energy.
     for (int s = 0; s < g.S; ++s)
         if (lv.c.flushed(s, g.D))
@@ -121,8 +97,8 @@ int live_check(emspec_engine* e, const LiveState& lv, int S, int n, int hop, int
 int live_post_buffers(emspec_engine* e, LiveState& lv) {
     const int R = e->cfg.rows;
     int rc;
-    if ((rc = grow(e, (void**)&lv.d_raw, &lv.raw_bytes, lv.g.out_bytes(R, lv.g.mmax)))) return rc;
-    const size_t want = lv.g.S * LiveGeometry::pstate_bytes(R);
+    if ((rc = grow(e, (void**)&lv.d_raw, &lv.raw_bytes, lv.ss.g.out_bytes(R, lv.ss.g.mmax)))) return rc;
+    const size_t want = lv.ss.g.S * LiveGeometry::pstate_bytes(R);
     if (lv.pstate_bytes < want) {
         if ((rc = grow(e, (void**)&lv.d_pstate, &lv.pstate_bytes, want))) return rc;
         HIPCHK(e, hipMemsetAsync(lv.d_pstate, 0, lv.pstate_bytes, e->stream));
@@ -144,7 +120,7 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
                 uint8_t* dst_rgba, int out_cols, int raw_cols, bool empty_col, emspec_peak* dst_peaks = nullptr,
                 emspec_wave* dst_wave = nullptr) {
     int rc;
-    const LiveGeometry& g = lv.g;
+    const LiveGeometry& g = lv.ss.g;
     const int R = e->cfg.rows;
     const bool post = e->smoothing > 0.0f || e->agc > 0.0f;
     if (post && (rc = live_post_buffers(e, lv))) return rc;
@@ -171,7 +147,6 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
     // every stream in the same state: the descriptor goes into the kernel arguments
     ls.uniform = live_uniform(lv.desc(), g.S) ? 1 : 0;
     ls.uni = lv.desc()[0];
-    const bool priming = live_priming(lv.desc(), g.S);   // multi-resolution session: the short band's first 2 shift + 1 frames
 #ifdef EMSPEC_DIAG
     ls.stamps = lv.stamps;
 #endif
@@ -190,107 +165,81 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
     }
     const DbMap m = db_map(e, g.n);
     const bool exact = e->exact();
-    // a multi-band session: its flush is one launch for all bands, and its bands defer their finalize together or not at all
-    // (emspec_live_band_plan.h: defers) - to one launch of live_finalize_bands_kernel behind the last band's frames
-    const LiveBandGeometry& mb = lv.mb;
-    const bool bands_defer = mb.bands && !flush && mb.defers(mlaunch, kInlineFinalize);
-    // One band: its frame launch (or, flush = true, the flush kernel) on rows [p.row0, p.row0 + p.rows) of the output column.
-    // A single-resolution session is one band of all rows; a multi-resolution one runs the long band, then the short band,
-    // each finalising its own rows of the same column in place (live.hip.inc: live_finalize_column).
-    // bl: the band's sinks; frames: the largest per-stream frame count of the band in this launch.
-    const auto band = [&](const Plan& p, const LiveSinks& bl, void* cells, int slots, int frames) -> int {
-        const DbMap bm = db_map(e, p.n);
-        const ExactPlanDev xpd = exact ? exact_plan_dev(e, p, g.hop, g.reassign) : ExactPlanDev{};
-        // (lo / inv_range / gate do not depend on the fft size: both bands index the palette as the batch's composition does)
-        const ExactDbMap xm = exact ? exact_db_map(e, p.n, xpd) : ExactDbMap{};
-        // many columns per stream: the frame kernel only scatters and a second kernel finalises them, one workgroup per column
-        // (inline they are one workgroup's serial round trips to the memory side, ~2 us per column)
-        // ... and so does a small transform: its workgroup has n / 16 (EXACT: n / 8) threads, and 1024 rows through 16 threads
-        // are 8 serial batches of round trips (emspec_column at N = 256: 32.6 us per call against 25.7 at N = 4096)
-        const bool defer = mb.bands ? bands_defer : !flush && (mlaunch > kInlineFinalize || p.n < 2048);
-        LiveSinks bs = bl;
+    const LiveSession& ss = lv.ss;
+    // band k's plan and - once a step needs them - its conversions (EXACT: xpd, xm; lo / inv_range / gate do not depend on the fft
+    // size: every band indexes the palette as the batch's composition does)
+    struct Band { Plan* p; DbMap bm; ExactPlanDev xpd; ExactDbMap xm; bool ready; } band[kMaxBands];
+    for (int k = 0; k < ss.bands; ++k) {
+        const LiveBand& b = ss.b[k];
+        // (one band: the engine's own plan at n - nothing new in the plan cache)
+        if ((rc = ss.bands == 1 ? get_plan(e, b.n, &band[k].p) : get_band_plan(e, b.n, b.lo, b.rows(), &band[k].p))) return rc;
+        band[k].ready = false;
+    }
+    const auto ready = [&](int k) -> const Band& {
+        Band& d = band[k];
+        if (d.ready) return d;
+        d.bm = db_map(e, ss.b[k].n);
+        d.xpd = exact ? exact_plan_dev(e, *d.p, g.hop, g.reassign) : ExactPlanDev{};
+        d.xm = exact ? exact_db_map(e, ss.b[k].n, d.xpd) : ExactDbMap{};
+        d.ready = true;
+        return d;
+    };
+    // band k's sinks: rows [lo, hi) of the output column, finalised in place (live.hip.inc: live_finalize_column) from the band's
+    // own ring with the band's own arrival counters
+    const auto sinks = [&](int k, bool defer) {
+        const LiveBand& b = ss.b[k];
+        LiveSinks bs = ls;
+        bs.row0 = b.lo;
+        bs.frame_shift = b.frame_shift;
+        bs.col_shift = b.shift;
+        bs.lat_extra = b.lat_extra;
+        bs.no_ingest = k ? 1 : 0;
+        bs.done = lv.d_done + (size_t)k * g.S;
         bs.defer_finalize = defer ? 1 : 0;
-        if (flush) {
-            HIPCHK(e, launch_live_flush(exact, bs, cells, slots, p.rows, g.D, bm, xm, g.S, 1, e->stream));
+        return bs;
+    };
+#ifdef EMSPEC_DIAG
+    // A/B aid (tools/live_multiband_rate.py): a multi-band session's finalize as K launches, one live_finalize_kernel per band
+    static const bool per_band = [] { const char* ev = getenv("EMSPEC_LIVE_FINALIZE_PER_BAND"); return ev && ev[0] == '1'; }();
+#else
+    constexpr bool per_band = false;
+#endif
+    // the launches, in the order and with the sizes emspec_live_plan.h lists (live_steps: the rule, run on the CPU by the tests)
+    const LiveSteps steps = live_steps(ss, mlaunch, flush, live_priming(lv.desc(), g.S), kInlineFinalize, per_band);
+    for (int i = 0; i < steps.count; ++i) {
+        const LiveStep& st = steps.step[i];
+        if (st.what == kStepFinalizeBands) {
+            LiveBandRings fin;
+            fin.bands = ss.bands;
+            for (int k = 0; k < ss.bands; ++k) {
+                const Band& d = ready(k);
+                fin.cells[k] = lv.d_cells[k];
+                fin.slots[k] = ss.b[k].slots; fin.rows[k] = ss.b[k].rows(); fin.row0[k] = ss.b[k].lo;
+                fin.m[k] = d.bm;
+                fin.xm[k] = d.xm;
+            }
+            HIPCHK(e, launch_live_finalize_bands(exact, ls, fin, g.D, g.S, st.ncol, e->stream));
+            continue;
+        }
+        const Band& d = ready(st.band);
+        const LiveBand& b = ss.b[st.band];
+        void* cells = lv.d_cells[st.band];
+        if (st.what == kStepFinalize) {
+            HIPCHK(e, launch_live_flush(exact, sinks(st.band, false), cells, b.slots, b.rows(), g.D, d.bm, d.xm, g.S, st.ncol, e->stream));
         } else if (exact) {
             ExactSinks xs;
             xs.hist = reinterpret_cast<unsigned long long*>(cells);
-            xs.hist_slots = slots; xs.total_cols = INT64_MAX; xs.ring = 1;
-            xs.live = bs;
-            xs.fin_map = xm;
-            HIPCHK(e, launch_exact_frames(p.n, xpd, nullptr, 0, g.S, 0, (int64_t)frames + 1, xs, e->stream));
+            xs.hist_slots = b.slots; xs.total_cols = INT64_MAX; xs.ring = 1;
+            xs.live = sinks(st.band, st.defer);
+            xs.fin_map = d.xm;
+            HIPCHK(e, launch_exact_frames(b.n, d.xpd, nullptr, 0, g.S, 0, (int64_t)st.groups + 1, xs, e->stream));
         } else {
             FrameSinks sk;
             sk.hist = reinterpret_cast<float*>(cells);
-            sk.hist_slots = slots; sk.total_cols = INT64_MAX; sk.ring = 1;
-            sk.live = bs;
-            sk.fin_map = bm;
-            HIPCHK(e, launch_frames(p.n, plan_dev(e, p, g.hop, g.reassign), nullptr, 0, g.S, 0, (int64_t)frames + 1, sk, e->stream));
-        }
-        // (the columns a launch completes are the long band's frame count for either band)
-        if (defer && !mb.bands) HIPCHK(e, launch_live_flush(exact, bs, cells, slots, p.rows, g.D, bm, xm, g.S, mlaunch, e->stream));
-        return EMSPEC_OK;
-    };
-    Plan* p;
-    if (mb.bands) {
-        Plan* pb[kMaxBands];
-        LiveBandRings fin;
-        fin.bands = mb.bands;
-        for (int k = 0; k < mb.bands; ++k) {
-            const LiveBand& b = mb.b[k];
-            if ((rc = get_band_plan(e, b.n, b.lo, b.rows(), &pb[k]))) return rc;
-            fin.cells[k] = k ? lv.d_cells_band[k - 1] : lv.d_cells;
-            fin.slots[k] = b.slots; fin.rows[k] = b.rows(); fin.row0[k] = b.lo;
-            if (!(flush || bands_defer)) continue;   // (the conversions are the bands kernel's alone)
-            fin.m[k] = db_map(e, b.n);
-            if (exact) fin.xm[k] = exact_db_map(e, b.n, exact_plan_dev(e, *pb[k], g.hop, g.reassign));
-        }
-        // band 0's frame launch carries the ingest workgroup; the others follow without one, and not at all when no stream has
-        // a frame
-        for (int k = 0; !flush && k < mb.bands && (k == 0 || mlaunch > 0); ++k) {
-            const LiveBand& b = mb.b[k];
-            LiveSinks bs = ls;
-            bs.row0 = b.lo;
-            bs.frame_shift = b.frame_shift;
-            bs.col_shift = b.shift;
-            bs.lat_extra = b.lat_extra;
-            bs.no_ingest = k ? 1 : 0;
-            bs.done = lv.d_done + (size_t)k * g.S;
-            if ((rc = band(*pb[k], bs, fin.cells[k], b.slots, mb.launch_frames(k, mlaunch, priming)))) return rc;
-        }
-        if (flush || bands_defer) {
-            const int ncol = flush ? 1 : mlaunch;
-#ifdef EMSPEC_DIAG
-            // A/B aid (tools/live_multiband_rate.py): the K-launch form, one live_finalize_kernel per band
-            static const bool per_band = [] { const char* ev = getenv("EMSPEC_LIVE_FINALIZE_PER_BAND"); return ev && ev[0] == '1'; }();
-            for (int k = 0; per_band && k < mb.bands; ++k) {
-                LiveSinks bs = ls;
-                bs.row0 = fin.row0[k];
-                HIPCHK(e, launch_live_flush(exact, bs, fin.cells[k], fin.slots[k], fin.rows[k], g.D, fin.m[k], fin.xm[k], g.S, ncol, e->stream));
-            }
-            if (per_band) fin.bands = 0;   // (the launcher does nothing without bands)
-#endif
-            HIPCHK(e, launch_live_finalize_bands(exact, ls, fin, g.D, g.S, ncol, e->stream));
-        }
-    } else if (!g.n_high) {
-        if ((rc = get_plan(e, g.n, &p))) return rc;
-        if ((rc = band(*p, ls, lv.d_cells, g.slots, mlaunch))) return rc;
-    } else {
-        Plan* ph;
-        if ((rc = get_band_plan(e, g.n, 0, g.split, &p))) return rc;
-        if ((rc = get_band_plan(e, g.n_high, g.split, R - g.split, &ph))) return rc;
-        if ((rc = band(*p, ls, lv.d_cells, g.slots, mlaunch))) return rc;
-        // the short band: no launch when no stream has a frame (a block that only fills the sample ring: the long band's
-        // ingest workgroup did that)
-        if (flush || mlaunch > 0) {
-            LiveSinks hs = ls;
-            hs.row0 = g.split;
-            hs.frame_shift = 2 * g.shift;
-            hs.col_shift = g.shift;
-            hs.lat_extra = g.D - g.D_high;
-            hs.no_ingest = 1;
-            hs.done = lv.d_done + g.S;
-            if ((rc = band(*ph, hs, lv.d_cells_band[0], g.slots_high, mlaunch + (priming ? 2 * g.shift : 0)))) return rc;
+            sk.hist_slots = b.slots; sk.total_cols = INT64_MAX; sk.ring = 1;
+            sk.live = sinks(st.band, st.defer);
+            sk.fin_map = d.bm;
+            HIPCHK(e, launch_frames(b.n, plan_dev(e, *d.p, g.hop, g.reassign), nullptr, 0, g.S, 0, (int64_t)st.groups + 1, sk, e->stream));
         }
     }
     if (post) {
@@ -385,10 +334,10 @@ int live_dest(emspec_engine* e, LiveState& lv, float* out_db, uint8_t* out_rgba,
         d.stage_db = out_db != nullptr; d.stage_rgba = out_rgba != nullptr; d.db = nullptr; d.rgba = nullptr;
         d.stage_peaks = e->live_peaks != nullptr; d.stage_wave = e->live_wave != nullptr;
     }
-    const size_t bytes = lv.g.out_bytes(e->cfg.rows, cols);
+    const size_t bytes = lv.ss.g.out_bytes(e->cfg.rows, cols);
     int rc;
-    if (d.stage_peaks && (rc = pinned_grow(e, &lv.h_opeaks, &lv.opeaks_bytes, live_peaks_bytes(lv.g, cols, e->live_peaks_k)))) return rc;
-    if (d.stage_wave && (rc = pinned_grow(e, &lv.h_owave, &lv.owave_bytes, live_wave_bytes(lv.g, cols)))) return rc;
+    if (d.stage_peaks && (rc = pinned_grow(e, &lv.h_opeaks, &lv.opeaks_bytes, live_peaks_bytes(lv.ss.g, cols, e->live_peaks_k)))) return rc;
+    if (d.stage_wave && (rc = pinned_grow(e, &lv.h_owave, &lv.owave_bytes, live_wave_bytes(lv.ss.g, cols)))) return rc;
     if (d.stage_peaks) d.peaks = reinterpret_cast<emspec_peak*>(lv.h_opeaks);
     if (d.stage_wave) d.wave = reinterpret_cast<emspec_wave*>(lv.h_owave);
     if (d.stage_db && (rc = pinned_grow(e, (void**)&lv.h_odb, &lv.odb_bytes, bytes))) return rc;
@@ -405,18 +354,18 @@ void live_copy_back(const emspec_engine* e, const LiveState& lv, const LiveDest&
                     const LivePush* p = nullptr, int64_t max_columns = 1) {
     const int k = e->live_peaks_k;
     if (!p) {
-        if (d.stage_db) std::memcpy(out_db, lv.h_odb, lv.g.out_bytes(R, 1));
-        if (d.stage_rgba) std::memcpy(out_rgba, lv.h_orgba, lv.g.out_bytes(R, 1));
-        if (d.stage_peaks) std::memcpy(e->live_peaks, lv.h_opeaks, live_peaks_bytes(lv.g, 1, k));
-        if (d.stage_wave) std::memcpy(e->live_wave, lv.h_owave, live_wave_bytes(lv.g, 1));
+        if (d.stage_db) std::memcpy(out_db, lv.h_odb, lv.ss.g.out_bytes(R, 1));
+        if (d.stage_rgba) std::memcpy(out_rgba, lv.h_orgba, lv.ss.g.out_bytes(R, 1));
+        if (d.stage_peaks) std::memcpy(e->live_peaks, lv.h_opeaks, live_peaks_bytes(lv.ss.g, 1, k));
+        if (d.stage_wave) std::memcpy(e->live_wave, lv.h_owave, live_wave_bytes(lv.ss.g, 1));
         return;
     }
-    for (int s = 0; s < lv.g.S; ++s) {
+    for (int s = 0; s < lv.ss.g.S; ++s) {
         if (p->nc[s] <= 0) continue;
-        const size_t from = LiveGeometry::out_cell(R, lv.g.mmax, s, 0), to = LiveGeometry::out_cell(R, max_columns, s, p->produced[s]);
+        const size_t from = LiveGeometry::out_cell(R, lv.ss.g.mmax, s, 0), to = LiveGeometry::out_cell(R, max_columns, s, p->produced[s]);
         if (d.stage_db) std::memcpy(out_db + to, lv.h_odb + from, LiveGeometry::columns_bytes(R, p->nc[s]));
         if (d.stage_rgba) std::memcpy(out_rgba + to * 4, lv.h_orgba + from * 4, LiveGeometry::columns_bytes(R, p->nc[s]));
-        const int64_t pfrom = live_overlay_pair(lv.g.mmax, s, 0), pto = live_overlay_pair(max_columns, s, p->produced[s]);
+        const int64_t pfrom = live_overlay_pair(lv.ss.g.mmax, s, 0), pto = live_overlay_pair(max_columns, s, p->produced[s]);
         if (d.stage_peaks)
             std::memcpy(e->live_peaks + pto * k, reinterpret_cast<const emspec_peak*>(lv.h_opeaks) + pfrom * k, (size_t)p->nc[s] * k * sizeof(emspec_peak));
         if (d.stage_wave)
@@ -435,16 +384,16 @@ bool pcm_same_format(const emspec_pcm_format& a, const emspec_pcm_format& b) {
 // (behind live_open: the session's streams are sources * views)
 int live_open_pcm(emspec_engine* e, LiveState& lv, const emspec_pcm_format& fmt) {
     int rc;
-    if ((rc = pinned_grow(e, (void**)&lv.h_raw, &lv.hraw_bytes, lv.g.raw_bytes(fmt.views, pcm_frame_bytes(fmt))))) return rc;
-    if ((rc = grow(e, (void**)&lv.d_fresh, &lv.dfresh_bytes, lv.g.decoded_bytes()))) return rc;
+    if ((rc = pinned_grow(e, (void**)&lv.h_raw, &lv.hraw_bytes, lv.ss.g.raw_bytes(fmt.views, pcm_frame_bytes(fmt))))) return rc;
+    if ((rc = grow(e, (void**)&lv.d_fresh, &lv.dfresh_bytes, lv.ss.g.decoded_bytes()))) return rc;
     lv.pcm = LivePcm{fmt.views, fmt};
     return EMSPEC_OK;
 }
 
 // the staged raw frames (pend of them per source) -> d_fresh, on the engine's stream in front of the frame launch
 int live_decode_pending(emspec_engine* e, LiveState& lv) {
-    HIPCHK(e, pcm_decode(lv.h_raw, lv.pcm.fmt, lv.g.S / lv.pcm.views, lv.c.pcm_staged(), lv.g.raw_stride(pcm_frame_bytes(lv.pcm.fmt)),
-                         lv.d_fresh, lv.g.cap, e->stream));
+    HIPCHK(e, pcm_decode(lv.h_raw, lv.pcm.fmt, lv.ss.g.S / lv.pcm.views, lv.c.pcm_staged(), lv.ss.g.raw_stride(pcm_frame_bytes(lv.pcm.fmt)),
+                         lv.d_fresh, lv.ss.g.cap, e->stream));
     return EMSPEC_OK;
 }
 
@@ -454,11 +403,11 @@ int live_decode_pending(emspec_engine* e, LiveState& lv) {
 int live_pcm_drain(emspec_engine* e, LiveState& lv) {
     if (!lv.pcm.views || lv.c.pcm_staged() == 0) return EMSPEC_OK;
     int rc;
-    live_drain_fill(lv.g, lv.c, lv.desc());
+    live_drain_fill(lv.ss.g, lv.c, lv.desc());
     if ((rc = live_decode_pending(e, lv))) return live_abandon(e, lv, rc);
-    if ((rc = live_launch(e, lv, lv.d_fresh, lv.g.cap, 0, false, nullptr, nullptr, 1, 1, false))) return live_abandon(e, lv, rc);
+    if ((rc = live_launch(e, lv, lv.d_fresh, lv.ss.g.cap, 0, false, nullptr, nullptr, 1, 1, false))) return live_abandon(e, lv, rc);
     if ((rc = live_sync(e, lv))) return rc;
-    live_drain_commit(lv.g, lv.c);
+    live_drain_commit(lv.ss.g, lv.c);
     return EMSPEC_OK;
 }
 
@@ -476,37 +425,34 @@ int live_overlay_check(emspec_engine* e, int S, int64_t cols) {
 // the time reduction (emspec_set_time_reduce) serves the batch entries only: every streaming call refuses while it is on
 const char* const kNoLiveReduce = "the streaming calls return full-rate columns: not available while a time reduction is set (emspec_set_time_reduce(e, 1) turns it off)";
 
-// (n_high != 0: the multi-resolution form - n is n_low, the frames are n_low samples long and the short band reads the newest
-// n_high of them; on a stream's first frame it reads all of it, frames 0 .. 2 shift.  bp != null: the multi-band form, n = n[0],
-// every shorter band as that short band)
-int columns_impl(emspec_engine* e, LiveState& lv, const float* frames, int32_t streams, int32_t n, int32_t hop, int32_t reassign,
-                 float* out_db, uint8_t* out_rgba, int32_t rows, int64_t* out_columns, int32_t n_high = 0, int32_t split = 0,
-                 const BandPlan* bp = nullptr) {
+// (ask: the session the entry's arguments describe, form 1.  The frames are n[0] samples long; a band behind the first reads the
+// newest n[k] of them - on a stream's first frame all of it, frames 0 .. 2 shift)
+int columns_impl(emspec_engine* e, LiveState& lv, const float* frames, const LiveAsk& ask, float* out_db, uint8_t* out_rgba,
+                 int32_t rows, int64_t* out_columns) {
     if (e && e->time_reduce > 1) return fail(e, EMSPEC_ERR_STATE, kNoLiveReduce);
     if (!e || !frames) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument");
-    reassign = reassign ? 1 : 0;
-    int rc = live_check(e, lv, streams, n, hop, reassign, rows, 1, n_high, split, bp);
+    int rc = live_check(e, lv, ask, rows);
     if (rc) return rc;
-    if ((rc = live_overlay_check(e, streams, 1))) return rc;
+    if ((rc = live_overlay_check(e, ask.S, 1))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
-    const bool opened = lv.g.form == 0;
-    if (opened && (rc = live_open(e, lv, streams, n, hop, reassign, 1, n_high, split, false, bp))) return rc;
+    const bool opened = lv.ss.g.form == 0;
+    if (opened && (rc = live_open(e, lv, ask))) return rc;
     if ((rc = history_ready(e, lv))) { if (opened) live_forget(lv); return rc; }
     if ((rc = audio_ready(e, lv))) { if (opened) live_forget(lv); return rc; }
     // the frames: read by the kernel where they are when the caller's block is page-locked, else staged
     const float* src = reinterpret_cast<const float*>(device_view(frames));
     if (!src) {
-        if ((rc = pinned_grow(e, (void**)&lv.h_fresh, &lv.fresh_bytes, lv.g.fresh_bytes()))) return rc;
-        std::memcpy(lv.h_fresh, frames, lv.g.fresh_bytes());
+        if ((rc = pinned_grow(e, (void**)&lv.h_fresh, &lv.fresh_bytes, lv.ss.g.fresh_bytes()))) return rc;
+        std::memcpy(lv.h_fresh, frames, lv.ss.g.fresh_bytes());
         src = lv.h_fresh;
     }
     LiveDest d;   // (one column per stream: each output in place or staged on its own)
     if ((rc = live_dest(e, lv, out_db, out_rgba, 1, d))) return rc;
-    live_frame_fill(lv.g, lv.c, lv.desc());
-    if ((rc = live_launch(e, lv, src, n, 1, false, d.db, d.rgba, 1, 1, true, d.peaks, d.wave))) return live_abandon(e, lv, rc);
+    live_frame_fill(lv.ss.g, lv.c, lv.desc());
+    if ((rc = live_launch(e, lv, src, lv.ss.g.n, 1, false, d.db, d.rgba, 1, 1, true, d.peaks, d.wave))) return live_abandon(e, lv, rc);
     if ((rc = live_sync(e, lv))) return rc;
     live_copy_back(e, lv, d, out_db, out_rgba, e->cfg.rows);
-    live_frame_commit(lv.g, lv.c, out_columns);
+    live_frame_commit(lv.ss.g, lv.c, out_columns);
     return EMSPEC_OK;
 }
 
@@ -514,63 +460,61 @@ int flush_impl(emspec_engine* e, LiveState& lv, float* out_db, uint8_t* out_rgba
     if (!e) return EMSPEC_ERR_INVALID_ARG;
     if (e->time_reduce > 1) return fail(e, EMSPEC_ERR_STATE, kNoLiveReduce);
     if (rows != e->cfg.rows) return fail(e, EMSPEC_ERR_INVALID_ARG, "rows does not match the engine configuration");
-    if (lv.g.form == 0 || !lv.c.any_pending()) return fail(e, EMSPEC_ERR_STATE, "no pending column");
+    if (lv.ss.g.form == 0 || !lv.c.any_pending()) return fail(e, EMSPEC_ERR_STATE, "no pending column");
     int rc;
-    if ((rc = live_overlay_check(e, lv.g.S, 1))) return rc;
+    if ((rc = live_overlay_check(e, lv.ss.g.S, 1))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     if ((rc = history_ready(e, lv))) return rc;
     LiveDest d;   // (as emspec_columns; the staging blocks are sized for a push's mmax columns at once)
-    if ((rc = live_dest(e, lv, out_db, out_rgba, lv.g.mmax, d))) return rc;
-    live_flush_fill(lv.g, lv.c, lv.desc());
+    if ((rc = live_dest(e, lv, out_db, out_rgba, lv.ss.g.mmax, d))) return rc;
+    live_flush_fill(lv.ss.g, lv.c, lv.desc());
     if ((rc = live_launch(e, lv, nullptr, 0, 0, true, d.db, d.rgba, 1, 1, true, d.peaks, d.wave))) return live_abandon(e, lv, rc);
     if ((rc = live_sync(e, lv))) return rc;
     live_copy_back(e, lv, d, out_db, out_rgba, e->cfg.rows);
-    live_flush_commit(lv.g, lv.c, out_columns);
+    live_flush_commit(lv.ss.g, lv.c, out_columns);
     return EMSPEC_OK;
 }
 
 int64_t push_columns_impl(const emspec_engine* e, const LiveState& lv, int64_t count, int32_t n, int32_t hop, int32_t reassign) {
     if (!e || count < 0 || !supported_fft(n) || hop < 1 || hop > n) return -1;
-    return live_push_columns(lv.g, lv.c, count, n, hop, reassign);
+    return live_push_columns(lv.ss.g, lv.c, count, n, hop, reassign);
 }
 
-// (n_high != 0, or bp != null: the multi-resolution / multi-band form - n is n_low / n[0]; max_columns then bounds what the block may complete whether or not an
-// output is given: it is the stride of every block the launch writes)
+// (ask: the session the entry's arguments describe, form 2.  With more than one band max_columns bounds what the block may
+// complete whether or not an output is given: it is the stride of every block the launch writes)
 // (fmt != null: the PCM form - `block` holds raw interleaved frames, `count` of them per source, source i at block + i * stride
-// BYTES, and streams = sources * fmt->views; as for the multi-resolution form, max_columns always bounds what a block completes)
-int push_impl(emspec_engine* e, LiveState& lv, const void* block, int32_t streams, int64_t count, int64_t stride, int32_t n,
-              int32_t hop, int32_t reassign, float* out_db, uint8_t* out_rgba, int32_t rows, int64_t max_columns,
-              int64_t* out_counts, int64_t* out_first_columns, int32_t n_high = 0, int32_t split = 0,
-              const emspec_pcm_format* fmt = nullptr, const BandPlan* bp = nullptr) {
+// BYTES, and ask.S = sources * fmt->views; as with several bands, max_columns always bounds what a block completes)
+int push_impl(emspec_engine* e, LiveState& lv, const void* block, const LiveAsk& ask, int64_t count, int64_t stride, float* out_db,
+              uint8_t* out_rgba, int32_t rows, int64_t max_columns, int64_t* out_counts, int64_t* out_first_columns,
+              const emspec_pcm_format* fmt = nullptr) {
     if (e && e->time_reduce > 1) return fail(e, EMSPEC_ERR_STATE, kNoLiveReduce);
     const float* samples = static_cast<const float*>(block);
     const int fb = fmt ? pcm_frame_bytes(*fmt) : 1;   // (the float form's stride counts samples)
     if (!e || (!block && count > 0) || count < 0 || stride / fb < count) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument, negative count or stride < count");
-    reassign = reassign ? 1 : 0;
-    int rc = live_check(e, lv, streams, n, hop, reassign, rows, 2, n_high, split, bp);
+    int rc = live_check(e, lv, ask, rows);
     if (rc) return rc;
-    if (lv.g.form != 0 && (fmt != nullptr) != (lv.pcm.views != 0))
+    if (lv.ss.g.form != 0 && (fmt != nullptr) != (lv.pcm.views != 0))
         return fail(e, EMSPEC_ERR_STATE, lv.pcm.views ? "the live session is a PCM one (emspec_push_samples_pcm); call emspec_reset() before a float call"
                                                       : "the live session is a float one; call emspec_reset() before a PCM call");
-    if (lv.g.form != 0 && fmt && !pcm_same_format(*fmt, lv.pcm.fmt))
+    if (lv.ss.g.form != 0 && fmt && !pcm_same_format(*fmt, lv.pcm.fmt))
         return fail(e, EMSPEC_ERR_STATE, "the PCM format changed mid-stream; call emspec_reset() first");
     if (max_columns < 0) return fail(e, EMSPEC_ERR_INVALID_ARG, "max_columns must be >= 0");
-    const int64_t expect = push_columns_impl(e, lv, count, n, hop, reassign);
+    const int64_t expect = push_columns_impl(e, lv, count, ask.p.n[0], ask.hop, ask.reassign);
     // (an overlay is an output too: its slots are the columns of [S][max_columns]; so is the history, whose columns pass
     // through a device block of that layout)
-    if ((out_db || out_rgba || n_high || bp || fmt || e->live_peaks || e->live_wave || e->history_W > 0) && expect > max_columns)
+    if ((out_db || out_rgba || ask.p.bands > 1 || fmt || e->live_peaks || e->live_wave || e->history_W > 0) && expect > max_columns)
         return fail(e, EMSPEC_ERR_INVALID_ARG, "output holds fewer columns than this block completes (" + std::to_string(expect) +
                                                    "); size it with emspec_push_columns() / emspec_push_columns_multi()");
-    if ((rc = live_overlay_check(e, streams, max_columns))) return rc;
+    if ((rc = live_overlay_check(e, ask.S, max_columns))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
-    const bool opened = lv.g.form == 0;
+    const bool opened = lv.ss.g.form == 0;
     if (opened) {
-        if ((rc = live_open(e, lv, streams, n, hop, reassign, 2, n_high, split, fmt != nullptr, bp))) return rc;
+        if ((rc = live_open(e, lv, ask, fmt != nullptr))) return rc;
         if (fmt && (rc = live_open_pcm(e, lv, *fmt))) { live_forget(lv); return rc; }
     }
     if ((rc = history_ready(e, lv))) { if (opened) live_forget(lv); return rc; }
     if ((rc = audio_ready(e, lv))) { if (opened) live_forget(lv); return rc; }
-    const LiveGeometry& g = lv.g;
+    const LiveGeometry& g = lv.ss.g;
     // Unlike the one-column calls, a push decides for both outputs together: page-locked outputs are written in place
     // ([S][max_columns][rows], every round at the columns produced so far) only when BOTH are page-locked and max_columns fits
     // the launch's int; otherwise both go through a staging block of mmax columns per launch.  The overlays' arrays count as
@@ -613,8 +557,8 @@ int push_impl(emspec_engine* e, LiveState& lv, const void* block, int32_t stream
 }
 
 void live_free(LiveState& lv) {
-    (void)hipFree(lv.d_cells); (void)hipFree(lv.d_sring);
-    for (void* ring : lv.d_cells_band) (void)hipFree(ring);
+    for (void* ring : lv.d_cells) (void)hipFree(ring);
+    (void)hipFree(lv.d_sring);
     (void)hipFree(lv.d_done); (void)hipFree(lv.d_raw); (void)hipFree(lv.d_pstate);
     if (lv.h_desc) (void)hipHostFree(lv.h_desc);
     if (lv.h_fresh) (void)hipHostFree(lv.h_fresh);
@@ -642,12 +586,12 @@ bool live_pending(const emspec_engine* e) {
 extern "C" {
 
 // ---- the live multi-stream session (e->live)
-int32_t emspec_live_streams(const emspec_engine* e) { return e ? e->live.g.S : 0; }
+int32_t emspec_live_streams(const emspec_engine* e) { return e ? e->live.ss.g.S : 0; }
 
 int emspec_columns(emspec_engine* e, const float* frames, int32_t streams, int32_t n, int32_t hop, int32_t reassign,
                    float* out_db, uint8_t* out_rgba, int32_t rows, int64_t* out_columns) {
     if (!e) return EMSPEC_ERR_INVALID_ARG;
-    return columns_impl(e, e->live, frames, streams, n, hop, reassign, out_db, out_rgba, rows, out_columns);
+    return columns_impl(e, e->live, frames, live_ask_single(streams, n, hop, reassign, 1, e->cfg.rows), out_db, out_rgba, rows, out_columns);
 }
 
 int emspec_columns_flush(emspec_engine* e, float* out_db, uint8_t* out_rgba, int32_t rows, int64_t* out_columns) {
@@ -663,8 +607,8 @@ int emspec_push_samples_multi(emspec_engine* e, const float* samples, int32_t st
                               int32_t n, int32_t hop, int32_t reassign, float* out_db, uint8_t* out_rgba, int32_t rows,
                               int64_t max_columns, int64_t* out_counts, int64_t* out_first_columns) {
     if (!e) return EMSPEC_ERR_INVALID_ARG;
-    return push_impl(e, e->live, samples, streams, count, stride, n, hop, reassign, out_db, out_rgba, rows, max_columns, out_counts,
-                     out_first_columns);
+    return push_impl(e, e->live, samples, live_ask_single(streams, n, hop, reassign, 2, e->cfg.rows), count, stride, out_db, out_rgba, rows,
+                     max_columns, out_counts, out_first_columns);
 }
 
 // ---- the live session's multi-resolution form: rows below split_row from n_low, the rest from n_high, one
@@ -675,7 +619,8 @@ int emspec_columns_multires(emspec_engine* e, const float* frames, int32_t strea
     if (!e) return EMSPEC_ERR_INVALID_ARG;
     // (a shape the batch rejects is rejected with the same words, before n_high = 0 could pass for "single resolution")
     if (const char* why = multires_shape_error(n_low, n_high, hop)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
-    return columns_impl(e, e->live, frames, streams, n_low, hop, reassign, out_db, out_rgba, rows, out_columns, n_high, split_row);
+    return columns_impl(e, e->live, frames, live_ask_two_band(streams, n_low, n_high, hop, split_row, reassign, 1, e->cfg.rows), out_db, out_rgba,
+                        rows, out_columns);
 }
 
 int64_t emspec_push_columns_multires(const emspec_engine* e, int64_t count, int32_t n_low, int32_t n_high, int32_t hop,
@@ -690,8 +635,8 @@ int emspec_push_samples_multires(emspec_engine* e, const float* samples, int32_t
                                  int64_t* out_first_columns) {
     if (!e) return EMSPEC_ERR_INVALID_ARG;
     if (const char* why = multires_shape_error(n_low, n_high, hop)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
-    return push_impl(e, e->live, samples, streams, count, stride, n_low, hop, reassign, out_db, out_rgba, rows, max_columns,
-                     out_counts, out_first_columns, n_high, split_row);
+    return push_impl(e, e->live, samples, live_ask_two_band(streams, n_low, n_high, hop, split_row, reassign, 2, e->cfg.rows), count, stride,
+                     out_db, out_rgba, rows, max_columns, out_counts, out_first_columns);
 }
 
 // ---- the live session's multi-band form: 2..4 bands of the row table, band k from n[k], one column per hop with
@@ -710,7 +655,7 @@ int emspec_columns_multiband(emspec_engine* e, const float* frames, int32_t stre
                              int64_t* out_columns) {
     if (int rc = multiband_entry_check(e, bands, n, split_rows, hop)) return rc;
     const BandPlan bp = band_plan(bands, n, split_rows, hop, e->cfg.rows);
-    return columns_impl(e, e->live, frames, streams, n[0], hop, reassign, out_db, out_rgba, rows, out_columns, 0, 0, &bp);
+    return columns_impl(e, e->live, frames, live_ask_bands(streams, bp, hop, reassign, 1), out_db, out_rgba, rows, out_columns);
 }
 
 int64_t emspec_push_columns_multiband(const emspec_engine* e, int64_t count, int32_t bands, const int32_t* n, int32_t hop,
@@ -725,8 +670,8 @@ int emspec_push_samples_multiband(emspec_engine* e, const float* samples, int32_
                                   int64_t* out_first_columns) {
     if (int rc = multiband_entry_check(e, bands, n, split_rows, hop)) return rc;
     const BandPlan bp = band_plan(bands, n, split_rows, hop, e->cfg.rows);
-    return push_impl(e, e->live, samples, streams, count, stride, n[0], hop, reassign, out_db, out_rgba, rows, max_columns, out_counts,
-                     out_first_columns, 0, 0, nullptr, &bp);
+    return push_impl(e, e->live, samples, live_ask_bands(streams, bp, hop, reassign, 2), count, stride, out_db, out_rgba, rows, max_columns,
+                     out_counts, out_first_columns);
 }
 
 // ---- the live session fed raw interleaved frames (include/emspec.h, PCM front end): sources * views streams
@@ -741,8 +686,8 @@ int emspec_push_samples_pcm(emspec_engine* e, const void* block, const emspec_pc
                             int64_t stride_bytes, int32_t n, int32_t hop, int32_t reassign, float* out_db, uint8_t* out_rgba,
                             int32_t rows, int64_t max_columns, int64_t* out_counts, int64_t* out_first_columns) {
     if (int rc = pcm_entry_check(e, fmt, sources)) return rc;
-    return push_impl(e, e->live, block, sources * fmt->views, count, stride_bytes, n, hop, reassign, out_db, out_rgba, rows, max_columns,
-                     out_counts, out_first_columns, 0, 0, fmt);
+    return push_impl(e, e->live, block, live_ask_single(sources * fmt->views, n, hop, reassign, 2, e->cfg.rows), count, stride_bytes, out_db,
+                     out_rgba, rows, max_columns, out_counts, out_first_columns, fmt);
 }
 
 int emspec_push_samples_pcm_multires(emspec_engine* e, const void* block, const emspec_pcm_format* fmt, int32_t sources,
@@ -751,8 +696,8 @@ int emspec_push_samples_pcm_multires(emspec_engine* e, const void* block, const 
                                      int64_t max_columns, int64_t* out_counts, int64_t* out_first_columns) {
     if (int rc = pcm_entry_check(e, fmt, sources)) return rc;
     if (const char* why = multires_shape_error(n_low, n_high, hop)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
-    return push_impl(e, e->live, block, sources * fmt->views, count, stride_bytes, n_low, hop, reassign, out_db, out_rgba, rows,
-                     max_columns, out_counts, out_first_columns, n_high, split_row, fmt);
+    return push_impl(e, e->live, block, live_ask_two_band(sources * fmt->views, n_low, n_high, hop, split_row, reassign, 2, e->cfg.rows), count,
+                     stride_bytes, out_db, out_rgba, rows, max_columns, out_counts, out_first_columns, fmt);
 }
 
 int emspec_push_samples_pcm_multiband(emspec_engine* e, const void* block, const emspec_pcm_format* fmt, int32_t sources,
@@ -762,8 +707,8 @@ int emspec_push_samples_pcm_multiband(emspec_engine* e, const void* block, const
     if (int rc = pcm_entry_check(e, fmt, sources)) return rc;
     if (int rc = multiband_entry_check(e, bands, n, split_rows, hop)) return rc;
     const BandPlan bp = band_plan(bands, n, split_rows, hop, e->cfg.rows);
-    return push_impl(e, e->live, block, sources * fmt->views, count, stride_bytes, n[0], hop, reassign, out_db, out_rgba, rows,
-                     max_columns, out_counts, out_first_columns, 0, 0, fmt, &bp);
+    return push_impl(e, e->live, block, live_ask_bands(sources * fmt->views, bp, hop, reassign, 2), count, stride_bytes, out_db, out_rgba, rows,
+                     max_columns, out_counts, out_first_columns, fmt);
 }
 
 // ---- the renderer's own calls: ONE stream, the same machinery on the engine's second session (e->one).  Until round 5
@@ -772,7 +717,7 @@ int emspec_column(emspec_engine* e, const float* frame, int32_t n, int32_t hop, 
                   uint8_t* out_rgba, int32_t rows, int64_t* out_column) {
     if (!e) return EMSPEC_ERR_INVALID_ARG;
     int64_t c = -1;
-    const int rc = columns_impl(e, e->one, frame, 1, n, hop, reassign, out_db, out_rgba, rows, &c);
+    const int rc = columns_impl(e, e->one, frame, live_ask_single(1, n, hop, reassign, 1, e->cfg.rows), out_db, out_rgba, rows, &c);
     if (rc == EMSPEC_OK && out_column) *out_column = c;
     return rc;
 }
@@ -794,7 +739,8 @@ int emspec_push_samples(emspec_engine* e, const float* samples, int64_t count, i
                         int64_t* out_first_column) {
     if (!e) return EMSPEC_ERR_INVALID_ARG;
     int64_t cnt = 0, first = -1;
-    const int rc = push_impl(e, e->one, samples, 1, count, count, n, hop, reassign, out_db, out_rgba, rows, max_columns, &cnt, &first);
+    const int rc = push_impl(e, e->one, samples, live_ask_single(1, n, hop, reassign, 2, e->cfg.rows), count, count, out_db, out_rgba, rows,
+                             max_columns, &cnt, &first);
     if (rc == EMSPEC_OK) {
         if (out_count) *out_count = cnt;
         if (out_first_column) *out_first_column = first;
@@ -842,7 +788,7 @@ int emspec_set_live_wave(emspec_engine* e, emspec_wave* wave_out, int64_t capaci
     // the pair of a column is taken when its frame arrives: a stream that already has frames has columns without a pair
     for (const LiveState* lv : {&e->live, &e->one})
         for (int s = 0; s < lv->c.streams(); ++s)
-            if (lv->g.form != 0 && lv->c.fed[s] > 0)
+            if (lv->ss.g.form != 0 && lv->c.fed[s] > 0)
                 return fail(e, EMSPEC_ERR_STATE, "the envelope needs the samples of every column still to come: a session has frames fed; call emspec_reset() first");
     e->live_wave = wave_out; e->live_wave_capacity = capacity;
     return EMSPEC_OK;
@@ -851,17 +797,15 @@ int emspec_set_live_wave(emspec_engine* e, emspec_wave* wave_out, int64_t capaci
 int emspec_reset_stream(emspec_engine* e, int32_t stream) {
     if (!e) return EMSPEC_ERR_INVALID_ARG;
     LiveState& lv = e->live;
-    if (lv.g.form == 0) return fail(e, EMSPEC_ERR_STATE, "no live session");
-    if (stream < 0 || stream >= lv.g.S) return fail(e, EMSPEC_ERR_INVALID_ARG, "stream out of range");
+    if (lv.ss.g.form == 0) return fail(e, EMSPEC_ERR_STATE, "no live session");
+    if (stream < 0 || stream >= lv.ss.g.S) return fail(e, EMSPEC_ERR_INVALID_ARG, "stream out of range");
     HIPCHK(e, hipSetDevice(e->device));
     if (int rc = live_pcm_drain(e, lv)) return rc;
     const int R = e->cfg.rows;
     const size_t cell = e->exact() ? 8 : 4, perp = LiveGeometry::pstate_bytes(R);
-    // every band's ring: a multi-band session's K, a multi-resolution session's two, else the one
-    const int K = lv.mb.bands ? lv.mb.bands : lv.g.n_high ? 2 : 1;
-    for (int k = 0; k < K; ++k) {
-        const size_t per = lv.mb.bands ? lv.mb.ring_bytes(k, cell) : k ? lv.g.ring_high_bytes(R, cell) : lv.g.ring_bytes(R, cell);
-        HIPCHK(e, hipMemsetAsync(reinterpret_cast<char*>(k ? lv.d_cells_band[k - 1] : lv.d_cells) + stream * per, 0, per, e->stream));
+    for (int k = 0; k < lv.ss.bands; ++k) {   // every band's ring
+        const size_t per = lv.ss.ring_bytes(k, cell);
+        HIPCHK(e, hipMemsetAsync(reinterpret_cast<char*>(lv.d_cells[k]) + stream * per, 0, per, e->stream));
     }
     if (lv.d_pstate) HIPCHK(e, hipMemsetAsync(reinterpret_cast<char*>(lv.d_pstate) + stream * perp, 0, perp, e->stream));
     lv.c.reset_stream(stream);

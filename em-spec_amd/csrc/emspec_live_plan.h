@@ -1,8 +1,11 @@
 // emspec_live_plan.h — internal: the host arithmetic of a streaming session (emspec_live.cpp): the descriptor the
-// kernels read per stream, the session's geometry with every byte size derived from it, the per-stream counters, and the steps
-// of each call that decide which column an output slot holds.  Integer arithmetic only.  No HIP, nothing of the engine:
-// tests/test_live_plan_cpu.py runs it through a stand-alone program (tests/cdriver/live_plan_driver.cpp) without a GPU.
+// kernels read per stream, the session's geometry - a list of bands, whatever its kind - with every byte size derived from it,
+// the rule that refuses a call which does not fit the open session, the kernels each launch runs, the per-stream counters, and
+// the steps of each call that decide which column an output slot holds.  Integer arithmetic only.  No HIP, nothing of the engine:
+// tests/test_live_plan_cpu.py and tests/test_live_band_plan_cpu.py run it through a stand-alone program
+// (tests/cdriver/live_plan_driver.cpp) without a GPU.
 #pragma once
+#include "emspec_band_plan.h"
 #include "emspec_tables.h"
 
 #include <algorithm>
@@ -48,30 +51,18 @@ inline int live_frames_per_launch(int S) { return std::max(8, std::min(64, 2048 
 // whole frames in `total` samples
 inline int64_t frames_after(int64_t total, int n, int hop) { return total >= n ? (total - n) / hop + 1 : 0; }
 
-// ---- the session's geometry: fixed by its first call ----
+// ---- the session at its first fft size: fixed by its first call ----
+// What every kind of session shares: streams, hop, the feeding form, the staging block, the device sample ring, the output
+// layout.  Its column rings are the bands' (LiveSession below).
 struct LiveGeometry {
     int S = 0, n = 0, hop = 0, reassign = -1, D = 0;
     int form = 0;             // 0 none, 1 per-frame (emspec_columns), 2 per-sample-block (emspec_push_samples_multi)
     int mmax = 0;             // frames per stream and launch, at most
-    int slots = 0;            // column-ring slots per stream: 2 D + mmax
     int64_t cap = 0;          // samples per stream the staging block holds (form 1: n; form 2: mmax * hop)
     int ring_mask = 0;        // device sample ring per stream: ring_mask + 1 >= n + cap samples, a power of two (form 2)
-    // multi-resolution session (emspec_columns_multires / emspec_push_samples_multires): n / D / slots are the
-    // long band's (rows [0, split) at n_low); the short band (rows [split, R) at n_high) has its own column ring, indexed by the
-    // emitted column.  Its frame count follows the long band's: 0 while fed is 0, fed + 2 shift after.
-    int n_high = 0, split = 0, shift = 0, D_high = 0;   // n_high == 0: a single-resolution session
-    int slots_high = 0;       // mmax + shift + D + D_high
 
-    // rows of the long band's ring / of the short band's, of an engine with R rows
-    int rows_low(int R) const { return n_high ? split : R; }
-    int rows_high(int R) const { return n_high ? R - split : 0; }
-    // Every size below is in bytes.  Column rings, per stream, `cell` bytes per cell (FAST 4, EXACT 8): [slots][rows]
-    size_t ring_bytes(int R, size_t cell) const { return (size_t)slots * rows_low(R) * cell; }
-    size_t ring_high_bytes(int R, size_t cell) const { return (size_t)slots_high * rows_high(R) * cell; }
-    size_t rings_bytes(int R, size_t cell) const { return (size_t)S * ring_bytes(R, cell); }             // ... of all S streams
-    size_t rings_high_bytes(int R, size_t cell) const { return (size_t)S * ring_high_bytes(R, cell); }
+    // Every size below is in bytes.
     size_t sring_bytes() const { return (size_t)S * ((size_t)ring_mask + 1) * 4; }   // [S][ring_mask + 1] float32
-    size_t done_bytes() const { return (size_t)S * 4 * (n_high ? 2 : 1); }           // arrival counters, one set per band
     size_t desc_bytes() const { return (size_t)S * sizeof(LiveStream); }
     size_t fresh_bytes() const { return (size_t)S * cap * 4; }                       // staging samples [S][cap] float32
     size_t decoded_bytes() const { return fresh_bytes(); }                           // PCM session: the same block on the device
@@ -87,28 +78,177 @@ struct LiveGeometry {
     size_t raw_at(int source, int pend, int frame_bytes) const { return ((size_t)source * cap + pend) * frame_bytes; }
 };
 
-// n_high != 0: a multi-resolution session (n = n_low; rows below `split` from n, the rest from n_high)
-inline LiveGeometry live_geometry(int S, int n, int hop, int reassign, int form, int n_high = 0, int split = 0) {
+inline LiveGeometry live_geometry(int S, int n, int hop, int reassign, int form) {
     LiveGeometry g;
     g.S = S; g.n = n; g.hop = hop; g.reassign = reassign; g.form = form;
     g.D = latency(n, hop, reassign);
-    // The short band runs 2 shift frames ahead and its ring is indexed by the emitted column (its own column - shift).  A call
-    // that feeds long frames j .. j + m - 1 finds emitted columns >= j - D unfinalised, and its short frames, the last of them
-    // frame j + m - 1 + 2 shift = emitted column j + m - 1 + shift, add up to D_high columns further: m + shift + D + D_high
-    // columns are live at once (reassign on: D = D_high + shift, i.e. m + 2 shift + 2 D_high).
-    g.n_high = n_high;
-    g.split = n_high ? split : 0;
-    g.shift = n_high ? (n - n_high) / (2 * hop) : 0;
-    g.D_high = n_high ? latency(n_high, hop, reassign) : 0;
     // (a staging block of at most 2^17 samples per stream: at a large hop fewer frames per launch instead of megabytes pinned)
     g.mmax = form == 1 ? 1 : std::max(1, std::min(live_frames_per_launch(S), (1 << 17) / hop));
-    g.slots = 2 * g.D + g.mmax;
     g.cap = form == 1 ? n : (int64_t)g.mmax * hop;
     int ring = 1;
     while (ring < n + g.cap) ring <<= 1;
     g.ring_mask = ring - 1;
-    g.slots_high = n_high ? g.mmax + g.shift + g.D + g.D_high : 0;
     return g;
+}
+
+// ---- the session: a list of K >= 1 bands of the row table ----
+// Single-resolution (emspec_columns, emspec_push_samples*): one band, every row at n.  Two-band (*_multires): rows below
+// split_row at n_low, the rest at n_high.  Multi-band (*_multiband): the caller's 2..4 bands.  The counters, descriptors and
+// push / flush / frame steps below are those of the first band's fft size (`g`); a band adds what its frame launch and its
+// column ring need.
+enum LiveKind { kLiveNone = 0, kLiveSingle, kLiveTwoBand, kLiveMultiBand };
+
+// What a call asks for, from its arguments alone: compared with the open session (live_mismatch) and, on a session's first
+// call, turned into its geometry (live_session) - after the ABI's shape checks, no arithmetic before them.
+struct LiveAsk {
+    int kind = kLiveNone, S = 0, hop = 0, reassign = 0, form = 0;
+    BandPlan p;   // sizes and row ranges (its shifts are not read)
+};
+inline LiveAsk live_ask(int kind, int S, const BandPlan& p, int hop, int reassign, int form) {
+    LiveAsk a;
+    a.kind = kind; a.S = S; a.hop = hop; a.reassign = reassign ? 1 : 0; a.form = form; a.p = p;
+    return a;
+}
+inline LiveAsk live_ask_single(int S, int n, int hop, int reassign, int form, int rows) {
+    BandPlan p;
+    p.bands = 1; p.n[0] = n; p.hi[0] = rows;
+    return live_ask(kLiveSingle, S, p, hop, reassign, form);
+}
+inline LiveAsk live_ask_two_band(int S, int n_low, int n_high, int hop, int split, int reassign, int form, int rows) {
+    BandPlan p;
+    p.bands = 2; p.n[0] = n_low; p.n[1] = n_high; p.hi[0] = p.lo[1] = split; p.hi[1] = rows;
+    return live_ask(kLiveTwoBand, S, p, hop, reassign, form);
+}
+inline LiveAsk live_ask_bands(int S, const BandPlan& p, int hop, int reassign, int form) {
+    return live_ask(kLiveMultiBand, S, p, hop, reassign, form);
+}
+
+// One band of the session: rows [lo, hi) of the output column from fft size n.  Its frames run frame_shift ahead of the first
+// band's, its frame j sits on emitted column j - shift, and its ring is indexed by the emitted column.
+struct LiveBand {
+    int n = 0, lo = 0, hi = 0;
+    int shift = 0;         // (n[0] - n) / (2 hop)
+    int D = 0;             // latency(n, hop, reassign): the band's own
+    int frame_shift = 0;   // 2 shift
+    int lat_extra = 0;     // D_0 - D: what the frame kernel adds to its plan's D to finalise the emitted column
+    int slots = 0;         // column-ring slots per stream: mmax + shift + D_0 + D (band 0: 2 D_0 + mmax)
+    int rows() const { return hi - lo; }
+};
+
+struct LiveSession {
+    LiveGeometry g;        // at n[0]: mmax, cap, ring_mask, D, the staging and output sizes
+    int kind = kLiveNone;
+    int bands = 0;
+    LiveBand b[kMaxBands];
+    // Every size below is in bytes.  Band k's column ring, per stream and of all S streams, `cell` bytes per cell (FAST 4,
+    // EXACT 8): [slots][rows]
+    size_t ring_bytes(int k, size_t cell) const { return (size_t)b[k].slots * b[k].rows() * cell; }
+    size_t rings_bytes(int k, size_t cell) const { return (size_t)g.S * ring_bytes(k, cell); }
+    size_t done_bytes() const { return (size_t)g.S * 4 * bands; }   // arrival counters, one set per band: band k's at done + k S
+    // the workgroups per stream of band k's frame launch, without the ingest workgroup: on a stream's first frame (priming) the
+    // band transforms frames 0 .. 2 shift at once
+    int launch_frames(int k, int frames, bool priming) const { return frames + (priming ? b[k].frame_shift : 0); }
+    // The finalize rule.  A band defers its finalize to a second kernel when the launch completes more than inline_max columns
+    // per stream (inline they are one workgroup's serial round trips to the memory side, ~2 us per column) or its transform is
+    // small (n < 2048: its workgroup has n / 16 threads, too few for 1024 rows).  The bands of a single-resolution or two-band
+    // session decide each alone.  Those of a multi-band session decide together: when ANY band would defer, EVERY band's frame
+    // launch only scatters and one kernel finalises all bands' rows - K + 1 launches, not up to 2 K.
+    bool together() const { return kind == kLiveMultiBand; }
+    bool defers(int k, int frames, int inline_max) const {
+        if (frames > inline_max) return true;
+        for (int i = together() ? 0 : k; i < (together() ? bands : k + 1); ++i)
+            if (b[i].n < 2048) return true;
+        return false;
+    }
+    // the session was opened with these bands (sizes and row ranges)
+    bool same_bands(const BandPlan& p) const {
+        if (p.bands != bands) return false;
+        for (int k = 0; k < bands; ++k)
+            if (p.n[k] != b[k].n || p.lo[k] != b[k].lo || p.hi[k] != b[k].hi) return false;
+        return true;
+    }
+};
+
+// a: an accepted call (the ABI's shape and split checks passed)
+inline LiveSession live_session(const LiveAsk& a) {
+    LiveSession m;
+    m.g = live_geometry(a.S, a.p.n[0], a.hop, a.reassign, a.form);
+    m.kind = a.kind;
+    m.bands = a.p.bands;
+    // Band k's frames run 2 shift ahead and its ring is indexed by the emitted column.  A call that feeds long frames
+    // j .. j + m - 1 finds emitted columns >= j - D unfinalised, and the band's last frame, j + m - 1 + 2 shift = emitted column
+    // j + m - 1 + shift, adds up to D_k columns further: m + shift + D + D_k columns are live at once (reassign on:
+    // D = D_k + shift, i.e. m + 2 shift + 2 D_k).
+    for (int k = 0; k < m.bands; ++k) {
+        LiveBand& b = m.b[k];
+        b.n = a.p.n[k]; b.lo = a.p.lo[k]; b.hi = a.p.hi[k];
+        b.shift = (a.p.n[0] - b.n) / (2 * a.hop);
+        b.D = latency(b.n, a.hop, a.reassign);
+        b.frame_shift = 2 * b.shift;
+        b.lat_extra = m.g.D - b.D;
+        b.slots = m.g.mmax + b.shift + m.g.D + b.D;
+    }
+    return m;
+}
+
+// Null, or why a call that asks for `a` does not fit the open session (EMSPEC_ERR_STATE, include/emspec.h): a multi-band
+// session and a two-band one refuse each other's calls even at K = 2, and nothing of a session changes mid-stream.
+inline const char* live_mismatch(const LiveSession& open, const LiveAsk& a) {
+    if (open.kind == kLiveNone) return nullptr;
+    if (open.kind != a.kind) {
+        if (open.kind == kLiveMultiBand)
+            return "the live session is a multi-band one (emspec_columns_multiband / emspec_push_samples_multiband); call emspec_reset() first";
+        if (a.kind == kLiveMultiBand) return "the live session is not a multi-band one; call emspec_reset() before a multi-band call";
+        return open.kind == kLiveTwoBand ? "the live session is a multi-resolution one (emspec_columns_multires / emspec_push_samples_multires); call emspec_reset() first"
+                                         : "the live session is a single-resolution one; call emspec_reset() before a multi-resolution call";
+    }
+    const LiveGeometry& g = open.g;
+    if (a.S == g.S && a.hop == g.hop && a.reassign == g.reassign && a.form == g.form && open.same_bands(a.p)) return nullptr;
+    return a.kind == kLiveMultiBand ? "streams / bands / fft sizes / split rows / hop / reassign / feeding mode changed mid-stream; call emspec_reset() first"
+           : a.kind == kLiveTwoBand ? "streams / fft sizes / hop / split row / reassign / feeding mode changed mid-stream; call emspec_reset() first"
+                                    : "streams / fft size / hop / reassign / feeding mode changed mid-stream; call emspec_reset() first";
+}
+
+// ---- the launches of one call's round, in order (emspec_live.cpp: live_launch runs them; nothing else decides a launch) ----
+// mlaunch: the most frames any stream has in the round (0: it only moves samples into the sample rings); flush: no frames, one
+// pending column per stream; priming: some stream's first frame.  Only launches that reach the device are listed.
+enum LiveStepKind { kStepFrames = 0, kStepFinalize, kStepFinalizeBands };
+struct LiveStep {
+    int what = kStepFrames;
+    int band = 0;           // kStepFrames, kStepFinalize: the band
+    int groups = 0;         // kStepFrames: workgroups per stream without the ingest workgroup
+    int ncol = 0;           // the finalizes: columns per stream, at most
+    bool defer = false;     // kStepFrames: the launch only scatters; a finalize step follows unless no stream has a frame
+    bool ingest = false;    // kStepFrames: carries the ingest workgroup (band 0's)
+};
+struct LiveSteps {
+    int count = 0;
+    LiveStep step[2 * kMaxBands + 1];
+    void add(int what, int band, int groups, int ncol, bool defer = false, bool ingest = false) {
+        step[count++] = LiveStep{what, band, groups, ncol, defer, ingest};
+    }
+};
+// per_band: the diagnostic build's A/B aid (EMSPEC_LIVE_FINALIZE_PER_BAND) - a multi-band session's one finalize for all bands
+// as K finalizes, band after band
+inline LiveSteps live_steps(const LiveSession& m, int mlaunch, bool flush, bool priming, int inline_max, bool per_band = false) {
+    LiveSteps t;
+    const bool joint = m.together() && !per_band;
+    // the columns a launch completes are the first band's frame count for every band
+    const int ncol = flush ? 1 : mlaunch;
+    for (int k = 0; k < m.bands; ++k) {
+        // a band behind the first: no launch when no stream has a frame (a block that only fills the sample ring: the first
+        // band's ingest workgroup did that)
+        if (k > 0 && !flush && mlaunch <= 0) break;
+        const bool defer = !flush && m.defers(k, mlaunch, inline_max);
+        if (!flush) t.add(kStepFrames, k, m.launch_frames(k, mlaunch, priming), 0, defer, k == 0);
+        // each band alone: its finalize directly behind its frames; together: behind the last band's
+        if ((flush || defer) && ncol > 0 && !m.together()) t.add(kStepFinalize, k, 0, ncol);
+    }
+    if (m.together() && (flush || m.defers(0, mlaunch, inline_max)) && ncol > 0) {
+        if (joint) t.add(kStepFinalizeBands, 0, 0, ncol);
+        for (int k = 0; !joint && k < m.bands; ++k) t.add(kStepFinalize, k, 0, ncol);
+    }
+    return t;
 }
 
 // ---- per stream: frames fed, columns emitted, samples received, samples in the device ring, samples in the staging block ----

@@ -52,12 +52,12 @@ int view_launch(emspec_engine* e, int32_t session, int32_t stream0, int32_t pair
     if (e->history_W <= 0) return fail(e, EMSPEC_ERR_STATE, "no live history is set (emspec_set_live_history)");
     if (!lvp) return fail(e, EMSPEC_ERR_STATE, "session must be EMSPEC_SESSION_MULTI or EMSPEC_SESSION_ONE");
     LiveState& lv = *lvp;
-    if (lv.g.form == 0 || !lv.d_hring) return fail(e, EMSPEC_ERR_STATE, "the session has not started: it has no history");
+    if (lv.ss.g.form == 0 || !lv.d_hring) return fail(e, EMSPEC_ERR_STATE, "the session has not started: it has no history");
     if (factor < 1 || factor > kHistoryMaxFactor) return fail(e, EMSPEC_ERR_INVALID_ARG, "a view's factor must be in 1..65536");
     if (groups < 1) return fail(e, EMSPEC_ERR_INVALID_ARG, "a view needs at least one group");
     if (const char* why = stereo_pair_error(views, a, b)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
-    if (pairs < 1 || pairs > 65535 || stream0 < 0 || (int64_t)stream0 + (int64_t)pairs * views > lv.g.S)
-        return fail(e, EMSPEC_ERR_INVALID_ARG, "the view's streams (pairs x views from stream0 on) must lie inside the session's 0.." + std::to_string(lv.g.S - 1));
+    if (pairs < 1 || pairs > 65535 || stream0 < 0 || (int64_t)stream0 + (int64_t)pairs * views > lv.ss.g.S)
+        return fail(e, EMSPEC_ERR_INVALID_ARG, "the view's streams (pairs x views from stream0 on) must lie inside the session's 0.." + std::to_string(lv.ss.g.S - 1));
     if (!level && !index && !pan && !rgba) return fail(e, EMSPEC_ERR_INVALID_ARG, "a stereo image needs at least one output");
     const emspec_stereo_map m = map_of(e, map);
     if (const char* why = map_error(m)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);

@@ -26,7 +26,7 @@ hipError_t launch_live_flush(bool exact, const LiveSinks& lv, void* cells, int s
     return hipGetLastError();
 }
 
-// Finalise every band's rows of a column in one launch (a live multi-band session, DESIGN.md §3.13; emspec_live_band_plan.h): grid
+// Finalise every band's rows of a column in one launch (a live multi-band session, DESIGN.md §3.13; emspec_live_plan.h): grid
 // (columns, S) as above, and workgroup (i, s) runs one live_finalize_column per band - that band's ring, slots, rows, first row and
 // conversion, all in the kernel arguments - so a column of K bands costs one launch, not K.  It serves the session's flush and
 // its deferred finalize; as for live_finalize_kernel, the kernel boundary behind the bands' frame launches on the one stream

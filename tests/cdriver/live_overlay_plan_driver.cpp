@@ -33,7 +33,8 @@ struct Session {
     bool first_event = true;
 
     void open(int S, int n, int hop, int reassign, int form, int n_high, int split) {
-        g = live_geometry(S, n, hop, reassign, form, n_high, split);
+        // (the overlays read the session at its first fft size only: the same for a two-band session, whatever its rows)
+        g = live_session(n_high ? live_ask_two_band(S, n, n_high, hop, split, reassign, form, 1024) : live_ask_single(S, n, hop, reassign, form, 1024)).g;
         c.open(S);
         desc.assign(S, LiveStream{});
         epoch.assign(S, 0);

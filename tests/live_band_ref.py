@@ -1,5 +1,5 @@
 """The live multi-band session's host arithmetic restated in pure Python, written from the rules and not
-from em-spec_amd/csrc/emspec_live_band_plan.h; tests/test_live_band_plan_cpu.py compares the two field for field.
+from em-spec_amd/csrc/emspec_live_plan.h; tests/test_live_band_plan_cpu.py compares the two field for field.
 
 The rules.  K bands, fft sizes n[0] > ... > n[K-1], one hop.  Band k owns rows [lo_k, hi_k) cut by the K - 1 split rows.  All
 bands' frames END on the same sample: band k's frame j + 2 shift_k ends where the long band's frame j ends, shift_k =
@@ -53,7 +53,7 @@ def geometry(S, hop, reassign, form, R, cell, n, split):
     slots = [mmax + shift[k] + D + Dk[k] for k in range(K)]
     ring = [slots[k] * (cuts[k + 1] - cuts[k]) * cell for k in range(K)]
     small = any(v < 2048 for v in n)
-    return dict(S=S, n=n[0], hop=hop, reassign=reassign, D=D, form=form, mmax=mmax, cap=g["cap"], ring_mask=g["ring_mask"], n_high=0,
+    return dict(S=S, n=n[0], hop=hop, reassign=reassign, D=D, form=form, mmax=mmax, cap=g["cap"], ring_mask=g["ring_mask"],
                 bands=K, sring_bytes=S * (g["ring_mask"] + 1) * 4, desc_bytes=32 * S, fresh_bytes=4 * S * g["cap"],
                 out1_bytes=4 * S * R, done_bytes=4 * S * K, band_n=list(n), lo=cuts[:-1], hi=cuts[1:], shift=shift,
                 band_D=Dk, frame_shift=[2 * v for v in shift], lat_extra=[D - v for v in Dk], slots=slots, ring_bytes=ring,
@@ -61,71 +61,27 @@ def geometry(S, hop, reassign, form, R, cell, n, split):
                 defers_1=int(small), defers_2=int(small), defers_3=1)
 
 
-class Session:
+class Session(L.Session):
     """The calls of a multi-band session: tests/live_ref.py's session at n[0], and per launch what the bands do."""
 
     def __init__(self, S, hop, reassign, form, R, n, split):
-        self.one = L.Session(S, n[0], hop, reassign, form)
-        self.n, self.hop, self.S = list(n), hop, S
-        self.zero = [set() for _ in n]       # per band: streams whose ring is all zero (the driver fills every ring with ones)
+        super().__init__(S, n[0], hop, reassign, form)
+        self.n, self.hop = list(n), hop
+        self.zero = [set() for _ in n]       # per band: streams whose ring a reset has cleared
 
-    def _launch(self, l, flush):
-        if not l["launched"]:
-            return dict(launched=0, flush=0, mx=l["mx"], priming=0, defer=0, groups=[], kernels=0)
-        mx = 0 if flush else max(d[2] for d in l["desc"])
-        priming = l["priming"]
-        defer = int(not flush and (mx > INLINE or any(v < 2048 for v in self.n)))
-        groups, kernels = [], 0
-        for k, v in enumerate(self.n):
-            run = not flush and (k == 0 or mx > 0)
-            groups.append(mx + (((self.n[0] - v) // self.hop) if priming else 0) if run else -1)
-            kernels += int(run)
-        kernels += int(flush or (defer and mx > 0))
-        return dict(launched=1, flush=int(flush), mx=mx, priming=priming, defer=defer, groups=groups, kernels=kernels)
-
-    def _call(self, k):
-        out = dict(op=k["op"], arg=k["arg"], predict=k["predict"], refused=k["refused"],
-                   launches=[self._launch(l, k["op"] == "flush") for l in k["launches"]], counts=k["counts"], first=k["first"],
-                   cleared=[len(z) for z in self.zero], fed=k["fed"], emitted=k["emitted"], seen=k["seen"])
-        return out
-
-    def frame(self):
-        return self._call(self.one.frame())
-
-    def flush(self):
-        return self._call(self.one.flush())
-
-    def push(self, count, direct):
-        return self._call(self.one.push(count, direct))
-
-    def predict(self, count):
-        return self._call(self.one._call("predict", arg=count, predict=self.one.predict(count)))
-
-    def reset(self, s):
-        for z in self.zero:
-            z.add(s)
-        return self._call(self.one.reset(s))
+    def _steps(self, mlaunch, flush, priming):
+        defer = int(not flush and (mlaunch > INLINE or any(v < 2048 for v in self.n)))
+        steps = []
+        for k, v in enumerate(self.n):       # band 0 carries the ingest; the others follow only when some stream has a frame
+            if not flush and (k == 0 or mlaunch > 0):
+                steps.append([L.FRAMES, k, mlaunch + (((self.n[0] - v) // self.hop) if priming else 0), 0, defer, int(k == 0)])
+        if flush or (defer and mlaunch > 0):  # one kernel for all bands' rows
+            steps.append([L.FINALIZE_BANDS, 0, 0, 1 if flush else mlaunch, 0, 0])
+        return steps
 
 
 def run(script):
-    out, t = [], None
-    for line in script:
-        w = line.split()
-        if w[0] == "open":
-            S, hop, reassign, form, R, K = map(int, w[1:7])
-            n = list(map(int, w[7:7 + K]))
-            split = list(map(int, w[7 + K:7 + 2 * K - 1]))
-            t = Session(S, hop, reassign, form, R, n, split)
-        elif w[0] == "frame":
-            out.append(t.frame())
-        elif w[0] == "flush":
-            out.append(t.flush())
-        elif w[0] == "push":
-            out.append(t.push(int(w[1]), int(w[2]) != 0))
-        elif w[0] == "predict":
-            out.append(t.predict(int(w[1])))
-        elif w[0] == "reset":
-            out.append(t.reset(int(w[1])))
-        else:
-            raise ValueError(line)
-    return out
+    def session(o):
+        assert o["kind"] == 3 and not o["views"]
+        return Session(o["S"], o["hop"], o["reassign"], o["form"], o["R"], o["n"], o["split"])
+    return L.run(script, session)

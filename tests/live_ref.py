@@ -7,8 +7,18 @@ The rules.  A stream has received `seen` samples; frame j is samples [j hop, j h
 whole.  Frame j adds energy to columns j - D .. j + D, so column c is final once frame c + D is fed: a stream that has fed f frames
 has emitted max(f - D, 0) columns - unless it was flushed, which emits the columns still pending one by one and puts the stream at
 its end.  New samples wait in a page-locked staging block of `cap` samples per stream until a launch moves them to the stream's
-ring on the device; a launch takes at most mmax frames per stream."""
+ring on the device; a launch takes at most mmax frames per stream.
+
+The kernels of a launch (Session._steps), written from live_launch of em-spec_amd/csrc/emspec_live.cpp as it stood before the
+launch plan became data: the long band first, then - only when some stream has a frame, or on a flush - the short band.  A band's
+flush is one finalize kernel over 1 column.  Otherwise its frame kernel runs with the launch's most frames per stream as
+workgroups (the short band: 2 shift more while some stream is at its first frame), finalising in place unless the launch
+completes more than 2 columns per stream or the band's fft size is below 2048; then a finalize kernel over that many columns
+follows directly - none when no stream has a frame."""
 from dataclasses import dataclass
+
+INLINE = 2                                  # columns per stream a frame kernel finalises in place, at most
+FRAMES, FINALIZE, FINALIZE_BANDS = 0, 1, 2  # a step: [what, band, workgroups per stream, columns, defers, carries the ingest]
 
 
 def latency(n, hop, reassign):
@@ -72,20 +82,41 @@ class Session:
         self.g = geometry(S, n, hop, reassign, form, n_high, split)
         self.st = [Stream() for _ in range(S)]
         self.views, self.frame_bytes = views, frame_bytes
+        self.zero = [set() for _ in range(2 if n_high else 1)]   # per band: streams whose ring a reset has cleared
+
+    def _steps(self, mlaunch, flush, priming):
+        g, steps = self.g, []
+        bands = [(g["n"], 0)] + ([(g["n_high"], 2 * g["shift"])] if g["n_high"] else [])
+        for k, (n, ahead) in enumerate(bands):
+            if k and not (flush or mlaunch > 0):
+                continue
+            if flush:
+                steps.append([FINALIZE, k, 0, 1, 0, 0])
+                continue
+            defer = mlaunch > INLINE or n < 2048
+            steps.append([FRAMES, k, mlaunch + (ahead if priming and k else 0), 0, int(defer), int(k == 0)])
+            if defer and mlaunch > 0:
+                steps.append([FINALIZE, k, 0, mlaunch, 0, 0])
+        return steps
 
     # ---- what the driver prints after every call ----
     def _launch(self, desc, launched=1, take=0, maxpend=0, mx=0, at=(), nc=()):
-        return dict(launched=launched, take=take, maxpend=maxpend, mx=mx,
-                    uniform=int(all(d == desc[0] for d in desc)) if launched else 0,
-                    priming=int(any(d[0] == 0 and d[2] > 0 for d in desc)) if launched else 0,
-                    at=list(at), nc=list(nc), desc=[list(d) for d in desc] if launched else [])
+        if not launched:
+            return dict(launched=0, flush=0, mlaunch=0, take=take, maxpend=maxpend, mx=mx, uniform=0, priming=0, at=list(at), nc=list(nc),
+                        desc=[], steps=[])
+        flush = int(any(d[5] for d in desc))
+        mlaunch = max(d[2] for d in desc)
+        priming = int(any(d[0] == 0 and d[2] > 0 for d in desc))
+        return dict(launched=1, flush=flush, mlaunch=mlaunch, take=take, maxpend=maxpend, mx=mx,
+                    uniform=int(all(d == desc[0] for d in desc)), priming=priming, at=list(at), nc=list(nc), desc=[list(d) for d in desc],
+                    steps=self._steps(mlaunch, bool(flush), bool(priming)))
 
     def _call(self, op, arg=0, predict=-1, refused="", launches=(), counts=(), first=()):
         st = self.st
         return dict(op=op, arg=arg, predict=predict, refused=refused, launches=list(launches), counts=list(counts), first=list(first),
                     fed=[x.fed for x in st], emitted=[x.emitted for x in st], seen=[x.seen for x in st],
                     newbase=[x.in_ring for x in st], pend=[x.staged for x in st], pending=[int(x.fed > x.emitted) for x in st],
-                    any_pending=int(any(x.fed > x.emitted for x in st)))
+                    any_pending=int(any(x.fed > x.emitted for x in st)), cleared=[len(z) for z in self.zero])
 
     def _refusal(self):
         D = self.g["D"]
@@ -184,17 +215,36 @@ class Session:
                 x.in_ring, x.staged = x.seen, 0
             launches.append(self._launch(desc))
         self.st[s] = Stream()
+        for z in self.zero:                              # every band's ring of the stream
+            z.add(s)
         return self._call("reset", arg=s, launches=launches)
 
 
-def run(script):
-    """script: the driver's lines.  -> the list of objects the driver prints."""
+def open_line(kind, S, hop, reassign, form, R, n, split, views=0, fb=1):
+    """The driver's first line.  kind: 1 single-resolution, 2 two-band, 3 multi-band."""
+    return "open " + " ".join(map(str, [kind, S, hop, reassign, form, R, views, fb, len(n)] + list(n) + list(split)))
+
+
+def parse_open(line):
+    w = list(map(int, line.split()[1:]))
+    K = w[8]
+    return dict(kind=w[0], S=w[1], hop=w[2], reassign=w[3], form=w[4], R=w[5], views=w[6], fb=w[7], n=w[9:9 + K], split=w[9 + K:8 + 2 * K])
+
+
+def run(script, session=None):
+    """script: the driver's lines.  -> the list of objects the driver prints.  session: what an `open` line makes (default: the
+    single-resolution or two-band session here)."""
     out, t = [], None
     for line in script:
         w = line.split()
         if w[0] == "open":
-            S, n, hop, reassign, form, n_high, split, views, fb = map(int, w[1:])
-            t = Session(S, n, hop, reassign, form, n_high, split, views, fb)
+            o = parse_open(line)
+            if session:
+                t = session(o)
+            else:
+                assert o["kind"] == len(o["n"]) <= 2
+                t = Session(o["S"], o["n"][0], o["hop"], o["reassign"], o["form"], *(o["n"][1:] + o["split"]), views=o["views"],
+                            frame_bytes=o["fb"])
         elif w[0] == "frame":
             out.append(t.frame())
         elif w[0] == "flush":

@@ -1,12 +1,12 @@
-"""CPU: the live multi-band session's host arithmetic (em-spec_amd/csrc/emspec_live_band_plan.h) - every
-band's shift, latency, ring slots and byte sizes, the priming rule, the finalize rule and the launches of every call - against the
-pure-Python restatement tests/live_band_ref.py, against today's two-band geometry, and against closed forms, without a GPU.
+"""CPU: the live multi-band session's host arithmetic (the bands of em-spec_amd/csrc/emspec_live_plan.h) -
+every band's shift, latency, ring slots and byte sizes, the priming rule, the finalize rule and the launches of every call - against
+the pure-Python restatement tests/live_band_ref.py, against the two-band geometry, and against closed forms, without a GPU.
 
-tests/cdriver/live_band_plan_driver.cpp is a program of its own that includes only that header (and what it includes), built with
+tests/cdriver/live_plan_driver.cpp is a program of its own that includes only that header (and what it includes), built with
 the host compiler under ASan and UBSan (nothing is preloaded, nothing is loaded into Python under a sanitizer):
 
     g++ -std=c++17 -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -I em-spec_amd/csrc \
-        tests/cdriver/live_band_plan_driver.cpp -o live_band_plan_driver
+        tests/cdriver/live_plan_driver.cpp -o live_plan_driver
 
 Every run must exit with status 0 and an empty stderr."""
 import json
@@ -33,10 +33,10 @@ def _splits(K, rows=R):
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("live_band_plan")
-    exe = str(tmp / "live_band_plan_driver")
+    exe = str(tmp / "live_plan_driver")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-I", os.path.join(ROOT, "em-spec_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "cdriver", "live_band_plan_driver.cpp"), "-o", exe])
+                           os.path.join(ROOT, "tests", "cdriver", "live_plan_driver.cpp"), "-o", exe])
     count = [0]
 
     def run(cmd, lines):
@@ -50,7 +50,7 @@ def driver(tmp_path_factory):
 
 
 def _line(S, hop, reassign, form, rows, cell, n, split):
-    return " ".join(map(str, [S, hop, reassign, form, rows, cell, len(n)] + list(n) + list(split)))
+    return L.open_line(3, S, hop, reassign, form, rows, n, split)[5:] + " %d 1" % cell
 
 
 def _two_band_shapes():
@@ -104,7 +104,7 @@ def test_geometry_and_sizes_equal_the_restatement(driver):
                     "rings_bytes": have["rings_bytes"][0], "rings_high_bytes": have["rings_bytes"][1],
                     "sring_bytes": have["sring_bytes"], "desc_bytes": have["desc_bytes"], "fresh_bytes": have["fresh_bytes"],
                     "done_bytes": have["done_bytes"]}
-            assert two == same, (c, two, same)
+            assert {k: two[k] for k in same} == same, (c, two, same)
             g = L.geometry(S, n[0], hop, reassign, form, n[1], split[0])          # ... and the restatement's
             assert all(two[k] == g[k] for k in ("D", "mmax", "cap", "ring_mask", "slots", "slots_high", "shift", "D_high", "split")), c
     assert sum(1 for c in cases if len(c[6]) == 2) >= 4 * 2 * 10
@@ -131,7 +131,7 @@ def test_rejected_shapes_name_the_rule(driver, n, hop, split, rows, why):
 
 
 def _open(S, hop, reassign, form, n, split):
-    return "open " + " ".join(map(str, [S, hop, reassign, form, R, len(n)] + list(n) + list(split)))
+    return L.open_line(3, S, hop, reassign, form, R, n, split)
 
 
 def _scripts():
@@ -165,10 +165,9 @@ def test_sessions_report_the_columns_of_the_single_resolution_session_at_n0(driv
         for i, (have, ref) in enumerate(zip(got, want)):
             assert have == ref, (name, i, script[i + 1], {k: (have.get(k), ref[k]) for k in ref if have.get(k) != ref[k]})
         # the columns of every call: tests/live_ref.py's session at n[0], on its own
-        w = script[0].split()
-        S, hop, reassign, form, K = int(w[1]), int(w[2]), int(w[3]), int(w[4]), int(w[6])
-        n = list(map(int, w[7:7 + K]))
-        one = L.run(["open %d %d %d %d %d 0 0 0 1" % (S, n[0], hop, reassign, form)] + script[1:])
+        o = L.parse_open(script[0])
+        S, hop, reassign, form, n, K = o["S"], o["hop"], o["reassign"], o["form"], o["n"], len(o["n"])
+        one = L.run([L.open_line(1, S, hop, reassign, form, R, n[:1], [])] + script[1:])
         for have, ref in zip(got, one):
             assert (have["counts"], have["first"], have["predict"], have["refused"]) == (ref["counts"], ref["first"], ref["predict"], ref["refused"]), name
             assert (have["fed"], have["emitted"], have["seen"]) == (ref["fed"], ref["emitted"], ref["seen"]), name
@@ -177,6 +176,12 @@ def test_sessions_report_the_columns_of_the_single_resolution_session_at_n0(driv
                 if not l["launched"]:
                     branches.add("staged only")
                     continue
+                # of the launch's steps: per band the workgroups per stream of its frame launch (-1: none), the kernels in all,
+                # whether the frame launches only scatter
+                frames = {st[1]: st for st in l["steps"] if st[0] == L.FRAMES}
+                l = dict(l, mx=l["mlaunch"], groups=[frames[b][2] if b in frames else -1 for b in range(K)], kernels=len(l["steps"]),
+                         defer=max([st[4] for st in frames.values()] + [0]))
+                assert len({st[4] for st in frames.values()}) <= 1 and all(st[0] != L.FINALIZE for st in l["steps"]), (name, l)
                 assert l["kernels"] <= K + 1, (name, l)              # the bound the bands kernel is there for
                 if l["flush"]:
                     assert l["kernels"] == 1 and l["groups"] == [-1] * K

@@ -1,6 +1,8 @@
 """CPU: the streaming session's host arithmetic (em-spec_amd/csrc/emspec_live_plan.h) - the geometry of a
-session, every buffer size, and the per-stream accounting of every call (what a launch's descriptors say, which column each
-output slot holds) - against the pure-Python restatement tests/live_ref.py and against closed forms, without a GPU.
+session, every buffer size, the per-stream accounting of every call (what a launch's descriptors say, which column each
+output slot holds), the kernels each launch runs and the rule that refuses a call which does not fit the open session - against
+the pure-Python restatement tests/live_ref.py and against closed forms, without a GPU.  (The bands of a multi-band session:
+tests/test_live_band_plan_cpu.py, on the same driver.)
 
 tests/cdriver/live_plan_driver.cpp is a program of its own that includes only that header and runs the calls of emspec_live.cpp
 with the HIP calls left out, built with the host compiler under ASan and UBSan (nothing is preloaded, nothing is loaded into
@@ -76,7 +78,7 @@ def test_geometry_and_sizes_equal_the_restatement(driver):
     multi = [c for c in cases if c[5]]
     assert len(cases) - len(multi) == 7 * 6 * 5 * 2 * 2 - 5 * 2 * 2 * 3   # (hop 300 > N = 256; hop 256 is N / 2 or N at N = 512 / 256)
     assert len(multi) >= 12 * 39 and {c[2] for c in multi} >= {64, 128, 256, 512}
-    got = driver("geometry", [" ".join(map(str, c)) for c in cases])
+    got = driver("geometry", [_shape(*c[:8], views=c[9], fb=c[10]) + " %d %d" % (c[8], c[11]) for c in cases])
     assert len(got) == len(cases)
     for c, have in zip(cases, got):
         g = L.geometry(*c[:7])
@@ -97,8 +99,13 @@ def test_geometry_and_sizes_equal_the_restatement(driver):
 
 
 # ---- traces ----
-def _open(S, n, hop, reassign, form, n_high=0, split=0, views=0, fb=1):
-    return "open %d %d %d %d %d %d %d %d %d" % (S, n, hop, reassign, form, n_high, split, views, fb)
+def _shape(S, n, hop, reassign, form, n_high=0, split=0, R=1024, views=0, fb=1):
+    """A single-resolution or (n_high != 0) two-band session as the driver reads it."""
+    return L.open_line(2 if n_high else 1, S, hop, reassign, form, R, [n, n_high][:2 if n_high else 1], [split] if n_high else [], views, fb)[5:]
+
+
+def _open(*a, **kw):
+    return "open " + _shape(*a, **kw)
 
 
 CAP = 64 * 256   # 3 streams at hop 256: 64 frames per launch
@@ -122,6 +129,10 @@ SCRIPTS = {
     # multi-resolution sessions: a stream's first frame primes the short band
     "multires_push": [_open(2, 16384, 256, 1, 2, 4096, 300), "push 16000 0", "push 384 0", "push 256 0", "reset 1", "push 20000 1"],
     "multires_frames": [_open(2, 8192, 512, 0, 1, 2048, 100), "frame", "frame", "reset 0", "frame", "flush"],
+    # ... its staging block smaller than a frame, as "worklet": a launch that only moves samples runs the long band alone
+    "multires_worklet": [_open(64, 16384, 64, 1, 2, 4096, 300)] + ["push 128 0"] * 40 + ["push 16384 0", "push 64 1", "flush"],
+    # ... 16384 / 1024 at hop 512: a frame per call finalises the long band in place while the short band (n < 2048) defers
+    "multires_mixed": [_open(2, 16384, 512, 1, 1, 1024, 512)] + ["frame"] * 3 + ["flush"],
 }
 
 
@@ -161,6 +172,43 @@ def test_traces_equal_the_restatement_and_reach_every_branch(driver):
         prim = [l["priming"] for _, l in _launches(traces[name]) if l["launched"]]
         assert prim[0] == 1 and 0 in prim and 1 in prim[1:], name                                 # first frame; steady; after a reset
     assert not any(l["priming"] for k, l in every if k["op"] == "flush")
+    # the kernels of every launch equalled the restatement's above; between them the scripts reach every branch of that rule, for
+    # both kinds.  (A frame step: [FRAMES, band, workgroups, 0, defers, ingest]; a finalize: [FINALIZE, band, 0, columns, 0, 0].)
+    reached = set()
+    for name, t in traces.items():
+        kind, small = ("two-band", None) if name.startswith("multires") else ("single", int(SCRIPTS[name][0].split()[10]) < 2048)
+        for k, l in _launches(t):
+            assert len(l["steps"]) <= 4 and all(st[0] != L.FINALIZE_BANDS for st in l["steps"]), (name, l)
+            if not l["launched"]:
+                assert l["steps"] == []
+                reached.add((kind, "staged only"))
+                continue
+            frames = {st[1]: st for st in l["steps"] if st[0] == L.FRAMES}
+            fins = {st[1]: st for st in l["steps"] if st[0] == L.FINALIZE}
+            if l["flush"]:
+                assert not frames and [st[3] for st in l["steps"]] == [1] * (2 if kind == "two-band" else 1), (name, l)
+                reached.add((kind, "flush"))
+                continue
+            assert frames[0][5] == 1 and all(st[5] == 0 for b, st in frames.items() if b), (name, l)   # one ingest, the first band's
+            assert set(fins) == ({b for b, st in frames.items() if st[4]} if l["mlaunch"] else set()), (name, l)
+            assert all(st[3] == l["mlaunch"] for st in fins.values()), (name, l)
+            if l["mlaunch"] == 0:
+                assert list(frames) == [0] and frames[0][2] == 0, (name, l)
+                reached.add((kind, "samples only"))
+                continue
+            if l["priming"]:
+                reached.add((kind, "priming"))
+            if l["mlaunch"] > L.INLINE:
+                assert all(st[4] for st in frames.values()), (name, l)
+                reached.add((kind, "defers: many columns"))
+            elif kind == "single":
+                reached.add((kind, "defers: small transform" if small else "in place"))
+                assert frames[0][4] == int(small), (name, l)
+            else:
+                reached.add((kind, {(0, 0): "in place", (0, 1): "only the short band defers"}[(frames[0][4], frames[1][4])]))
+    assert reached >= {(kind, what) for kind in ("single", "two-band") for what in
+                       ("staged only", "samples only", "priming", "defers: many columns", "in place", "flush")}, reached
+    assert reached >= {("single", "defers: small transform"), ("two-band", "only the short band defers")}, reached
 
 
 # ---- closed forms, on the driver's output alone ----
@@ -226,5 +274,52 @@ def test_any_split_of_the_same_samples_gives_the_same_columns(driver):
 
 def test_invariants_hold_on_the_scripted_sessions(driver):
     for name in ("push", "worklet", "pcm", "multires_push"):
-        S, n, hop, reassign, form, n_high, split = map(int, SCRIPTS[name][0].split()[1:8])
-        _check_session(driver("trace", SCRIPTS[name]), L.geometry(S, n, hop, reassign, form, n_high, split))
+        o = L.parse_open(SCRIPTS[name][0])
+        _check_session(driver("trace", SCRIPTS[name]), L.geometry(o["S"], o["n"][0], o["hop"], o["reassign"], o["form"], *(o["n"][1:] + o["split"])))
+
+
+# ---- the rule that refuses a call which does not fit the open session ----
+# (the messages: copied from live_check of em-spec_amd/csrc/emspec_live.cpp as it stood before the rule moved into the header)
+IS_BANDS = "the live session is a multi-band one (emspec_columns_multiband / emspec_push_samples_multiband); call emspec_reset() first"
+NOT_BANDS = "the live session is not a multi-band one; call emspec_reset() before a multi-band call"
+IS_TWO = "the live session is a multi-resolution one (emspec_columns_multires / emspec_push_samples_multires); call emspec_reset() first"
+IS_SINGLE = "the live session is a single-resolution one; call emspec_reset() before a multi-resolution call"
+CHANGED = {1: "streams / fft size / hop / reassign / feeding mode changed mid-stream; call emspec_reset() first",
+           2: "streams / fft sizes / hop / split row / reassign / feeding mode changed mid-stream; call emspec_reset() first",
+           3: "streams / bands / fft sizes / split rows / hop / reassign / feeding mode changed mid-stream; call emspec_reset() first"}
+# kind, S, hop, reassign, form, R, sizes, split rows.  The two-band session and the K = 2 multi-band one: the same bands
+KINDS = {"single": (1, 3, 256, 1, 2, 1024, [16384], []), "two-band": (2, 3, 256, 1, 2, 1024, [16384, 4096], [512]),
+         "bands2": (3, 3, 256, 1, 2, 1024, [16384, 4096], [512]), "bands3": (3, 3, 256, 1, 2, 1024, [16384, 4096, 2048], [256, 512])}
+
+
+def test_a_call_that_does_not_fit_the_open_session_is_refused_in_the_same_words(driver):
+    def line(a, b):
+        return L.open_line(*a)[5:] + " | " + L.open_line(*b)[5:]
+
+    pairs, want = [], []
+    for a, have in KINDS.items():
+        for b, ask in KINDS.items():
+            pairs.append(line(have, ask))
+            if have[0] == ask[0] == 3:
+                want.append("" if a == b else CHANGED[3])          # K = 2 against K = 3: the bands changed
+            elif have[0] == 3:
+                want.append(IS_BANDS)
+            elif ask[0] == 3:
+                want.append(NOT_BANDS)
+            else:
+                want.append("" if a == b else IS_TWO if have[0] == 2 else IS_SINGLE)
+    assert len(pairs) == 16 and want.count("") == 4
+    # one field changed, every other as opened: streams, hop, reassign, the feeding form, a size, a split row - and the band count
+    for name, have in KINDS.items():
+        kind, S, hop, reassign, form, R, n, split = have
+        changes = [(kind, S + 1, hop, reassign, form, R, n, split), (kind, S, hop // 2, reassign, form, R, n, split),
+                   (kind, S, hop, 0, form, R, n, split), (kind, S, hop, reassign, 1, R, n, split),
+                   (kind, S, hop, reassign, form, R, [8192] + n[1:], split)]
+        if len(n) > 1:
+            changes += [(kind, S, hop, reassign, form, R, n[:-1] + [1024], split), (kind, S, hop, reassign, form, R, n, [split[0] - 4] + split[1:]),
+                        (kind, S, hop, reassign, form, R, n, split[:-1] + [split[-1] + 64])]
+        for ask in changes:
+            pairs.append(line(have, ask))
+            want.append(CHANGED[kind])
+    got = driver("compat", pairs)
+    assert [x["why"] for x in got] == want, [(p, x["why"], w) for p, x, w in zip(pairs, got, want) if x["why"] != w]
