@@ -44,6 +44,22 @@ inline const char* band_split_error(int bands, const int32_t* split, int rows) {
     return nullptr;
 }
 
+// The two-band form (emspec_batch_multires*, the *_multires live entries) keeps narrower rules and messages of its
+// own; whatever they accept, band_shape_error(2, ...) and band_split_error(2, ...) accept too (tests/test_band_plan_cpu.py).
+// null when (n_low, n_high, hop) is an accepted shape, else the rule it breaks
+inline const char* multires_shape_error(int n_low, int n_high, int hop) {
+    if (n_low != 8192 && n_low != 16384) return "n_low must be 8192 or 16384";
+    if (n_high != 1024 && n_high != 2048 && n_high != 4096) return "n_high must be 1024, 2048 or 4096";
+    if (hop < 1 || hop > n_high) return "hop must be in [1, n_high]";
+    if ((n_low - n_high) % (2 * hop)) return "(n_low - n_high) / (2 hop) must be an integer";
+    return nullptr;
+}
+// null when split_row cuts [0, rows) into two accepted bands, else the rule it breaks
+inline const char* multires_split_error(int split_row, int rows) {
+    if (split_row % 4 || split_row < 64 || split_row > rows - 64) return "split_row must be a multiple of 4 in [64, rows - 64]";
+    return nullptr;
+}
+
 // The bands of an accepted call: band k owns rows [lo[k], hi[k]) and takes column c + shift[k] of single(n[k]).
 struct BandPlan {
     int bands = 0;

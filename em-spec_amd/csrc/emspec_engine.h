@@ -20,7 +20,7 @@ namespace emspec {
 struct Plan {
     int n = 0;
     // the rows this plan serves: the engine's whole table (row0 = 0, rows = cfg.rows), or a band of it for the
-    // multi-resolution batch (emspec_multires.cpp) - h_ebin / d_ebin (/ h_ebin64, d_ebin64) are then that slice of the
+    // multi-resolution and multi-band batches (emspec_multiband.cpp) - h_ebin / d_ebin (/ h_ebin64, d_ebin64) are then that slice of the
     // full table, and d_tw / d_tw64 belong to the full plan of the same n
     int row0 = 0, rows = 0;
     float2* d_tw = nullptr;
@@ -154,8 +154,8 @@ int pcm_frame_bytes(const emspec_pcm_format& f);
 // the decode kernel (pcm.hip.inc) for a valid format
 hipError_t pcm_decode(const void* src, const emspec_pcm_format& f, int sources, int64_t frames, int64_t src_stride_bytes, float* out,
                       int64_t out_stride, hipStream_t st);
-// emspec_multires.cpp: what the multi-resolution batch and the multi-resolution live session accept
-const char* multires_shape_error(int n_low, int n_high, int hop);   // null, or the rule the shape breaks
+// emspec_multiband.cpp: what the multi-resolution batch and the multi-resolution live session accept (the rules and their messages:
+// emspec_band_plan.h)
 int multires_check(emspec_engine* e, int32_t S, int32_t n_low, int32_t n_high, int32_t hop, int32_t split_row);
 void live_destroy(emspec_engine* e);   // emspec_live.cpp: called by emspec_destroy
 void live_reset(emspec_engine* e);     // drops the live session's stream state (emspec_reset); buffers are kept
@@ -216,7 +216,7 @@ struct emspec_engine {
     float* d_raw = nullptr; size_t raw_bytes = 0;      // raw dB columns of a batch
     float* d_post = nullptr; size_t post_bytes = 0;    // post-processed dB when the caller wants none
     float* d_peak = nullptr; size_t peak_bytes = 0;    // column peaks + gains
-    // multi-resolution batch (emspec_multires.cpp): both bands' raw dB (+ the composed raw dB for the post-process)
+    // multi-resolution and multi-band batches (emspec_multiband.cpp): the bands' raw dB (+ the composed raw dB for the post-process)
     float* d_mres = nullptr; size_t mres_bytes = 0;
     // time reduction (emspec_set_time_reduce): the factor, and the device entries' full-rate columns of a chunk
     // of streams (dB and / or palette index), which reduce.hip.inc's kernel collapses into the caller's arrays

@@ -132,12 +132,8 @@ hipError_t launch_fused(int n, const PlanDev& pl, const DbMap& m, const uint8_t*
 hipError_t launch_postprocess(const float* db, float* out_db, uint8_t* rgba, uint8_t* index, int S, int64_t C, int R,
                               float sm, float agc, float db_top, const DbMap& dm, const uint8_t* lut, float* peak,
                               float* gain, hipStream_t st);
-// multi-resolution batch (multires.hip.inc): [S][C][split] low-band and [S][C + 2 shift][R - split] high-band raw dB -> the
-// composed columns [S][C][R]: dB and / or palette index and RGBA (any output null)
-hipError_t launch_multires_compose(const float* lo, const float* hi, int S, int64_t C, int R, int split, int shift,
-                                   const DbMap& dm, const uint8_t* lut, float* db, uint8_t* rgba, uint8_t* index,
-                                   hipStream_t st);
-// multi-band batch (multiband.hip.inc): up to kMaxBands bands' raw dB -> the composed columns [S][C][R], outputs as above.  Band k's
+// multi-band batch, the multi-resolution batch being its two-band case (multiband.hip.inc): up to kMaxBands bands' raw dB -> the
+// composed columns [S][C][R]: dB and / or palette index and RGBA (any output null).  Band k's
 // plane is [S][C + 2 shift[k]][rows[k]] and serves the quads of rows from q0[k] on, up to the next band's q0; an unused slot has
 // q0 = R / 4 (no quad reaches it) and any valid plane
 struct BandSrc {

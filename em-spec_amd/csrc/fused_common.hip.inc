@@ -1,6 +1,6 @@
 // fused_common.hip.inc — the straight-line arithmetic every batch kernel runs between its FFT and the output arrays, stated
 // once.  Included by kernels.hip before the first kernel that scatters or finalises (the tile / walk scatter, then
-// fused.hip.inc, post.hip.inc, multires.hip.inc).  A file of its own rather than a section of emspec_device.h: that header is
+// fused.hip.inc, post.hip.inc, multiband.hip.inc).  A file of its own rather than a section of emspec_device.h: that header is
 // also the EXACT-mode and live kernels', which use none of this, and these helpers know the fused kernels' ring layout.
 //
 // The kernels differ in their SCHEDULE (who runs which FFT pass when, barriers, s_setprio points, where the ring lives) and

@@ -603,7 +603,6 @@ hipError_t launch_occupy(int groups, int usec, unsigned* sink, hipStream_t st) {
 
 #include "fused.hip.inc"
 #include "post.hip.inc"
-#include "multires.hip.inc"
 #include "multiband.hip.inc"
 #include "pack.hip.inc"
 #include "reduce.hip.inc"

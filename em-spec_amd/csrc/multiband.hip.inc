@@ -1,5 +1,5 @@
 // multiband.hip.inc — the composition stage of the multi-band batch (DESIGN.md §3.13, §4.14; emspec_multiband.cpp): up to four
-// bands' raw dB, each of its own FFT size, stitched on the longest FFT's column grid.  Included by kernels.hip after multires.hip.inc.
+// bands' raw dB, each of its own FFT size, stitched on the longest FFT's column grid.  Included by kernels.hip after post.hip.inc.
 namespace emspec {
 
 // One wave per (stream, column), grid-stride over S * C of them.  Band k's plane is [S][C + 2 shift[k]][rows_k] raw dB; column c takes

@@ -1,12 +1,14 @@
 // band_plan_driver.cpp — prints, for a list of cases, what the multi-band batch accepts and how it lays out its workspace
 // (em-spec_amd/csrc/emspec_band_plan.h), as a JSON list with one object per case: the rule a shape breaks or its shifts, row ranges
-// and plane offsets, without a GPU.
+// and plane offsets, without a GPU.  With the argument "two": the two-band rules (multires_shape_error, multires_split_error) beside
+// the K = 2 answers of the multi-band ones over a grid of shapes and every split row, one object per shape.
 //   g++ -std=c++17 -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -I em-spec_amd/csrc
 //       tests/cdriver/band_plan_driver.cpp -o band_plan_driver
 // tests/test_band_plan_cpu.py checks the output against a numpy restatement of the rules.
 #include "emspec_band_plan.h"
 
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 using namespace emspec;
@@ -52,9 +54,53 @@ void run_case(std::vector<int32_t> n, int hop, std::vector<int32_t> split, int r
            (long long)w.chunk_offset(K, chunk), (long long)w.per_stream, (long long)w.chunk_bytes(chunk), (long long)kBandPad);
 }
 
+void text(const char* s) { s ? printf("\"%s\"", s) : printf("null"); }
+
+// What the two-band entries hand to band_plan after their own rules.  Per shape: both shape answers; when the two-band rules take the
+// shape, per (rows, split) "cells": [rows, split, two-band answer, multi-band answer] and, where the two-band rule takes the split,
+// behind them shift[0], shift[1], lo[0], hi[0], lo[1], hi[1] and band_layout's per_stream without / with the raw plane at C columns.
+void two_band_sweep() {
+    const int sizes[] = {1024, 2048, 4096, 8192, 16384}, hops[] = {1, 64, 128, 256, 512, 1024, 4096, 4097};
+    const int row_counts[] = {128, 256, 1024, 1000};
+    const long long C = 373;
+    printf("{\"C\": %lld, \"shapes\": [", C);
+    bool first_shape = true;
+    for (int n_low : sizes)
+        for (int n_high : sizes)
+            for (int hop : hops) {
+                const int32_t n[2] = {n_low, n_high};
+                const char* two = multires_shape_error(n_low, n_high, hop);
+                printf("%s\n{\"n_low\": %d, \"n_high\": %d, \"hop\": %d, \"two\": ", first_shape ? "" : ",", n_low, n_high, hop);
+                first_shape = false;
+                text(two), printf(", \"band\": "), text(band_shape_error(2, n, hop)), printf(", \"cells\": [");
+                bool first = true;
+                for (int rows : row_counts) {
+                    if (two) break;
+                    std::vector<int32_t> splits;
+                    for (int s = 0; s <= rows; s += 4) splits.push_back(s);
+                    for (int s : {-4, 1, 62, 66, 367, rows - 62, rows - 1, rows + 4}) splits.push_back(s);
+                    for (int32_t split : splits) {
+                        const char* why = multires_split_error(split, rows);
+                        printf("%s[%d, %d, ", first ? "" : ", ", rows, split);
+                        first = false;
+                        text(why), printf(", "), text(band_split_error(2, &split, rows));
+                        if (!why) {
+                            const BandPlan p = band_plan(2, n, &split, hop, rows);
+                            printf(", %d, %d, %d, %d, %d, %d, %lld, %lld", p.shift[0], p.shift[1], p.lo[0], p.hi[0], p.lo[1], p.hi[1],
+                                   (long long)band_layout(p, C, rows, false).per_stream, (long long)band_layout(p, C, rows, true).per_stream);
+                        }
+                        printf("]");
+                    }
+                }
+                printf("]}");
+            }
+    printf("\n]}\n");
+}
+
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc > 1 && !strcmp(argv[1], "two")) return two_band_sweep(), 0;
     const long long L = 1 << 17;
     // ---- accepted ----
     for (int post = 0; post < 2; ++post)

@@ -11,16 +11,16 @@ a header states to that header through tests/cdriver/chunk_plan_driver.cpp.
     d_hist     EXACT records (run_columns_exact)   C (n/2 + 4) 12         exact_record_bytes, emspec_kernel_plan.h  kChunkPad
     d_full     time reduction (reduce_streams)     [dB] C R 4 + [index or RGBA] C R      emspec_api.cpp:527-528     kChunkPad
     d_full     emspec_batch_peaks_device           C R 4                                 emspec_peaks.cpp:118       256
-    d_mres     two-band batch (multires_run)       C split 4 + Ch (R - split) 4 + [post] C R 4   emspec_multires.cpp:54, 61   1024
+    d_mres     two-band batch (multiband_run)      C split 4 + Ch (R - split) 4 + [post] C R 4   band_layout at K = 2   kBandPad
     d_mres     multi-band batch (multiband_run)    band_layout(...).per_stream           emspec_band_plan.h         kBandPad
 
-The three sizes that live in .cpp files cannot be reached from a header; they are cited by line above, and the budgets a GPU test
-uses (budget_for) leave a margin of 10 % around them.  Lives under tests/ (like multires_ref.py); the product never imports it."""
+The two sizes that live in .cpp files cannot be reached from a header; they are cited by line above, and the budgets a GPU test
+uses (budget_for) leave a margin of 10 % around them.  multires_bytes stays as the two-band row's own restatement: the CPU tests
+compare band_layout at K = 2 against it (tests/test_band_plan_cpu.py, tests/test_chunk_ref_cpu.py).  Lives under tests/ (like multires_ref.py); the product never imports it."""
 
 CHUNK_PAD = 256      # kChunkPad
 BAND_PAD = 1024      # kBandPad = 256 * kMaxBands
 PEAKS_PAD = 256
-MULTIRES_PAD = 1024
 FLOOR_MB = 256       # the unbudgeted rule never goes below 256 MiB
 
 

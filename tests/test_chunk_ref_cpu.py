@@ -2,9 +2,9 @@
 from - says what the HIP-free headers say (em-spec_amd/csrc/emspec_kernel_plan.h, emspec_band_plan.h).  A stand-alone program
 (tests/cdriver/chunk_plan_driver.cpp, built with the host compiler under ASan and UBSan) answers one line per question:
 f32_record_bytes, exact_record_bytes, first_chunk / next_chunk, second_array_offset, kChunkPad, band_plan + band_layout + kBandPad -
-for a few dozen argument sets of its own and for every workspace of every case of the GPU file.  The three per-stream sizes that
-live in .cpp files (time reduction, peaks, two-band) cannot be reached this way: chunk_ref cites their lines, and the GPU cases'
-budgets keep 10 % of margin around them, which is checked here."""
+for a few dozen argument sets of its own and for every workspace of every case of the GPU file (the two-band batch's: band_layout
+at K = 2).  The two per-stream sizes that live in .cpp files (time reduction, peaks) cannot be reached this way: chunk_ref cites
+their lines, and the GPU cases' budgets keep 10 % of margin around them, which is checked here."""
 import json
 import os
 import subprocess

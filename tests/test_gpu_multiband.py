@@ -17,6 +17,7 @@ import torch
 
 import emspec
 import multiband_ref as B
+import multires_ref as M
 import oracle as O
 import overview_ref as V
 import wave_ref as W
@@ -139,18 +140,20 @@ def test_exact_equals_the_engines_own_stitch_host_pinned_and_device():
             assert _same(dev[k], want[k]), ("device", k)
 
 
-# ---- 3. K = 2 is emspec_batch_multires
+# ---- 3. K = 2 is emspec_batch_multires: both go through one run function, so both are held to the two-band bit model
 @pytest.mark.parametrize("n_low,n_high,hop", [(16384, 4096, 256), (8192, 2048, 128)])
 def test_two_bands_equal_the_two_band_batch(n_low, n_high, hop):
     pcm = _pcm(3)
     with emspec.Engine(mode=emspec.MODE_EXACT) as e:
         split = e.split_row_for_hz(250.0)
-        want = e.batch_multires(pcm, n_low, n_high, hop, split, True, want=WANT)
+        two = e.batch_multires(pcm, n_low, n_high, hop, split, True, want=WANT)
         got = e.batch_multiband(pcm, (n_low, n_high), (split,), hop, True, want=WANT)
         dev = _device(e, _cuda(pcm), (n_low, n_high), (split,), hop)
+    want = M.compose(pcm, n_low, n_high, hop, split, True, exact=True)
     for k in WANT:
         assert _same(got[k], want[k]), ("host", k)
         assert _same(dev[k], want[k]), ("device", k)
+        assert _same(two[k], want[k]), ("batch_multires", k)
 
 
 # ---- 4. FAST within the project's tolerances

@@ -2,6 +2,7 @@
 single-resolution images (tests/multires_ref.py) - and what it is for: two bass notes 7.8 Hz apart separate in the long
 FFT's rows while clicks keep their column in the short FFT's rows."""
 import ctypes as C
+import functools
 import json
 import os
 import shutil
@@ -14,6 +15,7 @@ import torch
 import emspec
 import multires_ref as M
 import oracle as O
+import overview_ref as V
 from emspec import synth
 
 pytestmark = pytest.mark.gpu
@@ -147,6 +149,51 @@ def test_fast_within_the_design_tolerances(n_low, n_high, hop, L, boost):
     print(f"multires FAST {n_low}/{n_high}/{hop}: max dB err {err:.2e}, index off-by-one share {share:.2e}")
     assert di.max() <= 1 and share <= FAST_INDEX_SHARE[(n_low, n_high, hop)], (int(di.max()), share)
     assert np.array_equal(got["rgba"], O.default_lut()[got["index"]])
+
+
+SEAM = (8192, 1024, 512, 3, 1 << 15)   # n_low, n_high, hop, S, L: shift 7, 49 composed columns from 63 of the high band
+
+
+@functools.lru_cache(maxsize=None)
+def _seam_ref(split):
+    """The bit model's composition at a split row, computed once and shared (read-only)."""
+    n_low, n_high, hop, S, L = SEAM
+    out = M.compose(synth.streams(S, L), n_low, n_high, hop, split, True, exact=True)
+    for v in out.values():
+        v.setflags(write=False)
+    return out
+
+
+def _seam_device(e, x, split):
+    """The device entry at the engine's time reduction -> numpy arrays [S][Cr][R] (+[4])."""
+    n_low, n_high, hop, S, L = SEAM
+    Cr = emspec.reduced_columns(emspec.multires_columns(L, n_low, n_high, hop), e.time_reduce)
+    t = {"db": torch.full((S, Cr, e.rows), -1.0, dtype=torch.float32, device="cuda"),
+         "rgba": torch.full((S, Cr, e.rows, 4), 0x5A, dtype=torch.uint8, device="cuda"),
+         "index": torch.full((S, Cr, e.rows), 0x5A, dtype=torch.uint8, device="cuda")}
+    e.batch_multires_device(x, n_low, n_high, hop, split, True, **t)
+    torch.cuda.synchronize()
+    e.device_status()
+    return {k: v.cpu().numpy() for k, v in t.items()}
+
+
+@pytest.mark.parametrize("where,f", [("lowest", 1), ("highest", 1), ("lowest", 4)], ids=["split-64", "split-rows-64", "split-64-reduce-4"])
+def test_the_seam_at_the_limits_of_the_two_band_rules(where, f):
+    """split_row = 64 and rows - 64, the narrowest bands the two-band rules let through to the band plan: the device and the host
+    entry give the bit model's composition byte for byte; at split_row = 64 under time reduction 4, overview_ref of it."""
+    n_low, n_high, hop, S, L = SEAM
+    pcm = synth.streams(S, L)
+    assert emspec.multires_shift(n_low, n_high, hop) == 7
+    with emspec.Engine(mode=emspec.MODE_EXACT) as e:
+        split = 64 if where == "lowest" else e.rows - 64
+        e.set_time_reduce(f)
+        dev = _seam_device(e, torch.from_numpy(pcm).cuda(), split)
+        got = e.batch_multires(pcm, n_low, n_high, hop, split, True, want=WANT)
+    want = _seam_ref(split) if f == 1 else V.reduce(_seam_ref(split), f, O.default_lut())
+    assert want["db"].shape == (S, -(-49 // f), 1024)
+    for k in WANT:
+        assert _same(dev[k], want[k]), ("device", k)
+        assert _same(got[k], want[k]), ("host", k)
 
 
 @pytest.mark.parametrize("exact", [False, True], ids=["fast", "exact"])
