@@ -65,6 +65,12 @@ struct LiveState {
     void* d_wring = nullptr; size_t wring_bytes = 0;
     void* h_opeaks = nullptr; size_t opeaks_bytes = 0;
     void* h_owave = nullptr; size_t owave_bytes = 0;
+    // live level meters (emspec_set_live_level / emspec_set_live_cross), as the envelope's: the record rings [S][wslots] x 24 bytes
+    // and [S / views][wslots] x 16 bytes, page-locked staging of pageable outputs [S][cols] / [S / views][cols] records
+    void* d_lring = nullptr; size_t lring_bytes = 0;
+    void* d_xring = nullptr; size_t xring_bytes = 0;
+    void* h_olevel = nullptr; size_t olevel_bytes = 0;
+    void* h_ocross = nullptr; size_t ocross_bytes = 0;
     // live history (emspec_set_live_history; live_history.hip.inc, emspec_history_plan.h), allocated by the first call of the
     // session while a history is set: the ring [S][W][rows] float32 and, for the view kernel, the columns each stream has
     // emitted [S] (written by the store kernel; the host's own count is c.emitted).  view_done: recorded behind a device view
@@ -232,6 +238,10 @@ struct emspec_engine {
     // arrays (null: off) and their capacities in pairs
     emspec_peak* live_peaks = nullptr; int64_t live_peaks_capacity = 0; int live_peaks_k = 0; float live_peaks_min_db = 0.0f;
     emspec_wave* live_wave = nullptr; int64_t live_wave_capacity = 0;
+    // ... and their level meters (emspec_set_live_level / emspec_set_live_cross): capacities in records; a pair of the cross is
+    // streams p live_cross_views + live_cross_a and + live_cross_b of a session
+    emspec_level* live_level = nullptr; int64_t live_level_capacity = 0;
+    emspec_cross* live_cross = nullptr; int64_t live_cross_capacity = 0; int live_cross_views = 1, live_cross_a = 0, live_cross_b = 0;
     // live history (emspec_set_live_history; emspec_history.cpp): W columns per stream of both sessions below (0: off), and the
     // page-locked staging blocks of a host view's pageable outputs (dB, index, RGBA)
     int64_t history_W = 0;

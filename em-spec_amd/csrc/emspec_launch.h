@@ -8,6 +8,7 @@
 #include "emspec_history_plan.h"
 #include "emspec_live_plan.h"
 #include "emspec_stereo_plan.h"
+#include "emspec_window_plan.h"
 #include "emspec_wire_plan.h"
 
 namespace emspec {
@@ -160,7 +161,7 @@ struct LiveBandRings {
 hipError_t launch_live_finalize_bands(bool exact, const LiveSinks& lv, const LiveBandRings& r, int D, int S, int ncol, hipStream_t st);
 hipError_t launch_live_post(const LiveSinks& lv, const float* raw, int raw_cols, int rows, int D, float sm, float agc, float db_top,
                             const DbMap& dm, float* pstate, int S, hipStream_t st);
-// The overlays of a live launch (live_overlay.hip.inc; emspec_set_live_peaks / emspec_set_live_wave): one kernel behind the
+// The overlays of a live launch (live_overlay.hip.inc; emspec_set_live_peaks / _wave / _level / _cross): one kernel behind the
 // launch's last kernel, on the same descriptors.  lv.out_db / lv.out_cols: the CALLER's dB destination and the stride of every
 // block below; `units`: the most frames (flush form: columns) any stream has in the launch.
 struct LiveOverlay {
@@ -175,6 +176,14 @@ struct LiveOverlay {
     uint2* wring = nullptr;
     int wslots = 0, hop = 0, off = 0;
     int D = 0;   // latency of the emitted column
+    // level meters (level / cross == null: off), over the envelope's samples: level [S][out_cols] records and their ring
+    // [S][wslots]; cross [S / views][out_cols] records of the streams p views + a and p views + b, their ring [S / views][wslots].
+    // With either set, wslots / hop / off are read as for the envelope, and S is a multiple of views.
+    emspec_level* level = nullptr;
+    emspec_level* lring = nullptr;
+    emspec_cross* cross = nullptr;
+    emspec_cross* xring = nullptr;
+    int views = 1, a = 0, b = 0;
 };
 hipError_t launch_live_overlay(const LiveSinks& lv, const LiveOverlay& ov, int S, int units, hipStream_t st);
 // The live history (live_history.hip.inc; emspec_set_live_history; geometry: emspec_history_plan.h).  The store: one kernel

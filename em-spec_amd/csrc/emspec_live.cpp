@@ -113,19 +113,21 @@ int live_post_buffers(emspec_engine* e, LiveState& lv) {
 // dst_peaks / dst_wave: the overlays' device-visible destinations ([S][out_cols][k] and [S][out_cols] pairs; null: off) - the
 // overlay kernel goes behind the launch's last kernel.  While peaks are wanted the delivered dB goes to a device block laid out
 // like the destination (d_raw, or d_pdb behind the post kernel) and the overlay kernel writes dst_db from its copy of it.
+// dst_level / dst_cross: the level meters' destinations ([S][out_cols] and [S / views][out_cols] records; null: off), written by
+// the same overlay kernel from the envelope's samples.
 // While a history is set (emspec_set_live_history) the delivered dB takes the same way, and the store kernel (live_history.hip.inc)
 // goes behind the launch too: it copies every delivered column into the session's ring and, without peaks, writes dst_db.
 // While an audio history is set (emspec_set_live_audio) the audio store kernel (live_audio.hip.inc) goes last.
 int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fresh_stride, int mlaunch, bool flush, float* dst_db,
                 uint8_t* dst_rgba, int out_cols, int raw_cols, bool empty_col, emspec_peak* dst_peaks = nullptr,
-                emspec_wave* dst_wave = nullptr) {
+                emspec_wave* dst_wave = nullptr, emspec_level* dst_level = nullptr, emspec_cross* dst_cross = nullptr) {
     int rc;
     const LiveGeometry& g = lv.ss.g;
     const int R = e->cfg.rows;
     const bool post = e->smoothing > 0.0f || e->agc > 0.0f;
     if (post && (rc = live_post_buffers(e, lv))) return rc;
     // (a launch without a frame - one that only moves samples into the ring - completes no column: no overlay)
-    const bool overlay = (dst_peaks || dst_wave) && (flush || mlaunch > 0), peaks = overlay && dst_peaks;
+    const bool overlay = (dst_peaks || dst_wave || dst_level || dst_cross) && (flush || mlaunch > 0), peaks = overlay && dst_peaks;
     const bool hist = e->history_W > 0 && (flush || mlaunch > 0);
     const bool devdb = peaks || hist;   // the delivered dB goes to a device block first
     if (devdb) {
@@ -133,6 +135,8 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
         if (post ? (rc = grow(e, (void**)&lv.d_pdb, &lv.pdb_bytes, want)) : (rc = grow(e, (void**)&lv.d_raw, &lv.raw_bytes, want))) return rc;
     }
     if (overlay && dst_wave && (rc = grow(e, &lv.d_wring, &lv.wring_bytes, live_wave_ring_bytes(g)))) return rc;
+    if (overlay && dst_level && (rc = grow(e, &lv.d_lring, &lv.lring_bytes, live_level_ring_bytes(g)))) return rc;
+    if (overlay && dst_cross && (rc = grow(e, &lv.d_xring, &lv.xring_bytes, live_cross_ring_bytes(g, e->live_cross_views)))) return rc;
     LiveSinks ls;
     ls.streams = lv.desc();
     ls.fresh = fresh;
@@ -260,6 +264,17 @@ int live_launch(emspec_engine* e, LiveState& lv, const float* fresh, int64_t fre
         if (dst_wave) {
             ov.wave = reinterpret_cast<uint2*>(dst_wave);
             ov.wring = reinterpret_cast<uint2*>(lv.d_wring);
+        }
+        if (dst_level) {
+            ov.level = dst_level;
+            ov.lring = static_cast<emspec_level*>(lv.d_lring);
+        }
+        if (dst_cross) {
+            ov.cross = dst_cross;
+            ov.xring = static_cast<emspec_cross*>(lv.d_xring);
+            ov.views = e->live_cross_views; ov.a = e->live_cross_a; ov.b = e->live_cross_b;
+        }
+        if (dst_wave || dst_level || dst_cross) {   // the sample reducers' shared geometry
             ov.wslots = live_wave_slots(g);
             ov.hop = g.hop;
             ov.off = live_wave_offset(g);
@@ -315,6 +330,11 @@ struct LiveDest {
     emspec_peak* peaks = nullptr;
     emspec_wave* wave = nullptr;
     bool stage_peaks = false, stage_wave = false;
+    // ... and the level meters (emspec_set_live_level / emspec_set_live_cross)
+    emspec_level* level = nullptr;
+    emspec_cross* cross = nullptr;
+    bool stage_level = false, stage_cross = false;
+    bool staged() const { return stage_db || stage_rgba || stage_peaks || stage_wave || stage_level || stage_cross; }
 };
 // (the overlay kernel stores whole pairs: a page-locked array that is not 8-byte aligned is staged like a pageable one)
 void* device_view8(const void* p) { return reinterpret_cast<uintptr_t>(p) % 8 ? nullptr : device_view(p); }
@@ -325,14 +345,19 @@ int live_dest(emspec_engine* e, LiveState& lv, float* out_db, uint8_t* out_rgba,
     d.rgba = reinterpret_cast<uint8_t*>(device_view(out_rgba));
     d.peaks = reinterpret_cast<emspec_peak*>(device_view8(e->live_peaks));
     d.wave = reinterpret_cast<emspec_wave*>(device_view8(e->live_wave));
+    d.level = reinterpret_cast<emspec_level*>(device_view8(e->live_level));
+    d.cross = reinterpret_cast<emspec_cross*>(device_view8(e->live_cross));
     d.stage_db = out_db && !d.db;
     d.stage_rgba = out_rgba && !d.rgba;
     d.stage_peaks = e->live_peaks && !d.peaks;
     d.stage_wave = e->live_wave && !d.wave;
-    d.direct = !d.stage_db && !d.stage_rgba && !d.stage_peaks && !d.stage_wave && in_place_ok;
+    d.stage_level = e->live_level && !d.level;
+    d.stage_cross = e->live_cross && !d.cross;
+    d.direct = !d.staged() && in_place_ok;
     if (together && !d.direct) {
         d.stage_db = out_db != nullptr; d.stage_rgba = out_rgba != nullptr; d.db = nullptr; d.rgba = nullptr;
         d.stage_peaks = e->live_peaks != nullptr; d.stage_wave = e->live_wave != nullptr;
+        d.stage_level = e->live_level != nullptr; d.stage_cross = e->live_cross != nullptr;
     }
     const size_t bytes = lv.ss.g.out_bytes(e->cfg.rows, cols);
     int rc;
@@ -340,6 +365,10 @@ int live_dest(emspec_engine* e, LiveState& lv, float* out_db, uint8_t* out_rgba,
     if (d.stage_wave && (rc = pinned_grow(e, &lv.h_owave, &lv.owave_bytes, live_wave_bytes(lv.ss.g, cols)))) return rc;
     if (d.stage_peaks) d.peaks = reinterpret_cast<emspec_peak*>(lv.h_opeaks);
     if (d.stage_wave) d.wave = reinterpret_cast<emspec_wave*>(lv.h_owave);
+    if (d.stage_level && (rc = pinned_grow(e, &lv.h_olevel, &lv.olevel_bytes, live_level_bytes(lv.ss.g, cols)))) return rc;
+    if (d.stage_cross && (rc = pinned_grow(e, &lv.h_ocross, &lv.ocross_bytes, live_cross_bytes(lv.ss.g, e->live_cross_views, cols)))) return rc;
+    if (d.stage_level) d.level = reinterpret_cast<emspec_level*>(lv.h_olevel);
+    if (d.stage_cross) d.cross = reinterpret_cast<emspec_cross*>(lv.h_ocross);
     if (d.stage_db && (rc = pinned_grow(e, (void**)&lv.h_odb, &lv.odb_bytes, bytes))) return rc;
     if (d.stage_rgba && (rc = pinned_grow(e, (void**)&lv.h_orgba, &lv.orgba_bytes, bytes))) return rc;
     if (d.stage_db) d.db = lv.h_odb;
@@ -349,7 +378,8 @@ int live_dest(emspec_engine* e, LiveState& lv, float* out_db, uint8_t* out_rgba,
 // The staged columns to the caller.  p == null: one column per stream, [S][rows] (emspec_columns, the flush); else the round's
 // columns of a push: p->nc[s] columns of stream s, from the front of its mmax staged columns to column p->produced[s] of its
 // max_columns.
-// The staged overlays go the same way, k pairs and one pair per column, to the arrays the engine's settings name.
+// The staged overlays go the same way - k pairs, one pair, one level record per stream and column, one cross record per pair of
+// streams and column (a pair's streams are in step: channel a's counts are the pair's) - to the arrays the engine's settings name.
 void live_copy_back(const emspec_engine* e, const LiveState& lv, const LiveDest& d, float* out_db, uint8_t* out_rgba, int R,
                     const LivePush* p = nullptr, int64_t max_columns = 1) {
     const int k = e->live_peaks_k;
@@ -358,6 +388,8 @@ void live_copy_back(const emspec_engine* e, const LiveState& lv, const LiveDest&
         if (d.stage_rgba) std::memcpy(out_rgba, lv.h_orgba, lv.ss.g.out_bytes(R, 1));
         if (d.stage_peaks) std::memcpy(e->live_peaks, lv.h_opeaks, live_peaks_bytes(lv.ss.g, 1, k));
         if (d.stage_wave) std::memcpy(e->live_wave, lv.h_owave, live_wave_bytes(lv.ss.g, 1));
+        if (d.stage_level) std::memcpy(e->live_level, lv.h_olevel, live_level_bytes(lv.ss.g, 1));
+        if (d.stage_cross) std::memcpy(e->live_cross, lv.h_ocross, live_cross_bytes(lv.ss.g, e->live_cross_views, 1));
         return;
     }
     for (int s = 0; s < lv.ss.g.S; ++s) {
@@ -370,6 +402,13 @@ void live_copy_back(const emspec_engine* e, const LiveState& lv, const LiveDest&
             std::memcpy(e->live_peaks + pto * k, reinterpret_cast<const emspec_peak*>(lv.h_opeaks) + pfrom * k, (size_t)p->nc[s] * k * sizeof(emspec_peak));
         if (d.stage_wave)
             std::memcpy(e->live_wave + pto, reinterpret_cast<const emspec_wave*>(lv.h_owave) + pfrom, (size_t)p->nc[s] * sizeof(emspec_wave));
+        if (d.stage_level)
+            std::memcpy(e->live_level + pto, reinterpret_cast<const emspec_level*>(lv.h_olevel) + pfrom, (size_t)p->nc[s] * sizeof(emspec_level));
+        if (d.stage_cross && s % e->live_cross_views == e->live_cross_a) {
+            const int pr = s / e->live_cross_views;
+            std::memcpy(e->live_cross + live_overlay_pair(max_columns, pr, p->produced[s]),
+                        reinterpret_cast<const emspec_cross*>(lv.h_ocross) + live_overlay_pair(lv.ss.g.mmax, pr, 0), (size_t)p->nc[s] * sizeof(emspec_cross));
+        }
     }
 }
 }  // namespace
@@ -413,14 +452,36 @@ int live_pcm_drain(emspec_engine* e, LiveState& lv) {
 
 // ---- the calls, on one of the engine's two sessions ----
 
-// the overlays' capacity rule: a call that delivers [S][cols][rows] writes S cols k peaks and S cols envelope pairs
-int live_overlay_check(emspec_engine* e, int S, int64_t cols) {
+// the overlays' capacity rule: a call that delivers [S][cols][rows] writes S cols k peaks, S cols envelope pairs, S cols level
+// records and (S / views) cols cross records - and a session whose streams are no multiple of `views` has no pairs
+int live_overlay_check(emspec_engine* e, const LiveState& lv, int S, int64_t cols) {
     if (e->live_peaks && !live_overlay_fits(S, cols, e->live_peaks_k, e->live_peaks_capacity))
         return fail(e, EMSPEC_ERR_INVALID_ARG, "the array set with emspec_set_live_peaks is too small: the call needs streams x columns x k pairs");
     if (e->live_wave && !live_overlay_fits(S, cols, 1, e->live_wave_capacity))
         return fail(e, EMSPEC_ERR_INVALID_ARG, "the array set with emspec_set_live_wave is too small: the call needs streams x columns pairs");
+    if (e->live_level && !live_overlay_fits(S, cols, 1, e->live_level_capacity))
+        return fail(e, EMSPEC_ERR_INVALID_ARG, "the array set with emspec_set_live_level is too small: the call needs streams x columns records");
+    if (e->live_cross) {
+        if (const char* why = live_cross_error(S, e->live_cross_views)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
+        // (an open session whose streams emspec_reset_stream moved apart before the setting arrived)
+        if (lv.c.streams() == S && !live_pairs_in_step(lv.c, e->live_cross_views, e->live_cross_a, e->live_cross_b))
+            return fail(e, EMSPEC_ERR_STATE, "the streams of a pair are out of step (emspec_reset_stream before emspec_set_live_cross); call emspec_reset() first");
+        if (!live_overlay_fits(live_cross_pairs(S, e->live_cross_views), cols, 1, e->live_cross_capacity))
+            return fail(e, EMSPEC_ERR_INVALID_ARG, "the array set with emspec_set_live_cross is too small: the call needs pairs x columns records");
+    }
     return EMSPEC_OK;
 }
+
+// some stream of either session has frames fed: the overlays that are taken when a frame arrives (the envelope, the level and
+// cross records) cannot start - their columns still to come would lack what earlier frames left
+bool live_fed(const emspec_engine* e) {
+    for (const LiveState* lv : {&e->live, &e->one})
+        for (int s = 0; s < lv->c.streams(); ++s)
+            if (lv->ss.g.form != 0 && lv->c.fed[s] > 0) return true;
+    return false;
+}
+
+static_assert(sizeof(emspec_level) == kLiveLevelRecord && sizeof(emspec_cross) == kLiveCrossRecord, "the rings' record sizes (emspec_live_plan.h)");
 
 // the time reduction (emspec_set_time_reduce) serves the batch entries only: every streaming call refuses while it is on
 const char* const kNoLiveReduce = "the streaming calls return full-rate columns: not available while a time reduction is set (emspec_set_time_reduce(e, 1) turns it off)";
@@ -433,7 +494,7 @@ int columns_impl(emspec_engine* e, LiveState& lv, const float* frames, const Liv
     if (!e || !frames) return fail(e, EMSPEC_ERR_INVALID_ARG, "null argument");
     int rc = live_check(e, lv, ask, rows);
     if (rc) return rc;
-    if ((rc = live_overlay_check(e, ask.S, 1))) return rc;
+    if ((rc = live_overlay_check(e, lv, ask.S, 1))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     const bool opened = lv.ss.g.form == 0;
     if (opened && (rc = live_open(e, lv, ask))) return rc;
@@ -449,7 +510,7 @@ int columns_impl(emspec_engine* e, LiveState& lv, const float* frames, const Liv
     LiveDest d;   // (one column per stream: each output in place or staged on its own)
     if ((rc = live_dest(e, lv, out_db, out_rgba, 1, d))) return rc;
     live_frame_fill(lv.ss.g, lv.c, lv.desc());
-    if ((rc = live_launch(e, lv, src, lv.ss.g.n, 1, false, d.db, d.rgba, 1, 1, true, d.peaks, d.wave))) return live_abandon(e, lv, rc);
+    if ((rc = live_launch(e, lv, src, lv.ss.g.n, 1, false, d.db, d.rgba, 1, 1, true, d.peaks, d.wave, d.level, d.cross))) return live_abandon(e, lv, rc);
     if ((rc = live_sync(e, lv))) return rc;
     live_copy_back(e, lv, d, out_db, out_rgba, e->cfg.rows);
     live_frame_commit(lv.ss.g, lv.c, out_columns);
@@ -462,13 +523,13 @@ int flush_impl(emspec_engine* e, LiveState& lv, float* out_db, uint8_t* out_rgba
     if (rows != e->cfg.rows) return fail(e, EMSPEC_ERR_INVALID_ARG, "rows does not match the engine configuration");
     if (lv.ss.g.form == 0 || !lv.c.any_pending()) return fail(e, EMSPEC_ERR_STATE, "no pending column");
     int rc;
-    if ((rc = live_overlay_check(e, lv.ss.g.S, 1))) return rc;
+    if ((rc = live_overlay_check(e, lv, lv.ss.g.S, 1))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     if ((rc = history_ready(e, lv))) return rc;
     LiveDest d;   // (as emspec_columns; the staging blocks are sized for a push's mmax columns at once)
     if ((rc = live_dest(e, lv, out_db, out_rgba, lv.ss.g.mmax, d))) return rc;
     live_flush_fill(lv.ss.g, lv.c, lv.desc());
-    if ((rc = live_launch(e, lv, nullptr, 0, 0, true, d.db, d.rgba, 1, 1, true, d.peaks, d.wave))) return live_abandon(e, lv, rc);
+    if ((rc = live_launch(e, lv, nullptr, 0, 0, true, d.db, d.rgba, 1, 1, true, d.peaks, d.wave, d.level, d.cross))) return live_abandon(e, lv, rc);
     if ((rc = live_sync(e, lv))) return rc;
     live_copy_back(e, lv, d, out_db, out_rgba, e->cfg.rows);
     live_flush_commit(lv.ss.g, lv.c, out_columns);
@@ -502,10 +563,11 @@ int push_impl(emspec_engine* e, LiveState& lv, const void* block, const LiveAsk&
     const int64_t expect = push_columns_impl(e, lv, count, ask.p.n[0], ask.hop, ask.reassign);
     // (an overlay is an output too: its slots are the columns of [S][max_columns]; so is the history, whose columns pass
     // through a device block of that layout)
-    if ((out_db || out_rgba || ask.p.bands > 1 || fmt || e->live_peaks || e->live_wave || e->history_W > 0) && expect > max_columns)
+    if ((out_db || out_rgba || ask.p.bands > 1 || fmt || e->live_peaks || e->live_wave || e->live_level || e->live_cross || e->history_W > 0) &&
+        expect > max_columns)
         return fail(e, EMSPEC_ERR_INVALID_ARG, "output holds fewer columns than this block completes (" + std::to_string(expect) +
                                                    "); size it with emspec_push_columns() / emspec_push_columns_multi()");
-    if ((rc = live_overlay_check(e, ask.S, max_columns))) return rc;
+    if ((rc = live_overlay_check(e, lv, ask.S, max_columns))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     const bool opened = lv.ss.g.form == 0;
     if (opened) {
@@ -538,10 +600,10 @@ int push_impl(emspec_engine* e, LiveState& lv, const void* block, const LiveAsk&
         if (!live_push_round(g, lv.c, p, d.direct, lv.desc())) continue;   // no frame is due and the staging block has room
         if (fmt && (rc = live_decode_pending(e, lv))) return live_abandon(e, lv, rc);
         if ((rc = live_launch(e, lv, fmt ? lv.d_fresh : lv.h_fresh, g.cap, p.mx, false, d.db, d.rgba, d.direct ? (int)max_columns : g.mmax,
-                              d.direct ? (int)std::min<int64_t>(std::max<int64_t>(expect, 1), 0x7fffffff) : g.mmax, false, d.peaks, d.wave)))
+                              d.direct ? (int)std::min<int64_t>(std::max<int64_t>(expect, 1), 0x7fffffff) : g.mmax, false, d.peaks, d.wave, d.level, d.cross)))
             return live_abandon(e, lv, rc);
         inflight = true;
-        if (d.stage_db || d.stage_rgba || d.stage_peaks || d.stage_wave) {
+        if (d.staged()) {
             if ((rc = live_sync(e, lv))) return rc;
             inflight = false;
             live_copy_back(e, lv, d, out_db, out_rgba, e->cfg.rows, &p, max_columns);
@@ -569,6 +631,9 @@ void live_free(LiveState& lv) {
     (void)hipFree(lv.d_pdb); (void)hipFree(lv.d_wring);
     if (lv.h_opeaks) (void)hipHostFree(lv.h_opeaks);
     if (lv.h_owave) (void)hipHostFree(lv.h_owave);
+    (void)hipFree(lv.d_lring); (void)hipFree(lv.d_xring);
+    if (lv.h_olevel) (void)hipHostFree(lv.h_olevel);
+    if (lv.h_ocross) (void)hipHostFree(lv.h_ocross);
     history_free(lv);
     audio_free(lv);
     lv = LiveState{};
@@ -786,11 +851,42 @@ int emspec_set_live_wave(emspec_engine* e, emspec_wave* wave_out, int64_t capaci
     if (reinterpret_cast<uintptr_t>(wave_out) % 4) return fail(e, EMSPEC_ERR_INVALID_ARG, "wave_out must be 4-byte aligned");
     if (e->time_reduce > 1) return fail(e, EMSPEC_ERR_STATE, kNoLiveReduce);
     // the pair of a column is taken when its frame arrives: a stream that already has frames has columns without a pair
-    for (const LiveState* lv : {&e->live, &e->one})
-        for (int s = 0; s < lv->c.streams(); ++s)
-            if (lv->ss.g.form != 0 && lv->c.fed[s] > 0)
-                return fail(e, EMSPEC_ERR_STATE, "the envelope needs the samples of every column still to come: a session has frames fed; call emspec_reset() first");
+    if (live_fed(e))
+        return fail(e, EMSPEC_ERR_STATE, "the envelope needs the samples of every column still to come: a session has frames fed; call emspec_reset() first");
     e->live_wave = wave_out; e->live_wave_capacity = capacity;
+    return EMSPEC_OK;
+}
+
+// the level meters: the envelope's rules (a column's records are taken when its frame arrives), 8-byte records
+int emspec_set_live_level(emspec_engine* e, emspec_level* level_out, int64_t capacity) {
+    if (!e) return EMSPEC_ERR_INVALID_ARG;
+    if (!level_out) {
+        e->live_level = nullptr; e->live_level_capacity = 0;
+        return EMSPEC_OK;
+    }
+    if (capacity < 0) return fail(e, EMSPEC_ERR_INVALID_ARG, "the level records' capacity must not be negative");
+    if (reinterpret_cast<uintptr_t>(level_out) % 8) return fail(e, EMSPEC_ERR_INVALID_ARG, "level_out must be 8-byte aligned");
+    if (e->time_reduce > 1) return fail(e, EMSPEC_ERR_STATE, kNoLiveReduce);
+    if (live_fed(e))
+        return fail(e, EMSPEC_ERR_STATE, "the level records need the samples of every column still to come: a session has frames fed; call emspec_reset() first");
+    e->live_level = level_out; e->live_level_capacity = capacity;
+    return EMSPEC_OK;
+}
+
+int emspec_set_live_cross(emspec_engine* e, int32_t views, int32_t a, int32_t b, emspec_cross* cross_out, int64_t capacity) {
+    if (!e) return EMSPEC_ERR_INVALID_ARG;
+    if (!cross_out) {
+        e->live_cross = nullptr; e->live_cross_capacity = 0; e->live_cross_views = 1; e->live_cross_a = e->live_cross_b = 0;
+        return EMSPEC_OK;
+    }
+    if (const char* why = cross_pair_error(0, views, a, b)) return fail(e, EMSPEC_ERR_INVALID_ARG, why);
+    if (capacity < 0) return fail(e, EMSPEC_ERR_INVALID_ARG, "the cross records' capacity must not be negative");
+    if (reinterpret_cast<uintptr_t>(cross_out) % 8) return fail(e, EMSPEC_ERR_INVALID_ARG, "cross_out must be 8-byte aligned");
+    if (e->time_reduce > 1) return fail(e, EMSPEC_ERR_STATE, kNoLiveReduce);
+    if (live_fed(e))
+        return fail(e, EMSPEC_ERR_STATE, "the cross records need the samples of every column still to come: a session has frames fed; call emspec_reset() first");
+    e->live_cross = cross_out; e->live_cross_capacity = capacity;
+    e->live_cross_views = views; e->live_cross_a = a; e->live_cross_b = b;
     return EMSPEC_OK;
 }
 
@@ -799,6 +895,9 @@ int emspec_reset_stream(emspec_engine* e, int32_t stream) {
     LiveState& lv = e->live;
     if (lv.ss.g.form == 0) return fail(e, EMSPEC_ERR_STATE, "no live session");
     if (stream < 0 || stream >= lv.ss.g.S) return fail(e, EMSPEC_ERR_INVALID_ARG, "stream out of range");
+    // a cross record multiplies the two streams of a pair sample by sample: they must stay in step
+    if (e->live_cross)
+        return fail(e, EMSPEC_ERR_STATE, "emspec_set_live_cross is set: the streams of a pair restart together (emspec_reset), or clear the setting first");
     HIPCHK(e, hipSetDevice(e->device));
     if (int rc = live_pcm_drain(e, lv)) return rc;
     const int R = e->cfg.rows;

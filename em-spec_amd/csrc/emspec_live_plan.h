@@ -411,6 +411,39 @@ inline int live_wave_offset(const LiveGeometry& g) { return g.n / 2 - g.hop / 2;
 inline size_t live_peaks_bytes(const LiveGeometry& g, int64_t cols, int k) { return (size_t)g.S * cols * k * 8; }
 inline size_t live_wave_bytes(const LiveGeometry& g, int64_t cols) { return (size_t)g.S * cols * 8; }
 
+// ---- the live level meters (emspec_set_live_level / emspec_set_live_cross) ----
+// The records of frame j - the factor-1 level record of every stream and, per pair, the cross record, over the envelope's hop
+// samples - live in two more rings beside the pair ring, slot j % slots, by the same argument: slots = live_wave_slots(g).  A
+// pair is the streams p views + a and p views + b of the session (emspec_window_plan.h: cross_pair_error), so the session's
+// stream count must be a multiple of `views`; a stream that is not channel a of its pair writes no cross record.
+constexpr int kLiveLevelRecord = 24, kLiveCrossRecord = 16;   // sizeof(emspec_level), sizeof(emspec_cross) (include/emspec.h)
+// null, or why a session of S streams cannot deliver cross records of `views` streams per pair (EMSPEC_ERR_INVALID_ARG)
+inline const char* live_cross_error(int S, int views) {
+    if (views < 1 || S % views != 0) return "the session's streams are not a multiple of the views set with emspec_set_live_cross";
+    return nullptr;
+}
+inline int live_cross_pairs(int S, int views) { return views >= 1 ? S / views : 0; }
+// A cross record multiplies the two streams of a pair sample by sample, so channel a's wave reads channel b's samples at its
+// own frame's indices: both streams must have received, staged and framed the same (emspec_reset_stream, the one call that
+// moves a single stream, is refused while a cross is set; this is the check for a setting that arrives after it)
+inline bool live_pairs_in_step(const LiveCounters& c, int views, int a, int b) {
+    for (int p = 0; views >= 1 && (p + 1) * views <= c.streams(); ++p) {
+        const int sa = p * views + a, sb = p * views + b;
+        if (c.fed[sa] != c.fed[sb] || c.seen[sa] != c.seen[sb] || c.newbase[sa] != c.newbase[sb] || c.pend[sa] != c.pend[sb]) return false;
+    }
+    return true;
+}
+inline size_t live_level_ring_bytes(const LiveGeometry& g) { return (size_t)g.S * live_wave_slots(g) * kLiveLevelRecord; }
+inline size_t live_cross_ring_bytes(const LiveGeometry& g, int views) {
+    return (size_t)live_cross_pairs(g.S, views) * live_wave_slots(g) * kLiveCrossRecord;
+}
+// the caller's arrays level_out[s cols + slot] and cross_out[p cols + slot] and the page-locked staging blocks of pageable ones:
+// [S][cols] and [S / views][cols] records
+inline size_t live_level_bytes(const LiveGeometry& g, int64_t cols) { return (size_t)g.S * cols * kLiveLevelRecord; }
+inline size_t live_cross_bytes(const LiveGeometry& g, int views, int64_t cols) {
+    return (size_t)live_cross_pairs(g.S, views) * cols * kLiveCrossRecord;
+}
+
 // ---- PCM session: the staged samples into the device sample rings, no frame ----
 inline void live_drain_fill(const LiveGeometry& g, const LiveCounters& c, LiveStream* d) {
     for (int s = 0; s < g.S; ++s) d[s] = LiveStream{c.fed[s], c.newbase[s], 0, c.pend[s], 0, 0};

@@ -148,6 +148,36 @@ int64_t emspec_level_window(int64_t L, int32_t n, int32_t hop, int32_t factor, i
     return w.b - w.a;
 }
 
+// The factor law as a helper: the field-wise sum (peak: maximum) of `count` records - level_combine / cross_combine with checked
+// adds, so that a sum no limb can hold is refused instead of wrapping.  *out is written only on success (it may be records[i]).
+int emspec_level_sum(const emspec_level* records, int64_t count, emspec_level* out) {
+    if (!records || !out || count < 1) return fail(nullptr, EMSPEC_ERR_INVALID_ARG, "emspec_level_sum needs records, an output and count >= 1");
+    emspec_level r = LevelRed::start();
+    bool wrapped = false;
+    for (int64_t i = 0; i < count; ++i) {
+        wrapped |= __builtin_add_overflow(r.sq_lo, records[i].sq_lo, &r.sq_lo);
+        wrapped |= __builtin_add_overflow(r.sq_hi, records[i].sq_hi, &r.sq_hi);
+        wrapped |= __builtin_add_overflow(r.odd, records[i].odd, &r.odd);
+        r.peak = std::max(r.peak, records[i].peak);
+    }
+    if (wrapped) return fail(nullptr, EMSPEC_ERR_INVALID_ARG, "emspec_level_sum: a limb of the sum does not fit its field");
+    *out = r;
+    return EMSPEC_OK;
+}
+
+int emspec_cross_sum(const emspec_cross* records, int64_t count, emspec_cross* out) {
+    if (!records || !out || count < 1) return fail(nullptr, EMSPEC_ERR_INVALID_ARG, "emspec_cross_sum needs records, an output and count >= 1");
+    emspec_cross r = CrossRed::start();
+    bool wrapped = false;
+    for (int64_t i = 0; i < count; ++i) {
+        wrapped |= __builtin_add_overflow(r.lo, records[i].lo, &r.lo);
+        wrapped |= __builtin_add_overflow(r.hi, records[i].hi, &r.hi);
+    }
+    if (wrapped) return fail(nullptr, EMSPEC_ERR_INVALID_ARG, "emspec_cross_sum: a limb of the sum does not fit its field");
+    *out = r;
+    return EMSPEC_OK;
+}
+
 int emspec_level_values(const emspec_level* level, int64_t samples, double* rms_db, double* peak_db) {
     if (!level || samples < 1) return EMSPEC_ERR_INVALID_ARG;
     const double sum = std::ldexp((double)level->sq_hi, 32) + (double)level->sq_lo;

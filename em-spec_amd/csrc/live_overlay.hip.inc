@@ -1,6 +1,7 @@
-// live_overlay.hip.inc — the overlays of the live calls (include/emspec.h: emspec_set_live_peaks, emspec_set_live_wave;
-// DESIGN.md §3.11, §3.12, §4.15): beside the columns a streaming launch delivers, their spectral peaks and the waveform
-// envelope of the samples under them.  One kernel behind the last band's frame / flush launch (behind the post kernel when the
+// live_overlay.hip.inc — the overlays of the live calls (include/emspec.h: emspec_set_live_peaks, emspec_set_live_wave,
+// emspec_set_live_level, emspec_set_live_cross; DESIGN.md §3.11, §3.12, §3.17, §4.15): beside the columns a streaming launch
+// delivers, their spectral peaks, the waveform envelope of the samples under them and those samples' level and cross records.
+// One kernel behind the last band's frame / flush launch (behind the post kernel when the
 // display post-process is on), enqueued only while a setting is on.  It reads the launch's own LiveSinks descriptors, so it
 // knows j0, frames, flush, out_at, empty_col and uniform without another host round trip, and it writes exactly the column
 // slots the launch writes (emspec_live_plan.h: live_out_slot).  Included by kernels.hip behind live_launch.hip.inc (needs
@@ -113,6 +114,41 @@ __device__ __forceinline__ uint2 live_wave_pair(const LiveSinks& lv, const LiveS
     return make_uint2(wave_bits(lo), wave_bits(hi));
 }
 
+// The sample reducers of frame j of stream s while a level meter is set: ONE walk over the same hop samples for the envelope's
+// keys, the level record and - on a wave that serves channel a of a pair (`crossed`) - the cross record with stream sb's sample
+// at the same index, read by the same rule through stream sb's own descriptor.  take / combine are the plan header's
+// (emspec_window_plan.h), the butterfly is window.hip.inc's window_mix: no arithmetic is restated.  Every lane returns the
+// finished records; `keys` leaves as the samples' bits.
+struct LiveMeters { WaveKeys keys; emspec_level level; emspec_cross cross; };
+__device__ __forceinline__ LiveMeters live_meters_take(const LiveSinks& lv, const LiveStream& d, const LiveStream& db, int s, int sb, bool crossed, long long j,
+                                                       int hop, int off, int lane) {
+    const size_t rlen = (size_t)lv.ring_mask + 1;
+    const uint32_t* fresh = reinterpret_cast<const uint32_t*>(lv.fresh);
+    const uint32_t* sring = reinterpret_cast<const uint32_t*>(lv.sring);   // (null in the per-frame form: every sample is in the staging block)
+    const uint32_t *fa = fresh + (size_t)s * (size_t)lv.fresh_stride, *fb = fresh + (size_t)sb * (size_t)lv.fresh_stride;
+    const uint32_t *ra = sring ? sring + (size_t)s * rlen : nullptr, *rb = sring ? sring + (size_t)sb * rlen : nullptr;
+    const long long a0 = j * (long long)hop + off;
+    LiveMeters m{EnvelopeRed::start(), LevelRed::start(), CrossRed::start()};
+    for (int t = lane; t < hop; t += 64) {
+        const long long a = a0 + t, rel = a - d.newbase;
+        const uint32_t ua = rel >= 0 ? fa[rel] : ra[a & lv.ring_mask];
+        EnvelopeRed::take(m.keys, ua, 0);
+        LevelRed::take(m.level, ua, 0);
+        if (crossed) {   // (uniform in the wave)
+            const long long relb = a - db.newbase;
+            CrossRed::take(m.cross, ua, relb >= 0 ? fb[relb] : rb[a & lv.ring_mask]);
+        }
+    }
+#pragma unroll
+    for (int x = 32; x >= 1; x >>= 1) {
+        window_mix(m.keys, x);
+        window_mix(m.level, x);
+        if (crossed) window_mix(m.cross, x);
+    }
+    m.keys = EnvelopeRed::finish(m.keys);
+    return m;
+}
+
 // Grid (ceil(U / kPeakWaves), S), U = the most frames (flush form: columns) any stream has in the launch: wave (s, i) serves the
 // launch's i-th frame of stream s and its i-th column.
 //   peaks     the column's delivered dB (ov.db, a device block laid out like the launch's output) goes into the wave's R floats of
@@ -121,7 +157,14 @@ __device__ __forceinline__ uint2 live_wave_pair(const LiveSinks& lv, const LiveS
 //   envelope  the pair of frame j0 + i goes to slot (j0 + i) % wslots of the stream's pair ring; the pair of column
 //             c = j0 - D + i comes from that ring when frame c arrived in an earlier launch (c < j0) and from the samples when
 //             frame c is one of this launch's: no wave waits for another (emspec_live_plan.h: live_wave_slots).
+//   meters    (METERS: a level or cross setting is on) the level record of frame j0 + i, and on the waves with s % views == a the
+//             cross record of the pair s / views, go to the same slot of their own rings, and a column's records come from the
+//             same three sources as its pair: the ring, this wave's own walk when D == 0, else a second walk.  One walk feeds
+//             the envelope, the level and the cross (live_meters_take); one lane stores a record.
+// METERS is a template parameter, not a run-time branch: the instance without it is the kernel as it was before the meters,
+// instruction for instruction (profiles/live_level_rate.txt), so peaks and envelope alone cost what they did.
 // All global offsets are 64-bit; plain vector stores only.
+template <bool METERS>
 __global__ __launch_bounds__(64 * kPeakWaves) void live_overlay_kernel(LiveSinks lv, LiveOverlay ov) {
     extern __shared__ float overlay_lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -148,7 +191,47 @@ __global__ __launch_bounds__(64 * kPeakWaves) void live_overlay_kernel(LiveSinks
             peaks_select_column(x, R, Q, ov.k, ov.min_db, lane, ov.peaks + pair * (size_t)ov.k);
         }
     }
-    if (ov.wave) {
+    if constexpr (METERS) {
+        const bool crossed = ov.cross && s % ov.views == ov.a;
+        const int sb = crossed ? s - ov.a + ov.b : s, p = s / ov.views;
+        const LiveStream db = lv.uniform ? lv.uni : lv.streams[sb];
+        uint2* wring = ov.wave ? ov.wring + (size_t)s * (size_t)ov.wslots : nullptr;
+        emspec_level* lring = ov.level ? ov.lring + (size_t)s * (size_t)ov.wslots : nullptr;
+        emspec_cross* xring = crossed ? ov.xring + (size_t)p * (size_t)ov.wslots : nullptr;
+        const bool feeds = !d.flush && i < d.frames;
+        // the empty column's records: the pair (+inf, -inf), sums of no sample
+        LiveMeters mine{WaveKeys{0x7f800000u, 0xff800000u}, LevelRed::start(), CrossRed::start()};
+        if (feeds) {
+            mine = live_meters_take(lv, d, db, s, sb, crossed, d.j0 + i, ov.hop, ov.off, lane);
+            const int slot = (int)((d.j0 + i) % ov.wslots);
+            if (lane == 0) {
+                if (wring) wring[slot] = make_uint2(mine.keys.lo, mine.keys.hi);
+                if (lring) lring[slot] = mine.level;
+                if (xring) xring[slot] = mine.cross;
+            }
+        }
+        if (oc >= 0) {
+            const long long c = d.j0 - ov.D + i;
+            LiveMeters m{WaveKeys{0x7f800000u, 0xff800000u}, LevelRed::start(), CrossRed::start()};
+            if (c >= 0) {
+                if (d.flush || c < d.j0) {
+                    const int slot = (int)(c % ov.wslots);
+                    if (wring) { const uint2 w = wring[slot]; m.keys = WaveKeys{w.x, w.y}; }
+                    if (lring) m.level = lring[slot];
+                    if (xring) m.cross = xring[slot];
+                } else if (ov.D == 0) {
+                    m = mine;
+                } else {
+                    m = live_meters_take(lv, d, db, s, sb, crossed, c, ov.hop, ov.off, lane);
+                }
+            }
+            if (lane == 0) {
+                if (ov.wave) ov.wave[pair] = make_uint2(m.keys.lo, m.keys.hi);
+                if (ov.level) ov.level[pair] = m.level;
+                if (crossed) ov.cross[(size_t)p * (size_t)lv.out_cols + (size_t)oc] = m.cross;
+            }
+        }
+    } else if (ov.wave) {
         uint2* ring = ov.wring + (size_t)s * (size_t)ov.wslots;
         const bool feeds = !d.flush && i < d.frames;
         uint2 mine = make_uint2(0x7f800000u, 0xff800000u);   // (+inf, -inf): the empty column's pair
@@ -172,14 +255,20 @@ __global__ __launch_bounds__(64 * kPeakWaves) void live_overlay_kernel(LiveSinks
 // lv: the launch's sinks with out_db / out_cols the CALLER's dB destination and its stride (null: dB not wanted);
 // units: the most frames (flush form: columns) of any stream.  ov.k != 0 needs rows % 4 == 0, 4 <= rows <= 4096.
 hipError_t launch_live_overlay(const LiveSinks& lv, const LiveOverlay& ov, int S, int units, hipStream_t st) {
-    if (S <= 0 || units <= 0 || (!ov.k && !ov.wave)) return hipSuccess;
+    const bool meters = ov.level || ov.cross;
+    if (S <= 0 || units <= 0 || (!ov.k && !ov.wave && !meters)) return hipSuccess;
     if (S > 65535) return hipErrorInvalidValue;
     if (ov.k && (!ov.db || !ov.peaks || ov.rows % 4 || ov.rows < 4 || ov.rows > 4096 || ov.k < 1 || ov.k > 32 || ov.min_db != ov.min_db))
         return hipErrorInvalidValue;
     if (ov.wave && (!ov.wring || ov.wslots < 1 || ov.hop < 1)) return hipErrorInvalidValue;
+    if (meters && (ov.wslots < 1 || ov.hop < 1 || (ov.level && !ov.lring))) return hipErrorInvalidValue;
+    // a pair's two streams are streams of this launch: p views + a and p views + b below S
+    if (ov.cross && (!ov.xring || ov.views < 1 || S % ov.views || ov.a < 0 || ov.a >= ov.views || ov.b < 0 || ov.b >= ov.views)) return hipErrorInvalidValue;
+    if (meters && ((reinterpret_cast<uintptr_t>(ov.level) | reinterpret_cast<uintptr_t>(ov.cross)) & 7)) return hipErrorInvalidValue;
     const size_t lds = ov.k ? (size_t)kPeakWaves * ov.rows * sizeof(float) : 0;
-    hipLaunchKernelGGL(live_overlay_kernel, dim3((unsigned)((units + kPeakWaves - 1) / kPeakWaves), (unsigned)S), dim3(64 * kPeakWaves), lds, st,
-                       lv, ov);
+    const dim3 grid((unsigned)((units + kPeakWaves - 1) / kPeakWaves), (unsigned)S), block(64 * kPeakWaves);
+    if (meters) hipLaunchKernelGGL(live_overlay_kernel<true>, grid, block, lds, st, lv, ov);
+    else hipLaunchKernelGGL(live_overlay_kernel<false>, grid, block, lds, st, lv, ov);
     return hipGetLastError();
 }
 

@@ -77,8 +77,10 @@ STEREO_SYMBOLS = ["emspec_stereo_default_map", "emspec_make_stereo_colormap", "e
 # the level meters': likewise (tools/level_rate.py times the parent commit's library next to this build)
 LEVEL_SYMBOLS = ["emspec_level_device", "emspec_level_host", "emspec_cross_device", "emspec_cross_host", "emspec_set_level_out",
                  "emspec_set_cross_out", "emspec_level_window", "emspec_level_values", "emspec_cross_correlation"]
+# the live level meters': likewise (tools/live_rate.py times the parent commit's library next to this build)
+LIVE_LEVEL_SYMBOLS = ["emspec_set_live_level", "emspec_set_live_cross", "emspec_level_sum", "emspec_cross_sum"]
 SYMBOLS = (SYMBOLS + MULTIBAND_SYMBOLS + LIVE_OVERLAY_SYMBOLS + LIVE_MULTIBAND_SYMBOLS + HISTORY_SYMBOLS + AUDIO_SYMBOLS + STEREO_SYMBOLS
-           + LEVEL_SYMBOLS)
+           + LEVEL_SYMBOLS + LIVE_LEVEL_SYMBOLS)
 STEREO_PAN_CENTRE, STEREO_PAN_LEVELS = 16, 33
 SESSION_MULTI, SESSION_ONE = 0, 1
 _SESSIONS = {"multi": SESSION_MULTI, "one": SESSION_ONE, SESSION_MULTI: SESSION_MULTI, SESSION_ONE: SESSION_ONE}
@@ -323,6 +325,28 @@ def cross_correlation(level_a, level_b, cross, diag=False):
     if load(diag).emspec_cross_correlation(C.byref(la), C.byref(lb), C.byref(cr), C.byref(rho)) != OK:
         raise EmspecError(ERR_INVALID_ARG, "cross_correlation needs three records")
     return rho.value
+
+
+def _records_sum(fn, records, dtype, diag):
+    records = np.ascontiguousarray(records, dtype).reshape(-1)
+    out = np.zeros((), dtype)
+    lib = load(diag)
+    rc = getattr(lib, fn)(_np_ptr(records) if records.size else None, records.size, _np_ptr(out))
+    if rc != OK:
+        raise EmspecError(rc, lib.emspec_last_error(None).decode())
+    return out
+
+
+def level_sum(records, diag=False):
+    """emspec_level_sum: the field-wise sum (peak: maximum) of one or more LEVEL_DTYPE records - the record of their samples
+    together, e.g. a meter's 300 ms of per-hop records of Engine.set_live_level -> a 0-d LEVEL_DTYPE array.  A sum that a limb
+    cannot hold, or no record, raises."""
+    return _records_sum("emspec_level_sum", records, LEVEL_DTYPE, diag)
+
+
+def cross_sum(records, diag=False):
+    """emspec_cross_sum: as level_sum for CROSS_DTYPE records."""
+    return _records_sum("emspec_cross_sum", records, CROSS_DTYPE, diag)
 
 
 def make_stereo_colormap(brightness=0.5, diag=False):
@@ -580,6 +604,11 @@ def load(diag=False):
         lib.emspec_level_window.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64]
         lib.emspec_level_values.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         lib.emspec_cross_correlation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if all(hasattr(lib, sym) for sym in LIVE_LEVEL_SYMBOLS):
+        lib.emspec_set_live_level.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        lib.emspec_set_live_cross.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
+        lib.emspec_level_sum.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        lib.emspec_cross_sum.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
     _libs[diag] = lib
     return lib
 
@@ -1512,6 +1541,39 @@ class Engine:
         arr, pairs = self._overlay_array(out, WAVE_DTYPE)
         self._chk(self._lib.emspec_set_live_wave(self._h, _np_ptr(arr), pairs))
         self._live_wave = out
+
+    @staticmethod
+    def _record_array(out, dtype):
+        """out: a PinnedArray or a C-contiguous writable numpy array of `dtype` records (or of bytes) -> (array, records)."""
+        arr = out.array if isinstance(out, PinnedArray) else out
+        assert isinstance(arr, np.ndarray) and arr.flags.c_contiguous and arr.flags.writeable
+        assert arr.dtype == dtype or arr.dtype == np.uint8, arr.dtype
+        return arr, arr.nbytes // dtype.itemsize
+
+    def set_live_level(self, out):
+        """emspec_set_live_level: while set, every streaming call also writes the level record (LEVEL_DTYPE: exact sum of squares
+        in two limbs, peak, odd count) of the samples under each column it delivers to out[s * cols + slot].  out: an array of
+        LEVEL_DTYPE (or of bytes), 8-byte aligned, or a PinnedArray of either (written in place by the kernel); None clears.
+        Set it before the sessions' first frames (or after reset()).  level_values() / level_sum() turn records into dB."""
+        if out is None:
+            self._chk(self._lib.emspec_set_live_level(self._h, None, 0))
+            self._live_level = None
+            return
+        arr, records = self._record_array(out, LEVEL_DTYPE)
+        self._chk(self._lib.emspec_set_live_level(self._h, _np_ptr(arr), records))
+        self._live_level = out
+
+    def set_live_cross(self, views, a, b, out):
+        """emspec_set_live_cross: while set, every streaming call also writes the cross record (CROSS_DTYPE) of the streams
+        p views + a and p views + b under each column it delivers to out[p * cols + slot].  out as for set_live_level; None
+        clears.  While it is set, reset_stream() is refused (ERR_STATE): the streams of a pair restart together."""
+        if out is None:
+            self._chk(self._lib.emspec_set_live_cross(self._h, 0, 0, 0, None, 0))
+            self._live_cross = None
+            return
+        arr, records = self._record_array(out, CROSS_DTYPE)
+        self._chk(self._lib.emspec_set_live_cross(self._h, int(views), int(a), int(b), _np_ptr(arr), records))
+        self._live_cross = out
 
     # -- live history (include/emspec.h: emspec_set_live_history / emspec_history_view) ----------------------------------------
     def set_live_history(self, columns):

@@ -46,8 +46,8 @@ static napi_value throw_status(napi_env env, emspec_engine* e, int rc) {
 
 /* rows: the engine's row count, for output-size checks; wave: the array given to setWaveOut, referenced while it is set;
  * level / cross: likewise the arrays given to setLevelOut / setCrossOut; live_peaks / live_wave: those given to setLivePeaks /
- * setLiveWave */
-typedef struct { emspec_engine* e; int32_t rows; napi_ref wave, level, cross, live_peaks, live_wave; } handle_t;
+ * setLiveWave; live_level / live_cross: setLiveLevel / setLiveCross */
+typedef struct { emspec_engine* e; int32_t rows; napi_ref wave, level, cross, live_peaks, live_wave, live_level, live_cross; } handle_t;
 
 static void drop_ref(napi_env env, napi_ref* r) {
     if (*r) { napi_delete_reference(env, *r); *r = NULL; }
@@ -57,10 +57,16 @@ static void drop_wave(napi_env env, handle_t* h) {   /* ... and the level meters
     drop_ref(env, &h->level);
     drop_ref(env, &h->cross);
 }
+static void drop_live(napi_env env, handle_t* h) {   /* the arrays the live calls also fill */
+    drop_ref(env, &h->live_peaks);
+    drop_ref(env, &h->live_wave);
+    drop_ref(env, &h->live_level);
+    drop_ref(env, &h->live_cross);
+}
 static void finalize_handle(napi_env env, void* data, void* hint) {
     (void)hint;
     handle_t* h = (handle_t*)data;
-    if (h) { if (h->e) emspec_destroy(h->e); drop_wave(env, h); drop_ref(env, &h->live_peaks); drop_ref(env, &h->live_wave); free(h); }
+    if (h) { if (h->e) emspec_destroy(h->e); drop_wave(env, h); drop_live(env, h); free(h); }
 }
 
 static int get_number_prop(napi_env env, napi_value obj, const char* name, double* out) {
@@ -138,7 +144,7 @@ static napi_value Create(napi_env env, napi_callback_info info) {
     h->e = e;
     h->rows = cfg.rows;
     h->wave = h->level = h->cross = NULL;
-    h->live_peaks = h->live_wave = NULL;
+    h->live_peaks = h->live_wave = h->live_level = h->live_cross = NULL;
     napi_value ext;
     if (napi_create_external(env, h, finalize_handle, NULL, &ext) != napi_ok) {
         finalize_handle(env, h, NULL);
@@ -156,8 +162,7 @@ static napi_value Destroy(napi_env env, napi_callback_info info) {
         handle_t* h = (handle_t*)p;
         if (h->e) { emspec_destroy(h->e); h->e = NULL; }
         drop_wave(env, h);
-        drop_ref(env, &h->live_peaks);
-        drop_ref(env, &h->live_wave);
+        drop_live(env, h);
     }
     return NULL;
 }
@@ -1462,6 +1467,79 @@ static napi_value SetLiveWave(napi_env env, napi_callback_info info) {
     h->live_wave = ref;
     return NULL;
 }
+/* Live level meters (include/emspec.h: emspec_set_live_level / emspec_set_live_cross / emspec_level_sum / emspec_cross_sum).
+ * setLiveLevel(handle, level:Uint8Array | null): capacity level.length / 24 records
+ * setLiveCross(handle, views, a, b, cross:Uint8Array | null): capacity cross.length / 16 records
+ * levelSum(records:Uint8Array(count*24), out:Uint8Array(24));  crossSum(records:Uint8Array(count*16), out:Uint8Array(16))
+ * The arrays are referenced as the other overlays' are. */
+static napi_value SetLiveLevel(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "setLiveLevel(handle, level)"); return NULL; }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    void* arr = NULL; size_t len = 0;
+    if (!get_typed(env, argv[1], napi_uint8_array, &arr, &len, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "level must be a Uint8Array or null"); return NULL; }
+    napi_ref ref = NULL;
+    if (arr) NAPI_OK_OR_RETURN(env, napi_create_reference(env, argv[1], 1, &ref));
+    int rc = emspec_set_live_level(h->e, (emspec_level*)arr, arr ? (int64_t)(len / sizeof(emspec_level)) : 0);
+    if (rc != EMSPEC_OK) {
+        if (ref) napi_delete_reference(env, ref);
+        return throw_status(env, h->e, rc);
+    }
+    drop_ref(env, &h->live_level);
+    h->live_level = ref;
+    return NULL;
+}
+static napi_value SetLiveCross(napi_env env, napi_callback_info info) {
+    size_t argc = 5; napi_value argv[5];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 5) { napi_throw_error(env, "EMSPEC_ERR_INVALID_ARG", "setLiveCross(handle, views, a, b, cross)"); return NULL; }
+    handle_t* h = get_handle(env, argv[0]); if (!h) return NULL;
+    int32_t views = 0, a = 0, b = 0;
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[1], &views));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[2], &a));
+    NAPI_OK_OR_RETURN(env, napi_get_value_int32(env, argv[3], &b));
+    void* arr = NULL; size_t len = 0;
+    if (!get_typed(env, argv[4], napi_uint8_array, &arr, &len, 1)) { napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", "cross must be a Uint8Array or null"); return NULL; }
+    napi_ref ref = NULL;
+    if (arr) NAPI_OK_OR_RETURN(env, napi_create_reference(env, argv[4], 1, &ref));
+    int rc = emspec_set_live_cross(h->e, views, a, b, (emspec_cross*)arr, arr ? (int64_t)(len / sizeof(emspec_cross)) : 0);
+    if (rc != EMSPEC_OK) {
+        if (ref) napi_delete_reference(env, ref);
+        return throw_status(env, h->e, rc);
+    }
+    drop_ref(env, &h->live_cross);
+    h->live_cross = ref;
+    return NULL;
+}
+/* the shared body of levelSum / crossSum: records of `size` bytes, copied (a view may lie at any byte offset) */
+static napi_value records_sum(napi_env env, napi_callback_info info, size_t size, const char* usage) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK_OR_RETURN(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    void *rec = NULL, *out = NULL; size_t rlen = 0, olen = 0;
+    if (argc < 2 || !get_typed(env, argv[0], napi_uint8_array, &rec, &rlen, 0) || !get_typed(env, argv[1], napi_uint8_array, &out, &olen, 0) ||
+        olen != size || rlen % size) {
+        napi_throw_type_error(env, "EMSPEC_ERR_INVALID_ARG", usage);
+        return NULL;
+    }
+    const int64_t count = (int64_t)(rlen / size);
+    void* copy = malloc(rlen ? rlen : 1);
+    if (!copy) { napi_throw_error(env, "EMSPEC_ERR_OUT_OF_MEMORY", "out of memory"); return NULL; }
+    memcpy(copy, rec, rlen);
+    emspec_level lsum; emspec_cross xsum;
+    const int rc = size == sizeof(emspec_level) ? emspec_level_sum((const emspec_level*)copy, count, &lsum)
+                                                : emspec_cross_sum((const emspec_cross*)copy, count, &xsum);
+    free(copy);
+    if (rc != EMSPEC_OK) return throw_status(env, NULL, rc);
+    memcpy(out, size == sizeof(emspec_level) ? (const void*)&lsum : (const void*)&xsum, size);
+    return NULL;
+}
+static napi_value LevelSum(napi_env env, napi_callback_info info) {
+    return records_sum(env, info, sizeof(emspec_level), "levelSum(records:Uint8Array(count*24), out:Uint8Array(24))");
+}
+static napi_value CrossSum(napi_env env, napi_callback_info info) {
+    return records_sum(env, info, sizeof(emspec_cross), "crossSum(records:Uint8Array(count*16), out:Uint8Array(16))");
+}
 /* Live history (include/emspec.h: emspec_set_live_history / emspec_live_history / emspec_history_view).
  * setLiveHistory(handle, columns): W columns per stream, 0 clears
  * liveHistory(handle, session, stream) -> [end, first] or null (no history, or the session has no such stream)
@@ -1995,6 +2073,10 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"crossCorrelation", NULL, CrossCorrelation, NULL, NULL, NULL, napi_default, NULL},
         {"setLivePeaks", NULL, SetLivePeaks, NULL, NULL, NULL, napi_default, NULL},
         {"setLiveWave", NULL, SetLiveWave, NULL, NULL, NULL, napi_default, NULL},
+        {"setLiveLevel", NULL, SetLiveLevel, NULL, NULL, NULL, napi_default, NULL},
+        {"setLiveCross", NULL, SetLiveCross, NULL, NULL, NULL, napi_default, NULL},
+        {"levelSum", NULL, LevelSum, NULL, NULL, NULL, napi_default, NULL},
+        {"crossSum", NULL, CrossSum, NULL, NULL, NULL, napi_default, NULL},
         {"setLiveHistory", NULL, SetLiveHistory, NULL, NULL, NULL, napi_default, NULL},
         {"liveHistory", NULL, LiveHistory, NULL, NULL, NULL, napi_default, NULL},
         {"historyView", NULL, HistoryView, NULL, NULL, NULL, napi_default, NULL},

@@ -87,6 +87,32 @@ class Engine {
   }
 
   /**
+   * Live level meters (emspec_set_live_level / emspec_set_live_cross; DESIGN.md §3.17, §4.15): while set, every live call also
+   * fills engine.columnsLevel - a levelRecords block, record [s * cols + slot] - and engine.columnsCross - a crossRecords block,
+   * record [p * cols + slot] of pair p = streams p * views + a and p * views + b - for the column slots it writes, from the
+   * samples under each column: exact sums, the same bytes as levelsOf / crossOf of the samples fed.  Page-locked, sized for
+   * `columns` columns per stream (default 1), switched on before a session's first frame (or after reset()) like the envelope;
+   * levelValues / crossCorrelation / levelSum / crossSum read them.  While the cross is set, resetStream throws
+   * EMSPEC_ERR_STATE (a pair's streams restart together), and the engine's streams must be a multiple of `views`.
+   * null / false clears.
+   */
+  setLiveLevel(opts) {
+    if (!opts) { native.setLiveLevel(this._h, null); this.columnsLevel = undefined; return; }
+    const count = this.streams * Math.max(1, (opts === true ? 1 : opts.columns) | 0);
+    const rec = levelRecords(count, native.allocPinned(24 * count));
+    native.setLiveLevel(this._h, rec.bytes);
+    this.columnsLevel = rec;
+  }
+  setLiveCross(views, a, b, opts = true) {
+    if (!opts || views === null || views === false) { native.setLiveCross(this._h, 0, 0, 0, null); this.columnsCross = undefined; return; }
+    const pairs = views >= 1 ? Math.floor(this.streams / views) : 0;
+    const count = Math.max(1, pairs) * Math.max(1, (opts === true ? 1 : opts.columns) | 0);
+    const rec = crossRecords(count, native.allocPinned(16 * count));
+    native.setLiveCross(this._h, views | 0, a | 0, b | 0, rec.bytes);
+    this.columnsCross = rec;
+  }
+
+  /**
    * Live history (emspec_set_live_history / emspec_live_history / emspec_history_view, DESIGN.md §3.14): the engine keeps the
    * last `columns` dB columns every live call delivers, per stream, on the device; historyView reads them back reduced in time
    * and coloured - what a renderer needs when the scroll speed, the window, the dB range, the gain, the gate or the colour map
@@ -687,13 +713,27 @@ function waveOf(pcm, S, L, fftSize, hop, factor = 1) {
  * [6 i + 4], odd at [6 i + 5] };  crossRecords(count): { count, bytes, lo: BigUint64Array - at [2 i] -, hi: BigInt64Array - at
  * [2 i + 1] }.  The sum of squares of record i is limbs[3 i + 1] * 2n ** 32n + limbs[3 i], the sum of products hi * 2n ** 32n + lo.
  */
-function levelRecords(count) {
-  const buf = new ArrayBuffer(Math.max(0, count) * 24);
+function levelRecords(count, buf = new ArrayBuffer(Math.max(0, count) * 24)) {   // (buf: e.g. page-locked memory of that size)
   return { count, bytes: new Uint8Array(buf), limbs: new BigUint64Array(buf), words: new Uint32Array(buf) };
 }
-function crossRecords(count) {
-  const buf = new ArrayBuffer(Math.max(0, count) * 16);
+function crossRecords(count, buf = new ArrayBuffer(Math.max(0, count) * 16)) {
   return { count, bytes: new Uint8Array(buf), lo: new BigUint64Array(buf), hi: new BigInt64Array(buf) };
+}
+/**
+ * The record of several records' samples together (emspec_level_sum / emspec_cross_sum): records [first, first + count) of a
+ * levelRecords / crossRecords block summed field by field (the peak: the maximum) -> a block of one record, for levelValues
+ * (over count x hop samples) and crossCorrelation.  What a meter that integrates 300 or 400 ms does with the per-hop records of
+ * engine.setLiveLevel / setLiveCross.  Throws EMSPEC_ERR_INVALID_ARG for count < 1 or a sum no limb can hold.
+ */
+function levelSum(level, first = 0, count = level.count - first) {
+  const out = levelRecords(1);
+  native.levelSum(level.bytes.subarray(24 * first, 24 * (first + Math.max(0, count))), out.bytes);
+  return out;
+}
+function crossSum(cross, first = 0, count = cross.count - first) {
+  const out = crossRecords(1);
+  native.crossSum(cross.bytes.subarray(16 * first, 16 * (first + Math.max(0, count))), out.bytes);
+  return out;
 }
 function reducedColumnsOf(L, fftSize, hop, factor) {
   const C = L >= fftSize && hop >= 1 ? Math.floor((L - fftSize) / hop) + 1 : 0;
@@ -772,6 +812,8 @@ module.exports = {
   levelWindow: native.levelWindow,
   levelValues,
   crossCorrelation,
+  levelSum,
+  crossSum,
   /** hz -> {name, octave, cents}: 12-tone equal temperament around A4 = 440 Hz, the nearest semitone, cents in [-50, 50). */
   noteOf,
   latencyColumns: native.latencyColumns,

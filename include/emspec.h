@@ -962,6 +962,48 @@ int emspec_cross_correlation(const emspec_level* a, const emspec_level* b, const
  */
 int emspec_set_live_peaks(emspec_engine* e, int32_t k, float min_db, emspec_peak* peaks_out, int64_t capacity /* pairs */);
 int emspec_set_live_wave(emspec_engine* e, emspec_wave* wave_out, int64_t capacity /* pairs */);
+/*
+ * Live level meters: the level record of every stream and the cross record of every pair of streams,
+ * per emitted column, from the same kernel and the same walk over the samples as the envelope.  Serves the RMS / peak meter
+ * beside the waveform lane and the correlation meter beside a stereo image of a LIVE session - for a PCM session the decoded
+ * views exist in no host buffer; [BUILD-DEFINED].
+ *
+ * While a setting is on, every streaming call named above (and the _multiband forms), on either session, also writes, for
+ * exactly the column slots it writes,
+ *     level_out[s * cols + slot],  s in 0 .. S-1        and        cross_out[p * cols + slot],  p in 0 .. S / views - 1
+ * with cols as above, and leaves the other slots untouched.  Pair p is the streams p views + a and p views + b of the session,
+ * as in emspec_cross_device (a == b is allowed).
+ * The record of column c is the factor-1 record of the level meters' DEFINITION over the samples [c hop + off, c hop + off + hop)
+ * of the stream (of the pair), off = n / 2 - hop / 2, n the session's FFT size (n_low, n[0] for a multi-resolution or multi-band
+ * session); it is taken when frame c arrives and kept on the device until column c is emitted; the empty column "-1" of the
+ * per-frame form gives the all-zero record; for a PCM session the samples are the decoded, mixed float32 values of each view.
+ * For a stream fed [0, L) and then flushed, the emitted records are byte-equal to emspec_level_host(pcm, 1, L, n, hop, 1, ...),
+ * those of a pair to emspec_cross_host(pcm, pairs, views, a, b, L, n, hop, 1, ...), in both modes, in both feeding forms,
+ * however the samples were cut into calls.
+ *
+ * Both arrays are host memory, valid while set, 8-byte aligned (else EMSPEC_ERR_INVALID_ARG, as for emspec_set_level_out):
+ * page-locked they are written in place by the kernel, pageable they are staged and copied after the call's synchronisation.
+ * capacity counts records: a call that needs more - S cols, respectively (S / views) cols - returns EMSPEC_ERR_INVALID_ARG
+ * before anything is fed, and a push call with either setting on must fit max_columns like one with an output.  NULL clears a
+ * setting, always; with every overlay cleared the calls launch, allocate and write what they did before these entries.
+ * State: the envelope's rules - a non-NULL array is EMSPEC_ERR_STATE while either session has frames fed or a time reduction
+ * above 1 is set; emspec_reset_stream restarts that stream's level records with its columns.
+ * The cross: views in 1 .. 64, a and b in 0 .. views - 1 at set time (EMSPEC_ERR_INVALID_ARG).  A streaming call on a session
+ * whose stream count is not a multiple of `views` returns EMSPEC_ERR_INVALID_ARG before anything is fed; the session stays as
+ * it was.  The two streams of a pair must stay in step: WHILE A LIVE CROSS IS SET, emspec_reset_stream RETURNS
+ * EMSPEC_ERR_STATE and changes nothing (emspec_reset restarts all streams together) - the one place where a set overlay changes
+ * what another entry answers.  (A session whose streams emspec_reset_stream moved apart BEFORE the cross was set - possible
+ * only while no stream has a frame yet - refuses its streaming calls with EMSPEC_ERR_STATE until emspec_reset.)
+ *
+ * emspec_level_sum / emspec_cross_sum: pure, no engine - the field-wise sum (peak: maximum) of count >= 1 records, i.e. the law
+ * "the record at factor f is the sum of its f = 1 records" as a helper, so that a meter integrates 300 or 400 ms of per-hop
+ * records without restating the limb rules.  out may be one of the records.  A null pointer, count < 1, or a sum that a limb
+ * cannot hold returns EMSPEC_ERR_INVALID_ARG (emspec_last_error(NULL)) and leaves *out as it was.
+ */
+int emspec_set_live_level(emspec_engine* e, emspec_level* level_out, int64_t capacity /* records */);
+int emspec_set_live_cross(emspec_engine* e, int32_t views, int32_t a, int32_t b, emspec_cross* cross_out, int64_t capacity /* records */);
+int emspec_level_sum(const emspec_level* records, int64_t count, emspec_level* out);
+int emspec_cross_sum(const emspec_cross* records, int64_t count, emspec_cross* out);
 
 /*
  * ---- Live history: a ring on the device of the dB columns the streaming calls deliver, W per stream,

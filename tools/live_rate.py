@@ -4,8 +4,9 @@ S streams x one hop per call, N = 4096 / hop 256 (BASELINE configs[2] in its liv
 median / p90 microseconds per call and columns/s.  usage: live_rate.py [S] [calls] [filter,filter,...] [overlay,overlay,...]
 (filters: every token must appear in the variant's label, e.g. FAST,samples,pinned,out=db; an empty string: no filter)
 overlays: which overlay settings each variant runs with, in turn - none (the default), peaks (emspec_set_live_peaks, k = 8,
-min_db = -60), wave (emspec_set_live_wave), both, audio (emspec_set_live_audio, W = 2^19 samples per stream).  Their arrays are
-page-locked or pageable as the other buffers are.
+min_db = -60), wave (emspec_set_live_wave), both, audio (emspec_set_live_audio, W = 2^19 samples per stream), level
+(emspec_set_live_level), cross (emspec_set_live_cross, views = 2, a = 0, b = 1), meters (envelope + level + cross), all (meters +
+peaks).  Their arrays are page-locked or pageable as the other buffers are.
 EMSPEC_LIB=path times another build of the library (the parent commit's, which has no overlays: `none` only) in the same
 session, as tools/ab_kernel.py does; EMSPEC_MULTIRES=1 times the 16384 / 4096 multi-resolution session (split row 512) instead."""
 import os
@@ -51,7 +52,7 @@ def main():
                     label = f"{mname:5s} S={S:3d} {form:7s} {'pinned' if pinned else 'pageable':8s} out={'+'.join(outs):7s} "
                     if not all(tok in label + " " for tok in only if tok):
                         continue
-                    label += f"overlay={overlay:5s} " + ("multires " if multires else "")
+                    label += f"overlay={overlay:6s} " + ("multires " if multires else "")
                     with emspec.Engine(mode=mode) as e:
                         keep = []
                         def buf(shape, dt):
@@ -60,10 +61,14 @@ def main():
                                 keep.append(p)
                                 return p.array
                             return np.empty(shape, dt)
-                        if overlay in ("peaks", "both"):
+                        if overlay in ("peaks", "both", "all"):
                             e.set_live_peaks(8, -60.0, buf((S * 8 * 2,), np.float32))
-                        if overlay in ("wave", "both"):
+                        if overlay in ("wave", "both", "meters", "all"):
                             e.set_live_wave(buf((S * 2,), np.float32))
+                        if overlay in ("level", "meters", "all"):
+                            e.set_live_level(buf((S,), emspec.LEVEL_DTYPE))
+                        if overlay in ("cross", "meters", "all"):
+                            e.set_live_cross(2, 0, 1, buf((S // 2,), emspec.CROSS_DTYPE))
                         if overlay == "audio":
                             e.set_live_audio(1 << 19)
                         if form == "frames":
